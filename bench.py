@@ -5,6 +5,9 @@ wall-clock and bins/s).
 
     python bench.py --gpus 1 --steps 3 --warmup 1            # 16,000-bin map (BASELINE configs[2])
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --dump-outputs DIR                   # + the last timed step's outputs as DIR/<name>.npy
+
+The inputs are seeded: the same arguments give the same map, so two builds can be compared output for output.
 
 Rank 0 prints ONE JSON line (contract in the task prompt) with these extra objects:
   roofline       - the kernel family that took the most device time in the timed region: its ALGORITHMIC bytes per
@@ -74,6 +77,74 @@ def workload_label(n, part1_only, f32=False):
     else:
         cfg = "not a BASELINE.json size"
     return "%d-bin synthetic ICE-balanced map, %s (%s), contacts resident in HBM" % (n, what, cfg)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def output_arrays(job, part1_only):
+    """What the timed step handed its caller in its last run, as float64 tables: Part 1's filtered cut indices (its
+    return value) and the rows of the six files both parts wrote.  Scaffold names are their index in the synthetic
+    layout (-1 if unknown), orientations +1 / -1, '#' headers dropped; the group / chromosome number of a row is its
+    first column."""
+    import numpy as np
+    sid = {name: float(k) for k, name in enumerate(job.lay.scaffold_names)}
+
+    def rows(fname):
+        with open(job.f(fname)) as fh:
+            return [ln.rstrip("\n").split("\t") for ln in fh if ln.strip()]
+
+    def grouped(fname, convert, width):
+        out, group = [], 0
+        for r in rows(fname):
+            if r[0].startswith("#"):
+                group += r[0].startswith("### ")
+                continue
+            out.append([float(group)] + convert(r))
+        return np.asarray(out, dtype=np.float64).reshape(-1, width)
+
+    arrays = {"cut_indices": np.asarray(sorted(job.last.get("cuts", [])), dtype=np.float64)}
+    # dendrogramOrder.txt: "<scaffold>_<bin id>\t<leaf position>" -> [bin id, leaf position]
+    arrays["dendrogram_order"] = np.asarray([[float(r[0].rsplit("_", 1)[1]), float(r[1])] for r in rows("dendrogramOrder.txt")],
+                                            dtype=np.float64).reshape(-1, 2)
+    arrays["bin_groups"] = grouped("binGroups.txt",                      # [group, bin id, scaffold, start, stop, bias]
+                                   lambda r: [float(r[0]), sid.get(r[1], -1.0), float(r[2]), float(r[3]), float(r[4])], 6)
+    arrays["chromosome_groups"] = grouped("chromosomeGroups.txt",        # [group, bin id, scaffold]
+                                          lambda r: [float(r[0]), sid.get(r[1], -1.0)], 3)
+    scaff, totals = [], []
+    chrom = 0
+    for r in rows("assessment.txt"):
+        if r[0].startswith("### Chromosome"):
+            chrom += 1
+        elif r[0].startswith("#"):
+            continue
+        elif len(r) == 4:                                                # [chromosome, scaffold, assigned, total, assigned %]
+            scaff.append([float(chrom), sid.get(r[0], -1.0), float(r[1]), float(r[2]), float(r[3].rstrip("%"))])
+        else:                                    # summary lines ("Total scaffolds assigned to chromosome 8", ..., "Error rate ~0.0%")
+            totals.append(float(r[0].split()[-1].lstrip("~").rstrip("%")))
+    arrays["assessment"] = np.asarray(scaff, dtype=np.float64).reshape(-1, 5)
+    arrays["assessment_totals"] = np.asarray(totals, dtype=np.float64)
+    if not part1_only:
+        arrays["chromosome_orders"] = grouped("chromosomeOrders.txt",    # [group, scaffold, orientation]
+                                              lambda r: [sid.get(r[0], -1.0), 1.0 if r[1] == "+" else -1.0], 3)
+        arrays["plot_order"] = np.asarray([[sid.get(r[0], -1.0), float(r[1])] for r in rows("plotOrder.txt")[1:]],
+                                          dtype=np.float64).reshape(-1, 2)   # [scaffold, bin id]
+    return arrays
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_LIMIT_BYTES):
+    """DIR/<name>.npy for every array; above `limit` bytes in all, every 2-D table keeps the same fixed, seeded share of
+    its rows (in their original order)."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        keep = limit / total * 0.95
+        rng = np.random.default_rng(12345)
+        arrays = {k: a[np.sort(rng.choice(len(a), max(1, int(len(a) * keep)), replace=False))] if a.ndim == 2 and len(a) else a
+                  for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a, allow_pickle=False)
 
 
 def cpu_baseline(sample_bins, n_scaffolds, scan_scaffolds, work):
@@ -416,7 +487,11 @@ def main():
                     help="gloo: rehearse the multi-rank flow with several ranks on one GPU")
     ap.add_argument("--kernel-times", choices=["part1", "all"], default="part1",
                     help="which kernel families get HIP-event timing inside the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if os.environ.get("HICMI_SWITCH_INTERVAL"):
         sys.setswitchinterval(float(os.environ["HICMI_SWITCH_INTERVAL"]))
 
@@ -450,10 +525,12 @@ def main():
     # HIP events around the families that decide the roofline line (nn-chain, row sort, ...).  --kernel-times all
     # also brackets the hundreds of small launches of the scans and of Part 2, which costs about 10 ms per map.
     elapsed, timing, stats = timed_run(job, args.steps, args.warmup, timing_mode, dist.barrier, reduce_dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(output_arrays(job, args.part1_only), args.dump_outputs)
 
     out = None
     if rank == 0:
-        steps = max(args.steps, 1)
+        steps = args.steps
         ms_per_step = elapsed / steps * 1e3
         value = (1 if one_map else world) * n / (ms_per_step / 1e3)
         workers = max(1, min(p2.WORKERS, 8))
