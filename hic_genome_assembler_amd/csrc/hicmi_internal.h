@@ -77,7 +77,10 @@ __device__ __forceinline__ double serial_prefix_lds(double* t, int from, int to,
 }
 
 // ---- NumPy's pairwise summation tree (add.reduce of one contiguous or strided run of <= 8192 elements) -----------
-static constexpr int MAX_LEAVES = 64;                  // an 8192-element chunk splits into <= 64 leaves
+// An 8192-element chunk splits into 64 leaves, but a shorter one can split into 65: the left half is rounded down to a
+// multiple of 8, so the right halves of 7,689 ... 8,191-element runs reach 129+ elements one level earlier
+// (tests/test_host_cpu.py walks the recursion for every length up to 8192).
+static constexpr int MAX_LEAVES = 65;
 
 // Leaves of NumPy's pairwise recursion over [off, off+len), in order, with their depth in the
 // recursion tree.  The explicit stack lives in LDS (st_off/st_len/st_dep: 16 entries each): private

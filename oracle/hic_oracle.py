@@ -560,26 +560,110 @@ class Scaffold:
         self.binList = self.binList[::-1]
 
 
-class Part2Oracle:
-    """Literal OG:256-586 with the objective evaluated by oracle_c.c (numpy.trace semantics)."""
+def pool_size():
+    """Threads for batched literal costs: at most 16, never more than OMP_NUM_THREADS says, never sized from
+    os.cpu_count() alone (on a shared host that is the whole machine's count)."""
+    try:
+        omp = int(os.environ.get("OMP_NUM_THREADS") or 16)
+    except ValueError:
+        omp = 16
+    return max(1, min(16, omp, os.cpu_count() or 1))
 
-    def __init__(self, matrix, bins):
+
+_POOL = {}
+
+
+def _pool(threads):
+    if threads not in _POOL:
+        from concurrent.futures import ThreadPoolExecutor
+        _POOL[threads] = ThreadPoolExecutor(max_workers=threads, thread_name_prefix="hio_cost")
+    return _POOL[threads]
+
+
+def cost_literal_rows(mat, rows, total, threads=None):
+    """hio_cost_literal of every row of ``rows`` (n_cand x n indices into the square matrix ``mat``) under ``total``:
+    hio_cost_literal_batch on chunks of rows, on a thread pool (ctypes drops the GIL for the call).  Each value is
+    the same function of the same inputs as one hio_cost_literal call, so chunking cannot change a bit."""
+    mat = np.ascontiguousarray(mat, dtype=np.float64)
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    n_cand, n = rows.shape
+    out = np.empty(n_cand, np.float64)
+    if n_cand == 0:
+        return out
+    threads = pool_size() if threads is None else max(1, int(threads))
+    L = lib()
+
+    def run(a, b):
+        L.hio_cost_literal_batch(_dp(mat), mat.shape[1], _ip(rows[a:b]), b - a, n, total, _dp(out[a:b]))
+    if threads == 1 or n_cand == 1 or n_cand * n * n < (1 << 21):
+        run(0, n_cand)
+        return out
+    step = max(1, -(-n_cand // (4 * threads)))
+    for f in [_pool(threads).submit(run, a, min(a + step, n_cand)) for a in range(0, n_cand, step)]:
+        f.result()
+    return out
+
+
+class Part2Oracle:
+    """Literal OG:256-586 with the objective evaluated by oracle_c.c (numpy.trace semantics).
+
+    Every decision step (one brute force, one insertion, one window of the scan) first spells out all of its
+    candidates' index rows - they depend on the arrangement at the start of the step, not on each other's scores -
+    then scores them, then takes the reference's `cost > best` decisions in enumeration order.  batch=True scores a
+    step's rows with hio_cost_literal_batch on a contiguous copy of the chromosome's sub-matrix, in chunks on a thread
+    pool of ``threads`` (default pool_size()); batch=False makes one hio_cost_literal call per cost on the full matrix.
+    Both read the same matrix entries in the same order: the costs are identical, and ``costs`` keeps the reference's
+    call order either way."""
+
+    _BLOCK = 8192                 # brute-force candidates spelled out at a time (k = 8 has 5,160,960)
+
+    def __init__(self, matrix, bins, batch=True, threads=None):
         self.matrix = np.ascontiguousarray(matrix, dtype=np.float64)
         self.bin_index = {b.ID: i for i, b in enumerate(bins)}
         self.costs = []           # every evaluation, in the reference's call order
+        self.batch, self.threads = batch, threads
+        self._mat, self._index, self._rows = self.matrix, self.bin_index, {}
 
     # --- objective -------------------------------------------------------------------------
+    def _use_group(self, group):
+        """batch=True: the objective reads a contiguous copy of the group's rows and columns from here on."""
+        self._rows = {}
+        if not self.batch:
+            return
+        ids = sorted({bid for bid, _s in group})
+        g = np.array([self.bin_index[b] for b in ids], dtype=np.int64)
+        self._mat = np.ascontiguousarray(self.matrix[np.ix_(g, g)])
+        self._index = {b: i for i, b in enumerate(ids)}
+
+    def _scaf_row(self, s):
+        """Indices of a scaffold's bins in its current orientation.  binList is sorted for '+' and reversed for '-'
+        (initiate sorts, flipOrientation reverses), so (name, orientation) determines it."""
+        key = (s.name, s.orientation)
+        r = self._rows.get(key)
+        if r is None:
+            r = self._rows[key] = np.array([self._index[n] for n in s.binList], dtype=np.int32)
+        return r
+
     def _global(self, scaff_list):
-        return np.array([self.bin_index[n] for s in scaff_list for n in s.binList], dtype=np.int32)
+        return np.concatenate([self._scaf_row(s) for s in scaff_list]) if scaff_list else np.zeros(0, np.int32)
 
     def total(self, gidx):
-        return lib().hio_total_upper(_dp(self.matrix), self.matrix.shape[1], _ip(gidx), len(gidx))
+        gidx = np.ascontiguousarray(gidx, dtype=np.int32)
+        return lib().hio_total_upper(_dp(self._mat), self._mat.shape[1], _ip(gidx), len(gidx))
 
     def cost(self, gidx, total):
         gidx = np.ascontiguousarray(gidx, dtype=np.int32)
-        c = lib().hio_cost_literal(_dp(self.matrix), self.matrix.shape[1], _ip(gidx), len(gidx), total)
+        c = lib().hio_cost_literal(_dp(self._mat), self._mat.shape[1], _ip(gidx), len(gidx), total)
         self.costs.append(c)
         return c
+
+    def score_rows(self, rows, total):
+        """Literal costs of a step's candidate rows, recorded in enumeration order."""
+        if not self.batch:
+            return [self.cost(r, total) for r in rows]
+        out = cost_literal_rows(self._mat, np.stack(rows), total, self.threads).tolist()
+        self.costs.extend(out)
+        return out
 
     # --- OG:256-280 ------------------------------------------------------------------------
     @staticmethod
@@ -611,28 +695,33 @@ class Part2Oracle:
         if total == 0:
             return orders[0], orients[0], 0.0
         best, best_order, best_orient = 0., "NA", "NA"
-        for o in orders:
-            for r in orients:
-                lst = self.reorder(o, r, d)
-                c = self.cost(self._global(lst), total)
+        cands = [(o, r) for o in orders for r in orients]
+        for b0 in range(0, len(cands), self._BLOCK):
+            block = cands[b0:b0 + self._BLOCK]
+            rows = [self._global(self.reorder(o, r, d)) for o, r in block]
+            for (o, r), c in zip(block, self.score_rows(rows, total)):
                 if c > best:
                     best, best_order, best_orient = c, o, r
         return best_order, best_orient, best
 
     # --- OG:332-372 ------------------------------------------------------------------------
     def check_all_scores(self, ordered, scaff):
-        best, best_i, best_o = 0., 0, "+"
         total = self.total(self._global(ordered + [scaff]))     # adjMat was built with the new scaffold last (OG:484-486)
+        # OG:345-362 insert the scaffold at i, score, flip it in place, score, take it out: it enters position i + 1
+        # in the orientation it left position i with
+        rows, cands = [], []
         for i in range(len(ordered) + 1):
             ordered.insert(i, scaff)
-            c = self.cost(self._global(ordered), total)
+            rows.append(self._global(ordered))
+            cands.append((i, scaff.orientation))
+            scaff.flipOrientation()
+            rows.append(self._global(ordered))
+            cands.append((i, scaff.orientation))
+            ordered.pop(i)
+        best, best_i, best_o = 0., 0, "+"
+        for (i, o), c in zip(cands, self.score_rows(rows, total)):
             if c > best:
-                best, best_i, best_o = c, i, ordered[i].orientation
-            ordered[i].flipOrientation()
-            c = self.cost(self._global(ordered), total)
-            if c > best:
-                best, best_i, best_o = c, i, ordered[i].orientation
-            scaff = ordered.pop(i)
+                best, best_i, best_o = c, i, o
         if scaff.orientation != best_o:
             scaff.flipOrientation()
         ordered.insert(best_i, scaff)
@@ -649,17 +738,19 @@ class Part2Oracle:
                 names = [s.name for s in ordered[i:i + scan]]
                 orders = remove_reverse_duplicates(swap_permutations(names))
                 orients = plus_minus_perms(len(names))
+                # OG:519-541: the scaffolds outside the window keep their place and orientation in every candidate
+                beg, end = ordered[0:i], ordered[i + scan:]
+                head, tail = self._global(beg), self._global(end)
+                rows, cands = [], []
                 for o in orders:
                     for r in orients:
-                        beg = [s.name for s in ordered[0:i]]
-                        win = self.reorder(o, r, d)
-                        end = [s.name for s in ordered[i + scan:]]
-                        new_order = beg + [s.name for s in win] + end
-                        lst = [d[nm] for nm in new_order]
-                        new_orient = [s.orientation for s in lst]
-                        c = self.cost(self._global(lst), total)
-                        if c > best_cost:
-                            best_order, best_orient, best_cost, stop = new_order, new_orient, c, 1
+                        rows.append(np.concatenate([head, self._global(self.reorder(o, r, d)), tail]))
+                        cands.append((o, r))
+                for (o, r), c in zip(cands, self.score_rows(rows, total)):
+                    if c > best_cost:
+                        best_order = [s.name for s in beg] + list(o) + [s.name for s in end]
+                        best_orient = [s.orientation for s in beg] + list(r) + [s.orientation for s in end]
+                        best_cost, stop = c, 1
                 ordered = self.reorder(best_order, best_orient, d)
             if stop == 0:
                 break
@@ -671,6 +762,7 @@ class Part2Oracle:
             n_scaffolds = 8
         if scan_scaffolds > n_scaffolds:
             scan_scaffolds = n_scaffolds
+        self._use_group(group)
         rest, d = self.initiate(group)
         ordered = rest[:n_scaffolds]
         rest = rest[n_scaffolds:]
@@ -738,9 +830,10 @@ def write_bin_id_ordering(scaffolds, path):
 
 
 def run_part2(bed, bias, matrix, chrom_group_file, chrom_order_file, plot_order_file,
-              n_scaffolds=6, scan_scaffolds=5, trace=None, preloaded=None):
+              n_scaffolds=6, scan_scaffolds=5, trace=None, preloaded=None, batch=False):
     """OG:679-712 (plots omitted).  ``preloaded=(matrix, bins)`` skips the text loaders; bins that
-    are not in the group file are never selected, as in the reference's restricted re-load."""
+    are not in the group file are never selected, as in the reference's restricted re-load.  ``batch``: see
+    Part2Oracle; the default (one call per cost, one thread) is what bench.py's cpu_baseline leg times."""
     ids = read_groupings_to_valid_bins(chrom_group_file)
     if preloaded is not None:
         mat, bins = np.ascontiguousarray(preloaded[0], dtype=np.float64), list(preloaded[1])
@@ -748,7 +841,7 @@ def run_part2(bed, bias, matrix, chrom_group_file, chrom_order_file, plot_order_
         bins = initiate_loci(bed, bias, bin_ids=ids)
         mat = build_adjacency(matrix, bins)
     chroms = read_chroms(chrom_group_file)
-    orc = Part2Oracle(mat, bins)
+    orc = Part2Oracle(mat, bins, batch=batch)
     out, marks, bests = [], [], []
     for group in chroms:
         marks.append(len(orc.costs))

@@ -31,6 +31,10 @@ P2_CASES = [
     ("two-scaffold-windows", 180, 2, 6.0, None, 3, 2),
     ("six-scaffold-scan-windows", 150, 1, 9.0, None, 6, 6),
     ("seven-scaffold-brute-force", 120, 1, 12.0, (0.2, 2), 7, 4),
+    # the bench map's scaffold statistics (mean 13 bins) on chromosomes of 350 ... 550 bins and 25 ... 45 scaffolds,
+    # default windows; quantised: exact ties between the literal scores of different bin orders, and orientation ties
+    ("bench-scaffolds-1800", 1800, 4, 13.0, None, 6, 5),
+    ("bench-scaffolds-1800-quantised", 1800, 4, 13.0, (0.3, 2), 6, 5),
 ]
 
 
@@ -67,7 +71,7 @@ def test_pipeline_matches_oracle(case, tmp_path):
                           f("chromosomeGroups.txt"), min_size=5, modularity=0.0, psig=psig)
             orc.run_part2(paths["hicProBedFile"], paths["hicProBiasFile"], paths["hicProMatrixFile"],
                           f("chromosomeGroups.txt"), f("chromosomeOrders.txt"), f("plotOrder.txt"),
-                          n_scaffolds=n_scaffolds, scan_scaffolds=scan_scaffolds)
+                          n_scaffolds=n_scaffolds, scan_scaffolds=scan_scaffolds, batch=True)
         else:
             p1.runPipeline(paths["hicProBedFile"], paths["hicProBiasFile"], paths["hicProMatrixFile"],
                            paths["hicProScaffSizeFile"], f("dendrogramOrder.txt"), False, False, f("binGroups.txt"),
@@ -104,7 +108,8 @@ def test_part2_matches_oracle_on_planted_groups(case, tmp_path):
         f = lambda k: str(out / k)  # noqa: E731
         if who == "oracle":
             orc.run_part2(paths["hicProBedFile"], paths["hicProBiasFile"], paths["hicProMatrixFile"], str(groups),
-                          f("chromosomeOrders.txt"), f("plotOrder.txt"), n_scaffolds=n_scaffolds, scan_scaffolds=scan_scaffolds)
+                          f("chromosomeOrders.txt"), f("plotOrder.txt"), n_scaffolds=n_scaffolds, scan_scaffolds=scan_scaffolds,
+                          batch=True)
         else:
             p2.runPipeline(paths["hicProBedFile"], paths["hicProBiasFile"], paths["hicProMatrixFile"], str(groups),
                            f("chromosomeOrders.txt"), False, False, False, "t", f("plotOrder.txt"), n_scaffolds,

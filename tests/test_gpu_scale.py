@@ -2,7 +2,8 @@
 
 * 16,000 bins: Part 1 of the very step bench.py times against the CPU oracle - four files byte for byte
   (configs[1]/[2]; the oracle's SciPy linkage + NumPy argsort + hypergeometric scans take a minute or two); Part 2 of
-  configs[2] through fixed-point properties and file equality with the earlier implementations.
+  configs[2] against the oracle on a fixed choice of its chromosome groups (all of them with
+  HICMI_TEST_P2_ORACLE_ALL=1), and through fixed-point properties and file equality with the earlier implementations.
 * 32,000 bins: the UPGMA tree, leaf order, sampled rank rows and first-scan counts against the CPU oracle
   (north_star's Target size).
 * 32,000 bins (configs[3]'s map, north_star's single-GPU target) and 64,000 bins with fp32 contacts
@@ -109,7 +110,7 @@ def test_part2_at_16000_bins(tmp_path):
     from hic_genome_assembler_amd.hostio import Bin
     n, seed = 16000, 1
     lay = synth.make_layout(n, seed=seed)
-    ct = synth.dense_contacts_torch(lay, torch.device("cuda", 0), seed=seed, sinkhorn_iters=8)      # = _resident_map(n, 1, False)
+    ct = synth.dense_contacts_torch(lay, torch.device("cuda", 0), seed=seed, sinkhorn_iters=12)     # = _resident_map(n, 1, False)
     torch.cuda.synchronize()
     out = tmp_path / "default"
     out.mkdir()
@@ -140,6 +141,66 @@ def test_part2_at_16000_bins(tmp_path):
     assert res.returncode == 0, res.stderr[-3000:]
     for k in FILES:
         assert open(alt / k).read() == texts[k], k
+
+
+def _group_blocks(text, header):
+    """Lines of each '### <header> k ###' block of a Part 1 / Part 2 output file, in file order."""
+    blocks = []
+    for line in text.splitlines():
+        if line.startswith("### " + header + " "):
+            blocks.append([])
+        elif line:
+            blocks[-1].append(line)
+    return blocks
+
+
+def test_part2_matches_oracle_at_16000_bins(tmp_path):
+    """Part 2 of bench.py's step on its 16,000-bin map (resident Part 1, then resident Part 2 with 6 / 5 windows and
+    lock-step insertion over all of the map's chromosomes) against the CPU oracle, chromosome group by chromosome
+    group: the scaffold names and orientations of each group's block of chromosomeOrders.txt, and its lines of
+    plotOrder.txt.  A fixed rule picks the groups the oracle can order in test time: every group of at most 600 bins,
+    and the smallest group of at least 1,000 bins.  HICMI_TEST_P2_ORACLE_ALL=1 checks every group (about ten minutes
+    with 16 oracle threads)."""
+    import time
+    import torch
+    import hic_oracle as orc
+    from hic_genome_assembler_amd import _lib, orderGenome as p2, scaffoldToChromosomes as p1, synth
+    from hic_genome_assembler_amd.hostio import Bin
+    n = 16000
+    lay = synth.make_layout(n, seed=1)
+    ct = synth.dense_contacts_torch(lay, torch.device("cuda", 0), seed=1, sinkhorn_iters=12)        # bench.py's map
+    torch.cuda.synchronize()
+    sizes = _sizes_file(lay, tmp_path / "sizes.txt")
+    f = lambda k: str(tmp_path / k)  # noqa: E731
+    with _lib.Context(0) as ctx, contextlib.redirect_stdout(io.StringIO()):
+        ctx.set_contacts_device(ct.data_ptr(), n, keepalive=ct)
+        dm = p1.DeviceMatrix(ctx)
+        p1.runResident(dm, _bins(lay, Bin), sizes, *[f(k) for k in FILES[:4]], 5, 0.0, .05)
+        p2.runResident(p2.GenomeMatrix(ctx), dm.kept_bins, f(FILES[3]), f(FILES[4]), f(FILES[5]), 6, 5, lay.resolution)
+    c = ct.cpu().numpy()
+    del ct
+    torch.cuda.empty_cache()
+    groups = orc.read_chroms(f(FILES[3]))
+    orders = _group_blocks(open(f(FILES[4])).read(), "Chromosome grouping")
+    plotted = open(f(FILES[5])).read().split("\n")[1:]
+    assert len(orders) == len(groups) and len(plotted) == sum(len(g) for g in groups)
+    first_line = np.concatenate(([0], np.cumsum([len(g) for g in groups])))
+    n_scaf = [len({s for _b, s in g}) for g in groups]
+    if os.environ.get("HICMI_TEST_P2_ORACLE_ALL") == "1":
+        chosen = list(range(len(groups)))
+    else:
+        big = min((g for g in range(len(groups)) if len(groups[g]) >= 1000), key=lambda g: (len(groups[g]), g))
+        chosen = [g for g in range(len(groups)) if len(groups[g]) <= 600] + [big]
+    assert any(len(groups[g]) >= 1000 and n_scaf[g] >= 60 for g in chosen)
+    oracle = orc.Part2Oracle(c, _bins(lay, orc.Bin))
+    for g in sorted(chosen, key=lambda g: len(groups[g])):
+        t0, c0 = time.time(), len(oracle.costs)
+        ordered, _best = oracle.order_chromosome(groups[g], 6, 5)
+        print("group %d: %d bins, %d scaffolds, %d literal costs, oracle %.1f s"
+              % (g + 1, len(groups[g]), n_scaf[g], len(oracle.costs) - c0, time.time() - t0))
+        assert orders[g] == [s.name + "\t" + s.orientation for s in ordered], g + 1
+        assert plotted[first_line[g]:first_line[g + 1]] == [s.name + "\t" + str(b) for s in ordered for b in s.binList], g + 1
+    print("%d of %d chromosome groups equal to the oracle's" % (len(chosen), len(groups)))
 
 
 def _oracle_distance_blocked(orc, c, block=2048):
@@ -206,7 +267,7 @@ def _resident_map(n, seed, f32):
     from hic_genome_assembler_amd import synth
     lay = synth.make_layout(n, seed=seed)
     dev = torch.device("cuda", 0)
-    c = synth.dense_contacts_torch(lay, dev, seed=seed, sinkhorn_iters=8)
+    c = synth.dense_contacts_torch(lay, dev, seed=seed, sinkhorn_iters=12)                # bench.py's maps
     torch.cuda.synchronize()
     if not f32:
         return lay, c

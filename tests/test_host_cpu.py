@@ -340,3 +340,21 @@ def test_read_chroms_line_handling(tmp_path):
             fh.write(text)
         with contextlib.redirect_stdout(io.StringIO()):
             assert og.readChromsFromFile(str(path)) == literal(str(path)), text
+
+
+def test_pairwise_leaf_tables_hold_every_chunk():
+    """The kernels' NumPy pairwise sums (k_part1.hip row sums, k_part2.hip diagonal sums) list the leaves of one chunk of
+    at most 8,192 elements in LDS arrays of MAX_LEAVES entries, and walk the recursion with 16-entry stacks.  Every chunk
+    length must fit: the most leaves (65) come from runs of 7,689 ... 8,191 elements, not from 8,192 (64)."""
+    with open(os.path.join(ROOT, "hic_genome_assembler_amd", "csrc", "hicmi_internal.h")) as fh:
+        max_leaves = int(re.search(r"constexpr int MAX_LEAVES = (\d+);", fh.read()).group(1))
+    leaves, depth = [0] * 8193, [0] * 8193
+    for n in range(1, 8193):                       # oracle_c.c pairwise(): halves with the left one a multiple of 8
+        if n <= 128:
+            leaves[n], depth[n] = 1, 0
+        else:
+            n2 = n // 2 - (n // 2) % 8
+            leaves[n], depth[n] = leaves[n2] + leaves[n - n2], 1 + max(depth[n2], depth[n - n2])
+    assert max(leaves) == 65 and leaves[8192] == 64 and leaves[7689] == 65
+    assert max(leaves) <= max_leaves
+    assert max(depth) + 1 <= 16

@@ -177,3 +177,49 @@ def test_numba_trace_order_differs_in_the_last_bits_only():
     assert np.max(np.abs(a - b) / np.abs(a)) < 2e-15
     for fn in gc.OUTPUT_FILES:
         assert gc.golden_text("n160", fn) == gc.golden_text("n160_numba", fn)
+
+
+@pytest.mark.parametrize("name", ALL_CASES)
+def test_batched_part2_oracle_equals_one_call_per_cost(name, tmp_path):
+    """Part2Oracle scores each decision step's candidates in batches on a thread pool, on a copy of the chromosome's
+    sub-matrix (batch=True), or one hio_cost_literal call per cost on the full matrix (batch=False): the same cost
+    trace bit for bit, in the same order, and the same two files."""
+    spec = gc.load_case(name)[0]
+    paths = gc.write_case_files(name, str(tmp_path))
+    orc.set_trace_order("numba" if spec.get("numba_trace") else "numpy")
+    f = lambda who, k: str(tmp_path / (who + "_" + k))  # noqa: E731
+    orc.run_part1(paths["hicProBedFile"], paths["hicProBiasFile"], paths["hicProMatrixFile"], paths["hicProScaffSizeFile"],
+                  f("p1", "dendrogramOrder.txt"), f("p1", "binGroups.txt"), f("p1", "assessment.txt"),
+                  f("p1", "chromosomeGroups.txt"), min_size=spec["min_size"], modularity=0.0, psig=spec["psig"])
+    traces = {}
+    try:
+        for who, batch in (("single", False), ("batched", True)):
+            traces[who] = {}
+            orc.run_part2(paths["hicProBedFile"], paths["hicProBiasFile"], paths["hicProMatrixFile"],
+                          f("p1", "chromosomeGroups.txt"), f(who, "chromosomeOrders.txt"), f(who, "plotOrder.txt"),
+                          n_scaffolds=spec["n_scaffolds"], scan_scaffolds=spec["scan_scaffolds"], trace=traces[who],
+                          batch=batch)
+    finally:
+        orc.set_trace_order("numpy")
+    a, b = traces["single"], traces["batched"]
+    assert len(a["costs"]) == len(b["costs"]) > 0
+    assert np.array_equal(a["costs"], b["costs"])
+    assert np.array_equal(a["cost_marks"], b["cost_marks"])
+    assert a["chrom_orders"] == b["chrom_orders"]
+    for fn in ("chromosomeOrders.txt", "plotOrder.txt"):
+        assert open(f("single", fn)).read() == open(f("batched", fn)).read() == gc.golden_text(name, fn), fn
+
+
+def test_batched_literal_costs_on_the_thread_pool():
+    """cost_literal_rows (chunks of hio_cost_literal_batch on the pool) against one hio_cost_literal call per row,
+    for one thread and for several, with fewer rows than threads and with many."""
+    rng = np.random.default_rng(21)
+    n = 300
+    m = rng.random((n, n)); m = m + m.T
+    L = orc.lib()
+    for n_cand in (1, 3, 50):
+        rows = np.stack([rng.permutation(n) for _ in range(n_cand)]).astype(np.int32)
+        want = [L.hio_cost_literal(orc._dp(m), n, orc._ip(rows[k]), n, 123.5) for k in range(n_cand)]
+        for threads in (1, 4, None):
+            assert orc.cost_literal_rows(m, rows, 123.5, threads).tolist() == want
+    assert 1 <= orc.pool_size() <= 16
