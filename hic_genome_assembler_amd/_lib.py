@@ -80,6 +80,15 @@ SIGNATURES = {
                                           ctypes.POINTER(ctypes.c_int32)]),
     "hicmi_p2_scan_all": (ctypes.c_int, [_vp, _vp, _vp, c_i64, c_i64, c_dbl, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl),
                           ctypes.POINTER(c_i64)]),
+    "hicmi_hmm_load_obs": (ctypes.c_int, [_vp, _vp, c_i64, c_i64, c_i64]),
+    "hicmi_hmm_set_obs": (ctypes.c_int, [_vp, _vp, c_i64, c_i64]),
+    "hicmi_hmm_set_width": (ctypes.c_int, [_vp, c_i64]),
+    "hicmi_hmm_get_obs": (ctypes.c_int, [_vp, c_i64, c_i64, _vp]),
+    "hicmi_hmm_dist2": (ctypes.c_int, [_vp, _vp, c_i64, _vp]),
+    "hicmi_hmm_col_stats": (ctypes.c_int, [_vp, _vp, _vp]),
+    "hicmi_hmm_kmeans": (ctypes.c_int, [_vp, _vp, c_i64, c_dbl, _vp, _vp, ctypes.POINTER(c_dbl), ctypes.POINTER(c_i64)]),
+    "hicmi_hmm_fit": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, c_i64, c_dbl, _vp, ctypes.POINTER(c_i64)]),
+    "hicmi_hmm_decode": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "hicmi_timing_reset": (ctypes.c_int, [_vp]),
     "hicmi_timing_enable": (ctypes.c_int, [_vp, ctypes.c_int]),
     "hicmi_timing_get": (ctypes.c_int, [_vp, ctypes.c_char_p, c_i64, _vp, _vp, _vp, c_i64, ctypes.POINTER(c_i64)]),
@@ -519,6 +528,80 @@ class Context:
             n_sel, optr = len(keep), _ptr(keep)
         out = np.empty((int(px), int(px)), np.float64)
         _check(self._lib.hicmi_plot_downsample(self._h, int(kind), optr, n_sel, int(px), _ptr(out)))
+        return out
+
+    # ---- HMM boundary finder (hmm = True, S2C:730-942)
+    def hmm_load_obs(self, order, c, p):
+        """X = log10(similarity + 1) of rows [c, n) and columns [c, p) in ``order``, kept on the device.
+        Returns (T, D)."""
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        _check(self._lib.hicmi_hmm_load_obs(self._h, _ptr(order), len(order), int(c), int(p)))
+        self._hmm_shape = [len(order) - int(c), int(p) - int(c), int(p) - int(c)]      # T, built width, view width
+        return self._hmm_shape[0], self._hmm_shape[1]
+
+    def hmm_set_obs(self, X):
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim != 2:
+            raise ValueError("X must be 2-D")
+        _check(self._lib.hicmi_hmm_set_obs(self._h, _ptr(X), X.shape[0], X.shape[1]))
+        self._hmm_shape = [X.shape[0], X.shape[1], X.shape[1]]
+
+    def hmm_set_width(self, D):
+        """Use columns [0, D) of the X already on the device."""
+        _check(self._lib.hicmi_hmm_set_width(self._h, int(D)))
+        self._hmm_shape[2] = int(D)
+
+    def hmm_get_obs(self, row0=0, nrows=None):
+        T, _ld, D = self._hmm_shape
+        nrows = T - row0 if nrows is None else nrows
+        out = np.empty((nrows, D), np.float64)
+        _check(self._lib.hicmi_hmm_get_obs(self._h, int(row0), int(nrows), _ptr(out)))
+        return out
+
+    def hmm_dist2(self, rows):
+        """Squared distances of every row of X to the rows ``rows`` (1 or 2 of them): len(rows) x T."""
+        r = np.ascontiguousarray(rows, dtype=np.int64)
+        out = np.empty((len(r), self._hmm_shape[0]), np.float64)
+        _check(self._lib.hicmi_hmm_dist2(self._h, _ptr(r), len(r), _ptr(out)))
+        return out
+
+    def hmm_col_stats(self):
+        """(mean, sum of squared deviations) of every column of X."""
+        D = self._hmm_shape[2]
+        mean, m2 = np.empty(D, np.float64), np.empty(D, np.float64)
+        _check(self._lib.hicmi_hmm_col_stats(self._h, _ptr(mean), _ptr(m2)))
+        return mean, m2
+
+    def hmm_kmeans(self, centers, max_iter=300, tol=0.0, want_labels=True):
+        """Lloyd from ``centers`` (2 x D): (centers, labels or None, inertia, iterations)."""
+        cin = np.ascontiguousarray(centers, dtype=np.float64)
+        cout = np.empty_like(cin)
+        labels = np.empty(self._hmm_shape[0], np.int32) if want_labels else None
+        inertia, n_iter = c_dbl(), c_i64()
+        _check(self._lib.hicmi_hmm_kmeans(self._h, _ptr(cin), int(max_iter), float(tol), _ptr(cout), _ptr(labels),
+                                          ctypes.byref(inertia), ctypes.byref(n_iter)))
+        return cout, labels, inertia.value, int(n_iter.value)
+
+    def hmm_fit(self, startprob, means, covars, transmat, n_iter=1000, tol=1e-2):
+        """Baum-Welch: (means, covars, transmat, logprob of every iteration)."""
+        sp = np.ascontiguousarray(startprob, dtype=np.float64)
+        mu = np.array(means, dtype=np.float64, order="C")
+        cv = np.array(covars, dtype=np.float64, order="C")
+        tm = np.array(transmat, dtype=np.float64, order="C")
+        hist = np.empty(int(n_iter), np.float64)
+        done = c_i64()
+        _check(self._lib.hicmi_hmm_fit(self._h, _ptr(sp), _ptr(mu), _ptr(cv), _ptr(tm), int(n_iter), float(tol),
+                                       _ptr(hist), ctypes.byref(done)))
+        return mu, cv, tm, hist[:done.value].copy()
+
+    def hmm_decode(self, startprob, means, covars, transmat):
+        """Viterbi states (T int32)."""
+        sp = np.ascontiguousarray(startprob, dtype=np.float64)
+        mu = np.ascontiguousarray(means, dtype=np.float64)
+        cv = np.ascontiguousarray(covars, dtype=np.float64)
+        tm = np.ascontiguousarray(transmat, dtype=np.float64)
+        out = np.empty(self._hmm_shape[0], np.int32)
+        _check(self._lib.hicmi_hmm_decode(self._h, _ptr(sp), _ptr(mu), _ptr(cv), _ptr(tm), _ptr(out)))
         return out
 
     # ---- misc

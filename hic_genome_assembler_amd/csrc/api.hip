@@ -126,6 +126,16 @@ struct hicmi_ctx {
     double* d_ins_partial = nullptr; int64_t ins_partial_cap = 0;
     unsigned char* d_ins_blob = nullptr; int64_t ins_blob_cap = 0;   // per job: [InsState][InsLog x steps]
     InsStep* d_ins_steps = nullptr; int64_t ins_steps_cap = 0;       // [step][job] records of a lock-step queue
+    // HMM boundary finder (k_hmm.hip): observations T x hmm_ld (columns [0, hmm_D) in use), work areas sized per X
+    double* d_hx = nullptr; int64_t hx_cap = 0; int64_t hmm_T = 0, hmm_ld = 0, hmm_D = 0;
+    int32_t* d_horder = nullptr; int64_t horder_cap = 0;
+    double* d_hwork = nullptr; int64_t hwork_cap = 0;      // L, alpha, beta, gamma (T x 2 each), mind / dist (2T)
+    int32_t* d_hlab = nullptr; int64_t hlab_cap = 0;       // labels (two generations), states: 3T
+    uint8_t* d_hbt = nullptr; int64_t hbt_cap = 0;         // Viterbi back-pointer maps
+    double* d_hpart = nullptr; int64_t hpart_cap = 0;      // column-pass partials
+    double* d_hsmall = nullptr; int64_t hsmall_cap = 0;    // params (12 D + scalars), sums (4 D), centers (2 D), scalars
+    double* d_hhist = nullptr; int64_t hhist_cap = 0;      // logprob of every EM iteration
+    int* d_hst = nullptr; int64_t hst_cap = 0;             // k-means counters
     // plot support
     int32_t* d_plot_order = nullptr; int64_t plot_order_cap = 0;
     unsigned char* d_plot_work = nullptr; int64_t plot_work_cap = 0;
@@ -340,6 +350,8 @@ int hicmi_destroy(hicmi_ctx* c)
     free_dev(c->d_arr_packed2); free_dev(c->d_pos2sel2); free_dev(c->d_ins_T); free_dev(c->d_ins_partial);
     free_dev(c->d_ins_blob); free_dev(c->d_ins_steps);
     free_dev(c->d_plot_order); free_dev(c->d_plot_work); free_dev(c->d_plot_img);
+    free_dev(c->d_hx); free_dev(c->d_horder); free_dev(c->d_hwork); free_dev(c->d_hlab); free_dev(c->d_hbt);
+    free_dev(c->d_hpart); free_dev(c->d_hsmall); free_dev(c->d_hhist); free_dev(c->d_hst);
     if (c->pin_up) (void)hipHostFree(c->pin_up);
     if (c->pin_down) (void)hipHostFree(c->pin_down);
     for (auto& r : c->regions) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -2195,6 +2207,272 @@ int hicmi_plot_downsample(hicmi_ctx* c, int kind, const int32_t* order, int64_t 
     }
     HIPCHK(hipGetLastError());
     return download(c, out, c->d_plot_img, sizeof(double) * (size_t)(px * px));
+}
+
+
+// ---------------------------------------------------------------------------------------------------
+// HMM boundary finder (S2C:730-942, hmm = True): hmmlearn GaussianHMM(n_components=2, covariance_type="diag") restated
+// on the device, k_hmm.hip.
+namespace {
+
+// the small buffer: params | sums (4 D) | centers (2 D) | scalar slots (16)
+inline double* hmm_params(hicmi_ctx* c) { return c->d_hsmall; }
+inline double* hmm_sums(hicmi_ctx* c) { return c->d_hsmall + HMM_P_SCALARS * c->hmm_ld + HMM_S_COUNT; }
+inline double* hmm_cen(hicmi_ctx* c) { return hmm_sums(c) + 4 * c->hmm_ld; }
+inline double* hmm_slots(hicmi_ctx* c) { return hmm_cen(c) + 2 * c->hmm_ld; }
+
+// work areas for the current X (sized once per X: nothing is allocated inside the k-means or EM loops)
+int hmm_size_work(hicmi_ctx* c)
+{
+    const int64_t T = c->hmm_T, ld = c->hmm_ld;
+    int rc = ensure(c->d_hwork, c->hwork_cap, 10 * T);
+    if (!rc) rc = ensure(c->d_hlab, c->hlab_cap, 3 * T);
+    if (!rc) rc = ensure(c->d_hbt, c->hbt_cap, T);
+    // a column pass over width D <= ld has at most min(T, 1024) and at most 2048 / ceil(D / 256) + 1 row chunks
+    const int64_t cb = (ld + 255) / 256;
+    const int64_t part = 4 * std::min(std::min(T, (int64_t)1024) * ld, (2048 + cb) * 256);
+    if (!rc) rc = ensure(c->d_hpart, c->hpart_cap, part);
+    if (!rc) rc = ensure(c->d_hsmall, c->hsmall_cap, (HMM_P_SCALARS + 6) * ld + HMM_S_COUNT + 16);
+    if (!rc) rc = ensure(c->d_hst, c->hst_cap, 4);
+    return rc;
+}
+
+int hmm_check(hicmi_ctx* c)
+{
+    if (!c) return fail(HICMI_EINVAL, "NULL context");
+    if (c->hmm_T <= 0 || c->hmm_D <= 0) return fail(HICMI_EINVAL, "no HMM observations (hicmi_hmm_load_obs / hicmi_hmm_set_obs)");
+    return HICMI_OK;
+}
+
+// model parameters in, emission operands / log transition matrix computed on the device
+int hmm_upload_params(hicmi_ctx* c, const double* startprob, const double* means, const double* covars,
+                      const double* transmat)
+{
+    const int64_t D = c->hmm_D;
+    double* P = hmm_params(c);
+    int rc = upload(c, P + HMM_P_MEAN * D, means, sizeof(double) * 2 * D);
+    if (!rc) rc = upload(c, P + HMM_P_VAR * D, covars, sizeof(double) * 2 * D);
+    double sc[HMM_S_COUNT] = {0};
+    for (int q = 0; q < 4; q++) sc[HMM_S_A + q] = transmat[q];
+    sc[HMM_S_PI] = startprob[0]; sc[HMM_S_PI + 1] = startprob[1];
+    if (!rc) rc = upload(c, P + HMM_P_SCALARS * D, sc, sizeof(sc));
+    if (rc) return rc;
+    launch_hmm_params(nullptr, (int)D, 0, P, c->stream);
+    HIPCHK(hipGetLastError());
+    return HICMI_OK;
+}
+
+}  // namespace
+
+int hicmi_hmm_load_obs(hicmi_ctx* c, const int32_t* order, int64_t n, int64_t cut, int64_t prev)
+{
+    if (!c || !order) return fail(HICMI_EINVAL, "bad arguments");
+    if (!c->dC || n != c->n) return fail(HICMI_EINVAL, "order must have n entries (n = %lld)", (long long)c->n);
+    if (!c->have_sums) return fail(HICMI_EINVAL, "hicmi_row_sums has not run");
+    if (cut < 0 || cut >= n || prev <= cut || prev > n) return fail(HICMI_EINVAL, "need 0 <= c < p <= n");
+    for (int64_t i = 0; i < n; i++)
+        if (order[i] < 0 || order[i] >= n) return fail(HICMI_EINVAL, "order entry out of range");
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t T = n - cut, D = prev - cut;
+    int rc = ensure(c->d_horder, c->horder_cap, n);
+    if (!rc) rc = ensure(c->d_hx, c->hx_cap, T * D);
+    if (rc) return rc;
+    c->hmm_T = T; c->hmm_ld = D; c->hmm_D = D;
+    rc = hmm_size_work(c);
+    if (!rc) rc = upload(c, c->d_horder, order, sizeof(int32_t) * (size_t)n);
+    if (rc) return rc;
+    launch_hmm_obs(c->dC, c->ldc, c->d_horder, c->d_np, c->d_seq, (int)cut, (int)T, (int)D, c->d_hx, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(sync_stream(c));
+    return HICMI_OK;
+}
+
+int hicmi_hmm_set_obs(hicmi_ctx* c, const double* X, int64_t T, int64_t D)
+{
+    if (!c || !X || T < 1 || D < 1 || T > (1 << 24) || T * D > ((int64_t)1 << 31)) return fail(HICMI_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    int rc = ensure(c->d_hx, c->hx_cap, T * D);
+    if (rc) return rc;
+    c->hmm_T = T; c->hmm_ld = D; c->hmm_D = D;
+    rc = hmm_size_work(c);
+    if (!rc) rc = upload(c, c->d_hx, X, sizeof(double) * (size_t)(T * D));
+    if (rc) return rc;
+    HIPCHK(sync_stream(c));
+    return HICMI_OK;
+}
+
+int hicmi_hmm_set_width(hicmi_ctx* c, int64_t D)
+{
+    int rc = hmm_check(c);
+    if (rc) return rc;
+    if (D < 1 || D > c->hmm_ld) return fail(HICMI_EINVAL, "width %lld outside [1, %lld]", (long long)D, (long long)c->hmm_ld);
+    c->hmm_D = D;
+    return HICMI_OK;
+}
+
+int hicmi_hmm_get_obs(hicmi_ctx* c, int64_t row0, int64_t nrows, double* out)
+{
+    int rc = hmm_check(c);
+    if (rc) return rc;
+    if (!out || row0 < 0 || nrows < 0 || row0 + nrows > c->hmm_T) return fail(HICMI_EINVAL, "rows out of range");
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t ld = c->hmm_ld, D = c->hmm_D;
+    if (D == ld) return download(c, out, c->d_hx + row0 * ld, sizeof(double) * (size_t)(nrows * ld));
+    std::vector<double> tmp((size_t)(nrows * ld));
+    rc = download(c, tmp.data(), c->d_hx + row0 * ld, sizeof(double) * tmp.size());
+    if (rc) return rc;
+    for (int64_t r = 0; r < nrows; r++) memcpy(out + r * D, tmp.data() + r * ld, sizeof(double) * (size_t)D);
+    return HICMI_OK;
+}
+
+int hicmi_hmm_dist2(hicmi_ctx* c, const int64_t* rows, int64_t k, double* out)
+{
+    int rc = hmm_check(c);
+    if (rc) return rc;
+    if (!rows || !out || k < 1 || k > 2) return fail(HICMI_EINVAL, "k must be 1 or 2");
+    for (int64_t j = 0; j < k; j++)
+        if (rows[j] < 0 || rows[j] >= c->hmm_T) return fail(HICMI_EINVAL, "row out of range");
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t T = c->hmm_T, D = c->hmm_D, ld = c->hmm_ld;
+    double* cen = hmm_cen(c);
+    for (int64_t j = 0; j < k; j++)
+        HIPCHK(hipMemcpyAsync(cen + j * D, c->d_hx + rows[j] * ld, sizeof(double) * (size_t)D, hipMemcpyDeviceToDevice, c->stream));
+    double* dist = c->d_hwork + 8 * T;
+    launch_hmm_dist2(c->d_hx, ld, (int)T, (int)D, cen, (int)k, dist, c->stream);
+    HIPCHK(hipGetLastError());
+    return download(c, out, dist, sizeof(double) * (size_t)(k * T));
+}
+
+int hicmi_hmm_col_stats(hicmi_ctx* c, double* mean_out, double* m2_out)
+{
+    int rc = hmm_check(c);
+    if (rc) return rc;
+    if (!mean_out || !m2_out) return fail(HICMI_EINVAL, "NULL output");
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t T = c->hmm_T, D = c->hmm_D, ld = c->hmm_ld;
+    double* sums = hmm_sums(c);
+    launch_hmm_colsum(0, c->d_hx, ld, (int)T, (int)D, nullptr, nullptr, nullptr, c->d_hpart, sums, c->stream);
+    HIPCHK(hipGetLastError());
+    rc = download(c, mean_out, sums, sizeof(double) * (size_t)D);
+    if (rc) return rc;
+    for (int64_t d = 0; d < D; d++) mean_out[d] /= (double)T;
+    double* cen = hmm_cen(c);
+    rc = upload(c, cen, mean_out, sizeof(double) * (size_t)D);
+    if (rc) return rc;
+    launch_hmm_colsum(0, c->d_hx, ld, (int)T, (int)D, cen, nullptr, nullptr, c->d_hpart, sums, c->stream);
+    HIPCHK(hipGetLastError());
+    return download(c, m2_out, sums + D, sizeof(double) * (size_t)D);
+}
+
+int hicmi_hmm_kmeans(hicmi_ctx* c, const double* centers_in, int64_t max_iter, double tol, double* centers_out,
+                     int32_t* labels_out, double* inertia_out, int64_t* n_iter_out)
+{
+    int rc = hmm_check(c);
+    if (rc) return rc;
+    if (!centers_in || !centers_out || max_iter < 1) return fail(HICMI_EINVAL, "bad arguments");
+    if (c->hmm_T < 2) return fail(HICMI_EINVAL, "k-means with 2 clusters needs at least 2 rows");
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t T = c->hmm_T, D = c->hmm_D, ld = c->hmm_ld;
+    double* cen = hmm_cen(c);
+    double* sums = hmm_sums(c);
+    double* slots = hmm_slots(c);
+    double* mind = c->d_hwork + 8 * T;
+    int32_t* lab[2] = {c->d_hlab, c->d_hlab + T};
+    rc = upload(c, cen, centers_in, sizeof(double) * (size_t)(2 * D));
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(lab[0], 0xff, sizeof(int32_t) * (size_t)T, c->stream));     // "no label yet" (-1)
+    // sklearn _kmeans_single_lloyd: labels from the current centers, new centers from those labels; stop when the labels
+    // did not change (strict convergence) or the squared center shift is <= tol
+    int cur = 0;                                      // lab[cur]: the latest labels
+    bool strict = false;
+    int64_t it = 0;
+    for (it = 0; it < max_iter; it++) {
+        const int nxt = cur ^ 1;
+        HIPCHK(hipMemsetAsync(c->d_hst, 0, sizeof(int) * 4, c->stream));
+        launch_hmm_assign(c->d_hx, ld, (int)T, (int)D, cen, lab[cur], lab[nxt], mind, c->d_hst, c->stream);
+        launch_hmm_colsum(1, c->d_hx, ld, (int)T, (int)D, nullptr, lab[nxt], nullptr, c->d_hpart, sums, c->stream);
+        launch_hmm_center_update(sums, (int)T, (int)D, c->d_hst, cen, slots, c->stream);
+        HIPCHK(hipGetLastError());
+        cur = nxt;
+        double st[4];
+        rc = download(c, st, slots, sizeof(st));
+        if (rc) return rc;
+        if (st[2] == 0.0) { strict = true; it++; break; }
+        if (st[0] <= tol) { it++; break; }
+    }
+    if (!strict) {                                    // final labels from the final centers
+        const int nxt = cur ^ 1;
+        launch_hmm_assign(c->d_hx, ld, (int)T, (int)D, cen, lab[cur], lab[nxt], mind, c->d_hst, c->stream);
+        HIPCHK(hipGetLastError());
+        cur = nxt;
+    }
+    launch_hmm_sum(mind, (int)T, slots + 4, c->stream);
+    HIPCHK(hipGetLastError());
+    if (labels_out) { rc = download(c, labels_out, lab[cur], sizeof(int32_t) * (size_t)T); if (rc) return rc; }
+    if (inertia_out) { rc = download(c, inertia_out, slots + 4, sizeof(double)); if (rc) return rc; }
+    if (n_iter_out) *n_iter_out = it;
+    return download(c, centers_out, cen, sizeof(double) * (size_t)(2 * D));
+}
+
+int hicmi_hmm_fit(hicmi_ctx* c, const double* startprob, double* means, double* covars, double* transmat, int64_t n_iter,
+                  double tol, double* logprob_out, int64_t* n_done_out)
+{
+    int rc = hmm_check(c);
+    if (rc) return rc;
+    if (!startprob || !means || !covars || !transmat || !logprob_out || !n_done_out || n_iter < 1)
+        return fail(HICMI_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t T = c->hmm_T, D = c->hmm_D, ld = c->hmm_ld;
+    rc = ensure(c->d_hhist, c->hhist_cap, n_iter);
+    if (!rc) rc = hmm_upload_params(c, startprob, means, covars, transmat);
+    if (rc) return rc;
+    double* P = hmm_params(c);
+    double* sums = hmm_sums(c);
+    double *L = c->d_hwork, *alpha = L + 2 * T, *beta = L + 4 * T, *gam = L + 6 * T;
+    // hmmlearn BaseHMM.fit: E-step with the current parameters (its logprob is the monitor's value), M-step, then
+    // the convergence test history[-1] - history[-2] < tol
+    int64_t it = 0;
+    double prev = 0.0;
+    for (it = 0; it < n_iter; it++) {
+        launch_hmm_emission(c->d_hx, ld, (int)T, (int)D, P, L, c->stream);
+        launch_hmm_fb(L, (int)T, P, (int)D, alpha, beta, gam, c->d_hhist, (int)it, c->stream);
+        launch_hmm_colsum(2, c->d_hx, ld, (int)T, (int)D, nullptr, nullptr, gam, c->d_hpart, sums, c->stream);
+        launch_hmm_params(sums, (int)D, 1, P, c->stream);
+        HIPCHK(hipGetLastError());
+        double lp = 0.0;
+        rc = download(c, &lp, c->d_hhist + it, sizeof(double));
+        if (rc) return rc;
+        logprob_out[it] = lp;
+        if (it >= 1 && lp - prev < tol) { it++; break; }
+        prev = lp;
+    }
+    *n_done_out = it;
+    rc = download(c, means, P + HMM_P_MEAN * D, sizeof(double) * (size_t)(2 * D));
+    if (!rc) rc = download(c, covars, P + HMM_P_VAR * D, sizeof(double) * (size_t)(2 * D));
+    double sc[HMM_S_COUNT];
+    if (!rc) rc = download(c, sc, P + HMM_P_SCALARS * D, sizeof(sc));
+    if (rc) return rc;
+    for (int q = 0; q < 4; q++) transmat[q] = sc[HMM_S_A + q];
+    return HICMI_OK;
+}
+
+int hicmi_hmm_decode(hicmi_ctx* c, const double* startprob, const double* means, const double* covars,
+                     const double* transmat, int32_t* states_out)
+{
+    int rc = hmm_check(c);
+    if (rc) return rc;
+    if (!startprob || !means || !covars || !transmat || !states_out) return fail(HICMI_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t T = c->hmm_T, D = c->hmm_D, ld = c->hmm_ld;
+    rc = hmm_upload_params(c, startprob, means, covars, transmat);
+    if (rc) return rc;
+    double* P = hmm_params(c);
+    double* L = c->d_hwork;
+    int32_t* states = c->d_hlab + 2 * T;
+    launch_hmm_emission(c->d_hx, ld, (int)T, (int)D, P, L, c->stream);
+    launch_hmm_viterbi(L, (int)T, P, (int)D, c->d_hbt, states, c->stream);
+    HIPCHK(hipGetLastError());
+    return download(c, states_out, states, sizeof(int32_t) * (size_t)T);
 }
 
 // ---------------------------------------------------------------------------------------------------

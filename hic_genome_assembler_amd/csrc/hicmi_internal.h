@@ -302,4 +302,25 @@ double plot_select_value(const void* host_state, int t);
 void launch_plot_downsample(const double* C, int64_t ldc, const double* np_sum, const double* seq_sum, int kind,
                             const int32_t* order, int n_sel, int px, double* out, hipStream_t s);
 
+// k_hmm.hip: the HMM boundary finder (S2C:730-942).  Model parameters live in one fp64 buffer: blocks of 2 x D
+// (state-major) at offset HMM_P_* x D, then HMM_S_COUNT scalars at HMM_P_SCALARS x D.
+enum { HMM_P_MEAN = 0, HMM_P_VAR = 2, HMM_P_MOV = 4, HMM_P_IV = 6, HMM_P_LOGV = 8, HMM_P_MU2V = 10, HMM_P_SCALARS = 12 };
+enum { HMM_S_CONST = 0, HMM_S_A = 2, HMM_S_LOGA = 6, HMM_S_PI = 10, HMM_S_LOGPI = 12, HMM_S_XI = 14, HMM_S_POST = 18,
+       HMM_S_COUNT = 32 };
+int  hmm_col_chunks(int T, int D);                       // row chunks of a column pass (partials: chunks x 4 x D doubles)
+void launch_hmm_obs(const double* C, int64_t ldc, const int32_t* order, const double* np_sum, const double* seq_sum,
+                    int c, int T, int D, double* X, hipStream_t s);
+void launch_hmm_colsum(int mode, const double* X, int64_t ld, int T, int D, const double* shift, const int32_t* labels,
+                       const double* g, double* part, double* out, hipStream_t s);
+void launch_hmm_dist2(const double* X, int64_t ld, int T, int D, const double* cen, int nc, double* dist, hipStream_t s);
+void launch_hmm_assign(const double* X, int64_t ld, int T, int D, const double* cen, const int32_t* old_labels,
+                       int32_t* labels, double* mind, int* st, hipStream_t s);
+void launch_hmm_center_update(const double* sums, int T, int D, const int* st, double* cen, double* shift_out, hipStream_t s);
+void launch_hmm_sum(const double* v, int n, double* out, hipStream_t s);
+void launch_hmm_params(const double* sums, int D, int from_sums, double* P, hipStream_t s);
+void launch_hmm_emission(const double* X, int64_t ld, int T, int D, const double* P, double* L, hipStream_t s);
+void launch_hmm_fb(const double* L, int T, double* P, int D, double* alpha, double* beta, double* gam, double* hist, int it,
+                   hipStream_t s);
+void launch_hmm_viterbi(const double* L, int T, const double* P, int D, uint8_t* bt, int32_t* states, hipStream_t s);
+
 }  // namespace hicmi

@@ -140,12 +140,15 @@ def ensureAllVariablesAreSet(varDict):
         print('- WARNING - Both hyperGeom and hmm options are set to True... Set one option to "True" and the other '
               'to "False" or both to "False" in order to continue. Exiting...')
         return True
+    if varDict["hyperGeom"] is not True and varDict["hmm"] is True and os.environ.get("HICMI_HMM", "") == "1":
+        return False                      # the HMM boundary finder, opt-in (scaffoldToChromosomes.hmm_enabled)
     if varDict["hyperGeom"] is not True:
         # Not in the reference: its hmm = True / both-False paths need hmmlearn's stochastic EM (scaffoldToChromosomes.py:
         # 730-942; SURVEY.md section 2 row 7, out of scope).  Said here, before any part has touched a file, instead
         # of as a NotImplementedError in the middle of Part 1.
-        print('- ERROR - this MI355X build implements the hyperGeom = True boundary finder only (hmm = True needs '
-              'hmmlearn; see README.md). Set "hyperGeom = True" and "hmm = False" to continue. Exiting...')
+        print('- ERROR - this MI355X build implements the hyperGeom = True boundary finder by default (hmm = True is a '
+              'seeded restatement of hmmlearn\'s EM, enabled with HICMI_HMM=1; see README.md). Set "hyperGeom = True" '
+              'and "hmm = False", or HICMI_HMM=1 with "hmm = True", to continue. Exiting...')
         return True
     return False
 

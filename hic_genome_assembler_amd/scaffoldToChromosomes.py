@@ -14,11 +14,13 @@ heavy step is a hand-written gfx950 kernel reached through the C ABI of include/
   numpy.argsort[:, ::-1]       S2C:1132       hicmi_rank_matrix
   find_matrix_pvalue_breakpoints S2C:413-511  hicmi_cut_scan (+ host window logic)
   filter_noisy_breakpoints     S2C:553-727    hicmi_filter_scan (+ host control flow)
+  hmmChromosomes (hmm = True)  S2C:730-942    hicmi_hmm_* (k_hmm.hip) + host control flow; opt-in: HICMI_HMM=1
 
 Host control flow (loops over cut candidates, file formats, scaffold voting) is restated here in
 Python because its decisions are sequential and tiny.  There is no CPU fallback for the kernels.
 
-Not implemented: the HMM boundary finder.  The Louvain tail (``modularity > 0``,
+The HMM boundary finder (``hmm = True``, hmmlearn in the reference) is a seeded restatement of hmmlearn's 2-state
+diagonal GaussianHMM, enabled by HICMI_HMM=1.  The Louvain tail (``modularity > 0``,
 unseeded-random in the reference) is a seeded restatement in modularity.py.  The two Part 1 figures are drawn from the
 device-resident matrix by plotContactMaps.py (exact percentiles, figure-resolution block means).
 """
@@ -57,6 +59,13 @@ class DeviceMatrix:
 
     def __len__(self):
         return self.ctx.n
+
+    def hmm_states(self, c, p):
+        """hmmChromosomes' model.fit(X) + model.predict(X) (S2C:796-801) for X = rows [c, n), columns [c, p) of the
+        log-transformed similarity matrix in the current order."""
+        if getattr(self, "hmm", None) is None:
+            self.hmm = HmmDevice(self)
+        return self.hmm.states(c, p)
 
 
 class RankMatrix:
@@ -366,6 +375,219 @@ def filter_noisy_breakpoints(argsorted_mat: RankMatrix, original_inds, psig=.05)
 
 
 # ------------------------------------------------------------------------------------------------
+# HMM boundary finder (hmm = True, S2C:730-942).  hmmlearn's GaussianHMM(n_components=2, covariance_type="diag",
+# n_iter=1000, init_params="cm", params="cmt") restated from its formulas (not checked against hmmlearn itself, which
+# is not a dependency): the passes over X run on the device (k_hmm.hip), the k-means++ draws, the restarts and the
+# convergence tests here.  sklearn's unseeded KMeans(n_init=10) is replaced by seeded k-means++ (HICMI_HMM_SEED).
+HMM_N_ITER, HMM_TOL, HMM_MIN_COVAR = 1000, 1e-2, 1e-3
+HMM_KMEANS_RESTARTS, HMM_KMEANS_MAX_ITER, HMM_KMEANS_TOL = 10, 300, 1e-4
+# S2C:797-799: the reference sets model.startmat_ (misspelled, never read) - hmmlearn starts from a uniform startprob_,
+# and params has no 's', so it stays uniform
+HMM_STARTPROB = (.5, .5)
+HMM_TRANSMAT = ((.9, .1), (.0001, .9999))
+
+
+def hmm_enabled():
+    """The HMM path is opt-in: its parity with the reference is statistical (seeded initialisation)."""
+    return os.environ.get("HICMI_HMM", "") == "1"
+
+
+class HmmDevice:
+    """Fits and decodes the HMM of one (c, p) window of a DeviceMatrix.  X is built on the device once per boundary
+    at its widest D; narrower rounds of the same boundary read a column prefix of it."""
+
+    def __init__(self, matrix: DeviceMatrix, seed=None):
+        self.matrix = matrix
+        self.seed = int(os.environ.get("HICMI_HMM_SEED", "0")) if seed is None else int(seed)
+        self.fit_index = 0
+        self.built = None                       # (c, width) of the X on the device
+        self.profile = os.environ.get("HICMI_HMM_PROFILE") == "1"
+        self.stats = collections.Counter()
+
+    def _tick(self, key, t0):
+        self.stats[key + "_ms"] += (time.perf_counter() - t0) * 1e3
+
+    def states(self, c, p):
+        ctx = self.matrix.ctx
+        n = self.matrix.n
+        D = p - c
+        t0 = time.perf_counter()
+        if self.built is None or self.built[0] != c or self.built[1] < D:
+            order = self.matrix.order if self.matrix.order is not None else list(range(n))
+            ctx.hmm_load_obs(order, c, p)
+            self.built = (c, D)
+            self.stats["builds"] += 1
+        ctx.hmm_set_width(D)
+        self._tick("obs", t0)
+        T = n - c
+        t0 = time.perf_counter()
+        means, covars = hmm_init_params(ctx, T, self.seed, self.fit_index, self.stats)
+        self._tick("init", t0)
+        t0 = time.perf_counter()
+        means, covars, transmat, hist = ctx.hmm_fit(HMM_STARTPROB, means, covars, HMM_TRANSMAT, HMM_N_ITER, HMM_TOL)
+        self._tick("fit", t0)
+        t0 = time.perf_counter()
+        st = ctx.hmm_decode(HMM_STARTPROB, means, covars, transmat)
+        self._tick("decode", t0)
+        self.fit_index += 1
+        self.stats["fits"] += 1
+        self.stats["em_iterations"] += len(hist)
+        if self.profile:
+            sys.stderr.write("[hicmi] hmm fit %d: X %d x %d, %d EM iterations, logprob %.6f\n"
+                             % (self.fit_index, T, D, len(hist), hist[-1]))
+        return st
+
+    def report(self):
+        s = self.stats
+        sys.stderr.write("[hicmi] hmm: %d fits, %d EM iterations, %d k-means iterations, %d X builds; ms: obs %.1f, "
+                         "init (k-means) %.1f, fit %.1f, decode %.1f\n"
+                         % (s["fits"], s["em_iterations"], s["kmeans_iterations"], s["builds"], s["obs_ms"],
+                            s["init_ms"], s["fit_ms"], s["decode_ms"]))
+
+
+def hmm_init_params(ctx, T, seed, fit_index, stats=None):
+    """GaussianHMM._init with init_params="cm" on the X of ``ctx``: means from the best of 10 seeded k-means++ / Lloyd
+    restarts (lowest inertia, the first on a tie; numpy.random.default_rng([seed, fit_index, restart])), covariances
+    diag(numpy.cov(X.T)) + min_covar for both states."""
+    mean, m2 = ctx.hmm_col_stats()
+    var1 = m2 / (T - 1)
+    tol = HMM_KMEANS_TOL * float(np.mean(m2 / T))             # sklearn: tol * mean(var(X, axis=0))
+    best = None
+    for restart in range(HMM_KMEANS_RESTARTS):
+        rng = np.random.default_rng([seed, fit_index, restart])
+        rows = kmeans_plusplus_rows(T, ctx.hmm_dist2, rng)
+        init = np.vstack([ctx.hmm_get_obs(r, 1) for r in rows])
+        centers, _labels, inertia, n_iter = ctx.hmm_kmeans(init, HMM_KMEANS_MAX_ITER, tol, want_labels=False)
+        if stats is not None:
+            stats["kmeans_iterations"] += n_iter
+        if best is None or inertia < best[1]:
+            best = (centers, inertia)
+    covars = np.vstack([var1 + HMM_MIN_COVAR, var1 + HMM_MIN_COVAR])
+    return best[0], covars
+
+
+def kmeans_plusplus_rows(T, dist2, rng):
+    """sklearn's greedy k-means++ for 2 clusters (2 + int(log 2) = 2 local trials): the rows of X chosen as the initial
+    centers.  ``dist2(rows)``: squared distances of every row of X to the given rows (len(rows) x T)."""
+    first = int(rng.integers(T))
+    closest = dist2([first])[0]
+    pot = closest.sum()
+    rand_vals = rng.uniform(size=2) * pot
+    cand = np.minimum(np.searchsorted(np.cumsum(closest), rand_vals), T - 1)
+    dist = np.minimum(closest, dist2(cand))
+    best = int(np.argmin(dist.sum(axis=1)))
+    return [first, int(cand[best])]
+
+
+def identifyBoundry(hiddenStates, cutIndices, switchCount=10):
+    """S2C:730-752: the start state is the majority of the first switchCount states (a tie: state 0); the boundary is
+    the first window of switchCount states with no start state, over the windows range(0, len - switchCount)."""
+    states = np.asarray(hiddenStates).astype(np.int64)
+    head = states[0:switchCount]
+    ones = int((head == 1).sum())
+    startState = 1 if ones > len(head) - ones else 0
+    n_win = len(states) - switchCount
+    if n_win <= 0:
+        return 0
+    other = np.concatenate(([0], np.cumsum(states != startState)))
+    full = np.flatnonzero(other[switchCount:switchCount + n_win] - other[:n_win] == switchCount)
+    return int(full[0]) + cutIndices[-1] if len(full) else 0
+
+
+def hmmChromosomes(adjacencyMatrix, cutIndices, binList, minSize=20, convergenceRounds=8, lookAhead=False):
+    """S2C:754-819.  ``adjacencyMatrix``: the DeviceMatrix at its similarity stage (its ``hmm_states(c, p)`` fits and
+    decodes X = log10(similarity + 1)[c:n, c:p])."""
+    n = len(adjacencyMatrix)
+    if lookAhead != False:                                  # noqa: E712  (the reference's test: 0.0 means "all")
+        lookAhead = int((float(n - cutIndices[-1]) * lookAhead) + cutIndices[-1])
+    else:
+        lookAhead = n
+    prevCutInd, roundCount = lookAhead, 1
+    while roundCount <= convergenceRounds:
+        if (n - cutIndices[-1]) / 2 < minSize:
+            cutInd = prevCutInd
+            cutIndices.append("NA")
+            break
+        c = cutIndices[-1]
+        width = max(0, min(prevCutInd, n) - c)                 # len(X[0]) of r[c:prevCutInd]
+        print("Input matrix size = " + str(n - c) + " x " + str(width))
+        print("HMM round = " + str(roundCount))
+        if width < minSize:
+            cutInd = lookAhead
+        else:
+            hiddenStates = adjacencyMatrix.hmm_states(c, c + width)
+            cutInd = identifyBoundry(hiddenStates, cutIndices, switchCount=minSize)
+        if cutInd != prevCutInd:
+            prevCutInd = cutInd
+            roundCount += 1
+            continue
+        else:
+            print("HMM convergence rounds = " + str(roundCount))
+            cutIndices.append(int(cutInd))
+            break
+    if roundCount > convergenceRounds:
+        cutIndices.append(int(cutInd))
+        print("WARNING... HMM failed to converge after " + str(roundCount) + " rounds...")
+        print("Proceeding with last found cutIndex of " + str(cutInd) + "...")
+    return cutIndices
+
+
+def identifyChromosomeGroupsHMM(adjacencyMatrix, binList, minSize=5, modularity=.05, convergenceRounds=5, lookAhead=.2,
+                                louvainRounds=20, prev_cutInds=False):
+    """S2C:868-942.  One documented difference: where the reference raises IndexError (no cut left after the leading 0
+    is popped, S2C:920), this returns [] with a warning."""
+    print("#########################" + '\n' + "#########################")
+    print("Working on iterative 2 state HMMs to identify chromosome boundaries...")
+    startTime = time.time()
+    n = len(adjacencyMatrix)
+    matrixLength = float(n)
+    remainder = matrixLength - (modularity * matrixLength)
+    cutIndices = [0]
+    if modularity == 1:
+        return []
+    if prev_cutInds is not False:
+        cutIndices = prev_cutInds
+    while cutIndices[-1] <= remainder:
+        print("#########################" + '\n' + "#########################")
+        cutIndices = hmmChromosomes(adjacencyMatrix, cutIndices, binList, minSize=minSize,
+                                    convergenceRounds=convergenceRounds, lookAhead=lookAhead)
+        print("Cut indices =  " + str(cutIndices))
+        if cutIndices[-1] == 0:
+            print("Algorithm terminated. No obvious chromome boundry could be found... ")
+            break
+        if cutIndices[-1] == "NA":
+            cutIndices.pop(-1)
+            break
+    if cutIndices[0] == 0:
+        cutIndices.pop(0)
+    print("#########################" + '\n' + "#########################")
+    print("HMM rounds completed in " + str(time.time() - startTime) + " seconds")
+    print("Chromosome groups found via HMMs " + str(len(cutIndices)) + " / " + str(len(cutIndices) + 1))
+    if len(cutIndices) == 0:
+        print("- WARNING - no chromosome boundary found by the HMMs (the reference raises IndexError here)")
+        return []
+    if cutIndices[-1] == n:
+        print("- WARNING - Last cut index found to be length of current matrix removing index values of {}".format(cutIndices[-1]))
+        cutIndices.pop(-1)
+        if len(cutIndices) == 0:
+            print("- WARNING - no chromosome boundary left (the reference raises IndexError here)")
+            return []
+        if (n - cutIndices[-1]) >= (5 * (n * modularity)):
+            print("- convergenceRounds reduced from {} --> {}".format(convergenceRounds, convergenceRounds - 1))
+            if convergenceRounds - 1 == 0:
+                print("- Failed to converge after reducing convergence rounds all the way to 1... Returning current indices")
+                return cutIndices
+            else:
+                print("- Recursing on identifyChromosomeGroupsHMM function, due to remaining fraction of data being greater "
+                      "than 5x than that of desired fraction")
+                cutIndices = identifyChromosomeGroupsHMM(adjacencyMatrix, binList, minSize=5, modularity=.05,
+                                                         convergenceRounds=convergenceRounds - 1, lookAhead=.5,
+                                                         louvainRounds=20, prev_cutInds=cutIndices)
+    print("Total time to identify chromosome boundries = " + str(time.time() - startTime) + " seconds")
+    return cutIndices
+
+
+# ------------------------------------------------------------------------------------------------
 def _bin_line(b):
     return f"{b.ID}\t{b.chrom}\t{b.start}\t{b.stop}\t{b.bias}"
 
@@ -585,15 +807,17 @@ def runPipeline(hicProBedFile, hicProBiasFile, hicProMatrixFile, hicProScaffSize
     print("########################################")
     print("### Working on Part1 of the pipeline ###")
     t_all = time.time()
-    if hyperGeom is not True:
-        raise NotImplementedError("only the hyperGeom = True strategy is implemented on MI355X "
-                                  "(hmm needs hmmlearn's stochastic EM; SURVEY.md section 2 row 7)")
+    use_hmm = hyperGeom is not True and hmm is True and hmm_enabled()
+    if hyperGeom is not True and not use_hmm:
+        raise NotImplementedError("only the hyperGeom = True strategy is implemented on MI355X by default; hmm = True "
+                                  "(hmmlearn's EM, restated with a seeded initialisation) needs HICMI_HMM=1")
     binList = initiateLoci(hicProBedFile, hicProBiasFile)
     adjMat = buildAdjacencyMatrix(hicProMatrixFile, binList, device=device)
     try:
         cutIndices = runResident(adjMat, binList, hicProScaffSizeFile, dendrogramOrderFile, binGroupFile,
                                  assessmentFile, chromosomeGroupFile, minSize, modularity, psig,
-                                 louvainRounds=louvainRounds, shard=shard)
+                                 louvainRounds=louvainRounds, shard=shard, hmm=use_hmm,
+                                 convergenceRounds=convergenceRounds, lookAhead=lookAhead)
         # S2C:1124 / S2C:1155-1156: the clustered distance matrix, then - groups outlined - the distance transform of
         # the un-logged similarity matrix, which is the distance matrix again up to a few roundings
         if plotModule.plots_enabled(avgClusterPlot):
@@ -653,7 +877,7 @@ class _FileWriter:
 
 def runResident(adjMat: DeviceMatrix, binList, hicProScaffSizeFile, dendrogramOrderFile, binGroupFile,
                 assessmentFile, chromosomeGroupFile, minSize, modularity, psig, louvainRounds=20, shard=None,
-                overlap_files=False):
+                overlap_files=False, hmm=False, convergenceRounds=5, lookAhead=.2):
     """S2C:1117-1167 on a contact map that is already resident in HBM (what bench.py times): every
     stage after the text loaders, including the small intermediate files the reference round-trips
     through.  Returns the filtered cut indices; ``binList`` is left in .bed order for the caller.
@@ -662,7 +886,10 @@ def runResident(adjMat: DeviceMatrix, binList, hicProScaffSizeFile, dendrogramOr
     are sorted and scanned, the three group files while the caller goes on); the caller hands
     ``adjMat.chromosome_groups`` - what Part 2 would read back from chromosomeGroupFile - to
     ``orderGenome.runResident(..., chromosomeList=, on_native_phase=adjMat.release_files)`` and calls
-    ``adjMat.finish_files()`` before it uses the files."""
+    ``adjMat.finish_files()`` before it uses the files.
+
+    ``hmm=True``: the boundaries come from identifyChromosomeGroupsHMM (S2C:1138-1140, with ``convergenceRounds`` and
+    ``lookAhead``) instead of the rank matrix and the two hypergeometric scans; everything after is the same."""
     writer = _FileWriter(overlap_files)
     adjMat.finish_files = writer.finish
     adjMat.release_files = writer.release
@@ -705,16 +932,29 @@ def runResident(adjMat: DeviceMatrix, binList, hicProScaffSizeFile, dendrogramOr
         print("Total run-time to cluster = " + str(time.time() - t0))
         t0 = time.time()
         adjMat = convertMatrix(adjMat, binList, distance=False, similarity=True)
-        argsorted_adjMat = rankOrderMatrix(adjMat)
-        # the dendrogram file (16k formatted lines: ~5 ms of interpreter time) is handed to the writer thread only now: the
-        # two scan loops that follow are native calls that release the interpreter lock, the list work above is not
-        writer.submit(dendrogramLeafOrder_toFile, dendrogram, dendrogramOrderFile, prep["dend_lines"])
-        mark("reorder + rank matrix")
-        initial_cut_inds = pre_process_all_matrix_breakpoints(argsorted_adjMat, min_size=minSize,
-                                                              min_frac=modularity, psig=psig)
-        mark("first-pass scans")
-        cutIndices = filter_noisy_breakpoints(argsorted_adjMat, initial_cut_inds, psig=psig)
-        mark("filter scans")
+        if hmm:
+            # S2C:1138-1140: every rank of a shard runs the HMM whole (the matrix and the gathered row sums are on each)
+            writer.submit(dendrogramLeafOrder_toFile, dendrogram, dendrogramOrderFile, prep["dend_lines"])
+            mark("reorder")
+            adjMat.hmm = HmmDevice(adjMat)
+            cutIndices = identifyChromosomeGroupsHMM(adjMat, binList, minSize=minSize, modularity=modularity,
+                                                     convergenceRounds=convergenceRounds, lookAhead=lookAhead,
+                                                     louvainRounds=louvainRounds)
+            if adjMat.hmm.profile:
+                adjMat.hmm.report()
+            mark("HMM boundaries")
+        else:
+            argsorted_adjMat = rankOrderMatrix(adjMat)
+            # the dendrogram file (16k formatted lines: ~5 ms of interpreter time) is handed to the writer thread only
+            # now: the two scan loops that follow are native calls that release the interpreter lock, the list work
+            # above is not
+            writer.submit(dendrogramLeafOrder_toFile, dendrogram, dendrogramOrderFile, prep["dend_lines"])
+            mark("reorder + rank matrix")
+            initial_cut_inds = pre_process_all_matrix_breakpoints(argsorted_adjMat, min_size=minSize,
+                                                                  min_frac=modularity, psig=psig)
+            mark("first-pass scans")
+            cutIndices = filter_noisy_breakpoints(argsorted_adjMat, initial_cut_inds, psig=psig)
+            mark("filter scans")
         if modularity is not False and modularity > 0.0:
             # S2C:1148-1152: Louvain on log10(similarity + 1) of the bins after the last cut index (modularity.py:
             # seeded restatement of python-louvain; the cells come from the device in the current order)

@@ -294,6 +294,44 @@ int hicmi_plot_percentiles(hicmi_ctx *ctx, int kind, const int32_t *order, int64
                            double *out);
 int hicmi_plot_downsample(hicmi_ctx *ctx, int kind, const int32_t *order, int64_t n_sel, int64_t px, double *out);
 
+/* ---- Part 1: HMM boundary finder (hmm = True, S2C:730-942) -----------------------------------------
+ * hmmChromosomes (S2C:754-819) fits hmmlearn's GaussianHMM(n_components=2, covariance_type="diag", n_iter=1000,
+ * init_params="cm", params="cmt") to X = logTransformMatrix(similarity)[c:n, c:p] (S2C:785-786, S2C:165-183) and
+ * decodes it.  These entry points restate that model's numerics on the device; the host keeps
+ * the control flow, the k-means++ draws and the convergence tests.  X lives in the context (T x D, row-major).
+ *
+ * hicmi_hmm_load_obs: X[t][d] = log10(sim + 1) (0 where sim == 0) of rows c + t and columns c + d of the similarity
+ * matrix (S2C:149) in the row / column order `order` (n int32); T = n - c, D = p - c.  Needs hicmi_row_sums.
+ * hicmi_hmm_set_obs / hicmi_hmm_get_obs: an arbitrary X in (tests), rows [row0, row0 + nrows) of the current view out.
+ * hicmi_hmm_set_width: later rounds of one boundary use columns [0, D) of the X already built (S2C:786 with a smaller
+ * prevCutInd), without a rebuild; every call below works on that view. */
+int hicmi_hmm_load_obs(hicmi_ctx *ctx, const int32_t *order, int64_t n, int64_t c, int64_t p);
+int hicmi_hmm_set_obs(hicmi_ctx *ctx, const double *X, int64_t T, int64_t D);
+int hicmi_hmm_set_width(hicmi_ctx *ctx, int64_t D);
+int hicmi_hmm_get_obs(hicmi_ctx *ctx, int64_t row0, int64_t nrows, double *out);
+/* GaussianHMM._init (S2C:796-801): the k-means of the means (sklearn KMeans(n_clusters=2)) and the covariances
+ * diag(numpy.cov(X.T)) + min_covar.
+ * hicmi_hmm_dist2: out[j][t] = sum_d (X[t][d] - X[rows[j]][d])^2, k = 1 or 2 rows - the distances k-means++ seeding
+ * draws from (the host draws the indices).
+ * hicmi_hmm_col_stats: mean and sum of squared deviations from it of every column (var ddof=1 = m2 / (T - 1)).
+ * hicmi_hmm_kmeans: Lloyd from centers_in (2 x D) as sklearn's _kmeans_single_lloyd runs it - stop when no label
+ * changed, or when the summed squared center shift is <= tol, or after max_iter iterations; an empty cluster keeps
+ * its center; labels ties go to cluster 0.  centers_out (2 x D), labels_out (T int32, may be NULL), inertia_out (may be
+ * NULL), n_iter_out (may be NULL). */
+int hicmi_hmm_dist2(hicmi_ctx *ctx, const int64_t *rows, int64_t k, double *out);
+int hicmi_hmm_col_stats(hicmi_ctx *ctx, double *mean_out, double *m2_out);
+int hicmi_hmm_kmeans(hicmi_ctx *ctx, const double *centers_in, int64_t max_iter, double tol, double *centers_out,
+                     int32_t *labels_out, double *inertia_out, int64_t *n_iter_out);
+/* model.fit(X) (S2C:800): Baum-Welch from startprob (2, never re-estimated), means / covars (2 x D) and transmat
+ * (2 x 2, row-major), all updated in place.  logprob_out[i] = log-likelihood of iteration i under the parameters before
+ * its M-step; it stops after iteration i when logprob[i] - logprob[i-1] < tol, or after n_iter; *n_done_out =
+ * iterations run. */
+int hicmi_hmm_fit(hicmi_ctx *ctx, const double *startprob, double *means, double *covars, double *transmat,
+                  int64_t n_iter, double tol, double *logprob_out, int64_t *n_done_out);
+/* model.predict(X) (S2C:801): Viterbi under the given parameters, ties to state 0.  states_out: T int32. */
+int hicmi_hmm_decode(hicmi_ctx *ctx, const double *startprob, const double *means, const double *covars,
+                     const double *transmat, int32_t *states_out);
+
 /* ---- timing ----------------------------------------------------------------------------------
  * Accumulated device time (HIP events on the context stream) per kernel family since the last
  * reset, for bench.py's roofline object.  names_out: caller buffer receiving ';'-separated names;
