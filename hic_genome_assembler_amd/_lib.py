@@ -18,6 +18,7 @@ _lib = None
 c_i64 = ctypes.c_int64
 c_dbl = ctypes.c_double
 _vp = ctypes.c_void_p
+_M64 = (1 << 64) - 1
 
 # name: (restype, argtypes) - one row per declaration in include/hicmi.h
 SIGNATURES = {
@@ -89,6 +90,12 @@ SIGNATURES = {
     "hicmi_hmm_kmeans": (ctypes.c_int, [_vp, _vp, c_i64, c_dbl, _vp, _vp, ctypes.POINTER(c_dbl), ctypes.POINTER(c_i64)]),
     "hicmi_hmm_fit": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, c_i64, c_dbl, _vp, ctypes.POINTER(c_i64)]),
     "hicmi_hmm_decode": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "hicmi_louvain_graph": (ctypes.c_int, [_vp, _vp, c_i64]),
+    "hicmi_louvain_set_graph": (ctypes.c_int, [_vp, _vp, c_i64]),
+    "hicmi_louvain_get_graph": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "hicmi_louvain_level0": (ctypes.c_int, [_vp, c_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hicmi_louvain_induced": (ctypes.c_int, [_vp, _vp, c_i64, c_i64, _vp]),
+    "hicmi_louvain_modularity": (ctypes.c_int, [_vp, _vp, c_i64, c_i64, _vp]),
     "hicmi_timing_reset": (ctypes.c_int, [_vp]),
     "hicmi_timing_enable": (ctypes.c_int, [_vp, ctypes.c_int]),
     "hicmi_timing_get": (ctypes.c_int, [_vp, ctypes.c_char_p, c_i64, _vp, _vp, _vp, c_i64, ctypes.POINTER(c_i64)]),
@@ -187,6 +194,7 @@ class Context:
         self._keepalive = None
         self._workers = []
         self._n_window_cand = 0
+        self._lv_m = 0                          # nodes of the Louvain graph on the device
         self.shard = (0, 1)
 
     def close(self):
@@ -603,6 +611,66 @@ class Context:
         out = np.empty(self._hmm_shape[0], np.int32)
         _check(self._lib.hicmi_hmm_decode(self._h, _ptr(sp), _ptr(mu), _ptr(cv), _ptr(tm), _ptr(out)))
         return out
+
+    # ---- Louvain tail (modularity > 0, S2C:239-349)
+    def louvain_graph(self, rows):
+        """A = graph_weights(log_transform(similarity of ``rows`` x ``rows``)) built on the device; returns m."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        self._lv_m = 0
+        _check(self._lib.hicmi_louvain_graph(self._h, _ptr(rows), len(rows)))
+        self._lv_m = len(rows)
+        return self._lv_m
+
+    def louvain_set_graph(self, A):
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        if A.ndim != 2 or A.shape[0] != A.shape[1]:
+            raise ValueError("A must be square")
+        self._lv_m = 0
+        _check(self._lib.hicmi_louvain_set_graph(self._h, _ptr(A), A.shape[0]))
+        self._lv_m = A.shape[0]
+
+    def louvain_get_graph(self, with_matrix=True):
+        """(A or None, gdegrees, total_weight) of the graph on the device."""
+        m = self._lv_m
+        A = np.empty((m, m), np.float64) if with_matrix else None
+        gdeg, tw = np.empty(m, np.float64), np.empty(1, np.float64)
+        _check(self._lib.hicmi_louvain_get_graph(self._h, _ptr(A), _ptr(gdeg), _ptr(tw)))
+        return A, gdeg, float(tw[0])
+
+    def louvain_level0(self, states):
+        """Level 0 of best_partition for every PCG64 state in ``states`` (rng.bit_generator.state dicts).  Returns
+        (node2com R x m, states after, info R x 4 [passes, tie replays, near-threshold passes, 0], degrees R x m,
+        internals R x m)."""
+        R, m = len(states), self._lv_m
+        st = np.empty((R, 6), np.uint64)
+        for r, d in enumerate(states):
+            s, inc = int(d["state"]["state"]), int(d["state"]["inc"])
+            st[r] = [s & _M64, s >> 64, inc & _M64, inc >> 64, int(d["has_uint32"]), int(d["uinteger"])]
+        n2c, st_out = np.empty((R, m), np.int32), np.empty((R, 6), np.uint64)
+        info = np.empty((R, 4), np.int32)
+        deg, inr = np.empty((R, m), np.float64), np.empty((R, m), np.float64)
+        _check(self._lib.hicmi_louvain_level0(self._h, R, _ptr(st), _ptr(n2c), _ptr(st_out), _ptr(info), _ptr(deg),
+                                              _ptr(inr)))
+        out = []
+        for r in range(R):
+            v = [int(x) for x in st_out[r]]
+            out.append({"bit_generator": "PCG64", "state": {"state": v[0] | (v[1] << 64), "inc": v[2] | (v[3] << 64)},
+                        "has_uint32": v[4], "uinteger": v[5]})
+        return n2c, out, info, deg, inr
+
+    def louvain_induced(self, part, k):
+        """modularity._induced(A, part): k x k."""
+        part = np.ascontiguousarray(part, dtype=np.int32)
+        out = np.empty((int(k), int(k)), np.float64)
+        _check(self._lib.hicmi_louvain_induced(self._h, _ptr(part), len(part), int(k), _ptr(out)))
+        return out
+
+    def louvain_modularity(self, parts):
+        """modularity.modularity(part, A) of every row of ``parts`` (R x m)."""
+        parts = np.ascontiguousarray(np.atleast_2d(parts), dtype=np.int32)
+        q = np.empty(parts.shape[0], np.float64)
+        _check(self._lib.hicmi_louvain_modularity(self._h, _ptr(parts), parts.shape[0], parts.shape[1], _ptr(q)))
+        return q
 
     # ---- misc
     def synchronize(self):

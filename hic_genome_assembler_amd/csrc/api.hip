@@ -136,6 +136,12 @@ struct hicmi_ctx {
     double* d_hsmall = nullptr; int64_t hsmall_cap = 0;    // params (12 D + scalars), sums (4 D), centers (2 D), scalars
     double* d_hhist = nullptr; int64_t hhist_cap = 0;      // logprob of every EM iteration
     int* d_hst = nullptr; int64_t hst_cap = 0;             // k-means counters
+    // Louvain tail (k_louvain.hip): the graph A (lv_m x lv_m) and its _Status vectors: diag, row sums, gdegrees (m each),
+    // A.sum()'s chunk sums, diag.sum(), total_weight
+    double* d_lvA = nullptr; int64_t lvA_cap = 0; int64_t lv_m = 0;
+    double* d_lvvec = nullptr; int64_t lvvec_cap = 0;
+    int32_t* d_lvrows = nullptr; int64_t lvrows_cap = 0;
+    unsigned char* d_lvwork = nullptr; int64_t lvwork_cap = 0;   // per-call inputs, outputs and scratch
     // plot support
     int32_t* d_plot_order = nullptr; int64_t plot_order_cap = 0;
     unsigned char* d_plot_work = nullptr; int64_t plot_work_cap = 0;
@@ -352,6 +358,7 @@ int hicmi_destroy(hicmi_ctx* c)
     free_dev(c->d_plot_order); free_dev(c->d_plot_work); free_dev(c->d_plot_img);
     free_dev(c->d_hx); free_dev(c->d_horder); free_dev(c->d_hwork); free_dev(c->d_hlab); free_dev(c->d_hbt);
     free_dev(c->d_hpart); free_dev(c->d_hsmall); free_dev(c->d_hhist); free_dev(c->d_hst);
+    free_dev(c->d_lvA); free_dev(c->d_lvvec); free_dev(c->d_lvrows); free_dev(c->d_lvwork);
     if (c->pin_up) (void)hipHostFree(c->pin_up);
     if (c->pin_down) (void)hipHostFree(c->pin_down);
     for (auto& r : c->regions) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -2473,6 +2480,201 @@ int hicmi_hmm_decode(hicmi_ctx* c, const double* startprob, const double* means,
     launch_hmm_viterbi(L, (int)T, P, (int)D, c->d_hbt, states, c->stream);
     HIPCHK(hipGetLastError());
     return download(c, states_out, states, sizeof(int32_t) * (size_t)T);
+}
+
+
+// ---------------------------------------------------------------------------------------------------
+// Louvain tail (S2C:239-349, modularity > 0): level 0 of modularity.best_partition on the device, k_louvain.hip.
+namespace {
+
+inline double* lv_diag(hicmi_ctx* c) { return c->d_lvvec; }
+inline double* lv_gdeg(hicmi_ctx* c) { return c->d_lvvec + 2 * c->lv_m; }
+inline double* lv_total(hicmi_ctx* c) { return c->d_lvvec + 3 * c->lv_m + 1; }
+
+int lv_check(hicmi_ctx* c)
+{
+    if (!c) return fail(HICMI_EINVAL, "NULL context");
+    if (c->lv_m <= 0) return fail(HICMI_EINVAL, "no Louvain graph (hicmi_louvain_graph / hicmi_louvain_set_graph)");
+    return HICMI_OK;
+}
+
+int lv_size(hicmi_ctx* c, int64_t m)
+{
+    if (m < 1) return fail(HICMI_EINVAL, "the graph needs at least one node");
+    if (m > LOUVAIN_MAX_M) return fail(HICMI_EUNSUPPORTED, "m = %lld > %d Louvain nodes", (long long)m, LOUVAIN_MAX_M);
+    const int64_t chunks = (m * m + 8191) / 8192;
+    int rc = ensure(c->d_lvA, c->lvA_cap, m * m);
+    if (!rc) rc = ensure(c->d_lvvec, c->lvvec_cap, 3 * m + 2 + chunks);
+    return rc;
+}
+
+// the _Status vectors of the graph now in d_lvA.  Layout of d_lvvec: diag | row sums | gdegrees | diag.sum() | total |
+// chunk sums
+int lv_status(hicmi_ctx* c, int64_t m)
+{
+    c->lv_m = m;
+    double* v = c->d_lvvec;
+    launch_louvain_status(c->d_lvA, (int)m, v, v + m, v + 3 * m + 2, v + 3 * m, v + 2 * m, v + 3 * m + 1, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(sync_stream(c));
+    return HICMI_OK;
+}
+
+int lv_work(hicmi_ctx* c, size_t bytes) { return ensure(c->d_lvwork, c->lvwork_cap, (int64_t)bytes); }
+
+inline size_t lv_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+}  // namespace
+
+int hicmi_louvain_graph(hicmi_ctx* c, const int32_t* rows, int64_t m)
+{
+    if (m > LOUVAIN_MAX_M) return fail(HICMI_EUNSUPPORTED, "m = %lld > %d Louvain nodes", (long long)m, LOUVAIN_MAX_M);
+    if (!c || !rows) return fail(HICMI_EINVAL, "bad arguments");
+    if (!c->dC) return fail(HICMI_EINVAL, "no contact matrix");
+    if (!c->have_sums) return fail(HICMI_EINVAL, "hicmi_row_sums has not run");
+    if (m > c->n) return fail(HICMI_EINVAL, "m = %lld > n = %lld", (long long)m, (long long)c->n);
+    for (int64_t i = 0; i < m; i++)
+        if (rows[i] < 0 || rows[i] >= c->n) return fail(HICMI_EINVAL, "row entry out of range");
+    c->lv_m = 0;
+    int rc = lv_size(c, m);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    rc = ensure(c->d_lvrows, c->lvrows_cap, m);
+    if (!rc) rc = upload(c, c->d_lvrows, rows, sizeof(int32_t) * (size_t)m);
+    if (rc) return rc;
+    launch_louvain_graph(c->dC, c->ldc, c->d_lvrows, c->d_np, c->d_seq, (int)m, c->d_lvA, c->stream);
+    HIPCHK(hipGetLastError());
+    return lv_status(c, m);
+}
+
+int hicmi_louvain_set_graph(hicmi_ctx* c, const double* A, int64_t m)
+{
+    if (m > LOUVAIN_MAX_M) return fail(HICMI_EUNSUPPORTED, "m = %lld > %d Louvain nodes", (long long)m, LOUVAIN_MAX_M);
+    if (!c || !A) return fail(HICMI_EINVAL, "bad arguments");
+    c->lv_m = 0;
+    int rc = lv_size(c, m);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    rc = upload(c, c->d_lvA, A, sizeof(double) * (size_t)(m * m));
+    if (rc) return rc;
+    return lv_status(c, m);
+}
+
+int hicmi_louvain_get_graph(hicmi_ctx* c, double* out, double* gdeg_out, double* total_out)
+{
+    int rc = lv_check(c);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t m = c->lv_m;
+    if (out) { rc = download(c, out, c->d_lvA, sizeof(double) * (size_t)(m * m)); if (rc) return rc; }
+    if (gdeg_out) { rc = download(c, gdeg_out, lv_gdeg(c), sizeof(double) * (size_t)m); if (rc) return rc; }
+    if (total_out) { rc = download(c, total_out, lv_total(c), sizeof(double)); if (rc) return rc; }
+    return HICMI_OK;
+}
+
+int hicmi_louvain_level0(hicmi_ctx* c, int64_t rounds, const uint64_t* states_in, int32_t* node2com_out,
+                         uint64_t* states_out, int32_t* info_out, double* degrees_out, double* internals_out)
+{
+    int rc = lv_check(c);
+    if (rc) return rc;
+    if (!states_in || !node2com_out || !states_out || !info_out || !degrees_out || !internals_out)
+        return fail(HICMI_EINVAL, "NULL argument");
+    if (rounds < 1 || rounds > LOUVAIN_MAX_ROUNDS)
+        return fail(HICMI_EINVAL, "rounds = %lld outside [1, %d]", (long long)rounds, LOUVAIN_MAX_ROUNDS);
+    for (int64_t r = 0; r < rounds; r++)
+        if ((states_in[6 * r + 2] & 1) == 0 || states_in[6 * r + 4] > 1 || states_in[6 * r + 5] > 0xffffffffull)
+            return fail(HICMI_EINVAL, "round %lld: not a PCG64 state (odd increment, has_uint32 0/1, 32-bit uinteger)",
+                        (long long)r);
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t m = c->lv_m, R = rounds;
+    const bool in_lds = louvain_round_bytes((int)m) <= (size_t)louvain_level0_lds_max();
+    const size_t b_st = lv_align(sizeof(uint64_t) * 6 * R), b_n2c = lv_align(sizeof(int32_t) * R * m),
+                 b_info = lv_align(sizeof(int32_t) * 4 * R), b_vec = lv_align(sizeof(double) * R * m),
+                 b_scr = in_lds ? 0 : lv_align(louvain_round_bytes((int)m) * R);
+    rc = lv_work(c, 2 * b_st + b_n2c + b_info + 2 * b_vec + b_scr);
+    if (rc) return rc;
+    unsigned char* p = c->d_lvwork;
+    uint64_t* st_in = reinterpret_cast<uint64_t*>(p); p += b_st;
+    uint64_t* st_out = reinterpret_cast<uint64_t*>(p); p += b_st;
+    int32_t* n2c = reinterpret_cast<int32_t*>(p); p += b_n2c;
+    int32_t* info = reinterpret_cast<int32_t*>(p); p += b_info;
+    double* deg = reinterpret_cast<double*>(p); p += b_vec;
+    double* inr = reinterpret_cast<double*>(p); p += b_vec;
+    unsigned char* scratch = in_lds ? nullptr : p;
+    rc = upload(c, st_in, states_in, sizeof(uint64_t) * 6 * R);
+    if (rc) return rc;
+    launch_louvain_level0(c->d_lvA, (int)m, lv_gdeg(c), lv_diag(c), lv_total(c), (int)R, st_in, n2c, st_out, info, deg, inr,
+                          scratch, c->stream);
+    HIPCHK(hipGetLastError());
+    rc = download(c, node2com_out, n2c, sizeof(int32_t) * (size_t)(R * m));
+    if (!rc) rc = download(c, states_out, st_out, sizeof(uint64_t) * 6 * R);
+    if (!rc) rc = download(c, info_out, info, sizeof(int32_t) * 4 * R);
+    if (!rc) rc = download(c, degrees_out, deg, sizeof(double) * (size_t)(R * m));
+    if (!rc) rc = download(c, internals_out, inr, sizeof(double) * (size_t)(R * m));
+    return rc;
+}
+
+int hicmi_louvain_induced(hicmi_ctx* c, const int32_t* part, int64_t n_part, int64_t k, double* out)
+{
+    int rc = lv_check(c);
+    if (rc) return rc;
+    const int64_t m = c->lv_m;
+    if (n_part != m) return fail(HICMI_EINVAL, "partition of %lld nodes, graph of %lld", (long long)n_part, (long long)m);
+    if (!part || !out || k < 1 || k > m) return fail(HICMI_EINVAL, "bad arguments (need 1 <= k <= m)");
+    // members of every community in ascending node order (a counting sort of the partition)
+    std::vector<int32_t> moff((size_t)k + 1, 0), members((size_t)m);
+    for (int64_t i = 0; i < m; i++) {
+        if (part[i] < 0 || part[i] >= k) return fail(HICMI_EINVAL, "partition label outside [0, k)");
+        moff[(size_t)part[i] + 1]++;
+    }
+    for (int64_t b = 0; b < k; b++) moff[(size_t)b + 1] += moff[(size_t)b];
+    {
+        std::vector<int32_t> fill(moff.begin(), moff.end() - 1);
+        for (int64_t i = 0; i < m; i++) members[(size_t)fill[(size_t)part[i]]++] = (int32_t)i;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    const size_t b_mem = lv_align(sizeof(int32_t) * m), b_off = lv_align(sizeof(int32_t) * (k + 1)),
+                 b_agg = lv_align(sizeof(double) * m * k), b_B = lv_align(sizeof(double) * k * k);
+    rc = lv_work(c, b_mem + b_off + b_agg + b_B);
+    if (rc) return rc;
+    unsigned char* p = c->d_lvwork;
+    int32_t* d_mem = reinterpret_cast<int32_t*>(p); p += b_mem;
+    int32_t* d_off = reinterpret_cast<int32_t*>(p); p += b_off;
+    double* agg = reinterpret_cast<double*>(p); p += b_agg;
+    double* B = reinterpret_cast<double*>(p);
+    rc = upload(c, d_mem, members.data(), sizeof(int32_t) * (size_t)m);
+    if (!rc) rc = upload(c, d_off, moff.data(), sizeof(int32_t) * (size_t)(k + 1));
+    if (rc) return rc;
+    launch_louvain_induced(c->d_lvA, (int)m, d_mem, d_off, (int)k, agg, B, c->stream);
+    HIPCHK(hipGetLastError());
+    return download(c, out, B, sizeof(double) * (size_t)(k * k));
+}
+
+int hicmi_louvain_modularity(hicmi_ctx* c, const int32_t* parts, int64_t rounds, int64_t n_part, double* q_out)
+{
+    int rc = lv_check(c);
+    if (rc) return rc;
+    const int64_t m = c->lv_m, R = rounds;
+    if (n_part != m) return fail(HICMI_EINVAL, "partitions of %lld nodes, graph of %lld", (long long)n_part, (long long)m);
+    if (!parts || !q_out) return fail(HICMI_EINVAL, "NULL argument");
+    if (R < 1 || R > LOUVAIN_MAX_ROUNDS) return fail(HICMI_EINVAL, "rounds = %lld outside [1, %d]", (long long)R, LOUVAIN_MAX_ROUNDS);
+    for (int64_t i = 0; i < R * m; i++)
+        if (parts[i] < 0 || parts[i] >= m) return fail(HICMI_EINVAL, "partition label outside [0, m)");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t b_p = lv_align(sizeof(int32_t) * R * m), b_same = lv_align(sizeof(double) * R * m),
+                 b_acc = lv_align(sizeof(double) * 3 * R * m), b_q = lv_align(sizeof(double) * R);
+    rc = lv_work(c, b_p + b_same + b_acc + b_q);
+    if (rc) return rc;
+    unsigned char* p = c->d_lvwork;
+    int32_t* d_p = reinterpret_cast<int32_t*>(p); p += b_p;
+    double* same = reinterpret_cast<double*>(p); p += b_same;
+    double* acc = reinterpret_cast<double*>(p); p += b_acc;
+    double* q = reinterpret_cast<double*>(p);
+    rc = upload(c, d_p, parts, sizeof(int32_t) * (size_t)(R * m));
+    if (rc) return rc;
+    launch_louvain_score(c->d_lvA, (int)m, d_p, (int)R, lv_gdeg(c), lv_total(c), same, acc, q, c->stream);
+    HIPCHK(hipGetLastError());
+    return download(c, q_out, q, sizeof(double) * (size_t)R);
 }
 
 // ---------------------------------------------------------------------------------------------------

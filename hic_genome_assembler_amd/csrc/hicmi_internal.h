@@ -122,6 +122,7 @@ __device__ __forceinline__ double combine_leaves(int n_leaves, const double* lea
 // k_part1.hip
 void launch_row_sums(const double* C, int64_t ldc, int n, double* np_sum, double* seq_sum, int row_first, int row_stride,
                      hipStream_t s);
+void launch_pairwise_rows(const double* C, int64_t ldc, int len, int rows, double* out, hipStream_t s);
 void launch_compact(const double* src, int64_t ld_src, const int32_t* keep, int n_keep, double* dst, int64_t ld_dst,
                     hipStream_t s);
 void launch_widen_f32(const float* src, double* dst, int64_t cells, hipStream_t s);   // src = (float*)dst + cells
@@ -322,5 +323,23 @@ void launch_hmm_emission(const double* X, int64_t ld, int T, int D, const double
 void launch_hmm_fb(const double* L, int T, double* P, int D, double* alpha, double* beta, double* gam, double* hist, int it,
                    hipStream_t s);
 void launch_hmm_viterbi(const double* L, int T, const double* P, int D, uint8_t* bt, int32_t* states, hipStream_t s);
+
+// k_louvain.hip: level 0 of the Louvain tail (S2C:239-349, modularity.py).  The graph is m x m, leading dimension m.
+static constexpr int LOUVAIN_MAX_M = 16384;
+static constexpr int LOUVAIN_MAX_ROUNDS = 1024;
+// per-round work arrays of the level-0 sweep: 4 fp64 and 8 int32 arrays of m
+__host__ __device__ inline size_t louvain_round_bytes(int m) { return (size_t)m * (4 * sizeof(double) + 8 * sizeof(int)); }
+int  louvain_level0_lds_max();                            // the most of them one workgroup keeps in LDS
+void launch_louvain_graph(const double* C, int64_t ldc, const int32_t* rows, const double* np_sum, const double* seq_sum, int m,
+                          double* A, hipStream_t s);
+void launch_louvain_status(const double* A, int m, double* diag, double* rowsum, double* chunk, double* dsum, double* gdeg,
+                           double* total, hipStream_t s);
+void launch_louvain_level0(const double* A, int m, const double* gdeg, const double* loops, const double* total, int rounds,
+                           const uint64_t* st_in, int32_t* n2c_out, uint64_t* st_out, int32_t* info, double* deg_out,
+                           double* int_out, unsigned char* scratch, hipStream_t s);
+void launch_louvain_induced(const double* A, int m, const int32_t* members, const int32_t* moff, int k, double* rowagg,
+                            double* B, hipStream_t s);
+void launch_louvain_score(const double* A, int m, const int32_t* parts, int rounds, const double* gdeg, const double* total,
+                          double* same, double* acc, double* q, hipStream_t s);
 
 }  // namespace hicmi

@@ -91,6 +91,14 @@ void launch_row_sums(const double* C, int64_t ldc, int n, double* np_sum, double
     hipLaunchKernelGGL(k_row_sums_seq, dim3((mine + 63) / 64), dim3(64), 0, s, C, ldc, n, seq_sum, row_first, row_stride);
 }
 
+// NumPy's pairwise sum of `rows` runs of `len` elements, run r starting at C + r * ldc (one contiguous run of an
+// arbitrary array: a row, a diagonal copy, an 8192-element chunk of a flattened matrix)
+void launch_pairwise_rows(const double* C, int64_t ldc, int len, int rows, double* out, hipStream_t s)
+{
+    if (rows <= 0) return;
+    hipLaunchKernelGGL(k_row_sums_np, dim3(rows), dim3(64), 0, s, C, ldc, len, out, 0, 1);
+}
+
 // removeRows (S2C:100-136): dst = src[keep][:, keep]
 __global__ __launch_bounds__(256) void k_compact(const double* __restrict__ src, int64_t ld_src,
                                                  const int32_t* __restrict__ keep, int n_keep,

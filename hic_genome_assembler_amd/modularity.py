@@ -140,10 +140,14 @@ def best_partition(A, rng):
         return np.arange(n)
     st = _Status(A.copy())
     _one_level(st, rng)
-    mod = st.modularity()
     part = _renumber(st.node2com)
+    return upper_levels(_induced(A, part), st.modularity(), part, rng)
+
+
+def upper_levels(cur, mod, part, rng):
+    """best_partition after level 0: ``part`` = level 0's renumbered partition, ``mod`` its st.modularity(), ``cur`` =
+    _induced(A, part) and ``rng`` the generator as level 0 left it.  Levels >= 1 and their composition."""
     levels = [part]
-    cur = _induced(A, part)
     while True:
         st = _Status(cur)
         _one_level(st, rng)
@@ -192,6 +196,61 @@ def modularity_rounds(A, louvain_rounds=1, seed=None):
     return best, best_mod_score
 
 
+def louvain_device_enabled():
+    """The device level 0 is opt-in (HICMI_LOUVAIN_DEVICE=1); without it every output comes from the host code above."""
+    return os.environ.get("HICMI_LOUVAIN_DEVICE", "") == "1"
+
+
+def _status_modularity(node2com, degrees, internals, links):
+    """_Status.modularity() of a status given by its arrays (NumPy's float64 ** 2 is libm pow, not x * x)."""
+    if links <= 0:
+        return 0.0
+    res = 0.0
+    for com in np.unique(node2com):
+        res += internals[com] / links - (degrees[com] / (2.0 * links)) ** 2
+    return float(res)
+
+
+def modularity_rounds_device(ctx, louvain_rounds=1, seed=None, stats=None):
+    """modularity_rounds on the graph already on the device (Context.louvain_graph / louvain_set_graph): level 0 of every
+    round in one launch, levels >= 1 on the host from the generator state level 0 handed back, the score on the device.
+    The same seeds, the same strict '>' best-of-rounds and the same printed lines as modularity_rounds."""
+    if seed is None:
+        seed = int(os.environ.get("HICMI_LOUVAIN_SEED", "0"))
+    t0 = time.perf_counter()
+    rngs = [np.random.default_rng([seed, i]) for i in range(louvain_rounds)]
+    n2c, states, info, degrees, internals = ctx.louvain_level0([r.bit_generator.state for r in rngs])
+    t1 = time.perf_counter()
+    _A, _gdeg, links = ctx.louvain_get_graph(with_matrix=False)
+    parts = []
+    for i in range(louvain_rounds):
+        part0 = _renumber(n2c[i])
+        rng = rngs[i]
+        rng.bit_generator.state = states[i]
+        mod0 = _status_modularity(n2c[i], degrees[i], internals[i], links)
+        cur = ctx.louvain_induced(part0, int(part0.max()) + 1)
+        parts.append(upper_levels(cur, mod0, part0, rng))
+    t2 = time.perf_counter()
+    scores = ctx.louvain_modularity(np.stack(parts).astype(np.int32))
+    t3 = time.perf_counter()
+    if stats is not None:
+        stats.update(level0_ms=(t1 - t0) * 1e3, upper_ms=(t2 - t1) * 1e3, score_ms=(t3 - t2) * 1e3,
+                     passes=info[:, 0].tolist(), tie_replays=info[:, 1].tolist(), near_threshold=info[:, 2].tolist())
+    if int(info[:, 2].sum()):
+        print("- WARNING - a level-0 pass gain fell within 1e-12 of the 1e-7 threshold; the device and host sweeps may "
+              "stop after different passes (DESIGN.md section 9b)")
+    best_mod_score, best = -2.0, None
+    for i in range(louvain_rounds):
+        mod_score = float(scores[i])
+        if np.isnan(mod_score):
+            raise ValueError("A graph without link has an undefined modularity")
+        if mod_score > best_mod_score:
+            borg = best_mod_score
+            best_mod_score, best = mod_score, parts[i]
+            print("Previous best modularity score {}, Current best found {}, Louvain round {}".format(borg, mod_score, i + 1))
+    return best, best_mod_score
+
+
 def log_transform(similarity):
     """logTransformMatrix(matrix, logBase=10) (S2C:165-183): log10(v + 1) for non-zero cells, 0 otherwise."""
     s = np.asarray(similarity, dtype=np.float64)
@@ -201,10 +260,12 @@ def log_transform(similarity):
     return out
 
 
-def modularity_remaining_data(log_similarity_tail, binList, cutIndices, n_rounds=20, seed=None):
+def modularity_remaining_data(log_similarity_tail, binList, cutIndices, n_rounds=20, seed=None, ctx=None):
     """S2C:263-349 on the tail sub-matrix (rows/columns from the last cut index on, in the current order).
     Returns (new_order, cutIndices): the permutation of ``binList`` positions to apply - head unchanged, tail
-    grouped by community, largest community first - and the extended cut indices."""
+    grouped by community, largest community first - and the extended cut indices.
+    ``ctx``: a Context holding the tail's graph (Context.louvain_graph); ``log_similarity_tail`` is then unused and the
+    rounds run through modularity_rounds_device."""
     startTime = time.time()
     cutIndices = list(cutIndices)
     if len(cutIndices) == 0:
@@ -214,19 +275,23 @@ def modularity_remaining_data(log_similarity_tail, binList, cutIndices, n_rounds
     cutIndices = sorted(cutIndices)
     startIndex = cutIndices[-1]
     n_total = len(binList)
-    A = graph_weights(log_similarity_tail)
-    if len(A) != n_total - startIndex:
+    A = graph_weights(log_similarity_tail) if ctx is None else None
+    m = len(A) if ctx is None else ctx._lv_m
+    if m != n_total - startIndex:
         raise ValueError("tail matrix does not match binList[startIndex:]")
     print("- Maximizing so-called modularity...")
-    print("- Graph created with " + str(len(A)) + " nodes, and " + str(len(A) * (len(A) - 1) // 2 + len(A)) + " edges")
+    print("- Graph created with " + str(m) + " nodes, and " + str(m * (m - 1) // 2 + m) + " edges")
     print("- Performing " + str(n_rounds) + " rounds of the louvain method...")
-    node_to_group, _mod_score = modularity_rounds(A, louvain_rounds=n_rounds, seed=seed)
+    if ctx is None:
+        node_to_group, _mod_score = modularity_rounds(A, louvain_rounds=n_rounds, seed=seed)
+    else:
+        node_to_group, _mod_score = modularity_rounds_device(ctx, louvain_rounds=n_rounds, seed=seed)
     group_sizes = collections.Counter(node_to_group.tolist())
     group_count = len(group_sizes)
     remaining_groups = [k for k, _v in sorted(group_sizes.items(), key=lambda kv: kv[1], reverse=True)]
     remaining_order = []
     for rg in remaining_groups:
-        remaining_order += [startIndex + i for i in range(len(A)) if node_to_group[i] == rg]
+        remaining_order += [startIndex + i for i in range(m) if node_to_group[i] == rg]
         cutIndices.append(cutIndices[-1] + group_sizes[rg])
     new_order = list(range(startIndex)) + remaining_order
     if cutIndices[0] == 0:

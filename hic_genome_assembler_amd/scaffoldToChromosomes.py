@@ -15,6 +15,8 @@ heavy step is a hand-written gfx950 kernel reached through the C ABI of include/
   find_matrix_pvalue_breakpoints S2C:413-511  hicmi_cut_scan (+ host window logic)
   filter_noisy_breakpoints     S2C:553-727    hicmi_filter_scan (+ host control flow)
   hmmChromosomes (hmm = True)  S2C:730-942    hicmi_hmm_* (k_hmm.hip) + host control flow; opt-in: HICMI_HMM=1
+  modularity_remaining_data    S2C:263-349    modularity.py; level 0 on hicmi_louvain_* (k_louvain.hip) with
+                                              HICMI_LOUVAIN_DEVICE=1
 
 Host control flow (loops over cut candidates, file formats, scaffold voting) is restated here in
 Python because its decisions are sequential and tiny.  There is no CPU fallback for the kernels.
@@ -133,6 +135,21 @@ def convertMatrix(adjacencyMatrix: DeviceMatrix, binList, distance=True, similar
     elif similarity is True:
         adjacencyMatrix.kind = "similarity"
     return adjacencyMatrix
+
+
+def logTransformMatrix(matrix: DeviceMatrix, logBase=10, reverse=False):
+    """S2C:165-183: log10(v + 1) of every non-zero cell (``reverse=True``: back again).  The device kernels that read
+    the log-transformed similarity (k_hmm_obs, k_lv_graph) apply it themselves, so this only records the stage:
+    similarity <-> log-similarity.  Other stages and bases are not supported."""
+    if not isinstance(matrix, DeviceMatrix):
+        raise TypeError("logTransformMatrix expects a DeviceMatrix")
+    if logBase != 10:
+        raise ValueError("logTransformMatrix supports logBase=10 only (got %r)" % (logBase,))
+    frm, to = ("log-similarity", "similarity") if reverse else ("similarity", "log-similarity")
+    if matrix.kind != frm:
+        raise ValueError("logTransformMatrix(reverse=%r) expects the %s stage, not %s" % (reverse, frm, matrix.kind))
+    matrix.kind = to
+    return matrix
 
 
 def averageClusterNodes(adjacencyMatrix: DeviceMatrix, nodeLabels, noPlot=True, meanwhile=None, want_ivl=True):
@@ -372,6 +389,33 @@ def filter_noisy_breakpoints(argsorted_mat: RankMatrix, original_inds, psig=.05)
     print("- Original cut indices {}".format(list(original_inds)))
     print("- Filtered cut indices {}".format(out))
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+def _louvain_tail(adjMat: DeviceMatrix, binList, cutIndices, n_rounds):
+    """modularity.modularity_remaining_data on the bins after the last cut index: (new_order, cutIndices).  With
+    HICMI_LOUVAIN_DEVICE=1 the graph is built on the device from the resident matrix and level 0 runs there; otherwise
+    the tail's similarity comes down and the host restatement runs."""
+    start = sorted(cutIndices)[-1] if len(cutIndices) else 0
+    order = adjMat.order if adjMat.order is not None else list(range(adjMat.n))
+    tail_rows = list(order[start:])
+    if louvain.louvain_device_enabled():
+        adjMat.ctx.louvain_graph(tail_rows)
+        return louvain.modularity_remaining_data(None, binList, cutIndices, n_rounds=n_rounds, ctx=adjMat.ctx)
+    sim_tail = adjMat.ctx.plot_downsample(2, tail_rows, len(tail_rows))
+    return louvain.modularity_remaining_data(louvain.log_transform(sim_tail), binList, cutIndices, n_rounds=n_rounds)
+
+
+def modularity_remaining_data(adjacencyMatrix: DeviceMatrix, binList, cutIndices, n_rounds=20):
+    """S2C:263-349: partition the bins after the last cut index by modularity (the best of ``n_rounds`` Louvain runs)
+    and reorder that tail by community, largest first.  ``adjacencyMatrix``: a DeviceMatrix at its log-similarity stage
+    (logTransformMatrix).  Returns (adjacencyMatrix, binList, cutIndices), both reordered, as the reference does."""
+    if not isinstance(adjacencyMatrix, DeviceMatrix) or adjacencyMatrix.kind != "log-similarity":
+        raise ValueError("modularity_remaining_data expects a DeviceMatrix at its log-similarity stage "
+                         "(convertMatrix(similarity=True), then logTransformMatrix)")
+    new_order, cutIndices = _louvain_tail(adjacencyMatrix, binList, cutIndices, n_rounds)
+    adjacencyMatrix, binList = reorderMatrix(adjacencyMatrix, binList, new_order)
+    return adjacencyMatrix, binList, cutIndices
 
 
 # ------------------------------------------------------------------------------------------------
@@ -957,13 +1001,10 @@ def runResident(adjMat: DeviceMatrix, binList, hicProScaffSizeFile, dendrogramOr
             mark("filter scans")
         if modularity is not False and modularity > 0.0:
             # S2C:1148-1152: Louvain on log10(similarity + 1) of the bins after the last cut index (modularity.py:
-            # seeded restatement of python-louvain; the cells come from the device in the current order)
+            # seeded restatement of python-louvain; level 0 on the device with HICMI_LOUVAIN_DEVICE=1)
             start = sorted(cutIndices)[-1] if len(cutIndices) else 0
-            tail_rows = list(adjMat.order[start:])
-            if len(tail_rows) > 0:
-                sim_tail = adjMat.ctx.plot_downsample(2, tail_rows, len(tail_rows))
-                new_order, cutIndices = louvain.modularity_remaining_data(louvain.log_transform(sim_tail), binList,
-                                                                          cutIndices, n_rounds=louvainRounds)
+            if len(adjMat.order) - start > 0:
+                new_order, cutIndices = _louvain_tail(adjMat, binList, cutIndices, louvainRounds)
                 adjMat, binList = reorderMatrix(adjMat, binList, new_order)
         writer.submit(writeBinGroupingsToFile, list(cutIndices), list(binList), binGroupFile, prep["bin_lines"], deferred=True)
         binGroups = _bin_group_pairs(cutIndices, binList, prep["pairs"])

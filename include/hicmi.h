@@ -332,6 +332,35 @@ int hicmi_hmm_fit(hicmi_ctx *ctx, const double *startprob, double *means, double
 int hicmi_hmm_decode(hicmi_ctx *ctx, const double *startprob, const double *means, const double *covars,
                      const double *transmat, int32_t *states_out);
 
+/* ---- Part 1: Louvain tail (modularity > 0, S2C:239-349) ---------------------------------------------
+ * modularity_remaining_data (S2C:263-349) partitions the bins after the last cut index with the best of louvainRounds
+ * randomised Louvain runs (S2C:239-262), restated with a seeded generator in modularity.py.  These entry points run
+ * level 0 of modularity.best_partition for all rounds on the device; the host keeps levels >= 1.
+ * The graph A (m x m, m <= 16384) lives in the context.
+ *
+ * hicmi_louvain_graph: A = graph_weights(log_transform(similarity tail)) (modularity.py:32-37, 214-220; S2C:285-297):
+ * A[i][j] = log10(sim + 1) (0 where sim == 0) of row rows[max(i, j)] and column rows[min(i, j)] of the similarity matrix
+ * (S2C:149).  Needs hicmi_row_sums.  Both graph calls also compute _Status's total_weight and gdegrees (modularity.py:43-50)
+ * with NumPy's pairwise sums.
+ * hicmi_louvain_set_graph / hicmi_louvain_get_graph: an arbitrary symmetric A in; A, gdegrees (m) and total_weight out
+ * (each output may be NULL). */
+int hicmi_louvain_graph(hicmi_ctx *ctx, const int32_t *rows, int64_t m);
+int hicmi_louvain_set_graph(hicmi_ctx *ctx, const double *A, int64_t m);
+int hicmi_louvain_get_graph(hicmi_ctx *ctx, double *A_out, double *gdegrees_out, double *total_weight_out);
+/* modularity._one_level(_Status(A), rng) (modularity.py:65-112) for `rounds` independent generators, one workgroup each,
+ * bit for bit.  states_in / states_out: 6 uint64 per round - numpy PCG64 state low, high 64 bits, inc low, high,
+ * has_uint32, uinteger (rng.bit_generator.state).  node2com_out, degrees_out, internals_out: rounds x m (the _Status
+ * after level 0).  info_out: 4 int32 per round - passes, tie replays, passes whose gain was within 1e-12 of the 1e-7
+ * threshold, 0.  More than 1024 rounds: HICMI_EINVAL; m > 16384: HICMI_EUNSUPPORTED (at the graph call). */
+int hicmi_louvain_level0(hicmi_ctx *ctx, int64_t rounds, const uint64_t *states_in, int32_t *node2com_out,
+                         uint64_t *states_out, int32_t *info_out, double *degrees_out, double *internals_out);
+/* modularity._induced(A, part) (modularity.py:124-134): the k x k community graph of part (m labels in [0, k)).
+ * hicmi_louvain_modularity: modularity.modularity(part, A) (modularity.py:165-180) of `rounds` partitions (rounds x m,
+ * labels in [0, m)).  m must be the graph's.  Both sum in a fixed order of their own: within 1e-12 of the host's BLAS
+ * products. */
+int hicmi_louvain_induced(hicmi_ctx *ctx, const int32_t *part, int64_t m, int64_t k, double *out);
+int hicmi_louvain_modularity(hicmi_ctx *ctx, const int32_t *parts, int64_t rounds, int64_t m, double *q_out);
+
 /* ---- timing ----------------------------------------------------------------------------------
  * Accumulated device time (HIP events on the context stream) per kernel family since the last
  * reset, for bench.py's roofline object.  names_out: caller buffer receiving ';'-separated names;
