@@ -58,6 +58,7 @@ struct TimedRegion { int fam; hipEvent_t a, b; };
 struct hicmi_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
+    int probed_xcc = 0;                  // the lowest XCD id of the device (nnchain_probe_xcc): the nn-chain's default XCD
     // contacts
     int64_t n = 0, ldc = 0;
     double* dC = nullptr;
@@ -331,6 +332,7 @@ int hicmi_create(int device, hicmi_ctx** out)
     c->device = device;
     hipError_t se = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (se != hipSuccess) { delete c; return fail(HICMI_EHIP, "hipStreamCreate: %s", hipGetErrorString(se)); }
+    c->probed_xcc = nnchain_probe_xcc(c->stream);
     *out = c;
     return HICMI_OK;
 }
@@ -619,7 +621,7 @@ static int ensure_rank_buffers(hicmi_ctx* c, int64_t n, int64_t ldr, bool bitoni
 // free one) and notes which rows hold equal keys, and where; hicmi_rank_matrix then only relabels (k_rank_relabel, ~0.5 ms
 // at 16k), and finishes the rows with equal keys (sparse maps, fp32 contacts: possibly all of them) with a sort of
 // 32-bit (run, leaf position) keys - k_sort_tied.hip.  HICMI_NO_PRESORT=1 disables.
-static int start_presort(hicmi_ctx* c)
+static int start_presort(hicmi_ctx* c, int chain_xcc)
 {
     const bool off = getenv("HICMI_NO_PRESORT") != nullptr || getenv("HICMI_SORT_RADIX") != nullptr
                      || getenv("HICMI_SORT_LDS") != nullptr;
@@ -675,7 +677,7 @@ static int start_presort(hicmi_ctx* c)
         x.tie_limit = (unsigned)n;                                 // (never gives up: tied rows are finished by k_rank_rows_tied)
         x.tie_bits = c->d_tie_bits; x.ld_bits = ld_bits;
         x.max_workgroups = 192;                                    // (the chain: up to 64 single-wave workgroups, one CU each)
-        x.avoid_xcc = nnchain_local_xcc((int)n);                   // ... all on one XCD, which this kernel's workgroups leave alone
+        x.avoid_xcc = chain_xcc;                                   // ... all on one XCD, which this kernel's workgroups leave alone
         x.row_counter = reinterpret_cast<unsigned*>(c->d_ties) + 1;     // (zeroed with the tie count just above)
         if (getenv("HICMI_TEST_PRESORT_ALL_LEAVE")) x.avoid_xcc = -2;      // test hook: every workgroup behaves as if it were on that XCD
         c->presort_dealt = x.avoid_xcc >= 0 || x.avoid_xcc == -2;
@@ -730,24 +732,21 @@ int hicmi_upgma(hicmi_ctx* c, double* Z_out, int32_t* leaves_out)
     // The pre-sort runs beside the chain on the second stream - from the moment the chain's FIRST cache pass (k_nn_rowmin over
     // the whole matrix, the one full-chip pass the chain has) is queued: started right after k_build_w the pre-sort's 192
     // big workgroups shared the CUs with that pass and stretched it from 0.5 to 2.4 ms at 16k, from 2 to 9.8 ms at 32k.
+    const NNChainOptions nn_opt = nnchain_options(c->probed_xcc);
     int presort_rc = HICMI_OK;
     bool presort_started = false;
-    auto presort_now = [&] { if (!presort_started) { presort_started = true; presort_rc = start_presort(c); } };
+    auto presort_now = [&] {
+        if (!presort_started) { presort_started = true; presort_rc = start_presort(c, nnchain_local_xcc(nn_opt, (int)n)); }
+    };
     mark("build_w queued");
     // The nn-chain.  Algorithmic bytes: 8 B x (sum over row scans of the live columns + 3 x sum over merges
     // of the live columns), with the scans counted by the kernels themselves (a scan the neighbour cache answers moves
     // nothing); the merge term is 3 * 8 * sum_{k=0}^{n-2} (n - k).
-    const bool prof_on = getenv("HICMI_NNCHAIN_PROFILE") != nullptr;
-    // merges between two column flushes = merges per epoch launch.  Every row a merge reads is patched at the columns
-    // whose writes are still deferred, so a merge's cost grows with the list: 1024 -> 256 merges per epoch took the chain
-    // from 124.8 to 118.0 ms at 16k and from 282.5 to 272.4 ms at 32k (128: no further gain - ~40 us of launches per epoch)
-    const char* cap = getenv("HICMI_NNCHAIN_DCAP");
     struct { int state[16]; unsigned long long prof[8]; unsigned char mail[1152]; unsigned long long detail[32]; } nn;   // the head of the workspace
     for (int attempt = 0; attempt < 3; attempt++) {
         {
             Timed t(c, F_NNCHAIN, 0.0);
-            int epochs = launch_nnchain(c->dW, c->dW2, ldw, (int)n, c->d_chain, c->d_zraw, c->d_size, prof_on,
-                                        cap ? atoi(cap) : 256, getenv("HICMI_NNCHAIN_NO_COMPACT") == nullptr, attempt, c->stream,
+            int epochs = launch_nnchain(c->dW, c->dW2, ldw, (int)n, c->d_chain, c->d_zraw, c->d_size, nn_opt, attempt, c->stream,
                                         presort_now);
             presort_now();                                         // (whatever path the chain took)
             if (presort_rc) return presort_rc;
@@ -778,7 +777,7 @@ int hicmi_upgma(hicmi_ctx* c, double* Z_out, int32_t* leaves_out)
         if (rc_dl) return rc_dl;
     }
     mark("merge records to the host");
-    if (prof_on) {
+    if (nn_opt.profile) {
         const unsigned long long* pr = nn.prof;
         fprintf(stderr, "[hicmi] nnchain phases (ms @100MHz): bookkeeping %.2f scan %.2f pick %.2f merge %.2f update %.2f; "
                         "%llu scans (%.2f per merge), %llu cached steps\n",

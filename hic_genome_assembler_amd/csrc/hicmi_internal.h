@@ -129,8 +129,26 @@ void launch_widen_f32(const float* src, double* dst, int64_t cells, hipStream_t 
 void launch_build_w(const double* C, int64_t ldc, const double* np_sum, int n, double* W, int64_t ldw, hipStream_t s);
 // k_nnchain.hip
 size_t nnchain_workspace_bytes(int n);
-int launch_nnchain(double* W, double* W2, int64_t ldw, int n, int* chain, double* zraw, void* workspace, bool profile,
-                   int dcap, bool compact, int fallback, hipStream_t s, const std::function<void()>& after_first_rowmin = nullptr);
+// Every HICMI_NNCHAIN_* switch, read once per hicmi_upgma call (README.md lists them)
+struct NNChainOptions {
+    bool profile = false;                     // _PROFILE: phase time stamps
+    int dcap = 256;                           // _DCAP: merges per epoch of the 1024-lane kernels (clamped to 1 .. 1024)
+    bool dcap_forced = false;                 //   ... and of the one-wave kernel's epochs too
+    bool compact = true;                      // _NO_COMPACT turns compaction off
+    bool wgs_set = false; int wgs = 0;        // _WGS: the 1024-lane kernels at this width (1, 2, 4, 8, 16) for every epoch
+    bool plain = false;                       // _PLAIN: the cache-less k_nn_epoch
+    bool gsize = false;                       // _GSIZE: k_nn_epoch_mwc's sizes-in-global-memory form at every width
+    bool w1 = true;                           // _W1=0: not the one-wave kernel
+    int w1_s = 0;                             // _W1_S: its number of slices (0: planned)
+    int w1_cols = 0;                          // _W1_COLS: the columns per slice its plan aims at (at least 64)
+    int w1_maxs = 0;                          // _W1_MAXS: its largest number of slices
+    int xcc = -1;                             // _XCD: the XCD its parties claim (off: -1; 8: one that does not exist); unset: probed
+    int test_late = 0, test_diverge = 0, test_rollcall = 0;     // _TEST_LATE, _TEST_DIVERGE, _TEST_ROLLCALL: test hooks
+};
+NNChainOptions nnchain_options(int probed_xcc);
+int nnchain_probe_xcc(hipStream_t s);       // the lowest XCC id the device's workgroups report (once per device; waits on s)
+int launch_nnchain(double* W, double* W2, int64_t ldw, int n, int* chain, double* zraw, void* workspace, const NNChainOptions& o,
+                   int fallback, hipStream_t s, const std::function<void()>& after_first_rowmin = nullptr);
                                               // returns the number of epoch launches; fallback: 0, 1 (spread out), 2 (one workgroup);
                                               // after_first_rowmin: called once, when the first epoch's cache pass is queued
 void launch_selftest_division(unsigned long long seed, int blocks, int iters, unsigned long long* d_mismatches, hipStream_t s);
@@ -201,7 +219,7 @@ struct SortExtras {                        // optional modes of launch_sort_rows
 // s_getreg operand of HW_REG_XCC_ID (id 20), bits 3:0: which of the 8 XCDs a wave runs on
 static constexpr int GETREG_XCC_ID = 20 | (0 << 6) | (3 << 11);
 // The XCD the nn-chain's one-wave kernel claims for itself (k_nnchain.hip), or -1 when it runs spread over all of them
-int nnchain_local_xcc(int n);
+int nnchain_local_xcc(const NNChainOptions& o, int n);
 void launch_sort_rows(const double* C, int64_t ldc, const int32_t* order, const int32_t* inv, const double* np_sum,
                       const double* seq_sum, int n, void* scratch, uint16_t* R, int64_t ldr, int row_first, int row_stride,
                       hipStream_t s, const SortExtras& x = SortExtras());

@@ -27,7 +27,7 @@ namespace hicmi {
 
 static constexpr int NN_THREADS = 1024;
 static constexpr int NN_DMAX = 1024;                     // at most one dirty entry per lane
-static constexpr int NN_MAXWG = 16;                      // workgroups of the column-sliced chain (k_nn_epoch_mw / _mwc)
+static constexpr int NN_MAXWG = 16;                      // workgroups of the column-sliced chain (k_nn_epoch_mwc)
 static constexpr int NN_HEAD = 1536;                     // state 64 B, counters 64 B, hand-off slot 128 B, mailboxes 1024 B, profile detail 256 B
 static constexpr int NN_W1_MAXS = 64;                    // column slices (single-wave workgroups) of k_nn_epoch_w1
 static constexpr int NN_W1_MAIL = 2 * NN_W1_MAXS * 2 * NN_W1_MAXS * 16;   // its mailboxes: 2 parities x 64 readers x (2 slots x 64 writers) x 16 bytes
@@ -209,7 +209,7 @@ struct NNWorkspace {
                                 // [11] test: step whose record replica 1 falsifies
     unsigned long long* prof;   // [0..4] phase totals (100 MHz ticks), [5] columns visited by row scans, [6] row scans,
                                 // [7] chain steps answered by the neighbour cache
-    void* mail;                 // k_nn_epoch_mw: 2 x NN_MAXWG 16-byte mailbox slots; k_nn_epoch_mwc: two slots per workgroup
+    void* mail;                 // k_nn_epoch_mwc: 2 parities x NN_MAXWG workgroups x 2 slots of 16 bytes
     uint32_t* alive;            // nwords
     uint16_t* size;             // n
     int* gtime;                 // n: dirty time stamp of a slot in the finished epoch, -1 = clean
@@ -220,7 +220,7 @@ struct NNWorkspace {
     int* oldidx;                // n: scratch of the compaction (new slot -> old slot)
     double* nnval;              // n: neighbour cache - distance to the nearest live cluster of each slot
     uint32_t* nnc;              // n: neighbour cache - its slot (low 16 bits, 0xffff = unknown) | tie flag << 16
-    double* rec;                // NN_MAXWG x NN_DMAX x 4: the merges of the last epoch as every replica of k_nn_epoch_mw saw them
+    double* rec;                // NN_MAXWG x NN_DMAX x 4: the merges of the last epoch as every replica of k_nn_epoch_mwc saw them
     int* size_rep;              // NN_W1_MAXS x n: cluster sizes, one private copy per replica of k_nn_epoch_w1 and of
                                 // k_nn_epoch_mwc<.., .., true> (rows beyond 32,768 columns: the sizes do not fit the LDS beside the cache)
     void* mailw;                // k_nn_epoch_w1: NN_W1_MAIL bytes of mailboxes, then NN_W1_MAXS 8-byte merge-record hashes, then 16 bytes
@@ -786,9 +786,7 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_epoch_nc(double* __restrict__
     }
 }
 
-// ---- the same chain on several workgroups: protocol and helpers ------------------------------------------
-// (k_nn_epoch_mw, the cache-less sliced kernel of round 1 this text was written for, is gone: k_nn_epoch_mwc and
-//  k_nn_epoch_w1 below keep its protocol.)
+// ---- the same chain on several workgroups: protocol and helpers (k_nn_epoch_mwc, k_nn_epoch_w1) ----------------------
 // A lone CU streams a row at ~77 GB/s: at 16k bins a 128 KB scan is two thirds transfer, one third latency.
 // Here NWG workgroups (one CU each, any XCD) run the SAME chain as replicated state machines: each keeps the
 // full LDS state (liveness, sizes, dirty list, chain) and takes every decision itself, but streams only ITS
@@ -800,10 +798,7 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_epoch_nc(double* __restrict__
 // double-buffered by the parity of the sequence number: a workgroup can be at most one exchange ahead.
 // Visibility of matrix bytes: a workgroup plainly loads only columns of its own slice, which only it ever
 // writes (sc1 stores); every element that may lie in another slice - dirty partners' W[d][x], d(x, prev) - is
-// read with an sc1 load, and was written before the writer's previous exchange.  The single element that is
-// needed BEFORE an exchange has happened - W[y'][z] for the cluster y' merged a moment ago and the row z the
-// next scan visits - is handed from the owner of column z (which computes it in its update) to the owner of
-// column y' (the only reader: it lists y' among its dirty candidates) through a tagged 16-byte slot of its own.
+// read with an sc1 load, and was written before the writer's previous exchange.
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // (s_nop: a vector-memory store of more than 64 bits must not be followed at once by a vector instruction that overwrites
 //  its data registers; the compiler pads its own stores, but it does not look inside inline assembly - seen as wrong
@@ -828,11 +823,6 @@ __device__ __forceinline__ u32x4 ld16_sc1(const void* p)
     asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
     return v;
 }
-__device__ __forceinline__ double ld8_sc1(const double* p)
-{
-    return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED,
-                                                              __HIP_MEMORY_SCOPE_AGENT));
-}
 __device__ __forceinline__ void st8_sc1(double* p, double v)
 {
     __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED,
@@ -841,12 +831,25 @@ __device__ __forceinline__ void st8_sc1(double* p, double v)
 
 // Streaming loads of the workgroup's own slice are sc1 too: plain (and nontemporal) re-loads of a line this
 // workgroup had itself rewritten with sc1 stores returned pre-update values now and then (observed on gfx950;
-// with every load sc1 the chain is bit-exact and repeatable).  Issued in pairs from inline assembly - the
-// compiler's wait-count pass does not see them - and drained by one s_waitcnt that also "produces" the registers,
-// so no use can be scheduled ahead of it.
-#define NN_LD16_SC1(reg, ptr) asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(reg) : "v"(ptr) : "memory")
-#define NN_DRAIN2(a, b) asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b)::"memory")
-#define NN_DRAIN4(a, b, c, d) asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)::"memory")
+// with every load sc1 the chain is bit-exact and repeatable).
+// Every load of the chain kernels is COMPILER-VISIBLE - its wait-count pass tracks it: the streamed pairs are raw buffer
+// loads (buffer_load_dwordx4 ... offen, sc1 where the row may have been stored by this or another workgroup; a row is one
+// buffer resource, so lanes beyond its end read zeros instead of needing a branch), the gathered values relaxed
+// agent-scope atomic loads (global_load ... sc1).  A load issued from inline assembly and waited for in a LATER statement
+// pins the order but not the register allocation: the compiler takes the destination as written when the first
+// statement ends and may copy or reuse it before the data lands (seen: a fault at 16 pairs per lane).  Where a pass
+// issues its loads before other work, NN_FENCE keeps them ahead of that work and NN_KEEP makes every use come after it.
+#define NN_FENCE() asm volatile("" ::: "memory")
+#define NN_KEEP(reg) asm volatile("" : "+v"(reg))
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t nn_row(const double* row, int cols)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(row), 0, cols * 8, 0x00020000);
+}
+__device__ __forceinline__ u32x4 nn_ld16(__amdgpu_buffer_rsrc_t r, int byte_offset) { return __builtin_amdgcn_raw_buffer_load_b128(r, byte_offset, 0, 16); }   // (aux 16: sc1)
+__device__ __forceinline__ unsigned long long nn_ld8(const double* p)
+{
+    return __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 __device__ __forceinline__ double2 mw_pair(u32x4 r)
 {
     double2 v;
@@ -880,7 +883,7 @@ __global__ __launch_bounds__(256) void k_nn_check_replicas(NNWorkspace w, int nw
 // ---- column slices AND the neighbour cache: k_nn_epoch_mwc ---------------------------------------------------------
 // A lone CU ingests a row at ~55-77 GB/s whatever the loop looks like (the limit is the CU's outstanding misses), so
 // with the scans the cache leaves (~1.3 per merge) and the update, a merge on one workgroup still streams ~3.7 rows.
-// Here NWG workgroups are replicas of ONE state machine, as in k_nn_epoch_mw: each streams its column slice only.
+// Here NWG workgroups are replicas of ONE state machine (protocol above): each streams its column slice only.
 // On top of that:
 //  * the neighbour cache (nnidx, tie flags) is replicated in every workgroup's LDS and kept identical: scan results
 //    and the merged row's minimum arrive through the exchanges; "neighbour merged -> unknown" is applied by every
@@ -890,16 +893,9 @@ __global__ __launch_bounds__(256) void k_nn_check_replicas(NNWorkspace w, int nw
 //    Cached distances (nnval) are private to the owner of the column: nobody else reads them.
 //  * the scan that follows almost every merge - the new chain top `a`, whose neighbour was one of the merged pair -
 //    is FUSED into the update pass: the pass streams rows x, y and a together; d(a, y') is the element of the new row
-//    that the owner of column a computes anyway, so the hand-off slot of k_nn_epoch_mw is not needed, and one
+//    that the owner of column a computes anyway, so no value has to cross workgroups before an exchange, and one
 //    exchange carries both the merged row's minimum and row a's.
-// Per merge: ~1.3 passes over a slice and ~1.3 exchanges (k_nn_epoch_mw: 3.9 passes, 2.9 exchanges).
-#define NN_LD16(reg, ptr) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(reg) : "v"(ptr) : "memory")
-#define NN_DRAIN8(a, b, c, d, e, f, g, h) \
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h)::"memory")
-
-#define NN_LD8_SC1(reg, ptr) asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(reg) : "v"(ptr) : "memory")
-#define NN_LD8(reg, ptr) asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(reg) : "v"(ptr) : "memory")
-#define NN_DRAIN6(a, b, c, d, e, f) asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f)::"memory")
+// Per merge: ~1.3 passes over a slice and ~1.3 exchanges (without the cache and the fused scan: 3.9 passes, 2.9 exchanges).
 __device__ __forceinline__ double nn_f64(unsigned long long bits) { return __longlong_as_double((long long)bits); }
 
 //   {value bits 31..0, seq} {value bits 63..32, index (17 bits) | tie << 17 | event << 18 | (seq & 0x1fff) << 19}
@@ -1034,7 +1030,7 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_epoch_mwc(double* __restrict_
             // whichever row is the authoritative one) and the streamed slice are in flight together
             unsigned long long r_dp = 0, r_cv = 0;
             const bool want_dp = tid == 64 && prev >= 0 && ((smask[prev >> 5] >> (prev & 31)) & 1u);
-            if (want_dp) NN_LD8_SC1(r_dp, rowx + prev);
+            if (want_dp) r_dp = nn_ld8(rowx + prev);
             int cd = -1; bool cmine = false;
             if (tid < D) {
                 const int d = dslot[tid];
@@ -1043,19 +1039,19 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_epoch_mwc(double* __restrict_
                     if (cmine || d == prev) {
                         cd = d;
                         const double* src = dtime[tid] > tx ? W + (int64_t)d * ld + x : rowx + d;
-                        NN_LD8_SC1(r_cv, src);
+                        r_cv = nn_ld8(src);
                     }
                 }
             }
+            NN_FENCE();
+            const __amdgpu_buffer_rsrc_t bx = nn_row(rowx, (c1 + 1) & ~1);
             ArgMinT best = {__builtin_inf(), 0x7fffffff, 0};
             ArgMinT cand = {__builtin_inf(), 0x7fffffff, 0};
             for (int j0 = c0 + tid * 2; j0 < c1; j0 += 4 * NN_THREADS) {    // two 16-byte loads in flight per lane
                 const int j1 = j0 + 2 * NN_THREADS;
                 const bool two = j1 < c1;
-                u32x4 r0, r1;
-                NN_LD16_SC1(r0, rowx + j0);
-                NN_LD16_SC1(r1, rowx + (two ? j1 : j0));
-                NN_DRAIN2(r0, r1);
+                u32x4 r0 = nn_ld16(bx, j0 * 8), r1 = nn_ld16(bx, (two ? j1 : j0) * 8);
+                NN_KEEP(r0); NN_KEEP(r1);                        // (both land before either is used, whichever the lane needs)
                 {
                     const double2 v = mw_pair(r0);
                     const uint32_t bits = smask[j0 >> 5] >> (j0 & 31);
@@ -1069,7 +1065,6 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_epoch_mwc(double* __restrict_
                     if ((bits & 2u) && v.y <= best.v) { if (v.y < best.v) { best.v = v.y; best.i = j1 + 1; best.t = 0; } else best.t = 1; }
                 }
             }
-            NN_DRAIN2(r_dp, r_cv);
             if (want_dp) s_dprev = nn_f64(r_dp);
             if (cd >= 0) {
                 const double v = nn_f64(r_cv);
@@ -1205,9 +1200,9 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_epoch_mwc(double* __restrict_
             // ---- issue every gathered load (nothing waits yet)
             unsigned long long r_h = 0, r_dp = 0, r_dxi = 0, r_dyi = 0, r_nvd = 0, r_av = 0;
             // the merge height d(x, y): the row of whichever cluster merged last is the authoritative one
-            if (tid == NN_THREADS - 1) { const double* src = tmx > tmy ? rx + my : ry + mx; NN_LD8_SC1(r_h, src); }
+            if (tid == NN_THREADS - 1) r_h = nn_ld8(tmx > tmy ? rx + my : ry + mx);
             const bool want_dp = tid == 64 && aprev >= 0 && ((smask[aprev >> 5] >> (aprev & 31)) & 1u);
-            if (want_dp) NN_LD8_SC1(r_dp, ra + aprev);
+            if (want_dp) r_dp = nn_ld8(ra + aprev);
             int dd = -1, ad = -1;                                // dirty partner this lane updates / offers to row a's scan
             bool amine = false;
             if (tid < D) {
@@ -1218,17 +1213,20 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_epoch_mwc(double* __restrict_
                         dd = d;
                         const double* sx = dtime[tid] > tmx ? W + (int64_t)d * ld + mx : rx + d;
                         const double* sy = dtime[tid] > tmy ? W + (int64_t)d * ld + my : ry + d;
-                        NN_LD8_SC1(r_dxi, sx);
-                        NN_LD8_SC1(r_dyi, sy);
-                        NN_LD8(r_nvd, w.nnval + d);
+                        r_dxi = nn_ld8(sx);
+                        r_dyi = nn_ld8(sy);
+                        r_nvd = *reinterpret_cast<const unsigned long long*>(w.nnval + d);
                     }
                     if (a >= 0 && d != a && (mine || d == aprev)) {
                         ad = d; amine = mine;
                         const double* sa = dtime[tid] > ta ? W + (int64_t)d * ld + a : ra + d;
-                        NN_LD8_SC1(r_av, sa);
+                        r_av = nn_ld8(sa);
                     }
                 }
             }
+            NN_FENCE();
+            const __amdgpu_buffer_rsrc_t bx = nn_row(rx, (c1 + 1) & ~1), by = nn_row(ry, (c1 + 1) & ~1);
+            const __amdgpu_buffer_rsrc_t ba = nn_row(ra, (c1 + 1) & ~1), bn = nn_row(w.nnval, (c1 + 1) & ~1);
             ArgMinT rbest = {__builtin_inf(), 0x7fffffff, 0};   // this slice of the new row: the merged cluster's cache entry
             ArgMinT abest = {__builtin_inf(), 0x7fffffff, 0};   // this slice of row a: the streamed columns (ascending per lane)
             ArgMinT acand = {__builtin_inf(), 0x7fffffff, 0};   // ... and its gathered candidates (dirty partners, the new cluster)
@@ -1240,11 +1238,9 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_epoch_mwc(double* __restrict_
             for (int j0 = c0 + tid * 2; j0 < c1 || first; j0 += 2 * NN_THREADS) {
                 const bool any = j0 < c1;
                 const int j = any ? j0 : 0;                      // lanes without a pair re-read column 0 (always in bounds)
-                u32x4 qa, qb, qc, qn;
-                NN_LD16_SC1(qa, rx + j);
-                NN_LD16_SC1(qb, ry + j);
-                NN_LD16_SC1(qc, ra + j);
-                NN_LD16(qn, w.nnval + j);
+                u32x4 qa = nn_ld16(bx, j * 8), qb = nn_ld16(by, j * 8), qc = nn_ld16(ba, j * 8);
+                u32x4 qn = __builtin_amdgcn_raw_buffer_load_b128(bn, j * 8, 0, 0);    // (the cached distances: this workgroup's own, plain)
+                NN_FENCE();
                 if (first) {
                     // while the loads are in flight: every replica drops "my neighbour is x or y" for the rows outside its
                     // slice (LDS only; the own slice is handled with the streamed / gathered values below)
@@ -1268,7 +1264,7 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_epoch_mwc(double* __restrict_
                     }
                     if (prof) { const unsigned long long t1 = wall_clock64(); s_tp[9] += t1 - t0; t0 = t1; }
                 }
-                NN_DRAIN4(qa, qb, qc, qn);
+                NN_KEEP(qa); NN_KEEP(qb); NN_KEEP(qc); NN_KEEP(qn);
                 if (prof && first) { const unsigned long long t1 = wall_clock64(); s_tp[10] += t1 - t0; t0 = t1; }
                 first = false;
                 if (!any) continue;
@@ -1314,7 +1310,6 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_epoch_mwc(double* __restrict_
             }
             if (prof) { const unsigned long long t1 = wall_clock64(); s_tp[11] += t1 - t0; t0 = t1; }
             // ---- the gathered values: dirty partners of the update, candidates of row a's scan
-            NN_DRAIN6(r_h, r_dp, r_dxi, r_dyi, r_nvd, r_av);
             if (want_dp) s_dprev = nn_f64(r_dp);
             if (dd >= 0) {
                 const double dv = div_by_small_int(fx * nn_f64(r_dxi) + fy * nn_f64(r_dyi), fs, rcp);
@@ -1459,7 +1454,7 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_epoch_mwc(double* __restrict_
 //    count: select-based arg-min updates instead of branches, cluster sizes in a private global array per replica (two
 //    loads per merge, issued with the row loads), the replicas' merge records compared as one running hash per replica
 //    (k_nn_check_hashes) instead of 4 stores per merge and replica.
-// Visibility between the workgroups is the protocol of k_nn_epoch_mw / _mwc unchanged (sc1 stores and loads of every
+// Visibility between the workgroups is the protocol of k_nn_epoch_mwc unchanged (sc1 stores and loads of every
 // matrix byte, stores drained before the mailbox store, bounded spins, double-buffered 16-byte slots that carry their
 // sequence number in both halves).
 static constexpr int NN_W1_DCAP = 252;                   // merges per epoch: 8-bit times
@@ -1469,23 +1464,8 @@ static constexpr int NN_W1_DCAP = 252;                   // merges per epoch: 8-
 static constexpr int NN_W1_COLS = 128;
 static constexpr int NN_W1_MAX = 32767;                  // 15-bit slot numbers; one 4-byte word per column in the LDS of every replica
 static constexpr uint32_t W1_NOIDX = 0x7fffu;
-// Loads of this kernel are COMPILER-VISIBLE (its wait-count pass tracks them): the streamed pairs are raw buffer loads with
-// the sc1 bit (buffer_load_dwordx4 ... offen sc1; a row is one buffer resource, so lanes beyond the slice read zeros
-// instead of needing a branch), the gathered values and sizes relaxed agent-scope atomic loads (global_load ... sc1).
-// The earlier kernels issue their loads from inline assembly and wait in a later statement; with up to ~60 loads in
-// flight per lane the register allocator then copies a destination register before its load has landed (seen: a fault at
-// 16 pairs per lane).  All loads of a pass are issued before NN_FENCE; NN_KEEP makes every use come after it.
-#define NN_FENCE() asm volatile("" ::: "memory")
-#define NN_KEEP(reg) asm volatile("" : "+v"(reg))
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t w1_row(const double* row, int cols)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(row), 0, cols * 8, 0x00020000);
-}
-__device__ __forceinline__ u32x4 w1_ld16(__amdgpu_buffer_rsrc_t r, int byte_offset) { return __builtin_amdgcn_raw_buffer_load_b128(r, byte_offset, 0, 16); }
-__device__ __forceinline__ unsigned long long w1_ld8(const double* p)
-{
-    return __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// Loads go through the compiler-visible helpers above (nn_row, nn_ld16, nn_ld8).  With up to ~60 of them in flight per lane,
+// all loads of a pass are issued before NN_FENCE, and NN_KEEP makes every use come after it.
 __device__ __forceinline__ int w1_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 // both mailbox slots of a peer: issue and wait in ONE statement
 __device__ __forceinline__ void w1_poll(u32x4& a, u32x4& b, const u32x4* pa, const u32x4* pb)
@@ -1797,12 +1777,12 @@ __global__ __launch_bounds__(64) void k_nn_epoch_w1(double* __restrict__ W, int6
             const uint32_t ex = umeta(x);
             W1_STAMP(0);
             const double* __restrict__ rowx = W + (int64_t)x * ld;
-            const __amdgpu_buffer_rsrc_t bx = w1_row(rowx, (c1 + 1) & ~1);
+            const __amdgpu_buffer_rsrc_t bx = nn_row(rowx, (c1 + 1) & ~1);
             unsigned long long r_dp = 0;
-            if (lane == 63 && prev >= 0) r_dp = w1_ld8(rowx + prev);
+            if (lane == 63 && prev >= 0) r_dp = nn_ld8(rowx + prev);
             u32x4 q[TRIPS];
 #pragma unroll
-            for (int t = 0; t < TRIPS; t++) q[t] = w1_ld16(bx, (jl0 + 2 * t) * 8);
+            for (int t = 0; t < TRIPS; t++) q[t] = nn_ld16(bx, (jl0 + 2 * t) * 8);
             NN_FENCE();
             NN_KEEP(r_dp);
 #pragma unroll
@@ -1849,17 +1829,17 @@ __global__ __launch_bounds__(64) void k_nn_epoch_w1(double* __restrict__ W, int6
         // Lance-Williams pass over x and y
         const double* __restrict__ rx = W + (int64_t)mx * ld;
         double* __restrict__ ry = W + (int64_t)my * ld;
-        const __amdgpu_buffer_rsrc_t bx = w1_row(rx, (c1 + 1) & ~1), by = w1_row(ry, (c1 + 1) & ~1);
+        const __amdgpu_buffer_rsrc_t bx = nn_row(rx, (c1 + 1) & ~1), by = nn_row(ry, (c1 + 1) & ~1);
         int r_nx = __hip_atomic_load(gsize + mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         int r_ny = __hip_atomic_load(gsize + my, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         unsigned long long r_h = 0, r_dp = 0;
-        if (lane == 62) r_h = w1_ld8(rx + my);                   // the merge height d(x, y)
+        if (lane == 62) r_h = nn_ld8(rx + my);                   // the merge height d(x, y)
         u32x4 qa[TRIPS], qb[TRIPS], qc[TRIPS];
 #pragma unroll
         for (int t = 0; t < TRIPS; t++) {
             const int off = (jl0 + 2 * t) * 8;
-            qa[t] = w1_ld16(bx, off);
-            qb[t] = w1_ld16(by, off);
+            qa[t] = nn_ld16(bx, off);
+            qb[t] = nn_ld16(by, off);
         }
         NN_FENCE();
         len -= 2;
@@ -1885,12 +1865,12 @@ __global__ __launch_bounds__(64) void k_nn_epoch_w1(double* __restrict__ W, int6
         double dprev = __builtin_inf(), fs = 0.0;
         {
             const double* __restrict__ ra = W + (int64_t)(a >= 0 ? a : mx) * ld;
-            const __amdgpu_buffer_rsrc_t ba = w1_row(ra, (c1 + 1) & ~1);
-            if (lane == 63 && aprev >= 0) r_dp = w1_ld8(ra + aprev);
+            const __amdgpu_buffer_rsrc_t ba = nn_row(ra, (c1 + 1) & ~1);
+            if (lane == 63 && aprev >= 0) r_dp = nn_ld8(ra + aprev);
 #pragma unroll
             for (int t = 0; t < TRIPS; t++) {
                 qc[t] = u32x4{0u, 0u, 0u, 0u};
-                if (a >= 0) qc[t] = w1_ld16(ba, (jl0 + 2 * t) * 8);
+                if (a >= 0) qc[t] = nn_ld16(ba, (jl0 + 2 * t) * 8);
             }
             NN_FENCE();
             W1_STAMP(4);
@@ -2198,114 +2178,87 @@ __global__ __launch_bounds__(256) void k_nn_translate(double* __restrict__ zraw,
     zraw[4 * (int64_t)s + 1] = (double)w.orig[(int)zraw[4 * (int64_t)s + 1]];
 }
 
-template <int NWG>
-static void launch_mwc_n(bool profile, size_t lds, hipStream_t s, double* cur, int64_t ldw, int n_cur, int* chain, double* zraw,
-                         NNWorkspace w, int dcap, int total_steps)
+// ---- the options, the plan of one epoch, the launch -------------------------------------------------------------
+NNChainOptions nnchain_options(int probed_xcc)
 {
-    if (profile) hipLaunchKernelGGL((k_nn_epoch_mwc<NWG, true>), dim3(NWG), dim3(NN_THREADS), lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps);
-    else hipLaunchKernelGGL((k_nn_epoch_mwc<NWG, false>), dim3(NWG), dim3(NN_THREADS), lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps);
+    NNChainOptions o;
+    o.profile = getenv("HICMI_NNCHAIN_PROFILE") != nullptr;
+    // merges between two column flushes = merges per epoch launch of the 1024-lane kernels.  Every row a merge reads is
+    // patched at the columns whose writes are still deferred, so a merge's cost grows with the list: 1024 -> 256 merges per
+    // epoch took the chain from 124.8 to 118.0 ms at 16k and from 282.5 to 272.4 ms at 32k (128: no further gain - ~40 us
+    // of launches per epoch)
+    if (const char* t = getenv("HICMI_NNCHAIN_DCAP")) { o.dcap_forced = true; o.dcap = atoi(t); }
+    o.dcap = o.dcap < 1 ? 1 : (o.dcap > NN_DMAX ? NN_DMAX : o.dcap);
+    o.compact = getenv("HICMI_NNCHAIN_NO_COMPACT") == nullptr;
+    if (const char* t = getenv("HICMI_NNCHAIN_WGS")) { o.wgs_set = true; o.wgs = atoi(t); }
+    o.plain = getenv("HICMI_NNCHAIN_PLAIN") != nullptr;
+    o.gsize = getenv("HICMI_NNCHAIN_GSIZE") != nullptr;
+    if (const char* t = getenv("HICMI_NNCHAIN_W1")) o.w1 = atoi(t) != 0;
+    if (const char* t = getenv("HICMI_NNCHAIN_W1_S")) o.w1_s = atoi(t);
+    const char* cols = getenv("HICMI_NNCHAIN_W1_COLS");
+    o.w1_cols = cols ? (atoi(cols) > 64 ? atoi(cols) : 64) : NN_W1_COLS;
+    const char* maxs = getenv("HICMI_NNCHAIN_W1_MAXS");
+    o.w1_maxs = maxs ? atoi(maxs) : NN_W1_MAXS;
+    // off | 0 .. 7 (8: an XCD that does not exist - nobody claims a slice; tests); unset: the probed one
+    const char* xcd = getenv("HICMI_NNCHAIN_XCD");
+    o.xcc = !xcd ? probed_xcc : ((xcd[0] < '0' || xcd[0] > '8') ? -1 : xcd[0] - '0');
+    if (const char* t = getenv("HICMI_NNCHAIN_TEST_LATE")) o.test_late = atoi(t);
+    if (const char* t = getenv("HICMI_NNCHAIN_TEST_DIVERGE")) o.test_diverge = atoi(t);
+    if (const char* t = getenv("HICMI_NNCHAIN_TEST_ROLLCALL")) o.test_rollcall = atoi(t);
+    return o;
 }
 
-static void launch_mwc(int wgs, bool profile, size_t lds, hipStream_t s, double* cur, int64_t ldw, int n_cur, int* chain,
-                       double* zraw, NNWorkspace w, int dcap, int total_steps, bool gsize = false)
+// Every epoch kernel, by template arguments: [width 2, 4, 8, 16][PROF] for k_nn_epoch_mwc, [8, 16][PROF] for its GSIZE form,
+// [trips 1, 2, 4, 8, 16][PROF][LOCAL] for k_nn_epoch_w1.
+#define NN_K(...) reinterpret_cast<const void*>(__VA_ARGS__)
+static const void* const kEpoch[2] = {NN_K(k_nn_epoch<false>), NN_K(k_nn_epoch<true>)};
+static const void* const kEpochNc[2] = {NN_K(k_nn_epoch_nc<false>), NN_K(k_nn_epoch_nc<true>)};
+static const void* const kMwc[4][2] = {{NN_K(k_nn_epoch_mwc<2, false>), NN_K(k_nn_epoch_mwc<2, true>)},
+                                       {NN_K(k_nn_epoch_mwc<4, false>), NN_K(k_nn_epoch_mwc<4, true>)},
+                                       {NN_K(k_nn_epoch_mwc<8, false>), NN_K(k_nn_epoch_mwc<8, true>)},
+                                       {NN_K(k_nn_epoch_mwc<16, false>), NN_K(k_nn_epoch_mwc<16, true>)}};
+static const void* const kMwcG[2][2] = {{NN_K(k_nn_epoch_mwc<8, false, true>), NN_K(k_nn_epoch_mwc<8, true, true>)},
+                                        {NN_K(k_nn_epoch_mwc<16, false, true>), NN_K(k_nn_epoch_mwc<16, true, true>)}};
+#define NN_W1(T) {{NN_K(k_nn_epoch_w1<T, false, false>), NN_K(k_nn_epoch_w1<T, false, true>)}, \
+                  {NN_K(k_nn_epoch_w1<T, true, false>), NN_K(k_nn_epoch_w1<T, true, true>)}}
+static const void* const kW1[5][2][2] = {NN_W1(1), NN_W1(2), NN_W1(4), NN_W1(8), NN_W1(16)};
+#undef NN_W1
+#undef NN_K
+static int log2_small(int v) { int l = 0; while ((1 << (l + 1)) <= v) l++; return l; }      // 1, 2, 4, 8, 16 -> 0 .. 4
+
+// Dynamic LDS the kernels may ask for: what a CU has (160 KB) minus the largest static part of the family, 256 bytes to
+// spare.  Set once as every epoch kernel's limit.
+struct NNLdsRoom { size_t w1 = 0; int gsize_max = 0; };
+static const NNLdsRoom& nn_lds_room()
 {
-    if (gsize) {                                           // (8 or 16 slices: what rows beyond 32,768 columns use)
-        if (wgs == 16) {
-            if (profile) hipLaunchKernelGGL((k_nn_epoch_mwc<16, true, true>), dim3(16), dim3(NN_THREADS), lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps);
-            else hipLaunchKernelGGL((k_nn_epoch_mwc<16, false, true>), dim3(16), dim3(NN_THREADS), lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps);
-        } else {
-            if (profile) hipLaunchKernelGGL((k_nn_epoch_mwc<8, true, true>), dim3(8), dim3(NN_THREADS), lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps);
-            else hipLaunchKernelGGL((k_nn_epoch_mwc<8, false, true>), dim3(8), dim3(NN_THREADS), lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps);
+    static const NNLdsRoom room = [] {
+        auto room_of = [](const void* const* fns, int count) {
+            size_t stat = 0;
+            for (int i = 0; i < count; i++) {
+                hipFuncAttributes a;
+                if (hipFuncGetAttributes(&a, fns[i]) != hipSuccess) return (size_t)0;
+                if (a.sharedSizeBytes > stat) stat = a.sharedSizeBytes;
+            }
+            const size_t r = 160 * 1024 > stat + 256 ? 160 * 1024 - stat - 256 : 0;
+            for (int i = 0; i < count; i++) hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)r);
+            return r;
+        };
+        NNLdsRoom r;
+        room_of(kEpoch, 2);
+        room_of(kEpochNc, 2);
+        room_of(&kMwc[0][0], 8);
+        r.w1 = room_of(&kW1[0][0][0], 20);
+        // the largest row the GSIZE form takes: bitmaps (12 bytes per 32 columns) + cache (2 bytes per column)
+        const size_t g = room_of(&kMwcG[0][0], 4);
+        int n = NN_MWC_GMAX;
+        while (n > 0) {
+            const size_t nw4 = ((((size_t)n + 31) / 32) + 3) & ~(size_t)3;
+            if (align16(nw4 * 12 + (((size_t)n + 7) & ~(size_t)7) * 2) <= g) break;
+            n -= 64;
         }
-        return;
-    }
-    if (wgs == 16) launch_mwc_n<16>(profile, lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps);
-    else if (wgs == 2) launch_mwc_n<2>(profile, lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps);
-    else if (wgs == 4) launch_mwc_n<4>(profile, lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps);
-    else launch_mwc_n<8>(profile, lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps);
-}
-
-static void mwc_set_lds(int bytes)
-{
-    const void* fns[] = {reinterpret_cast<const void*>(k_nn_epoch_mwc<2, false>), reinterpret_cast<const void*>(k_nn_epoch_mwc<2, true>),
-                         reinterpret_cast<const void*>(k_nn_epoch_mwc<4, false>), reinterpret_cast<const void*>(k_nn_epoch_mwc<4, true>),
-                         reinterpret_cast<const void*>(k_nn_epoch_mwc<8, false>), reinterpret_cast<const void*>(k_nn_epoch_mwc<8, true>),
-                         reinterpret_cast<const void*>(k_nn_epoch_mwc<16, false>), reinterpret_cast<const void*>(k_nn_epoch_mwc<16, true>)};
-    for (const void* f : fns) hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
-// Largest row the GSIZE variant can take: bitmaps (12 bytes per 32 columns) + cache (2 bytes per column) + the kernel's
-// static LDS within the 160 KB of a CU.  Also raises the kernels' dynamic-LDS limit to what is left.
-static int mwc_gsize_max_columns()
-{
-    static int cached = -1;
-    if (cached >= 0) return cached;
-    size_t stat = 0;
-    const void* fns[] = {reinterpret_cast<const void*>(k_nn_epoch_mwc<8, false, true>), reinterpret_cast<const void*>(k_nn_epoch_mwc<8, true, true>),
-                         reinterpret_cast<const void*>(k_nn_epoch_mwc<16, false, true>), reinterpret_cast<const void*>(k_nn_epoch_mwc<16, true, true>)};
-    for (const void* f : fns) {
-        hipFuncAttributes a;
-        if (hipFuncGetAttributes(&a, f) != hipSuccess) { cached = 0; return 0; }
-        if (a.sharedSizeBytes > stat) stat = a.sharedSizeBytes;
-    }
-    const size_t room = 160 * 1024 > stat + 256 ? 160 * 1024 - stat - 256 : 0;
-    for (const void* f : fns) hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)room);
-    int n = NN_MWC_GMAX;
-    while (n > 0) {
-        const size_t nw4 = ((((size_t)n + 31) / 32) + 3) & ~(size_t)3;
-        if (align16(nw4 * 12 + (((size_t)n + 7) & ~(size_t)7) * 2) <= room) break;
-        n -= 64;
-    }
-    cached = n > 0 ? n : 0;
-    return cached;
-}
-
-// ---- k_nn_epoch_w1: slices, trips and LDS of one epoch ----------------------------------------------------------
-template <int TRIPS>
-static void launch_w1_t(bool profile, int S, int slice, size_t lds, hipStream_t s, double* cur, int64_t ldw, int n_cur, int* chain,
-                        double* zraw, NNWorkspace w, int dcap, int total_steps, int xcc, bool fail_rollcall)
-{
-    if (xcc >= 0) {                                              // LOCAL (see the kernel), and behind it the launch that takes over if it gives up
-        const int need = fail_rollcall ? 0x40000000 : S;          // (test hook: a party that never comes)
-        hipMemsetAsync(w.state + 15, 0, sizeof(int), s);
-        if (profile) hipLaunchKernelGGL((k_nn_epoch_w1<TRIPS, true, true>), dim3(16 * S), dim3(64), lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps, slice, S, xcc, need);
-        else hipLaunchKernelGGL((k_nn_epoch_w1<TRIPS, false, true>), dim3(16 * S), dim3(64), lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps, slice, S, xcc, need);
-        hipLaunchKernelGGL((k_nn_epoch_w1<TRIPS, false, false>), dim3(S), dim3(64), lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps, slice, S, -2, S);
-        return;
-    }
-    if (profile) hipLaunchKernelGGL((k_nn_epoch_w1<TRIPS, true, false>), dim3(S), dim3(64), lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps, slice, S, -1, S);
-    else hipLaunchKernelGGL((k_nn_epoch_w1<TRIPS, false, false>), dim3(S), dim3(64), lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps, slice, S, -1, S);
-}
-
-static void launch_w1(bool profile, int S, int slice, size_t lds, hipStream_t s, double* cur, int64_t ldw, int n_cur, int* chain,
-                      double* zraw, NNWorkspace w, int dcap, int total_steps, int xcc, bool fail_rollcall)
-{
-    const int trips = (slice + 127) / 128;
-    if (trips <= 1) launch_w1_t<1>(profile, S, slice, lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps, xcc, fail_rollcall);
-    else if (trips <= 2) launch_w1_t<2>(profile, S, slice, lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps, xcc, fail_rollcall);
-    else if (trips <= 4) launch_w1_t<4>(profile, S, slice, lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps, xcc, fail_rollcall);
-    else if (trips <= 8) launch_w1_t<8>(profile, S, slice, lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps, xcc, fail_rollcall);
-    else launch_w1_t<16>(profile, S, slice, lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps, xcc, fail_rollcall);
-}
-
-// Dynamic LDS the kernels may ask for: what the CU has (160 KB) minus their static part.
-static size_t w1_lds_room()
-{
-    static size_t room = 0;
-    if (room) return room;
-#define W1_FNS(T) reinterpret_cast<const void*>(k_nn_epoch_w1<T, false, false>), reinterpret_cast<const void*>(k_nn_epoch_w1<T, true, false>), \
-                  reinterpret_cast<const void*>(k_nn_epoch_w1<T, false, true>), reinterpret_cast<const void*>(k_nn_epoch_w1<T, true, true>)
-    const void* fns[] = {W1_FNS(1), W1_FNS(2), W1_FNS(4), W1_FNS(8), W1_FNS(16)};
-#undef W1_FNS
-    size_t stat = 0;
-    for (const void* f : fns) {
-        hipFuncAttributes a;
-        if (hipFuncGetAttributes(&a, f) != hipSuccess) return 0;
-        if (a.sharedSizeBytes > stat) stat = a.sharedSizeBytes;
-    }
-    const size_t r = 160 * 1024 > stat + 256 ? 160 * 1024 - stat - 256 : 0;
-    for (const void* f : fns) hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r);
-    room = r;
+        r.gsize_max = n > 0 ? n : 0;
+        return r;
+    }();
     return room;
 }
 
@@ -2325,227 +2278,196 @@ static bool w1_plan(int n, int cols, int max_s, int force_s, int* S_out, int* sl
     S = (n + slice - 1) / slice;                                  // (rounding the width up can leave the last slices empty)
     const int n4 = (n + 3) & ~3;
     const size_t lds = align16((size_t)n4 * 4 + (size_t)slice * 8);
-    if (lds > w1_lds_room()) return false;
+    if (lds > nn_lds_room().w1) return false;
     *S_out = S; *slice_out = slice; *lds_out = lds;
     return true;
 }
 
-// The XCD the one-wave kernel claims (its LOCAL form), or -1: HICMI_NNCHAIN_XCD=off | 0..7 (default 0).  The pre-sort that runs
-// beside the chain leaves that XCD alone (api.hip: start_presort), so its 32 CUs are free for up to 64 parties.
-// Which XCC ids this device's workgroups report at all: the lowest is the default target.  (A whole MI355X answers 0 ... 7; a
-// partition of one may answer with a single id, and not necessarily 0 - a fixed target would then never be claimed.)
+enum NNKind { NN_PLAIN, NN_NC, NN_MWC, NN_W1 };
+struct NNEpochPlan {
+    NNKind kind = NN_PLAIN;
+    int grid = 1;               // workgroups (k_nn_epoch_mwc: its width NWG; k_nn_epoch_w1: its slices S)
+    bool gsize = false;         // k_nn_epoch_mwc: cluster sizes in global memory
+    int trips = 0;              // k_nn_epoch_w1: TRIPS
+    int slice = 0;              // k_nn_epoch_w1: columns per slice
+    size_t lds = 0;             // dynamic LDS
+    int xcc = -1;               // k_nn_epoch_w1: the XCD its LOCAL form claims, -1 = spread over the chip
+    int dcap = 0;               // merges of the epoch
+    bool rowmin = false;        // k_nn_rowmin rebuilds the neighbour cache first
+    bool flush = false;         // k_nn_flush writes the deferred columns after
+};
+
+// fallback (the retries after "a peer answered late"): 1 = the one-wave kernel spread over the chip, never on one XCD;
+// 2 = one workgroup, which waits for nobody
+static bool nn_w1_on(const NNChainOptions& o, int fallback)
+{
+    // One wave per column slice (k_nn_epoch_w1): the default at every width up to 32,767 live columns.
+    // HICMI_NNCHAIN_W1=0 selects the 1024-lane kernels instead (A/B; so does every switch that names one of them).
+    return o.w1 && !o.wgs_set && fallback < 2 && !o.plain && !o.gsize;
+}
+
+// The kernel, its shape and what runs around it for the epoch that starts with `done` merges made and n_cur columns.
+static NNEpochPlan nn_plan(const NNChainOptions& o, int n, int n_cur, int done, int fallback, bool cache_valid)
+{
+    // Column-sliced chain on several workgroups (k_nn_epoch_mwc): HICMI_NNCHAIN_WGS = 1, 2, 4, 8 or 16 forces a width for
+    // every epoch (tests, A/B).  Narrower epochs run on one workgroup with the neighbour cache (k_nn_epoch_nc);
+    // HICMI_NNCHAIN_PLAIN=1 selects the cache-less k_nn_epoch instead (A/B, and the reference point of the tests).
+    const bool wgs_set = o.wgs_set || fallback >= 2;
+    const int wgs_env = fallback >= 2 ? 1 : o.wgs;
+    const int wgs = wgs_set ? (wgs_env >= 16 ? 16 : (wgs_env >= 8 ? 8 : (wgs_env >= 4 ? 4 : (wgs_env >= 2 ? 2 : 1)))) : 8;
+    // 16 slices instead of 8 while the rows are long: a merge costs ~7.4 / 8.5 / 11.4 us at 2,000 / 4,000 / 8,000 columns per
+    // slice, and the sixteen-way exchange only a little more than the eight-way one.  Measured (nn-chain per map, threshold
+    // off / 24,000 / 16,000 / 12,000 live columns): 32k 272 / 264 / 256 / 259 ms, 64k 730 / 682 / 678 / - ms, 16k 118.3 / - / - / 116.8
+    const int w16_from = wgs_set ? 0x7fffffff : 14000;
+    // live columns from which an epoch runs sliced: with the cache and the fused scan a merge costs ~1.3 exchanges instead
+    // of ~2.9, so eight slices pay from ~6,000 columns on (16k map: nn-chain 200 -> 153 ms; 4,000 and 8,000 measure the same)
+    const int mw_from = wgs_set ? 64 * wgs : 6000;
+    // Rebuild the whole cache (k_nn_rowmin, a full-chip pass over the flushed matrix: 0.13 ms at 8,000 live columns) before
+    // every epoch that has at most this many live columns: rows whose neighbour merged are then known again without a scan
+    // of their own.  Worth 1.5 ms per 16k map (scans per merge 1.28 -> 1.23: most such rows are walked within the epoch that
+    // invalidated them); above ~12,000 columns the pass costs more than the scans it saves.
+    const int refresh_below = 8000;
+    const int nw4 = (((n_cur + 31) / 32) + 3) & ~3;
+    NNEpochPlan p;
+    p.dcap = o.dcap;
+    p.flush = true;
+    int S = 0, slice = 0; size_t lds = 0;
+    if (nn_w1_on(o, fallback) && w1_plan(n_cur, o.w1_cols, o.w1_maxs, o.w1_s, &S, &slice, &lds)) {
+        p.kind = NN_W1;
+        p.grid = S; p.slice = slice; p.lds = lds;
+        const int trips = (slice + 127) / 128;
+        p.trips = trips <= 1 ? 1 : (trips <= 2 ? 2 : (trips <= 4 ? 4 : (trips <= 8 ? 8 : 16)));
+        // all parties on one XCD while they fit there together: 32 CUs x the workgroups a CU's LDS holds
+        p.xcc = fallback >= 1 ? -1 : o.xcc;
+        if (p.xcc >= 0 && S > 32 * (int)((160 * 1024) / (lds + 2048))) p.xcc = -1;
+        // the one-wave kernel renormalises its time stamps itself: an epoch runs until the next compaction is due, at
+        // least 256 merges; HICMI_NNCHAIN_DCAP still forces a length
+        if (!o.dcap_forced) {
+            const int until = o.compact ? (n - done) - n_cur / 2 : 4096;
+            p.dcap = until > 256 ? until : 256;
+        }
+        p.flush = false;                                            // it keeps the matrix symmetric itself
+    } else {
+        const int width = n_cur >= w16_from ? 16 : wgs;
+        // rows beyond 32,768 columns (or HICMI_NNCHAIN_GSIZE=1: all, for the tests): cluster sizes in global memory, the
+        // cache alone in LDS - 64,000 columns fit; 8 or 16 slices
+        const bool gsize = width >= 8 && (n_cur > NN_MWC_MAX || o.gsize) && n_cur <= nn_lds_room().gsize_max;
+        if (wgs > 1 && n_cur >= mw_from && !o.plain && (n_cur <= NN_MWC_MAX || gsize)) {
+            p.kind = NN_MWC;
+            p.grid = width; p.gsize = gsize;
+            p.lds = align16((size_t)nw4 * 12 + (size_t)((n_cur + 7) & ~7) * (gsize ? 2 : 4));
+        } else if (!o.plain && n_cur <= NN_NC_MAX) {
+            p.kind = NN_NC;
+            p.lds = align16((size_t)nw4 * 12 + (size_t)((n_cur + 7) & ~7) * 4);
+        } else {
+            p.kind = NN_PLAIN;
+            p.lds = align16((size_t)nw4 * 8 + (size_t)n_cur * 2);
+        }
+    }
+    p.rowmin = p.kind != NN_PLAIN && (!cache_valid || n_cur <= refresh_below);
+    return p;
+}
+
+// The XCD the one-wave kernel claims (its LOCAL form), for the pre-sort's benefit (api.hip: start_presort leaves it
+// alone, so its 32 CUs are free for up to 64 parties): the chain's XCD if its FIRST epoch runs there, else -1.  (A wider
+// map starts spread out - 8 parties per XCD, which the pre-sort's 192 workgroups leave room for on every XCD - and by the
+// time it has shrunk to one XCD's capacity the pre-sort is over.)
+int nnchain_local_xcc(const NNChainOptions& o, int n)
+{
+    const NNEpochPlan p = nn_plan(o, n, n, 0, 0, false);
+    return p.kind == NN_W1 ? p.xcc : -1;
+}
+
+// Which XCC ids this device's workgroups report at all: the lowest is the default target of the one-wave kernel.  (A
+// whole MI355X answers 0 ... 7; a partition of one may answer with a single id, and not necessarily 0 - a fixed target
+// would then never be claimed.)
 __global__ void k_probe_xcc(int* __restrict__ out)
 {
     if (threadIdx.x == 0) out[blockIdx.x] = (int)(__builtin_amdgcn_s_getreg(GETREG_XCC_ID) & 0xfu);
 }
 
-static int w1_probed_xcc()
+int nnchain_probe_xcc(hipStream_t s)
 {
-    static std::atomic<int> cached[64];
-    static std::atomic<bool> init{false};
-    if (!init.exchange(true)) for (auto& c : cached) c.store(-2);
+    static std::atomic<int> cached[64];                      // per device: the value + 1 (zero-initialised: not probed yet)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    int v = cached[dev].load();
-    if (v != -2) return v;
-    v = 0;
+    const int known = cached[dev].load();
+    if (known) return known - 1;
+    int v = 0;
     int* d = nullptr;
     if (hipMalloc((void**)&d, 256 * sizeof(int)) == hipSuccess) {
         int h[256];
-        hipLaunchKernelGGL(k_probe_xcc, dim3(256), dim3(64), 0, 0, d);
-        if (hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess) {
+        hipLaunchKernelGGL(k_probe_xcc, dim3(256), dim3(64), 0, s, d);
+        if (hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess) {
             v = 15;
             for (int i = 0; i < 256; i++) if (h[i] >= 0 && h[i] < v) v = h[i];
             if (v > 7) v = 0;
         }
         (void)hipFree(d);
     }
-    cached[dev].store(v);
+    cached[dev].store(v + 1);
     return v;
 }
 
-static int w1_xcc_env()
-{
-    const char* t = getenv("HICMI_NNCHAIN_XCD");          // off | 0 .. 7 (8: an XCD that does not exist - nobody claims a slice; tests)
-    if (!t) return w1_probed_xcc();
-    return (t[0] < '0' || t[0] > '8') ? -1 : t[0] - '0';
-}
-
-// ... for the pre-sort's benefit: the XCD it should leave alone, i.e. the chain's XCD if the chain's FIRST epoch at n columns
-// already runs there.  (A wider map starts spread out - 8 parties per XCD, which the pre-sort's 192 workgroups leave room
-// for on every XCD - and by the time it has shrunk to one XCD's capacity the pre-sort is over.)
-int nnchain_local_xcc(int n)
-{
-    const int xcc = w1_xcc_env();
-    if (xcc < 0 || n > NN_W1_MAX) return -1;
-    const char* w1_text = getenv("HICMI_NNCHAIN_W1");
-    if ((w1_text && atoi(w1_text) == 0) || getenv("HICMI_NNCHAIN_WGS") || getenv("HICMI_NNCHAIN_PLAIN") || getenv("HICMI_NNCHAIN_GSIZE")) return -1;
-    if (getenv("HICMI_NNCHAIN_XCD_WIDE")) return xcc;
-    int S = 0, slice = 0; size_t lds = 0;
-    if (!w1_plan(n, NN_W1_COLS, NN_W1_MAXS, 0, &S, &slice, &lds)) return -1;
-    return S <= 32 * (int)((160 * 1024) / (lds + 2048)) ? xcc : -1;
-}
-
 // W and W2: two n x ldw buffers (W holds the distances on entry; both are scratch afterwards).
-// Returns the number of epoch launches.  force_single: never the column-sliced kernel (the retry after a late peer).
-int launch_nnchain(double* W, double* W2, int64_t ldw, int n, int* chain, double* zraw, void* workspace, bool profile,
-                   int dcap, bool compact, int fallback, hipStream_t s, const std::function<void()>& after_first_rowmin)
+// Returns the number of epoch launches.
+int launch_nnchain(double* W, double* W2, int64_t ldw, int n, int* chain, double* zraw, void* workspace,
+                   const NNChainOptions& o, int fallback, hipStream_t s, const std::function<void()>& after_first_rowmin)
 {
     bool told = false;
     auto tell = [&] { if (!told && after_first_rowmin) after_first_rowmin(); told = true; };
-    // fallback (the retries after "a peer answered late"): 1 = the one-wave kernel spread over the chip, never on one XCD;
-    // 2 = one workgroup, which waits for nobody
-    const bool force_single = fallback >= 2;
-    int epochs = 0;
+    const int prof = o.profile ? 1 : 0;
     NNWorkspace w = carve(workspace, n);
-    // Column-sliced chain on several workgroups (k_nn_epoch_mw): its fixed cost per scan (one exchange) is paid back
-    // by the shorter streams from about 20k live columns on.  HICMI_NNCHAIN_WGS = 1, 2, 4 or 8 forces a width for
-    // every epoch (tests, A/B).  Narrower epochs run on one workgroup with the neighbour cache (k_nn_epoch_nc);
-    // HICMI_NNCHAIN_PLAIN=1 selects the cache-less k_nn_epoch instead (A/B, and the reference point of the tests).
-    const char* wgs_text = force_single ? "1" : getenv("HICMI_NNCHAIN_WGS");
-    const int wgs_env = wgs_text ? atoi(wgs_text) : 0;
-    const int wgs = wgs_text ? (wgs_env >= 16 ? 16 : (wgs_env >= 8 ? 8 : (wgs_env >= 4 ? 4 : (wgs_env >= 2 ? 2 : 1)))) : 8;
-    // 16 slices instead of 8 while the rows are long: a merge costs ~7.4 / 8.5 / 11.4 us at 2,000 / 4,000 / 8,000 columns per
-    // slice, and the sixteen-way exchange only a little more than the eight-way one.  Measured (nn-chain per map, threshold
-    // off / 24,000 / 16,000 / 12,000 live columns): 32k 272 / 264 / 256 / 259 ms, 64k 730 / 682 / 678 / - ms, 16k 118.3 / - / - / 116.8
-    const int w16_from = wgs_text ? 0x7fffffff : 14000;
-    // live columns from which an epoch runs sliced: with the cache and the fused scan a merge costs ~1.3 exchanges instead
-    // of ~2.9, so eight slices pay from ~6,000 columns on (16k map: nn-chain 200 -> 153 ms; 4,000 and 8,000 measure the same)
-    const int mw_from = wgs_text ? 64 * wgs : 6000;
-    const bool plain = getenv("HICMI_NNCHAIN_PLAIN") != nullptr;
-    // Rebuild the whole cache (k_nn_rowmin, a full-chip pass over the flushed matrix: 0.13 ms at 8,000 live columns) before
-    // every epoch that has at most this many live columns: rows whose neighbour merged are then known again without a scan
-    // of their own.  Worth 1.5 ms per 16k map (scans per merge 1.28 -> 1.23: most such rows are walked within the epoch that
-    // invalidated them); above ~12,000 columns the pass costs more than the scans it saves.  0 = never.
-    const int refresh_below = 8000;
-    // The matrix is compacted - live rows and columns copied into the other buffer - when HALF of its columns have merged
-    // away.  (Rounds 1-2 and the first one-wave kernel compacted at three quarters: with deferred column writes a merge's
-    // cost grew with the width.  The one-wave kernel's does not until the slice drops under the next power-of-two number of
-    // pairs per lane, an epoch boundary costs ~100 us plus the copy, and a 32k map is down to one XCD's capacity after ONE
-    // compaction instead of two.  Measured on one box, 3/4 | 2/3 | 3/5 | 1/2 | 2/5 | 1/3 | 1/4 of the columns left:
-    // 16k 81.6 | 80.4 | 80.1 | 80.0 | 80.3 | 80.5 | 80.8 ms, 32k 203.5 | 197.6 | 200.2 | 194.0 | 198.3 | 202.4 | 206.0 ms;
-    // 64k 602.7 -> 586.6 ms.)  HICMI_NNCHAIN_COMPACT_AT=<num>/<den> sets another fraction (A/B).
-    int cnum = 1, cden = 2;
-    if (const char* t = getenv("HICMI_NNCHAIN_COMPACT_AT")) {
-        int a = 0, b = 0;
-        if (sscanf(t, "%d/%d", &a, &b) == 2 && a >= 1 && b > a && b <= 64) { cnum = a; cden = b; }
-    }
-    const bool force_gsize = getenv("HICMI_NNCHAIN_GSIZE") != nullptr;   // the GSIZE variant of k_nn_epoch_mwc at every width (tests)
-    // One wave per column slice (k_nn_epoch_w1): the default at every width up to 32,768 live columns.  HICMI_NNCHAIN_W1=0
-    // selects the 1024-lane kernels of rounds 1-2 instead (A/B; so does every switch that names one of them);
-    // HICMI_NNCHAIN_W1_S forces the number of slices (tests), HICMI_NNCHAIN_W1_COLS / _MAXS set the columns per slice the
-    // plan aims at and the largest number of slices.
-    const char* w1_text = getenv("HICMI_NNCHAIN_W1");
-    const char* w1_s_text = getenv("HICMI_NNCHAIN_W1_S");
-    const char* w1_cols_text = getenv("HICMI_NNCHAIN_W1_COLS");
-    const char* w1_maxs_text = getenv("HICMI_NNCHAIN_W1_MAXS");
-    const bool w1_on = !(w1_text && atoi(w1_text) == 0) && !wgs_text && !force_single && !plain && !force_gsize;
-    const int w1_force_s = w1_s_text ? atoi(w1_s_text) : 0;
-    const int w1_cols = w1_cols_text ? (atoi(w1_cols_text) > 64 ? atoi(w1_cols_text) : 64) : NN_W1_COLS;
-    const int w1_max_s = w1_maxs_text ? atoi(w1_maxs_text) : NN_W1_MAXS;
-    const bool dcap_forced = getenv("HICMI_NNCHAIN_DCAP") != nullptr;
-    const bool w1_xcd_wide = getenv("HICMI_NNCHAIN_XCD_WIDE") != nullptr;
-    const int gsize_max = (n > NN_MWC_MAX || force_gsize) ? mwc_gsize_max_columns() : 0;
-    if (dcap < 1) dcap = 1;
-    if (dcap > NN_DMAX) dcap = NN_DMAX;
     hipLaunchKernelGGL(k_nn_init, dim3(64), dim3(256), 0, s, w, n);
-    if (w1_on) hipMemsetAsync(w.mailw, 0, NN_W1_MAIL, s);          // (its exchange numbers run on over the epochs of a map)
-    if (profile) { static const int one = 1; hipMemcpyAsync(w.state + 8, &one, sizeof(int), hipMemcpyHostToDevice, s); }
+    if (nn_w1_on(o, fallback)) hipMemsetAsync(w.mailw, 0, NN_W1_MAIL, s);      // (its exchange numbers run on over the epochs of a map)
+    if (o.profile) { static const int one = 1; hipMemcpyAsync(w.state + 8, &one, sizeof(int), hipMemcpyHostToDevice, s); }
     {
         static int hooks[2];                                     // test hooks: see NNWorkspace::state[10], [11]
-        const char* a = getenv("HICMI_NNCHAIN_TEST_LATE"); const char* b = getenv("HICMI_NNCHAIN_TEST_DIVERGE");
-        hooks[0] = (a && fallback == 0) ? atoi(a) : 0; hooks[1] = b ? atoi(b) : 0;      // (the retries run without the late-peer hook)
+        hooks[0] = fallback == 0 ? o.test_late : 0; hooks[1] = o.test_diverge;      // (the retries run without the late-peer hook)
         if (hooks[0] || hooks[1]) hipMemcpyAsync(w.state + 10, hooks, sizeof(hooks), hipMemcpyHostToDevice, s);
     }
-    const int total_steps = n - 1;
-    int n_cur = n, done = 0, interval_start = 0;
+    int total_steps = n - 1;
+    int n_cur = n, done = 0, interval_start = 0, epochs = 0;
     double *cur = W, *other = W2;
     bool cache_valid = false;                                    // w.nnval / w.nnc describe the current matrix
-    {
-        const int nwords = (n + 31) / 32, nw4 = (nwords + 3) & ~3;
-        size_t lds_max = align16((size_t)nw4 * 8 + (size_t)n * 2);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_nn_epoch<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_nn_epoch<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
-        const int nc = n < NN_NC_MAX ? n : NN_NC_MAX, ncw4 = (((nc + 31) / 32) + 3) & ~3;
-        size_t lds_nc = align16((size_t)ncw4 * 12 + (size_t)((nc + 7) & ~7) * 4);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_nn_epoch_nc<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_nc);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_nn_epoch_nc<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_nc);
-        const int mc = n < NN_MWC_MAX ? n : NN_MWC_MAX, mcw4 = (((mc + 31) / 32) + 3) & ~3;
-        size_t lds_mc = align16((size_t)mcw4 * 12 + (size_t)((mc + 7) & ~7) * 4);
-        mwc_set_lds((int)lds_mc);
-    }
     while (done < total_steps) {
-        const int nwords = (n_cur + 31) / 32, nw4 = (nwords + 3) & ~3;
-        const size_t lds = align16((size_t)nw4 * 8 + (size_t)n_cur * 2);
-        const bool sliced = wgs > 1 && n_cur >= mw_from;
-        const int wgs_e = n_cur >= w16_from ? 16 : wgs;            // this epoch's width (k_nn_epoch_mwc only)
-        // rows beyond 32,768 columns (or HICMI_NNCHAIN_GSIZE=1: all, for the tests): cluster sizes in global memory, the
-        // cache alone in LDS - 64,000 columns fit; 8 or 16 slices
-        const bool gsize = wgs_e >= 8 && (n_cur > NN_MWC_MAX || force_gsize) && n_cur <= gsize_max;
-        int w1_S = 0, w1_slice = 0; size_t w1_lds = 0;
-        bool flush_needed = true;
-        int dcap_e = dcap;                                          // merges of this epoch
-        if (w1_on && w1_plan(n_cur, w1_cols, w1_max_s, w1_force_s, &w1_S, &w1_slice, &w1_lds)) {
-            if (!cache_valid || (refresh_below > 0 && n_cur <= refresh_below)) hipLaunchKernelGGL(k_nn_rowmin, dim3(n_cur), dim3(256), 0, s, cur, ldw, n_cur, w);
-            cache_valid = true;
-            tell();
-            // the one-wave kernel renormalises its time stamps itself: an epoch runs until the next compaction is due
-            // (half of the columns have merged away), at least 256 merges; HICMI_NNCHAIN_DCAP still forces a length
-            if (!dcap_forced) {
-                const int until = compact ? (n - done) - (int)(((int64_t)n_cur * cnum) / cden) : 4096;
-                dcap_e = until > 256 ? until : 256;
-            }
-            // all parties on one XCD while they fit there together: 32 CUs x the workgroups a CU's LDS holds
-            int xcc = (fallback >= 1 ? -1 : w1_xcc_env());
-            if (xcc >= 0) {
-                const int per_cu = (int)((160 * 1024) / (w1_lds + 2048));
-                if (w1_S > 32 * per_cu) {
-                    // too many parties for one XCD: spread out as before - or (HICMI_NNCHAIN_XCD_WIDE=1, A/B) fewer, wider slices
-                    int S2 = 0, slice2 = 0; size_t lds2 = 0;
-                    if (w1_xcd_wide && w1_force_s <= 0 && w1_plan(n_cur, w1_cols, 32 * per_cu, 0, &S2, &slice2, &lds2) &&
-                        S2 <= 32 * (int)((160 * 1024) / (lds2 + 2048))) { w1_S = S2; w1_slice = slice2; w1_lds = lds2; }
-                    else xcc = -1;
-                }
-            }
-            // test hook: HICMI_NNCHAIN_TEST_ROLLCALL=k makes epoch k's roll call (1-based) wait for a party that never comes
-            const char* rc_text = getenv("HICMI_NNCHAIN_TEST_ROLLCALL");
-            launch_w1(profile, w1_S, w1_slice, w1_lds, s, cur, ldw, n_cur, chain, zraw, w, dcap_e, total_steps, xcc,
-                      rc_text && atoi(rc_text) == epochs + 1);
+        const NNEpochPlan p = nn_plan(o, n, n_cur, done, fallback, cache_valid);
+        if (p.rowmin) hipLaunchKernelGGL(k_nn_rowmin, dim3(n_cur), dim3(256), 0, s, cur, ldw, n_cur, w);
+        cache_valid = p.kind != NN_PLAIN;
+        tell();
+        int dcap = p.dcap;
+        void* args[] = {&cur, &ldw, &n_cur, &chain, &zraw, &w, &dcap, &total_steps, nullptr, nullptr, nullptr, nullptr};
+        if (p.kind == NN_W1) {
+            int slice = p.slice, S = p.grid, xcc = p.xcc, need = S;
+            args[8] = &slice; args[9] = &S; args[10] = &xcc; args[11] = &need;
+            const int t = log2_small(p.trips);
+            if (p.xcc >= 0) {
+                // LOCAL (see the kernel), and behind it the launch that takes over if it gives up; test hook: epoch k's roll call
+                // (1-based) waits for a party that never comes
+                if (o.test_rollcall == epochs + 1) need = 0x40000000;
+                hipMemsetAsync(w.state + 15, 0, sizeof(int), s);
+                hipLaunchKernel(kW1[t][prof][1], dim3(16 * S), dim3(64), args, p.lds, s);
+                xcc = -2; need = S;
+                hipLaunchKernel(kW1[t][0][0], dim3(S), dim3(64), args, p.lds, s);
+            } else hipLaunchKernel(kW1[t][prof][0], dim3(S), dim3(64), args, p.lds, s);
             hipLaunchKernelGGL(k_nn_settle, dim3((n_cur + 255) / 256), dim3(256), 0, s, w, n_cur);
-            hipLaunchKernelGGL(k_nn_check_hashes, dim3(1), dim3(64), 0, s, w, w1_S);
-            flush_needed = false;                                   // it keeps the matrix symmetric itself
-        }
-        else if (sliced && !plain && (n_cur <= NN_MWC_MAX || gsize)) {
-            // column slices + neighbour cache + the next scan fused into the update (k_nn_epoch_mwc)
-            if (!cache_valid || (refresh_below > 0 && n_cur <= refresh_below)) hipLaunchKernelGGL(k_nn_rowmin, dim3(n_cur), dim3(256), 0, s, cur, ldw, n_cur, w);
-            cache_valid = true;
-            tell();
-            const size_t lds_c = align16((size_t)nw4 * 12 + (size_t)((n_cur + 7) & ~7) * (gsize ? 2 : 4));
+            hipLaunchKernelGGL(k_nn_check_hashes, dim3(1), dim3(64), 0, s, w, S);
+        } else if (p.kind == NN_MWC) {
             hipMemsetAsync(reinterpret_cast<unsigned char*>(w.state) + 128, 0, 1152, s);      // mailboxes
-            launch_mwc(wgs_e, profile, lds_c, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps, gsize);
-            hipLaunchKernelGGL(k_nn_check_replicas, dim3((NN_DMAX + 255) / 256), dim3(256), 0, s, w, wgs_e);
-        }
-        else if (!plain && n_cur <= NN_NC_MAX) {
-            if (!cache_valid || (refresh_below > 0 && n_cur <= refresh_below)) hipLaunchKernelGGL(k_nn_rowmin, dim3(n_cur), dim3(256), 0, s, cur, ldw, n_cur, w);
-            cache_valid = true;
-            tell();
-            const size_t lds_nc = align16((size_t)nw4 * 12 + (size_t)((n_cur + 7) & ~7) * 4);
-            if (profile) hipLaunchKernelGGL(k_nn_epoch_nc<true>, dim3(1), dim3(NN_THREADS), lds_nc, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps);
-            else hipLaunchKernelGGL(k_nn_epoch_nc<false>, dim3(1), dim3(NN_THREADS), lds_nc, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps);
-        }
-        else {
-            tell();
-            if (profile) hipLaunchKernelGGL(k_nn_epoch<true>, dim3(1), dim3(NN_THREADS), lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps);
-            else hipLaunchKernelGGL(k_nn_epoch<false>, dim3(1), dim3(NN_THREADS), lds, s, cur, ldw, n_cur, chain, zraw, w, dcap, total_steps);
-            cache_valid = false;
+            const void* f = p.gsize ? kMwcG[p.grid == 16][prof] : kMwc[log2_small(p.grid) - 1][prof];
+            hipLaunchKernel(f, dim3(p.grid), dim3(NN_THREADS), args, p.lds, s);
+            hipLaunchKernelGGL(k_nn_check_replicas, dim3((NN_DMAX + 255) / 256), dim3(256), 0, s, w, p.grid);
+        } else {
+            hipLaunchKernel(p.kind == NN_NC ? kEpochNc[prof] : kEpoch[prof], dim3(1), dim3(NN_THREADS), args, p.lds, s);
         }
         epochs++;
-        const int did = total_steps - done < dcap_e ? total_steps - done : dcap_e;
-        done += did;
+        done += total_steps - done < p.dcap ? total_steps - done : p.dcap;
         if (done >= total_steps) break;
-        if (flush_needed) hipLaunchKernelGGL(k_nn_flush, dim3((n_cur + 255) / 256, dcap), dim3(256), 0, s, cur, ldw, n_cur, w);
+        if (p.flush) hipLaunchKernelGGL(k_nn_flush, dim3((n_cur + 255) / 256, p.dcap), dim3(256), 0, s, cur, ldw, n_cur, w);
+        // The matrix is compacted - live rows and columns copied into the other buffer - when HALF of its columns have
+        // merged away (DESIGN.md section 5 records the fractions that were measured).
         const int live = n - done;
-        if (compact && other && live >= 2 && (int64_t)live * cden <= (int64_t)n_cur * cnum) {
+        if (o.compact && other && live >= 2 && (int64_t)live * 2 <= (int64_t)n_cur) {
             hipLaunchKernelGGL(k_nn_translate, dim3((done - interval_start + 255) / 256), dim3(256), 0, s, zraw, interval_start,
                                done, w);
             interval_start = done;

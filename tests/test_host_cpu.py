@@ -358,3 +358,39 @@ def test_pairwise_leaf_tables_hold_every_chunk():
     assert max(leaves) == 65 and leaves[8192] == 64 and leaves[7689] == 65
     assert max(leaves) <= max_leaves
     assert max(depth) + 1 <= 16
+
+
+def _asm_templates(text):
+    """The template string of every asm statement in a HIP source (macro bodies included): the string literals that follow
+    `asm` / `asm volatile` / `__asm__` up to the first operand colon or the closing parenthesis."""
+    text = re.sub(r"\\\n", " ", text)                                   # macro continuation lines
+    text = re.sub(r"//[^\n]*", "", text)
+    for m in re.finditer(r"\b(?:asm|__asm__)\s*(?:volatile\s*|__volatile__\s*)?\(", text):
+        pieces, pos = [], m.end()
+        while True:
+            lit = re.compile(r'\s*"((?:[^"\\]|\\.)*)"').match(text, pos)
+            if not lit:
+                break
+            pieces.append(lit.group(1))
+            pos = lit.end()
+        yield "".join(pieces)
+
+
+def test_inline_asm_loads_wait_in_the_same_statement():
+    """A load issued from inline assembly is invisible to the compiler's wait-count pass: it takes the destination register
+    as written when the statement ends, and may copy, spill or reuse it before the data lands.  So an asm statement that
+    loads (a *_load_* or ds_read* mnemonic) must also wait for it (s_waitcnt); loads that are waited for later go through
+    compiler-visible builtins instead."""
+    csrc = os.path.join(ROOT, "hic_genome_assembler_amd", "csrc")
+    loads = re.compile(r"\b(?:[a-z]+_load_[a-z0-9_]*|ds_read[a-z0-9_]*)\b")
+    checked, bad = 0, []
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith(".hip"):
+            continue
+        with open(os.path.join(csrc, name)) as fh:
+            for tmpl in _asm_templates(fh.read()):
+                checked += 1
+                if loads.search(tmpl) and "s_waitcnt" not in tmpl:
+                    bad.append("%s: %s" % (name, tmpl))
+    assert checked > 10
+    assert not bad, bad
