@@ -47,6 +47,8 @@ SIGNATURES = {
     "hicmi_filter_scan": (ctypes.c_int, [_vp, c_i64, c_i64, c_i64, c_i64, c_dbl, _vp, _vp]),
     "hicmi_first_pass_cuts": (ctypes.c_int, [_vp, c_i64, c_i64, c_dbl, _vp, c_i64, _vp, _vp, c_i64, _vp]),
     "hicmi_filter_cuts": (ctypes.c_int, [_vp, _vp, c_i64, c_dbl, _vp, c_i64, _vp, _vp]),
+    "hicmi_first_pass_cuts_multi": (ctypes.c_int, [_vp, c_i64, _vp, _vp, c_dbl, _vp, c_i64, _vp, _vp, c_i64, _vp]),
+    "hicmi_filter_cuts_multi": (ctypes.c_int, [_vp, c_i64, _vp, _vp, _vp, _vp, c_i64, _vp, _vp]),
     "hicmi_hypergeom_decide": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, c_dbl]),
     "hicmi_hypergeom_sf": (c_dbl, [c_i64, c_i64, c_i64, c_i64]),
     "hicmi_selftest_division": (ctypes.c_int, [_vp, ctypes.c_uint64, c_i64, ctypes.POINTER(ctypes.c_uint64)]),
@@ -357,6 +359,45 @@ class Context:
         _check(self._lib.hicmi_filter_cuts(self._h, _ptr(cuts), len(cuts), float(psig), _ptr(out), self.n,
                                            ctypes.byref(m), ctypes.byref(warned)))
         return [int(v) for v in out[:m.value]], int(warned.value)
+
+    SCAN_MAX_SETS = 64                                     # HICMI_SCAN_MAX_SETS: larger grids go in chunks
+
+    def first_pass_cuts_multi(self, sets, psig):
+        """first_pass_cuts for many (min_size, stop_ind) sets in lock step (hicmi_first_pass_cuts_multi): one
+        (cuts, [(M before, M after), ...]) per set, in order."""
+        out = []
+        n = self.n
+        for c0 in range(0, len(sets), self.SCAN_MAX_SETS):
+            part = sets[c0:c0 + self.SCAN_MAX_SETS]
+            k = len(part)
+            ms = np.array([int(a) for a, _b in part], np.int64)
+            si = np.array([int(b) for _a, b in part], np.int64)
+            cuts = np.empty((k, n), np.int32)
+            mlog = np.empty((k, n, 2), np.int32)
+            nc, nl = np.zeros(k, np.int64), np.zeros(k, np.int64)
+            _check(self._lib.hicmi_first_pass_cuts_multi(self._h, k, _ptr(ms), _ptr(si), float(psig), _ptr(cuts), n,
+                                                         _ptr(nc), _ptr(mlog), n, _ptr(nl)))
+            out += [([int(v) for v in cuts[j, :nc[j]]], [(int(a), int(b)) for a, b in mlog[j, :nl[j]]]) for j in range(k)]
+        return out
+
+    def filter_cuts_multi(self, lists, psigs):
+        """filter_cuts for many (candidate list, psig) sets in lock step (hicmi_filter_cuts_multi): one
+        (sorted kept cuts, warnings) per set, in order.  An empty list gives ([], 0)."""
+        out = []
+        n = self.n
+        for c0 in range(0, len(lists), self.SCAN_MAX_SETS):
+            part = [np.asarray(v, dtype=np.int32) for v in lists[c0:c0 + self.SCAN_MAX_SETS]]
+            k = len(part)
+            off = np.zeros(k + 1, np.int64)
+            off[1:] = np.cumsum([len(v) for v in part])
+            cand = np.ascontiguousarray(np.concatenate(part) if off[-1] else np.zeros(1, np.int32), dtype=np.int32)
+            ps = np.array([float(v) for v in psigs[c0:c0 + self.SCAN_MAX_SETS]], np.float64)
+            kept = np.empty((k, n), np.int32)
+            m, warned = np.zeros(k, np.int64), np.zeros(k, np.int64)
+            _check(self._lib.hicmi_filter_cuts_multi(self._h, k, _ptr(off), _ptr(cand), _ptr(ps), _ptr(kept), n,
+                                                     _ptr(m), _ptr(warned)))
+            out += [([int(v) for v in kept[j, :m[j]]], int(warned[j])) for j in range(k)]
+        return out
 
     # ---- Part 2
     def p2_select(self, sel):

@@ -92,6 +92,7 @@ struct hicmi_ctx {
     // cut scan
     int32_t* d_x = nullptr; uint8_t* d_sig = nullptr; int64_t x_cap = 0;
     unsigned char* d_scan_prog = nullptr; int64_t scan_prog_cap = 0;     // device-driven scan loops: state record + lists
+    unsigned char* d_scan_multi = nullptr; size_t scan_multi_bytes = 0;  // the same for many parameter sets (the *_multi calls)
     int64_t cached_start = -1;
     double* d_tmp = nullptr; int64_t tmp_cap = 0;
     // part 2
@@ -349,7 +350,7 @@ int hicmi_destroy(hicmi_ctx* c)
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
-    free_dev(c->d_x); free_dev(c->d_sig); free_dev(c->d_tmp); free_dev(c->d_scan_prog);
+    free_dev(c->d_x); free_dev(c->d_sig); free_dev(c->d_tmp); free_dev(c->d_scan_prog); free_dev(c->d_scan_multi);
     free_dev(c->dM2); free_dev(c->d_sel); free_dev(c->d_H); free_dev(c->d_perms); free_dev(c->d_scores);
     free_dev(c->d_partial); free_dev(c->d_T);
     free_dev(c->d_scaf_start); free_dev(c->d_scaf_len); free_dev(c->d_arr_packed);
@@ -1241,6 +1242,185 @@ int hicmi_filter_cuts(hicmi_ctx* c, const int32_t* cuts_in, int64_t n_in, double
         if (kept[(size_t)e]) { if (m >= cuts_cap) return fail(HICMI_EINVAL, "filtered cuts do not fit cuts_cap"); cuts_out[m++] = (int32_t)e; }
     *n_out = m;
     if (warned_out) *warned_out = h.f_warned;
+    return HICMI_OK;
+}
+
+// ---- many parameter sets in lock step (k_part1_scan.hip: k_cut_rows_multi + k_*_decide_multi) ----------------------
+// One allocation, sized from n_sets x n: [ScanState x SCAN_MAX_SETS][psig x SCAN_MAX_SETS], then per set
+// x n, cuts n, M log 2n, alt n, seg 3n, seg_x n int32 and sig n, filt n, prev n bytes (39 B per row and set).
+static_assert(SCAN_MAX_SETS == HICMI_SCAN_MAX_SETS, "hicmi.h and the kernels disagree on the set cap");
+
+struct ScanMulti {
+    ScanState* st; double* psig; int32_t *x, *cuts, *mlog, *alt, *seg, *seg_x; uint8_t *sig, *filt, *prev;
+};
+
+static int ensure_scan_multi(hicmi_ctx* c, int sets, ScanMulti& m)
+{
+    const size_t n = (size_t)c->n, S = (size_t)sets;
+    const size_t head = (sizeof(ScanState) * SCAN_MAX_SETS + sizeof(double) * SCAN_MAX_SETS + 255) & ~(size_t)255;
+    const size_t bytes = head + S * n * (sizeof(int32_t) * 9 + 3) + 64;
+    if (c->scan_multi_bytes < bytes || !c->d_scan_multi) {
+        free_dev(c->d_scan_multi); c->d_scan_multi = nullptr; c->scan_multi_bytes = 0;
+        HIPCHK(hipMalloc((void**)&c->d_scan_multi, bytes));
+        c->scan_multi_bytes = bytes;
+    }
+    unsigned char* b = c->d_scan_multi;
+    m.st = reinterpret_cast<ScanState*>(b);
+    m.psig = reinterpret_cast<double*>(b + sizeof(ScanState) * SCAN_MAX_SETS);
+    m.x = reinterpret_cast<int32_t*>(b + head);
+    m.cuts = m.x + S * n; m.mlog = m.cuts + S * n; m.alt = m.mlog + 2 * S * n; m.seg = m.alt + S * n; m.seg_x = m.seg + 3 * S * n;
+    m.sig = reinterpret_cast<uint8_t*>(m.seg_x + S * n); m.filt = m.sig + S * n; m.prev = m.filt + S * n;
+    return HICMI_OK;
+}
+
+static int scan_share()
+{
+    const char* e = getenv("HICMI_SCAN_SHARE");                    // "0": every set counts its own rows (the A/B)
+    return e && !strcmp(e, "0") ? 0 : 1;
+}
+
+// Batches of lock-step scans until every set's loop has ended; the records are read once per batch, and the runaway
+// guard of run_scan_program applies to every set on its own.
+static int run_scan_multi(hicmi_ctx* c, std::vector<ScanState>& h, const ScanMulti& m, const std::vector<double>& psig,
+                          const std::vector<int64_t>& max_scans, const std::function<void(int)>& enqueue)
+{
+    const size_t S = h.size();
+    int rc = upload(c, m.st, h.data(), sizeof(ScanState) * S);
+    if (rc) return rc;
+    rc = upload(c, m.psig, psig.data(), sizeof(double) * S);
+    if (rc) return rc;
+    const int pairs = 32;
+    int64_t batches = 0;
+    for (int64_t issued = 0; ; issued += pairs) {
+        bool all_done = true;
+        for (size_t k = 0; k < S; k++) {
+            if (h[k].done) continue;
+            all_done = false;
+            if (issued > max_scans[k] + pairs)
+                return fail(HICMI_ESTATE, "scan loop of set %d did not end after %lld scans", (int)k, (long long)issued);
+        }
+        if (all_done) break;
+        {
+            Timed t(c, F_CUT_COUNT, 0.0);
+            enqueue(pairs);
+        }
+        HIPCHK(hipGetLastError());
+        batches++;
+        rc = download(c, h.data(), m.st, sizeof(ScanState) * S);
+        if (rc) return rc;
+    }
+    int64_t scans = 0; double bytes = 0;
+    for (const ScanState& r : h) { scans += r.scans; bytes += (double)r.bytes; }
+    c->launches[F_CUT_COUNT] += scans - batches;                  // reported per set and scan, as run_scan_program does
+    c->launches[F_HYPER_FLAGS] += scans;
+    c->bytes[F_CUT_COUNT] += bytes;
+    c->cached_start = -1;
+    return HICMI_OK;
+}
+
+int hicmi_first_pass_cuts_multi(hicmi_ctx* c, int64_t n_sets, const int64_t* min_size, const int64_t* stop_ind, double psig,
+                                int32_t* cuts_out, int64_t cuts_cap, int64_t* n_cuts_out, int32_t* m_log_out, int64_t log_cap,
+                                int64_t* n_log_out)
+{
+    if (!c || !min_size || !stop_ind || !cuts_out || !n_cuts_out || !n_log_out || (log_cap > 0 && !m_log_out))
+        return fail(HICMI_EINVAL, "bad arguments");
+    if (n_sets < 1 || n_sets > SCAN_MAX_SETS) return fail(HICMI_EINVAL, "n_sets must be in [1, %d]", SCAN_MAX_SETS);
+    if (!c->have_rank) return fail(HICMI_EINVAL, "hicmi_rank_matrix has not run");
+    if (c->shard_stride != 1) return fail(HICMI_EINVAL, "the device-driven scan loops need the whole rank matrix (no row shard)");
+    for (int64_t k = 0; k < n_sets; k++)
+        if (min_size[k] < 1) return fail(HICMI_EINVAL, "min_size must be >= 1 (set %lld)", (long long)k);
+    const int64_t n = c->n;
+    HIPCHK(hipSetDevice(c->device));
+    ScanMulti m;
+    int rc = ensure_scan_multi(c, (int)n_sets, m);
+    if (rc) return rc;
+    std::vector<ScanState> h((size_t)n_sets);
+    for (int64_t k = 0; k < n_sets; k++) {                         // hicmi_first_pass_cuts' record, set by set
+        ScanState& r = h[(size_t)k];
+        memset(&r, 0, sizeof(r));
+        r.mode = 0; r.start = 0; r.M = n; r.recount = 1;
+        r.min_size = (int)std::min<int64_t>(min_size[k], n + 1); r.stop_ind = (int)std::min<int64_t>(stop_ind[k], INT32_MAX);
+    }
+    const int lcap = (int)n;
+    const int share = scan_share();
+    rc = run_scan_multi(c, h, m, std::vector<double>((size_t)n_sets, psig), std::vector<int64_t>((size_t)n_sets, 6 * n),
+                        [&](int pairs) {
+        launch_first_pass_multi_pairs(c->dRank, c->ldr, (int)n, (int)n_sets, m.st, m.x, m.sig, m.psig, share, m.cuts, m.mlog,
+                                      lcap, pairs, c->stream);
+    });
+    if (rc) return rc;
+    for (int64_t k = 0; k < n_sets; k++) {
+        const ScanState& r = h[(size_t)k];
+        if (r.n_cuts > cuts_cap) return fail(HICMI_EINVAL, "%d cuts of set %lld do not fit cuts_cap", r.n_cuts, (long long)k);
+        if (r.n_log > lcap || r.n_log > log_cap) return fail(HICMI_EINVAL, "%d M changes of set %lld do not fit the log", r.n_log, (long long)k);
+    }
+    for (int64_t k = 0; k < n_sets; k++) {
+        const ScanState& r = h[(size_t)k];
+        if (r.n_cuts) { rc = download(c, cuts_out + k * cuts_cap, m.cuts + k * n, sizeof(int32_t) * (size_t)r.n_cuts); if (rc) return rc; }
+        if (r.n_log) { rc = download(c, m_log_out + 2 * k * log_cap, m.mlog + 2 * k * n, sizeof(int32_t) * 2 * (size_t)r.n_log); if (rc) return rc; }
+        n_cuts_out[k] = r.n_cuts; n_log_out[k] = r.n_log;
+    }
+    return HICMI_OK;
+}
+
+int hicmi_filter_cuts_multi(hicmi_ctx* c, int64_t n_sets, const int64_t* cand_off, const int32_t* cuts_in, const double* psig,
+                            int32_t* cuts_out, int64_t cuts_cap, int64_t* n_out, int64_t* warned_out)
+{
+    if (!c || !cand_off || !psig || !cuts_out || !n_out || !warned_out) return fail(HICMI_EINVAL, "bad arguments");
+    if (n_sets < 1 || n_sets > SCAN_MAX_SETS) return fail(HICMI_EINVAL, "n_sets must be in [1, %d]", SCAN_MAX_SETS);
+    if (!c->have_rank) return fail(HICMI_EINVAL, "hicmi_rank_matrix has not run");
+    if (c->shard_stride != 1) return fail(HICMI_EINVAL, "the device-driven scan loops need the whole rank matrix (no row shard)");
+    const int64_t n = c->n;
+    if (cand_off[0] != 0) return fail(HICMI_EINVAL, "cand_off[0] must be 0");
+    for (int64_t k = 0; k < n_sets; k++) {
+        const int64_t a = cand_off[k], b = cand_off[k + 1];
+        if (b < a || b - a > n) return fail(HICMI_EINVAL, "candidate list %lld: bad offsets", (long long)k);
+        if (b > a && !cuts_in) return fail(HICMI_EINVAL, "bad arguments");
+        for (int64_t i = a; i < b; i++)
+            if (cuts_in[i] < 0 || cuts_in[i] >= n || (i > a && cuts_in[i] <= cuts_in[i - 1]))
+                return fail(HICMI_EINVAL, "cuts must be ascending indices in [0, n) (set %lld)", (long long)k);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    ScanMulti m;
+    int rc = ensure_scan_multi(c, (int)n_sets, m);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(m.filt, 0, 2 * (size_t)n_sets * (size_t)n, c->stream));   // filtered = {}, prev_filtered = {}
+    std::vector<ScanState> h((size_t)n_sets);
+    std::vector<int64_t> max_scans((size_t)n_sets);
+    const int max_rows = (int)std::min<int64_t>(n, n / 5 + 1);
+    for (int64_t k = 0; k < n_sets; k++) {                         // hicmi_filter_cuts' record, set by set
+        const int64_t a = cand_off[k], n_in = cand_off[k + 1] - a;
+        ScanState& r = h[(size_t)k];
+        memset(&r, 0, sizeof(r));
+        r.mode = 1; r.start = 0; r.M = n; r.recount = 1;
+        r.MD = (int)(n / 5);
+        r.n_alt = (int)n_in; r.f_max_rounds = (int)std::min<int64_t>(10 * n_in, INT32_MAX);
+        r.cut = n_in ? cuts_in[a] : 0;
+        r.n_rows = max_rows;
+        r.done = n_in == 0;                                        // nothing to filter
+        max_scans[(size_t)k] = std::min<int64_t>((int64_t)4000000, 20 * n_in * n_in * 10 + 1000);
+        if (n_in) { rc = upload(c, m.alt + k * n, cuts_in + a, sizeof(int32_t) * (size_t)n_in); if (rc) return rc; }
+    }
+    const int share = scan_share();
+    rc = run_scan_multi(c, h, m, std::vector<double>(psig, psig + n_sets), max_scans, [&](int pairs) {
+        launch_filter_multi_pairs(c->dRank, c->ldr, (int)n, max_rows, (int)n_sets, m.st, m.x, m.sig, m.psig, share, m.alt, m.filt,
+                                  m.prev, m.seg, m.seg_x, pairs, c->stream);
+    });
+    if (rc) return rc;
+    std::vector<uint8_t> kept((size_t)n_sets * (size_t)n);
+    rc = download(c, kept.data(), m.filt, kept.size());
+    if (rc) return rc;
+    for (int64_t k = 0; k < n_sets; k++) {
+        int64_t cnt = 0;
+        const uint8_t* f = kept.data() + (size_t)k * (size_t)n;
+        for (int64_t e = 0; e < n; e++)
+            if (f[e]) {
+                if (cnt >= cuts_cap) return fail(HICMI_EINVAL, "filtered cuts of set %lld do not fit cuts_cap", (long long)k);
+                cuts_out[k * cuts_cap + cnt++] = (int32_t)e;
+            }
+        n_out[k] = cnt;
+        warned_out[k] = h[(size_t)k].f_warned;
+    }
     return HICMI_OK;
 }
 

@@ -178,6 +178,15 @@ void launch_first_pass_pairs(const uint16_t* rank, int64_t ldr, int n, ScanState
 void launch_filter_pairs(const uint16_t* rank, int64_t ldr, int n, int max_rows, ScanState* st, int32_t* x, uint8_t* sig,
                          double psig, int32_t* alt, uint8_t* filt, uint8_t* prev, int32_t* seg, int32_t* seg_x, int pairs,
                          hipStream_t s);
+// The same loops for up to SCAN_MAX_SETS parameter sets in lock step: records st[0..n_sets), per-set lists at k * n
+// (mlog at k * 2n, seg at k * 3n), per-set psig; `share`: sets that recount at the same arguments share the count.
+static constexpr int SCAN_MAX_SETS = 64;
+void launch_first_pass_multi_pairs(const uint16_t* rank, int64_t ldr, int n, int n_sets, ScanState* st, int32_t* x, uint8_t* sig,
+                                   const double* psig, int share, int32_t* cuts, int32_t* mlog, int log_cap, int pairs,
+                                   hipStream_t s);
+void launch_filter_multi_pairs(const uint16_t* rank, int64_t ldr, int n, int max_rows, int n_sets, ScanState* st, int32_t* x,
+                               uint8_t* sig, const double* psig, int share, int32_t* alt, uint8_t* filt, uint8_t* prev,
+                               int32_t* seg, int32_t* seg_x, int pairs, hipStream_t s);
 
 // The value lane ^ M holds, M a power of two below 64, without the LDS crossbar (ds_bpermute, which __shfl_xor compiles
 // to, issues at a fraction of the VALU rate and was what the bitonic networks' in-wave stages waited for): DPP quad

@@ -20,6 +20,32 @@
 namespace hicmi {
 
 // ---- the scan itself ------------------------------------------------------------------------------------------------
+// one lane's part of #{ j in [lo, end) : r[j] < thr } (a workgroup of 256 lanes covers the segment)
+__device__ __forceinline__ int row_count_partial(const uint16_t* __restrict__ r, int lo, int end, int thr, int tid)
+{
+    int cnt = 0;
+    int body0 = (lo + 7) & ~7;                        // first 16-byte aligned element
+    if (body0 > end) body0 = end;
+    const int body1 = body0 + ((end - body0) & ~7);
+    for (int j = lo + tid; j < body0; j += 256) cnt += (int)r[j] < thr;
+    for (int j = body0 + tid * 8; j < body1; j += 256 * 8) {
+        uint4 q = *reinterpret_cast<const uint4*>(r + j);
+        cnt += (int)(q.x & 0xffffu) < thr; cnt += (int)(q.x >> 16) < thr;
+        cnt += (int)(q.y & 0xffffu) < thr; cnt += (int)(q.y >> 16) < thr;
+        cnt += (int)(q.z & 0xffffu) < thr; cnt += (int)(q.z >> 16) < thr;
+        cnt += (int)(q.w & 0xffffu) < thr; cnt += (int)(q.w >> 16) < thr;
+    }
+    for (int j = body1 + tid; j < end; j += 256) cnt += (int)r[j] < thr;
+    return cnt;
+}
+
+// the flag of entry t from its count (mode 0: L = t, mode 1: L = thr = cut - start)
+__device__ __forceinline__ uint8_t row_flag(int mode, int total, long long M, int t, int thr, double psig)
+{
+    if (mode == 0) return hypergeom_decide((int64_t)total, M, (int64_t)t, (int64_t)t, psig) == 0 ? 0 : 1;
+    return hypergeom_decide((int64_t)total, M, (int64_t)thr, (int64_t)thr, psig) == 1 ? 1 : 0;
+}
+
 // mode 0 (first pass, S2C:455-469): entry t = row start + t counts #{ j in [start, start + t] : rank < t } and tests
 //   hyper_geom(x, M, t, t) >= psig -> 0, otherwise (NaN included) 1; entry 0 is 0.
 // mode 1 (filter, S2C:626-636): entry t < n_rows counts #{ j in [start, cut] : rank < cut - start } and tests
@@ -40,21 +66,7 @@ __global__ __launch_bounds__(256) void k_cut_rows(const uint16_t* __restrict__ r
     const int thr = hi - lo;
     int total;
     if (st->recount) {
-        const uint16_t* __restrict__ r = rank + (int64_t)i * ldr;
-        int cnt = 0;
-        const int end = hi + 1;                       // half-open [lo, end)
-        int body0 = (lo + 7) & ~7;                    // first 16-byte aligned element
-        if (body0 > end) body0 = end;
-        const int body1 = body0 + ((end - body0) & ~7);
-        for (int j = lo + tid; j < body0; j += 256) cnt += (int)r[j] < thr;
-        for (int j = body0 + tid * 8; j < body1; j += 256 * 8) {
-            uint4 q = *reinterpret_cast<const uint4*>(r + j);
-            cnt += (int)(q.x & 0xffffu) < thr; cnt += (int)(q.x >> 16) < thr;
-            cnt += (int)(q.y & 0xffffu) < thr; cnt += (int)(q.y >> 16) < thr;
-            cnt += (int)(q.z & 0xffffu) < thr; cnt += (int)(q.z >> 16) < thr;
-            cnt += (int)(q.w & 0xffffu) < thr; cnt += (int)(q.w >> 16) < thr;
-        }
-        for (int j = body1 + tid; j < end; j += 256) cnt += (int)r[j] < thr;
+        int cnt = row_count_partial(rank + (int64_t)i * ldr, lo, hi + 1, thr, tid);
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
         if ((tid & 63) == 0) s_part[tid >> 6] = cnt;
@@ -66,19 +78,13 @@ __global__ __launch_bounds__(256) void k_cut_rows(const uint16_t* __restrict__ r
         if (tid != 0) return;
         total = x[t];                                 // the same start: only M has changed (S2C:473-483)
     }
-    const int64_t M = st->M;
-    if (mode == 0) {
-        const int dec = hypergeom_decide((int64_t)total, M, (int64_t)t, (int64_t)t, psig);
-        sig[t] = dec == 0 ? 0 : 1;
-    } else {
-        const int dec = hypergeom_decide((int64_t)total, M, (int64_t)thr, (int64_t)thr, psig);
-        sig[t] = dec == 1 ? 1 : 0;
-    }
+    sig[t] = row_flag(mode, total, st->M, t, thr, psig);
 }
 
 // ---- first pass: what happens between two scans (S2C:430-511 and 513-551) --------------------------------------------
-__global__ __launch_bounds__(1024) void k_first_pass_decide(int n, ScanState* __restrict__ st, const uint8_t* __restrict__ sig,
-                                                            int32_t* __restrict__ cuts, int32_t* __restrict__ mlog, int log_cap)
+// (a device function: k_first_pass_decide runs it for one set, k_first_pass_decide_multi for set blockIdx.x)
+__device__ __forceinline__ void first_pass_decide(int n, ScanState* __restrict__ st, const uint8_t* __restrict__ sig,
+                                                  int32_t* __restrict__ cuts, int32_t* __restrict__ mlog, int log_cap)
 {
     __shared__ int s_sum[16];
     __shared__ int s_first;
@@ -130,6 +136,12 @@ __global__ __launch_bounds__(1024) void k_first_pass_decide(int n, ScanState* __
     st->start = ind; st->M = n - ind; st->loop_count = 0; st->recount = 1;
 }
 
+__global__ __launch_bounds__(1024) void k_first_pass_decide(int n, ScanState* __restrict__ st, const uint8_t* __restrict__ sig,
+                                                            int32_t* __restrict__ cuts, int32_t* __restrict__ mlog, int log_cap)
+{
+    first_pass_decide(n, st, sig, cuts, mlog, log_cap);
+}
+
 // ---- filter: what happens between two scans (S2C:553-727) ------------------------------------------------------------
 // Lists live in global memory behind the state record: `alt` (the candidate cuts still in play, `alt_off` = what
 // altered[keep_from:] has dropped), `filt` / `prev` (the dictionaries `filtered` / `prev_filtered` as one byte per index).
@@ -151,10 +163,11 @@ __device__ __forceinline__ void filter_set_scan(ScanState* st, const int32_t* al
 
 static constexpr int FD_CAP = 2048;                     // candidates kept in LDS; longer lists are walked in global memory
 
-__global__ __launch_bounds__(1024) void k_filter_decide(int n, ScanState* __restrict__ st, const uint8_t* __restrict__ sig,
-                                                        int32_t* __restrict__ alt, uint8_t* __restrict__ filt,
-                                                        uint8_t* __restrict__ prev, int32_t* __restrict__ seg_g,
-                                                        int32_t* __restrict__ seg_x_g, double psig)
+// (a device function: k_filter_decide runs it for one set, k_filter_decide_multi for set blockIdx.x)
+__device__ __forceinline__ void filter_decide(int n, ScanState* __restrict__ st, const uint8_t* __restrict__ sig,
+                                              int32_t* __restrict__ alt, uint8_t* __restrict__ filt,
+                                              uint8_t* __restrict__ prev, int32_t* __restrict__ seg_g,
+                                              int32_t* __restrict__ seg_x_g, double psig)
 {
     __shared__ int s_alt[FD_CAP], s_seg[3 * FD_CAP], s_seg_x[FD_CAP];
     __shared__ int s_nseg, s_last, s_phase, s_diff, s_wave[16];
@@ -271,6 +284,106 @@ __global__ __launch_bounds__(1024) void k_filter_decide(int n, ScanState* __rest
     if (tid == 0 && total) { __threadfence_block(); filter_begin_round(st, n); filter_set_scan(st, alt, n); }
 }
 
+__global__ __launch_bounds__(1024) void k_filter_decide(int n, ScanState* __restrict__ st, const uint8_t* __restrict__ sig,
+                                                        int32_t* __restrict__ alt, uint8_t* __restrict__ filt,
+                                                        uint8_t* __restrict__ prev, int32_t* __restrict__ seg_g,
+                                                        int32_t* __restrict__ seg_x_g, double psig)
+{
+    filter_decide(n, st, sig, alt, filt, prev, seg_g, seg_x_g, psig);
+}
+
+// ---- many parameter sets in lock step (hicmi_first_pass_cuts_multi / hicmi_filter_cuts_multi) -------------------------
+// Set k has its own record st[k] and its own lists at k * n (k * 2n for the M log, k * 3n for the segments); a step is
+// one count launch for every live set and one decide launch with a workgroup per set.  A set that is done costs its
+// decide workgroup one load and no work in the count launch.
+//
+// The count launch deals out (set, row) work items grid-stride, numbered set by set from a prefix over the live sets'
+// row counts that every workgroup builds from the records.  Counts depend on the start only (mode 0) or on (start, cut)
+// (mode 1) - never on M, min_size or psig - so a set that recounts at the same arguments as a lower-numbered set
+// (`share`) brings no items of its own: the lower set's workgroup hands it the count and it takes its own flag from it.
+__global__ __launch_bounds__(256) void k_cut_rows_multi(const uint16_t* __restrict__ rank, int64_t ldr, int n, int n_sets,
+                                                        const ScanState* __restrict__ st, int32_t* __restrict__ x,
+                                                        uint8_t* __restrict__ sig, const double* __restrict__ psig, int share)
+{
+    __shared__ int s_pre[SCAN_MAX_SETS + 1];              // work items of the sets before k
+    __shared__ int s_lead[SCAN_MAX_SETS];                 // the set whose items serve set k (-1: done)
+    __shared__ int s_key[SCAN_MAX_SETS][4];               // live, mode, start, cut (-1 for a set that reuses its counts)
+    __shared__ int s_part[4];
+    const int tid = threadIdx.x;
+    if (tid < SCAN_MAX_SETS) {
+        int live = 0, mode = 0, start = 0, cut = 0, rows = 0;
+        if (tid < n_sets && !st[tid].done) {
+            live = 1; mode = st[tid].mode; start = st[tid].start;
+            cut = st[tid].recount ? (mode == 0 ? 0 : st[tid].cut) : -1;
+            rows = mode == 0 ? n - start : st[tid].n_rows;
+        }
+        s_key[tid][0] = live; s_key[tid][1] = mode; s_key[tid][2] = start; s_key[tid][3] = cut;
+        s_lead[tid] = live ? tid : -1;
+        s_pre[tid + 1] = rows;
+    }
+    __syncthreads();
+    if (tid < SCAN_MAX_SETS) {
+        int rows = s_pre[tid + 1];
+        if (share && s_key[tid][0] && s_key[tid][3] >= 0) {
+            for (int j = 0; j < tid; j++)
+                if (s_key[j][0] && s_key[j][3] == s_key[tid][3] && s_key[j][1] == s_key[tid][1] && s_key[j][2] == s_key[tid][2]) {
+                    s_lead[tid] = j; rows = 0; break;
+                }
+        }
+        int incl = rows;                                  // inclusive prefix over the 64 lanes of the first wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d, 64); if (tid >= d) incl += o; }
+        s_pre[tid + 1] = incl;
+        if (tid == 0) s_pre[0] = 0;
+    }
+    __syncthreads();
+    const int items = s_pre[n_sets];
+    for (int w = blockIdx.x; w < items; w += gridDim.x) {
+        int k = 0;
+        while (s_pre[k + 1] <= w) k++;
+        const int t = w - s_pre[k];
+        const int mode = s_key[k][1], lo = s_key[k][2];
+        if (mode == 0 && t == 0) {
+            if (tid < n_sets && s_lead[tid] == k) sig[(size_t)tid * n] = 0;
+            continue;
+        }
+        const int i = lo + t;
+        const int hi = mode == 0 ? i : st[k].cut;
+        const int thr = hi - lo;
+        if (s_key[k][3] >= 0) {                           // recount: for set k and every set it serves
+            int cnt = row_count_partial(rank + (int64_t)i * ldr, lo, hi + 1, thr, tid);
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+            if ((tid & 63) == 0) s_part[tid >> 6] = cnt;
+            __syncthreads();
+            const int total = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+            if (tid < n_sets && s_lead[tid] == k) {
+                x[(size_t)tid * n + t] = total;
+                sig[(size_t)tid * n + t] = row_flag(mode, total, st[tid].M, t, thr, psig[tid]);
+            }
+            __syncthreads();                              // (s_part is written again by the next item)
+        } else if (tid == 0) {                            // the same start as the last scan: only M has changed
+            sig[(size_t)k * n + t] = row_flag(mode, x[(size_t)k * n + t], st[k].M, t, thr, psig[k]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(1024) void k_first_pass_decide_multi(int n, ScanState* __restrict__ st, const uint8_t* __restrict__ sig,
+                                                                  int32_t* __restrict__ cuts, int32_t* __restrict__ mlog, int log_cap)
+{
+    const size_t k = blockIdx.x;
+    first_pass_decide(n, st + k, sig + k * n, cuts + k * n, mlog + k * 2 * n, log_cap);
+}
+
+__global__ __launch_bounds__(1024) void k_filter_decide_multi(int n, ScanState* __restrict__ st, const uint8_t* __restrict__ sig,
+                                                              int32_t* __restrict__ alt, uint8_t* __restrict__ filt,
+                                                              uint8_t* __restrict__ prev, int32_t* __restrict__ seg_g,
+                                                              int32_t* __restrict__ seg_x_g, const double* __restrict__ psig)
+{
+    const size_t k = blockIdx.x;
+    filter_decide(n, st + k, sig + k * n, alt + k * n, filt + k * n, prev + k * n, seg_g + k * 3 * n, seg_x_g + k * n, psig[k]);
+}
+
 // ---- launchers ---------------------------------------------------------------------------------------------------------
 void launch_first_pass_pairs(const uint16_t* rank, int64_t ldr, int n, ScanState* st, int32_t* x, uint8_t* sig, double psig,
                              int32_t* cuts, int32_t* mlog, int log_cap, int pairs, hipStream_t s)
@@ -288,6 +401,26 @@ void launch_filter_pairs(const uint16_t* rank, int64_t ldr, int n, int max_rows,
     for (int k = 0; k < pairs; k++) {
         hipLaunchKernelGGL(k_cut_rows, dim3(max_rows), dim3(256), 0, s, rank, ldr, n, st, x, sig, psig);
         hipLaunchKernelGGL(k_filter_decide, dim3(1), dim3(1024), 0, s, n, st, sig, alt, filt, prev, seg, seg_x, psig);
+    }
+}
+
+void launch_first_pass_multi_pairs(const uint16_t* rank, int64_t ldr, int n, int n_sets, ScanState* st, int32_t* x, uint8_t* sig,
+                                   const double* psig, int share, int32_t* cuts, int32_t* mlog, int log_cap, int pairs,
+                                   hipStream_t s)
+{
+    for (int k = 0; k < pairs; k++) {
+        hipLaunchKernelGGL(k_cut_rows_multi, dim3(n), dim3(256), 0, s, rank, ldr, n, n_sets, st, x, sig, psig, share);
+        hipLaunchKernelGGL(k_first_pass_decide_multi, dim3(n_sets), dim3(1024), 0, s, n, st, sig, cuts, mlog, log_cap);
+    }
+}
+
+void launch_filter_multi_pairs(const uint16_t* rank, int64_t ldr, int n, int max_rows, int n_sets, ScanState* st, int32_t* x,
+                               uint8_t* sig, const double* psig, int share, int32_t* alt, uint8_t* filt, uint8_t* prev,
+                               int32_t* seg, int32_t* seg_x, int pairs, hipStream_t s)
+{
+    for (int k = 0; k < pairs; k++) {
+        hipLaunchKernelGGL(k_cut_rows_multi, dim3(max_rows), dim3(256), 0, s, rank, ldr, n, n_sets, st, x, sig, psig, share);
+        hipLaunchKernelGGL(k_filter_decide_multi, dim3(n_sets), dim3(1024), 0, s, n, st, sig, alt, filt, prev, seg, seg_x, psig);
     }
 }
 

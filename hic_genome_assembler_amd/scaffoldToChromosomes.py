@@ -303,9 +303,7 @@ def pre_process_all_matrix_breakpoints(argsorted_mat: RankMatrix, min_size=5, mi
     if _device_scan_loops(argsorted_mat.ctx) and min_size >= 1:
         # the same loop with its decisions on the device (hicmi_first_pass_cuts): one host round trip per batch of scans
         cinds, m_changes = argsorted_mat.ctx.first_pass_cuts(min_size, stop_ind, .05)
-        for morg, m in m_changes:
-            print("- M value (world_size) changed to dynamic {} --> {}".format(morg, m))
-        print("- Breakpoints found {}".format(len(cinds)))
+        print("\n".join(first_pass_report(cinds, m_changes)))
         return cinds
     while True:
         _vals, pre_cut_inds = find_matrix_pvalue_breakpoints(argsorted_mat, ind, min_size, mat_size - ind, psig=.05)
@@ -319,6 +317,18 @@ def pre_process_all_matrix_breakpoints(argsorted_mat: RankMatrix, min_size=5, mi
     return cinds
 
 
+def first_pass_report(cinds, m_changes):
+    """The lines pre_process_all_matrix_breakpoints prints, from the device loop's results (cuts, M changes)."""
+    return ["- M value (world_size) changed to dynamic {} --> {}".format(morg, m) for morg, m in m_changes] + \
+        ["- Breakpoints found {}".format(len(cinds))]
+
+
+def filter_report(original_inds, out, warned):
+    """The lines filter_noisy_breakpoints prints, from the device loop's results (kept cuts, warnings)."""
+    return ["- WARNING - Maximum number of rounds {} exceeded".format(10 * len(original_inds))] * warned + \
+        ["- Original cut indices {}".format(list(original_inds)), "- Filtered cut indices {}".format(out)]
+
+
 def filter_noisy_breakpoints(argsorted_mat: RankMatrix, original_inds, psig=.05):
     """S2C:553-727.  Row tests run on the GPU (hicmi_filter_scan); the merge decisions between
     candidate cuts are scalar hypergeometric tests evaluated by libhicmi's host code."""
@@ -330,10 +340,7 @@ def filter_noisy_breakpoints(argsorted_mat: RankMatrix, original_inds, psig=.05)
     ascending = all(b > a for a, b in zip(original_inds, original_inds[1:]))
     if _device_scan_loops(ctx) and ascending and 0 <= original_inds[0] and original_inds[-1] < n:
         out, warned = ctx.filter_cuts(original_inds, psig)          # the loops below, on the device (hicmi_filter_cuts)
-        for _ in range(warned):
-            print("- WARNING - Maximum number of rounds {} exceeded".format(10 * len(original_inds)))
-        print("- Original cut indices {}".format(list(original_inds)))
-        print("- Filtered cut indices {}".format(out))
+        print("\n".join(filter_report(original_inds, out, warned)))
         return out
     MD = int(n / 5)
     MAX_ROUNDS = 10 * len(original_inds)
@@ -919,6 +926,38 @@ class _FileWriter:
             self.pool = None
 
 
+def _cluster_resident(adjMat: DeviceMatrix, binList, hicProScaffSizeFile, mark, t0):
+    """runResident's stages from removeRows to the similarity stage in leaf order (S2C:1117-1131): returns
+    (adjMat, binList in leaf order, dendrogram, prep) - ``prep`` holds the host tables built beside the chain."""
+    adjMat, binList = removeRows(adjMat, binList, zeroRows=True, biasVals=False, store_row_sums=False)
+    adjMat.kept_bins = list(binList)                  # rows of the device matrix, in .bed order
+    adjMat = convertMatrix(adjMat, binList, distance=True, similarity=False)
+    mark("row sums")
+    # host work that does not depend on the tree runs while the chain does (a single ~100 ms native call): the labels,
+    # the size table and the scaffold -> bins table of the assessment
+    prep = {}
+
+    def meanwhile(bl=binList, sums=adjMat.seq_sum):
+        _store_row_sums(bl, sums)                     # (Bin.rowSum, S2C:133-135: nothing reads it before the chain ends)
+        prep["labels"] = [b.chrom + '_' + str(b.ID) for b in bl]
+        prep["sizes"] = readSizeFileToDict(hicProScaffSizeFile)
+        prep["scaffolds"] = _scaffold_bins((b.ID, b.chrom) for b in bl)
+        prep["pairs"] = _bin_pairs(bl)
+        # the text of the three per-bin files, line by line: ~12 ms of formatting at 16k that would otherwise hold the
+        # interpreter lock while Part 2's threads want it (the writer thread only joins the lines)
+        prep["dend_lines"] = [lab + "\t" + str(i) for i, lab in enumerate(prep["labels"])]
+        prep["bin_lines"] = {b.ID: _bin_line(b) for b in bl}
+        prep["entry_lines"] = {int(b.ID): str(int(b.ID)) + "\t" + str(b.chrom) + "\n" for b in bl}
+    # ('ivl', the labels in leaf order, is only wanted by the dendrogram file, whose lines are ready: prep["dend_lines"])
+    dendrogram = averageClusterNodes(adjMat, lambda: prep["labels"], noPlot=True, meanwhile=meanwhile, want_ivl=False)
+    mark("UPGMA + leaf order")
+    # the reference parses the file back (readDengrogramLeavesFromFile); the leaves are the same integers
+    adjMat, binList = reorderMatrix(adjMat, binList, dendrogram['leaves'])
+    print("Total run-time to cluster = " + str(time.time() - t0))
+    adjMat = convertMatrix(adjMat, binList, distance=False, similarity=True)
+    return adjMat, binList, dendrogram, prep
+
+
 def runResident(adjMat: DeviceMatrix, binList, hicProScaffSizeFile, dendrogramOrderFile, binGroupFile,
                 assessmentFile, chromosomeGroupFile, minSize, modularity, psig, louvainRounds=20, shard=None,
                 overlap_files=False, hmm=False, convergenceRounds=5, lookAhead=.2):
@@ -949,33 +988,8 @@ def runResident(adjMat: DeviceMatrix, binList, hicProScaffSizeFile, dendrogramOr
             # the scans are computed for rows == shard[0] (mod shard[1]) only and all-gathered; UPGMA and the host control
             # flow run on every rank (deterministic: all ranks write the same files)
             adjMat.ctx.set_row_shard(shard[0], shard[1])
-        adjMat, binList = removeRows(adjMat, binList, zeroRows=True, biasVals=False, store_row_sums=False)
-        adjMat.kept_bins = list(binList)                  # rows of the device matrix, in .bed order
-        adjMat = convertMatrix(adjMat, binList, distance=True, similarity=False)
-        mark("row sums")
-        # host work that does not depend on the tree runs while the chain does (a single ~100 ms native call): the labels,
-        # the size table and the scaffold -> bins table of the assessment
-        prep = {}
-
-        def meanwhile(bl=binList, sums=adjMat.seq_sum):
-            _store_row_sums(bl, sums)                     # (Bin.rowSum, S2C:133-135: nothing reads it before the chain ends)
-            prep["labels"] = [b.chrom + '_' + str(b.ID) for b in bl]
-            prep["sizes"] = readSizeFileToDict(hicProScaffSizeFile)
-            prep["scaffolds"] = _scaffold_bins((b.ID, b.chrom) for b in bl)
-            prep["pairs"] = _bin_pairs(bl)
-            # the text of the three per-bin files, line by line: ~12 ms of formatting at 16k that would otherwise hold the
-            # interpreter lock while Part 2's threads want it (the writer thread only joins the lines)
-            prep["dend_lines"] = [lab + "\t" + str(i) for i, lab in enumerate(prep["labels"])]
-            prep["bin_lines"] = {b.ID: _bin_line(b) for b in bl}
-            prep["entry_lines"] = {int(b.ID): str(int(b.ID)) + "\t" + str(b.chrom) + "\n" for b in bl}
-        # ('ivl', the labels in leaf order, is only wanted by the dendrogram file, whose lines are ready: prep["dend_lines"])
-        dendrogram = averageClusterNodes(adjMat, lambda: prep["labels"], noPlot=True, meanwhile=meanwhile, want_ivl=False)
-        mark("UPGMA + leaf order")
-        # the reference parses the file back (readDengrogramLeavesFromFile); the leaves are the same integers
-        adjMat, binList = reorderMatrix(adjMat, binList, dendrogram['leaves'])
-        print("Total run-time to cluster = " + str(time.time() - t0))
+        adjMat, binList, dendrogram, prep = _cluster_resident(adjMat, binList, hicProScaffSizeFile, mark, t0)
         t0 = time.time()
-        adjMat = convertMatrix(adjMat, binList, distance=False, similarity=True)
         if hmm:
             # S2C:1138-1140: every rank of a shard runs the HMM whole (the matrix and the gathered row sums are on each)
             writer.submit(dendrogramLeafOrder_toFile, dendrogram, dendrogramOrderFile, prep["dend_lines"])

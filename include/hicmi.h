@@ -152,6 +152,24 @@ int hicmi_first_pass_cuts(hicmi_ctx *ctx, int64_t min_size, int64_t stop_ind, do
 int hicmi_filter_cuts(hicmi_ctx *ctx, const int32_t *cuts_in, int64_t n_in, double psig, int32_t *cuts_out,
                       int64_t cuts_cap, int64_t *n_out, int64_t *warned_out);
 
+/* The same two loops for n_sets parameter sets at once, in lock step on the resident rank matrix (Part 1 parameter
+ * sweeps: sweepPart1.py).  Each set's outputs are exactly those of the single-set call with that set alone.
+ * 1 <= n_sets <= HICMI_SCAN_MAX_SETS, else HICMI_EINVAL (callers split larger grids).  One scan step is one count launch
+ * for every live set plus one decide launch with a workgroup per set; sets that recount at the same arguments share
+ * the count (counts never depend on M, min_size or psig).  HICMI_SCAN_SHARE=0 in the environment turns that off.
+ * hicmi_first_pass_cuts_multi = pre_process_all_matrix_breakpoints (S2C:513-551, with S2C:413-511 inside) for set k =
+ * (min_size[k], stop_ind[k]) and the one psig of the call: cuts_out + k * cuts_cap holds n_cuts_out[k] cuts,
+ * m_log_out + k * 2 * log_cap holds n_log_out[k] (M before, M after) pairs.
+ * hicmi_filter_cuts_multi = filter_noisy_breakpoints (S2C:553-727) for set k = (cuts_in[cand_off[k] : cand_off[k+1]],
+ * psig[k]): cuts_out + k * cuts_cap holds n_out[k] kept cuts, warned_out[k] the warnings.  An empty candidate list
+ * gives an empty result (the single-set call rejects it; the reference returns [] before its loops). */
+#define HICMI_SCAN_MAX_SETS 64
+int hicmi_first_pass_cuts_multi(hicmi_ctx *ctx, int64_t n_sets, const int64_t *min_size, const int64_t *stop_ind, double psig,
+                                int32_t *cuts_out, int64_t cuts_cap, int64_t *n_cuts_out, int32_t *m_log_out, int64_t log_cap,
+                                int64_t *n_log_out);
+int hicmi_filter_cuts_multi(hicmi_ctx *ctx, int64_t n_sets, const int64_t *cand_off, const int32_t *cuts_in, const double *psig,
+                            int32_t *cuts_out, int64_t cuts_cap, int64_t *n_out, int64_t *warned_out);
+
 /* hyper_geom (S2C:352-368) = scipy.stats.hypergeom.sf(x-1, M, n, N); NaN for invalid arguments.
  * Host-side scalar evaluation with the same code the kernels run. */
 double hicmi_hypergeom_sf(int64_t x, int64_t M, int64_t n, int64_t N);
