@@ -92,6 +92,10 @@ SIGNATURES = {
     "hicmi_hmm_kmeans": (ctypes.c_int, [_vp, _vp, c_i64, c_dbl, _vp, _vp, ctypes.POINTER(c_dbl), ctypes.POINTER(c_i64)]),
     "hicmi_hmm_fit": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, c_i64, c_dbl, _vp, ctypes.POINTER(c_i64)]),
     "hicmi_hmm_decode": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "hicmi_hmm_load_obs_slot": (ctypes.c_int, [_vp, c_i64, _vp, c_i64, c_i64, c_i64]),
+    "hicmi_hmm_use_obs": (ctypes.c_int, [_vp, c_i64]),
+    "hicmi_hmm_dist2_multi": (ctypes.c_int, [_vp, c_i64, _vp, _vp, _vp, _vp, _vp]),
+    "hicmi_hmm_kmeans_multi": (ctypes.c_int, [_vp, c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hicmi_louvain_graph": (ctypes.c_int, [_vp, _vp, c_i64]),
     "hicmi_louvain_set_graph": (ctypes.c_int, [_vp, _vp, c_i64]),
     "hicmi_louvain_get_graph": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
@@ -586,6 +590,8 @@ class Context:
         order = np.ascontiguousarray(order, dtype=np.int32)
         _check(self._lib.hicmi_hmm_load_obs(self._h, _ptr(order), len(order), int(c), int(p)))
         self._hmm_shape = [len(order) - int(c), int(p) - int(c), int(p) - int(c)]      # T, built width, view width
+        self.__dict__.setdefault("_hmm_slots", {})[0] = self._hmm_shape                # (slot 0, now selected)
+        self._hmm_cur = 0
         return self._hmm_shape[0], self._hmm_shape[1]
 
     def hmm_set_obs(self, X):
@@ -594,6 +600,8 @@ class Context:
             raise ValueError("X must be 2-D")
         _check(self._lib.hicmi_hmm_set_obs(self._h, _ptr(X), X.shape[0], X.shape[1]))
         self._hmm_shape = [X.shape[0], X.shape[1], X.shape[1]]
+        self.__dict__.setdefault("_hmm_slots", {})[0] = self._hmm_shape
+        self._hmm_cur = 0
 
     def hmm_set_width(self, D):
         """Use columns [0, D) of the X already on the device."""
@@ -651,6 +659,75 @@ class Context:
         tm = np.ascontiguousarray(transmat, dtype=np.float64)
         out = np.empty(self._hmm_shape[0], np.int32)
         _check(self._lib.hicmi_hmm_decode(self._h, _ptr(sp), _ptr(mu), _ptr(cv), _ptr(tm), _ptr(out)))
+        return out
+
+    HMM_MAX_SLOTS = 16                                     # HICMI_HMM_MAX_SLOTS
+    HMM_MAX_PROBLEMS = 256                                 # HICMI_HMM_MAX_PROBLEMS: larger batches go in chunks
+
+    def hmm_load_obs_slot(self, slot, order, c, p):
+        """hmm_load_obs into observation slot ``slot`` (the selected slot does not change unless it is this one).
+        Returns (T, D)."""
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        _check(self._lib.hicmi_hmm_load_obs_slot(self._h, int(slot), _ptr(order), len(order), int(c), int(p)))
+        shapes = self.__dict__.setdefault("_hmm_slots", {})
+        shapes[int(slot)] = [len(order) - int(c), int(p) - int(c), int(p) - int(c)]
+        if int(slot) == getattr(self, "_hmm_cur", 0):
+            self._hmm_shape = shapes[int(slot)]
+        return len(order) - int(c), int(p) - int(c)
+
+    def hmm_use_obs(self, slot):
+        """Make slot ``slot`` the X of the single-problem hmm_* calls."""
+        _check(self._lib.hicmi_hmm_use_obs(self._h, int(slot)))
+        self._hmm_cur = int(slot)
+        self._hmm_shape = self._hmm_slots[int(slot)]
+
+    def hmm_slot_rows(self, slot):
+        return self._hmm_slots[int(slot)][0]
+
+    def hmm_dist2_multi(self, problems):
+        """hmm_dist2 of many views at once: ``problems`` = [(slot, width, rows)] with 1 or 2 rows each; returns one
+        len(rows) x T array per problem."""
+        out = []
+        for c0 in range(0, len(problems), self.HMM_MAX_PROBLEMS):
+            part = problems[c0:c0 + self.HMM_MAX_PROBLEMS]
+            k = len(part)
+            slots = np.array([int(q[0]) for q in part], np.int64)
+            widths = np.array([int(q[1]) for q in part], np.int64)
+            nrows = np.array([len(q[2]) for q in part], np.int64)
+            rows = np.zeros(2 * k, np.int64)
+            for j, q in enumerate(part):
+                rows[2 * j:2 * j + len(q[2])] = [int(r) for r in q[2]]
+            Ts = [self.hmm_slot_rows(s) for s in slots]
+            buf = np.empty(int(sum(int(r) * T for r, T in zip(nrows, Ts))), np.float64)
+            _check(self._lib.hicmi_hmm_dist2_multi(self._h, k, _ptr(slots), _ptr(widths), _ptr(nrows), _ptr(rows),
+                                                   _ptr(buf)))
+            off = 0
+            for r, T in zip(nrows, Ts):
+                out.append(buf[off:off + int(r) * T].reshape(int(r), T))
+                off += int(r) * T
+        return out
+
+    def hmm_kmeans_multi(self, problems):
+        """hmm_kmeans of many views in lock step: ``problems`` = [(slot, width, (row0, row1), max_iter, tol)], the
+        initial centers being those rows of the view; returns [(centers 2 x width, inertia, iterations)]."""
+        out = []
+        for c0 in range(0, len(problems), self.HMM_MAX_PROBLEMS):
+            part = problems[c0:c0 + self.HMM_MAX_PROBLEMS]
+            k = len(part)
+            slots = np.array([int(q[0]) for q in part], np.int64)
+            widths = np.array([int(q[1]) for q in part], np.int64)
+            rows = np.array([int(r) for q in part for r in q[2]], np.int64)
+            max_iter = np.array([int(q[3]) for q in part], np.int64)
+            tol = np.array([float(q[4]) for q in part], np.float64)
+            cen = np.empty(int(2 * widths.sum()), np.float64)
+            inertia = np.empty(k, np.float64)
+            n_iter = np.empty(k, np.int64)
+            _check(self._lib.hicmi_hmm_kmeans_multi(self._h, k, _ptr(slots), _ptr(widths), _ptr(rows), _ptr(max_iter),
+                                                    _ptr(tol), _ptr(cen), _ptr(inertia), _ptr(n_iter)))
+            off = 0
+            for j, D in enumerate(widths):
+                out.append((cen[off:off + 2 * int(D)].reshape(2, int(D)), float(inertia[j]), int(n_iter[j])))
+                off += 2 * int(D)
         return out
 
     # ---- Louvain tail (modularity > 0, S2C:239-349)

@@ -128,8 +128,13 @@ struct hicmi_ctx {
     double* d_ins_partial = nullptr; int64_t ins_partial_cap = 0;
     unsigned char* d_ins_blob = nullptr; int64_t ins_blob_cap = 0;   // per job: [InsState][InsLog x steps]
     InsStep* d_ins_steps = nullptr; int64_t ins_steps_cap = 0;       // [step][job] records of a lock-step queue
-    // HMM boundary finder (k_hmm.hip): observations T x hmm_ld (columns [0, hmm_D) in use), work areas sized per X
-    double* d_hx = nullptr; int64_t hx_cap = 0; int64_t hmm_T = 0, hmm_ld = 0, hmm_D = 0;
+    // HMM boundary finder (k_hmm.hip): resident observation matrices, one per slot (T x ld, columns [0, D) in use);
+    // the selected slot's view is mirrored in d_hx / hmm_T / hmm_ld / hmm_D for the single-problem entry points.  The
+    // work areas are sized for the largest slot built
+    struct HmmSlot { double* d_x = nullptr; int64_t cap = 0, T = 0, ld = 0, D = 0; };
+    HmmSlot hslot[HICMI_HMM_MAX_SLOTS]; int hcur = 0;
+    double* d_hx = nullptr; int64_t hmm_T = 0, hmm_ld = 0, hmm_D = 0;
+    unsigned char* d_hmulti = nullptr; int64_t hmulti_cap = 0;   // problem tables and work areas of the *_multi calls
     int32_t* d_horder = nullptr; int64_t horder_cap = 0;
     double* d_hwork = nullptr; int64_t hwork_cap = 0;      // L, alpha, beta, gamma (T x 2 each), mind / dist (2T)
     int32_t* d_hlab = nullptr; int64_t hlab_cap = 0;       // labels (two generations), states: 3T
@@ -359,7 +364,8 @@ int hicmi_destroy(hicmi_ctx* c)
     free_dev(c->d_arr_packed2); free_dev(c->d_pos2sel2); free_dev(c->d_ins_T); free_dev(c->d_ins_partial);
     free_dev(c->d_ins_blob); free_dev(c->d_ins_steps);
     free_dev(c->d_plot_order); free_dev(c->d_plot_work); free_dev(c->d_plot_img);
-    free_dev(c->d_hx); free_dev(c->d_horder); free_dev(c->d_hwork); free_dev(c->d_hlab); free_dev(c->d_hbt);
+    for (auto& sl : c->hslot) free_dev(sl.d_x);
+    free_dev(c->d_hmulti); free_dev(c->d_horder); free_dev(c->d_hwork); free_dev(c->d_hlab); free_dev(c->d_hbt);
     free_dev(c->d_hpart); free_dev(c->d_hsmall); free_dev(c->d_hhist); free_dev(c->d_hst);
     free_dev(c->d_lvA); free_dev(c->d_lvvec); free_dev(c->d_lvrows); free_dev(c->d_lvwork);
     if (c->pin_up) (void)hipHostFree(c->pin_up);
@@ -2407,10 +2413,10 @@ inline double* hmm_sums(hicmi_ctx* c) { return c->d_hsmall + HMM_P_SCALARS * c->
 inline double* hmm_cen(hicmi_ctx* c) { return hmm_sums(c) + 4 * c->hmm_ld; }
 inline double* hmm_slots(hicmi_ctx* c) { return hmm_cen(c) + 2 * c->hmm_ld; }
 
-// work areas for the current X (sized once per X: nothing is allocated inside the k-means or EM loops)
-int hmm_size_work(hicmi_ctx* c)
+// work areas for an X of T rows and leading dimension ld (sized when a slot is built: nothing is allocated inside the
+// k-means or EM loops); ensure() only grows them, so they fit every slot built before
+int hmm_size_work(hicmi_ctx* c, int64_t T, int64_t ld)
 {
-    const int64_t T = c->hmm_T, ld = c->hmm_ld;
     int rc = ensure(c->d_hwork, c->hwork_cap, 10 * T);
     if (!rc) rc = ensure(c->d_hlab, c->hlab_cap, 3 * T);
     if (!rc) rc = ensure(c->d_hbt, c->hbt_cap, T);
@@ -2421,6 +2427,27 @@ int hmm_size_work(hicmi_ctx* c)
     if (!rc) rc = ensure(c->d_hsmall, c->hsmall_cap, (HMM_P_SCALARS + 6) * ld + HMM_S_COUNT + 16);
     if (!rc) rc = ensure(c->d_hst, c->hst_cap, 4);
     return rc;
+}
+
+// the single-problem entry points work on slot s from now on
+void hmm_select(hicmi_ctx* c, int s)
+{
+    const auto& sl = c->hslot[s];
+    c->hcur = s;
+    c->d_hx = sl.d_x; c->hmm_T = sl.T; c->hmm_ld = sl.ld; c->hmm_D = sl.D;
+}
+
+// (re)size slot s for a T x ld matrix; the slot is left empty (T = 0) if that fails
+int hmm_slot_alloc(hicmi_ctx* c, int s, int64_t T, int64_t ld)
+{
+    auto& sl = c->hslot[s];
+    sl.T = sl.ld = sl.D = 0;
+    int rc = ensure(sl.d_x, sl.cap, T * ld);
+    if (!rc) rc = hmm_size_work(c, T, ld);
+    if (rc) { if (c->hcur == s) hmm_select(c, s); return rc; }
+    sl.T = T; sl.ld = ld; sl.D = ld;
+    if (c->hcur == s) hmm_select(c, s);
+    return HICMI_OK;
 }
 
 int hmm_check(hicmi_ctx* c)
@@ -2450,9 +2477,10 @@ int hmm_upload_params(hicmi_ctx* c, const double* startprob, const double* means
 
 }  // namespace
 
-int hicmi_hmm_load_obs(hicmi_ctx* c, const int32_t* order, int64_t n, int64_t cut, int64_t prev)
+int hicmi_hmm_load_obs_slot(hicmi_ctx* c, int64_t slot, const int32_t* order, int64_t n, int64_t cut, int64_t prev)
 {
     if (!c || !order) return fail(HICMI_EINVAL, "bad arguments");
+    if (slot < 0 || slot >= HICMI_HMM_MAX_SLOTS) return fail(HICMI_EINVAL, "slot %lld outside [0, %d)", (long long)slot, HICMI_HMM_MAX_SLOTS);
     if (!c->dC || n != c->n) return fail(HICMI_EINVAL, "order must have n entries (n = %lld)", (long long)c->n);
     if (!c->have_sums) return fail(HICMI_EINVAL, "hicmi_row_sums has not run");
     if (cut < 0 || cut >= n || prev <= cut || prev > n) return fail(HICMI_EINVAL, "need 0 <= c < p <= n");
@@ -2461,28 +2489,39 @@ int hicmi_hmm_load_obs(hicmi_ctx* c, const int32_t* order, int64_t n, int64_t cu
     HIPCHK(hipSetDevice(c->device));
     const int64_t T = n - cut, D = prev - cut;
     int rc = ensure(c->d_horder, c->horder_cap, n);
-    if (!rc) rc = ensure(c->d_hx, c->hx_cap, T * D);
-    if (rc) return rc;
-    c->hmm_T = T; c->hmm_ld = D; c->hmm_D = D;
-    rc = hmm_size_work(c);
+    if (!rc) rc = hmm_slot_alloc(c, (int)slot, T, D);
     if (!rc) rc = upload(c, c->d_horder, order, sizeof(int32_t) * (size_t)n);
     if (rc) return rc;
-    launch_hmm_obs(c->dC, c->ldc, c->d_horder, c->d_np, c->d_seq, (int)cut, (int)T, (int)D, c->d_hx, c->stream);
+    launch_hmm_obs(c->dC, c->ldc, c->d_horder, c->d_np, c->d_seq, (int)cut, (int)T, (int)D, c->hslot[slot].d_x, c->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(sync_stream(c));
     return HICMI_OK;
+}
+
+int hicmi_hmm_use_obs(hicmi_ctx* c, int64_t slot)
+{
+    if (!c) return fail(HICMI_EINVAL, "NULL context");
+    if (slot < 0 || slot >= HICMI_HMM_MAX_SLOTS) return fail(HICMI_EINVAL, "slot %lld outside [0, %d)", (long long)slot, HICMI_HMM_MAX_SLOTS);
+    if (c->hslot[slot].T <= 0) return fail(HICMI_EINVAL, "HMM slot %lld holds no observations", (long long)slot);
+    hmm_select(c, (int)slot);
+    return HICMI_OK;
+}
+
+int hicmi_hmm_load_obs(hicmi_ctx* c, const int32_t* order, int64_t n, int64_t cut, int64_t prev)
+{
+    int rc = hicmi_hmm_load_obs_slot(c, 0, order, n, cut, prev);
+    if (!rc) hmm_select(c, 0);
+    return rc;
 }
 
 int hicmi_hmm_set_obs(hicmi_ctx* c, const double* X, int64_t T, int64_t D)
 {
     if (!c || !X || T < 1 || D < 1 || T > (1 << 24) || T * D > ((int64_t)1 << 31)) return fail(HICMI_EINVAL, "bad arguments");
     HIPCHK(hipSetDevice(c->device));
-    int rc = ensure(c->d_hx, c->hx_cap, T * D);
+    int rc = hmm_slot_alloc(c, 0, T, D);
+    if (!rc) rc = upload(c, c->hslot[0].d_x, X, sizeof(double) * (size_t)(T * D));
     if (rc) return rc;
-    c->hmm_T = T; c->hmm_ld = D; c->hmm_D = D;
-    rc = hmm_size_work(c);
-    if (!rc) rc = upload(c, c->d_hx, X, sizeof(double) * (size_t)(T * D));
-    if (rc) return rc;
+    hmm_select(c, 0);
     HIPCHK(sync_stream(c));
     return HICMI_OK;
 }
@@ -2493,6 +2532,7 @@ int hicmi_hmm_set_width(hicmi_ctx* c, int64_t D)
     if (rc) return rc;
     if (D < 1 || D > c->hmm_ld) return fail(HICMI_EINVAL, "width %lld outside [1, %lld]", (long long)D, (long long)c->hmm_ld);
     c->hmm_D = D;
+    c->hslot[c->hcur].D = D;
     return HICMI_OK;
 }
 
@@ -2661,6 +2701,140 @@ int hicmi_hmm_decode(hicmi_ctx* c, const double* startprob, const double* means,
     return download(c, states_out, states, sizeof(int32_t) * (size_t)T);
 }
 
+
+namespace {
+
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// The problem table and work areas of a *_multi call in d_hmulti: problems | states | done counter | centers | sums |
+// column partials | out | labels.  Checks every problem, fills `pr` (device pointers included) and returns the largest
+// row count, column-pass work item count and 2 D in `mx`.
+int hmm_multi_plan(hicmi_ctx* c, int64_t n_prob, const int64_t* slots, const int64_t* widths, const int64_t* nrows,
+                   const int64_t* rows, bool kmeans, std::vector<HmmKmProb>& pr, int64_t mx[3])
+{
+    if (n_prob < 1 || n_prob > HICMI_HMM_MAX_PROBLEMS)
+        return fail(HICMI_EINVAL, "%lld problems outside [1, %d]", (long long)n_prob, HICMI_HMM_MAX_PROBLEMS);
+    if (!slots || !widths || !rows) return fail(HICMI_EINVAL, "bad arguments");
+    pr.assign((size_t)n_prob, HmmKmProb{});
+    int64_t n_dbl = 0, n_lab = 0;
+    mx[0] = mx[1] = mx[2] = 0;
+    for (int64_t p = 0; p < n_prob; p++) {
+        if (slots[p] < 0 || slots[p] >= HICMI_HMM_MAX_SLOTS || c->hslot[slots[p]].T <= 0)
+            return fail(HICMI_EINVAL, "problem %lld: slot %lld holds no observations", (long long)p, (long long)slots[p]);
+        const auto& sl = c->hslot[slots[p]];
+        const int64_t T = sl.T, D = widths[p];
+        if (D < 1 || D > sl.ld) return fail(HICMI_EINVAL, "problem %lld: width %lld outside [1, %lld]", (long long)p, (long long)D, (long long)sl.ld);
+        const int nc = kmeans ? 2 : (int)nrows[p];
+        if (nc < 1 || nc > 2) return fail(HICMI_EINVAL, "problem %lld: 1 or 2 rows", (long long)p);
+        if (kmeans && T < 2) return fail(HICMI_EINVAL, "problem %lld: k-means with 2 clusters needs at least 2 rows", (long long)p);
+        HmmKmProb& q = pr[(size_t)p];
+        for (int k = 0; k < nc; k++) {
+            if (rows[2 * p + k] < 0 || rows[2 * p + k] >= T) return fail(HICMI_EINVAL, "problem %lld: row out of range", (long long)p);
+            q.rows[k] = rows[2 * p + k];
+        }
+        q.X = sl.d_x; q.ld = sl.ld; q.T = (int)T; q.D = (int)D; q.nc = nc;
+        hmm_col_shape((int)T, hmm_col_chunks((int)T, (int)D), q.rows_per, q.Rr);
+        n_dbl += 4 * D + (kmeans ? (int64_t)q.Rr * 2 * D : 0) + nc * T;
+        n_lab += kmeans ? 2 * T : 0;
+        mx[0] = std::max(mx[0], T);
+        mx[1] = std::max(mx[1], (int64_t)q.Rr * ((D + 255) / 256));
+        mx[2] = std::max(mx[2], 2 * D);
+    }
+    const size_t b_pr = align256(sizeof(HmmKmProb) * (size_t)n_prob), b_st = align256(sizeof(HmmKmState) * (size_t)n_prob);
+    const size_t bytes = b_pr + b_st + 256 + sizeof(double) * (size_t)n_dbl + sizeof(int32_t) * (size_t)n_lab;
+    int rc = ensure(c->d_hmulti, c->hmulti_cap, (int64_t)bytes);
+    if (rc) return rc;
+    double* dp = (double*)(c->d_hmulti + b_pr + b_st + 256);
+    for (auto& q : pr) { q.cen = dp; dp += 2 * q.D; }                   // the centers of all problems are contiguous
+    for (auto& q : pr) { q.sums = dp; dp += 2 * q.D; }
+    if (kmeans) for (auto& q : pr) { q.part = dp; dp += (int64_t)q.Rr * 2 * q.D; }
+    for (auto& q : pr) { q.out = dp; dp += (int64_t)q.nc * q.T; }       // the distances of all problems are contiguous
+    int32_t* lp = (int32_t*)dp;
+    if (kmeans) for (auto& q : pr) { q.lab = lp; lp += 2 * (int64_t)q.T; }
+    return HICMI_OK;
+}
+
+inline HmmKmProb* hmm_multi_probs(hicmi_ctx* c) { return (HmmKmProb*)c->d_hmulti; }
+inline HmmKmState* hmm_multi_states(hicmi_ctx* c, int64_t n_prob)
+{
+    return (HmmKmState*)(c->d_hmulti + align256(sizeof(HmmKmProb) * (size_t)n_prob));
+}
+inline int* hmm_multi_done(hicmi_ctx* c, int64_t n_prob)
+{
+    return (int*)((unsigned char*)hmm_multi_states(c, n_prob) + align256(sizeof(HmmKmState) * (size_t)n_prob));
+}
+
+}  // namespace
+
+int hicmi_hmm_dist2_multi(hicmi_ctx* c, int64_t n_prob, const int64_t* slots, const int64_t* widths, const int64_t* nrows,
+                          const int64_t* rows, double* out)
+{
+    if (!c) return fail(HICMI_EINVAL, "NULL context");
+    if (!nrows || !out) return fail(HICMI_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<HmmKmProb> pr;
+    int64_t mx[3];
+    int rc = hmm_multi_plan(c, n_prob, slots, widths, nrows, rows, false, pr, mx);
+    if (!rc) rc = upload(c, hmm_multi_probs(c), pr.data(), sizeof(HmmKmProb) * pr.size());
+    if (rc) return rc;
+    launch_hmm_multi_seed(hmm_multi_probs(c), hmm_multi_states(c, n_prob), (int)n_prob, 2 * (int)mx[2], 0, c->stream);
+    launch_hmm_dist2_multi(hmm_multi_probs(c), (int)n_prob, (int)mx[0], c->stream);
+    HIPCHK(hipGetLastError());
+    int64_t total = 0;
+    for (const auto& q : pr) total += (int64_t)q.nc * q.T;
+    return download(c, out, pr[0].out, sizeof(double) * (size_t)total);
+}
+
+int hicmi_hmm_kmeans_multi(hicmi_ctx* c, int64_t n_prob, const int64_t* slots, const int64_t* widths, const int64_t* rows,
+                           const int64_t* max_iter, const double* tol, double* centers_out, double* inertia_out,
+                           int64_t* n_iter_out)
+{
+    if (!c) return fail(HICMI_EINVAL, "NULL context");
+    if (!max_iter || !tol || !centers_out || !inertia_out || !n_iter_out) return fail(HICMI_EINVAL, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<HmmKmProb> pr;
+    int64_t mx[3];
+    int rc = hmm_multi_plan(c, n_prob, slots, widths, nullptr, rows, true, pr, mx);
+    if (rc) return rc;
+    int64_t steps = 0;                                         // a problem is done after at most max_iter + 1 steps
+    for (int64_t p = 0; p < n_prob; p++) {
+        if (max_iter[p] < 1 || max_iter[p] > (1 << 30)) return fail(HICMI_EINVAL, "problem %lld: max_iter < 1", (long long)p);
+        pr[(size_t)p].max_iter = (int)max_iter[p];
+        pr[(size_t)p].tol = tol[p];
+        steps = std::max(steps, max_iter[p] + 1);
+    }
+    HmmKmProb* dpr = hmm_multi_probs(c);
+    HmmKmState* dst = hmm_multi_states(c, n_prob);
+    int* done = hmm_multi_done(c, n_prob);
+    rc = upload(c, dpr, pr.data(), sizeof(HmmKmProb) * pr.size());
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(done, 0, sizeof(int), c->stream));
+    launch_hmm_multi_seed(dpr, dst, (int)n_prob, std::max(2 * (int)mx[2], (int)mx[0]), 1, c->stream);
+    HIPCHK(hipGetLastError());
+    // the done count is read back every `poll` steps; a step is a no-op for a finished problem, so the interval changes
+    // no result
+    const char* ev = getenv("HICMI_HMM_POLL");
+    const int64_t poll = ev && atoi(ev) > 0 ? atoi(ev) : 8;
+    int n_done = 0;
+    for (int64_t step = 0; step < steps && n_done < n_prob;) {
+        for (int64_t j = 0; j < poll && step < steps; j++, step++)
+            launch_hmm_kmeans_multi_step(dpr, dst, done, (int)n_prob, (int)mx[0], (int)mx[1], (int)mx[2], c->stream);
+        HIPCHK(hipGetLastError());
+        rc = download(c, &n_done, done, sizeof(int));
+        if (rc) return rc;
+    }
+    if (n_done != n_prob) return fail(HICMI_ESTATE, "k-means: %d of %lld problems finished", n_done, (long long)n_prob);
+    std::vector<HmmKmState> st((size_t)n_prob);
+    rc = download(c, st.data(), dst, sizeof(HmmKmState) * st.size());
+    if (rc) return rc;
+    int64_t total = 0;
+    for (int64_t p = 0; p < n_prob; p++) {
+        inertia_out[p] = st[(size_t)p].inertia;
+        n_iter_out[p] = st[(size_t)p].it;
+        total += 2 * (int64_t)pr[(size_t)p].D;
+    }
+    return download(c, centers_out, pr[0].cen, sizeof(double) * (size_t)total);
+}
 
 // ---------------------------------------------------------------------------------------------------
 // Louvain tail (S2C:239-349, modularity > 0): level 0 of modularity.best_partition on the device, k_louvain.hip.

@@ -336,6 +336,27 @@ enum { HMM_P_MEAN = 0, HMM_P_VAR = 2, HMM_P_MOV = 4, HMM_P_IV = 6, HMM_P_LOGV = 
 enum { HMM_S_CONST = 0, HMM_S_A = 2, HMM_S_LOGA = 6, HMM_S_PI = 10, HMM_S_LOGPI = 12, HMM_S_XI = 14, HMM_S_POST = 18,
        HMM_S_COUNT = 32 };
 int  hmm_col_chunks(int T, int D);                       // row chunks of a column pass (partials: chunks x 4 x D doubles)
+// the row chunking of a column pass: rows per chunk and the chunks that hold rows
+__host__ __device__ inline void hmm_col_shape(int T, int R, int& rows_per, int& Rr)
+{
+    rows_per = (T + R - 1) / R;
+    Rr = (T + rows_per - 1) / rows_per;
+}
+// One problem of hicmi_hmm_dist2_multi / hicmi_hmm_kmeans_multi: a view (T x D, leading dimension ld) of a resident X,
+// its nc seed rows, and its own work areas - centers (2 D), combined sums (2 D), column partials (Rr x 2 x D), out
+// (dist2: nc x T distances; k-means: T per-row minimum distances), labels (two generations, 2 T).
+struct HmmKmProb {
+    const double* X; int64_t ld; int T, D;
+    int nc, rows_per, Rr, max_iter;
+    int64_t rows[2];
+    double tol;
+    double *cen, *sums, *part, *out;
+    int32_t* lab;
+};
+enum { HMM_KM_LLOYD = 0, HMM_KM_FINAL = 1, HMM_KM_SUM = 2, HMM_KM_DONE = 3 };
+// the device-side state of one k-means problem: phase, which label generation is current, iterations run, the
+// iteration's counters (labels changed, rows with label 1), the inertia once done
+struct HmmKmState { int phase, cur, it, strict, changed, n1; double inertia; };
 void launch_hmm_obs(const double* C, int64_t ldc, const int32_t* order, const double* np_sum, const double* seq_sum,
                     int c, int T, int D, double* X, hipStream_t s);
 void launch_hmm_colsum(int mode, const double* X, int64_t ld, int T, int D, const double* shift, const int32_t* labels,
@@ -350,6 +371,11 @@ void launch_hmm_emission(const double* X, int64_t ld, int T, int D, const double
 void launch_hmm_fb(const double* L, int T, double* P, int D, double* alpha, double* beta, double* gam, double* hist, int it,
                    hipStream_t s);
 void launch_hmm_viterbi(const double* L, int T, const double* P, int D, uint8_t* bt, int32_t* states, hipStream_t s);
+void launch_hmm_multi_seed(const HmmKmProb* pr, HmmKmState* st, int n_prob, int max_rows, int kmeans, hipStream_t s);
+void launch_hmm_dist2_multi(const HmmKmProb* pr, int n_prob, int max_T, hipStream_t s);
+// one Lloyd step of every live problem: assignment, label-masked column sums, combine, center update + stop rule
+void launch_hmm_kmeans_multi_step(const HmmKmProb* pr, HmmKmState* st, int* done, int n_prob, int max_T, int max_items,
+                                  int max_2d, hipStream_t s);
 
 // k_louvain.hip: level 0 of the Louvain tail (S2C:239-349, modularity.py).  The graph is m x m, leading dimension m.
 static constexpr int LOUVAIN_MAX_M = 16384;

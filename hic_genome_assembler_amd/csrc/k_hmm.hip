@@ -13,6 +13,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "hicmi_internal.h"
 
 namespace hicmi {
@@ -56,15 +58,14 @@ void launch_hmm_obs(const double* C, int64_t ldc, const int32_t* order, const do
 }
 
 // ---- column pass: partial sums per (row chunk, column).  mode 0: (x - shift), (x - shift)^2; mode 1: x where
-// label == 0, x where label == 1; mode 2: g0 x, g1 x, g0 x^2, g1 x^2 (g = posteriors, T x 2)
+// label == 0, x where label == 1; mode 2: g0 x, g1 x, g0 x^2, g1 x^2 (g = posteriors, T x 2).  Column d of row chunk
+// `chunk` (rows [chunk * rows_per, min(T, (chunk + 1) * rows_per))), written to part[chunk][q][d].
 template <int MODE>
-__global__ __launch_bounds__(256) void k_hmm_colsum(const double* __restrict__ X, int64_t ld, int T, int D, int rows_per,
-                                                    const double* __restrict__ shift, const int32_t* __restrict__ labels,
-                                                    const double* __restrict__ g, double* __restrict__ part)
+__device__ __forceinline__ void colsum_chunk(const double* __restrict__ X, int64_t ld, int T, int D, int rows_per, int chunk,
+                                             int d, const double* __restrict__ shift, const int32_t* __restrict__ labels,
+                                             const double* __restrict__ g, double* __restrict__ part)
 {
-    const int d = blockIdx.x * kColThreads + threadIdx.x;
-    if (d >= D) return;
-    const int t0 = blockIdx.y * rows_per;
+    const int t0 = chunk * rows_per;
     const int t1 = min(T, t0 + rows_per);
     constexpr int NQ = MODE == 2 ? 4 : 2;
     double s[NQ];
@@ -88,26 +89,40 @@ __global__ __launch_bounds__(256) void k_hmm_colsum(const double* __restrict__ X
         }
     }
 #pragma unroll
-    for (int q = 0; q < NQ; q++) part[((int64_t)blockIdx.y * NQ + q) * D + d] = s[q];
+    for (int q = 0; q < NQ; q++) part[((int64_t)chunk * NQ + q) * D + d] = s[q];
 }
 
-// out[q][d] = sum over chunks (in chunk order) of part[chunk][q][d]
+template <int MODE>
+__global__ __launch_bounds__(256) void k_hmm_colsum(const double* __restrict__ X, int64_t ld, int T, int D, int rows_per,
+                                                    const double* __restrict__ shift, const int32_t* __restrict__ labels,
+                                                    const double* __restrict__ g, double* __restrict__ part)
+{
+    const int d = blockIdx.x * kColThreads + threadIdx.x;
+    if (d >= D) return;
+    colsum_chunk<MODE>(X, ld, T, D, rows_per, blockIdx.y, d, shift, labels, g, part);
+}
+
+// out[i] = sum over chunks (in chunk order) of part[chunk][i], i < NQ * D
+__device__ __forceinline__ double combine_one(const double* __restrict__ part, int R, int NQ, int D, int i)
+{
+    double s = 0.0;
+    for (int r = 0; r < R; r++) s += part[(int64_t)r * NQ * D + i];
+    return s;
+}
+
 __global__ __launch_bounds__(256) void k_hmm_combine(const double* __restrict__ part, int R, int NQ, int D,
                                                      double* __restrict__ out)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= NQ * D) return;
-    double s = 0.0;
-    for (int r = 0; r < R; r++) s += part[(int64_t)r * NQ * D + i];
-    out[i] = s;
+    out[i] = combine_one(part, R, NQ, D, i);
 }
 
 void launch_hmm_colsum(int mode, const double* X, int64_t ld, int T, int D, const double* shift, const int32_t* labels,
                        const double* g, double* part, double* out, hipStream_t s)
 {
-    const int R = hmm_col_chunks(T, D);
-    const int rows_per = (T + R - 1) / R;
-    const int Rr = (T + rows_per - 1) / rows_per;             // chunks that hold rows
+    int rows_per, Rr;                                         // Rr: chunks that hold rows
+    hmm_col_shape(T, hmm_col_chunks(T, D), rows_per, Rr);
     const dim3 grid((D + kColThreads - 1) / kColThreads, Rr);
     const int nq = mode == 2 ? 4 : 2;
     if (mode == 0) hipLaunchKernelGGL(k_hmm_colsum<0>, grid, dim3(kColThreads), 0, s, X, ld, T, D, rows_per, shift, labels, g, part);
@@ -124,15 +139,11 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
-// dist[k][t] = sum_d (X[t][d] - cen[k][d])^2 for k < nc (nc = 1 or 2)
-__global__ __launch_bounds__(256) void k_hmm_dist2(const double* __restrict__ X, int64_t ld, int T, int D,
-                                                   const double* __restrict__ cen, int nc, double* __restrict__ dist)
+// sum_d (x[d] - cen[k][d])^2 for k < nc (nc = 1 or 2), reduced over the wave: the distances of one row
+__device__ __forceinline__ void dist2_row(const double* __restrict__ x, int D, const double* __restrict__ cen, int nc, int lane,
+                                          double& a0, double& a1)
 {
-    const int lane = threadIdx.x & 63;
-    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= T) return;
-    const double* x = X + (int64_t)t * ld;
-    double a0 = 0.0, a1 = 0.0;
+    a0 = 0.0; a1 = 0.0;
     for (int d = lane; d < D; d += 64) {
         const double v = x[d];
         const double e0 = v - cen[d];
@@ -141,6 +152,17 @@ __global__ __launch_bounds__(256) void k_hmm_dist2(const double* __restrict__ X,
     }
     a0 = wave_sum(a0);
     a1 = wave_sum(a1);
+}
+
+// dist[k][t] = sum_d (X[t][d] - cen[k][d])^2 for k < nc (nc = 1 or 2)
+__global__ __launch_bounds__(256) void k_hmm_dist2(const double* __restrict__ X, int64_t ld, int T, int D,
+                                                   const double* __restrict__ cen, int nc, double* __restrict__ dist)
+{
+    const int lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= T) return;
+    double a0, a1;
+    dist2_row(X + (int64_t)t * ld, D, cen, nc, lane, a0, a1);
     if (lane == 0) {
         dist[t] = a0;
         if (nc > 1) dist[T + t] = a1;
@@ -154,15 +176,10 @@ void launch_hmm_dist2(const double* X, int64_t ld, int T, int D, const double* c
 
 // ---- k-means: assignment (ties to center 0, as sklearn's strict '<'), plus the counters of the iteration
 // st: [0] rows whose label changed, [1] rows with label 1
-__global__ __launch_bounds__(256) void k_hmm_assign(const double* __restrict__ X, int64_t ld, int T, int D,
-                                                    const double* __restrict__ cen, const int32_t* __restrict__ old_labels,
-                                                    int32_t* __restrict__ labels, double* __restrict__ mind,
-                                                    int* __restrict__ st)
+__device__ __forceinline__ void assign_row(const double* __restrict__ x, int D, const double* __restrict__ cen, int lane,
+                                           int t, const int32_t* __restrict__ old_labels, int32_t* __restrict__ labels,
+                                           double* __restrict__ mind, int* __restrict__ changed, int* __restrict__ n1)
 {
-    const int lane = threadIdx.x & 63;
-    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= T) return;
-    const double* x = X + (int64_t)t * ld;
     double a0 = 0.0, a1 = 0.0;
     for (int d = lane; d < D; d += 64) {
         const double v = x[d];
@@ -176,19 +193,28 @@ __global__ __launch_bounds__(256) void k_hmm_assign(const double* __restrict__ X
         const int l = a1 < a0 ? 1 : 0;
         labels[t] = l;
         mind[t] = l ? a1 : a0;
-        if (l != old_labels[t]) atomicAdd(&st[0], 1);
-        if (l) atomicAdd(&st[1], 1);
+        if (l != old_labels[t]) atomicAdd(changed, 1);
+        if (l) atomicAdd(n1, 1);
     }
 }
 
-// new centers from the combined sums (an empty cluster keeps its center); out[0] = sum_d of the squared shift,
-// out[2], out[3] = the iteration's counters (one read-back per Lloyd iteration)
-__global__ __launch_bounds__(1024) void k_hmm_center_update(const double* __restrict__ sums, int T, int D,
-                                                            const int* __restrict__ st, double* __restrict__ cen,
-                                                            double* __restrict__ shift_out)
+__global__ __launch_bounds__(256) void k_hmm_assign(const double* __restrict__ X, int64_t ld, int T, int D,
+                                                    const double* __restrict__ cen, const int32_t* __restrict__ old_labels,
+                                                    int32_t* __restrict__ labels, double* __restrict__ mind,
+                                                    int* __restrict__ st)
 {
-    __shared__ double red[1024];
-    const int n1 = st[1], n0 = T - n1;
+    const int lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= T) return;
+    assign_row(X + (int64_t)t * ld, D, cen, lane, t, old_labels, labels, mind, &st[0], &st[1]);
+}
+
+// new centers from the combined sums (an empty cluster keeps its center); returns the summed squared shift in thread 0.
+// red: 1024 doubles of LDS, blockDim.x == 1024
+__device__ __forceinline__ double center_update_block(const double* __restrict__ sums, int T, int D, int n1,
+                                                      double* __restrict__ cen, double* red)
+{
+    const int n0 = T - n1;
     double sh = 0.0;
     for (int i = threadIdx.x; i < 2 * D; i += 1024) {
         const int k = i / D;
@@ -205,17 +231,12 @@ __global__ __launch_bounds__(1024) void k_hmm_center_update(const double* __rest
         if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
         __syncthreads();
     }
-    if (threadIdx.x == 0) {
-        shift_out[0] = red[0];
-        shift_out[2] = (double)st[0];
-        shift_out[3] = (double)st[1];
-    }
+    return red[0];
 }
 
-// sum of v[0..n) in a fixed order (one workgroup)
-__global__ __launch_bounds__(1024) void k_hmm_sum(const double* __restrict__ v, int n, double* __restrict__ out)
+// sum of v[0..n) in a fixed order (returned in thread 0); red: 1024 doubles of LDS, blockDim.x == 1024
+__device__ __forceinline__ double sum_block(const double* __restrict__ v, int n, double* red)
 {
-    __shared__ double red[1024];
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += 1024) s += v[i];
     red[threadIdx.x] = s;
@@ -224,7 +245,28 @@ __global__ __launch_bounds__(1024) void k_hmm_sum(const double* __restrict__ v, 
         if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
         __syncthreads();
     }
-    if (threadIdx.x == 0) *out = red[0];
+    return red[0];
+}
+
+// out[0] = sum_d of the squared shift, out[2], out[3] = the iteration's counters (one read-back per Lloyd iteration)
+__global__ __launch_bounds__(1024) void k_hmm_center_update(const double* __restrict__ sums, int T, int D,
+                                                            const int* __restrict__ st, double* __restrict__ cen,
+                                                            double* __restrict__ shift_out)
+{
+    __shared__ double red[1024];
+    const double sh = center_update_block(sums, T, D, st[1], cen, red);
+    if (threadIdx.x == 0) {
+        shift_out[0] = sh;
+        shift_out[2] = (double)st[0];
+        shift_out[3] = (double)st[1];
+    }
+}
+
+__global__ __launch_bounds__(1024) void k_hmm_sum(const double* __restrict__ v, int n, double* __restrict__ out)
+{
+    __shared__ double red[1024];
+    const double s = sum_block(v, n, red);
+    if (threadIdx.x == 0) *out = s;
 }
 
 void launch_hmm_assign(const double* X, int64_t ld, int T, int D, const double* cen, const int32_t* old_labels,
@@ -590,6 +632,141 @@ __global__ __launch_bounds__(kScanThreads) void k_hmm_viterbi(const double* __re
 void launch_hmm_viterbi(const double* L, int T, const double* P, int D, uint8_t* bt, int32_t* states, hipStream_t s)
 {
     hipLaunchKernelGGL(k_hmm_viterbi, dim3(1), dim3(kScanThreads), 0, s, L, T, P, D, bt, states);
+}
+
+// ---- many k-means problems in lock step (hicmi_hmm_dist2_multi / hicmi_hmm_kmeans_multi).  Problem p is one
+// workgroup row of the grid (blockIdx.y); its workgroups walk their rows / column chunks grid-stride and run the device
+// functions of the single-problem kernels above with that problem's own chunking, so every result equals the single
+// call's bit for bit.  A finished problem's workgroups return at once.
+__global__ __launch_bounds__(256) void k_hmm_multi_seed(const HmmKmProb* __restrict__ pr, HmmKmState* __restrict__ st,
+                                                        int kmeans)
+{
+    const HmmKmProb& q = pr[blockIdx.y];
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < q.nc * q.D; i += gridDim.x * 256) {
+        const int k = i / q.D, d = i - k * q.D;
+        q.cen[i] = q.X[q.rows[k] * q.ld + d];
+    }
+    if (!kmeans) return;
+    for (int t = blockIdx.x * 256 + threadIdx.x; t < q.T; t += gridDim.x * 256) q.lab[t] = -1;     // "no label yet"
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        HmmKmState& s = st[blockIdx.y];
+        s.phase = HMM_KM_LLOYD; s.cur = 0; s.it = 0; s.strict = 0; s.changed = 0; s.n1 = 0; s.inertia = 0.0;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_hmm_dist2_multi(const HmmKmProb* __restrict__ pr)
+{
+    const HmmKmProb& q = pr[blockIdx.y];
+    const int lane = threadIdx.x & 63;
+    for (int t = blockIdx.x * 4 + (threadIdx.x >> 6); t < q.T; t += gridDim.x * 4) {
+        double a0, a1;
+        dist2_row(q.X + (int64_t)t * q.ld, q.D, q.cen, q.nc, lane, a0, a1);
+        if (lane == 0) {
+            q.out[t] = a0;
+            if (q.nc > 1) q.out[q.T + t] = a1;
+        }
+    }
+}
+
+// assignment of the live problems: Lloyd iterations and the final labels from the final centers
+__global__ __launch_bounds__(256) void k_hmm_assign_multi(const HmmKmProb* __restrict__ pr, HmmKmState* __restrict__ st)
+{
+    HmmKmState& s = st[blockIdx.y];
+    const int phase = s.phase;
+    if (phase != HMM_KM_LLOYD && phase != HMM_KM_FINAL) return;
+    const HmmKmProb& q = pr[blockIdx.y];
+    const int cur = s.cur;
+    const int32_t* old_labels = q.lab + (int64_t)cur * q.T;
+    int32_t* labels = q.lab + (int64_t)(cur ^ 1) * q.T;
+    const int lane = threadIdx.x & 63;
+    for (int t = blockIdx.x * 4 + (threadIdx.x >> 6); t < q.T; t += gridDim.x * 4)
+        assign_row(q.X + (int64_t)t * q.ld, q.D, q.cen, lane, t, old_labels, labels, q.out, &s.changed, &s.n1);
+}
+
+// label-masked column sums of the problems in a Lloyd iteration: work items (row chunk, 256 columns)
+__global__ __launch_bounds__(256) void k_hmm_colsum_multi(const HmmKmProb* __restrict__ pr, const HmmKmState* __restrict__ st)
+{
+    const HmmKmState& s = st[blockIdx.y];
+    if (s.phase != HMM_KM_LLOYD) return;
+    const HmmKmProb& q = pr[blockIdx.y];
+    const int32_t* labels = q.lab + (int64_t)(s.cur ^ 1) * q.T;
+    const int cb = (q.D + kColThreads - 1) / kColThreads;
+    for (int item = blockIdx.x; item < q.Rr * cb; item += gridDim.x) {
+        const int chunk = item / cb;
+        const int d = (item - chunk * cb) * kColThreads + threadIdx.x;
+        if (d < q.D) colsum_chunk<1>(q.X, q.ld, q.T, q.D, q.rows_per, chunk, d, nullptr, labels, nullptr, q.part);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_hmm_combine_multi(const HmmKmProb* __restrict__ pr, const HmmKmState* __restrict__ st)
+{
+    if (st[blockIdx.y].phase != HMM_KM_LLOYD) return;
+    const HmmKmProb& q = pr[blockIdx.y];
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < 2 * q.D; i += gridDim.x * 256) q.sums[i] = combine_one(q.part, q.Rr, 2, q.D, i);
+}
+
+// one workgroup per problem: the center update and sklearn's stop rule (strict convergence when no label changed, else
+// squared center shift <= tol, else max_iter), then - once the final labels are in - the inertia
+__global__ __launch_bounds__(1024) void k_hmm_step_multi(const HmmKmProb* __restrict__ pr, HmmKmState* __restrict__ st,
+                                                         int* __restrict__ done)
+{
+    __shared__ double red[1024];
+    __shared__ int s_next;
+    HmmKmState& s = st[blockIdx.x];
+    const int phase = s.phase;
+    if (phase != HMM_KM_LLOYD && phase != HMM_KM_FINAL) return;
+    const HmmKmProb& q = pr[blockIdx.x];
+    if (phase == HMM_KM_LLOYD) {
+        const double sh = center_update_block(q.sums, q.T, q.D, s.n1, q.cen, red);
+        if (threadIdx.x == 0) {
+            s.cur ^= 1;
+            s.it++;
+            int next = HMM_KM_LLOYD;
+            if (s.changed == 0) { s.strict = 1; next = HMM_KM_SUM; }
+            else if (sh <= q.tol || s.it >= q.max_iter) next = HMM_KM_FINAL;
+            s.changed = 0; s.n1 = 0;
+            s_next = next;
+        }
+    } else if (threadIdx.x == 0) {                            // the final assignment ran in this step
+        s.cur ^= 1;
+        s_next = HMM_KM_SUM;
+    }
+    __syncthreads();
+    const int next = s_next;
+    if (next == HMM_KM_SUM) {
+        const double inertia = sum_block(q.out, q.T, red);
+        if (threadIdx.x == 0) {
+            s.inertia = inertia;
+            s.phase = HMM_KM_DONE;
+            atomicAdd(done, 1);
+        }
+    } else if (threadIdx.x == 0) {
+        s.phase = next;
+    }
+}
+
+static int multi_grid(int64_t items, int cap)
+{
+    return (int)std::max<int64_t>(1, std::min<int64_t>(items, cap));
+}
+
+void launch_hmm_multi_seed(const HmmKmProb* pr, HmmKmState* st, int n_prob, int max_rows, int kmeans, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_hmm_multi_seed, dim3(multi_grid((max_rows + 255) / 256, 256), n_prob), dim3(256), 0, s, pr, st, kmeans);
+}
+
+void launch_hmm_dist2_multi(const HmmKmProb* pr, int n_prob, int max_T, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_hmm_dist2_multi, dim3(multi_grid((max_T + 3) / 4, 1024), n_prob), dim3(256), 0, s, pr);
+}
+
+void launch_hmm_kmeans_multi_step(const HmmKmProb* pr, HmmKmState* st, int* done, int n_prob, int max_T, int max_items,
+                                  int max_2d, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_hmm_assign_multi, dim3(multi_grid((max_T + 3) / 4, 1024), n_prob), dim3(256), 0, s, pr, st);
+    hipLaunchKernelGGL(k_hmm_colsum_multi, dim3(multi_grid(max_items, 4096), n_prob), dim3(kColThreads), 0, s, pr, st);
+    hipLaunchKernelGGL(k_hmm_combine_multi, dim3(multi_grid((max_2d + 255) / 256, 1024), n_prob), dim3(256), 0, s, pr, st);
+    hipLaunchKernelGGL(k_hmm_step_multi, dim3(n_prob), dim3(1024), 0, s, pr, st, done);
 }
 
 }  // namespace hicmi

@@ -349,6 +349,30 @@ int hicmi_hmm_fit(hicmi_ctx *ctx, const double *startprob, double *means, double
 /* model.predict(X) (S2C:801): Viterbi under the given parameters, ties to state 0.  states_out: T int32. */
 int hicmi_hmm_decode(hicmi_ctx *ctx, const double *startprob, const double *means, const double *covars,
                      const double *transmat, int32_t *states_out);
+/* Many k-means problems per call: the restarts of many fits (the reference fits one model at a time, S2C:796-801; a
+ * parameter sweep fits many - DESIGN.md section 9c).
+ * Observation slots: X matrices kept side by side in the context, each with its own T, built width and leading
+ * dimension.  hicmi_hmm_load_obs_slot builds slot `slot` as hicmi_hmm_load_obs does (and sizes the work areas of every
+ * call above for it); hicmi_hmm_use_obs makes a built slot the X of the single-problem calls above (col_stats, kmeans,
+ * fit, decode, get_obs, set_width, dist2).  hicmi_hmm_load_obs and hicmi_hmm_set_obs build slot 0 and select it.
+ * A problem is a (slots[p], widths[p]) view: columns [0, widths[p]) of that slot's X, 1 <= widths[p] <= its built width.
+ * hicmi_hmm_dist2_multi: for problem p, nrows[p] (1 or 2) rows rows[2p], rows[2p + 1] of its view; out holds, problem
+ * after problem, the nrows[p] x T_p distances hicmi_hmm_dist2 gives on that view, bit for bit.
+ * hicmi_hmm_kmeans_multi: Lloyd from the rows rows[2p], rows[2p + 1] of its view (copied on the device) with max_iter[p]
+ * and tol[p], all problems in lock step; the stop rule is evaluated per problem on the device, the host reads a done
+ * count every few steps (HICMI_HMM_POLL, default 8; it changes no result).  centers_out holds, problem after problem,
+ * the 2 x D_p centers; inertia_out[p], n_iter_out[p].  Every output equals hicmi_hmm_kmeans on that view from those
+ * rows, bit for bit.
+ * 1 <= n_prob <= HICMI_HMM_MAX_PROBLEMS, else HICMI_EINVAL (callers split larger batches). */
+#define HICMI_HMM_MAX_SLOTS 16
+#define HICMI_HMM_MAX_PROBLEMS 256
+int hicmi_hmm_load_obs_slot(hicmi_ctx *ctx, int64_t slot, const int32_t *order, int64_t n, int64_t c, int64_t p);
+int hicmi_hmm_use_obs(hicmi_ctx *ctx, int64_t slot);
+int hicmi_hmm_dist2_multi(hicmi_ctx *ctx, int64_t n_prob, const int64_t *slots, const int64_t *widths, const int64_t *nrows,
+                          const int64_t *rows, double *out);
+int hicmi_hmm_kmeans_multi(hicmi_ctx *ctx, int64_t n_prob, const int64_t *slots, const int64_t *widths, const int64_t *rows,
+                           const int64_t *max_iter, const double *tol, double *centers_out, double *inertia_out,
+                           int64_t *n_iter_out);
 
 /* ---- Part 1: Louvain tail (modularity > 0, S2C:239-349) ---------------------------------------------
  * modularity_remaining_data (S2C:263-349) partitions the bins after the last cut index with the best of louvainRounds
