@@ -91,8 +91,7 @@ struct hicmi_ctx {
     bool presort_dealt = false;                           // its rows were dealt out by a counter (workgroups on the chain's XCD left)
     // cut scan
     int32_t* d_x = nullptr; uint8_t* d_sig = nullptr; int64_t x_cap = 0;
-    unsigned char* d_scan_prog = nullptr; int64_t scan_prog_cap = 0;     // device-driven scan loops: state record + lists
-    unsigned char* d_scan_multi = nullptr; size_t scan_multi_bytes = 0;  // the same for many parameter sets (the *_multi calls)
+    unsigned char* d_scan_multi = nullptr; size_t scan_multi_bytes = 0;  // device-driven scan loops: state records + lists
     int64_t cached_start = -1;
     double* d_tmp = nullptr; int64_t tmp_cap = 0;
     // part 2
@@ -355,7 +354,7 @@ int hicmi_destroy(hicmi_ctx* c)
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
-    free_dev(c->d_x); free_dev(c->d_sig); free_dev(c->d_tmp); free_dev(c->d_scan_prog); free_dev(c->d_scan_multi);
+    free_dev(c->d_x); free_dev(c->d_sig); free_dev(c->d_tmp); free_dev(c->d_scan_multi);
     free_dev(c->dM2); free_dev(c->d_sel); free_dev(c->d_H); free_dev(c->d_perms); free_dev(c->d_scores);
     free_dev(c->d_partial); free_dev(c->d_T);
     free_dev(c->d_scaf_start); free_dev(c->d_scaf_len); free_dev(c->d_arr_packed);
@@ -1123,147 +1122,19 @@ double hicmi_hypergeom_sf(int64_t x, int64_t M, int64_t n, int64_t N) { return h
 int hicmi_hypergeom_decide(int64_t x, int64_t M, int64_t n, int64_t N, double psig) { return hypergeom_decide(x, M, n, N, psig); }
 
 // ---- the two scan loops with their control flow on the device (k_part1_scan.hip) -------------------------------------
-// One allocation: [ScanState, 256 B][cuts n][M log 2n][alt n][seg 3n][seg_x n] int32, then [filt n][prev n] bytes.
-static int ensure_scan_program(hicmi_ctx* c)
-{
-    if (c->scan_prog_cap >= c->n && c->d_scan_prog) return HICMI_OK;
-    free_dev(c->d_scan_prog); c->d_scan_prog = nullptr; c->scan_prog_cap = 0;
-    HIPCHK(hipMalloc((void**)&c->d_scan_prog, 256 + sizeof(int32_t) * 8 * (size_t)c->n + 2 * (size_t)c->n + 64));
-    c->scan_prog_cap = c->n;
-    return HICMI_OK;
-}
-
-struct ScanProgram {
-    ScanState* st; int32_t *cuts, *mlog, *alt, *seg, *seg_x; uint8_t *filt, *prev;
-    explicit ScanProgram(hicmi_ctx* c)
-    {
-        unsigned char* b = c->d_scan_prog;
-        const size_t n = (size_t)c->scan_prog_cap;
-        st = reinterpret_cast<ScanState*>(b);
-        cuts = reinterpret_cast<int32_t*>(b + 256);
-        mlog = cuts + n; alt = mlog + 2 * n; seg = alt + n; seg_x = seg + 3 * n;
-        filt = reinterpret_cast<uint8_t*>(seg_x + n); prev = filt + n;
-    }
-};
-
-// Batches of scans until the device says the loop has ended.  `pairs` launches per batch: the record is read once per batch.
-static int run_scan_program(hicmi_ctx* c, ScanState& h, const ScanProgram& p, int64_t max_scans,
-                            const std::function<void(int)>& enqueue)
-{
-    int rc = upload(c, p.st, &h, sizeof(h));
-    if (rc) return rc;
-    const int pairs = 32;
-    int64_t batches = 0;
-    for (int64_t issued = 0; ; issued += pairs) {
-        if (issued > max_scans + pairs) return fail(HICMI_ESTATE, "scan loop did not end after %lld scans", (long long)issued);
-        {
-            Timed t(c, F_CUT_COUNT, 0.0);
-            enqueue(pairs);
-        }
-        HIPCHK(hipGetLastError());
-        batches++;
-        rc = download(c, &h, p.st, sizeof(h));
-        if (rc) return rc;
-        if (h.done) break;
-    }
-    c->launches[F_CUT_COUNT] += (int64_t)h.scans - batches;       // the family is reported per scan
-    c->launches[F_HYPER_FLAGS] += (int64_t)h.scans;               // (the decisions ride in the same launches)
-    c->bytes[F_CUT_COUNT] += (double)h.bytes;
-    c->cached_start = -1;                                          // d_x was reused
-    return HICMI_OK;
-}
-
-int hicmi_first_pass_cuts(hicmi_ctx* c, int64_t min_size, int64_t stop_ind, double psig, int32_t* cuts_out, int64_t cuts_cap,
-                          int64_t* n_cuts_out, int32_t* m_log_out, int64_t log_cap, int64_t* n_log_out)
-{
-    if (!c || !cuts_out || !n_cuts_out || !n_log_out || (log_cap > 0 && !m_log_out)) return fail(HICMI_EINVAL, "bad arguments");
-    if (!c->have_rank) return fail(HICMI_EINVAL, "hicmi_rank_matrix has not run");
-    if (c->shard_stride != 1) return fail(HICMI_EINVAL, "the device-driven scan loops need the whole rank matrix (no row shard)");
-    if (min_size < 1) return fail(HICMI_EINVAL, "min_size must be >= 1");
-    const int64_t n = c->n;
-    HIPCHK(hipSetDevice(c->device));
-    int rc = ensure_scan_buffers(c);
-    if (rc) return rc;
-    rc = ensure_scan_program(c);
-    if (rc) return rc;
-    ScanProgram p(c);
-    ScanState h;
-    memset(&h, 0, sizeof(h));
-    h.mode = 0; h.start = 0; h.M = n; h.recount = 1;
-    h.min_size = (int)std::min<int64_t>(min_size, n + 1); h.stop_ind = (int)std::min<int64_t>(stop_ind, INT32_MAX);
-    const int lcap = (int)n;                                       // pairs that fit the device log
-    rc = run_scan_program(c, h, p, 6 * n, [&](int pairs) {
-        launch_first_pass_pairs(c->dRank, c->ldr, (int)n, p.st, c->d_x, c->d_sig, psig, p.cuts, p.mlog, lcap, pairs, c->stream);
-    });
-    if (rc) return rc;
-    if (h.n_cuts > cuts_cap) return fail(HICMI_EINVAL, "%d cuts do not fit cuts_cap", h.n_cuts);
-    if (h.n_log > lcap || h.n_log > log_cap) return fail(HICMI_EINVAL, "%d M changes do not fit the log", h.n_log);
-    if (h.n_cuts) { rc = download(c, cuts_out, p.cuts, sizeof(int32_t) * (size_t)h.n_cuts); if (rc) return rc; }
-    if (h.n_log) { rc = download(c, m_log_out, p.mlog, sizeof(int32_t) * 2 * (size_t)h.n_log); if (rc) return rc; }
-    *n_cuts_out = h.n_cuts; *n_log_out = h.n_log;
-    return HICMI_OK;
-}
-
-int hicmi_filter_cuts(hicmi_ctx* c, const int32_t* cuts_in, int64_t n_in, double psig, int32_t* cuts_out, int64_t cuts_cap,
-                      int64_t* n_out, int64_t* warned_out)
-{
-    if (!c || !cuts_in || !cuts_out || !n_out || n_in < 1) return fail(HICMI_EINVAL, "bad arguments");
-    if (!c->have_rank) return fail(HICMI_EINVAL, "hicmi_rank_matrix has not run");
-    if (c->shard_stride != 1) return fail(HICMI_EINVAL, "the device-driven scan loops need the whole rank matrix (no row shard)");
-    const int64_t n = c->n;
-    if (n_in > n) return fail(HICMI_EINVAL, "more cuts than rows");
-    for (int64_t i = 0; i < n_in; i++)
-        if (cuts_in[i] < 0 || cuts_in[i] >= n || (i && cuts_in[i] <= cuts_in[i - 1]))
-            return fail(HICMI_EINVAL, "cuts must be ascending indices in [0, n)");
-    HIPCHK(hipSetDevice(c->device));
-    int rc = ensure_scan_buffers(c);
-    if (rc) return rc;
-    rc = ensure_scan_program(c);
-    if (rc) return rc;
-    ScanProgram p(c);
-    rc = upload(c, p.alt, cuts_in, sizeof(int32_t) * (size_t)n_in);
-    if (rc) return rc;
-    HIPCHK(hipMemsetAsync(p.filt, 0, 2 * (size_t)c->scan_prog_cap, c->stream));      // filtered = {}, prev_filtered = {}
-    ScanState h;
-    memset(&h, 0, sizeof(h));
-    h.mode = 1; h.start = 0; h.M = n; h.recount = 1;
-    h.MD = (int)(n / 5);                                           // MD = int(n / 5)  (S2C:575)
-    h.n_alt = (int)n_in; h.f_max_rounds = (int)std::min<int64_t>(10 * n_in, INT32_MAX);   // S2C:577
-    h.cut = cuts_in[0];
-    h.n_rows = (int)std::min<int64_t>(n, (int64_t)h.MD + 1);
-    const int max_rows = (int)std::min<int64_t>(n, (int64_t)h.MD + 1);
-    // every pass over the candidates runs at most 10 * n_in rounds of at most n_in scans; the passes end when the set
-    // of kept cuts repeats - bounded here far above anything a map produces
-    const int64_t max_scans = std::min<int64_t>((int64_t)4000000, 20 * n_in * n_in * 10 + 1000);
-    rc = run_scan_program(c, h, p, max_scans, [&](int pairs) {
-        launch_filter_pairs(c->dRank, c->ldr, (int)n, max_rows, p.st, c->d_x, c->d_sig, psig, p.alt, p.filt, p.prev, p.seg,
-                            p.seg_x, pairs, c->stream);
-    });
-    if (rc) return rc;
-    std::vector<uint8_t> kept((size_t)n);
-    rc = download(c, kept.data(), p.filt, (size_t)n);
-    if (rc) return rc;
-    int64_t m = 0;
-    for (int64_t e = 0; e < n; e++)
-        if (kept[(size_t)e]) { if (m >= cuts_cap) return fail(HICMI_EINVAL, "filtered cuts do not fit cuts_cap"); cuts_out[m++] = (int32_t)e; }
-    *n_out = m;
-    if (warned_out) *warned_out = h.f_warned;
-    return HICMI_OK;
-}
-
-// ---- many parameter sets in lock step (k_part1_scan.hip: k_cut_rows_multi + k_*_decide_multi) ----------------------
-// One allocation, sized from n_sets x n: [ScanState x SCAN_MAX_SETS][psig x SCAN_MAX_SETS], then per set
-// x n, cuts n, M log 2n, alt n, seg 3n, seg_x n int32 and sig n, filt n, prev n bytes (39 B per row and set).
+// Up to SCAN_MAX_SETS parameter sets in lock step; the single-set entries are the one-set case.  One allocation, sized
+// from n_sets x n: [ScanState x SCAN_MAX_SETS], then per set x n, cuts n, M log 2n, alt n, seg 3n, seg_x n int32 and
+// sig n, filt n, prev n bytes (39 B per row and set).
 static_assert(SCAN_MAX_SETS == HICMI_SCAN_MAX_SETS, "hicmi.h and the kernels disagree on the set cap");
 
 struct ScanMulti {
-    ScanState* st; double* psig; int32_t *x, *cuts, *mlog, *alt, *seg, *seg_x; uint8_t *sig, *filt, *prev;
+    ScanState* st; int32_t *x, *cuts, *mlog, *alt, *seg, *seg_x; uint8_t *sig, *filt, *prev;
 };
 
 static int ensure_scan_multi(hicmi_ctx* c, int sets, ScanMulti& m)
 {
     const size_t n = (size_t)c->n, S = (size_t)sets;
-    const size_t head = (sizeof(ScanState) * SCAN_MAX_SETS + sizeof(double) * SCAN_MAX_SETS + 255) & ~(size_t)255;
+    const size_t head = (sizeof(ScanState) * SCAN_MAX_SETS + 255) & ~(size_t)255;
     const size_t bytes = head + S * n * (sizeof(int32_t) * 9 + 3) + 64;
     if (c->scan_multi_bytes < bytes || !c->d_scan_multi) {
         free_dev(c->d_scan_multi); c->d_scan_multi = nullptr; c->scan_multi_bytes = 0;
@@ -1272,7 +1143,6 @@ static int ensure_scan_multi(hicmi_ctx* c, int sets, ScanMulti& m)
     }
     unsigned char* b = c->d_scan_multi;
     m.st = reinterpret_cast<ScanState*>(b);
-    m.psig = reinterpret_cast<double*>(b + sizeof(ScanState) * SCAN_MAX_SETS);
     m.x = reinterpret_cast<int32_t*>(b + head);
     m.cuts = m.x + S * n; m.mlog = m.cuts + S * n; m.alt = m.mlog + 2 * S * n; m.seg = m.alt + S * n; m.seg_x = m.seg + 3 * S * n;
     m.sig = reinterpret_cast<uint8_t*>(m.seg_x + S * n); m.filt = m.sig + S * n; m.prev = m.filt + S * n;
@@ -1285,15 +1155,13 @@ static int scan_share()
     return e && !strcmp(e, "0") ? 0 : 1;
 }
 
-// Batches of lock-step scans until every set's loop has ended; the records are read once per batch, and the runaway
-// guard of run_scan_program applies to every set on its own.
-static int run_scan_multi(hicmi_ctx* c, std::vector<ScanState>& h, const ScanMulti& m, const std::vector<double>& psig,
-                          const std::vector<int64_t>& max_scans, const std::function<void(int)>& enqueue)
+// Batches of lock-step scans until every set's loop has ended.  `pairs` launches per batch: the records are read once
+// per batch, and the runaway guard applies to every set on its own.
+static int run_scan_multi(hicmi_ctx* c, std::vector<ScanState>& h, const ScanMulti& m, const std::vector<int64_t>& max_scans,
+                          const std::function<void(int)>& enqueue)
 {
     const size_t S = h.size();
     int rc = upload(c, m.st, h.data(), sizeof(ScanState) * S);
-    if (rc) return rc;
-    rc = upload(c, m.psig, psig.data(), sizeof(double) * S);
     if (rc) return rc;
     const int pairs = 32;
     int64_t batches = 0;
@@ -1317,11 +1185,52 @@ static int run_scan_multi(hicmi_ctx* c, std::vector<ScanState>& h, const ScanMul
     }
     int64_t scans = 0; double bytes = 0;
     for (const ScanState& r : h) { scans += r.scans; bytes += (double)r.bytes; }
-    c->launches[F_CUT_COUNT] += scans - batches;                  // reported per set and scan, as run_scan_program does
-    c->launches[F_HYPER_FLAGS] += scans;
+    c->launches[F_CUT_COUNT] += scans - batches;                  // the family is reported per set and scan
+    c->launches[F_HYPER_FLAGS] += scans;                          // (the decisions ride in the same launches)
     c->bytes[F_CUT_COUNT] += bytes;
-    c->cached_start = -1;
     return HICMI_OK;
+}
+
+// A first-pass set's record before its first scan.
+static ScanState first_pass_record(int64_t n, int64_t min_size, int64_t stop_ind, double psig)
+{
+    ScanState r;
+    memset(&r, 0, sizeof(r));
+    r.mode = 0; r.start = 0; r.M = n; r.recount = 1; r.psig = psig;
+    r.min_size = (int)std::min<int64_t>(min_size, n + 1); r.stop_ind = (int)std::min<int64_t>(stop_ind, INT32_MAX);
+    return r;
+}
+
+// A filter set's record before its first scan: n_in candidates, the first of them `first`.
+static ScanState filter_record(int64_t n, int64_t n_in, int32_t first, double psig)
+{
+    ScanState r;
+    memset(&r, 0, sizeof(r));
+    r.mode = 1; r.start = 0; r.M = n; r.recount = 1; r.psig = psig;
+    r.MD = (int)(n / 5);                                           // MD = int(n / 5)  (S2C:575)
+    r.n_alt = (int)n_in; r.f_max_rounds = (int)std::min<int64_t>(10 * n_in, INT32_MAX);   // S2C:577
+    r.cut = first;
+    r.n_rows = (int)std::min<int64_t>(n, (int64_t)r.MD + 1);
+    r.done = n_in == 0;                                            // nothing to filter
+    return r;
+}
+
+int hicmi_first_pass_cuts(hicmi_ctx* c, int64_t min_size, int64_t stop_ind, double psig, int32_t* cuts_out, int64_t cuts_cap,
+                          int64_t* n_cuts_out, int32_t* m_log_out, int64_t log_cap, int64_t* n_log_out)
+{
+    return hicmi_first_pass_cuts_multi(c, 1, &min_size, &stop_ind, psig, cuts_out, cuts_cap, n_cuts_out, m_log_out, log_cap,
+                                       n_log_out);
+}
+
+int hicmi_filter_cuts(hicmi_ctx* c, const int32_t* cuts_in, int64_t n_in, double psig, int32_t* cuts_out, int64_t cuts_cap,
+                      int64_t* n_out, int64_t* warned_out)
+{
+    if (!c || !cuts_in || !cuts_out || !n_out || n_in < 1) return fail(HICMI_EINVAL, "bad arguments");
+    const int64_t cand_off[2] = {0, n_in};
+    int64_t warned = 0;
+    const int rc = hicmi_filter_cuts_multi(c, 1, cand_off, cuts_in, &psig, cuts_out, cuts_cap, n_out, &warned);
+    if (!rc && warned_out) *warned_out = warned;
+    return rc;
 }
 
 int hicmi_first_pass_cuts_multi(hicmi_ctx* c, int64_t n_sets, const int64_t* min_size, const int64_t* stop_ind, double psig,
@@ -1341,17 +1250,11 @@ int hicmi_first_pass_cuts_multi(hicmi_ctx* c, int64_t n_sets, const int64_t* min
     int rc = ensure_scan_multi(c, (int)n_sets, m);
     if (rc) return rc;
     std::vector<ScanState> h((size_t)n_sets);
-    for (int64_t k = 0; k < n_sets; k++) {                         // hicmi_first_pass_cuts' record, set by set
-        ScanState& r = h[(size_t)k];
-        memset(&r, 0, sizeof(r));
-        r.mode = 0; r.start = 0; r.M = n; r.recount = 1;
-        r.min_size = (int)std::min<int64_t>(min_size[k], n + 1); r.stop_ind = (int)std::min<int64_t>(stop_ind[k], INT32_MAX);
-    }
-    const int lcap = (int)n;
+    for (int64_t k = 0; k < n_sets; k++) h[(size_t)k] = first_pass_record(n, min_size[k], stop_ind[k], psig);
+    const int lcap = (int)n;                                       // pairs that fit the device log
     const int share = scan_share();
-    rc = run_scan_multi(c, h, m, std::vector<double>((size_t)n_sets, psig), std::vector<int64_t>((size_t)n_sets, 6 * n),
-                        [&](int pairs) {
-        launch_first_pass_multi_pairs(c->dRank, c->ldr, (int)n, (int)n_sets, m.st, m.x, m.sig, m.psig, share, m.cuts, m.mlog,
+    rc = run_scan_multi(c, h, m, std::vector<int64_t>((size_t)n_sets, 6 * n), [&](int pairs) {
+        launch_first_pass_multi_pairs(c->dRank, c->ldr, (int)n, (int)n_sets, m.st, m.x, m.sig, psig, share, m.cuts, m.mlog,
                                       lcap, pairs, c->stream);
     });
     if (rc) return rc;
@@ -1394,23 +1297,18 @@ int hicmi_filter_cuts_multi(hicmi_ctx* c, int64_t n_sets, const int64_t* cand_of
     std::vector<ScanState> h((size_t)n_sets);
     std::vector<int64_t> max_scans((size_t)n_sets);
     const int max_rows = (int)std::min<int64_t>(n, n / 5 + 1);
-    for (int64_t k = 0; k < n_sets; k++) {                         // hicmi_filter_cuts' record, set by set
+    for (int64_t k = 0; k < n_sets; k++) {
         const int64_t a = cand_off[k], n_in = cand_off[k + 1] - a;
-        ScanState& r = h[(size_t)k];
-        memset(&r, 0, sizeof(r));
-        r.mode = 1; r.start = 0; r.M = n; r.recount = 1;
-        r.MD = (int)(n / 5);
-        r.n_alt = (int)n_in; r.f_max_rounds = (int)std::min<int64_t>(10 * n_in, INT32_MAX);
-        r.cut = n_in ? cuts_in[a] : 0;
-        r.n_rows = max_rows;
-        r.done = n_in == 0;                                        // nothing to filter
+        h[(size_t)k] = filter_record(n, n_in, n_in ? cuts_in[a] : 0, psig[k]);
+        // every pass over the candidates runs at most 10 * n_in rounds of at most n_in scans; the passes end when the
+        // set of kept cuts repeats - bounded here far above anything a map produces
         max_scans[(size_t)k] = std::min<int64_t>((int64_t)4000000, 20 * n_in * n_in * 10 + 1000);
         if (n_in) { rc = upload(c, m.alt + k * n, cuts_in + a, sizeof(int32_t) * (size_t)n_in); if (rc) return rc; }
     }
     const int share = scan_share();
-    rc = run_scan_multi(c, h, m, std::vector<double>(psig, psig + n_sets), max_scans, [&](int pairs) {
-        launch_filter_multi_pairs(c->dRank, c->ldr, (int)n, max_rows, (int)n_sets, m.st, m.x, m.sig, m.psig, share, m.alt, m.filt,
-                                  m.prev, m.seg, m.seg_x, pairs, c->stream);
+    rc = run_scan_multi(c, h, m, max_scans, [&](int pairs) {
+        launch_filter_multi_pairs(c->dRank, c->ldr, (int)n, max_rows, (int)n_sets, m.st, m.x, m.sig, psig[0], share, m.alt,
+                                  m.filt, m.prev, m.seg, m.seg_x, pairs, c->stream);
     });
     if (rc) return rc;
     std::vector<uint8_t> kept((size_t)n_sets * (size_t)n);

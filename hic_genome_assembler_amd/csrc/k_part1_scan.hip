@@ -7,10 +7,11 @@
 // Both are chains of scans in which every scan's arguments come out of the previous scan's flags: ~230 scans per 16k map,
 // each a few tens of microseconds of device work - and, driven from the host, as much again of launch + download +
 // decision latency.  Here a scan is two launches that take their arguments from a small state record in device memory:
-//   k_cut_rows     one workgroup per row: the count over the row's rank segment (the k_cut_count query) and, by its first
-//                  lane, the hypergeometric decision -> one flag per row
-//   k_*_decide     one workgroup: reads the flags, takes the reference's decision, writes the next scan's arguments
-// so the host enqueues a batch of such pairs back to back and only looks at the state record once per batch; launches
+//   k_cut_rows        one workgroup per row: the count over the row's rank segment (the k_cut_count query) and, by its
+//                     first lane, the hypergeometric decision -> one flag per row (k_cut_rows_multi: many sets' rows)
+//   k_*_decide_multi  one workgroup per set: reads the flags, takes the reference's decision, writes the next scan's
+//                     arguments
+// so the host enqueues a batch of such pairs back to back and only looks at the state records once per batch; launches
 // behind the end of the loop find `done` set and return.  The decisions are the reference's, statement by statement
 // (cited below); everything is integer work except the scalar p-values of the filter, which use the same hyper.h routine
 // as the host-side hicmi_hypergeom_sf.
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(256) void k_cut_rows(const uint16_t* __restrict__ r
 }
 
 // ---- first pass: what happens between two scans (S2C:430-511 and 513-551) --------------------------------------------
-// (a device function: k_first_pass_decide runs it for one set, k_first_pass_decide_multi for set blockIdx.x)
+// (k_first_pass_decide_multi runs it for set blockIdx.x)
 __device__ __forceinline__ void first_pass_decide(int n, ScanState* __restrict__ st, const uint8_t* __restrict__ sig,
                                                   int32_t* __restrict__ cuts, int32_t* __restrict__ mlog, int log_cap)
 {
@@ -136,12 +137,6 @@ __device__ __forceinline__ void first_pass_decide(int n, ScanState* __restrict__
     st->start = ind; st->M = n - ind; st->loop_count = 0; st->recount = 1;
 }
 
-__global__ __launch_bounds__(1024) void k_first_pass_decide(int n, ScanState* __restrict__ st, const uint8_t* __restrict__ sig,
-                                                            int32_t* __restrict__ cuts, int32_t* __restrict__ mlog, int log_cap)
-{
-    first_pass_decide(n, st, sig, cuts, mlog, log_cap);
-}
-
 // ---- filter: what happens between two scans (S2C:553-727) ------------------------------------------------------------
 // Lists live in global memory behind the state record: `alt` (the candidate cuts still in play, `alt_off` = what
 // altered[keep_from:] has dropped), `filt` / `prev` (the dictionaries `filtered` / `prev_filtered` as one byte per index).
@@ -163,7 +158,7 @@ __device__ __forceinline__ void filter_set_scan(ScanState* st, const int32_t* al
 
 static constexpr int FD_CAP = 2048;                     // candidates kept in LDS; longer lists are walked in global memory
 
-// (a device function: k_filter_decide runs it for one set, k_filter_decide_multi for set blockIdx.x)
+// (k_filter_decide_multi runs it for set blockIdx.x)
 __device__ __forceinline__ void filter_decide(int n, ScanState* __restrict__ st, const uint8_t* __restrict__ sig,
                                               int32_t* __restrict__ alt, uint8_t* __restrict__ filt,
                                               uint8_t* __restrict__ prev, int32_t* __restrict__ seg_g,
@@ -284,18 +279,10 @@ __device__ __forceinline__ void filter_decide(int n, ScanState* __restrict__ st,
     if (tid == 0 && total) { __threadfence_block(); filter_begin_round(st, n); filter_set_scan(st, alt, n); }
 }
 
-__global__ __launch_bounds__(1024) void k_filter_decide(int n, ScanState* __restrict__ st, const uint8_t* __restrict__ sig,
-                                                        int32_t* __restrict__ alt, uint8_t* __restrict__ filt,
-                                                        uint8_t* __restrict__ prev, int32_t* __restrict__ seg_g,
-                                                        int32_t* __restrict__ seg_x_g, double psig)
-{
-    filter_decide(n, st, sig, alt, filt, prev, seg_g, seg_x_g, psig);
-}
-
 // ---- many parameter sets in lock step (hicmi_first_pass_cuts_multi / hicmi_filter_cuts_multi) -------------------------
 // Set k has its own record st[k] and its own lists at k * n (k * 2n for the M log, k * 3n for the segments); a step is
-// one count launch for every live set and one decide launch with a workgroup per set.  A set that is done costs its
-// decide workgroup one load and no work in the count launch.
+// one count launch for every live set (k_cut_rows when there is one set) and one decide launch with a workgroup per set.
+// A set that is done costs its decide workgroup one load and no work in the count launch.
 //
 // The count launch deals out (set, row) work items grid-stride, numbered set by set from a prefix over the live sets'
 // row counts that every workgroup builds from the records.  Counts depend on the start only (mode 0) or on (start, cut)
@@ -303,7 +290,7 @@ __global__ __launch_bounds__(1024) void k_filter_decide(int n, ScanState* __rest
 // (`share`) brings no items of its own: the lower set's workgroup hands it the count and it takes its own flag from it.
 __global__ __launch_bounds__(256) void k_cut_rows_multi(const uint16_t* __restrict__ rank, int64_t ldr, int n, int n_sets,
                                                         const ScanState* __restrict__ st, int32_t* __restrict__ x,
-                                                        uint8_t* __restrict__ sig, const double* __restrict__ psig, int share)
+                                                        uint8_t* __restrict__ sig, int share)
 {
     __shared__ int s_pre[SCAN_MAX_SETS + 1];              // work items of the sets before k
     __shared__ int s_lead[SCAN_MAX_SETS];                 // the set whose items serve set k (-1: done)
@@ -359,11 +346,11 @@ __global__ __launch_bounds__(256) void k_cut_rows_multi(const uint16_t* __restri
             const int total = s_part[0] + s_part[1] + s_part[2] + s_part[3];
             if (tid < n_sets && s_lead[tid] == k) {
                 x[(size_t)tid * n + t] = total;
-                sig[(size_t)tid * n + t] = row_flag(mode, total, st[tid].M, t, thr, psig[tid]);
+                sig[(size_t)tid * n + t] = row_flag(mode, total, st[tid].M, t, thr, st[tid].psig);
             }
             __syncthreads();                              // (s_part is written again by the next item)
         } else if (tid == 0) {                            // the same start as the last scan: only M has changed
-            sig[(size_t)k * n + t] = row_flag(mode, x[(size_t)k * n + t], st[k].M, t, thr, psig[k]);
+            sig[(size_t)k * n + t] = row_flag(mode, x[(size_t)k * n + t], st[k].M, t, thr, st[k].psig);
         }
     }
 }
@@ -378,49 +365,39 @@ __global__ __launch_bounds__(1024) void k_first_pass_decide_multi(int n, ScanSta
 __global__ __launch_bounds__(1024) void k_filter_decide_multi(int n, ScanState* __restrict__ st, const uint8_t* __restrict__ sig,
                                                               int32_t* __restrict__ alt, uint8_t* __restrict__ filt,
                                                               uint8_t* __restrict__ prev, int32_t* __restrict__ seg_g,
-                                                              int32_t* __restrict__ seg_x_g, const double* __restrict__ psig)
+                                                              int32_t* __restrict__ seg_x_g)
 {
     const size_t k = blockIdx.x;
-    filter_decide(n, st + k, sig + k * n, alt + k * n, filt + k * n, prev + k * n, seg_g + k * 3 * n, seg_x_g + k * n, psig[k]);
+    filter_decide(n, st + k, sig + k * n, alt + k * n, filt + k * n, prev + k * n, seg_g + k * 3 * n, seg_x_g + k * n,
+                  st[k].psig);
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------
-void launch_first_pass_pairs(const uint16_t* rank, int64_t ldr, int n, ScanState* st, int32_t* x, uint8_t* sig, double psig,
-                             int32_t* cuts, int32_t* mlog, int log_cap, int pairs, hipStream_t s)
+// One set counts through k_cut_rows with its psig by value: k_cut_rows_multi's per-workgroup prologue over the records
+// costs a lone set ~3 us per scan.
+static void launch_cut_rows(const uint16_t* rank, int64_t ldr, int n, int rows, int n_sets, const ScanState* st, int32_t* x,
+                            uint8_t* sig, double psig0, int share, hipStream_t s)
 {
-    for (int k = 0; k < pairs; k++) {
-        hipLaunchKernelGGL(k_cut_rows, dim3(n), dim3(256), 0, s, rank, ldr, n, st, x, sig, psig);
-        hipLaunchKernelGGL(k_first_pass_decide, dim3(1), dim3(1024), 0, s, n, st, sig, cuts, mlog, log_cap);
-    }
-}
-
-void launch_filter_pairs(const uint16_t* rank, int64_t ldr, int n, int max_rows, ScanState* st, int32_t* x, uint8_t* sig,
-                         double psig, int32_t* alt, uint8_t* filt, uint8_t* prev, int32_t* seg, int32_t* seg_x, int pairs,
-                         hipStream_t s)
-{
-    for (int k = 0; k < pairs; k++) {
-        hipLaunchKernelGGL(k_cut_rows, dim3(max_rows), dim3(256), 0, s, rank, ldr, n, st, x, sig, psig);
-        hipLaunchKernelGGL(k_filter_decide, dim3(1), dim3(1024), 0, s, n, st, sig, alt, filt, prev, seg, seg_x, psig);
-    }
+    if (n_sets == 1) hipLaunchKernelGGL(k_cut_rows, dim3(rows), dim3(256), 0, s, rank, ldr, n, st, x, sig, psig0);
+    else hipLaunchKernelGGL(k_cut_rows_multi, dim3(rows), dim3(256), 0, s, rank, ldr, n, n_sets, st, x, sig, share);
 }
 
 void launch_first_pass_multi_pairs(const uint16_t* rank, int64_t ldr, int n, int n_sets, ScanState* st, int32_t* x, uint8_t* sig,
-                                   const double* psig, int share, int32_t* cuts, int32_t* mlog, int log_cap, int pairs,
-                                   hipStream_t s)
+                                   double psig0, int share, int32_t* cuts, int32_t* mlog, int log_cap, int pairs, hipStream_t s)
 {
     for (int k = 0; k < pairs; k++) {
-        hipLaunchKernelGGL(k_cut_rows_multi, dim3(n), dim3(256), 0, s, rank, ldr, n, n_sets, st, x, sig, psig, share);
+        launch_cut_rows(rank, ldr, n, n, n_sets, st, x, sig, psig0, share, s);
         hipLaunchKernelGGL(k_first_pass_decide_multi, dim3(n_sets), dim3(1024), 0, s, n, st, sig, cuts, mlog, log_cap);
     }
 }
 
 void launch_filter_multi_pairs(const uint16_t* rank, int64_t ldr, int n, int max_rows, int n_sets, ScanState* st, int32_t* x,
-                               uint8_t* sig, const double* psig, int share, int32_t* alt, uint8_t* filt, uint8_t* prev,
+                               uint8_t* sig, double psig0, int share, int32_t* alt, uint8_t* filt, uint8_t* prev,
                                int32_t* seg, int32_t* seg_x, int pairs, hipStream_t s)
 {
     for (int k = 0; k < pairs; k++) {
-        hipLaunchKernelGGL(k_cut_rows_multi, dim3(max_rows), dim3(256), 0, s, rank, ldr, n, n_sets, st, x, sig, psig, share);
-        hipLaunchKernelGGL(k_filter_decide_multi, dim3(n_sets), dim3(1024), 0, s, n, st, sig, alt, filt, prev, seg, seg_x, psig);
+        launch_cut_rows(rank, ldr, n, max_rows, n_sets, st, x, sig, psig0, share, s);
+        hipLaunchKernelGGL(k_filter_decide_multi, dim3(n_sets), dim3(1024), 0, s, n, st, sig, alt, filt, prev, seg, seg_x);
     }
 }
 

@@ -545,10 +545,12 @@ def identifyBoundry(hiddenStates, cutIndices, switchCount=10):
     return int(full[0]) + cutIndices[-1] if len(full) else 0
 
 
-def hmmChromosomes(adjacencyMatrix, cutIndices, binList, minSize=20, convergenceRounds=8, lookAhead=False):
-    """S2C:754-819.  ``adjacencyMatrix``: the DeviceMatrix at its similarity stage (its ``hmm_states(c, p)`` fits and
-    decodes X = log10(similarity + 1)[c:n, c:p])."""
-    n = len(adjacencyMatrix)
+# hmmChromosomes / identifyChromosomeGroupsHMM (S2C:754-942) as generators: every ``adjacencyMatrix.hmm_states(c, p)``
+# becomes ``states = yield (c, width, fit_index)`` with width = p - c, every print a call of ``emit``.  fit_index counts
+# the fits of one run from 0, as HmmDevice.fit_index does.  identifyChromosomeGroupsHMM drives them with a matrix and
+# print; the HMM sweep (sweepHMM.py) drives the generators of many settings in lock step.
+def hmm_chromosomes_steps(n, cutIndices, minSize, convergenceRounds, lookAhead, counter, emit):
+    """S2C:754-819 on an n-bin matrix."""
     if lookAhead != False:                                  # noqa: E712  (the reference's test: 0.0 means "all")
         lookAhead = int((float(n - cutIndices[-1]) * lookAhead) + cutIndices[-1])
     else:
@@ -561,36 +563,37 @@ def hmmChromosomes(adjacencyMatrix, cutIndices, binList, minSize=20, convergence
             break
         c = cutIndices[-1]
         width = max(0, min(prevCutInd, n) - c)                 # len(X[0]) of r[c:prevCutInd]
-        print("Input matrix size = " + str(n - c) + " x " + str(width))
-        print("HMM round = " + str(roundCount))
+        emit("Input matrix size = " + str(n - c) + " x " + str(width))
+        emit("HMM round = " + str(roundCount))
         if width < minSize:
             cutInd = lookAhead
         else:
-            hiddenStates = adjacencyMatrix.hmm_states(c, c + width)
+            hiddenStates = yield (c, width, counter[0])
+            counter[0] += 1
             cutInd = identifyBoundry(hiddenStates, cutIndices, switchCount=minSize)
         if cutInd != prevCutInd:
             prevCutInd = cutInd
             roundCount += 1
             continue
         else:
-            print("HMM convergence rounds = " + str(roundCount))
+            emit("HMM convergence rounds = " + str(roundCount))
             cutIndices.append(int(cutInd))
             break
     if roundCount > convergenceRounds:
         cutIndices.append(int(cutInd))
-        print("WARNING... HMM failed to converge after " + str(roundCount) + " rounds...")
-        print("Proceeding with last found cutIndex of " + str(cutInd) + "...")
+        emit("WARNING... HMM failed to converge after " + str(roundCount) + " rounds...")
+        emit("Proceeding with last found cutIndex of " + str(cutInd) + "...")
     return cutIndices
 
 
-def identifyChromosomeGroupsHMM(adjacencyMatrix, binList, minSize=5, modularity=.05, convergenceRounds=5, lookAhead=.2,
-                                louvainRounds=20, prev_cutInds=False):
-    """S2C:868-942.  One documented difference: where the reference raises IndexError (no cut left after the leading 0
-    is popped, S2C:920), this returns [] with a warning."""
-    print("#########################" + '\n' + "#########################")
-    print("Working on iterative 2 state HMMs to identify chromosome boundaries...")
-    startTime = time.time()
-    n = len(adjacencyMatrix)
+def hmm_groups_steps(n, minSize=5, modularity=.05, convergenceRounds=5, lookAhead=.2, louvainRounds=20,
+                     prev_cutInds=False, emit=print, counter=None, clock=time.time):
+    """identifyChromosomeGroupsHMM on an n-bin matrix; yields fit requests (c, width, fit_index), is sent the decoded
+    states, and returns the cut indices."""
+    counter = [0] if counter is None else counter
+    emit("#########################" + '\n' + "#########################")
+    emit("Working on iterative 2 state HMMs to identify chromosome boundaries...")
+    startTime = clock()
     matrixLength = float(n)
     remainder = matrixLength - (modularity * matrixLength)
     cutIndices = [0]
@@ -599,43 +602,64 @@ def identifyChromosomeGroupsHMM(adjacencyMatrix, binList, minSize=5, modularity=
     if prev_cutInds is not False:
         cutIndices = prev_cutInds
     while cutIndices[-1] <= remainder:
-        print("#########################" + '\n' + "#########################")
-        cutIndices = hmmChromosomes(adjacencyMatrix, cutIndices, binList, minSize=minSize,
-                                    convergenceRounds=convergenceRounds, lookAhead=lookAhead)
-        print("Cut indices =  " + str(cutIndices))
+        emit("#########################" + '\n' + "#########################")
+        cutIndices = yield from hmm_chromosomes_steps(n, cutIndices, minSize, convergenceRounds, lookAhead, counter, emit)
+        emit("Cut indices =  " + str(cutIndices))
         if cutIndices[-1] == 0:
-            print("Algorithm terminated. No obvious chromome boundry could be found... ")
+            emit("Algorithm terminated. No obvious chromome boundry could be found... ")
             break
         if cutIndices[-1] == "NA":
             cutIndices.pop(-1)
             break
     if cutIndices[0] == 0:
         cutIndices.pop(0)
-    print("#########################" + '\n' + "#########################")
-    print("HMM rounds completed in " + str(time.time() - startTime) + " seconds")
-    print("Chromosome groups found via HMMs " + str(len(cutIndices)) + " / " + str(len(cutIndices) + 1))
+    emit("#########################" + '\n' + "#########################")
+    emit("HMM rounds completed in " + str(clock() - startTime) + " seconds")
+    emit("Chromosome groups found via HMMs " + str(len(cutIndices)) + " / " + str(len(cutIndices) + 1))
     if len(cutIndices) == 0:
-        print("- WARNING - no chromosome boundary found by the HMMs (the reference raises IndexError here)")
+        emit("- WARNING - no chromosome boundary found by the HMMs (the reference raises IndexError here)")
         return []
     if cutIndices[-1] == n:
-        print("- WARNING - Last cut index found to be length of current matrix removing index values of {}".format(cutIndices[-1]))
+        emit("- WARNING - Last cut index found to be length of current matrix removing index values of {}".format(cutIndices[-1]))
         cutIndices.pop(-1)
         if len(cutIndices) == 0:
-            print("- WARNING - no chromosome boundary left (the reference raises IndexError here)")
+            emit("- WARNING - no chromosome boundary left (the reference raises IndexError here)")
             return []
         if (n - cutIndices[-1]) >= (5 * (n * modularity)):
-            print("- convergenceRounds reduced from {} --> {}".format(convergenceRounds, convergenceRounds - 1))
+            emit("- convergenceRounds reduced from {} --> {}".format(convergenceRounds, convergenceRounds - 1))
             if convergenceRounds - 1 == 0:
-                print("- Failed to converge after reducing convergence rounds all the way to 1... Returning current indices")
+                emit("- Failed to converge after reducing convergence rounds all the way to 1... Returning current indices")
                 return cutIndices
             else:
-                print("- Recursing on identifyChromosomeGroupsHMM function, due to remaining fraction of data being greater "
-                      "than 5x than that of desired fraction")
-                cutIndices = identifyChromosomeGroupsHMM(adjacencyMatrix, binList, minSize=5, modularity=.05,
+                emit("- Recursing on identifyChromosomeGroupsHMM function, due to remaining fraction of data being greater "
+                     "than 5x than that of desired fraction")
+                cutIndices = yield from hmm_groups_steps(n, minSize=5, modularity=.05,
                                                          convergenceRounds=convergenceRounds - 1, lookAhead=.5,
-                                                         louvainRounds=20, prev_cutInds=cutIndices)
-    print("Total time to identify chromosome boundries = " + str(time.time() - startTime) + " seconds")
+                                                         louvainRounds=20, prev_cutInds=cutIndices, emit=emit,
+                                                         counter=counter, clock=clock)
+    emit("Total time to identify chromosome boundries = " + str(clock() - startTime) + " seconds")
     return cutIndices
+
+
+def drive(gen, states_of):
+    """Run one generator to its end with ``states_of(c, width, fit_index)`` serving its requests; returns its result."""
+    try:
+        req = next(gen)
+        while True:
+            req = gen.send(states_of(*req))
+    except StopIteration as stop:
+        return stop.value
+
+
+def identifyChromosomeGroupsHMM(adjacencyMatrix, binList, minSize=5, modularity=.05, convergenceRounds=5, lookAhead=.2,
+                                louvainRounds=20, prev_cutInds=False):
+    """S2C:868-942.  ``adjacencyMatrix``: the DeviceMatrix at its similarity stage (its ``hmm_states(c, p)`` fits and
+    decodes X = log10(similarity + 1)[c:n, c:p]).  One documented difference: where the reference raises IndexError
+    (no cut left after the leading 0 is popped, S2C:920), this returns [] with a warning."""
+    steps = hmm_groups_steps(len(adjacencyMatrix), minSize=minSize, modularity=modularity,
+                             convergenceRounds=convergenceRounds, lookAhead=lookAhead, louvainRounds=louvainRounds,
+                             prev_cutInds=prev_cutInds, emit=print)
+    return drive(steps, lambda c, width, _fit_index: adjacencyMatrix.hmm_states(c, c + width))
 
 
 # ------------------------------------------------------------------------------------------------

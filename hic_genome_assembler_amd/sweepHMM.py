@@ -5,10 +5,10 @@
            -convergenceRounds 5,8 -lookAhead .2,.5 [-louvainRounds 20] [-device 0] [-out DIR] [-plots]
 
 The map is loaded, clustered (UPGMA) and reordered once.  Every setting then runs identifyChromosomeGroupsHMM's control
-flow as a generator (hmm_groups_steps) that asks for fits instead of making them.  The generators run in lock step:
-each round collects the live settings' fit requests, drops duplicates (a fit is a pure function of (c, width,
-fit_index) for one HICMI_HMM_SEED), and makes the remaining fits together - the X of every distinct c resident in its
-own slot, the k-means++ distances of all restarts in two calls (hicmi_hmm_dist2_multi) and all Lloyd runs in one
+flow as a generator (scaffoldToChromosomes.hmm_groups_steps) that asks for fits instead of making them.  The generators
+run in lock step: each round collects the live settings' fit requests, drops duplicates (a fit is a pure function of
+(c, width, fit_index) for one HICMI_HMM_SEED), and makes the remaining fits together - the X of every distinct c
+resident in its own slot, the k-means++ distances of all restarts in two calls (hicmi_hmm_dist2_multi) and all Lloyd runs in one
 (hicmi_hmm_kmeans_multi); EM and Viterbi stay one fit at a time.  Each setting's directory
 ``DIR/minSize<a>_convergenceRounds<b>_lookAhead<c>_modularity<d>[_louvainRounds<e>]/`` holds the binGroupFile,
 assessmentFile and chromosomeGroupFile (config base names) that ``run_hicAssembler.py -part1`` writes with that setting,
@@ -25,122 +25,16 @@ import time
 
 import numpy as np
 
-from . import plotContactMaps as plotModule
 from . import scaffoldToChromosomes as s2c
-from .hostio import initiateLoci, paused_gc
 from .run_hicAssembler import ensureAllVariablesAreSet, readConfigFileToVariables
-from .sweepPart1 import _captured, _fmt, _is_runtime_line, _split_scaffolds, parse_values
+from .scaffoldToChromosomes import drive, hmm_groups_steps  # noqa: F401  (drive: re-exported with the generator)
+from .sweepPart1 import _fmt, _is_runtime_line, parse_values, resident_map, write_setting, write_summary
 
 SUMMARY_COLUMNS = ["minSize", "convergenceRounds", "lookAhead", "modularity", "louvainRounds", "hmm_cuts", "groups",
                    "louvain_groups", "scaffolds_assigned", "split_scaffolds", "fits_requested", "fits_run", "cut_indices"]
 # the X of all slots resident at once stays under this many bytes (HICMI_HMM_SWEEP_BYTES); more distinct c in one
 # round are built in turn
 SLOT_BYTES = int(os.environ.get("HICMI_HMM_SWEEP_BYTES", str(8 << 30)))
-
-
-# ------------------------------------------------------------------------------------------------
-# identifyChromosomeGroupsHMM / hmmChromosomes (scaffoldToChromosomes.py, S2C:754-942) as generators: every
-# ``adjacencyMatrix.hmm_states(c, c + width)`` becomes ``states = yield (c, width, fit_index)``, every print a call of
-# ``emit``.  fit_index counts the fits of one setting from 0, as HmmDevice.fit_index does in a standalone run.
-def hmm_chromosomes_steps(n, cutIndices, minSize, convergenceRounds, lookAhead, counter, emit):
-    if lookAhead != False:                                  # noqa: E712  (the reference's test: 0.0 means "all")
-        lookAhead = int((float(n - cutIndices[-1]) * lookAhead) + cutIndices[-1])
-    else:
-        lookAhead = n
-    prevCutInd, roundCount = lookAhead, 1
-    while roundCount <= convergenceRounds:
-        if (n - cutIndices[-1]) / 2 < minSize:
-            cutInd = prevCutInd
-            cutIndices.append("NA")
-            break
-        c = cutIndices[-1]
-        width = max(0, min(prevCutInd, n) - c)
-        emit("Input matrix size = " + str(n - c) + " x " + str(width))
-        emit("HMM round = " + str(roundCount))
-        if width < minSize:
-            cutInd = lookAhead
-        else:
-            hiddenStates = yield (c, width, counter[0])
-            counter[0] += 1
-            cutInd = s2c.identifyBoundry(hiddenStates, cutIndices, switchCount=minSize)
-        if cutInd != prevCutInd:
-            prevCutInd = cutInd
-            roundCount += 1
-            continue
-        else:
-            emit("HMM convergence rounds = " + str(roundCount))
-            cutIndices.append(int(cutInd))
-            break
-    if roundCount > convergenceRounds:
-        cutIndices.append(int(cutInd))
-        emit("WARNING... HMM failed to converge after " + str(roundCount) + " rounds...")
-        emit("Proceeding with last found cutIndex of " + str(cutInd) + "...")
-    return cutIndices
-
-
-def hmm_groups_steps(n, minSize=5, modularity=.05, convergenceRounds=5, lookAhead=.2, louvainRounds=20,
-                     prev_cutInds=False, emit=print, counter=None, clock=time.time):
-    """identifyChromosomeGroupsHMM on an n-bin matrix; yields fit requests (c, width, fit_index), is sent the decoded
-    states, and returns the cut indices."""
-    counter = [0] if counter is None else counter
-    emit("#########################" + '\n' + "#########################")
-    emit("Working on iterative 2 state HMMs to identify chromosome boundaries...")
-    startTime = clock()
-    matrixLength = float(n)
-    remainder = matrixLength - (modularity * matrixLength)
-    cutIndices = [0]
-    if modularity == 1:
-        return []
-    if prev_cutInds is not False:
-        cutIndices = prev_cutInds
-    while cutIndices[-1] <= remainder:
-        emit("#########################" + '\n' + "#########################")
-        cutIndices = yield from hmm_chromosomes_steps(n, cutIndices, minSize, convergenceRounds, lookAhead, counter, emit)
-        emit("Cut indices =  " + str(cutIndices))
-        if cutIndices[-1] == 0:
-            emit("Algorithm terminated. No obvious chromome boundry could be found... ")
-            break
-        if cutIndices[-1] == "NA":
-            cutIndices.pop(-1)
-            break
-    if cutIndices[0] == 0:
-        cutIndices.pop(0)
-    emit("#########################" + '\n' + "#########################")
-    emit("HMM rounds completed in " + str(clock() - startTime) + " seconds")
-    emit("Chromosome groups found via HMMs " + str(len(cutIndices)) + " / " + str(len(cutIndices) + 1))
-    if len(cutIndices) == 0:
-        emit("- WARNING - no chromosome boundary found by the HMMs (the reference raises IndexError here)")
-        return []
-    if cutIndices[-1] == n:
-        emit("- WARNING - Last cut index found to be length of current matrix removing index values of {}".format(cutIndices[-1]))
-        cutIndices.pop(-1)
-        if len(cutIndices) == 0:
-            emit("- WARNING - no chromosome boundary left (the reference raises IndexError here)")
-            return []
-        if (n - cutIndices[-1]) >= (5 * (n * modularity)):
-            emit("- convergenceRounds reduced from {} --> {}".format(convergenceRounds, convergenceRounds - 1))
-            if convergenceRounds - 1 == 0:
-                emit("- Failed to converge after reducing convergence rounds all the way to 1... Returning current indices")
-                return cutIndices
-            else:
-                emit("- Recursing on identifyChromosomeGroupsHMM function, due to remaining fraction of data being greater "
-                     "than 5x than that of desired fraction")
-                cutIndices = yield from hmm_groups_steps(n, minSize=5, modularity=.05,
-                                                         convergenceRounds=convergenceRounds - 1, lookAhead=.5,
-                                                         louvainRounds=20, prev_cutInds=cutIndices, emit=emit,
-                                                         counter=counter, clock=clock)
-    emit("Total time to identify chromosome boundries = " + str(clock() - startTime) + " seconds")
-    return cutIndices
-
-
-def drive(gen, states_of):
-    """Run one generator to its end with ``states_of(c, width, fit_index)`` serving its requests; returns its result."""
-    try:
-        req = next(gen)
-        while True:
-            req = gen.send(states_of(*req))
-    except StopIteration as stop:
-        return stop.value
 
 
 # ------------------------------------------------------------------------------------------------
@@ -337,68 +231,27 @@ def runSweep(hicProBedFile, hicProBiasFile, hicProMatrixFile, hicProScaffSizeFil
     os.makedirs(outDir, exist_ok=True)
     print("### Part 1 HMM sweep: %d settings ###" % len(grid))
     t_all = time.time()
-    binList = initiateLoci(hicProBedFile, hicProBiasFile)
-    adjMat = s2c.buildAdjacencyMatrix(hicProMatrixFile, binList, device=device)
-    writer = s2c._FileWriter(True)
     rows = []
-    try:
-        with paused_gc():
-            adjMat, binList, dendrogram, prep = s2c._cluster_resident(adjMat, binList, hicProScaffSizeFile,
-                                                                      lambda _name: None, time.time())
-            writer.submit(s2c.dendrogramLeafOrder_toFile, dendrogram, dendrogramOrderFile, prep["dend_lines"])
-            n = adjMat.n
-            t0 = time.time()
-            fitter = HmmBatchFitter(adjMat)
-            found = run_lock_step(n, grid, fitter)
-            print("- HMM fits: %d requested, %d run for %d settings in %.3f s"
-                  % (sum(f[2] for f in found), sum(f[3] for f in found), len(grid), time.time() - t0))
-            if os.environ.get("HICMI_HMM_PROFILE") == "1":
-                fitter.report()
-            for (ms, cr, la, mod, lr), (cuts, lines, n_req, n_run) in zip(grid, found):
-                log = [ln for ln in "\n".join(lines).split("\n") if not _is_hmm_runtime_line(ln)]
-                order, bins = list(adjMat.order), binList
-                louvain_groups = 0
-                cuts_final = list(cuts)
-                if mod is not False and mod > 0.0:
-                    start = sorted(cuts)[-1] if len(cuts) else 0
-                    if n - start > 0:
-                        (new_order, final), lns = _captured(s2c._louvain_tail, adjMat, binList, list(cuts), lr)
-                        log += [ln for ln in lns if not _is_hmm_runtime_line(ln)]
-                        order = [order[i] for i in new_order]
-                        bins = [binList[i] for i in new_order]
-                        louvain_groups = len(final) + 1 - len(cuts)
-                        cuts_final = list(final)
-                d = os.path.join(outDir, setting_name(ms, cr, la, mod, lr if name_louvain_rounds else None))
-                os.makedirs(d, exist_ok=True)
-                writer.submit(s2c.writeBinGroupingsToFile, cuts_final, bins, os.path.join(d, os.path.basename(binGroupFile)),
-                              prep["bin_lines"])
-                binGroups = s2c._bin_group_pairs(cuts_final, bins, prep["pairs"])
-                log.append(str(len(binGroups)) + " chromosomes read in from file")
-                with_louvain = mod is not False and mod > 0.0
-                chrGroups = s2c.assessChromosomeClustering(binGroups, os.path.join(d, os.path.basename(assessmentFile)),
-                                                           write=writer.submit,
-                                                           scaffolds=None if with_louvain else prep["scaffolds"])
-                writer.submit(s2c.writeChromosomeGroupingsToFile, chrGroups, prep["sizes"],
-                              os.path.join(d, os.path.basename(chromosomeGroupFile)), prep["entry_lines"])
-                writer.submit(s2c._write_text, os.path.join(d, "part1.log"), "\n".join(log) + "\n")
-                if plots and avgClusterPlot_outlined and plotModule.plots_enabled(avgClusterPlot_outlined):
-                    plotModule.plotContactMap(plotModule.DeviceImage(adjMat.ctx, 1, order), resolution=resolution,
-                                              highlightChroms=cuts_final, showPlot=False,
-                                              savePlot=os.path.join(d, os.path.basename(avgClusterPlot_outlined)))
-                rows.append({"minSize": ms, "convergenceRounds": cr, "lookAhead": la, "modularity": mod,
-                             "louvainRounds": lr, "hmm_cuts": len(cuts), "groups": len(binGroups),
-                             "louvain_groups": louvain_groups,
-                             "scaffolds_assigned": sum(len(names) for names in chrGroups.scaffolds),
-                             "split_scaffolds": _split_scaffolds(binGroups), "fits_requested": n_req, "fits_run": n_run,
-                             "cut_indices": cuts_final})
-    finally:
-        writer.finish()
-        adjMat.ctx.close()
-    with open(os.path.join(outDir, "sweep_summary.tsv"), "w") as fh:
-        fh.write("\t".join(SUMMARY_COLUMNS) + "\n")
-        for r in rows:
-            fh.write("\t".join(",".join(str(c) for c in r[k]) if k == "cut_indices" else str(r[k])
-                               for k in SUMMARY_COLUMNS) + "\n")
+    with resident_map(hicProBedFile, hicProBiasFile, hicProMatrixFile, hicProScaffSizeFile, dendrogramOrderFile,
+                      device) as res:
+        n = res.adjMat.n
+        t0 = time.time()
+        fitter = HmmBatchFitter(res.adjMat)
+        found = run_lock_step(n, grid, fitter)
+        print("- HMM fits: %d requested, %d run for %d settings in %.3f s"
+              % (sum(f[2] for f in found), sum(f[3] for f in found), len(grid), time.time() - t0))
+        if os.environ.get("HICMI_HMM_PROFILE") == "1":
+            fitter.report()
+        for (ms, cr, la, mod, lr), (cuts, lines, n_req, n_run) in zip(grid, found):
+            log = [ln for ln in "\n".join(lines).split("\n") if not _is_hmm_runtime_line(ln)]
+            d = os.path.join(outDir, setting_name(ms, cr, la, mod, lr if name_louvain_rounds else None))
+            common = write_setting(res, d, cuts, log, mod, lr, _is_hmm_runtime_line,
+                                   (binGroupFile, assessmentFile, chromosomeGroupFile),
+                                   avgClusterPlot_outlined if plots else None, resolution)
+            rows.append(dict({"minSize": ms, "convergenceRounds": cr, "lookAhead": la, "modularity": mod,
+                              "louvainRounds": lr, "hmm_cuts": len(cuts), "fits_requested": n_req, "fits_run": n_run},
+                             **common))
+    write_summary(outDir, SUMMARY_COLUMNS, rows)
     print("Total run-time of the Part 1 HMM sweep = " + str(time.time() - t_all))
     return rows
 

@@ -15,6 +15,7 @@ can be given to ``-part2``.  A flag that is not given takes the config's value; 
 from __future__ import annotations
 
 import argparse
+import collections
 import contextlib
 import io
 import os
@@ -139,6 +140,77 @@ def _split_scaffolds(binGroups):
     return sum(1 for v in where.values() if len(v) > 1)
 
 
+# ---- what both sweeps (this one and sweepHMM.py) share ----------------------------------------------------------------
+Resident = collections.namedtuple("Resident", "adjMat binList prep writer")
+
+
+@contextlib.contextmanager
+def resident_map(hicProBedFile, hicProBiasFile, hicProMatrixFile, hicProScaffSizeFile, dendrogramOrderFile, device=0):
+    """The map loaded, clustered (UPGMA) and reordered once, its dendrogramOrderFile queued on a writer thread: yields a
+    Resident.  On the way out the writer is drained and the device context closed."""
+    binList = initiateLoci(hicProBedFile, hicProBiasFile)
+    adjMat = s2c.buildAdjacencyMatrix(hicProMatrixFile, binList, device=device)
+    writer = s2c._FileWriter(True)
+    try:
+        with paused_gc():
+            adjMat, binList, dendrogram, prep = s2c._cluster_resident(adjMat, binList, hicProScaffSizeFile,
+                                                                      lambda _name: None, time.time())
+            writer.submit(s2c.dendrogramLeafOrder_toFile, dendrogram, dendrogramOrderFile, prep["dend_lines"])
+            yield Resident(adjMat, binList, prep, writer)
+    finally:
+        writer.finish()
+        adjMat.ctx.close()
+
+
+def write_setting(res, d, cuts, log, modularity, louvainRounds, is_runtime, files, plot=None, resolution=100000):
+    """One setting's outputs in directory ``d``, from the cut indices of its boundary phase and the lines ``log`` that
+    phase printed: the Louvain tail when modularity > 0 (its lines appended, run-time lines dropped by ``is_runtime``),
+    the binGroupFile, assessmentFile and chromosomeGroupFile of ``files`` (their base names), part1.log and, when
+    ``plot`` names a file, the outlined clustered map.  Returns the summary columns both sweeps have."""
+    adjMat, binList, prep, writer = res
+    n = adjMat.n
+    binGroupFile, assessmentFile, chromosomeGroupFile = (os.path.join(d, os.path.basename(f)) for f in files)
+    log = list(log)
+    order, bins = list(adjMat.order), binList
+    cuts_final = list(cuts)
+    louvain_groups = 0
+    with_louvain = modularity is not False and modularity > 0.0
+    if with_louvain:
+        start = sorted(cuts)[-1] if len(cuts) else 0
+        if n - start > 0:
+            (new_order, final), lines = _captured(s2c._louvain_tail, adjMat, binList, list(cuts), louvainRounds)
+            log += [ln for ln in lines if not is_runtime(ln)]
+            order = [order[i] for i in new_order]
+            bins = [binList[i] for i in new_order]
+            louvain_groups = len(final) + 1 - len(cuts)
+            cuts_final = list(final)
+    os.makedirs(d, exist_ok=True)
+    writer.submit(s2c.writeBinGroupingsToFile, cuts_final, bins, binGroupFile, prep["bin_lines"])
+    binGroups = s2c._bin_group_pairs(cuts_final, bins, prep["pairs"])
+    log.append(str(len(binGroups)) + " chromosomes read in from file")
+    chrGroups = s2c.assessChromosomeClustering(binGroups, assessmentFile, write=writer.submit,
+                                               scaffolds=None if with_louvain else prep["scaffolds"])
+    writer.submit(s2c.writeChromosomeGroupingsToFile, chrGroups, prep["sizes"], chromosomeGroupFile, prep["entry_lines"])
+    writer.submit(s2c._write_text, os.path.join(d, "part1.log"), "\n".join(log) + "\n")
+    if plot and plotModule.plots_enabled(plot):
+        plotModule.plotContactMap(plotModule.DeviceImage(adjMat.ctx, 1, order), resolution=resolution,
+                                  highlightChroms=cuts_final, showPlot=False,
+                                  savePlot=os.path.join(d, os.path.basename(plot)))
+    return {"groups": len(binGroups), "louvain_groups": louvain_groups,
+            "scaffolds_assigned": sum(len(names) for names in chrGroups.scaffolds),
+            "split_scaffolds": _split_scaffolds(binGroups), "cut_indices": cuts_final}
+
+
+def write_summary(outDir, columns, rows):
+    """``outDir/sweep_summary.tsv``: one row per setting, cut_indices comma-separated."""
+    with open(os.path.join(outDir, "sweep_summary.tsv"), "w") as fh:
+        fh.write("\t".join(columns) + "\n")
+        for r in rows:
+            fh.write("\t".join(",".join(str(c) for c in r[k]) if k == "cut_indices" else str(r[k])
+                               for k in columns) + "\n")
+
+
+# ------------------------------------------------------------------------------------------------
 def runSweep(hicProBedFile, hicProBiasFile, hicProMatrixFile, hicProScaffSizeFile, dendrogramOrderFile,
              binGroupFile, assessmentFile, chromosomeGroupFile, minSizes, psigs, modularities, louvainRounds, outDir,
              name_louvain_rounds=None, avgClusterPlot_outlined=None, resolution=100000, plots=False, device=0,
@@ -154,78 +226,33 @@ def runSweep(hicProBedFile, hicProBiasFile, hicProMatrixFile, hicProScaffSizeFil
     os.makedirs(outDir, exist_ok=True)
     print("### Part 1 sweep: %d combinations ###" % len(combos))
     t_all = time.time()
-    binList = initiateLoci(hicProBedFile, hicProBiasFile)
-    adjMat = s2c.buildAdjacencyMatrix(hicProMatrixFile, binList, device=device)
-    writer = s2c._FileWriter(True)
     rows = []
-    try:
-        with paused_gc():
-            adjMat, binList, dendrogram, prep = s2c._cluster_resident(adjMat, binList, hicProScaffSizeFile,
-                                                                      lambda _name: None, time.time())
-            rm = s2c.rankOrderMatrix(adjMat)
-            writer.submit(s2c.dendrogramLeafOrder_toFile, dendrogram, dendrogramOrderFile, prep["dend_lines"])
-            n = len(rm)
-            t0 = time.time()
-            fp_keys, combo_fp = plan(n, combos)
-            fp = first_passes(rm, fp_keys)
-            fp[None] = ([], [])                                   # min_frac == 1: no scan, nothing printed
-            flt_keys = []
-            for (_ms, ps, _mod, _lr), k in zip(combos, combo_fp):
-                key = (tuple(fp[k][0]), ps)
-                if key not in flt_keys:
-                    flt_keys.append(key)
-            flt = filters(rm, [k for k in flt_keys if len(k[0])])
-            print("- Scan loops: %d first-pass and %d filter sets for %d combinations in %.3f s"
-                  % (len(fp_keys), len(flt), len(combos), time.time() - t0))
-            for (ms, ps, mod, lr), k in zip(combos, combo_fp):
-                first, first_lines = fp[k]
-                cuts, flt_lines = flt[(tuple(first), ps)] if len(first) else ([], [])
-                log = list(first_lines) + list(flt_lines)
-                order, bins = list(adjMat.order), binList
-                with_louvain = mod is not False and mod > 0.0
-                louvain_groups = 0
-                if with_louvain:
-                    start = sorted(cuts)[-1] if len(cuts) else 0
-                    if n - start > 0:
-                        (new_order, final), lines = _captured(s2c._louvain_tail, adjMat, binList, cuts, lr)
-                        log += [ln for ln in lines if not _is_runtime_line(ln)]
-                        order = [order[i] for i in new_order]
-                        bins = [binList[i] for i in new_order]
-                        louvain_groups = len(final) + 1 - len(cuts)
-                        cuts_final = list(final)
-                    else:
-                        cuts_final = list(cuts)
-                else:
-                    cuts_final = list(cuts)
-                d = os.path.join(outDir, combo_name(ms, ps, mod, lr if name_louvain_rounds else None))
-                os.makedirs(d, exist_ok=True)
-                writer.submit(s2c.writeBinGroupingsToFile, cuts_final, bins, os.path.join(d, os.path.basename(binGroupFile)),
-                              prep["bin_lines"])
-                binGroups = s2c._bin_group_pairs(cuts_final, bins, prep["pairs"])
-                log.append(str(len(binGroups)) + " chromosomes read in from file")
-                chrGroups = s2c.assessChromosomeClustering(binGroups, os.path.join(d, os.path.basename(assessmentFile)),
-                                                           write=writer.submit,
-                                                           scaffolds=None if with_louvain else prep["scaffolds"])
-                writer.submit(s2c.writeChromosomeGroupingsToFile, chrGroups, prep["sizes"],
-                              os.path.join(d, os.path.basename(chromosomeGroupFile)), prep["entry_lines"])
-                writer.submit(s2c._write_text, os.path.join(d, "part1.log"), "\n".join(log) + "\n")
-                if plots and avgClusterPlot_outlined and plotModule.plots_enabled(avgClusterPlot_outlined):
-                    plotModule.plotContactMap(plotModule.DeviceImage(adjMat.ctx, 1, order), resolution=resolution,
-                                              highlightChroms=cuts_final, showPlot=False,
-                                              savePlot=os.path.join(d, os.path.basename(avgClusterPlot_outlined)))
-                rows.append({"minSize": ms, "psig": ps, "modularity": mod, "louvainRounds": lr,
-                             "first_pass_cuts": len(first), "filtered_cuts": len(cuts), "groups": len(binGroups),
-                             "louvain_groups": louvain_groups,
-                             "scaffolds_assigned": sum(len(names) for names in chrGroups.scaffolds),
-                             "split_scaffolds": _split_scaffolds(binGroups), "cut_indices": cuts_final})
-    finally:
-        writer.finish()
-        adjMat.ctx.close()
-    with open(os.path.join(outDir, "sweep_summary.tsv"), "w") as fh:
-        fh.write("\t".join(SUMMARY_COLUMNS) + "\n")
-        for r in rows:
-            fh.write("\t".join(",".join(str(c) for c in r[k]) if k == "cut_indices" else str(r[k])
-                               for k in SUMMARY_COLUMNS) + "\n")
+    with resident_map(hicProBedFile, hicProBiasFile, hicProMatrixFile, hicProScaffSizeFile, dendrogramOrderFile,
+                      device) as res:
+        rm = s2c.rankOrderMatrix(res.adjMat)
+        n = len(rm)
+        t0 = time.time()
+        fp_keys, combo_fp = plan(n, combos)
+        fp = first_passes(rm, fp_keys)
+        fp[None] = ([], [])                                   # min_frac == 1: no scan, nothing printed
+        flt_keys = []
+        for (_ms, ps, _mod, _lr), k in zip(combos, combo_fp):
+            key = (tuple(fp[k][0]), ps)
+            if key not in flt_keys:
+                flt_keys.append(key)
+        flt = filters(rm, [k for k in flt_keys if len(k[0])])
+        print("- Scan loops: %d first-pass and %d filter sets for %d combinations in %.3f s"
+              % (len(fp_keys), len(flt), len(combos), time.time() - t0))
+        for (ms, ps, mod, lr), k in zip(combos, combo_fp):
+            first, first_lines = fp[k]
+            cuts, flt_lines = flt[(tuple(first), ps)] if len(first) else ([], [])
+            d = os.path.join(outDir, combo_name(ms, ps, mod, lr if name_louvain_rounds else None))
+            common = write_setting(res, d, cuts, list(first_lines) + list(flt_lines), mod, lr, _is_runtime_line,
+                                   (binGroupFile, assessmentFile, chromosomeGroupFile),
+                                   avgClusterPlot_outlined if plots else None, resolution)
+            rows.append(dict({"minSize": ms, "psig": ps, "modularity": mod, "louvainRounds": lr,
+                              "first_pass_cuts": len(first), "filtered_cuts": len(cuts)}, **common))
+    write_summary(outDir, SUMMARY_COLUMNS, rows)
     print("Total run-time of the Part 1 sweep = " + str(time.time() - t_all))
     return rows
 

@@ -1,12 +1,16 @@
 """The Part 1 HMM sweep (sweepHMM.py) on the CPU: grid parsing, names, refusals, the generator form of
-identifyChromosomeGroupsHMM against the function itself, and the lock-step planner's sharing of fits."""
+identifyChromosomeGroupsHMM against recorded digests and the literal restatement, and the lock-step planner's sharing of
+fits."""
 import contextlib
+import hashlib
 import io
+import json
 import os
 
 import numpy as np
 import pytest
 
+import hmm_reference as ref
 from test_sweep_cpu import _config
 
 PATHS = {k: "x" for k in ("hicProBedFile", "hicProBiasFile", "hicProMatrixFile", "hicProScaffSizeFile")}
@@ -79,44 +83,68 @@ def _strip(lines):
     return [ln for ln in "\n".join(lines).split("\n") if not sw._is_hmm_runtime_line(ln)]
 
 
-def test_generator_equals_identifyChromosomeGroupsHMM():
-    from hic_genome_assembler_amd import scaffoldToChromosomes as s2c, sweepHMM as sw
-    seen = set()
-    for n in (40, 90, 300):
-        for seed in range(6):
-            for ms in (3, 5, 12):
-                for mod in (0.0, .05, .3, 1):
-                    for cr in (1, 2, 4):
-                        for la in (False, .2, .5, 1.0):
-                            fm = _FakeMatrix(n, _scripted(seed))
-                            buf = io.StringIO()
-                            with contextlib.redirect_stdout(buf):
-                                want = s2c.identifyChromosomeGroupsHMM(fm, None, minSize=ms, modularity=mod,
-                                                                       convergenceRounds=cr, lookAhead=la)
-                            lines, reqs = [], []
-                            fn = _scripted(seed)
+# n x seed x minSize x modularity x convergenceRounds x lookAhead; tests/golden/hmm_groups_digests.json holds one digest
+# per case in this order, recorded from the function before it was driven by the generator
+HMM_GRID = [(n, seed, ms, mod, cr, la) for n in (40, 90, 300) for seed in range(6) for ms in (3, 5, 12)
+            for mod in (0.0, .05, .3, 1) for cr in (1, 2, 4) for la in (False, .2, .5, 1.0)]
+HMM_DIGESTS = os.path.join(os.path.dirname(__file__), "golden", "hmm_groups_digests.json")
 
-                            def serve(c, width, fit_index):
-                                reqs.append((c, width))
-                                assert fit_index == len(reqs) - 1
-                                return fn(c, width, fit_index, n)
-                            got = sw.drive(sw.hmm_groups_steps(n, minSize=ms, modularity=mod, convergenceRounds=cr,
-                                                               lookAhead=la, emit=lines.append), serve)
-                            assert got == want, (n, seed, ms, mod, cr, la)
-                            assert reqs == fm.calls
-                            printed = _strip(buf.getvalue().splitlines())
-                            assert _strip(lines) == printed
-                            text = "\n".join(printed)
-                            seen.update(k for k, s in (("NA", "'NA']"), ("noconv", "failed to converge"),
-                                                       ("pop", "Last cut index found to be length"),
-                                                       ("recurse", "Recursing on identifyChromosomeGroupsHMM"),
-                                                       ("terminated", "Algorithm terminated"))
-                                        if s in text)
-                            if mod == 1:
-                                assert got == [] and not reqs
-                                seen.add("mod1")
-                            if mod == 0.0:
-                                seen.add("mod0")
+
+def _digest(cuts, calls, lines):
+    """12 hex digits of the cut list, the (c, width) requests and the printed lines (run-time lines stripped)."""
+    blob = json.dumps([cuts, [list(k) for k in calls], lines])
+    return hashlib.sha256(blob.encode()).hexdigest()[:12]
+
+
+def _run_identify(n, seed, ms, mod, cr, la):
+    """identifyChromosomeGroupsHMM on a scripted matrix: (cuts, requests, printed lines without run-time lines)."""
+    from hic_genome_assembler_amd import scaffoldToChromosomes as s2c
+    fm = _FakeMatrix(n, _scripted(seed))
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        cuts = s2c.identifyChromosomeGroupsHMM(fm, None, minSize=ms, modularity=mod, convergenceRounds=cr, lookAhead=la)
+    return cuts, fm.calls, _strip(buf.getvalue().splitlines())
+
+
+def test_generator_equals_identifyChromosomeGroupsHMM():
+    """identifyChromosomeGroupsHMM (the generator driven with print) matches the recorded digests of the function it
+    replaced, the literal restatement in hmm_reference.py on cuts and requests, and the generator driven by hand on
+    cuts, requests, fit indices and lines."""
+    from hic_genome_assembler_amd import scaffoldToChromosomes as s2c
+    with open(HMM_DIGESTS) as fh:
+        digests = json.load(fh)
+    assert len(digests) == len(HMM_GRID)
+    seen = set()
+    for (n, seed, ms, mod, cr, la), digest in zip(HMM_GRID, digests):
+        case = (n, seed, ms, mod, cr, la)
+        want, calls, printed = _run_identify(*case)
+        assert _digest(want, calls, printed) == digest, case
+        ref_backend = _FakeMatrix(n, _scripted(seed))
+        assert ref.identifyChromosomeGroupsHMM(ref_backend, ms, mod, cr, la) == want, case
+        assert ref_backend.calls == calls, case
+        lines, reqs = [], []
+        fn = _scripted(seed)
+
+        def serve(c, width, fit_index):
+            reqs.append((c, width))
+            assert fit_index == len(reqs) - 1
+            return fn(c, width, fit_index, n)
+        got = s2c.drive(s2c.hmm_groups_steps(n, minSize=ms, modularity=mod, convergenceRounds=cr, lookAhead=la,
+                                             emit=lines.append), serve)
+        assert got == want, case
+        assert reqs == calls
+        assert _strip(lines) == printed
+        text = "\n".join(printed)
+        seen.update(k for k, s in (("NA", "'NA']"), ("noconv", "failed to converge"),
+                                   ("pop", "Last cut index found to be length"),
+                                   ("recurse", "Recursing on identifyChromosomeGroupsHMM"),
+                                   ("terminated", "Algorithm terminated"))
+                    if s in text)
+        if mod == 1:
+            assert got == [] and not reqs
+            seen.add("mod1")
+        if mod == 0.0:
+            seen.add("mod0")
     assert seen >= {"NA", "noconv", "pop", "recurse", "terminated", "mod0", "mod1"}, seen
 
 
