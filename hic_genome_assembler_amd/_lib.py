@@ -69,6 +69,7 @@ SIGNATURES = {
     "hicmi_p2_score_window": (ctypes.c_int, [_vp, c_i64, c_i64, _vp]),
     "hicmi_p2_decide_window": (ctypes.c_int, [_vp, c_i64, c_i64, c_dbl, c_dbl, c_dbl, ctypes.POINTER(c_i64),
                                               ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl)]),
+    "hicmi_p2_window_shortlist": (ctypes.c_int, [_vp, c_i64, c_i64, c_i64, c_dbl, c_dbl, c_dbl, c_i64, _vp, _vp, _vp]),
     "hicmi_p2_decide_insertion": (ctypes.c_int, [_vp, _vp, _vp, c_i64, ctypes.c_int32, ctypes.c_int32,
                                                  ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_int32),
                                                  ctypes.POINTER(c_dbl)]),
@@ -485,6 +486,17 @@ class Context:
                                                 float("nan") if cur_fast is None else float(cur_fast),
                                                 ctypes.byref(pick), ctypes.byref(best), ctypes.byref(pf)))
         return pick.value, best.value, pf.value
+
+    def p2_window_shortlist(self, first, count, k, total, floor, cur_fast=None, cap=4096):
+        """Device short lists of ``count`` consecutive windows (hicmi_p2_window_shortlist): per window
+        (candidate indices, fast scores), or None when its list overflowed ``cap``."""
+        n_near = np.zeros(int(count), np.int64)
+        idx = np.zeros((int(count), int(cap)), np.int64)
+        fast = np.zeros((int(count), int(cap)), np.float64)
+        _check(self._lib.hicmi_p2_window_shortlist(self._h, int(first), int(count), int(k), float(total), float(floor),
+                                                   float("nan") if cur_fast is None else float(cur_fast), int(cap),
+                                                   _ptr(n_near), _ptr(idx), _ptr(fast)))
+        return [None if m > cap else (idx[w, :m].copy(), fast[w, :m].copy()) for w, m in enumerate(n_near.tolist())]
 
     def p2_decide_insertion(self, ids, rev, new_id, new_rev_now):
         """One whole checkAllScores step; returns (gap or -1, reversed flag, literal best)."""

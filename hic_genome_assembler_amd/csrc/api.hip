@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -120,6 +121,10 @@ struct hicmi_ctx {
     double* d_G = nullptr; int64_t g_cap = 0;
     double* d_delta = nullptr; int64_t delta_cap = 0;
     WindowBatchEntry* d_wb = nullptr; int64_t wb_cap = 0;
+    // short lists of wide windows decided on the device (HICMI_P2_DEVICE_DECIDE, read at creation): windows of at least
+    // near_min_k scaffolds; [per-window counters][pass-1 partials][NearEntry lists]
+    int near_min_k = 7;
+    unsigned char* d_wnear = nullptr; int64_t wnear_cap = 0;
     // device-decided insertion (k_part2_insert.hip): second arrangement buffers (ping-pong) and work areas
     int32_t* d_arr_packed2 = nullptr; int64_t arr2_cap = 0;
     int32_t* d_pos2sel2 = nullptr; int64_t pos2_cap = 0;
@@ -338,6 +343,11 @@ int hicmi_create(int device, hicmi_ctx** out)
     hipError_t se = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (se != hipSuccess) { delete c; return fail(HICMI_EHIP, "hipStreamCreate: %s", hipGetErrorString(se)); }
     c->probed_xcc = nnchain_probe_xcc(c->stream);
+    // "off": every window downloads its deltas; a number n >= 1: windows of at least n scaffolds use the device short list
+    if (const char* dd = getenv("HICMI_P2_DEVICE_DECIDE")) {
+        if (!strcmp(dd, "off")) c->near_min_k = INT_MAX;
+        else if (atoi(dd) >= 1) c->near_min_k = atoi(dd);
+    }
     *out = c;
     return HICMI_OK;
 }
@@ -359,7 +369,7 @@ int hicmi_destroy(hicmi_ctx* c)
     free_dev(c->d_partial); free_dev(c->d_T);
     free_dev(c->d_scaf_start); free_dev(c->d_scaf_len); free_dev(c->d_arr_packed);
     free_dev(c->d_pos2sel); free_dev(c->d_orders); free_dev(c->d_orients);
-    free_dev(c->d_G); free_dev(c->d_delta); free_dev(c->d_wb);
+    free_dev(c->d_G); free_dev(c->d_delta); free_dev(c->d_wb); free_dev(c->d_wnear);
     free_dev(c->d_arr_packed2); free_dev(c->d_pos2sel2); free_dev(c->d_ins_T); free_dev(c->d_ins_partial);
     free_dev(c->d_ins_blob); free_dev(c->d_ins_steps);
     free_dev(c->d_plot_order); free_dev(c->d_plot_work); free_dev(c->d_plot_img);
@@ -1596,17 +1606,29 @@ int hicmi_p2_window_tables(hicmi_ctx* c, int64_t k, const int8_t* orders, int64_
 }
 
 namespace {
-// deltas of `count` consecutive windows (first0, first0+1, ...) of k scaffolds against the CURRENT
-// arrangement, one launch pair; delta_out: count x n_cand
-int window_batch(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k, double* delta_out)
+// candidate index of window `first`'s current configuration: identity order + the window's current signs (-1: its signs
+// are not in the orientation table)
+int64_t window_c0(const hicmi_ctx* c, int64_t first, int64_t k)
+{
+    for (int64_t r = 0; r < c->n_orients; r++) {
+        bool same = true;
+        for (int64_t j = 0; j < k; j++) same = same && ((c->h_orients[(size_t)(r * k + j)] != 0) == (c->h_arr_rev[(size_t)(first + j)] != 0));
+        if (same) return r;
+    }
+    return -1;
+}
+
+struct BatchCost { int64_t g_total = 0; int max_m = 0; double g_bytes = 0.0, d_bytes = 0.0, g_flops = 0.0; };
+
+// the batch records of `count` consecutive windows (first0, first0+1, ...) of k scaffolds against the CURRENT arrangement
+int fill_batch(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k, std::vector<WindowBatchEntry>& wb, BatchCost& bc)
 {
     const int64_t S = (int64_t)c->h_arr_id.size();
     if (c->n_arr < 1 || S < 1) return fail(HICMI_EINVAL, "hicmi_p2_set_arrangement has not run");
     if (k != c->tab_k) return fail(HICMI_EINVAL, "hicmi_p2_window_tables has not been called for k = %lld", (long long)k);
     if (first0 < 0 || count < 1 || first0 + count - 1 + k > S) return fail(HICMI_EINVAL, "window out of range");
-    HIPCHK(hipSetDevice(c->device));
     const int64_t n_cand = c->n_orders * c->n_orients;
-    std::vector<WindowBatchEntry> wb((size_t)count);
+    wb.assign((size_t)count, WindowBatchEntry{});
     int64_t g_total = 0; int max_m = 0; double g_bytes = 0.0, d_bytes = 0.0, g_flops = 0.0;
     for (int64_t wdx = 0; wdx < count; wdx++) {
         const int64_t first = first0 + wdx;
@@ -1627,10 +1649,26 @@ int window_batch(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k, double*
         g_flops += 2.0 * (double)e.m * (double)e.m * (double)(c->n_arr - e.m);       // A (m x (n - m)) . Toeplitz ((n - m) x m), all scaffolds of the window
         d_bytes += 8.0 * (double)n_cand * (0.5 * (double)e.m * (double)(e.m - 1) + (double)e.m);
     }
+    bc.g_total = g_total; bc.max_m = max_m; bc.g_bytes = g_bytes; bc.d_bytes = d_bytes; bc.g_flops = g_flops;
+    return HICMI_OK;
+}
+
+// deltas of `count` consecutive windows (first0, first0+1, ...) of k scaffolds against the CURRENT
+// arrangement, one launch pair; delta_out: count x n_cand
+int window_batch(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k, double* delta_out)
+{
+    std::vector<WindowBatchEntry> wb;
+    BatchCost bc;
+    int rc = fill_batch(c, first0, count, k, wb, bc);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t n_cand = c->n_orders * c->n_orients;
+    int64_t g_total = bc.g_total; const int max_m = bc.max_m;
+    const double g_bytes = bc.g_bytes, d_bytes = bc.d_bytes, g_flops = bc.g_flops;
     // placement tables (k_part2_window.hip) unless the direct per-candidate kernels are asked for (A/B switch)
     static const bool direct = getenv("HICMI_P2_WINDOW_DIRECT") != nullptr;
     if (!direct) g_total = count * window_table_doubles((int)k);
-    int rc = ensure(c->d_G, c->g_cap, g_total);
+    rc = ensure(c->d_G, c->g_cap, g_total);
     if (rc) return rc;
     rc = ensure(c->d_delta, c->delta_cap, n_cand * count);
     if (rc) return rc;
@@ -1734,33 +1772,18 @@ void short_list(const std::vector<double>& fast, double floor, std::vector<int64
 }  // namespace
 
 namespace {
-// the decision of one window from its deltas; cur_fast (fast score of the current arrangement) is
-// computed on first use when NaN
-int decide_from_delta(hicmi_ctx* c, int64_t first, int64_t k, double total, double floor, double& cur_fast,
-                      const double* delta, int64_t* pick_out, double* best_out, double* pick_fast_out)
+// The decision of one window from its short list: `near` = the candidates within kNearTop of max(best fast, floor) in
+// enumeration order, `near_fast` their fast scores, c0 the current configuration's candidate.  Shared by the host list
+// (decide_from_delta) and the device list (window_near_batch).
+int decide_from_near(hicmi_ctx* c, int64_t first, int64_t k, double total, double floor, double cur_fast, int64_t c0,
+                     const std::vector<int64_t>& near, const std::vector<double>& near_fast, int64_t* pick_out,
+                     double* best_out, double* pick_fast_out)
 {
     const int64_t S = (int64_t)c->h_arr_id.size();
-    const int64_t n_ord = c->n_orders, n_ori = c->n_orients, n_cand = n_ord * n_ori;
+    const int64_t n_ori = c->n_orients;
     *pick_out = -1; *best_out = floor; *pick_fast_out = cur_fast;
-    // candidate index of the current configuration: identity order + the window's current signs
-    int64_t c0 = -1;
-    for (int64_t r = 0; r < n_ori && c0 < 0; r++) {
-        bool same = true;
-        for (int64_t j = 0; j < k; j++) same = same && ((c->h_orients[(size_t)(r * k + j)] != 0) == (c->h_arr_rev[(size_t)(first + j)] != 0));
-        if (same) c0 = r;
-    }
-    if (c0 < 0) return fail(HICMI_EINVAL, "current orientation not in the orientation table");
-    std::vector<double> fast((size_t)n_cand);
-    int rc;
-    if (k == S) for (int64_t i = 0; i < n_cand; i++) fast[(size_t)i] = delta[(size_t)i] / total;
-    else {
-        if (std::isnan(cur_fast)) { rc = hicmi_p2_arrangement_score(c, total, &cur_fast); if (rc) return rc; }
-        for (int64_t i = 0; i < n_cand; i++) fast[(size_t)i] = cur_fast + (delta[(size_t)i] - delta[(size_t)c0]) / total;
-    }
-    *pick_fast_out = cur_fast;
-    std::vector<int64_t> near;
-    short_list(fast, floor, near);
     if (near.empty()) return HICMI_OK;
+    int rc;
     // The candidate that IS the current arrangement is near the top in every window (its fast score is the floor's twin)
     // and its bin order is the same in all of them: its literal score is worked out once per arrangement and total, not
     // through a 7 KB row and cache key per window (138 windows x 1-2 rounds per chromosome at 16k: ~3 ms of a 4.5 ms scan).
@@ -1777,7 +1800,7 @@ int decide_from_delta(hicmi_ctx* c, int64_t first, int64_t k, double total, doub
             }
             lit_c0 = c->cur_lit_value;
             if (near.size() == 1) {                          // nothing but the arrangement itself: decided
-                if (lit_c0 > floor) { *pick_out = c0; *best_out = lit_c0; *pick_fast_out = fast[(size_t)c0]; }
+                if (lit_c0 > floor) { *pick_out = c0; *best_out = lit_c0; *pick_fast_out = near_fast[0]; }
                 return HICMI_OK;
             }
         }
@@ -1802,12 +1825,112 @@ int decide_from_delta(hicmi_ctx* c, int64_t first, int64_t k, double total, doub
     std::vector<double> lit;
     rc = literal_scores(c, rows, total, lit);
     if (rc) return rc;
-    double best = floor; int64_t pick = -1;
-    for (size_t q = 0; q < near.size(); q++) if (lit[q] > best) { best = lit[q]; pick = near[q]; }
+    double best = floor; int64_t pick = -1; size_t pick_q = 0;
+    for (size_t q = 0; q < near.size(); q++) if (lit[q] > best) { best = lit[q]; pick = near[q]; pick_q = q; }
     *pick_out = pick; *best_out = best;
-    if (pick >= 0) *pick_fast_out = fast[(size_t)pick];
+    if (pick >= 0) *pick_fast_out = near_fast[pick_q];
     return HICMI_OK;
 }
+
+// the decision of one window from its deltas; cur_fast (fast score of the current arrangement) is
+// computed on first use when NaN
+int decide_from_delta(hicmi_ctx* c, int64_t first, int64_t k, double total, double floor, double& cur_fast,
+                      const double* delta, int64_t* pick_out, double* best_out, double* pick_fast_out)
+{
+    const int64_t S = (int64_t)c->h_arr_id.size();
+    const int64_t n_ord = c->n_orders, n_ori = c->n_orients, n_cand = n_ord * n_ori;
+    *pick_out = -1; *best_out = floor; *pick_fast_out = cur_fast;
+    const int64_t c0 = window_c0(c, first, k);
+    if (c0 < 0) return fail(HICMI_EINVAL, "current orientation not in the orientation table");
+    std::vector<double> fast((size_t)n_cand);
+    int rc;
+    if (k == S) for (int64_t i = 0; i < n_cand; i++) fast[(size_t)i] = delta[(size_t)i] / total;
+    else {
+        if (std::isnan(cur_fast)) { rc = hicmi_p2_arrangement_score(c, total, &cur_fast); if (rc) return rc; }
+        for (int64_t i = 0; i < n_cand; i++) fast[(size_t)i] = cur_fast + (delta[(size_t)i] - delta[(size_t)c0]) / total;
+    }
+    std::vector<int64_t> near;
+    short_list(fast, floor, near);
+    std::vector<double> near_fast(near.size());
+    for (size_t q = 0; q < near.size(); q++) near_fast[q] = fast[(size_t)near[q]];
+    return decide_from_near(c, first, k, total, floor, cur_fast, c0, near, near_fast, pick_out, best_out, pick_fast_out);
+}
+
+// Short lists of `count` consecutive windows of k scaffolds against the CURRENT arrangement, from the device
+// (k_win_near): per window its near-top candidates in enumeration order and their fast scores, equal to short_list over
+// the downloaded deltas.  All windows share floor and cur_fast (NaN: computed here when k < S).  n_near[w] > cap: the
+// window's list overflowed, near[w] / near_fast[w] are left empty.
+int window_near_batch(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k, double total, double floor, double& cur_fast,
+                      int64_t cap, std::vector<int64_t>& n_near, std::vector<std::vector<int64_t>>& near,
+                      std::vector<std::vector<double>>& near_fast)
+{
+    std::vector<WindowBatchEntry> wb;
+    BatchCost bc;
+    int rc = fill_batch(c, first0, count, k, wb, bc);
+    if (rc) return rc;
+    if (k > 8 || cap < 1 || cap > (1 << 24)) return fail(HICMI_EINVAL, "short lists take k <= 8 and 1 <= cap <= 2^24");
+    const int64_t S = (int64_t)c->h_arr_id.size();
+    for (int64_t wdx = 0; wdx < count; wdx++) {
+        const int64_t c0 = window_c0(c, first0 + wdx, k);
+        if (c0 < 0) return fail(HICMI_EINVAL, "current orientation not in the orientation table");
+        wb[(size_t)wdx].c0 = (int32_t)c0;
+    }
+    if (k != S && std::isnan(cur_fast)) { rc = hicmi_p2_arrangement_score(c, total, &cur_fast); if (rc) return rc; }
+    HIPCHK(hipSetDevice(c->device));
+    const int n_blocks = window_near_blocks((int)c->n_orders);
+    const size_t off_part = ((size_t)count * sizeof(int32_t) + 15) & ~(size_t)15;
+    const size_t off_list = off_part + (size_t)count * (size_t)n_blocks * sizeof(double);
+    const size_t bytes = off_list + (size_t)count * (size_t)cap * sizeof(NearEntry);
+    rc = ensure(c->d_G, c->g_cap, count * window_table_doubles((int)k));
+    if (rc) return rc;
+    rc = ensure(c->d_wnear, c->wnear_cap, (int64_t)bytes);
+    if (rc) return rc;
+    rc = ensure(c->d_wb, c->wb_cap, count);
+    if (rc) return rc;
+    rc = upload(c, c->d_wb, wb.data(), sizeof(WindowBatchEntry) * (size_t)count);
+    if (rc) return rc;
+    int32_t* d_count = reinterpret_cast<int32_t*>(c->d_wnear);
+    NearEntry* d_list = reinterpret_cast<NearEntry*>(c->d_wnear + off_list);
+    {
+        c->launches[F_P2_WINDOW_FLOPS]++; c->bytes[F_P2_WINDOW_FLOPS] += bc.g_flops;
+        Timed t(c, F_P2_WINDOW_G, bc.g_bytes);
+        launch_p2_window_near(c->dM2, c->ld2, c->d_pos2sel, (int)c->n_arr, (int)k, c->d_wb, wb.data(), (int)count, bc.max_m,
+                              c->d_orders, c->d_orients, (int)c->n_orders, (int)c->n_orients, c->d_H, c->d_G, k == S ? 1 : 0,
+                              total, cur_fast, floor, kNearTop, reinterpret_cast<double*>(c->d_wnear + off_part), d_count,
+                              d_list, (int)cap, c->stream);
+    }
+    HIPCHK(hipGetLastError());
+    std::vector<int32_t> cnt((size_t)count);
+    rc = download(c, cnt.data(), d_count, sizeof(int32_t) * (size_t)count);
+    if (rc) return rc;
+    n_near.assign((size_t)count, 0); near.assign((size_t)count, {}); near_fast.assign((size_t)count, {});
+    int64_t widest = 0;
+    for (int64_t w = 0; w < count; w++) {
+        n_near[(size_t)w] = cnt[(size_t)w];
+        if (cnt[(size_t)w] <= cap) widest = std::max<int64_t>(widest, cnt[(size_t)w]);
+    }
+    if (widest == 0) return HICMI_OK;
+    // the first `widest` entries of every window in one strided copy
+    const size_t row = (size_t)widest * sizeof(NearEntry);
+    rc = ensure_pin_down(c, row * (size_t)count);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy2DAsync(c->pin_down, row, d_list, (size_t)cap * sizeof(NearEntry), row, (size_t)count,
+                            hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_stream(c));
+    std::vector<NearEntry> ent;
+    for (int64_t w = 0; w < count; w++) {
+        const int64_t m = cnt[(size_t)w];
+        if (m < 1 || m > cap) continue;
+        const NearEntry* src = reinterpret_cast<const NearEntry*>(c->pin_down + row * (size_t)w);
+        ent.assign(src, src + m);
+        std::sort(ent.begin(), ent.end(), [](const NearEntry& a, const NearEntry& b) { return a.cand < b.cand; });
+        near[(size_t)w].resize((size_t)m); near_fast[(size_t)w].resize((size_t)m);
+        for (int64_t q = 0; q < m; q++) { near[(size_t)w][(size_t)q] = ent[(size_t)q].cand; near_fast[(size_t)w][(size_t)q] = ent[(size_t)q].fast; }
+    }
+    return HICMI_OK;
+}
+
+const int64_t kNearCap = 4096;     // candidates per window list; a window beyond it sends its batch down the delta path
 
 int check_window_call(hicmi_ctx* c, int64_t first, int64_t k)
 {
@@ -1827,10 +1950,37 @@ int hicmi_p2_decide_window(hicmi_ctx* c, int64_t first, int64_t k, double total,
     int rc = check_window_call(c, first, k);
     if (rc) return rc;
     use_total(c, total);
+    if (k >= c->near_min_k) {
+        std::vector<int64_t> n_near; std::vector<std::vector<int64_t>> near; std::vector<std::vector<double>> near_fast;
+        rc = window_near_batch(c, first, 1, k, total, floor, cur_fast, kNearCap, n_near, near, near_fast);
+        if (rc) return rc;
+        if (n_near[0] <= kNearCap)
+            return decide_from_near(c, first, k, total, floor, cur_fast, window_c0(c, first, k), near[0], near_fast[0],
+                                    pick_out, best_out, pick_fast_out);
+    }
     std::vector<double> delta((size_t)(c->n_orders * c->n_orients));
     rc = window_batch(c, first, 1, k, delta.data());
     if (rc) return rc;
     return decide_from_delta(c, first, k, total, floor, cur_fast, delta.data(), pick_out, best_out, pick_fast_out);
+}
+
+int hicmi_p2_window_shortlist(hicmi_ctx* c, int64_t first, int64_t count, int64_t k, double total, double floor,
+                              double cur_fast, int64_t cap, int64_t* n_near_out, int64_t* idx_out, double* fast_out)
+{
+    if (!c || !n_near_out || !idx_out || !fast_out || count < 1) return fail(HICMI_EINVAL, "bad arguments");
+    int rc = check_window_call(c, first, k);
+    if (rc) return rc;
+    std::vector<int64_t> n_near; std::vector<std::vector<int64_t>> near; std::vector<std::vector<double>> near_fast;
+    rc = window_near_batch(c, first, count, k, total, floor, cur_fast, cap, n_near, near, near_fast);
+    if (rc) return rc;
+    for (int64_t w = 0; w < count; w++) {
+        n_near_out[w] = n_near[(size_t)w];
+        for (size_t q = 0; q < near[(size_t)w].size(); q++) {
+            idx_out[w * cap + (int64_t)q] = near[(size_t)w][q];
+            fast_out[w * cap + (int64_t)q] = near_fast[(size_t)w][q];
+        }
+    }
+    return HICMI_OK;
 }
 
 int hicmi_p2_decide_insertion(hicmi_ctx* c, const int32_t* ids, const uint8_t* rev, int64_t S, int32_t new_id,
@@ -2156,16 +2306,31 @@ int hicmi_p2_scan_pass(hicmi_ctx* c, int32_t* ids, uint8_t* rev, int64_t S, int6
     // of a chromosome change little, and a batch costs a launch pair + a synchronisation whatever its size)
     int64_t batch = c->scan_first_batch > 0 ? c->scan_first_batch : 8;
     int64_t n_improved = 0;
+    std::vector<int64_t> n_near; std::vector<std::vector<int64_t>> near; std::vector<std::vector<double>> near_fast;
     while (first <= last) {
         const int64_t count = std::min<int64_t>(batch, last - first + 1);
-        delta.resize((size_t)(count * n_cand));
-        rc = window_batch(c, first, count, k, delta.data());
-        if (rc) return rc;
+        // wide windows: short lists from the device (cur_fast and the floor are the same for every window of the batch,
+        // which ends at the first improvement); a list beyond the cap sends the batch down the delta path
+        bool on_device = k >= c->near_min_k;
+        if (on_device) {
+            rc = window_near_batch(c, first, count, k, total, *best_io, *cur_fast_io, kNearCap, n_near, near, near_fast);
+            if (rc) return rc;
+            for (int64_t w = 0; w < count; w++) on_device = on_device && n_near[(size_t)w] <= kNearCap;
+        }
+        if (!on_device) {
+            delta.resize((size_t)(count * n_cand));
+            rc = window_batch(c, first, count, k, delta.data());
+            if (rc) return rc;
+        }
         bool applied = false;
         for (int64_t wdx = 0; wdx < count && !applied; wdx++) {
             int64_t pick = -1; double best = *best_io, pf = *cur_fast_io;
             double cf = *cur_fast_io;
-            rc = decide_from_delta(c, first + wdx, k, total, *best_io, cf, delta.data() + wdx * n_cand, &pick, &best, &pf);
+            if (on_device)
+                rc = decide_from_near(c, first + wdx, k, total, *best_io, cf, window_c0(c, first + wdx, k), near[(size_t)wdx],
+                                      near_fast[(size_t)wdx], &pick, &best, &pf);
+            else
+                rc = decide_from_delta(c, first + wdx, k, total, *best_io, cf, delta.data() + wdx * n_cand, &pick, &best, &pf);
             if (rc) return rc;
             *cur_fast_io = pf;
             if (pick < 0) continue;

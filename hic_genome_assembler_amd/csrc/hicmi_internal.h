@@ -273,6 +273,7 @@ struct WindowBatchEntry {      // one window of a batch (device array)
     WindowDesc w;
     int32_t p0, m;             // first position and number of bins of the window
     int64_t g_off;             // offset of its m x m table in the batch's G buffer
+    int32_t c0, pad;           // candidate of the current configuration (identity order, current signs): short lists
 };
 void launch_p2_window_batch(const double* M2, int64_t ld2, const int32_t* pos2sel, int n, int k,
                             const WindowBatchEntry* wb, int n_win, int max_m, const int8_t* orders, const uint8_t* orients,
@@ -285,6 +286,17 @@ int64_t window_table_doubles(int k);
 void launch_p2_window_tables(const double* M2, int64_t ld2, const int32_t* pos2sel, int n, int k,
                              const WindowBatchEntry* wb, const WindowBatchEntry* h_wb, int n_win, int max_m, const int8_t* orders, const uint8_t* orients,
                              int n_ord, int n_ori, const double* H, double* tables, double* delta_all, hipStream_t s);
+// The same tables, then only the near-top candidates of every window (the short list of decide_from_delta) without the
+// deltas: pass 1 takes each window's largest finite fast score, pass 2 appends the candidates with fast >= thr to
+// near[w * cap ...] through the counter count[w] (count[w] > cap: the list overflowed and is incomplete).  whole: k == S
+// (fast = delta / total), else fast = cur_fast + (delta - delta[c0]) / total.  part: n_win x window_near_blocks(k, n_ord)
+struct NearEntry { int32_t cand, pad; double fast; };
+int window_near_blocks(int n_ord);
+void launch_p2_window_near(const double* M2, int64_t ld2, const int32_t* pos2sel, int n, int k,
+                           const WindowBatchEntry* wb, const WindowBatchEntry* h_wb, int n_win, int max_m, const int8_t* orders,
+                           const uint8_t* orients, int n_ord, int n_ori, const double* H, double* tables, int whole, double total,
+                           double cur_fast, double floor, double near_top, double* part, int32_t* count, NearEntry* near, int cap,
+                           hipStream_t s);
 
 // Lock-step insertion (k_part2_insert.hip): orderRemainderScaffolds for several chromosomes at once, every
 // decision taken on the device.  One InsStep per (step, chromosome), built by the host in advance.

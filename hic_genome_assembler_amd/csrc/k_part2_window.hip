@@ -384,14 +384,155 @@ __global__ __launch_bounds__(256) void k_win_candidates(int k, const int8_t* __r
     delta_all[(int64_t)blockIdx.y * n_cand + c] = sum;
 }
 
+// ---- short list of the near-top candidates, without the deltas ------------------------------------------------------
+// One wave per (window, order): the before / between sets of an order do not depend on the orientations, so the 2k Q and
+// 4 * k(k-1)/2 P entries a candidate of that order can use (128 doubles at k = 8) are staged in LDS once, and the lanes
+// take the 2^k orientations.  Each candidate adds ΣC, then per position s its Q entry and its P entries for t > s, in
+// k_win_candidates' order: the sum is the same double as its delta, and fast is formed as decide_from_delta forms it.
+// Pass 1 (LIST = false) stores each workgroup's largest finite fast score; pass 2 reduces them to the window's top,
+// thr = top - |top| * near_top with top = max(floor, largest finite fast), recomputes and appends every finite candidate
+// with fast >= thr (integer counter; the host sorts the few indices).  Workgroups run NL_ITERS orders per wave with two
+// barriers per order, all waves the same trip count.
+static constexpr int NL_ITERS = 32;
+static constexpr int NL_ORDERS = 4 * NL_ITERS;          // orders per workgroup
+static inline int64_t stride_of(int k) { return window_table_doubles(k); }
+
+template <bool LIST>
+__global__ __launch_bounds__(256) void k_win_near(int k, const int8_t* __restrict__ orders, const uint8_t* __restrict__ orients,
+                                                  int n_ord, int n_ori, const double* __restrict__ tables, int64_t table_stride,
+                                                  const WindowBatchEntry* __restrict__ wb, int whole, double total, double cur_fast,
+                                                  double floor, double near_top, double* __restrict__ part,
+                                                  int32_t* __restrict__ count, NearEntry* __restrict__ near, int cap)
+{
+    __shared__ double s_stage[4][128];                  // per wave: [2k Q entries (s, r)][4 P entries per pair (s < t)]
+    __shared__ int s_omask[256];                        // orientation table row as a bit mask (bit s: position s reversed)
+    __shared__ int s_ps[28], s_pt[28];                  // pair p -> (s, t), s < t, in the candidates' summation order
+    __shared__ double s_red[4];
+    __shared__ double s_c[3];                           // ΣC, delta of c0, thr
+    __shared__ int s_any;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, win = blockIdx.y;
+    const double* __restrict__ Q = tables + (int64_t)win * table_stride;
+    const double* __restrict__ P = Q + WT_SLICES * wt_q_size(k);
+    const double* __restrict__ C = P + wt_p_size(k);
+    const int npairs = k * (k - 1) / 2, n_stage = 2 * k + 4 * npairs;
+    for (int oi = tid; oi < n_ori; oi += 256) {
+        int m = 0;
+        for (int s = 0; s < k; s++) if (orients[(int64_t)oi * k + s]) m |= 1 << s;
+        s_omask[oi] = m;
+    }
+    if (tid == 0) {
+        int p = 0;
+        for (int s = 0; s < k; s++)
+            for (int t = s + 1; t < k; t++) { s_ps[p] = s; s_pt[p] = t; p++; }
+        double sum = 0.0;
+        for (int j = 0; j < k; j++) sum += C[j];
+        s_c[0] = sum;
+        // c0 = identity order in the window's current orientation (k_win_candidates' sum with ord[s] = s)
+        const uint8_t* __restrict__ ori = orients + (int64_t)wb[win].c0 * k;
+        int before = 0;
+        for (int s = 0; s < k; s++) {
+            const int ra = ori[s] ? 1 : 0;
+            sum += Q[((int64_t)(s * 2 + ra) << k) | before];
+            int between = 0;
+            for (int t = s + 1; t < k; t++) {
+                const int rb = ori[t] ? 1 : 0;
+                sum += P[((((int64_t)s * k + t) * 4 + ra * 2 + rb) << k) | between];
+                between |= 1 << t;
+            }
+            before |= 1 << s;
+        }
+        s_c[1] = sum;
+    }
+    if (LIST) {                                         // the window's largest finite fast score from pass 1's partials
+        double v = -INFINITY;
+        for (int b = tid; b < (int)gridDim.x; b += 256) v = fmax(v, part[(int64_t)win * gridDim.x + b]);
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+        if (lane == 0) s_red[wave] = v;
+        __syncthreads();
+        if (tid == 0) {
+            const double mx = fmax(fmax(s_red[0], s_red[1]), fmax(s_red[2], s_red[3]));
+            s_any = mx > -INFINITY;                     // (only finite values enter the partials)
+            const double top = mx > floor ? mx : floor; // short_list: top starts at floor, takes every larger finite value
+            s_c[2] = top - fabs(top) * near_top;
+        }
+    }
+    __syncthreads();
+    if (LIST && !s_any) return;                         // no finite candidate: empty list (whole workgroup, after the barriers)
+    const double sumC = s_c[0], d0 = s_c[1], thr = LIST ? s_c[2] : 0.0;
+    double vmax = -INFINITY;
+    double* __restrict__ st = s_stage[wave];
+    for (int it = 0; it < NL_ITERS; it++) {
+        const int o = blockIdx.x * NL_ORDERS + it * 4 + wave;
+        const bool live = o < n_ord;                    // uniform per wave
+        if (live) {
+            const int8_t* __restrict__ ord = orders + (int64_t)o * k;
+            int a_[8];
+#pragma unroll
+            for (int t = 0; t < 8; t++) a_[t] = t < k ? ord[t] : 0;
+            for (int e = lane; e < n_stage; e += 64) {
+                double v;
+                if (e < 2 * k) {
+                    const int s = e >> 1, r = e & 1;
+                    int a = 0, before = 0;
+#pragma unroll
+                    for (int t = 0; t < 8; t++) { if (t < s) before |= 1 << a_[t]; if (t == s) a = a_[t]; }
+                    v = Q[((int64_t)(a * 2 + r) << k) | before];
+                } else {
+                    const int p = (e - 2 * k) >> 2, rr = (e - 2 * k) & 3, s = s_ps[p], t = s_pt[p];
+                    int a = 0, b = 0, between = 0;
+#pragma unroll
+                    for (int u = 0; u < 8; u++) {
+                        if (u == s) a = a_[u];
+                        if (u == t) b = a_[u];
+                        if (u > s && u < t) between |= 1 << a_[u];
+                    }
+                    v = P[((((int64_t)a * k + b) * 4 + rr) << k) | between];
+                }
+                st[e] = v;
+            }
+        }
+        __syncthreads();
+        if (live) {
+            for (int oi = lane; oi < n_ori; oi += 64) {
+                const int om = s_omask[oi];
+                double sum = sumC;
+                int p4 = 2 * k;
+                for (int s = 0; s < k; s++) {
+                    const int rs = (om >> s) & 1;
+                    sum += st[2 * s + rs];
+                    for (int t = s + 1; t < k; t++, p4 += 4) sum += st[p4 + rs * 2 + ((om >> t) & 1)];
+                }
+                const double f = whole ? sum / total : cur_fast + (sum - d0) / total;
+                if (!__builtin_isfinite(f)) continue;
+                if (!LIST) vmax = fmax(vmax, f);
+                else if (f >= thr) {
+                    const int slot = atomicAdd(count + win, 1);
+                    if (slot < cap) {
+                        NearEntry& ne = near[(int64_t)win * cap + slot];
+                        ne.cand = o * n_ori + oi; ne.pad = 0; ne.fast = f;
+                    }
+                }
+            }
+        }
+        __syncthreads();                                // the stage is overwritten by the next order
+    }
+    if (!LIST) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) vmax = fmax(vmax, __shfl_xor(vmax, off, 64));
+        if (lane == 0) s_red[wave] = vmax;
+        __syncthreads();
+        if (tid == 0) part[(int64_t)win * gridDim.x + blockIdx.x] = fmax(fmax(s_red[0], s_red[1]), fmax(s_red[2], s_red[3]));
+    }
+}
+
 static std::atomic<int> g_lds_out{0}, g_lds_pairs{0};
 
-// tables: n_win * window_table_doubles(k) doubles of scratch; delta_all: n_win x (n_ord * n_ori)
-void launch_p2_window_tables(const double* M2, int64_t ld2, const int32_t* pos2sel, int n, int k,
-                             const WindowBatchEntry* wb, const WindowBatchEntry* h_wb, int n_win, int max_m, const int8_t* orders, const uint8_t* orients,
-                             int n_ord, int n_ori, const double* H, double* tables, double* delta_all, hipStream_t s)
+// the Q, P and C tables of every window of a batch (tables: n_win * window_table_doubles(k) doubles of scratch)
+static void build_window_tables(const double* M2, int64_t ld2, const int32_t* pos2sel, int n, int k,
+                                const WindowBatchEntry* wb, const WindowBatchEntry* h_wb, int n_win, int max_m,
+                                const double* H, double* tables, hipStream_t s)
 {
-    if (n_win <= 0 || k < 1) return;
     const int64_t stride = window_table_doubles(k);
     const size_t h_all = (((size_t)n * sizeof(double)) + 15) & ~(size_t)15;
     const size_t h_win = (((size_t)max_m * sizeof(double)) + 15) & ~(size_t)15;
@@ -435,9 +576,36 @@ void launch_p2_window_tables(const double* M2, int64_t ld2, const int32_t* pos2s
     } else {
         hipLaunchKernelGGL(k_win_pairs<false>, dim3(k * k, n_win), dim3(256), 0, s, M2, ld2, n, k, wb, H, tables, stride);
     }
+}
+
+// tables: n_win * window_table_doubles(k) doubles of scratch; delta_all: n_win x (n_ord * n_ori)
+void launch_p2_window_tables(const double* M2, int64_t ld2, const int32_t* pos2sel, int n, int k,
+                             const WindowBatchEntry* wb, const WindowBatchEntry* h_wb, int n_win, int max_m, const int8_t* orders, const uint8_t* orients,
+                             int n_ord, int n_ori, const double* H, double* tables, double* delta_all, hipStream_t s)
+{
+    if (n_win <= 0 || k < 1) return;
+    build_window_tables(M2, ld2, pos2sel, n, k, wb, h_wb, n_win, max_m, H, tables, s);
     const int n_cand = n_ord * n_ori;
     hipLaunchKernelGGL(k_win_candidates, dim3((n_cand + 255) / 256, n_win), dim3(256), 0, s, k, orders, orients, n_ori, n_cand,
-                       tables, stride, delta_all);
+                       tables, stride_of(k), delta_all);
+}
+
+int window_near_blocks(int n_ord) { return (n_ord + NL_ORDERS - 1) / NL_ORDERS; }
+
+void launch_p2_window_near(const double* M2, int64_t ld2, const int32_t* pos2sel, int n, int k,
+                           const WindowBatchEntry* wb, const WindowBatchEntry* h_wb, int n_win, int max_m, const int8_t* orders,
+                           const uint8_t* orients, int n_ord, int n_ori, const double* H, double* tables, int whole, double total,
+                           double cur_fast, double floor, double near_top, double* part, int32_t* count, NearEntry* near, int cap,
+                           hipStream_t s)
+{
+    if (n_win <= 0 || k < 1 || k > 8) return;
+    build_window_tables(M2, ld2, pos2sel, n, k, wb, h_wb, n_win, max_m, H, tables, s);
+    const dim3 grid(window_near_blocks(n_ord), n_win);
+    hipLaunchKernelGGL(k_win_near<false>, grid, dim3(256), 0, s, k, orders, orients, n_ord, n_ori, (const double*)tables,
+                       stride_of(k), wb, whole, total, cur_fast, floor, near_top, part, count, near, cap);
+    (void)hipMemsetAsync(count, 0, sizeof(int32_t) * (size_t)n_win, s);
+    hipLaunchKernelGGL(k_win_near<true>, grid, dim3(256), 0, s, k, orders, orients, n_ord, n_ori, (const double*)tables,
+                       stride_of(k), wb, whole, total, cur_fast, floor, near_top, part, count, near, cap);
 }
 
 }  // namespace hicmi

@@ -257,6 +257,19 @@ int hicmi_p2_score_window(hicmi_ctx *ctx, int64_t first, int64_t k, double *delt
  * pick_fast_out = fast score of the arrangement that is current after applying the pick. */
 int hicmi_p2_decide_window(hicmi_ctx *ctx, int64_t first, int64_t k, double total, double floor, double cur_fast,
                            int64_t *pick_out, double *best_out, double *pick_fast_out);
+/* The short lists behind bruteForceBestScore / scanOrdering's window steps (OG:457-466, 519-538), taken on the device
+ * without downloading the deltas: for the `count` consecutive windows first, first+1, ... of k <= 8 scaffolds against
+ * the current arrangement and tables (like hicmi_p2_score_window), the candidates c whose fast score
+ *     fast[c] = delta[c] / total                                    (k == S)
+ *     fast[c] = cur_fast + (delta[c] - delta[c0]) / total           (otherwise; c0 = identity order, current signs;
+ *                                                                     cur_fast NaN: computed here)
+ * is finite and >= top - |top| * 1e-9, top = max(floor, largest finite fast), in ascending candidate order, with their
+ * fast scores: equal bit for bit to that rule applied to hicmi_p2_score_window's deltas.  Window w's list is
+ * idx_out[w * cap ...] / fast_out[w * cap ...] with n_near_out[w] entries; n_near_out[w] > cap reports an overflow (that
+ * window's list is not returned).  Windows of at least HICMI_P2_DEVICE_DECIDE scaffolds (default 7, "off": none) are
+ * decided through these lists in hicmi_p2_decide_window and the scan calls. */
+int hicmi_p2_window_shortlist(hicmi_ctx *ctx, int64_t first, int64_t count, int64_t k, double total, double floor,
+                              double cur_fast, int64_t cap, int64_t *n_near_out, int64_t *idx_out, double *fast_out);
 /* checkAllScores (OG:332-372) for scaffold new_id against the arrangement (ids, rev): computes the
  * literal total of "arrangement + new scaffold last" (OG:484-487, 343), scores the 2(S+1) candidates in
  * the reference's enumeration order (orientation tested first alternates with the gap, starting from
