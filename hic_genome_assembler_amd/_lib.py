@@ -80,6 +80,8 @@ SIGNATURES = {
     "hicmi_plot_percentiles": (ctypes.c_int, [_vp, ctypes.c_int, _vp, c_i64, _vp, c_i64, _vp]),
     "hicmi_plot_downsample": (ctypes.c_int, [_vp, ctypes.c_int, _vp, c_i64, c_i64, _vp]),
     "hicmi_p2_insert_all_multi": (ctypes.c_int, [c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hicmi_p2_support": (ctypes.c_int, [_vp, _vp, _vp, c_i64, c_dbl, _vp, _vp]),
+    "hicmi_p2_support_multi": (ctypes.c_int, [c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hicmi_p2_scan_pass": (ctypes.c_int, [_vp, _vp, _vp, c_i64, c_i64, c_dbl, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl),
                                           ctypes.POINTER(ctypes.c_int32)]),
     "hicmi_p2_scan_all": (ctypes.c_int, [_vp, _vp, _vp, c_i64, c_i64, c_dbl, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl),
@@ -546,6 +548,41 @@ class Context:
         for ctx, _i, _r, _n in jobs:
             ctx._arr_sig = None
         return [(a_l[j], b_l[j], best[j]) for j in range(n)]
+
+    def p2_support(self, ids, rev, total: float):
+        """Placement support of one chromosome (hicmi_p2_support): (S x S x 2 table of closed-form scores,
+        S x 2 int32 of [first maximum 2 g + r among the candidates that differ from the arrangement or -1,
+        how many of them lie within 1e-9 of it])."""
+        a = np.ascontiguousarray(ids, dtype=np.int32)
+        b = np.ascontiguousarray(rev, dtype=np.uint8)
+        S = len(a)
+        table, best = np.empty((S, S, 2), np.float64), np.empty((S, 2), np.int32)
+        _check(self._lib.hicmi_p2_support(self._h, _ptr(a), _ptr(b), S, float(total), _ptr(table), _ptr(best)))
+        self._arr_sig = a.tobytes() + b.tobytes()
+        self._arr_len = S
+        return table, best
+
+    @staticmethod
+    def p2_support_multi(jobs):
+        """p2_support for several chromosomes in one pair of launches (hicmi_p2_support_multi).
+        jobs: [(context, ids, rev, total)], one distinct context per chromosome; returns [(table, best)]."""
+        n = len(jobs)
+        if n == 0:
+            return []
+        lib = jobs[0][0]._lib
+        a_l = [np.ascontiguousarray(j[1], dtype=np.int32) for j in jobs]
+        b_l = [np.ascontiguousarray(j[2], dtype=np.uint8) for j in jobs]
+        t_l = [np.empty((len(a), len(a), 2), np.float64) for a in a_l]
+        o_l = [np.empty((len(a), 2), np.int32) for a in a_l]
+        handles = (ctypes.c_void_p * n)(*[j[0]._h for j in jobs])
+        pa, pb, pt, po = ((ctypes.c_void_p * n)(*[x.ctypes.data for x in arrs]) for arrs in (a_l, b_l, t_l, o_l))
+        sizes = (c_i64 * n)(*[len(a) for a in a_l])
+        totals = (c_dbl * n)(*[float(j[3]) for j in jobs])
+        _check(lib.hicmi_p2_support_multi(n, handles, pa, pb, sizes, totals, pt, po))
+        for (ctx, _i, _r, _t), a, b in zip(jobs, a_l, b_l):
+            ctx._arr_sig = a.tobytes() + b.tobytes()
+            ctx._arr_len = len(a)
+        return list(zip(t_l, o_l))
 
     def p2_scan_pass(self, ids, rev, k, total, best, cur_fast):
         """One round of scanOrdering; returns (ids, rev, best, cur_fast, improved)."""

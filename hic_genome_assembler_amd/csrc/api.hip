@@ -132,6 +132,7 @@ struct hicmi_ctx {
     double* d_ins_partial = nullptr; int64_t ins_partial_cap = 0;
     unsigned char* d_ins_blob = nullptr; int64_t ins_blob_cap = 0;   // per job: [InsState][InsLog x steps]
     InsStep* d_ins_steps = nullptr; int64_t ins_steps_cap = 0;       // [step][job] records of a lock-step queue
+    SupRec* d_sup_recs = nullptr; int64_t sup_recs_cap = 0;          // hicmi_p2_support_multi: (chromosome, left-out scaffold) records
     // HMM boundary finder (k_hmm.hip): resident observation matrices, one per slot (T x ld, columns [0, D) in use);
     // the selected slot's view is mirrored in d_hx / hmm_T / hmm_ld / hmm_D for the single-problem entry points.  The
     // work areas are sized for the largest slot built
@@ -371,7 +372,7 @@ int hicmi_destroy(hicmi_ctx* c)
     free_dev(c->d_pos2sel); free_dev(c->d_orders); free_dev(c->d_orients);
     free_dev(c->d_G); free_dev(c->d_delta); free_dev(c->d_wb); free_dev(c->d_wnear);
     free_dev(c->d_arr_packed2); free_dev(c->d_pos2sel2); free_dev(c->d_ins_T); free_dev(c->d_ins_partial);
-    free_dev(c->d_ins_blob); free_dev(c->d_ins_steps);
+    free_dev(c->d_ins_blob); free_dev(c->d_ins_steps); free_dev(c->d_sup_recs);
     free_dev(c->d_plot_order); free_dev(c->d_plot_work); free_dev(c->d_plot_img);
     for (auto& sl : c->hslot) free_dev(sl.d_x);
     free_dev(c->d_hmulti); free_dev(c->d_horder); free_dev(c->d_hwork); free_dev(c->d_hlab); free_dev(c->d_hbt);
@@ -2280,6 +2281,98 @@ int hicmi_p2_insert_all_multi(int64_t n_jobs, hicmi_ctx* const* ctxs, int32_t* c
     if (rc) return rc;
     for (int64_t j = 0; j < n_jobs; j++) best_out[j] = jobs[(size_t)j].best;
     return HICMI_OK;
+}
+
+// Placement support (k_part2_support.hip): every scaffold of every job's arrangement taken out and scored at every gap
+// in both orientations, one record per (job, scaffold), one pair of launches and one download for all jobs.
+int hicmi_p2_support_multi(int64_t n_jobs, hicmi_ctx* const* ctxs, const int32_t* const* ids, const uint8_t* const* rev,
+                           const int64_t* S, const double* totals, double* const* scores_out, int32_t* const* best_out)
+{
+    if (n_jobs < 1 || !ctxs || !ids || !rev || !S || !totals || !scores_out || !best_out) return fail(HICMI_EINVAL, "bad arguments");
+    hicmi_ctx* lead = ctxs[0];
+    const int NB = SUP_BASE_SLABS;
+    std::vector<size_t> out_off((size_t)n_jobs, 0);
+    std::vector<uint8_t> run((size_t)n_jobs, 0);
+    size_t blob_bytes = 0;
+    int64_t n_rec = 0;
+    int max_S = 1, max_n = 1;
+    for (int64_t j = 0; j < n_jobs; j++) {
+        hicmi_ctx* c = ctxs[j];
+        if (!c || !lead || c->device != lead->device) return fail(HICMI_EINVAL, "contexts must share one device");
+        for (int64_t q = 0; q < j; q++) if (ctxs[q] == c) return fail(HICMI_EINVAL, "one context per chromosome");
+        if (!ids[j] || !rev[j] || !scores_out[j] || !best_out[j] || S[j] < 1) return fail(HICMI_EINVAL, "bad arguments");
+        if (S[j] > SUP_MAX_S) return fail(HICMI_EUNSUPPORTED, "more than %d scaffolds in one chromosome", SUP_MAX_S);
+        int rc = hicmi_p2_set_arrangement(c, ids[j], rev[j], S[j]);
+        if (rc) return rc;
+        if (c != lead) HIPCHK(sync_stream(c));             // the launches run on lead's stream
+        if (c->n_arr * (int64_t)sizeof(int32_t) > 160 * 1024) return fail(HICMI_EUNSUPPORTED, "candidate longer than 40960 bins");
+        // fewer than 2 bins, or no contacts: every score is 0.0 and there is no candidate
+        for (int64_t i = 0; i < 2 * S[j] * S[j]; i++) scores_out[j][i] = 0.0;
+        for (int64_t i = 0; i < S[j]; i++) { best_out[j][2 * i] = -1; best_out[j][2 * i + 1] = 0; }
+        if (c->n_arr < 2 || !(totals[j] > 0.0)) continue;
+        run[(size_t)j] = 1;
+        rc = ensure(c->d_ins_partial, c->ins_partial_cap, S[j] * (NB + c->n_arr + 2 * S[j]));
+        if (rc) return rc;
+        out_off[(size_t)j] = blob_bytes;
+        blob_bytes += ((size_t)(2 * S[j] * S[j]) * sizeof(double) + (size_t)(2 * S[j]) * sizeof(int32_t) + 15) & ~(size_t)15;
+        n_rec += S[j];
+        max_S = std::max(max_S, (int)S[j]);
+        max_n = std::max(max_n, (int)c->n_arr);
+    }
+    if (n_rec == 0) return HICMI_OK;
+    HIPCHK(hipSetDevice(lead->device));
+    int rc = ensure(lead->d_ins_blob, lead->ins_blob_cap, (int64_t)blob_bytes);
+    if (rc) return rc;
+    rc = ensure(lead->d_sup_recs, lead->sup_recs_cap, n_rec);
+    if (rc) return rc;
+    std::vector<SupRec> recs;
+    recs.reserve((size_t)n_rec);
+    double algo = 0.0;
+    for (int64_t j = 0; j < n_jobs; j++) {
+        if (!run[(size_t)j]) continue;
+        hicmi_ctx* c = ctxs[j];
+        const int64_t Sj = S[j], n = c->n_arr;
+        double* d_scores = reinterpret_cast<double*>(lead->d_ins_blob + out_off[(size_t)j]);
+        int32_t* d_best = reinterpret_cast<int32_t*>(d_scores + 2 * Sj * Sj);
+        for (int64_t k = 0; k < Sj; k++) {
+            SupRec d;
+            memset(&d, 0, sizeof(d));
+            const int32_t sid = ids[j][k];
+            d.M2 = c->dM2; d.H = c->d_H; d.ld2 = c->ld2;
+            d.pos = c->d_pos2sel; d.arr_pos = c->d_arr_packed + Sj;
+            d.partial = c->d_ins_partial + k * (NB + n + 2 * Sj);
+            d.scores = d_scores + 2 * Sj * k; d.best = d_best + 2 * k;
+            d.total = totals[j];
+            d.n = (int32_t)n; d.S = (int32_t)Sj; d.j = (int32_t)k;
+            d.start = c->h_scaf_start[(size_t)sid]; d.L = c->h_scaf_len[(size_t)sid]; d.cur_rev = rev[j][k] ? 1 : 0;
+            recs.push_back(d);
+            const double nn = (double)(n - d.L);
+            algo += 8.0 * (0.5 * nn * nn + nn * nn + 2.0 * (double)Sj * (double)d.L * nn);
+        }
+    }
+    rc = upload(lead, lead->d_sup_recs, recs.data(), sizeof(SupRec) * recs.size());
+    if (rc) return rc;
+    {
+        Timed timed(lead, F_P2_INSERT, algo);
+        launch_sup(lead->d_sup_recs, (int)n_rec, max_S, max_n, kNearTop, lead->stream);
+    }
+    HIPCHK(hipGetLastError());
+    std::vector<unsigned char> blob(blob_bytes);
+    rc = download(lead, blob.data(), lead->d_ins_blob, blob_bytes);
+    if (rc) return rc;
+    for (int64_t j = 0; j < n_jobs; j++) {
+        if (!run[(size_t)j]) continue;
+        const size_t nd = (size_t)(2 * S[j] * S[j]);
+        memcpy(scores_out[j], blob.data() + out_off[(size_t)j], nd * sizeof(double));
+        memcpy(best_out[j], blob.data() + out_off[(size_t)j] + nd * sizeof(double), (size_t)(2 * S[j]) * sizeof(int32_t));
+    }
+    return HICMI_OK;
+}
+
+int hicmi_p2_support(hicmi_ctx* c, const int32_t* ids, const uint8_t* rev, int64_t S, double total, double* scores_out,
+                     int32_t* best_out)
+{
+    return hicmi_p2_support_multi(1, &c, &ids, &rev, &S, &total, &scores_out, &best_out);
 }
 
 int hicmi_p2_scan_pass(hicmi_ctx* c, int32_t* ids, uint8_t* rev, int64_t S, int64_t k, double total, double* best_io,

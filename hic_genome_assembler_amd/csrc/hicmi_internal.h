@@ -298,6 +298,40 @@ void launch_p2_window_near(const double* M2, int64_t ld2, const int32_t* pos2sel
                            double cur_fast, double floor, double near_top, double* part, int32_t* count, NearEntry* near, int cap,
                            hipStream_t s);
 
+// ---- block sums and the closed-form BASE term, shared by k_part2_search.hip and k_part2_support.hip
+__device__ __forceinline__ double wave_sum_s(double v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__device__ __forceinline__ double block_sum_256(double v, double* s_w)
+{
+    v = wave_sum_s(v);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+}
+
+// slab `blk` of `n_blk`: rows blk*4 + wave, stepping by 4*n_blk (256-lane workgroup); p: the arrangement in LDS
+__device__ __forceinline__ void base_partial_body(const double* __restrict__ M2, int64_t ld2, const int32_t* p, int n_arr,
+                                                  const double* __restrict__ H, int n_tot, int blk, int n_blk,
+                                                  double* __restrict__ out)
+{
+    __shared__ double s_w[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double hn = H[n_tot - 1];
+    double acc = 0.0;
+    for (int a = blk * 4 + wave; a < n_arr - 1; a += n_blk * 4) {
+        const double* __restrict__ row = M2 + (int64_t)p[a] * ld2;
+#pragma unroll 4
+        for (int b = a + 1 + lane; b < n_arr; b += 64) acc += row[p[b]] * (hn - H[b - a - 1]);
+    }
+    double sum = block_sum_256(acc, s_w);
+    if (threadIdx.x == 0) out[0] = sum;
+}
+
 // Lock-step insertion (k_part2_insert.hip): orderRemainderScaffolds for several chromosomes at once, every
 // decision taken on the device.  One InsStep per (step, chromosome), built by the host in advance.
 static constexpr int INS_MAXC = 8;       // candidates re-scored literally per step; more -> the host decides that step
@@ -326,6 +360,22 @@ void launch_insb_shortlist(const InsStep* steps, int n_chrom, int max_S, int max
 void launch_insb_diag_cand(const InsStep* steps, int n_chrom, int max_n_used, hipStream_t s);
 void launch_insb_cost(const InsStep* steps, int n_chrom, int max_n_used, hipStream_t s);
 void launch_insb_apply(const InsStep* steps, int n_chrom, int max_n_used, hipStream_t s);
+
+// k_part2_support.hip: placement support (hicmi_p2_support_multi).  One record per (chromosome, left-out scaffold j):
+// the insertion step "A without j, j put back", read through A's own arrays.
+static constexpr int SUP_BASE_SLABS = 64;     // partial sums of a record's BASE term
+static constexpr int SUP_MAX_S = 4096;        // scaffolds per chromosome (the table has 2 S^2 entries)
+struct SupRec {
+    const double* M2; const double* H; int64_t ld2;
+    const int32_t* pos;                       // A as bin order, n entries
+    const int32_t* arr_pos;                   // prefix positions of A's S scaffolds, S + 1 entries
+    double* partial;                          // [SUP_BASE_SLABS BASE slabs][n - L row values][2 S CROSS terms]
+    double* scores;                           // out: score(j, g, r) at [2 g + r]
+    int32_t* best;                            // out: first closed-form maximum among the counted candidates (-1: none), how many within near_top
+    double total;
+    int32_t n, S, j, start, L, cur_rev;       // start, L: j's range of the selection; cur_rev: its orientation in A
+};
+void launch_sup(const SupRec* recs, int n_rec, int max_S, int max_n, double near_top, hipStream_t s);
 
 // k_plot.hip
 void launch_plot_select(const double* C, int64_t ldc, const double* np_sum, const double* seq_sum, int kind,

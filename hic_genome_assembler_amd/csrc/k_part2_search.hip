@@ -24,21 +24,6 @@
 
 namespace hicmi {
 
-__device__ __forceinline__ double wave_sum_s(double v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ double block_sum_256(double v, double* s_w)
-{
-    v = wave_sum_s(v);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
-}
-
 __device__ __forceinline__ double block_sum_1024(double v, double* s_w)      // s_w: 16 doubles
 {
     v = wave_sum_s(v);
@@ -82,24 +67,7 @@ void launch_arr_materialize(const int32_t* packed, int S, const int32_t* scaf_st
 }
 
 // ---- closed-form score of the arrangement itself --------------------------------------------------
-// slab `blk` of `n_blk`: rows blk*4 + wave, stepping by 4*n_blk (256-lane workgroup); p: the arrangement in LDS
-__device__ __forceinline__ void base_partial_body(const double* __restrict__ M2, int64_t ld2, const int32_t* p, int n_arr,
-                                                  const double* __restrict__ H, int n_tot, int blk, int n_blk,
-                                                  double* __restrict__ out)
-{
-    __shared__ double s_w[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const double hn = H[n_tot - 1];
-    double acc = 0.0;
-    for (int a = blk * 4 + wave; a < n_arr - 1; a += n_blk * 4) {
-        const double* __restrict__ row = M2 + (int64_t)p[a] * ld2;
-#pragma unroll 4
-        for (int b = a + 1 + lane; b < n_arr; b += 64) acc += row[p[b]] * (hn - H[b - a - 1]);
-    }
-    double sum = block_sum_256(acc, s_w);
-    if (threadIdx.x == 0) out[0] = sum;
-}
-
+// base_partial_body (hicmi_internal.h): slab `blk` of `n_blk` of BASE for an arrangement staged in LDS
 __global__ __launch_bounds__(256) void k_p2_base_partial(const double* __restrict__ M2, int64_t ld2,
                                                          const int32_t* __restrict__ pos2sel, int n_arr,
                                                          const double* __restrict__ H, int n_tot,

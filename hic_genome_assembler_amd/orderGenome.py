@@ -860,6 +860,253 @@ def writeBinIDsOrderingToFile(scaffoldList, outFile, rows=None):
     print("BinIDs written to file " + str(sum(r[1] for r in rows)))
 
 
+# ---- placement support of a finished ordering -----------------------------------------
+SUPPORT_DIRECT_BYTES = 64 << 20        # HICMI_P2_SUPPORT_DIRECT=1: bytes of materialised candidate rows resident at a time
+
+
+def scaffoldsFromOrderFile(chromList, chromosomeOrderFile):
+    """A chromosomeOrderFile (this project's or the reference's) back as lists of Scaffold objects: chromosome i of the
+    order file takes its bins from group i of ``chromList`` (readChromsFromFile of the group file)."""
+    groups, cur = [], None
+    with open(chromosomeOrderFile) as fh:
+        for line in fh:
+            line = line.rstrip("\r\n")
+            if not line:
+                continue
+            if line[0] == "#":
+                cur = []
+                groups.append(cur)
+            else:
+                if cur is None:
+                    raise ValueError(chromosomeOrderFile + ": a scaffold line before the first chromosome header")
+                cols = line.split("\t")
+                if len(cols) < 2 or cols[1] not in ("+", "-"):
+                    raise ValueError(chromosomeOrderFile + ": expected 'scaffold<TAB>+/-', found " + repr(line))
+                cur.append((cols[0], cols[1]))
+    if len(groups) != len(chromList):
+        raise ValueError("%s lists %d chromosomes, the group file %d" % (chromosomeOrderFile, len(groups), len(chromList)))
+    out = []
+    for i, (group, chrom) in enumerate(zip(groups, chromList)):
+        bins_of = {}
+        for bin_id, name in chrom:
+            bins_of.setdefault(name, []).append(bin_id)
+        if sorted(bins_of) != sorted(name for name, _o in group):
+            raise ValueError("chromosome %d: the order file and the group file do not list the same scaffolds" % (i + 1))
+        scaffs = []
+        for name, orient in group:
+            sc = Scaffold(name, sorted(bins_of[name]), "+")
+            if orient == "-":
+                sc.flipOrientation()
+            scaffs.append(sc)
+        out.append(scaffs)
+    return out
+
+
+def _support_row(layout, ids, rev, j, g, r):
+    """Bin order (selection indices) of "the arrangement without scaffold j, j put back at gap g in orientation r"."""
+    oi = [int(v) for k, v in enumerate(ids) if k != j]
+    orr = [int(v) for k, v in enumerate(rev) if k != j]
+    oi.insert(g, int(ids[j]))
+    orr.insert(g, int(r))
+    return layout.node_row(oi, orr)
+
+
+def support_counts(lengths, rev):
+    """(S, S, 2) mask of the candidates that compete for a scaffold's best move: those whose bin order differs from the
+    arrangement's - not (g = j, r = its orientation) - and, of a one-bin scaffold, only '+' away from its own gap ('-'
+    is the same bin order and comes second in enumeration order, so it can never be a strict maximum).  A chromosome
+    of one scaffold has no other placement (its flip is the whole chromosome read backwards)."""
+    S = len(lengths)
+    m = np.ones((S, S, 2), dtype=bool)
+    if S == 1:
+        m[:] = False
+    for j in range(S):
+        if lengths[j] == 1:
+            m[j, :, 1] = False
+            m[j, j, :] = False
+        else:
+            m[j, j, int(rev[j])] = False
+    return m
+
+
+def support_summary(table, lengths, rev):
+    """What hicmi_p2_support returns as ``best`` from a table of scores: per scaffold [2 g + r of the first maximum over
+    support_counts, or -1; how many counted candidates lie within NEAR_TOP of it]."""
+    S = len(lengths)
+    counts = support_counts(lengths, rev).reshape(S, 2 * S)
+    flat = np.asarray(table, dtype=np.float64).reshape(S, 2 * S)
+    out = np.zeros((S, 2), np.int32)
+    for j in range(S):
+        ok = counts[j] & np.isfinite(flat[j])
+        if not ok.any():
+            out[j] = (-1, 0)
+            continue
+        v = np.where(ok, flat[j], -np.inf)
+        top = float(v.max())
+        out[j] = (int(np.argmax(v)), int(np.count_nonzero(v >= top - abs(top) * NEAR_TOP)))
+    return out
+
+
+def _support_direct(layout, ids, rev, total):
+    """A/B path (HICMI_P2_SUPPORT_DIRECT=1): the same table from hicmi_p2_score on every candidate's materialised bin
+    order, at most SUPPORT_DIRECT_BYTES of rows at a time."""
+    S, n = len(ids), layout.n
+    table = np.zeros((S, S, 2))
+    lengths = [layout.length[int(i)] for i in ids]
+    if n >= 2 and total > 0:
+        flat = table.reshape(-1)
+        per = max(1, SUPPORT_DIRECT_BYTES // (4 * n))
+        for c0 in range(0, 2 * S * S, per):
+            cand = range(c0, min(c0 + per, 2 * S * S))
+            rows = np.stack([_support_row(layout, ids, rev, c // (2 * S), (c // 2) % S, c % 2) for c in cand])
+            flat[c0:c0 + len(rows)] = layout.ctx.p2_score(rows, total)
+        return table, support_summary(table, lengths, rev)
+    return table, np.tile(np.array([-1, 0], np.int32), (S, 1))
+
+
+def _literal_rows(layout, rows, total):
+    """hicmi_p2_score_exact of explicit bin orders, at most SUPPORT_DIRECT_BYTES of rows per call."""
+    per = max(1, SUPPORT_DIRECT_BYTES // (4 * max(1, layout.n)))
+    out = [layout.ctx.p2_score_exact(np.stack(rows[i:i + per]).astype(np.int32), total) for i in range(0, len(rows), per)]
+    return np.concatenate(out) if out else np.zeros(0)
+
+
+def _support_one(layout, ids, rev, total, table, best):
+    """One chromosome's result from its table: score0, flip / best columns and verdicts.  The table ranks; a scaffold
+    whose best move has rivals within NEAR_TOP is decided on their literal scores (hicmi_p2_score_exact), first strict
+    maximum.  The reported deltas are literal scores too - of the arrangement, each in-place flip and each best move, one
+    call - so that they do not depend on how the table was computed."""
+    S = len(ids)
+    lengths = [layout.length[int(i)] for i in ids]
+    live = layout.n >= 2 and total > 0
+    counts = support_counts(lengths, rev).reshape(S, 2 * S)
+    flat = table.reshape(S, 2 * S)
+    picks = []
+    for j in range(S):
+        pick, n_near = (int(best[j][0]), int(best[j][1])) if live else (-1, 0)
+        if pick >= 0 and n_near > 1:
+            top = float(flat[j][pick])
+            near = np.flatnonzero(counts[j] & np.isfinite(flat[j]) & (flat[j] >= top - abs(top) * NEAR_TOP))
+            lit = _literal_rows(layout, [_support_row(layout, ids, rev, j, int(c) // 2, int(c) % 2) for c in near], total)
+            top_lit = -math.inf
+            for c, v in zip(near, lit):                   # first strict maximum in enumeration order
+                if v > top_lit:
+                    pick, top_lit = int(c), float(v)
+        picks.append(pick)
+    flips = [j for j in range(S) if live and lengths[j] > 1 and S > 1]
+    moves = [j for j in range(S) if picks[j] >= 0]
+    lit = _literal_rows(layout, [layout.node_row(ids, rev)]
+                        + [_support_row(layout, ids, rev, j, j, 1 - int(rev[j])) for j in flips]
+                        + [_support_row(layout, ids, rev, j, picks[j] // 2, picks[j] % 2) for j in moves], total) if live else [0.0]
+    score0 = float(lit[0])
+    # a one-bin scaffold reads the same both ways, and a lone scaffold's flip is the chromosome read backwards: 0.0
+    flip_of = dict(zip(flips, (float(v) - score0 for v in lit[1:1 + len(flips)])))
+    move_of = dict(zip(moves, (float(v) - score0 for v in lit[1 + len(flips):])))
+    rows = []
+    for j in range(S):
+        flip, delta = flip_of.get(j, 0.0), move_of.get(j)
+        gap, orient = (None, None) if delta is None else (picks[j] // 2, "-" if picks[j] % 2 else "+")
+        verdict = "improvable" if delta is not None and delta > 0 else ("orientation_open" if flip == 0 else "supported")
+        rows.append({"bins": lengths[j], "flip_delta": flip, "best_gap": gap, "best_orientation": orient,
+                     "best_delta": delta, "verdict": verdict})
+    return {"score0": score0, "total": total, "table": table, "rows": rows}
+
+
+def placementSupport(matrix: GenomeMatrix, orderedChromosomes, binList, chromList=None):
+    """How well the map supports a finished ordering: every scaffold of every chromosome is taken out of its
+    chromosome's arrangement and put back at every gap in both orientations (include/hicmi.h,
+    hicmi_p2_support).  Returns one dict per chromosome: 'score0' (literal objective of the arrangement), 'total',
+    'table' (S x S x 2 scores: left-out scaffold, gap of the arrangement without it, '+'/'-'), 'names', 'orientations'
+    and 'rows' (per scaffold in arrangement order: bins, flip_delta, best_gap, best_orientation, best_delta, verdict).
+
+    All scores of a chromosome are under ONE total, that of its selection in layout order with every scaffold '+', the
+    layout being orderChromosome's: ``chromList[i]`` (the group file's rows) fixes it; without it the scaffolds are
+    taken largest first in arrangement order.  On the device all chromosomes go through one hicmi_p2_support_multi
+    call, one context each; HICMI_P2_SUPPORT_DIRECT=1 scores materialised candidates with hicmi_p2_score instead."""
+    ctx = matrix.ctx
+    matrix.bin_index(binList)
+    direct = os.environ.get("HICMI_P2_SUPPORT_DIRECT", "") not in ("", "0")
+    multi = not direct and SCORE_HOOK is None and hasattr(ctx, "workers") and hasattr(ctx, "p2_support_multi")
+    lanes = [matrix]
+    if multi and len(orderedChromosomes) > 1:
+        lanes += [GenomeMatrix(x) for x in ctx.workers(len(orderedChromosomes) - 1)]
+        for m in lanes[1:]:
+            m._bin_index, m._bin_index_src = matrix._bin_index, matrix._bin_index_src
+    out = []
+    for c0 in range(0, len(orderedChromosomes), len(lanes)):
+        jobs = []
+        for lane, k in zip(lanes, range(c0, min(c0 + len(lanes), len(orderedChromosomes)))):
+            group = orderedChromosomes[k]
+            if chromList is not None:
+                by_name = {s.name: s for s in group}
+                order = [by_name[s.name] for s in _layoutScaffolds(chromList[k])]
+            else:
+                order = sorted(group, key=lambda s: len(s.binList), reverse=True)
+            layout = lane.chrom = ChromosomeLayout(lane, order, binList)
+            S0 = len(layout.start)
+            total = 0.0
+            if layout.n >= 2:
+                layout.ctx.p2_set_arrangement(np.arange(S0, dtype=np.int32), np.zeros(S0, np.uint8))
+                total = layout.ctx.p2_arrangement_total()
+            ids, rev = layout.describe(group)
+            jobs.append((layout, ids, rev, total, group))
+        if direct:
+            tables = [_support_direct(layout, ids, rev, total) for layout, ids, rev, total, _g in jobs]
+        elif multi:
+            tables = ctx.p2_support_multi([(layout.ctx, ids, rev, total) for layout, ids, rev, total, _g in jobs])
+        else:
+            tables = [layout.ctx.p2_support(ids, rev, total) for layout, ids, rev, total, _g in jobs]
+        for (layout, ids, rev, total, group), (table, best) in zip(jobs, tables):
+            res = _support_one(layout, ids, rev, total, np.asarray(table), best)
+            res["names"] = [s.name for s in group]
+            res["orientations"] = [s.orientation for s in group]
+            out.append(res)
+    return out
+
+
+def _layoutScaffolds(nodeList):
+    """initiateBinsAndScaffolds' scaffold list (the layout order of orderChromosome) without its printed line."""
+    bins_of = {}
+    for bin_id, name in nodeList:
+        bins_of.setdefault(name, []).append(bin_id)
+    return sorted((Scaffold(name, sorted(b), "+") for name, b in bins_of.items()), key=lambda s: len(s.binList),
+                  reverse=True)
+
+
+def _support_text(v):
+    return "NA" if v is None else (repr(v) if isinstance(v, float) else str(v))
+
+
+def placementSupportText(results):
+    """The report: per chromosome ``### Chromosome grouping i ### score0``, then one tab-separated line per scaffold in
+    arrangement order: scaffold, orientation, bins, flip_delta, best_gap, best_orientation, best_delta, verdict.  Floats
+    are written with repr; a chromosome of one scaffold has no other placement: NA."""
+    text = []
+    for k, res in enumerate(results):
+        text.append("### Chromosome grouping " + str(k + 1) + " ### " + repr(res["score0"]) + "\n")
+        for name, orient, row in zip(res["names"], res["orientations"], res["rows"]):
+            text.append("\t".join([name, orient] + [_support_text(row[key]) for key in
+                                                    ("bins", "flip_delta", "best_gap", "best_orientation", "best_delta",
+                                                     "verdict")]) + "\n")
+    return "".join(text)
+
+
+def writePlacementSupportToFile(results, outFile, fullDir=None):
+    """placementSupportText to ``outFile``; ``fullDir``: also each chromosome's S x 2S table as ``Chr_i.support.tsv``
+    (row = left-out scaffold, columns = gap0+, gap0-, gap1+, ...)."""
+    with open(outFile, "w") as fh:
+        fh.write(placementSupportText(results))
+    if fullDir:
+        os.makedirs(fullDir, exist_ok=True)
+        for k, res in enumerate(results):
+            S = len(res["names"])
+            with open(os.path.join(fullDir, "Chr_%d.support.tsv" % (k + 1)), "w") as fh:
+                fh.write("\t".join(["scaffold"] + ["gap%d%s" % (g, o) for g in range(S) for o in "+-"]) + "\n")
+                for name, line in zip(res["names"], np.asarray(res["table"]).reshape(S, 2 * S)):
+                    fh.write("\t".join([name] + [repr(float(v)) for v in line]) + "\n")
+    print("Placement support written for scaffolds " + str(sum(len(r["rows"]) for r in results)))
+
+
 def getChromosomeOutlineCoords(orderedChromosomes):
     """OG:662-674."""
     coords, index = [], 0
@@ -869,10 +1116,19 @@ def getChromosomeOutlineCoords(orderedChromosomes):
     return coords
 
 
+def _read_groups_quietly(chromosomeGroupFile):
+    import contextlib
+    import io
+    with contextlib.redirect_stdout(io.StringIO()):
+        return readChromsFromFile(chromosomeGroupFile)
+
+
 def runPipeline(hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroupFile, chromosomeOrderFile,
                 savePlotsDirectory, chromosomePlotSuffix, fullGenomePlot, fullGenomePlotTitle, plotOrderFile,
-                nScaffolds, scanScaffolds, resolution, device=0, resident=None):
-    """OG:679-712, same positional arguments (``device`` and ``resident`` are optional extras).
+                nScaffolds, scanScaffolds, resolution, device=0, resident=None, placementSupportFile=None):
+    """OG:679-712, same positional arguments (``device``, ``resident`` and ``placementSupportFile`` are optional extras).
+
+    ``placementSupportFile``: also write the placement-support report of the final ordering there (placementSupport).
 
     ``resident=(DeviceMatrix, bins of its rows)`` from Part 1's ``runPipeline(..., keep_resident=True)``: the contact
     matrix already in HBM is used instead of parsing the HiC-Pro text again.  The reference re-loads the matrix
@@ -891,6 +1147,9 @@ def runPipeline(hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroup
         orderedChromosomes = runResident(adjMat, binList, chromosomeGroupFile, chromosomeOrderFile, plotOrderFile,
                                          nScaffolds, scanScaffolds, resolution, savePlotDir=savePlotsDirectory,
                                          plotTitleSuffix=chromosomePlotSuffix)
+        if placementSupportFile:
+            writePlacementSupportToFile(placementSupport(adjMat, orderedChromosomes, binList,
+                                                         _read_groups_quietly(chromosomeGroupFile)), placementSupportFile)
         if plotModule.plots_enabled(fullGenomePlot):                      # OG:700-707
             where = adjMat.bin_index(binList)
             rows = [where[b] for group in orderedChromosomes for s in group for b in s.binList]

@@ -61,6 +61,8 @@ _SPEC = [
     ("assembledFastaFile", '', "str", "saveFilesDirectory"),
 ]
 _BY_KEY = {k: (kind, prefix) for k, _d, kind, prefix in _SPEC}
+# keys a config may leave out: absent from the returned dictionary unless the file sets them
+_OPTIONAL = {"placementSupportFile": "saveFilesDirectory"}     # -part2 also writes the placement-support report there
 
 
 def _convert(values, key, text):
@@ -124,6 +126,8 @@ def readConfigFileToVariables(configFile):
             key, text = parts[0], parts[1]
             if key in _BY_KEY and text:
                 _convert(values, key, text)
+            elif key in _OPTIONAL and text:
+                values[key] = values[_OPTIONAL[key]] + '/' + text
     return values
 
 
@@ -186,7 +190,8 @@ def main(argv=None):
         part2.runPipeline(v["hicProBedFile"], v["hicProBiasFile"], v["hicProMatrixFile"], v["chromosomeGroupFile"],
                           v["chromosomeOrderFile"], v["savePlotsDirectory"], v["chromosomePlotSuffix"],
                           v["fullGenomePlot"], v["fullGenomePlotTitle"], v["plotOrderFile"],
-                          v["nScaffolds"], v["scanScaffolds"], v["resolution"], device=args.device, resident=resident)
+                          v["nScaffolds"], v["scanScaffolds"], v["resolution"], device=args.device, resident=resident,
+                          **({"placementSupportFile": v["placementSupportFile"]} if "placementSupportFile" in v else {}))
     if args.part3:
         from . import orientSmallScaffolds as part3
         part3.runPipeline(v["chromosomeOrderFile"], v["hicProScaffSizeFile"], v["restrictionSiteFile"], v["validPairFile"],

@@ -1,7 +1,7 @@
 """Part 2 parameter sweep: one map, one GPU, many ``nScaffolds x scanScaffolds`` settings.
 
     python -m hic_genome_assembler_amd.sweepPart2 -config cfg.txt -nScaffolds 5,6,7,8 -scanScaffolds 4,5,6,7,8
-           [-chromosomeGroupFile FILE] [-device 0] [-out DIR] [-plots]
+           [-chromosomeGroupFile FILE] [-device 0] [-out DIR] [-plots] [-support]
 
 The map is read once (the grouped bins only, as ``-part2`` reads it).  The settings are the distinct pairs after
 _startChromosome's clamps (nScaffolds >= 9 -> 8, scanScaffolds > nScaffolds -> nScaffolds).  Chromosomes are ordered
@@ -23,6 +23,8 @@ setting of its highest final_score (ties: the earlier setting in grid order).  f
 (hicmi_p2_score_exact, NumPy-trace order) of a chromosome's final bin order under ONE total per chromosome, the total
 of its selection (what hicmi_p2_total returns for it), so that settings compare on one footing; it is not the printed
 bestCost, whose total is rounded in arrangement order (OG:343 vs OG:506).  DIR defaults to saveFilesDirectory/sweep_part2.
+``-support`` also writes ``DIR/best/placementSupport.txt``, the placement-support report (orderGenome.placementSupport) of
+the best orderings; its score0 column is their final_score.
 """
 from __future__ import annotations
 
@@ -349,7 +351,7 @@ def _plots(matrix, binList, orders, outDir, fullGenomePlot, fullGenomePlotTitle,
 
 def runSweep(hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroupFile, chromosomeOrderFile, plotOrderFile,
              nScaffolds, scanScaffolds, outDir, resolution=100000, plots=False, fullGenomePlot="fullGenome.png",
-             fullGenomePlotTitle="", chromosomePlotSuffix=False, device=0, shard=None):
+             fullGenomePlotTitle="", chromosomePlotSuffix=False, device=0, shard=None, support=False):
     """OG:679-712 for every setting of the grid on one map (see the module docstring).  Returns a dict: 'grid' (the
     clamped settings), 'folded', 'best' (per chromosome the index of its best setting) and order_settings' results."""
     if shard is not None and shard[1] > 1:
@@ -379,6 +381,9 @@ def runSweep(hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroupFil
             best_text = [res["text"][best[c]][c] for c in range(len(chromList))]
             _write_files(os.path.join(outDir, "best"), best_orders, best_text, chromosomeOrderFile, plotOrderFile)
             write_summary(outDir, grid, res, chromList, best)
+            if support:
+                _lines(p2.writePlacementSupportToFile, p2.placementSupport(matrix, best_orders, binList, chromList),
+                       os.path.join(outDir, "best", "placementSupport.txt"))
             if plots and plotModule.plots_enabled(fullGenomePlot):
                 _plots(matrix, binList, best_orders, os.path.join(outDir, "best"), fullGenomePlot, fullGenomePlotTitle,
                        resolution, chromosomePlotSuffix)
@@ -400,6 +405,7 @@ def _parse_args(argv):
     p.add_argument("-device", type=int, default=0, help="GPU index (default 0)")
     p.add_argument("-out", type=str, default=None, help="output directory (default: saveFilesDirectory/sweep_part2)")
     p.add_argument("-plots", action="store_true", help="draw the best orderings' chromosome and genome figures")
+    p.add_argument("-support", action="store_true", help="write the placement-support report of the best orderings")
     return p.parse_args(argv)
 
 
@@ -420,7 +426,7 @@ def main(argv=None):
              args.chromosomeGroupFile or v["chromosomeGroupFile"], v["chromosomeOrderFile"], v["plotOrderFile"],
              nScaffolds, scanScaffolds, out, resolution=v["resolution"], plots=args.plots,
              fullGenomePlot=v["fullGenomePlot"], fullGenomePlotTitle=v["fullGenomePlotTitle"],
-             chromosomePlotSuffix=v["chromosomePlotSuffix"], device=args.device)
+             chromosomePlotSuffix=v["chromosomePlotSuffix"], device=args.device, support=args.support)
 
 
 if __name__ == "__main__":

@@ -301,6 +301,29 @@ int hicmi_p2_scan_all(hicmi_ctx *ctx, int32_t *ids, uint8_t *rev, int64_t S, int
 int hicmi_p2_insert_all_multi(int64_t n_jobs, hicmi_ctx *const *ctxs, int32_t *const *ids, uint8_t *const *rev,
                               const int64_t *S0, const int32_t *const *new_ids, const int64_t *n_new, double *best_out);
 
+/* Placement support of a finished ordering.  For one chromosome: its selection and layout (hicmi_p2_select,
+ * hicmi_p2_layout), its final arrangement A = (ids, rev) of S scaffolds and ONE total (the caller's: the literal total
+ * of the layout in layout order, every scaffold '+', so that all scores of a chromosome are on one footing).
+ * scores_out[(j * S + g) * 2 + r] = objective, under that total, of "A without scaffold j, j put back at gap g
+ * (0 ... S-1 of the arrangement without j) in orientation r (0 '+', 1 '-')": S x S x 2 doubles in enumeration order
+ * (j, then g ascending, then '+' before '-'), closed form BASE - STRADDLE(g) + CROSS(g, r), fp64.  (g = j, r = rev[j])
+ * is A itself; for a one-bin scaffold (g = j, the other r) has A's bin order too.
+ * best_out[2 j] = 2 g + r of the first maximum, in enumeration order, of the closed-form scores over the candidates of
+ * j whose bin order differs from A's - of a one-bin scaffold only its '+' candidates count, '-' being the same bin
+ * order - or -1 when there is none (S = 1: the only other candidate is the whole chromosome read backwards, which is
+ * not counted); best_out[2 j + 1] = how many of those candidates lie within 1e-9 (relative)
+ * of that maximum.  1: the move is decided.  More: the caller re-scores them literally (hicmi_p2_score_exact) and the
+ * first strict maximum of those values wins.
+ * A chromosome of fewer than 2 bins, or with total <= 0, gets 0.0 everywhere and no candidate.
+ * More than 4096 scaffolds or 40960 bins in one chromosome: HICMI_EUNSUPPORTED.
+ * hicmi_p2_support_multi: n_jobs chromosomes (one context each, all on one device) in one pair of launches - the grid
+ * runs over (chromosome, left-out scaffold) records - and one download.  Matrix reads are O(S n^2) per chromosome.
+ * Replaces the contexts' current arrangement by A.  Must not run concurrently with other calls on the contexts. */
+int hicmi_p2_support(hicmi_ctx *ctx, const int32_t *ids, const uint8_t *rev, int64_t S, double total, double *scores_out,
+                     int32_t *best_out);
+int hicmi_p2_support_multi(int64_t n_jobs, hicmi_ctx *const *ctxs, const int32_t *const *ids, const uint8_t *const *rev,
+                           const int64_t *S, const double *totals, double *const *scores_out, int32_t *const *best_out);
+
 /* ---- Part 3 input scan (host code, no GPU) -----------------------------------------------------
  * readValidPairFile (orientSmallScaffolds.py:159-177): of a HiC-Pro allValidPairs file
  * (read, scaffold1, pos1, strand1, scaffold2, pos2, ...) keep the lines whose (scaffold1, scaffold2) is one of the
