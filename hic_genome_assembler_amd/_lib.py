@@ -80,6 +80,9 @@ SIGNATURES = {
     "hicmi_plot_percentiles": (ctypes.c_int, [_vp, ctypes.c_int, _vp, c_i64, _vp, c_i64, _vp]),
     "hicmi_plot_downsample": (ctypes.c_int, [_vp, ctypes.c_int, _vp, c_i64, c_i64, _vp]),
     "hicmi_p2_insert_all_multi": (ctypes.c_int, [c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hicmi_p2_start_all": (ctypes.c_int, [c_i64] + [_vp] * 16),
+    "hicmi_p2_scan_arranged": (ctypes.c_int, [_vp, _vp, _vp, c_i64, c_i64, _vp, c_i64, _vp, c_i64, ctypes.POINTER(c_dbl),
+                                              ctypes.POINTER(c_dbl), ctypes.POINTER(c_i64)]),
     "hicmi_p2_support": (ctypes.c_int, [_vp, _vp, _vp, c_i64, c_dbl, _vp, _vp]),
     "hicmi_p2_support_multi": (ctypes.c_int, [c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hicmi_p2_scan_pass": (ctypes.c_int, [_vp, _vp, _vp, c_i64, c_i64, c_dbl, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl),
@@ -548,6 +551,51 @@ class Context:
         for ctx, _i, _r, _n in jobs:
             ctx._arr_sig = None
         return [(a_l[j], b_l[j], best[j]) for j in range(n)]
+
+    @staticmethod
+    def p2_start_all(jobs, tables):
+        """The start phase of several chromosomes in one call (hicmi_p2_start_all).  jobs: [(context, sel, scaf_start,
+        scaf_len, first_ids)], one distinct context per chromosome; tables: {k: (orders, orients as 0 / 1)} for every
+        k = len(first_ids) that occurs.  Returns [(total, pick or -1, literal cost, status)]; status 0 decided, 1 total is
+        0 (nothing scored), 2 no candidate above 0."""
+        n = len(jobs)
+        if n == 0:
+            return []
+        lib = jobs[0][0]._lib
+        i32 = lambda col: np.ascontiguousarray(np.concatenate([np.asarray(j[col], dtype=np.int32) for j in jobs]), dtype=np.int32)
+        sel, st, ln, ids = i32(1), i32(2), i32(3), i32(4)
+        n_sel = (c_i64 * n)(*[len(j[1]) for j in jobs])
+        n_scaf = (c_i64 * n)(*[len(j[2]) for j in jobs])
+        ks = (c_i64 * n)(*[len(j[4]) for j in jobs])
+        keep = {k: (np.ascontiguousarray(o, dtype=np.int8), np.ascontiguousarray(r, dtype=np.uint8)) for k, (o, r) in tables.items()}
+        po = (ctypes.c_void_p * 9)(*[keep[k][0].ctypes.data if k in keep else None for k in range(9)])
+        pr = (ctypes.c_void_p * 9)(*[keep[k][1].ctypes.data if k in keep else None for k in range(9)])
+        no = (c_i64 * 9)(*[keep[k][0].shape[0] if k in keep else 0 for k in range(9)])
+        nr = (c_i64 * 9)(*[keep[k][1].shape[0] if k in keep else 0 for k in range(9)])
+        handles = (ctypes.c_void_p * n)(*[j[0]._h for j in jobs])
+        total, pick, cost, status = (c_dbl * n)(), (c_i64 * n)(), (c_dbl * n)(), (ctypes.c_int32 * n)()
+        _check(lib.hicmi_p2_start_all(n, handles, _ptr(sel), n_sel, _ptr(st), _ptr(ln), n_scaf, _ptr(ids), ks, po, no, pr, nr,
+                                      total, pick, cost, status))
+        for j, job in enumerate(jobs):
+            ctx, k = job[0], len(job[4])
+            ctx._arr_sig, ctx._arr_len = None, k
+            if status[j] != 1:
+                ctx._n_window_cand = keep[k][0].shape[0] * keep[k][1].shape[0]
+        return [(total[j], int(pick[j]), cost[j], int(status[j])) for j in range(n)]
+
+    def p2_scan_arranged(self, ids, rev, k, orders, orients, best):
+        """scanOrdering from the arrangement the insertion phase returned (hicmi_p2_scan_arranged): returns (ids, rev,
+        best, rounds, total)."""
+        a = np.ascontiguousarray(ids, dtype=np.int32).copy()
+        b = np.ascontiguousarray(rev, dtype=np.uint8).copy()
+        o = np.ascontiguousarray(orders, dtype=np.int8)
+        r = np.ascontiguousarray(orients, dtype=np.uint8)
+        bst, total, rounds = c_dbl(float(best)), c_dbl(), c_i64()
+        _check(self._lib.hicmi_p2_scan_arranged(self._h, _ptr(a), _ptr(b), len(a), int(k), _ptr(o), o.shape[0], _ptr(r), r.shape[0],
+                                                ctypes.byref(total), ctypes.byref(bst), ctypes.byref(rounds)))
+        self._arr_sig = None
+        self._n_window_cand = o.shape[0] * r.shape[0]
+        return a, b, bst.value, int(rounds.value), total.value
 
     def p2_support(self, ids, rev, total: float):
         """Placement support of one chromosome (hicmi_p2_support): (S x S x 2 table of closed-form scores,

@@ -122,7 +122,7 @@ struct hicmi_ctx {
     double* d_delta = nullptr; int64_t delta_cap = 0;
     WindowBatchEntry* d_wb = nullptr; int64_t wb_cap = 0;
     // short lists of wide windows decided on the device (HICMI_P2_DEVICE_DECIDE, read at creation): windows of at least
-    // near_min_k scaffolds; [per-window counters][pass-1 partials][NearEntry lists]
+    // near_min_k scaffolds; [pass-1 partials][per-window counters][NearEntry lists]
     int near_min_k = 7;
     unsigned char* d_wnear = nullptr; int64_t wnear_cap = 0;
     // device-decided insertion (k_part2_insert.hip): second arrangement buffers (ping-pong) and work areas
@@ -1340,7 +1340,17 @@ int hicmi_filter_cuts_multi(hicmi_ctx* c, int64_t n_sets, const int64_t* cand_of
 }
 
 // ---------------------------------------------------------------------------------------------------
-int hicmi_p2_select(hicmi_ctx* c, const int32_t* sel, int64_t n)
+namespace {
+// H[k] = 1 + 1/2 + ... + 1/k, left to right in fp64 (H[0] = 0): entries [0, n]
+void harmonic_table(std::vector<double>& H, int64_t n)
+{
+    H.assign((size_t)(n + 1), 0.0);
+    for (int64_t k = 1; k <= n; k++) H[(size_t)k] = H[(size_t)k - 1] + 1.0 / (double)k;
+}
+
+// hicmi_p2_select without its wait: the H table (when it has to grow; `H_shared`, if given, holds at least n + 1 entries of
+// harmonic_table), the selection and the gather kernel are queued on the context's stream
+int select_enqueue(hicmi_ctx* c, const int32_t* sel, int64_t n, const std::vector<double>* H_shared)
 {
     if (!c || !sel || n < 1) return fail(HICMI_EINVAL, "bad arguments");
     if (!c->dC) return fail(HICMI_EINVAL, "no contact matrix set");
@@ -1352,16 +1362,13 @@ int hicmi_p2_select(hicmi_ctx* c, const int32_t* sel, int64_t n)
     if (rc) return rc;
     rc = ensure(c->d_sel, c->sel_cap, n);
     if (rc) return rc;
-    // H[k] = 1 + 1/2 + ... + 1/k, left to right in fp64
     if (c->h_cap < n + 1) {
-        std::vector<double> H((size_t)(n + 1));
-        H[0] = 0.0;
-        for (int64_t k = 1; k <= n; k++) H[(size_t)k] = H[(size_t)k - 1] + 1.0 / (double)k;
+        std::vector<double> own;
+        if (!H_shared || (int64_t)H_shared->size() < n + 1) { harmonic_table(own, n); H_shared = &own; }
         rc = ensure(c->d_H, c->h_cap, n + 1);
         if (rc) return rc;
-        rc = upload(c, c->d_H, H.data(), sizeof(double) * (size_t)(n + 1));
+        rc = upload(c, c->d_H, H_shared->data(), sizeof(double) * (size_t)(n + 1));
         if (rc) return rc;
-        HIPCHK(sync_stream(c));
     }
     rc = upload(c, c->d_sel, sel, sizeof(int32_t) * (size_t)n);
     if (rc) return rc;
@@ -1370,10 +1377,18 @@ int hicmi_p2_select(hicmi_ctx* c, const int32_t* sel, int64_t n)
         launch_p2_select(c->dC, c->ldc, c->d_sel, (int)n, c->dM2, ld2, c->stream);
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(sync_stream(c));
     c->n2 = n; c->ld2 = ld2;
     c->n_scaf = 0; c->n_arr = 0; c->h_arr_id.clear();
     c->cache_valid = false; c->exact_cache.clear();
+    return HICMI_OK;
+}
+}  // namespace
+
+int hicmi_p2_select(hicmi_ctx* c, const int32_t* sel, int64_t n)
+{
+    int rc = select_enqueue(c, sel, n, nullptr);
+    if (rc) return rc;
+    HIPCHK(sync_stream(c));
     return HICMI_OK;
 }
 
@@ -1507,22 +1522,36 @@ int hicmi_p2_set_arrangement(hicmi_ctx* c, const int32_t* ids, const uint8_t* re
     return HICMI_OK;
 }
 
-int hicmi_p2_arrangement_total(hicmi_ctx* c, double* total_out)
+namespace {
+// hicmi_p2_arrangement_total without its wait: the kernel and the copy of the total to the head of the pinned download
+// buffer are queued; the value is there after sync_stream
+int arrangement_total_enqueue(hicmi_ctx* c)
 {
-    if (!c || !total_out) return fail(HICMI_EINVAL, "bad arguments");
     if (c->n_arr < 1) return fail(HICMI_EINVAL, "hicmi_p2_set_arrangement has not run");
     HIPCHK(hipSetDevice(c->device));
     int rc = ensure(c->d_T, c->t_cap, c->n_arr + 1);
     if (rc) return rc;
     rc = ensure(c->d_scores, c->scores_cap, 1);
     if (rc) return rc;
+    rc = ensure_pin_down(c, sizeof(double));
+    if (rc) return rc;
     {
         Timed t(c, F_P2_TOTAL, 4.0 * (double)c->n_arr * (double)c->n_arr);
         launch_p2_total_perm(c->dM2, c->ld2, c->d_pos2sel, (int)c->n_arr, c->d_T, c->d_scores, c->stream);
     }
     HIPCHK(hipGetLastError());
-    rc = download(c, total_out, c->d_scores, sizeof(double));
+    HIPCHK(hipMemcpyAsync(c->pin_down, c->d_scores, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return HICMI_OK;
+}
+}  // namespace
+
+int hicmi_p2_arrangement_total(hicmi_ctx* c, double* total_out)
+{
+    if (!c || !total_out) return fail(HICMI_EINVAL, "bad arguments");
+    int rc = arrangement_total_enqueue(c);
     if (rc) return rc;
+    HIPCHK(sync_stream(c));
+    memcpy(total_out, c->pin_down, sizeof(double));
     return HICMI_OK;
 }
 
@@ -1655,8 +1684,8 @@ int fill_batch(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k, std::vect
 }
 
 // deltas of `count` consecutive windows (first0, first0+1, ...) of k scaffolds against the CURRENT
-// arrangement, one launch pair; delta_out: count x n_cand
-int window_batch(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k, double* delta_out)
+// arrangement, one launch pair, and their copy to the pinned download buffer (count x n_cand doubles), all queued
+int window_batch_enqueue(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k)
 {
     std::vector<WindowBatchEntry> wb;
     BatchCost bc;
@@ -1691,8 +1720,19 @@ int window_batch(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k, double*
                                     c->stream);
     }
     HIPCHK(hipGetLastError());
-    rc = download(c, delta_out, c->d_delta, sizeof(double) * (size_t)(n_cand * count));
+    rc = ensure_pin_down(c, sizeof(double) * (size_t)(n_cand * count));
     if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(c->pin_down, c->d_delta, sizeof(double) * (size_t)(n_cand * count), hipMemcpyDeviceToHost, c->stream));
+    return HICMI_OK;
+}
+
+// ... and waited for; delta_out: count x n_cand
+int window_batch(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k, double* delta_out)
+{
+    int rc = window_batch_enqueue(c, first0, count, k);
+    if (rc) return rc;
+    HIPCHK(sync_stream(c));
+    memcpy(delta_out, c->pin_down, sizeof(double) * (size_t)(c->n_orders * c->n_orients * count));
     return HICMI_OK;
 }
 }  // namespace
@@ -1716,48 +1756,65 @@ void use_total(hicmi_ctx* c, double total)
     if (!c->cache_valid || c->cache_total != total) { c->exact_cache.clear(); c->cache_total = total; c->cache_valid = true; }
 }
 
-// literal scores of rows (each n_used selection indices) under `total`, through the cache
-int literal_scores(hicmi_ctx* c, const std::vector<std::vector<int32_t>>& rows, double total, std::vector<double>& out)
+// literal scores of rows (each n_used selection indices) under `total`, through the cache: literal_enqueue queues the
+// kernel for the rows the cache does not hold and the copy of their scores to the pinned download buffer, literal_collect
+// waits for them, fills the cache and reads every row's score from it
+struct LiteralPending { std::vector<std::string> keys; std::vector<size_t> todo; bool queued = false; };
+
+int literal_enqueue(hicmi_ctx* c, const std::vector<std::vector<int32_t>>& rows, double total, LiteralPending& p)
 {
-    out.assign(rows.size(), 0.0);
+    p.keys.assign(rows.size(), std::string()); p.todo.clear(); p.queued = false;
     if (rows.empty()) return HICMI_OK;
     const int64_t n_used = (int64_t)rows[0].size();
-    std::vector<std::string> keys(rows.size());
-    std::vector<size_t> todo;
     std::unordered_map<std::string, size_t> pending;
     for (size_t i = 0; i < rows.size(); i++) {
-        keys[i].assign(reinterpret_cast<const char*>(rows[i].data()), rows[i].size() * sizeof(int32_t));
-        if (c->exact_cache.count(keys[i]) || pending.count(keys[i])) continue;
-        pending[keys[i]] = todo.size();
-        todo.push_back(i);
+        p.keys[i].assign(reinterpret_cast<const char*>(rows[i].data()), rows[i].size() * sizeof(int32_t));
+        if (c->exact_cache.count(p.keys[i]) || pending.count(p.keys[i])) continue;
+        pending[p.keys[i]] = p.todo.size();
+        p.todo.push_back(i);
     }
-    if (!todo.empty()) {
-        std::vector<double> vals(todo.size(), 0.0);
-        if (n_used >= 2) {
-            std::vector<int32_t> flat((size_t)n_used * todo.size());
-            for (size_t t = 0; t < todo.size(); t++) memcpy(flat.data() + t * n_used, rows[todo[t]].data(), sizeof(int32_t) * (size_t)n_used);
-            const int64_t n_cand = (int64_t)todo.size();
-            int rc = ensure(c->d_perms, c->perms_cap, n_cand * n_used);
-            if (rc) return rc;
-            rc = ensure(c->d_scores, c->scores_cap, n_cand);
-            if (rc) return rc;
-            rc = ensure(c->d_T, c->t_cap, 2 * n_cand * n_used);
-            if (rc) return rc;
-            rc = upload(c, c->d_perms, flat.data(), sizeof(int32_t) * flat.size());
-            if (rc) return rc;
-            {
-                Timed t(c, F_P2_EXACT, 8.0 * (double)n_cand * 0.5 * (double)n_used * (double)(n_used - 1));
-                launch_p2_score_exact(c->dM2, c->ld2, c->d_perms, (int)n_cand, (int)n_used, total, c->d_T,
-                                      c->d_T + n_cand * n_used, c->d_scores, c->stream);
-            }
-            HIPCHK(hipGetLastError());
-            rc = download(c, vals.data(), c->d_scores, sizeof(double) * vals.size());
-            if (rc) return rc;
-        }
-        for (size_t t = 0; t < todo.size(); t++) c->exact_cache[keys[todo[t]]] = vals[t];
+    if (p.todo.empty() || n_used < 2) return HICMI_OK;
+    std::vector<int32_t> flat((size_t)n_used * p.todo.size());
+    for (size_t t = 0; t < p.todo.size(); t++) memcpy(flat.data() + t * n_used, rows[p.todo[t]].data(), sizeof(int32_t) * (size_t)n_used);
+    const int64_t n_cand = (int64_t)p.todo.size();
+    int rc = ensure(c->d_perms, c->perms_cap, n_cand * n_used);
+    if (rc) return rc;
+    rc = ensure(c->d_scores, c->scores_cap, n_cand);
+    if (rc) return rc;
+    rc = ensure(c->d_T, c->t_cap, 2 * n_cand * n_used);
+    if (rc) return rc;
+    rc = ensure_pin_down(c, sizeof(double) * (size_t)n_cand);
+    if (rc) return rc;
+    rc = upload(c, c->d_perms, flat.data(), sizeof(int32_t) * flat.size());
+    if (rc) return rc;
+    {
+        Timed t(c, F_P2_EXACT, 8.0 * (double)n_cand * 0.5 * (double)n_used * (double)(n_used - 1));
+        launch_p2_score_exact(c->dM2, c->ld2, c->d_perms, (int)n_cand, (int)n_used, total, c->d_T,
+                              c->d_T + n_cand * n_used, c->d_scores, c->stream);
     }
-    for (size_t i = 0; i < rows.size(); i++) out[i] = c->exact_cache[keys[i]];
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->pin_down, c->d_scores, sizeof(double) * (size_t)n_cand, hipMemcpyDeviceToHost, c->stream));
+    p.queued = true;
     return HICMI_OK;
+}
+
+int literal_collect(hicmi_ctx* c, const LiteralPending& p, std::vector<double>& out)
+{
+    out.assign(p.keys.size(), 0.0);
+    if (p.keys.empty()) return HICMI_OK;
+    if (p.queued) HIPCHK(sync_stream(c));
+    const double* vals = reinterpret_cast<const double*>(c->pin_down);
+    for (size_t t = 0; t < p.todo.size(); t++) c->exact_cache[p.keys[p.todo[t]]] = p.queued ? vals[t] : 0.0;   // fewer than 2 bins: cost 0.0
+    for (size_t i = 0; i < p.keys.size(); i++) out[i] = c->exact_cache[p.keys[i]];
+    return HICMI_OK;
+}
+
+int literal_scores(hicmi_ctx* c, const std::vector<std::vector<int32_t>>& rows, double total, std::vector<double>& out)
+{
+    LiteralPending p;
+    int rc = literal_enqueue(c, rows, total, p);
+    if (rc) return rc;
+    return literal_collect(c, p, out);
 }
 
 // indices of the candidates whose fast score is within kNearTop of max(best fast, floor)
@@ -1773,6 +1830,39 @@ void short_list(const std::vector<double>& fast, double floor, std::vector<int64
 }  // namespace
 
 namespace {
+// bin orders (selection indices) of the candidates `near` of the window first .. first + k - 1 of the CURRENT arrangement
+void near_rows(const hicmi_ctx* c, int64_t first, int64_t k, const std::vector<int64_t>& near, std::vector<std::vector<int32_t>>& rows)
+{
+    const int64_t n_ori = c->n_orients;
+    const int p0 = c->h_arr_pos[(size_t)first], p1 = c->h_arr_pos[(size_t)(first + k)];
+    rows.assign(near.size(), {});
+    for (size_t q = 0; q < near.size(); q++) {
+        const int64_t cand = near[q];
+        const int8_t* ord = c->h_orders.data() + (cand / n_ori) * k;
+        const uint8_t* ori = c->h_orients.data() + (cand % n_ori) * k;
+        std::vector<int32_t>& row = rows[q];
+        row.reserve((size_t)c->n_arr);
+        row.insert(row.end(), c->h_pos2sel.begin(), c->h_pos2sel.begin() + p0);
+        for (int64_t j = 0; j < k; j++) {
+            const int32_t sc = c->h_arr_id[(size_t)(first + ord[j])];
+            const int32_t st = c->h_scaf_start[(size_t)sc], ln = c->h_scaf_len[(size_t)sc];
+            if (ori[j]) for (int32_t e = 0; e < ln; e++) row.push_back(st + ln - 1 - e);
+            else        for (int32_t e = 0; e < ln; e++) row.push_back(st + e);
+        }
+        row.insert(row.end(), c->h_pos2sel.begin() + p1, c->h_pos2sel.end());
+    }
+}
+
+// the reference's `if cost > bestCost` over a short list in enumeration order, on the literal scores `lit`
+void pick_first_strict_max(const std::vector<int64_t>& near, const std::vector<double>& near_fast, const std::vector<double>& lit,
+                           double floor, int64_t* pick_out, double* best_out, double* pick_fast_out)
+{
+    double best = floor; int64_t pick = -1; size_t pick_q = 0;
+    for (size_t q = 0; q < near.size(); q++) if (lit[q] > best) { best = lit[q]; pick = near[q]; pick_q = q; }
+    *pick_out = pick; *best_out = best;
+    if (pick >= 0) *pick_fast_out = near_fast[pick_q];
+}
+
 // The decision of one window from its short list: `near` = the candidates within kNearTop of max(best fast, floor) in
 // enumeration order, `near_fast` their fast scores, c0 the current configuration's candidate.  Shared by the host list
 // (decide_from_delta) and the device list (window_near_batch).
@@ -1781,7 +1871,6 @@ int decide_from_near(hicmi_ctx* c, int64_t first, int64_t k, double total, doubl
                      double* best_out, double* pick_fast_out)
 {
     const int64_t S = (int64_t)c->h_arr_id.size();
-    const int64_t n_ori = c->n_orients;
     *pick_out = -1; *best_out = floor; *pick_fast_out = cur_fast;
     if (near.empty()) return HICMI_OK;
     int rc;
@@ -1806,30 +1895,17 @@ int decide_from_near(hicmi_ctx* c, int64_t first, int64_t k, double total, doubl
             }
         }
     }
-    const int p0 = c->h_arr_pos[(size_t)first], p1 = c->h_arr_pos[(size_t)(first + k)];
-    std::vector<std::vector<int32_t>> rows(near.size());
-    for (size_t q = 0; q < near.size(); q++) {
-        const int64_t cand = near[q];
-        const int8_t* ord = c->h_orders.data() + (cand / n_ori) * k;
-        const uint8_t* ori = c->h_orients.data() + (cand % n_ori) * k;
-        std::vector<int32_t>& row = rows[q];
-        row.reserve((size_t)c->n_arr);
-        row.insert(row.end(), c->h_pos2sel.begin(), c->h_pos2sel.begin() + p0);
-        for (int64_t j = 0; j < k; j++) {
-            const int32_t sc = c->h_arr_id[(size_t)(first + ord[j])];
-            const int32_t st = c->h_scaf_start[(size_t)sc], ln = c->h_scaf_len[(size_t)sc];
-            if (ori[j]) for (int32_t e = 0; e < ln; e++) row.push_back(st + ln - 1 - e);
-            else        for (int32_t e = 0; e < ln; e++) row.push_back(st + e);
-        }
-        row.insert(row.end(), c->h_pos2sel.begin() + p1, c->h_pos2sel.end());
-    }
-    std::vector<double> lit;
-    rc = literal_scores(c, rows, total, lit);
+    // (the arrangement's own row is not built and keyed again: it has the same bin order, hence the same cache key and value)
+    std::vector<int64_t> others;
+    for (int64_t cand : near) if (!(have_c0 && cand == c0)) others.push_back(cand);
+    std::vector<std::vector<int32_t>> rows;
+    near_rows(c, first, k, others, rows);
+    std::vector<double> lit_others;
+    rc = literal_scores(c, rows, total, lit_others);
     if (rc) return rc;
-    double best = floor; int64_t pick = -1; size_t pick_q = 0;
-    for (size_t q = 0; q < near.size(); q++) if (lit[q] > best) { best = lit[q]; pick = near[q]; pick_q = q; }
-    *pick_out = pick; *best_out = best;
-    if (pick >= 0) *pick_fast_out = near_fast[pick_q];
+    std::vector<double> lit(near.size());
+    for (size_t q = 0, o = 0; q < near.size(); q++) lit[q] = (have_c0 && near[q] == c0) ? lit_c0 : lit_others[o++];
+    pick_first_strict_max(near, near_fast, lit, floor, pick_out, best_out, pick_fast_out);
     return HICMI_OK;
 }
 
@@ -1861,9 +1937,16 @@ int decide_from_delta(hicmi_ctx* c, int64_t first, int64_t k, double total, doub
 // (k_win_near): per window its near-top candidates in enumeration order and their fast scores, equal to short_list over
 // the downloaded deltas.  All windows share floor and cur_fast (NaN: computed here when k < S).  n_near[w] > cap: the
 // window's list overflowed, near[w] / near_fast[w] are left empty.
-int window_near_batch(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k, double total, double floor, double& cur_fast,
-                      int64_t cap, std::vector<int64_t>& n_near, std::vector<std::vector<int64_t>>& near,
-                      std::vector<std::vector<double>>& near_fast)
+// window_near_enqueue queues the kernels and the copy of every window's count and of the first kNearHead entries of its
+// list to the pinned download buffer; window_near_collect waits for them ONCE and goes back to the device only for a
+// list that is longer.  Device work area: [pass-1 partials][per-window counters][NearEntry lists] - the counters lie
+// directly in front of the lists, so that a single window's count and list head come down in one copy.
+const int64_t kNearHead = 16;
+
+struct NearPending { int64_t count = 0, cap = 0, head = 0; size_t off_cnt = 0, off_list = 0, host_list = 0; };
+
+int window_near_enqueue(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k, double total, double floor, double& cur_fast,
+                        int64_t cap, NearPending& p)
 {
     std::vector<WindowBatchEntry> wb;
     BatchCost bc;
@@ -1879,8 +1962,8 @@ int window_near_batch(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k, do
     if (k != S && std::isnan(cur_fast)) { rc = hicmi_p2_arrangement_score(c, total, &cur_fast); if (rc) return rc; }
     HIPCHK(hipSetDevice(c->device));
     const int n_blocks = window_near_blocks((int)c->n_orders);
-    const size_t off_part = ((size_t)count * sizeof(int32_t) + 15) & ~(size_t)15;
-    const size_t off_list = off_part + (size_t)count * (size_t)n_blocks * sizeof(double);
+    const size_t off_cnt = (size_t)count * (size_t)n_blocks * sizeof(double);
+    const size_t off_list = off_cnt + (((size_t)count * sizeof(int32_t) + 15) & ~(size_t)15);
     const size_t bytes = off_list + (size_t)count * (size_t)cap * sizeof(NearEntry);
     rc = ensure(c->d_G, c->g_cap, count * window_table_doubles((int)k));
     if (rc) return rc;
@@ -1890,20 +1973,39 @@ int window_near_batch(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k, do
     if (rc) return rc;
     rc = upload(c, c->d_wb, wb.data(), sizeof(WindowBatchEntry) * (size_t)count);
     if (rc) return rc;
-    int32_t* d_count = reinterpret_cast<int32_t*>(c->d_wnear);
+    int32_t* d_count = reinterpret_cast<int32_t*>(c->d_wnear + off_cnt);
     NearEntry* d_list = reinterpret_cast<NearEntry*>(c->d_wnear + off_list);
     {
         c->launches[F_P2_WINDOW_FLOPS]++; c->bytes[F_P2_WINDOW_FLOPS] += bc.g_flops;
         Timed t(c, F_P2_WINDOW_G, bc.g_bytes);
         launch_p2_window_near(c->dM2, c->ld2, c->d_pos2sel, (int)c->n_arr, (int)k, c->d_wb, wb.data(), (int)count, bc.max_m,
                               c->d_orders, c->d_orients, (int)c->n_orders, (int)c->n_orients, c->d_H, c->d_G, k == S ? 1 : 0,
-                              total, cur_fast, floor, kNearTop, reinterpret_cast<double*>(c->d_wnear + off_part), d_count,
+                              total, cur_fast, floor, kNearTop, reinterpret_cast<double*>(c->d_wnear), d_count,
                               d_list, (int)cap, c->stream);
     }
     HIPCHK(hipGetLastError());
-    std::vector<int32_t> cnt((size_t)count);
-    rc = download(c, cnt.data(), d_count, sizeof(int32_t) * (size_t)count);
+    p.count = count; p.cap = cap; p.head = std::min<int64_t>(kNearHead, cap); p.off_cnt = off_cnt; p.off_list = off_list;
+    p.host_list = off_list - off_cnt;                       // pinned buffer: [counters, padded][count x head entries]
+    const size_t row = (size_t)p.head * sizeof(NearEntry);
+    rc = ensure_pin_down(c, p.host_list + row * (size_t)count);
     if (rc) return rc;
+    if (count == 1)
+        HIPCHK(hipMemcpyAsync(c->pin_down, d_count, p.host_list + row, hipMemcpyDeviceToHost, c->stream));
+    else {
+        HIPCHK(hipMemcpyAsync(c->pin_down, d_count, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpy2DAsync(c->pin_down + p.host_list, row, d_list, (size_t)cap * sizeof(NearEntry), row, (size_t)count,
+                                hipMemcpyDeviceToHost, c->stream));
+    }
+    return HICMI_OK;
+}
+
+int window_near_collect(hicmi_ctx* c, const NearPending& p, std::vector<int64_t>& n_near,
+                        std::vector<std::vector<int64_t>>& near, std::vector<std::vector<double>>& near_fast)
+{
+    const int64_t count = p.count, cap = p.cap;
+    HIPCHK(sync_stream(c));
+    std::vector<int32_t> cnt((size_t)count);
+    memcpy(cnt.data(), c->pin_down, sizeof(int32_t) * (size_t)count);
     n_near.assign((size_t)count, 0); near.assign((size_t)count, {}); near_fast.assign((size_t)count, {});
     int64_t widest = 0;
     for (int64_t w = 0; w < count; w++) {
@@ -1911,24 +2013,39 @@ int window_near_batch(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k, do
         if (cnt[(size_t)w] <= cap) widest = std::max<int64_t>(widest, cnt[(size_t)w]);
     }
     if (widest == 0) return HICMI_OK;
-    // the first `widest` entries of every window in one strided copy
-    const size_t row = (size_t)widest * sizeof(NearEntry);
-    rc = ensure_pin_down(c, row * (size_t)count);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy2DAsync(c->pin_down, row, d_list, (size_t)cap * sizeof(NearEntry), row, (size_t)count,
-                            hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(sync_stream(c));
+    size_t row = (size_t)p.head * sizeof(NearEntry);
+    const char* lists = c->pin_down + p.host_list;
+    if (widest > p.head) {
+        // a list beyond the head: the first `widest` entries of every window in one strided copy
+        row = (size_t)widest * sizeof(NearEntry);
+        int rc = ensure_pin_down(c, row * (size_t)count);
+        if (rc) return rc;
+        HIPCHK(hipMemcpy2DAsync(c->pin_down, row, c->d_wnear + p.off_list, (size_t)cap * sizeof(NearEntry), row, (size_t)count,
+                                hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(sync_stream(c));
+        lists = c->pin_down;
+    }
     std::vector<NearEntry> ent;
     for (int64_t w = 0; w < count; w++) {
         const int64_t m = cnt[(size_t)w];
         if (m < 1 || m > cap) continue;
-        const NearEntry* src = reinterpret_cast<const NearEntry*>(c->pin_down + row * (size_t)w);
+        const NearEntry* src = reinterpret_cast<const NearEntry*>(lists + row * (size_t)w);
         ent.assign(src, src + m);
         std::sort(ent.begin(), ent.end(), [](const NearEntry& a, const NearEntry& b) { return a.cand < b.cand; });
         near[(size_t)w].resize((size_t)m); near_fast[(size_t)w].resize((size_t)m);
         for (int64_t q = 0; q < m; q++) { near[(size_t)w][(size_t)q] = ent[(size_t)q].cand; near_fast[(size_t)w][(size_t)q] = ent[(size_t)q].fast; }
     }
     return HICMI_OK;
+}
+
+int window_near_batch(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k, double total, double floor, double& cur_fast,
+                      int64_t cap, std::vector<int64_t>& n_near, std::vector<std::vector<int64_t>>& near,
+                      std::vector<std::vector<double>>& near_fast)
+{
+    NearPending p;
+    int rc = window_near_enqueue(c, first0, count, k, total, floor, cur_fast, cap, p);
+    if (rc) return rc;
+    return window_near_collect(c, p, n_near, near, near_fast);
 }
 
 const int64_t kNearCap = 4096;     // candidates per window list; a window beyond it sends its batch down the delta path
@@ -2465,6 +2582,163 @@ int hicmi_p2_scan_all(hicmi_ctx* c, int32_t* ids, uint8_t* rev, int64_t S, int64
         if (!improved) return HICMI_OK;
         if (*rounds_out > 100000) return fail(HICMI_ESTATE, "scanOrdering does not converge");
     }
+}
+
+int hicmi_p2_scan_arranged(hicmi_ctx* c, int32_t* ids, uint8_t* rev, int64_t S, int64_t k, const int8_t* orders,
+                           int64_t n_orders, const uint8_t* orients, int64_t n_orients, double* total_out, double* best_io,
+                           int64_t* rounds_out)
+{
+    // scanOrdering (OG:495-549) from the arrangement the insertion phase left, all of it in one call: the arrangement,
+    // its total in exactly that order (OG:506), the window tables for k unless they are the loaded ones, then the rounds
+    if (!c || !ids || !rev || !orders || !orients || !total_out || !best_io || !rounds_out || S < 1 || k < 1 || k > S)
+        return fail(HICMI_EINVAL, "bad arguments");
+    int rc = hicmi_p2_set_arrangement(c, ids, rev, S);
+    if (rc) return rc;
+    double total = 0.0;                                    // fewer than 2 bins: nothing above the diagonal
+    if (c->n_arr >= 2) { rc = hicmi_p2_arrangement_total(c, &total); if (rc) return rc; }
+    *total_out = total;
+    const bool loaded = c->tab_k == (int)k && c->n_orders == n_orders && c->n_orients == n_orients
+                        && (int64_t)c->h_orders.size() == n_orders * k && (int64_t)c->h_orients.size() == n_orients * k
+                        && !memcmp(c->h_orders.data(), orders, (size_t)(n_orders * k))
+                        && !memcmp(c->h_orients.data(), orients, (size_t)(n_orients * k));
+    if (!loaded) { rc = hicmi_p2_window_tables(c, k, orders, n_orders, orients, n_orients); if (rc) return rc; }
+    double cur_fast = std::nan("");
+    return hicmi_p2_scan_all(c, ids, rev, S, k, total, best_io, &cur_fast, rounds_out);
+}
+
+int hicmi_p2_start_all(int64_t n_jobs, hicmi_ctx* const* ctxs, const int32_t* sel, const int64_t* n_sel,
+                       const int32_t* scaf_start, const int32_t* scaf_len, const int64_t* n_scaf, const int32_t* first_ids,
+                       const int64_t* k, const int8_t* const* orders, const int64_t* n_orders, const uint8_t* const* orients,
+                       const int64_t* n_orients, double* total_out, int64_t* pick_out, double* cost_out, int32_t* status_out)
+{
+    // _startChromosome (OG:551-576 up to the brute force) of n_jobs chromosomes, one context each: what hicmi_p2_select,
+    // _layout, _set_arrangement, _arrangement_total, _window_tables and _decide_window(0, k, total, 0., NaN) do for one
+    // chromosome, through the same functions, but PHASE BY PHASE over all jobs - everything of a phase is queued on each
+    // job's own stream before any stream is waited for, so the jobs overlap on the device and the calling thread waits
+    // three times per job instead of five or six
+    if (n_jobs < 1 || !ctxs || !sel || !n_sel || !scaf_start || !scaf_len || !n_scaf || !first_ids || !k || !orders || !n_orders
+        || !orients || !n_orients || !total_out || !pick_out || !cost_out || !status_out)
+        return fail(HICMI_EINVAL, "bad arguments");
+    const size_t nj = (size_t)n_jobs;
+    std::vector<int64_t> sel_off(nj), scaf_off(nj), id_off(nj);
+    int64_t n_max = 0;
+    {
+        int64_t so = 0, fo = 0, io = 0;
+        for (size_t j = 0; j < nj; j++) {
+            hicmi_ctx* c = ctxs[j];
+            if (!c || c->device != ctxs[0]->device) return fail(HICMI_EINVAL, "contexts must share one device");
+            for (size_t q = 0; q < j; q++) if (ctxs[q] == c) return fail(HICMI_EINVAL, "one context per chromosome");
+            if (n_sel[j] < 1 || n_scaf[j] < 1 || k[j] < 1 || k[j] > 8 || k[j] > n_scaf[j]) return fail(HICMI_EINVAL, "bad job %lld", (long long)j);
+            if (!orders[k[j]] || !orients[k[j]] || n_orders[k[j]] < 1 || n_orients[k[j]] < 1)
+                return fail(HICMI_EINVAL, "no order / orientation tables for k = %lld", (long long)k[j]);
+            sel_off[j] = so; scaf_off[j] = fo; id_off[j] = io;
+            so += n_sel[j]; fo += n_scaf[j]; io += k[j];
+            n_max = std::max(n_max, n_sel[j]);
+        }
+    }
+    std::vector<double> H;
+    harmonic_table(H, n_max);                              // the same prefix for every job
+    enum { DECIDED = 0, ZERO_TOTAL = 1, NO_CANDIDATE = 2 };
+    enum { IDLE, TOTAL, NEAR, DELTA, LITERAL };
+    std::vector<int> phase(nj, IDLE);
+    auto drain = [&](int rc) {                             // an error with work in flight: leave no stream busy
+        for (size_t j = 0; j < nj; j++) (void)sync_stream(ctxs[j]);
+        return rc;
+    };
+    int rc;
+    // ---- a. selection, layout, the k largest scaffolds as the arrangement, its total
+    for (size_t j = 0; j < nj; j++) {
+        hicmi_ctx* c = ctxs[j];
+        total_out[j] = 0.0; pick_out[j] = -1; cost_out[j] = 0.0; status_out[j] = ZERO_TOTAL;
+        rc = select_enqueue(c, sel + sel_off[j], n_sel[j], &H);
+        if (rc) return drain(rc);
+        rc = hicmi_p2_layout(c, scaf_start + scaf_off[j], scaf_len + scaf_off[j], n_scaf[j]);
+        if (rc) return drain(rc);
+        const int32_t* ids = first_ids + id_off[j];
+        int64_t n_bins = 0;
+        for (int64_t q = 0; q < k[j]; q++) {
+            if (ids[q] < 0 || ids[q] >= n_scaf[j]) return drain(fail(HICMI_EINVAL, "arrangement must list distinct scaffolds of the layout"));
+            n_bins += c->h_scaf_len[(size_t)ids[q]];
+        }
+        if (n_bins < 2) continue;                          // one bin: total 0.0 without asking the device
+        const uint8_t plus[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        rc = hicmi_p2_set_arrangement(c, ids, plus, k[j]);
+        if (rc) return drain(rc);
+        rc = arrangement_total_enqueue(c);
+        if (rc) return drain(rc);
+        phase[j] = TOTAL;
+    }
+    for (size_t j = 0; j < nj; j++) {
+        hicmi_ctx* c = ctxs[j];
+        if (sync_stream(c) != hipSuccess) return drain(fail(HICMI_EHIP, "hipStreamSynchronize failed in the start phase"));
+        if (phase[j] == TOTAL) memcpy(&total_out[j], c->pin_down, sizeof(double));
+    }
+    // ---- b. the brute force: every order and orientation of the k scaffolds (k == S: nothing lies outside the window)
+    std::vector<NearPending> np(nj);
+    for (size_t j = 0; j < nj; j++) {
+        hicmi_ctx* c = ctxs[j];
+        if (phase[j] != TOTAL || total_out[j] == 0.0) { phase[j] = IDLE; continue; }
+        const int64_t kj = k[j];
+        rc = hicmi_p2_window_tables(c, kj, orders[kj], n_orders[kj], orients[kj], n_orients[kj]);
+        if (rc) return drain(rc);
+        rc = check_window_call(c, 0, kj);
+        if (rc) return drain(rc);
+        use_total(c, total_out[j]);
+        if (kj >= c->near_min_k) {
+            double cur_fast = std::nan("");
+            rc = window_near_enqueue(c, 0, 1, kj, total_out[j], 0.0, cur_fast, kNearCap, np[j]);
+            phase[j] = NEAR;
+        } else {
+            rc = window_batch_enqueue(c, 0, 1, kj);
+            phase[j] = DELTA;
+        }
+        if (rc) return drain(rc);
+    }
+    std::vector<std::vector<int64_t>> near(nj);
+    std::vector<std::vector<double>> near_fast(nj);
+    for (size_t j = 0; j < nj; j++) {
+        hicmi_ctx* c = ctxs[j];
+        if (phase[j] == NEAR) {
+            std::vector<int64_t> n_near; std::vector<std::vector<int64_t>> nr; std::vector<std::vector<double>> nf;
+            rc = window_near_collect(c, np[j], n_near, nr, nf);
+            if (rc) return drain(rc);
+            if (n_near[0] <= kNearCap) { near[j].swap(nr[0]); near_fast[j].swap(nf[0]); phase[j] = LITERAL; continue; }
+            rc = window_batch_enqueue(c, 0, 1, k[j]);      // the list overflowed: the deltas, as hicmi_p2_decide_window does
+            if (rc) return drain(rc);
+            phase[j] = DELTA;
+        }
+        if (phase[j] == DELTA) {
+            if (sync_stream(c) != hipSuccess) return drain(fail(HICMI_EHIP, "hipStreamSynchronize failed in the start phase"));
+            if (window_c0(c, 0, k[j]) < 0) return drain(fail(HICMI_EINVAL, "current orientation not in the orientation table"));
+            const int64_t n_cand = c->n_orders * c->n_orients;
+            const double* delta = reinterpret_cast<const double*>(c->pin_down);
+            std::vector<double> fast((size_t)n_cand);
+            for (int64_t i = 0; i < n_cand; i++) fast[(size_t)i] = delta[(size_t)i] / total_out[j];
+            short_list(fast, 0.0, near[j]);
+            near_fast[j].resize(near[j].size());
+            for (size_t q = 0; q < near[j].size(); q++) near_fast[j][q] = fast[(size_t)near[j][q]];
+            phase[j] = LITERAL;
+        }
+    }
+    // ---- c. the short lists in the reference's operation order, then the first strict maximum above 0. (OG:464)
+    std::vector<LiteralPending> lp(nj);
+    for (size_t j = 0; j < nj; j++) {
+        if (phase[j] != LITERAL) continue;
+        std::vector<std::vector<int32_t>> rows;
+        near_rows(ctxs[j], 0, k[j], near[j], rows);
+        rc = literal_enqueue(ctxs[j], rows, total_out[j], lp[j]);
+        if (rc) return drain(rc);
+    }
+    for (size_t j = 0; j < nj; j++) {
+        if (phase[j] != LITERAL) continue;
+        std::vector<double> lit;
+        rc = literal_collect(ctxs[j], lp[j], lit);
+        if (rc) return drain(rc);
+        double pick_fast = 0.0;
+        pick_first_strict_max(near[j], near_fast[j], lit, 0.0, &pick_out[j], &cost_out[j], &pick_fast);
+        status_out[j] = pick_out[j] >= 0 ? DECIDED : NO_CANDIDATE;
+    }
+    return HICMI_OK;
 }
 
 // ---- plot support (plotContactMaps.py:15-91) --------------------------------------------------------

@@ -35,6 +35,8 @@ _PROFILE = bool(os.environ.get("HICMI_PART2_PROFILE"))   # per-chromosome wall c
 WORKERS = int(os.environ.get("HICMI_PART2_WORKERS", "8"))
 LOCKSTEP = os.environ.get("HICMI_PART2_LOCKSTEP", "1") != "0"   # all chromosomes' insertion loops in one queue of launches   # chromosomes ordered concurrently (1 = sequential)
 START_THREADS = int(os.environ.get("HICMI_PART2_START_THREADS", "0"))   # A/B: the start phase on this many threads (0: the calling thread)
+START_ALL = os.environ.get("HICMI_PART2_START_ALL", "1") != "0"   # A/B: every chromosome's start phase in ONE native call (0: one after the other)
+SCAN_ARRANGED = os.environ.get("HICMI_PART2_SCAN_ARRANGED", "1") != "0"   # A/B: the scan entered with the insertion's ids / rev (0: through Scaffold objects)
 NEAR_TOP = 1e-9        # relative band around a step's best fast score that is re-scored literally
 
 
@@ -62,7 +64,9 @@ class ChromosomeLayout:
     """All scaffolds of one chromosome selected on the device: scaffold s <-> a contiguous range of
     the selection holding its bins in ascending-ID ('+') order."""
 
-    def __init__(self, matrix: GenomeMatrix, scaffolds, binList):
+    def __init__(self, matrix: GenomeMatrix, scaffolds, binList, issue=True):
+        """``issue=False``: only the host side - the selection and the ranges are handed to the device by the caller
+        (hicmi_p2_start_all takes ``sel``, ``start`` and ``length`` of all chromosomes at once)."""
         self.ctx = matrix.ctx
         where = matrix.bin_index(binList)
         self.sid, self.start, self.length, self.names = {}, [], [], []
@@ -76,8 +80,10 @@ class ChromosomeLayout:
             sel.extend(map(where.__getitem__, bins))
             pos += len(bins)
         self.n = pos
-        self.ctx.p2_select(sel)
-        self.ctx.p2_layout(self.start, self.length)
+        self.sel = sel
+        if issue:
+            self.ctx.p2_select(sel)
+            self.ctx.p2_layout(self.start, self.length)
         self._tables_k = None
         self._pos_cache = {}
 
@@ -243,9 +249,9 @@ class Scaffold:
         self.binList = self.binList[::-1]
 
 
-def initiateBinsAndScaffolds(nodeList):
+def initiateBinsAndScaffolds(nodeList, quiet=False):
     """OG:256-280: scaffolds in order of first appearance, bins ascending, then a stable sort by
-    bin count, largest first."""
+    bin count, largest first.  ``quiet``: the caller prints the "Scaffolds to order" line itself."""
     bins_of = {}
     for bin_id, name in nodeList:
         b = bins_of.get(name)
@@ -254,7 +260,8 @@ def initiateBinsAndScaffolds(nodeList):
         else:
             b.append(bin_id)
     scaffDict = {name: Scaffold(name, sorted(b), "+") for name, b in bins_of.items()}      # (order of first appearance)
-    print("Scaffolds to order for this chromosome " + str(len(scaffDict)))
+    if not quiet:
+        print("Scaffolds to order for this chromosome " + str(len(scaffDict)))
     for s in scaffDict.values():
         s.nodeCount = len(s.binList)
     scaffList = sorted(scaffDict.values(), key=lambda s: len(s.binList), reverse=True)
@@ -394,6 +401,18 @@ def _enumeration(k):
         orients = plusMinusPerms(list(range(k)))
         _ENUM_CACHE[k] = (orders, orients, {tuple(r): i for i, r in enumerate(orients)})
     return _ENUM_CACHE[k][0], _ENUM_CACHE[k][1]
+
+
+_TABLE_CACHE = {}
+
+
+def _table_arrays(k):
+    """_enumeration(k) as the arrays the library takes: orders (int8), orientations (uint8, 1 = '-')."""
+    if k not in _TABLE_CACHE:
+        orders, orients = _enumeration(k)
+        _TABLE_CACHE[k] = (np.asarray(orders, dtype=np.int8),
+                           np.asarray([[1 if sg == "-" else 0 for sg in r] for r in orients], dtype=np.uint8))
+    return _TABLE_CACHE[k]
 
 
 def _orient_index(k, signs):
@@ -644,6 +663,104 @@ def _startChromosome(chromGroup, matrix: GenomeMatrix, binList, nScaffolds=6, sc
             "nScaffolds": nScaffolds, "scanScaffolds": scanScaffolds}
 
 
+def _start_all_applies(ctx):
+    """Every chromosome's start phase in one native call (hicmi_p2_start_all) unless a test wants to see every fast score
+    (SCORE_HOOK), the context is a test double without the call, or an A/B switch asks for the per-chromosome path."""
+    return START_ALL and START_THREADS == 0 and SCORE_HOOK is None and hasattr(ctx, "p2_start_all")
+
+
+def _startJobs(todo, chromList, lanes, binList, nScaffolds):
+    """Host side of the batched start phase: per chromosome of ``todo`` its scaffold grouping, its ChromosomeLayout
+    (nothing issued to the device) and the job tuple of ``Context.p2_start_all`` - (context, selection, scaffold starts,
+    scaffold lengths, ids of the scaffolds the brute force orders).  ``nScaffolds`` is already clipped to 8."""
+    prepared, jobs = {}, []
+    for i in todo:
+        scaffoldList, scaffoldDict = initiateBinsAndScaffolds(chromList[i], quiet=True)
+        layout = ChromosomeLayout(lanes[i], scaffoldList, binList, issue=False)
+        orderedScaffolds, scaffoldList = pullScaffolds([], scaffoldList, nScaffolds)
+        first_ids = [layout.sid[s.name] for s in orderedScaffolds]
+        prepared[i] = (layout, orderedScaffolds, scaffoldList, scaffoldDict)
+        jobs.append((lanes[i].ctx, layout.sel, layout.start, layout.length, first_ids))
+    return prepared, jobs
+
+
+def _startAll(todo, chromList, lanes, binList, nScaffolds=6, scanScaffolds=5):
+    """_startChromosome for every chromosome of ``todo`` with ONE native call: the same printed lines in the same order,
+    the same state per chromosome (the per-chromosome function stays the reference implementation of this one)."""
+    clipped = nScaffolds >= 9
+    if clipped:
+        nScaffolds = 8
+    if scanScaffolds > nScaffolds:
+        scanScaffolds = nScaffolds
+    tm = [time.perf_counter()]
+    prepared, jobs = _startJobs(todo, chromList, lanes, binList, nScaffolds)
+    tm.append(time.perf_counter())
+    results = lanes[todo[0]].ctx.p2_start_all(jobs, {k: _table_arrays(k) for k in {len(j[4]) for j in jobs}}) if jobs else []
+    tm.append(time.perf_counter())
+    states = {}
+    for i, (total, best, _bfScore, status) in zip(todo, results):
+        layout, orderedScaffolds, scaffoldList, scaffoldDict = prepared[i]
+        print("#####################\n#####################")
+        print("Working on Chr_" + str(i + 1) + "...")
+        if clipped:
+            print("Number of initial scaffolds to order by brute force method is set too high... setting it to 8")
+        print("Scaffolds to order for this chromosome " + str(len(scaffoldDict)))
+        lanes[i].chrom = layout
+        orderDict = _OrderDict(orderedScaffolds)
+        names = [s.name for s in orderedScaffolds]
+        k = len(names)
+        orders, orients = _enumeration(k)
+        if status == 1:                                  # OG:449: nothing is scored
+            print("WARNING/ERROR - Zero contact values found between scaffolds assigned to chromosome group "
+                  + ",".join(str(e) for e in names))
+            bfOrder, bfOrient = [names[j] for j in orders[0]], list(orients[0])
+        else:
+            print("Initial permutations to test " + str(len(orders) * len(orients)) + "...")
+            layout._tables_k = k
+            # the enumeration leaves every scaffold in the last candidate's orientation (OG:459)
+            reorderScaffList([names[j] for j in orders[-1]], orients[-1], scaffoldDict)
+            if best < 0:
+                raise RuntimeError("no candidate order scored above 0 (the reference fails here too, OG:473 -> OG:576)")
+            bfOrder, bfOrient = [names[j] for j in orders[best // len(orients)]], list(orients[best % len(orients)])
+        orderedScaffolds, _nodes = reorderScaffList(bfOrder, bfOrient, scaffoldDict)
+        states[i] = {"ordered": orderedScaffolds, "rest": scaffoldList, "dict": scaffoldDict, "orderDict": orderDict,
+                     "nScaffolds": nScaffolds, "scanScaffolds": scanScaffolds}
+    if _PROFILE:
+        tm.append(time.perf_counter())
+        sys.stderr.write("[hicmi] part2 start of %d chromosomes in one call (ms): scaffolds + flat arrays %.2f, native call %.2f, "
+                         "reorder %.2f\n" % ((len(todo),) + tuple((b - a) * 1e3 for a, b in zip(tm, tm[1:]))))
+    return states
+
+
+def _scan_arranged_applies(ctx):
+    return SCAN_ARRANGED and _fused(ctx) and hasattr(ctx, "p2_scan_arranged")
+
+
+def _finishArranged(state, ids, rev, bestCost, matrix: GenomeMatrix):
+    """_finishChromosome (OG:578-586) for a chromosome that is scanned, entered with the arrangement as the insertion
+    queue returned it: set-up, total (OG:506) and rounds are one native call (hicmi_p2_scan_arranged), and the Scaffold
+    objects are rebuilt once, after it.  The printed lines are those of _finishChromosome / scanOrdering."""
+    print("BestCost at the end of first two steps " + str(bestCost))
+    layout = matrix.chrom
+    w = state["scanScaffolds"]
+    orders, orients = _table_arrays(w)
+    ids, rev, bestCost, roundNumber, _total = layout.ctx.p2_scan_arranged(ids, rev, w, orders, orients, bestCost)
+    layout._tables_k = w
+    for r in range(roundNumber):
+        print("Working on round " + str(r + 1) + " of final step...")
+    del state["rest"][:]
+    orderedScaffolds, _nodes = reorderScaffList([layout.names[i] for i in ids], ["-" if r else "+" for r in rev], state["dict"])
+    print("Sliding window conversion after " + str(roundNumber) + " rounds")
+    print("Best cost at the end of the final step = " + str(bestCost))
+    if _PROFILE:
+        sys.stderr.write("[hicmi] part2 scan: %d scaffolds, %d rounds\n" % (len(ids), roundNumber))
+    print("Final ordering...")
+    for s in orderedScaffolds:
+        print(s.name, s.orientation)
+    orderChromosome.last_cost = bestCost
+    return orderedScaffolds
+
+
 def _finishChromosome(state, orderedScaffolds, bestCost, matrix: GenomeMatrix, binList):
     """OG:578-586: the sliding-window rounds and the final listing."""
     print("BestCost at the end of first two steps " + str(bestCost))
@@ -732,7 +849,11 @@ def orderGenome(matrix: GenomeMatrix, chromList, binList, resolution, nScaffolds
             # the start phase runs on THIS thread, one chromosome after the other: it is half interpreter work and half
             # short native calls, and threads that hand the interpreter lock to each other at every one of those calls
             # took 12-14 ms (16k) / 22-24 ms (32k) where the plain loop takes 7.7 / 13.5 ms
-            if START_THREADS > 0:
+            if _start_all_applies(matrix.ctx):
+                # ... and its native half as ONE call over all chromosomes (hicmi_p2_start_all): their kernels are queued
+                # behind each other on their own streams and waited for phase by phase
+                states = _startAll(todo, chromList, lanes, binList, nScaffolds, scanScaffolds)
+            elif START_THREADS > 0:
                 with ThreadPoolExecutor(max_workers=START_THREADS) as starters:
                     states = dict(starters.map(start, todo))
             else:
@@ -752,12 +873,16 @@ def orderGenome(matrix: GenomeMatrix, chromList, binList, resolution, nScaffolds
             def finish(i):
                 tf = time.perf_counter()
                 st = states[i]
-                if i in raw:
-                    ids, rev, best = raw[i]
-                    ordered = _insertion_result(ids, rev, st["ordered"], st["rest"], lanes[i])
-                else:                                                           # e.g. nothing left to add (OG:475-493)
-                    ordered, best = orderRemainderScaffolds(st["ordered"], st["rest"], st["orderDict"], lanes[i], binList)
-                res = _finishChromosome(st, ordered, best, lanes[i], binList)
+                if i in raw and len(raw[i][0]) > st["nScaffolds"] and _scan_arranged_applies(lanes[i].ctx):
+                    # scanned: the insertion's ids / rev go straight back into native code, Scaffold objects come afterwards
+                    res = _finishArranged(st, raw[i][0], raw[i][1], raw[i][2], lanes[i])
+                else:
+                    if i in raw:
+                        ids, rev, best = raw[i]
+                        ordered = _insertion_result(ids, rev, st["ordered"], st["rest"], lanes[i])
+                    else:                                                       # e.g. nothing left to add (OG:475-493)
+                        ordered, best = orderRemainderScaffolds(st["ordered"], st["rest"], st["orderDict"], lanes[i], binList)
+                    res = _finishChromosome(st, ordered, best, lanes[i], binList)
                 # this chromosome's lines of the two output files, formatted here - beside the other chromosomes' native scan
                 # calls - instead of for the whole genome at the very end (2.5 ms at 16k, 5 ms at 32k, nothing to hide behind)
                 text = (_scaffold_lines(res), _bin_rows(res))

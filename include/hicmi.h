@@ -301,6 +301,29 @@ int hicmi_p2_scan_all(hicmi_ctx *ctx, int32_t *ids, uint8_t *rev, int64_t S, int
 int hicmi_p2_insert_all_multi(int64_t n_jobs, hicmi_ctx *const *ctxs, int32_t *const *ids, uint8_t *const *rev,
                               const int64_t *S0, const int32_t *const *new_ids, const int64_t *n_new, double *best_out);
 
+/* The start of n_jobs chromosomes (OG:551-576 up to and including the brute force) in one call, one context each, all on
+ * one device: for job j what hicmi_p2_select, hicmi_p2_layout, hicmi_p2_set_arrangement, hicmi_p2_arrangement_total,
+ * hicmi_p2_window_tables and hicmi_p2_decide_window(0, k, total, 0., NaN) do, with the same results bit for bit and the
+ * same state left in the context, but phase by phase over all jobs: a phase is queued on every job's stream before any
+ * of them is waited for.
+ * Flat inputs, job after job: sel (n_sel[j] matrix rows: the bins scaffold by scaffold, ascending), scaf_start / scaf_len
+ * (n_scaf[j] ranges of that selection), first_ids (the k[j] scaffolds the brute force orders, all '+'; 1 <= k[j] <= 8,
+ * k[j] <= n_scaf[j]).  orders[k] / orients[k] with n_orders[k] / n_orients[k] rows, k = 0 .. 8: the tables of
+ * hicmi_p2_window_tables for every k that occurs (unused entries may be NULL).
+ * Outputs per job: total_out (OG:448), status_out = 0 decided: pick_out = winning candidate (order index * n_orients +
+ * orientation index), cost_out its literal cost; 1: total is 0 ("Zero contact values found", nothing was scored);
+ * 2: no candidate scored above 0 (pick_out = -1).  Must not run concurrently with other calls on the contexts. */
+int hicmi_p2_start_all(int64_t n_jobs, hicmi_ctx *const *ctxs, const int32_t *sel, const int64_t *n_sel,
+                       const int32_t *scaf_start, const int32_t *scaf_len, const int64_t *n_scaf, const int32_t *first_ids,
+                       const int64_t *k, const int8_t *const *orders, const int64_t *n_orders, const uint8_t *const *orients,
+                       const int64_t *n_orients, double *total_out, int64_t *pick_out, double *cost_out, int32_t *status_out);
+/* scanOrdering (OG:495-549) entered with the arrangement as the insertion calls return it: sets it, takes its total in
+ * exactly that order (OG:506; *total_out), loads the window tables for k unless they are the loaded ones, then runs
+ * hicmi_p2_scan_all from *best_io.  ids / rev updated in place. */
+int hicmi_p2_scan_arranged(hicmi_ctx *ctx, int32_t *ids, uint8_t *rev, int64_t S, int64_t k, const int8_t *orders,
+                           int64_t n_orders, const uint8_t *orients, int64_t n_orients, double *total_out, double *best_io,
+                           int64_t *rounds_out);
+
 /* Placement support of a finished ordering.  For one chromosome: its selection and layout (hicmi_p2_select,
  * hicmi_p2_layout), its final arrangement A = (ids, rev) of S scaffolds and ONE total (the caller's: the literal total
  * of the layout in layout order, every scaffold '+', so that all scores of a chromosome are on one footing).
