@@ -59,6 +59,20 @@ class GenomeMatrix:
             self._bin_index_src = binList
         return self._bin_index
 
+    def lanes(self, count):
+        """This matrix and ``count`` - 1 more on worker contexts (own HIP stream, own scratch) that read the same
+        device-resident contacts and share the bin index: one per job in flight."""
+        out = [self] + [GenomeMatrix(c) for c in self.ctx.workers(count - 1)]
+        for m in out[1:]:
+            m._bin_index, m._bin_index_src = self._bin_index, self._bin_index_src
+        return out
+
+    def select(self, layout):
+        """Make ``layout`` the chromosome selected on the device again (a context that served several layouts in turn)."""
+        if self.chrom is not layout:
+            layout.issue()
+            self.chrom = layout
+
 
 class ChromosomeLayout:
     """All scaffolds of one chromosome selected on the device: scaffold s <-> a contiguous range of
@@ -81,11 +95,24 @@ class ChromosomeLayout:
             pos += len(bins)
         self.n = pos
         self.sel = sel
-        if issue:
-            self.ctx.p2_select(sel)
-            self.ctx.p2_layout(self.start, self.length)
-        self._tables_k = None
         self._pos_cache = {}
+        self._tables_k = None
+        if issue:
+            self.issue()
+
+    def issue(self):
+        self.ctx.p2_select(self.sel)
+        self.ctx.p2_layout(self.start, self.length)
+        self._tables_k = None
+
+    def whole_total(self):
+        """The total of the whole selection: every scaffold in layout order, '+' (the one footing on which different
+        arrangements of the chromosome compare)."""
+        if self.n < 2:
+            return 0.0
+        S = len(self.start)
+        self.ctx.p2_set_arrangement(np.arange(S, dtype=np.int32), np.zeros(S, np.uint8))
+        return self.ctx.p2_arrangement_total()
 
     def covers(self, scaffs):
         return all(s.name in self.sid for s in scaffs)
@@ -247,6 +274,11 @@ class Scaffold:
     def flipOrientation(self):
         self.orientation = "-" if self.orientation == "+" else "+"
         self.binList = self.binList[::-1]
+
+    def copy(self):
+        out = Scaffold(self.name, list(self.binList), self.orientation)
+        out.nodeCount = getattr(self, "nodeCount", len(self.binList))
+        return out
 
 
 def initiateBinsAndScaffolds(nodeList, quiet=False):
@@ -582,18 +614,10 @@ def scanOrdering(orderedScaffolds, scaffoldDict, orderDict, matrix: GenomeMatrix
         layout = adjMat.layout
         layout.tables(w)
         ids, rev = layout.describe(orderedScaffolds)
-        if hasattr(adjMat.ctx, "p2_scan_all"):
-            # the whole loop as one native call (the interpreter lock is free for the other chromosomes meanwhile)
-            ids, rev, bestCost, cur_fast, roundNumber = adjMat.ctx.p2_scan_all(ids, rev, w, total, bestCost, cur_fast)
-            for r in range(roundNumber):
-                print("Working on round " + str(r + 1) + " of final step...")
-        else:
-            while True:
-                print("Working on round " + str(roundNumber + 1) + " of final step...")
-                ids, rev, bestCost, cur_fast, improved = adjMat.ctx.p2_scan_pass(ids, rev, w, total, bestCost, cur_fast)
-                roundNumber += 1
-                if not improved:
-                    break
+        # the whole loop as one native call (the interpreter lock is free for the other chromosomes meanwhile)
+        ids, rev, bestCost, cur_fast, roundNumber = adjMat.ctx.p2_scan_all(ids, rev, w, total, bestCost, cur_fast)
+        for r in range(roundNumber):
+            print("Working on round " + str(r + 1) + " of final step...")
         orderedScaffolds, _nodes = reorderScaffList([layout.names[i] for i in ids], ["-" if r else "+" for r in rev],
                                                     scaffoldDict)
         print("Sliding window conversion after " + str(roundNumber) + " rounds")
@@ -605,18 +629,12 @@ def scanOrdering(orderedScaffolds, scaffoldDict, orderDict, matrix: GenomeMatrix
         improved = False
         print("Working on round " + str(roundNumber + 1) + " of final step...")
         for i in range(0, len(orderedScaffolds) - w + 1):
-            if _fused(adjMat.ctx):
-                adjMat.layout.tables(w)
-                adjMat.ctx.p2_set_arrangement(*adjMat.layout.describe(orderedScaffolds))
-                pick, bestCost, cur_fast = adjMat.ctx.p2_decide_window(i, w, total, bestCost, cur_fast)
-                fast = None
-            else:
-                if cur_fast is None:
-                    ids, rev = adjMat.layout.describe(orderedScaffolds)
-                    adjMat.ctx.p2_set_arrangement(ids, rev)
-                    cur_fast = adjMat.ctx.p2_arrangement_score(total)
-                fast, row_of = _window_scores(adjMat, orderedScaffolds, i, w, known_fast=cur_fast)
-                pick, bestCost = adjMat.first_strict_max(fast, bestCost, row_of)   # strict '>' vs the global best (OG:535)
+            if cur_fast is None:
+                ids, rev = adjMat.layout.describe(orderedScaffolds)
+                adjMat.ctx.p2_set_arrangement(ids, rev)
+                cur_fast = adjMat.ctx.p2_arrangement_score(total)
+            fast, row_of = _window_scores(adjMat, orderedScaffolds, i, w, known_fast=cur_fast)
+            pick, bestCost = adjMat.first_strict_max(fast, bestCost, row_of)   # strict '>' vs the global best (OG:535)
             if pick >= 0:
                 improved = True
                 o, r = orders[pick // len(orients)], orients[pick % len(orients)]
@@ -625,8 +643,7 @@ def scanOrdering(orderedScaffolds, scaffoldDict, orderDict, matrix: GenomeMatrix
                 outside = {s.name: s.orientation for s in orderedScaffolds}
                 bestOrder = names[:i] + [window[j].name for j in o] + names[i + w:]
                 bestOrientation = ([outside[nm] for nm in names[:i]] + list(r) + [outside[nm] for nm in names[i + w:]])
-                if fast is not None:
-                    cur_fast = float(fast[pick])
+                cur_fast = float(fast[pick])
             orderedScaffolds, _nodes = reorderScaffList(bestOrder, bestOrientation, scaffoldDict)
         roundNumber += 1
         if not improved:
@@ -669,62 +686,80 @@ def _start_all_applies(ctx):
     return START_ALL and START_THREADS == 0 and SCORE_HOOK is None and hasattr(ctx, "p2_start_all")
 
 
-def _startJobs(todo, chromList, lanes, binList, nScaffolds):
-    """Host side of the batched start phase: per chromosome of ``todo`` its scaffold grouping, its ChromosomeLayout
-    (nothing issued to the device) and the job tuple of ``Context.p2_start_all`` - (context, selection, scaffold starts,
-    scaffold lengths, ids of the scaffolds the brute force orders).  ``nScaffolds`` is already clipped to 8."""
-    prepared, jobs = {}, []
+def _uncaptured(fn, *args):
+    """The ``capture`` of a plain run: what ``fn`` prints goes to stdout as it is."""
+    return fn(*args), None
+
+
+def _startOne(c, width, chromList, lane, binList):
+    """One start job, chromosome ``c`` at brute-force width ``width``, by the per-chromosome calls."""
+    print("#####################\n#####################")
+    print("Working on Chr_" + str(c + 1) + "...")
+    return _startChromosome(chromList[c], lane, binList, width, width)
+
+
+def _startJobs(todo, chromList, lanes, binList, nScaffolds, jobs=None):
+    """Host side of the batched start phase: per job of ``todo`` its scaffold grouping, its ChromosomeLayout (nothing
+    issued to the device) and the job tuple of ``Context.p2_start_all`` - (context, selection, scaffold starts, scaffold
+    lengths, ids of the scaffolds the brute force orders).  A job is a chromosome index at the width ``nScaffolds``
+    (already clipped to 8), or, with ``jobs``, a key of it: ``jobs[key]`` = (chromosome index, width)."""
+    prepared, out = {}, []
     for i in todo:
-        scaffoldList, scaffoldDict = initiateBinsAndScaffolds(chromList[i], quiet=True)
+        c, width = (i, nScaffolds) if jobs is None else jobs[i]
+        scaffoldList, scaffoldDict = initiateBinsAndScaffolds(chromList[c], quiet=True)
         layout = ChromosomeLayout(lanes[i], scaffoldList, binList, issue=False)
-        orderedScaffolds, scaffoldList = pullScaffolds([], scaffoldList, nScaffolds)
+        orderedScaffolds, scaffoldList = pullScaffolds([], scaffoldList, min(width, 8))
         first_ids = [layout.sid[s.name] for s in orderedScaffolds]
         prepared[i] = (layout, orderedScaffolds, scaffoldList, scaffoldDict)
-        jobs.append((lanes[i].ctx, layout.sel, layout.start, layout.length, first_ids))
-    return prepared, jobs
+        out.append((lanes[i].ctx, layout.sel, layout.start, layout.length, first_ids))
+    return prepared, out
 
 
-def _startAll(todo, chromList, lanes, binList, nScaffolds=6, scanScaffolds=5):
-    """_startChromosome for every chromosome of ``todo`` with ONE native call: the same printed lines in the same order,
-    the same state per chromosome (the per-chromosome function stays the reference implementation of this one)."""
-    clipped = nScaffolds >= 9
-    if clipped:
-        nScaffolds = 8
-    if scanScaffolds > nScaffolds:
-        scanScaffolds = nScaffolds
+def _started(c, width, scanScaffolds, lane, prepared, result):
+    """What _startOne prints and returns, for a job whose native half hicmi_p2_start_all has done."""
+    layout, orderedScaffolds, scaffoldList, scaffoldDict = prepared
+    total, best, _bfScore, status = result
+    print("#####################\n#####################")
+    print("Working on Chr_" + str(c + 1) + "...")
+    if width >= 9:
+        print("Number of initial scaffolds to order by brute force method is set too high... setting it to 8")
+    print("Scaffolds to order for this chromosome " + str(len(scaffoldDict)))
+    lane.chrom = layout
+    orderDict = _OrderDict(orderedScaffolds)
+    names = [s.name for s in orderedScaffolds]
+    k = len(names)
+    orders, orients = _enumeration(k)
+    if status == 1:                                  # OG:449: nothing is scored
+        print("WARNING/ERROR - Zero contact values found between scaffolds assigned to chromosome group "
+              + ",".join(str(e) for e in names))
+        bfOrder, bfOrient = [names[j] for j in orders[0]], list(orients[0])
+    else:
+        print("Initial permutations to test " + str(len(orders) * len(orients)) + "...")
+        layout._tables_k = k
+        # the enumeration leaves every scaffold in the last candidate's orientation (OG:459)
+        reorderScaffList([names[j] for j in orders[-1]], orients[-1], scaffoldDict)
+        if best < 0:
+            raise RuntimeError("no candidate order scored above 0 (the reference fails here too, OG:473 -> OG:576)")
+        bfOrder, bfOrient = [names[j] for j in orders[best // len(orients)]], list(orients[best % len(orients)])
+    orderedScaffolds, _nodes = reorderScaffList(bfOrder, bfOrient, scaffoldDict)
+    return {"ordered": orderedScaffolds, "rest": scaffoldList, "dict": scaffoldDict, "orderDict": orderDict,
+            "nScaffolds": min(width, 8), "scanScaffolds": min(scanScaffolds, width, 8)}
+
+
+def _startAll(todo, chromList, lanes, binList, nScaffolds=6, scanScaffolds=5, jobs=None, capture=None):
+    """_startOne for every job of ``todo`` (see _startJobs) with ONE native call: the same printed lines in the same order,
+    the same state per job (the per-chromosome function stays the reference implementation of this one).  Returns
+    {job: state}, or with ``capture`` {job: (state, the job's lines)}."""
     tm = [time.perf_counter()]
-    prepared, jobs = _startJobs(todo, chromList, lanes, binList, nScaffolds)
+    prepared, calls = _startJobs(todo, chromList, lanes, binList, nScaffolds, jobs)
     tm.append(time.perf_counter())
-    results = lanes[todo[0]].ctx.p2_start_all(jobs, {k: _table_arrays(k) for k in {len(j[4]) for j in jobs}}) if jobs else []
+    results = lanes[todo[0]].ctx.p2_start_all(calls, {k: _table_arrays(k) for k in {len(j[4]) for j in calls}}) if calls else []
     tm.append(time.perf_counter())
+    call = capture or (lambda fn, *args: fn(*args))
     states = {}
-    for i, (total, best, _bfScore, status) in zip(todo, results):
-        layout, orderedScaffolds, scaffoldList, scaffoldDict = prepared[i]
-        print("#####################\n#####################")
-        print("Working on Chr_" + str(i + 1) + "...")
-        if clipped:
-            print("Number of initial scaffolds to order by brute force method is set too high... setting it to 8")
-        print("Scaffolds to order for this chromosome " + str(len(scaffoldDict)))
-        lanes[i].chrom = layout
-        orderDict = _OrderDict(orderedScaffolds)
-        names = [s.name for s in orderedScaffolds]
-        k = len(names)
-        orders, orients = _enumeration(k)
-        if status == 1:                                  # OG:449: nothing is scored
-            print("WARNING/ERROR - Zero contact values found between scaffolds assigned to chromosome group "
-                  + ",".join(str(e) for e in names))
-            bfOrder, bfOrient = [names[j] for j in orders[0]], list(orients[0])
-        else:
-            print("Initial permutations to test " + str(len(orders) * len(orients)) + "...")
-            layout._tables_k = k
-            # the enumeration leaves every scaffold in the last candidate's orientation (OG:459)
-            reorderScaffList([names[j] for j in orders[-1]], orients[-1], scaffoldDict)
-            if best < 0:
-                raise RuntimeError("no candidate order scored above 0 (the reference fails here too, OG:473 -> OG:576)")
-            bfOrder, bfOrient = [names[j] for j in orders[best // len(orients)]], list(orients[best % len(orients)])
-        orderedScaffolds, _nodes = reorderScaffList(bfOrder, bfOrient, scaffoldDict)
-        states[i] = {"ordered": orderedScaffolds, "rest": scaffoldList, "dict": scaffoldDict, "orderDict": orderDict,
-                     "nScaffolds": nScaffolds, "scanScaffolds": scanScaffolds}
+    for i, result in zip(todo, results):
+        c, width = (i, nScaffolds) if jobs is None else jobs[i]
+        states[i] = call(_started, c, width, scanScaffolds, lanes[i], prepared[i], result)
     if _PROFILE:
         tm.append(time.perf_counter())
         sys.stderr.write("[hicmi] part2 start of %d chromosomes in one call (ms): scaffolds + flat arrays %.2f, native call %.2f, "
@@ -782,6 +817,113 @@ def orderChromosome(chromGroup, matrix: GenomeMatrix, binList, nScaffolds=6, sca
     return _finishChromosome(state, orderedScaffolds, bestCost, matrix, binList)
 
 
+def _finishJob(state, after, scanScaffolds, lane, binList, own):
+    """One scan job from where its start job's insertion ended - ``after`` is (ids, rev, bestCost) as the lock step returned
+    them, or (Scaffold objects, bestCost) from orderRemainderScaffolds: the sliding-window rounds, the final listing and the
+    chromosome's text in the two output files, formatted here, beside the other lanes' native scan calls.  ``own``: the start
+    job has other scans too, and a scan flips Scaffold objects in place, so this one works on copies."""
+    if own:
+        mine = {name: s.copy() for name, s in state["dict"].items()}
+        state = dict(state, dict=mine, **{k: [mine[s.name] for s in state[k]] for k in ("ordered", "rest")})
+        if len(after) == 2:
+            after = ([mine[s.name] for s in after[0]], after[1])
+    state = dict(state, scanScaffolds=state["nScaffolds"] if scanScaffolds is None else min(scanScaffolds, state["nScaffolds"]))
+    if len(after) == 3 and len(after[0]) > state["nScaffolds"] and _scan_arranged_applies(lane.ctx):
+        # scanned: the insertion's ids / rev go straight back into native code (which works on copies of them), Scaffold
+        # objects come afterwards
+        res = _finishArranged(state, after[0], after[1], after[2], lane)
+    else:
+        if len(after) == 3:
+            after = (_insertion_result(after[0], after[1], state["ordered"], state["rest"], lane), after[2])
+        res = _finishChromosome(state, after[0], after[1], lane, binList)
+    return res, (_scaffold_lines(res), _bin_rows(res))
+
+
+def orderJobs(matrix: GenomeMatrix, chromList, binList, starts, scans, workers, capture=_uncaptured, on_native_phase=None):
+    """Part 2's three phases over any set of jobs: a -part2 run is one start and one scan job per chromosome, a sweep
+    (sweepPart2.py) shares start jobs between settings.
+
+    ``starts``: [(chromosome index, brute-force width)] - selection, brute force and insertion, each job on a lane of its
+    own.  ``scans``: [(index into starts, scanScaffolds or None for the width)] - the sliding-window rounds (when the
+    chromosome has more scaffolds than the width) and the final listing; the scans of one start job run one after the other
+    on its lane.  Phases: (1) every start job, on this thread, in one native call where that applies; (2) every insertion loop in
+    lock step, decided on the device - one queue of launches serving all of them (hicmi_p2_insert_all_multi); (3) the scans
+    on ``workers`` threads.  A context without worker lanes or the lock step (a test double; SCORE_HOOK) runs the same
+    steps one start job after the other on the one context.
+
+    ``capture(fn, *args) -> (result, lines)`` wraps everything that prints a job's lines.  Returns
+    ([(lane, layout, lines) per start job], [((scaffolds, (_scaffold_lines, _bin_rows)), lines) per scan job])."""
+    t0 = time.perf_counter()
+    matrix.bin_index(binList)
+    ctx = matrix.ctx
+    lockstep = SCORE_HOOK is None and hasattr(ctx, "workers") and hasattr(ctx, "p2_insert_all_multi")
+    lanes = matrix.lanes(len(starts)) if lockstep else [matrix] * len(starts)
+    todo = sorted(range(len(starts)), key=lambda j: -len(chromList[starts[j][0]]))             # largest first
+    by_start = {}
+    for s, (j, _w) in enumerate(scans):
+        by_start.setdefault(j, []).append(s)
+    started, raw, finished = [None] * len(starts), {}, [None] * len(scans)
+    marks = [time.perf_counter()]
+    if _PROFILE:
+        sys.stderr.write("[hicmi] part2 set-up (bin index, one context per chromosome): %.1f ms\n" % ((marks[0] - t0) * 1e3))
+
+    def start(j):
+        state, lines = capture(_startOne, starts[j][0], starts[j][1], chromList, lanes[j], binList)
+        started[j] = (state, lanes[j].chrom, lines)
+
+    def finish(j):
+        state, lane = started[j][0], lanes[j]
+        after = raw.get(j)
+        if after is None:                                        # e.g. nothing left to add (OG:475-493)
+            after = orderRemainderScaffolds(state["ordered"], state["rest"], state["orderDict"], lane, binList)
+        for s in by_start.get(j, ()):
+            tf = time.perf_counter()
+            finished[s] = capture(_finishJob, state, after, scans[s][1], lane, binList, len(by_start[j]) > 1)
+            if _PROFILE:
+                c = starts[j][0]
+                sys.stderr.write("[hicmi] part2 scan of chromosome %d (%d bins): start +%.1f ms, %.1f ms\n"
+                                 % (c + 1, len(chromList[c]), (tf - marks[-1]) * 1e3, (time.perf_counter() - tf) * 1e3))
+
+    if not lockstep:
+        for j in range(len(starts)):
+            start(j)
+            finish(j)
+    else:
+        # the start phase runs on THIS thread, one job after the other: it is half interpreter work and half short native
+        # calls, and threads that hand the interpreter lock to each other at every one of those calls took 12-14 ms (16k) /
+        # 22-24 ms (32k) where the plain loop takes 7.7 / 13.5 ms
+        if _start_all_applies(ctx):
+            # ... and its native half as ONE call over all jobs (hicmi_p2_start_all): their kernels are queued behind each
+            # other on their own streams and waited for phase by phase
+            for j, (state, lines) in _startAll(todo, chromList, lanes, binList, jobs=starts, capture=capture).items():
+                started[j] = (state, lanes[j].chrom, lines)
+        elif START_THREADS > 0:
+            with ThreadPoolExecutor(max_workers=START_THREADS) as starters:
+                list(starters.map(start, todo))
+        else:
+            for j in todo:
+                start(j)
+        marks.append(time.perf_counter())
+        jobs, job_of = [], []
+        for j in todo:
+            job = _insertion_job(started[j][0]["ordered"], started[j][0]["rest"], lanes[j])
+            if job is not None:
+                jobs.append((lanes[j].ctx,) + job)
+                job_of.append(j)
+        if on_native_phase is not None:
+            on_native_phase()                     # a long native call follows: background Python work may take the GIL
+        raw.update(zip(job_of, ctx.p2_insert_all_multi(jobs)))     # (turned into scaffold lists by the scan threads)
+        marks.append(time.perf_counter())
+        with ThreadPoolExecutor(max_workers=max(1, min(workers, len(by_start)))) as pool:
+            list(pool.map(finish, todo))
+        marks.append(time.perf_counter())
+        if _PROFILE:
+            sys.stderr.write("[hicmi] part2 lock step: start %.1f ms, insertion %.1f ms (%d chromosomes), scan %.1f ms\n"
+                             % ((marks[1] - marks[0]) * 1e3, (marks[2] - marks[1]) * 1e3, len(jobs),
+                                (marks[3] - marks[2]) * 1e3))
+    return [(lanes[j], layout, lines) for j, (_state, layout, lines) in enumerate(started)], finished
+
+
 def chromosomesOfRank(chromList, rank, world):
     """The chromosomes one rank orders when a single map is spread over ``world`` processes: largest first, each
     to the rank with the least work so far (work ~ bins squared, the size of the chromosome's sub-matrix; ties go
@@ -812,7 +954,6 @@ def orderGenome(matrix: GenomeMatrix, chromList, binList, resolution, nScaffolds
     orderGenome.file_text = None
     indices = list(range(len(chromList))) if shard is None else chromosomesOfRank(chromList, shard[0], shard[1])
     n_workers = 1 if SCORE_HOOK is not None else max(1, min(WORKERS, len(indices)))
-    matrix.bin_index(binList)
 
     def one(i, m):
         print("#####################\n#####################")
@@ -829,81 +970,16 @@ def orderGenome(matrix: GenomeMatrix, chromList, binList, resolution, nScaffolds
     if n_workers == 1 or not hasattr(matrix.ctx, "workers"):
         done = {i: one(i, matrix) for i in indices}
     elif LOCKSTEP and hasattr(matrix.ctx, "p2_insert_all_multi"):
-        # Three phases over ALL chromosomes, one context each: (1) selection + brute force on worker threads,
-        # (2) every chromosome's insertion loop in lock step, decided on the device - one queue of launches
-        # serving all of them (hicmi_p2_insert_all_multi), (3) the sliding-window rounds on worker threads.
-        lanes = [matrix] + [GenomeMatrix(c) for c in matrix.ctx.workers(len(indices) - 1)]
-        for m in lanes[1:]:
-            m._bin_index, m._bin_index_src = matrix._bin_index, matrix._bin_index_src
-        lanes = dict(zip(indices, lanes))
-        todo = sorted(indices, key=lambda i: -len(chromList[i]))                    # largest first
-        marks = [time.perf_counter()]
-        if _PROFILE:
-            sys.stderr.write("[hicmi] part2 set-up (bin index, one context per chromosome): %.1f ms\n" % ((marks[0] - t0p) * 1e3))
-
-        def start(i):
-            print("#####################\n#####################")
-            print("Working on Chr_" + str(i + 1) + "...")
-            return i, _startChromosome(chromList[i], lanes[i], binList, nScaffolds, scanScaffolds)
-        with ThreadPoolExecutor(max_workers=n_workers) as pool:
-            # the start phase runs on THIS thread, one chromosome after the other: it is half interpreter work and half
-            # short native calls, and threads that hand the interpreter lock to each other at every one of those calls
-            # took 12-14 ms (16k) / 22-24 ms (32k) where the plain loop takes 7.7 / 13.5 ms
-            if _start_all_applies(matrix.ctx):
-                # ... and its native half as ONE call over all chromosomes (hicmi_p2_start_all): their kernels are queued
-                # behind each other on their own streams and waited for phase by phase
-                states = _startAll(todo, chromList, lanes, binList, nScaffolds, scanScaffolds)
-            elif START_THREADS > 0:
-                with ThreadPoolExecutor(max_workers=START_THREADS) as starters:
-                    states = dict(starters.map(start, todo))
-            else:
-                states = dict(map(start, todo))
-            marks.append(time.perf_counter())
-            jobs, job_of = [], []
-            for i in todo:
-                job = _insertion_job(states[i]["ordered"], states[i]["rest"], lanes[i])
-                if job is not None:
-                    jobs.append((lanes[i].ctx,) + job)
-                    job_of.append(i)
-            if on_native_phase is not None:
-                on_native_phase()                     # a long native call follows: background Python work may take the GIL
-            raw = dict(zip(job_of, matrix.ctx.p2_insert_all_multi(jobs)))     # (turned into scaffold lists by the scan threads)
-            marks.append(time.perf_counter())
-
-            def finish(i):
-                tf = time.perf_counter()
-                st = states[i]
-                if i in raw and len(raw[i][0]) > st["nScaffolds"] and _scan_arranged_applies(lanes[i].ctx):
-                    # scanned: the insertion's ids / rev go straight back into native code, Scaffold objects come afterwards
-                    res = _finishArranged(st, raw[i][0], raw[i][1], raw[i][2], lanes[i])
-                else:
-                    if i in raw:
-                        ids, rev, best = raw[i]
-                        ordered = _insertion_result(ids, rev, st["ordered"], st["rest"], lanes[i])
-                    else:                                                       # e.g. nothing left to add (OG:475-493)
-                        ordered, best = orderRemainderScaffolds(st["ordered"], st["rest"], st["orderDict"], lanes[i], binList)
-                    res = _finishChromosome(st, ordered, best, lanes[i], binList)
-                # this chromosome's lines of the two output files, formatted here - beside the other chromosomes' native scan
-                # calls - instead of for the whole genome at the very end (2.5 ms at 16k, 5 ms at 32k, nothing to hide behind)
-                text = (_scaffold_lines(res), _bin_rows(res))
-                if _PROFILE:
-                    sys.stderr.write("[hicmi] part2 scan of chromosome %d (%d bins): start +%.1f ms, %.1f ms\n"
-                                     % (i + 1, len(chromList[i]), (tf - marks[2]) * 1e3, (time.perf_counter() - tf) * 1e3))
-                return i, (res, text)
-            finished = dict(pool.map(finish, todo))
-            done = {i: v[0] for i, v in finished.items()}
-            if shard is None:
-                pieces = {i: v[1] for i, v in finished.items()}
-        marks.append(time.perf_counter())
-        if _PROFILE:
-            sys.stderr.write("[hicmi] part2 lock step: start %.1f ms, insertion %.1f ms (%d chromosomes), scan %.1f ms\n"
-                             % ((marks[1] - marks[0]) * 1e3, (marks[2] - marks[1]) * 1e3, len(jobs),
-                                (marks[3] - marks[2]) * 1e3))
+        # one start job and one scan job per chromosome, all in flight together (orderJobs)
+        _started_jobs, finished = orderJobs(matrix, chromList, binList, [(i, nScaffolds) for i in indices],
+                                            [(k, scanScaffolds) for k in range(len(indices))], n_workers,
+                                            on_native_phase=on_native_phase)
+        done = {i: res for i, ((res, _text), _lines) in zip(indices, finished)}
+        if shard is None:
+            pieces = {i: text for i, ((_res, text), _lines) in zip(indices, finished)}
     else:
-        lanes = [matrix] + [GenomeMatrix(c) for c in matrix.ctx.workers(n_workers - 1)]
-        for m in lanes[1:]:
-            m._bin_index, m._bin_index_src = matrix._bin_index, matrix._bin_index_src
-        free = list(lanes)
+        matrix.bin_index(binList)
+        free = matrix.lanes(n_workers)
         todo = sorted(indices, key=lambda i: -len(chromList[i]))                    # largest first
 
         def run(i):
@@ -1152,11 +1228,7 @@ def placementSupport(matrix: GenomeMatrix, orderedChromosomes, binList, chromLis
     matrix.bin_index(binList)
     direct = os.environ.get("HICMI_P2_SUPPORT_DIRECT", "") not in ("", "0")
     multi = not direct and SCORE_HOOK is None and hasattr(ctx, "workers") and hasattr(ctx, "p2_support_multi")
-    lanes = [matrix]
-    if multi and len(orderedChromosomes) > 1:
-        lanes += [GenomeMatrix(x) for x in ctx.workers(len(orderedChromosomes) - 1)]
-        for m in lanes[1:]:
-            m._bin_index, m._bin_index_src = matrix._bin_index, matrix._bin_index_src
+    lanes = matrix.lanes(len(orderedChromosomes)) if multi and len(orderedChromosomes) > 1 else [matrix]
     out = []
     for c0 in range(0, len(orderedChromosomes), len(lanes)):
         jobs = []
@@ -1168,11 +1240,7 @@ def placementSupport(matrix: GenomeMatrix, orderedChromosomes, binList, chromLis
             else:
                 order = sorted(group, key=lambda s: len(s.binList), reverse=True)
             layout = lane.chrom = ChromosomeLayout(lane, order, binList)
-            S0 = len(layout.start)
-            total = 0.0
-            if layout.n >= 2:
-                layout.ctx.p2_set_arrangement(np.arange(S0, dtype=np.int32), np.zeros(S0, np.uint8))
-                total = layout.ctx.p2_arrangement_total()
+            total = layout.whole_total()
             ids, rev = layout.describe(group)
             jobs.append((layout, ids, rev, total, group))
         if direct:

@@ -4,16 +4,19 @@
            [-chromosomeGroupFile FILE] [-device 0] [-out DIR] [-plots] [-support]
 
 The map is read once (the grouped bins only, as ``-part2`` reads it).  The settings are the distinct pairs after
-_startChromosome's clamps (nScaffolds >= 9 -> 8, scanScaffolds > nScaffolds -> nScaffolds).  Chromosomes are ordered
+orderGenome._startChromosome's clamps (nScaffolds >= 9 -> 8, scanScaffolds > nScaffolds -> nScaffolds).  Chromosomes are ordered
 independently (OG:608-612), and per chromosome of S scaffolds the work is shared between settings:
 
 * S <= nScaffolds: brute force over all S scaffolds, the do-while re-insertion of the last one (OG:475-493), no scan -
   one job for every such setting;
 * S > nScaffolds: selection, brute force and insertion depend on nScaffolds alone, only the scan on scanScaffolds.
 
-Phases: one context and layout per (chromosome, brute-force width); the brute force of each; all insertion loops in one
-hicmi_p2_insert_all_multi lock step; the scans on a pool of HICMI_PART2_WORKERS threads, each from its own copy of the
-insertion result.  Contexts without those entry points run the same steps one after the other on the one context.
+The jobs go through the one Part 2 driver, orderGenome.orderJobs, which a ``-part2`` run uses for its one-setting grid:
+one lane (context and layout) per (chromosome, brute-force width); every start phase in one hicmi_p2_start_all call; all
+insertion loops in one hicmi_p2_insert_all_multi lock step; the scans on a pool of HICMI_PART2_WORKERS threads, entered
+through hicmi_p2_scan_arranged, each on its own copy of the insertion result.  Contexts without those entry points run
+the same steps one after the other on the one context.  What is left here is the plan, each job's printed lines, and
+final_score.
 
 ``DIR/nScaffolds<a>_scanScaffolds<b>/`` holds the chromosomeOrderFile and plotOrderFile (config base names) that
 ``-part2`` writes with that setting and ``part2.log`` with the lines a one-worker ``-part2`` run prints from "Chromosomes
@@ -35,7 +38,6 @@ import os
 import sys
 import threading
 import time
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -47,7 +49,6 @@ from .sweepPart1 import parse_values
 
 SUMMARY_COLUMNS = ["nScaffolds", "scanScaffolds", "chromosomes", "chromosomes_scanned", "scan_rounds", "best_for",
                    "final_scores"]
-HEADER = "#####################\n#####################"
 
 
 def clamp(nScaffolds, scanScaffolds):
@@ -149,36 +150,29 @@ def _lines(fn, *args, **kw):
     return res, buf.getvalue().splitlines()
 
 
-def _copy_scaffolds(ordered):
-    """Fresh Scaffold objects (a scan flips them in place) and their name dictionary."""
-    out = []
-    for s in ordered:
-        t = p2.Scaffold(s.name, list(s.binList), s.orientation)
-        t.nodeCount = getattr(s, "nodeCount", len(s.binList))
-        out.append(t)
-    return out, {s.name: s for s in out}
-
-
-def _native(ctx):
-    return (p2.SCORE_HOOK is None and hasattr(ctx, "workers") and hasattr(ctx, "p2_insert_all_multi")
-            and hasattr(ctx, "p2_decide_window"))
-
-
-class _Start:
-    """One (chromosome, brute-force width) job: its lane (GenomeMatrix with the chromosome's layout), the state
-    _startChromosome returns, the lines it printed, then the insertion result."""
-
-    def __init__(self, lane):
-        self.lane, self.state, self.lines, self.ordered, self.best = lane, None, [], None, None
-
-
-def _final_score(lane, ordered, total):
-    layout = lane.chrom
-    ids, rev = layout.describe(ordered)
-    row = layout.node_row(ids, rev)
-    if len(row) < 2:
-        return 0.0
-    return float(lane.ctx.p2_score_exact(np.ascontiguousarray(row, dtype=np.int32)[None, :], total)[0])
+def _final_scores(started, finished, start_of_scan, chromosome_of):
+    """final_score of every scan job: the literal objective of its final bin order under ONE total per chromosome, that of
+    the chromosome's whole selection.  One hicmi_p2_score_exact call per start job, over the distinct final orders of its
+    scans that no earlier job of the chromosome ended with."""
+    totals, cache, key_of = {}, {}, [None] * len(finished)
+    scans_of = [[] for _ in started]
+    for s, j in enumerate(start_of_scan):
+        scans_of[j].append(s)
+    for (lane, layout, _lines), c, mine in zip(started, chromosome_of, scans_of):
+        lane.select(layout)                              # (a context without worker lanes has served other layouts since)
+        if c not in totals:
+            totals[c] = layout.whole_total()
+        rows = {}
+        for s in mine:
+            ids, rev = layout.describe(finished[s][0][0])
+            key_of[s] = (c, ids.tobytes() + rev.tobytes())
+            if key_of[s] not in cache:
+                rows[key_of[s]] = layout.node_row(ids, rev)
+        if rows:
+            vals = [0.0] * len(rows) if layout.n < 2 else \
+                lane.ctx.p2_score_exact(np.stack(list(rows.values())).astype(np.int32), totals[c])
+            cache.update(zip(rows, map(float, vals)))
+    return [cache[k] for k in key_of]
 
 
 def order_settings(matrix, chromList, binList, grid, workers=None, report=print):
@@ -186,111 +180,40 @@ def order_settings(matrix, chromList, binList, grid, workers=None, report=print)
     the work shared as the module docstring says.  Returns a dict with, per setting, per chromosome: 'orders' (scaffold
     lists), 'lines' (what a one-worker -part2 run prints for it), 'scores' (final_score), 'rounds', 'scanned'; and
     'counts' (jobs requested / run)."""
-    workers = p2.WORKERS if workers is None else workers
-    matrix.bin_index(binList)
     counts = [len({name for _b, name in chrom}) for chrom in chromList]
     starts, scans, per_setting = plan(counts, grid)
     n_jobs = len(grid) * len(chromList)
     report("- Part 2 sweep plan: %d settings x %d chromosomes = %d orderings; brute force + insertion jobs: %d requested / "
            "%d run; scan jobs: %d requested / %d run" % (len(grid), len(chromList), n_jobs, n_jobs, len(starts), n_jobs,
                                                          len(scans)))
-    native = _native(matrix.ctx)
-    start_of = {}
-    totals = {}
-    finals = {}                                          # scan key -> (ordered scaffolds, lines, rounds, scanned, text)
-    score_cache = {}
-
-    def start(sk):
-        c, width = sk
-        job = start_of[sk]
-        job.state, job.lines = _lines(p2._startChromosome, chromList[c], job.lane, binList, width, width)
-        if c not in totals:
-            # one total per chromosome: its whole selection, i.e. every scaffold in layout order, forward
-            layout = job.lane.chrom
-            S = len(layout.start)
-            job.lane.ctx.p2_set_arrangement(np.arange(S, dtype=np.int32), np.zeros(S, np.uint8))
-            totals[c] = job.lane.ctx.p2_arrangement_total() if layout.n >= 2 else 0.0
-
-    def finish_plain(sk):
-        job = start_of[sk]
-        st = job.state
-        job.ordered, job.best = p2.orderRemainderScaffolds(st["ordered"], st["rest"], st["orderDict"], job.lane, binList)
-
-    def scan(fk):
-        sk = scans[fk]
-        job = start_of[sk]
-        c = sk[0]
-        ordered, sdict = _copy_scaffolds(job.ordered)
-        st = dict(job.state, dict=sdict, nScaffolds=sk[1] if fk[2] is None else fk[1],
-                  scanScaffolds=sk[1] if fk[2] is None else fk[2])
-        res, lines = _lines(p2._finishChromosome, st, ordered, job.best, job.lane, binList)
-        rounds = sum(1 for ln in lines if ln.startswith("Working on round "))
-        key = b"".join(np.asarray(job.lane.chrom.describe(res)[i]).tobytes() for i in (0, 1))
-        if (c, key) not in score_cache:
-            score_cache[(c, key)] = _final_score(job.lane, res, totals[c])
-        finals[fk] = (res, lines, rounds, fk[2] is not None, (p2._scaffold_lines(res), p2._bin_rows(res)),
-                      score_cache[(c, key)])
-
+    start_keys, scan_keys = list(starts), list(scans)
+    start_of_scan = [start_keys.index(scans[fk]) for fk in scan_keys]
     t0 = time.time()
-    if native:
-        lanes = [matrix] + [p2.GenomeMatrix(x) for x in matrix.ctx.workers(len(starts) - 1)]
-        for m in lanes[1:]:
-            m._bin_index, m._bin_index_src = matrix._bin_index, matrix._bin_index_src
-        for sk, lane in zip(starts, lanes):
-            start_of[sk] = _Start(lane)
-        for sk in starts:
-            start(sk)
-        jobs, job_keys = [], []
-        for sk in starts:
-            st = start_of[sk].state
-            job = p2._insertion_job(st["ordered"], st["rest"], start_of[sk].lane)
-            if job is not None:
-                jobs.append((start_of[sk].lane.ctx,) + job)
-                job_keys.append(sk)
-        raw = dict(zip(job_keys, matrix.ctx.p2_insert_all_multi(jobs))) if jobs else {}
-        for sk in starts:
-            job, st = start_of[sk], start_of[sk].state
-            if sk in raw:
-                ids, rev, job.best = raw[sk]
-                job.ordered = p2._insertion_result(ids, rev, st["ordered"], st["rest"], job.lane)
-            else:
-                finish_plain(sk)
-        # scans of one start job share its lane: they run one after the other on one thread
-        by_start = {}
-        for fk, sk in scans.items():
-            by_start.setdefault(sk, []).append(fk)
-        real = sys.stdout
-        sys.stdout = _ThreadOut(real)
-        try:
-            with ThreadPoolExecutor(max_workers=max(1, min(workers, len(by_start)))) as pool:
-                list(pool.map(lambda sk: [scan(fk) for fk in by_start[sk]],
-                              sorted(by_start, key=lambda sk: -len(chromList[sk[0]]))))
-        finally:
-            sys.stdout = real
-    else:
-        # the same steps on the one context, one start job (layout) after the other
-        for sk in starts:
-            start_of[sk] = _Start(matrix)
-            start(sk)
-            finish_plain(sk)
-            for fk, s in scans.items():
-                if s == sk:
-                    scan(fk)
+    real = sys.stdout
+    sys.stdout = _ThreadOut(real)                        # the scan threads' lines, job by job (_lines)
+    try:
+        started, finished = p2.orderJobs(matrix, chromList, binList, start_keys,
+                                         [(j, fk[2]) for j, fk in zip(start_of_scan, scan_keys)],
+                                         p2.WORKERS if workers is None else workers, capture=_lines)
+    finally:
+        sys.stdout = real
+    scores = _final_scores(started, finished, start_of_scan, [sk[0] for sk in start_keys])
     report("- Part 2 sweep: %d brute-force / insertion jobs and %d scans in %.3f s" % (len(starts), len(scans),
                                                                                       time.time() - t0))
     out = {"orders": [], "lines": [], "scores": [], "rounds": [], "scanned": [], "text": [],
            "counts": {"orderings": n_jobs, "start_jobs": len(starts), "scan_jobs": len(scans)},
-           "start_keys": list(starts), "scan_keys": list(scans)}
+           "start_keys": start_keys, "scan_keys": scan_keys}
+    scan_index = {fk: s for s, fk in enumerate(scan_keys)}
     for keys in per_setting:
         o, ln, sc, rd, sd, tx = [], [], [], [], [], []
-        for c, fk in enumerate(keys):
-            res, lines, rounds, scanned, text, score = finals[fk]
-            sk = scans[fk]
+        for fk in keys:
+            s = scan_index[fk]
+            (res, text), lines = finished[s]
             o.append(res)
-            ln.append([*HEADER.split("\n"), "Working on Chr_" + str(c + 1) + "...", *start_of[sk].lines, *lines])
-            sc.append(score)
-            rd.append(rounds)
-            sd.append(scanned)
+            ln.append([*started[start_of_scan[s]][2], *lines])
+            sc.append(scores[s])
+            rd.append(sum(1 for line in lines if line.startswith("Working on round ")))
+            sd.append(fk[2] is not None)
             tx.append(text)
         for k, v in zip(("orders", "lines", "scores", "rounds", "scanned", "text"), (o, ln, sc, rd, sd, tx)):
             out[k].append(v)

@@ -375,3 +375,38 @@ def test_sweep_equals_separate_runs(case, tmp_path, monkeypatch):
                 order = [where[b] for s in res["orders"][si][ci] for b in s.binList]
                 lit = orc.cost_literal_rows(c, np.asarray([order], np.int32), total)[0]
                 assert rows[si]["final_scores"][ci] == res["scores"][si][ci] == float(lit), (g, ci)
+
+
+def test_sweep_takes_the_batched_calls(tmp_path, monkeypatch):
+    """The sweep runs on the driver of a -part2 run, so on a real context it reaches hicmi_p2_start_all and
+    hicmi_p2_scan_arranged; with both switched off it reaches neither and writes the same tree, file for file."""
+    from hic_genome_assembler_amd import _lib, orderGenome as p2, sweepPart2 as sw, synth
+    lay = synth.make_layout(1800, seed=18, n_chrom=4, mean_scaffold_bins=13.0)
+    paths = synth.write_hicpro(str(tmp_path / "in"), lay, _contacts(lay, 18), "d")
+    groups = _groups_file(tmp_path / "groups.txt", lay)
+    calls = []
+    start_all, scan_arranged = _lib.Context.p2_start_all, _lib.Context.p2_scan_arranged
+    monkeypatch.setattr(_lib.Context, "p2_start_all",
+                        staticmethod(lambda jobs, tables: (calls.append("start_all"), start_all(jobs, tables))[1]))
+    monkeypatch.setattr(_lib.Context, "p2_scan_arranged",
+                        lambda self, *a: (calls.append("scan_arranged"), scan_arranged(self, *a))[1])
+    trees = {}
+    for batched in (True, False):
+        monkeypatch.setattr(p2, "START_ALL", batched)
+        monkeypatch.setattr(p2, "SCAN_ARRANGED", batched)
+        del calls[:]
+        out = tmp_path / ("sweep%d" % batched)
+        with contextlib.redirect_stdout(io.StringIO()):
+            res = sw.runSweep(paths["hicProBedFile"], paths["hicProBiasFile"], paths["hicProMatrixFile"], groups,
+                              "chromosomeOrders.txt", "plotOrder.txt", [4, 6], [3, 5], str(out))
+        assert res["grid"] == [(4, 3), (4, 4), (6, 3), (6, 5)]
+        if batched:
+            assert calls.count("start_all") == 1                 # every start job of the sweep in the one call
+            assert calls.count("scan_arranged") == sum(1 for fk in res["scan_keys"] if fk[2] is not None) > 0
+        else:
+            assert calls == []
+        trees[batched] = {os.path.relpath(os.path.join(d, f), str(out)): open(os.path.join(d, f)).read()
+                          for d, _dirs, files in os.walk(str(out)) for f in files}
+    assert sorted(trees[True]) == sorted(trees[False]) and len(trees[True]) == 3 * 4 + 2 + 2
+    for name in trees[True]:
+        assert trees[True][name] == trees[False][name], name
