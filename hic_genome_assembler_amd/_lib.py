@@ -38,6 +38,7 @@ SIGNATURES = {
     "hicmi_set_row_shard": (ctypes.c_int, [_vp, c_i64, c_i64]),
     "hicmi_set_row_sums": (ctypes.c_int, [_vp, _vp, _vp]),
     "hicmi_compact": (ctypes.c_int, [_vp, _vp, c_i64]),
+    "hicmi_group_sums": (ctypes.c_int, [_vp, _vp, _vp, c_i64, c_i64, _vp, _vp]),
     "hicmi_upgma": (ctypes.c_int, [_vp, _vp, _vp]),
     "hicmi_rank_matrix": (ctypes.c_int, [_vp, _vp]),
     "hicmi_presort_state": (ctypes.c_int, [_vp, _vp, _vp]),
@@ -289,6 +290,19 @@ class Context:
         keep = np.ascontiguousarray(keep, dtype=np.int32)
         _check(self._lib.hicmi_compact(self._h, _ptr(keep), len(keep)))
         self.n = len(keep)
+
+    def group_sums(self, grp, scaf, n_groups, n_scaffolds, want_bins=True):
+        """Group support sums (hicmi_group_sums): (bin sums n x n_groups or None, scaffold sums
+        n_scaffolds x n_groups) for the group label (-1: none) and the dense scaffold id of every bin."""
+        g = np.ascontiguousarray(grp, dtype=np.int32)
+        s = np.ascontiguousarray(scaf, dtype=np.int32)
+        if g.shape != (self.n,) or s.shape != (self.n,):
+            raise ValueError("grp and scaf must have n entries")
+        bins = np.empty((self.n, int(n_groups)), np.float64) if want_bins else None
+        scaffolds = np.empty((int(n_scaffolds), int(n_groups)), np.float64)
+        _check(self._lib.hicmi_group_sums(self._h, _ptr(g), _ptr(s), int(n_groups), int(n_scaffolds), _ptr(bins),
+                                          _ptr(scaffolds)))
+        return bins, scaffolds
 
     # ---- Part 1
     def upgma(self, want_linkage: bool = True):

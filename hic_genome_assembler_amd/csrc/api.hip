@@ -133,6 +133,9 @@ struct hicmi_ctx {
     unsigned char* d_ins_blob = nullptr; int64_t ins_blob_cap = 0;   // per job: [InsState][InsLog x steps]
     InsStep* d_ins_steps = nullptr; int64_t ins_steps_cap = 0;       // [step][job] records of a lock-step queue
     SupRec* d_sup_recs = nullptr; int64_t sup_recs_cap = 0;          // hicmi_p2_support_multi: (chromosome, left-out scaffold) records
+    // group support (k_group_support.hip): the member lists of a call, and its partials + the two tables
+    int32_t* d_gs_lists = nullptr; int64_t gs_lists_cap = 0;
+    double* d_gs_sums = nullptr; int64_t gs_sums_cap = 0;
     // HMM boundary finder (k_hmm.hip): resident observation matrices, one per slot (T x ld, columns [0, D) in use);
     // the selected slot's view is mirrored in d_hx / hmm_T / hmm_ld / hmm_D for the single-problem entry points.  The
     // work areas are sized for the largest slot built
@@ -373,6 +376,7 @@ int hicmi_destroy(hicmi_ctx* c)
     free_dev(c->d_G); free_dev(c->d_delta); free_dev(c->d_wb); free_dev(c->d_wnear);
     free_dev(c->d_arr_packed2); free_dev(c->d_pos2sel2); free_dev(c->d_ins_T); free_dev(c->d_ins_partial);
     free_dev(c->d_ins_blob); free_dev(c->d_ins_steps); free_dev(c->d_sup_recs);
+    free_dev(c->d_gs_lists); free_dev(c->d_gs_sums);
     free_dev(c->d_plot_order); free_dev(c->d_plot_work); free_dev(c->d_plot_img);
     for (auto& sl : c->hslot) free_dev(sl.d_x);
     free_dev(c->d_hmulti); free_dev(c->d_horder); free_dev(c->d_hwork); free_dev(c->d_hlab); free_dev(c->d_hbt);
@@ -532,6 +536,68 @@ int hicmi_compact(hicmi_ctx* c, const int32_t* keep, int64_t n_keep)
     int rc = alloc_sums(c);
     if (rc) return rc;
     return compute_sums(c);
+}
+
+// Group support: extends the scaffold vote of assessChromosomeClustering (S2C:1001-1077) with the
+// contacts themselves.  The host sorts the grouped rows by group and cuts them into chunks of GS_CHUNK; the kernels of
+// k_group_support.hip read every grouped row once.
+int hicmi_group_sums(hicmi_ctx* c, const int32_t* grp, const int32_t* scaf, int64_t n_groups, int64_t n_scaffolds,
+                     double* bin_sums_out, double* scaffold_sums_out)
+{
+    if (!c || !grp || !scaf || !scaffold_sums_out) return fail(HICMI_EINVAL, "NULL argument");
+    if (!c->dC) return fail(HICMI_EINVAL, "no contact matrix set");
+    if (n_groups < 1 || n_groups > 65536) return fail(HICMI_EINVAL, "n_groups = %lld outside 1 .. 65536", (long long)n_groups);
+    if (n_scaffolds < 1 || n_scaffolds > INT_MAX / 2) return fail(HICMI_EINVAL, "n_scaffolds = %lld out of range", (long long)n_scaffolds);
+    const int64_t n = c->n, G = n_groups, S = n_scaffolds;
+    std::vector<int32_t> gcount(G + 1, 0), soff(S + 1, 0);
+    for (int64_t i = 0; i < n; i++) {
+        if (grp[i] < -1 || grp[i] >= G) return fail(HICMI_EINVAL, "grp[%lld] = %d outside -1 .. %lld", (long long)i, grp[i], (long long)(G - 1));
+        if (scaf[i] < 0 || scaf[i] >= S) return fail(HICMI_EINVAL, "scaf[%lld] = %d outside 0 .. %lld", (long long)i, scaf[i], (long long)(S - 1));
+        if (grp[i] >= 0) gcount[grp[i] + 1]++;
+        soff[scaf[i] + 1]++;
+    }
+    for (int64_t g = 0; g < G; g++) gcount[g + 1] += gcount[g];
+    for (int64_t s = 0; s < S; s++) soff[s + 1] += soff[s];
+    const int64_t R = gcount[G];
+    // one host image of every list: [chunks][rows][group_chunk0][scaf][sbins][soff]
+    std::vector<GsChunk> chunks;
+    std::vector<int32_t> gc0(G + 1, 0);
+    for (int64_t g = 0; g < G; g++) {
+        gc0[g] = (int32_t)chunks.size();
+        for (int32_t r0 = gcount[g]; r0 < gcount[g + 1]; r0 += GS_CHUNK)
+            chunks.push_back({r0, std::min<int32_t>(GS_CHUNK, gcount[g + 1] - r0), (int32_t)g, 0});
+    }
+    gc0[G] = (int32_t)chunks.size();
+    const int64_t NC = (int64_t)chunks.size();
+    const int64_t o_rows = 4 * NC, o_gc0 = o_rows + R, o_scaf = o_gc0 + G + 1, o_sbins = o_scaf + n, o_soff = o_sbins + n,
+                  n_ints = o_soff + S + 1;
+    std::vector<int32_t> img((size_t)n_ints);
+    if (NC) memcpy(img.data(), chunks.data(), sizeof(GsChunk) * (size_t)NC);
+    {
+        std::vector<int32_t> gfill(gcount.begin(), gcount.end() - 1), sfill(soff.begin(), soff.end() - 1);
+        for (int64_t i = 0; i < n; i++) {                  // ascending i: ascending rows inside a group, bin-list order inside a scaffold
+            if (grp[i] >= 0) img[(size_t)(o_rows + gfill[grp[i]]++)] = (int32_t)i;
+            img[(size_t)(o_sbins + sfill[scaf[i]]++)] = (int32_t)i;
+        }
+    }
+    memcpy(&img[(size_t)o_gc0], gc0.data(), sizeof(int32_t) * (size_t)(G + 1));
+    memcpy(&img[(size_t)o_scaf], scaf, sizeof(int32_t) * (size_t)n);
+    memcpy(&img[(size_t)o_soff], soff.data(), sizeof(int32_t) * (size_t)(S + 1));
+    const char* env = getenv("HICMI_GROUP_SUPPORT_PLAIN");
+    const bool plain = env && !strcmp(env, "1");
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t o_bin = plain ? 0 : NC * n, o_sc = o_bin + n * G, n_dbl = o_sc + S * G;
+    int rc = ensure(c->d_gs_lists, c->gs_lists_cap, n_ints);
+    if (!rc) rc = ensure(c->d_gs_sums, c->gs_sums_cap, n_dbl);
+    if (!rc) rc = upload(c, c->d_gs_lists, img.data(), sizeof(int32_t) * (size_t)n_ints);
+    if (rc) return rc;
+    const int32_t* L = c->d_gs_lists;
+    launch_group_sums(c->dC, c->ldc, (int)n, (int)G, (int)S, L + o_rows, reinterpret_cast<const GsChunk*>(L), (int)NC, L + o_gc0,
+                      L + o_scaf, L + o_sbins, L + o_soff, c->d_gs_sums, c->d_gs_sums + o_bin, c->d_gs_sums + o_sc, plain,
+                      c->stream);
+    HIPCHK(hipGetLastError());
+    if (bin_sums_out) { rc = download(c, bin_sums_out, c->d_gs_sums + o_bin, sizeof(double) * (size_t)(n * G)); if (rc) return rc; }
+    return download(c, scaffold_sums_out, c->d_gs_sums + o_sc, sizeof(double) * (size_t)(S * G));
 }
 
 int hicmi_selftest_division(hicmi_ctx* c, uint64_t seed, int64_t samples, uint64_t* mismatches_out)

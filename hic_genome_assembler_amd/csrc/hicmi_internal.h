@@ -377,6 +377,15 @@ struct SupRec {
 };
 void launch_sup(const SupRec* recs, int n_rec, int max_S, int max_n, double near_top, hipStream_t s);
 
+// k_group_support.hip: group support (hicmi_group_sums).  rows: the grouped rows sorted by group, ascending inside a
+// group; chunks[c]: rows[row0 .. row0 + cnt) with cnt <= GS_CHUNK, all of one group; group_chunk0[g] .. [g + 1]: the
+// chunks of group g; sbins / soff: the bins sorted by scaffold.  partial: n_chunks x n, binsum: n x G, scafsum: S x G.
+static constexpr int GS_CHUNK = 64;           // member rows per chunk: part of the definition
+struct GsChunk { int32_t row0, cnt, group, pad; };
+void launch_group_sums(const double* C, int64_t ld, int n, int G, int S, const int32_t* rows, const GsChunk* chunks,
+                       int n_chunks, const int32_t* group_chunk0, const int32_t* scaf, const int32_t* sbins,
+                       const int32_t* soff, double* partial, double* binsum, double* scafsum, bool plain, hipStream_t s);
+
 // k_plot.hip
 void launch_plot_select(const double* C, int64_t ldc, const double* np_sum, const double* seq_sum, int kind,
                         const int32_t* order, int n_sel, int n_targets, struct SelectState* d_state, unsigned int* d_hist,

@@ -62,7 +62,9 @@ _SPEC = [
 ]
 _BY_KEY = {k: (kind, prefix) for k, _d, kind, prefix in _SPEC}
 # keys a config may leave out: absent from the returned dictionary unless the file sets them
-_OPTIONAL = {"placementSupportFile": "saveFilesDirectory"}     # -part2 also writes the placement-support report there
+_OPTIONAL = {"placementSupportFile": "saveFilesDirectory",     # -part2 also writes the placement-support report there
+             "groupSupportFile": "saveFilesDirectory",         # -part1 also writes the group-support report there
+             "rescuedChromosomeGroupFile": "saveFilesDirectory"}   # ... and the group file with the rescued scaffolds
 
 
 def _convert(values, key, text):
@@ -184,7 +186,8 @@ def main(argv=None):
                                      v["binGroupFile"], v["assessmentFile"], v["chromosomeGroupFile"],
                                      v["hyperGeom"], v["hmm"], v["minSize"], v["modularity"], v["louvainRounds"],
                                      v["psig"], v["convergenceRounds"], v["lookAhead"], v["resolution"], device=args.device,
-                                     keep_resident=keep)
+                                     keep_resident=keep,
+                                     **{k: v[k] for k in ("groupSupportFile", "rescuedChromosomeGroupFile") if k in v})
     if args.part2:
         from . import orderGenome as part2
         part2.runPipeline(v["hicProBedFile"], v["hicProBiasFile"], v["hicProMatrixFile"], v["chromosomeGroupFile"],

@@ -870,12 +870,177 @@ def writeChromosomeGroupingsToFile(chromList, scaffSizeDict, outFile, entry_line
 
 
 # ------------------------------------------------------------------------------------------------
+# Group support: the contacts' own evidence for the scaffold vote of assessChromosomeClustering.
+def readScaffoldBinCounts(hicProBedFile):
+    """{scaffold: number of bins in the bed}, in order of first appearance (bins with a NaN bias included)."""
+    counts = {}
+    with open(hicProBedFile) as fh:
+        for line in fh:
+            name = line.split("\t", 1)[0]
+            counts[name] = counts.get(name, 0) + 1
+    return counts
+
+
+def _run_lengths(labels):
+    """'3:12,7:9' for 12 labels '3' followed by 9 labels '7'; 'NA' for none."""
+    out, k = [], 0
+    while k < len(labels):
+        j = k + 1
+        while j < len(labels) and labels[j] == labels[k]:
+            j += 1
+        out.append(labels[k] + ":" + str(j - k))
+        k = j
+    return ",".join(out) if out else "NA"
+
+
+def groupSupport(matrix, binList, chromList, scaffoldBins, minRatio=3.0):
+    """One record per scaffold of ``scaffoldBins`` ({scaffold: bins in the bed}, bed order): how densely its bins touch
+    every chromosome group of ``chromList`` (orderGenome.readChromsFromFile's groups) in the resident map whose rows are
+    ``binList``, zero rows compacted away or not.  The sums come from the device (hicmi_group_sums).
+
+    Record: scaffold, bins, live_bins (present with a non-zero row), assigned / best / second (group indices or None),
+    best_density, second_density, ratio, verdict (supported, contested, rescued, ambiguous, no_contacts), runs (the
+    per-bin best group, run-length encoded with 1-based group numbers), density (one value per group), live_ids."""
+    names = list(scaffoldBins)
+    sid = {name: k for k, name in enumerate(names)}
+    n, G, S = len(binList), len(chromList), len(names)
+    if G < 1 or n != matrix.ctx.n:
+        raise ValueError("groupSupport needs at least one group and the bins of the matrix rows")
+    ids = np.fromiter((b.ID for b in binList), dtype=np.int64, count=n)
+    scaf = np.fromiter((sid[b.chrom] for b in binList), dtype=np.int32, count=n)
+    np_sum = getattr(matrix, "np_sum", None)
+    if np_sum is None or len(np_sum) != n:
+        np_sum = matrix.ctx.row_sums()[0]
+    live = np.asarray(np_sum) != 0
+    label = {int(e[0]): g for g, group in enumerate(chromList) for e in group}
+    grp = np.fromiter((label.get(i, -1) for i in ids.tolist()), dtype=np.int32, count=n)
+    grp[~live] = -1                                        # a label on a zero row is ignored: compaction changes nothing
+    binsum, scafsum = matrix.ctx.group_sums(grp, scaf, G, S, want_bins=True)
+    labelled = grp >= 0
+    m = np.bincount(grp[labelled], minlength=G).astype(np.int64)
+    own = np.zeros((S, G), dtype=np.int64)
+    np.add.at(own, (scaf[labelled], grp[labelled]), 1)
+    L = np.bincount(scaf[live], minlength=S).astype(np.int64)
+    pairs = L[:, None] * (m[None, :] - own)
+    density = np.divide(scafsum, pairs, out=np.zeros_like(scafsum), where=pairs != 0)
+    by_id = np.argsort(ids, kind="stable")
+    bins_of = [[] for _ in range(S)]
+    for i in by_id[live[by_id]].tolist():
+        bins_of[scaf[i]].append(i)
+    records = []
+    for s, name in enumerate(names):
+        d, rows = density[s], bins_of[s]
+        rec = {"scaffold": name, "bins": int(scaffoldBins[name]), "live_bins": int(L[s]),
+               "assigned": int(np.argmax(own[s])) if own[s].any() else None,
+               "best": None, "best_density": None, "second": None, "second_density": None, "ratio": None,
+               "density": d.tolist(), "live_ids": [int(ids[i]) for i in rows]}
+        if L[s] == 0 or not d.any():
+            rec["verdict"] = "no_contacts"
+        else:
+            best = int(np.argmax(d))                       # numpy.argmax: the lowest index among equals
+            rec["best"], rec["best_density"], rec["ratio"] = best, float(d[best]), float("inf")
+            if G > 1:
+                rest = d.copy()
+                rest[best] = -np.inf
+                second = int(np.argmax(rest))
+                rec["second"], rec["second_density"] = second, float(d[second])
+                if d[second] != 0.0:
+                    rec["ratio"] = float(d[best] / d[second])
+            if rec["assigned"] is not None:
+                rec["verdict"] = "supported" if best == rec["assigned"] else "contested"
+            else:
+                rec["verdict"] = "rescued" if rec["ratio"] >= minRatio else "ambiguous"
+        if rows:
+            denom = (m - own[s])[None, :]
+            v = np.divide(binsum[rows], denom, out=np.zeros((len(rows), G)), where=denom != 0)
+            side = [str(a + 1) if hit else "-" for a, hit in zip(v.argmax(axis=1).tolist(), v.any(axis=1).tolist())]
+        else:
+            side = []
+        rec["runs"] = _run_lengths(side)
+        records.append(rec)
+    return records
+
+
+def _gs_text(v):
+    return "NA" if v is None else (repr(v) if isinstance(v, float) else str(v))
+
+
+def _gs_group(g):
+    return None if g is None else g + 1
+
+
+def groupSupportText(records):
+    """The report: a '#' header line, then one tab-separated line per scaffold in bed order.  Groups are the file's
+    1-based numbers, floats are written with repr, a missing value is NA."""
+    text = ["#scaffold\tbins\tlive_bins\tassigned\tbest\tbest_density\tsecond\tsecond_density\tratio\tverdict\truns\n"]
+    for r in records:
+        text.append("\t".join([r["scaffold"], str(r["bins"]), str(r["live_bins"]), _gs_text(_gs_group(r["assigned"])),
+                               _gs_text(_gs_group(r["best"])), _gs_text(r["best_density"]), _gs_text(_gs_group(r["second"])),
+                               _gs_text(r["second_density"]), _gs_text(r["ratio"]), r["verdict"], r["runs"]]) + "\n")
+    return "".join(text)
+
+
+def writeGroupSupportToFile(records, outFile, fullDir=None):
+    """groupSupportText to ``outFile``; ``fullDir``: also the S x G density table as ``groupSupport.full.tsv``."""
+    _write_text(outFile, groupSupportText(records))
+    if fullDir:
+        os.makedirs(fullDir, exist_ok=True)
+        G = len(records[0]["density"]) if records else 0
+        with open(os.path.join(fullDir, "groupSupport.full.tsv"), "w") as fh:
+            fh.write("\t".join(["scaffold"] + ["group%d" % (g + 1) for g in range(G)]) + "\n")
+            for r in records:
+                fh.write("\t".join([r["scaffold"]] + [repr(float(v)) for v in r["density"]]) + "\n")
+    print("Group support written for scaffolds " + str(len(records)))
+
+
+def writeRescuedGroupsToFile(records, chromosomeGroupFile, outFile):
+    """``chromosomeGroupFile`` again - its groups in its order and numbering, every line verbatim - with, after each
+    group's own lines, the present non-zero-row bins of the scaffolds rescued into it as ``binID<TAB>scaffold`` (scaffolds
+    in bed order, bins ascending).  One pass: the rescued scaffolds were scored against the input's groups only.
+    Returns the number of rescued scaffolds."""
+    with open(chromosomeGroupFile) as fh:
+        lines = fh.read().splitlines(keepends=True)
+    groups = []                                            # the first line is group 1's header (orderGenome.readChromsFromFile)
+    for k, line in enumerate(lines):
+        if k == 0 or line[0] == "#":
+            groups.append([line])
+        else:
+            groups[-1].append(line)
+    rescued = [r for r in records if r["verdict"] == "rescued"]
+    text = []
+    for g, group in enumerate(groups):
+        if not group[-1].endswith("\n"):
+            group[-1] += "\n"
+        text.extend(group)
+        for r in rescued:
+            if r["best"] == g:
+                text.extend(str(b) + "\t" + r["scaffold"] + "\n" for b in r["live_ids"])
+    _write_text(outFile, "".join(text))
+    print("Scaffolds rescued into chromosome groups " + str(len(rescued)))
+    return len(rescued)
+
+
+def groupSupportToFiles(matrix, binList, chromList, hicProBedFile, chromosomeGroupFile, groupSupportFile=None,
+                        rescuedChromosomeGroupFile=None, minRatio=3.0, fullDir=None):
+    """groupSupport of a resident map and the files wanted of it; returns the records."""
+    records = groupSupport(matrix, binList, chromList, readScaffoldBinCounts(hicProBedFile), minRatio=minRatio)
+    if groupSupportFile:
+        writeGroupSupportToFile(records, groupSupportFile, fullDir)
+    if rescuedChromosomeGroupFile:
+        writeRescuedGroupsToFile(records, chromosomeGroupFile, rescuedChromosomeGroupFile)
+    return records
+
+
+# ------------------------------------------------------------------------------------------------
 def runPipeline(hicProBedFile, hicProBiasFile, hicProMatrixFile, hicProScaffSizeFile,
                 dendrogramOrderFile, avgClusterPlot, avgClusterPlot_outlined,
                 binGroupFile, assessmentFile, chromosomeGroupFile,
                 hyperGeom, hmm, minSize, modularity, louvainRounds,
-                psig, convergenceRounds, lookAhead, resolution, device=0, shard=None, keep_resident=False):
-    """S2C:1104-1174, same positional arguments (``device``, ``shard`` and ``keep_resident`` are optional extras;
+                psig, convergenceRounds, lookAhead, resolution, device=0, shard=None, keep_resident=False,
+                groupSupportFile=None, rescuedChromosomeGroupFile=None):
+    """S2C:1104-1174, same positional arguments (``device``, ``shard``, ``keep_resident`` and the two file names are
+    optional extras; ``groupSupportFile`` / ``rescuedChromosomeGroupFile``: also write the group-support report and the
+    group file with the rescued scaffolds (groupSupport) from the resident map;
     ``shard=(rank, world)``: this process is one of ``world`` that work on the same map, see runResident;
     ``keep_resident=True``: the context with the contact matrix in HBM is not closed but returned as
     ``(DeviceMatrix, bins of its rows)`` so that Part 2 of the same run need not parse the text matrix again)."""
@@ -901,6 +1066,9 @@ def runPipeline(hicProBedFile, hicProBiasFile, hicProMatrixFile, hicProScaffSize
         if plotModule.plots_enabled(avgClusterPlot_outlined):
             plotModule.plotContactMap(plotModule.DeviceImage(adjMat.ctx, 1, adjMat.order), resolution=resolution,
                                       highlightChroms=cutIndices, showPlot=False, savePlot=avgClusterPlot_outlined)
+        if groupSupportFile or rescuedChromosomeGroupFile:
+            groupSupportToFiles(adjMat, adjMat.kept_bins, adjMat.chromosome_groups, hicProBedFile, chromosomeGroupFile,
+                                groupSupportFile, rescuedChromosomeGroupFile)
     except BaseException:
         adjMat.ctx.close()
         raise

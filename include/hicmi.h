@@ -462,6 +462,23 @@ int hicmi_louvain_level0(hicmi_ctx *ctx, int64_t rounds, const uint64_t *states_
 int hicmi_louvain_induced(hicmi_ctx *ctx, const int32_t *part, int64_t m, int64_t k, double *out);
 int hicmi_louvain_modularity(hicmi_ctx *ctx, const int32_t *parts, int64_t rounds, int64_t m, double *q_out);
 
+/* ---- Part 1: group support ----------------------------------------------------
+ * assessChromosomeClustering (S2C:1001-1077) assigns a scaffold to a chromosome group by a vote of its bins; this entry
+ * point extends that call site with the evidence of the contacts: how densely every bin and every scaffold touches
+ * every group.  On the context's contact matrix as it stands (uploaded, adopted with ld > n, or compacted; n bins):
+ * grp[i] in -1 .. n_groups - 1 (the group of bin i, -1: none) and scaf[i] in 0 .. n_scaffolds - 1 (a dense scaffold id)
+ * for every bin; a value outside those ranges: HICMI_EINVAL.
+ *   bin_sums_out[i * n_groups + g]      = sum of M[j][i] over the rows j with grp[j] == g and scaf[j] != scaf[i]
+ *                                         (n x n_groups, may be NULL): a scaffold's own bins never vote for it;
+ *   scaffold_sums_out[s * n_groups + g] = sum of that over the bins i of scaffold s (n_scaffolds x n_groups).
+ * The order of every sum is fixed, so the tables are reproducible to the last bit: the members of g by ascending row in
+ * chunks of 64, each chunk left to right from 0.0, the chunk sums left to right; a scaffold's bins left to right in
+ * matrix order.  Every grouped row is read once (k_gs_partial, k_gs_reduce); HICMI_GROUP_SUPPORT_PLAIN=1 in the
+ * environment takes the one-thread-per-(column, group) kernel instead, with the same bits.
+ * Device scratch: (grouped rows / 64 + n_groups) x n partials and the two tables; n_groups <= 65536. */
+int hicmi_group_sums(hicmi_ctx *ctx, const int32_t *grp, const int32_t *scaf, int64_t n_groups, int64_t n_scaffolds,
+                     double *bin_sums_out, double *scaffold_sums_out);
+
 /* ---- timing ----------------------------------------------------------------------------------
  * Accumulated device time (HIP events on the context stream) per kernel family since the last
  * reset, for bench.py's roofline object.  names_out: caller buffer receiving ';'-separated names;
