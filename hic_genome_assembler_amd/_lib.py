@@ -86,6 +86,8 @@ SIGNATURES = {
                                               ctypes.POINTER(c_dbl), ctypes.POINTER(c_i64)]),
     "hicmi_p2_support": (ctypes.c_int, [_vp, _vp, _vp, c_i64, c_dbl, _vp, _vp]),
     "hicmi_p2_support_multi": (ctypes.c_int, [c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hicmi_p2_breaks": (ctypes.c_int, [_vp, _vp, _vp, c_i64, c_dbl, c_i64, _vp, _vp]),
+    "hicmi_p2_breaks_multi": (ctypes.c_int, [c_i64, _vp, _vp, _vp, _vp, _vp, c_i64, _vp, _vp]),
     "hicmi_p2_scan_pass": (ctypes.c_int, [_vp, _vp, _vp, c_i64, c_i64, c_dbl, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl),
                                           ctypes.POINTER(ctypes.c_int32)]),
     "hicmi_p2_scan_all": (ctypes.c_int, [_vp, _vp, _vp, c_i64, c_i64, c_dbl, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl),
@@ -644,6 +646,39 @@ class Context:
         for (ctx, _i, _r, _t), a, b in zip(jobs, a_l, b_l):
             ctx._arr_sig = a.tobytes() + b.tobytes()
             ctx._arr_len = len(a)
+        return list(zip(t_l, o_l))
+
+    def p2_breaks(self, ids, rev, lengths, total: float, min_piece: int = 1):
+        """Break support of one chromosome (hicmi_p2_breaks): see p2_breaks_multi."""
+        return Context.p2_breaks_multi([(self, ids, rev, lengths, total)], min_piece, single=True)[0]
+
+    @staticmethod
+    def p2_breaks_multi(jobs, min_piece: int = 1, single=False):
+        """Break support of several chromosomes in one pair of launches (hicmi_p2_breaks_multi).
+        jobs: [(context, ids, rev, lengths, total)], one distinct context per chromosome, ``lengths`` the bins of each
+        scaffold of the arrangement; returns [(table, best)]: the scaffolds' (L - 1) x 8 blocks of closed-form scores
+        concatenated in arrangement order as one (sum of L - 1) x 8 array, and S x 2 int32 of [8 (p - 1) + k of the first
+        maximum among the competing candidates or -1, how many of them lie within 1e-9 of it]."""
+        n = len(jobs)
+        if n == 0:
+            return []
+        lib = jobs[0][0]._lib
+        a_l = [np.ascontiguousarray(j[1], dtype=np.int32) for j in jobs]
+        b_l = [np.ascontiguousarray(j[2], dtype=np.uint8) for j in jobs]
+        t_l = [np.empty((sum(max(int(ln) - 1, 0) for ln in j[3]), 8), np.float64) for j in jobs]
+        o_l = [np.empty((len(a), 2), np.int32) for a in a_l]
+        if single:
+            _check(lib.hicmi_p2_breaks(jobs[0][0]._h, _ptr(a_l[0]), _ptr(b_l[0]), len(a_l[0]), float(jobs[0][4]), int(min_piece),
+                                       t_l[0].ctypes.data, _ptr(o_l[0])))
+        else:
+            handles = (ctypes.c_void_p * n)(*[j[0]._h for j in jobs])
+            pa, pb, pt, po = ((ctypes.c_void_p * n)(*[x.ctypes.data for x in arrs]) for arrs in (a_l, b_l, t_l, o_l))
+            sizes = (c_i64 * n)(*[len(a) for a in a_l])
+            totals = (c_dbl * n)(*[float(j[4]) for j in jobs])
+            _check(lib.hicmi_p2_breaks_multi(n, handles, pa, pb, sizes, totals, int(min_piece), pt, po))
+        for j, a, b in zip(jobs, a_l, b_l):
+            j[0]._arr_sig = a.tobytes() + b.tobytes()
+            j[0]._arr_len = len(a)
         return list(zip(t_l, o_l))
 
     def p2_scan_pass(self, ids, rev, k, total, best, cur_fast):

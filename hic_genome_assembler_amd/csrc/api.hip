@@ -133,6 +133,7 @@ struct hicmi_ctx {
     unsigned char* d_ins_blob = nullptr; int64_t ins_blob_cap = 0;   // per job: [InsState][InsLog x steps]
     InsStep* d_ins_steps = nullptr; int64_t ins_steps_cap = 0;       // [step][job] records of a lock-step queue
     SupRec* d_sup_recs = nullptr; int64_t sup_recs_cap = 0;          // hicmi_p2_support_multi: (chromosome, left-out scaffold) records
+    BrkRec* d_brk_recs = nullptr; int64_t brk_recs_cap = 0;          // hicmi_p2_breaks_multi: (chromosome, scaffold of 2+ bins) records
     // group support (k_group_support.hip): the member lists of a call, and its partials + the two tables
     int32_t* d_gs_lists = nullptr; int64_t gs_lists_cap = 0;
     double* d_gs_sums = nullptr; int64_t gs_sums_cap = 0;
@@ -374,7 +375,7 @@ int hicmi_destroy(hicmi_ctx* c)
     free_dev(c->d_scaf_start); free_dev(c->d_scaf_len); free_dev(c->d_arr_packed);
     free_dev(c->d_pos2sel); free_dev(c->d_orders); free_dev(c->d_orients);
     free_dev(c->d_G); free_dev(c->d_delta); free_dev(c->d_wb); free_dev(c->d_wnear);
-    free_dev(c->d_arr_packed2); free_dev(c->d_pos2sel2); free_dev(c->d_ins_T); free_dev(c->d_ins_partial);
+    free_dev(c->d_arr_packed2); free_dev(c->d_pos2sel2); free_dev(c->d_ins_T); free_dev(c->d_ins_partial); free_dev(c->d_brk_recs);
     free_dev(c->d_ins_blob); free_dev(c->d_ins_steps); free_dev(c->d_sup_recs);
     free_dev(c->d_gs_lists); free_dev(c->d_gs_sums);
     free_dev(c->d_plot_order); free_dev(c->d_plot_work); free_dev(c->d_plot_img);
@@ -2556,6 +2557,119 @@ int hicmi_p2_support(hicmi_ctx* c, const int32_t* ids, const uint8_t* rev, int64
                      int32_t* best_out)
 {
     return hicmi_p2_support_multi(1, &c, &ids, &rev, &S, &total, &scores_out, &best_out);
+}
+
+// Break support (k_part2_breaks.hip): every scaffold of every job's arrangement cut at every bin boundary, the two
+// pieces swapped and / or reversed in place; one record per (job, scaffold of at least 2 bins), one pair of launches
+// and one download for all jobs.
+int hicmi_p2_breaks_multi(int64_t n_jobs, hicmi_ctx* const* ctxs, const int32_t* const* ids, const uint8_t* const* rev,
+                          const int64_t* S, const double* totals, int64_t min_piece, double* const* scores_out,
+                          int32_t* const* best_out)
+{
+    if (n_jobs < 1 || !ctxs || !ids || !rev || !S || !totals || !scores_out || !best_out || min_piece < 1)
+        return fail(HICMI_EINVAL, "bad arguments");
+    hicmi_ctx* lead = ctxs[0];
+    const int NB = BRK_BASE_SLABS;
+    std::vector<size_t> out_off((size_t)n_jobs, 0);
+    std::vector<int64_t> n_scores((size_t)n_jobs, 0);
+    std::vector<uint8_t> run((size_t)n_jobs, 0);
+    size_t blob_bytes = 0;
+    int64_t n_rec = 0;
+    for (int64_t j = 0; j < n_jobs; j++) {
+        hicmi_ctx* c = ctxs[j];
+        if (!c || !lead || c->device != lead->device) return fail(HICMI_EINVAL, "contexts must share one device");
+        for (int64_t q = 0; q < j; q++) if (ctxs[q] == c) return fail(HICMI_EINVAL, "one context per chromosome");
+        if (!ids[j] || !rev[j] || !scores_out[j] || !best_out[j] || S[j] < 1) return fail(HICMI_EINVAL, "bad arguments");
+        int rc = hicmi_p2_set_arrangement(c, ids[j], rev[j], S[j]);
+        if (rc) return rc;
+        if (c != lead) HIPCHK(sync_stream(c));             // the launches run on lead's stream
+        if (c->n_arr * (int64_t)sizeof(int32_t) > 160 * 1024) return fail(HICMI_EUNSUPPORTED, "candidate longer than 40960 bins");
+        int64_t cand = 0, scratch = NB, multi = 0;
+        for (int64_t k = 0; k < S[j]; k++) {
+            const int64_t L = c->h_scaf_len[(size_t)ids[j][k]];
+            if (L < 2) continue;
+            cand += 8 * (L - 1); scratch += L * L + 3 * (L - 1); multi++;
+        }
+        n_scores[(size_t)j] = cand;
+        // fewer than 2 bins, or no contacts: every score is 0.0 and there is no candidate
+        for (int64_t i = 0; i < cand; i++) scores_out[j][i] = 0.0;
+        for (int64_t i = 0; i < S[j]; i++) { best_out[j][2 * i] = -1; best_out[j][2 * i + 1] = 0; }
+        if (c->n_arr < 2 || !(totals[j] > 0.0) || multi == 0) continue;
+        run[(size_t)j] = 1;
+        rc = ensure(c->d_ins_partial, c->ins_partial_cap, scratch);
+        if (rc) return rc;
+        out_off[(size_t)j] = blob_bytes;
+        blob_bytes += ((size_t)cand * sizeof(double) + (size_t)(2 * S[j]) * sizeof(int32_t) + 15) & ~(size_t)15;
+        n_rec += multi;
+    }
+    if (n_rec == 0) return HICMI_OK;
+    HIPCHK(hipSetDevice(lead->device));
+    int rc = ensure(lead->d_ins_blob, lead->ins_blob_cap, (int64_t)blob_bytes);
+    if (rc) return rc;
+    rc = ensure(lead->d_brk_recs, lead->brk_recs_cap, n_rec);
+    if (rc) return rc;
+    std::vector<BrkRec> recs;
+    recs.reserve((size_t)n_rec);
+    double algo = 0.0;
+    int64_t n_wg = 0;
+    for (int64_t j = 0; j < n_jobs; j++) {
+        if (!run[(size_t)j]) continue;
+        hicmi_ctx* c = ctxs[j];
+        const int64_t Sj = S[j], n = c->n_arr;
+        double* d_scores = reinterpret_cast<double*>(lead->d_ins_blob + out_off[(size_t)j]);
+        int32_t* d_best = reinterpret_cast<int32_t*>(d_scores + n_scores[(size_t)j]);
+        // one-bin scaffolds have no record: their (-1, 0) is written here, beside the records' pairs
+        rc = upload(lead, d_best, best_out[j], sizeof(int32_t) * (size_t)(2 * Sj));
+        if (rc) return rc;
+        double* scratch = c->d_ins_partial + NB;
+        int64_t row = 0;
+        bool first = true;
+        for (int64_t k = 0; k < Sj; k++) {
+            const int64_t L = c->h_scaf_len[(size_t)ids[j][k]];
+            if (L < 2) continue;
+            BrkRec d;
+            memset(&d, 0, sizeof(d));
+            d.M2 = c->dM2; d.H = c->d_H; d.ld2 = c->ld2;
+            d.pos = c->d_pos2sel;
+            d.X = scratch; d.pq = scratch + L * L; scratch += L * L + 3 * (L - 1);
+            d.base = c->d_ins_partial;
+            d.scores = d_scores + 8 * row; d.best = d_best + 2 * k; row += L - 1;
+            d.total = totals[j];
+            d.wg0 = n_wg;
+            d.n = (int32_t)n; d.B = c->h_arr_pos[(size_t)k]; d.L = (int32_t)L;
+            d.min_piece = (int32_t)std::min<int64_t>(min_piece, 1 << 30);
+            d.n_base = first ? NB : 0;
+            first = false;
+            n_wg += d.n_base + L * ((L + 3) / 4) + (L - 1);
+            recs.push_back(d);
+            algo += 8.0 * ((double)L * (double)L * (double)(n - L) + (double)L * (double)L * (double)L / 6.0);
+        }
+        algo += 4.0 * (double)n * (double)n;
+    }
+    if (n_wg > 0x7fffffff) return fail(HICMI_EUNSUPPORTED, "more than 2^31 - 1 workgroups in one call");
+    rc = upload(lead, lead->d_brk_recs, recs.data(), sizeof(BrkRec) * recs.size());
+    if (rc) return rc;
+    {
+        Timed timed(lead, F_P2_INSERT, algo);
+        launch_brk(lead->d_brk_recs, (int)n_rec, n_wg, kNearTop, lead->stream);
+    }
+    HIPCHK(hipGetLastError());
+    std::vector<unsigned char> blob(blob_bytes);
+    rc = download(lead, blob.data(), lead->d_ins_blob, blob_bytes);
+    if (rc) return rc;
+    for (int64_t j = 0; j < n_jobs; j++) {
+        if (!run[(size_t)j]) continue;
+        const size_t nd = (size_t)n_scores[(size_t)j];
+        memcpy(scores_out[j], blob.data() + out_off[(size_t)j], nd * sizeof(double));
+        memcpy(best_out[j], blob.data() + out_off[(size_t)j] + nd * sizeof(double), (size_t)(2 * S[j]) * sizeof(int32_t));
+    }
+    return HICMI_OK;
+}
+
+int hicmi_p2_breaks(hicmi_ctx* c, const int32_t* ids, const uint8_t* rev, int64_t S, double total, int64_t min_piece,
+                    double* scores_out, int32_t* best_out)
+{
+    return hicmi_p2_breaks_multi(1, &c, &ids, &rev, &S, &total, min_piece, &scores_out, &best_out);
 }
 
 int hicmi_p2_scan_pass(hicmi_ctx* c, int32_t* ids, uint8_t* rev, int64_t S, int64_t k, double total, double* best_io,

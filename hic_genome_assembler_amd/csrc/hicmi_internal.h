@@ -377,6 +377,24 @@ struct SupRec {
 };
 void launch_sup(const SupRec* recs, int n_rec, int max_S, int max_n, double near_top, hipStream_t s);
 
+// k_part2_breaks.hip: break support (hicmi_p2_breaks_multi).  One record per (chromosome, scaffold j of at least 2 bins):
+// j cut between two of its bins, the two pieces swapped and / or reversed in place.
+static constexpr int BRK_BASE_SLABS = 64;     // partial sums of a chromosome's BASE term
+struct BrkRec {
+    const double* M2; const double* H; int64_t ld2;
+    const int32_t* pos;                       // A as bin order, n entries
+    double* X;                                // scratch: L x L, [bin of the block as laid down][position inside the block]
+    double* pq;                               // scratch: [L - 1 cuts][3 P x Q sums]
+    double* base;                             // the chromosome's BRK_BASE_SLABS BASE slabs (one area for all its records)
+    double* scores;                           // out: score(p, k) at [8 (p - 1) + k]
+    int32_t* best;                            // out: first closed-form maximum among the competing candidates (-1: none), how many within near_top
+    double total;
+    int64_t wg0;                              // first workgroup of this record in k_brk_tables
+    int32_t n, B, L, min_piece;               // B: first position of j in A
+    int32_t n_base, pad;                      // BRK_BASE_SLABS for a chromosome's first record (it forms the slabs), else 0
+};
+void launch_brk(const BrkRec* recs, int n_rec, int64_t n_wg, double near_top, hipStream_t s);
+
 // k_group_support.hip: group support (hicmi_group_sums).  rows: the grouped rows sorted by group, ascending inside a
 // group; chunks[c]: rows[row0 .. row0 + cnt) with cnt <= GS_CHUNK, all of one group; group_chunk0[g] .. [g + 1]: the
 // chunks of group g; sbins / soff: the bins sorted by scaffold.  partial: n_chunks x n, binsum: n x G, scafsum: S x G.

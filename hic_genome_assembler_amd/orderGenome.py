@@ -1213,6 +1213,26 @@ def _support_one(layout, ids, rev, total, table, best):
     return {"score0": score0, "total": total, "table": table, "rows": rows}
 
 
+def _layout_jobs(lanes, orderedChromosomes, binList, chromList):
+    """The chromosomes of a finished ordering, len(lanes) at a time, each selected on its lane in orderChromosome's layout
+    order (``chromList[k]``, the group file's rows, fixes it; without it the scaffolds are taken largest first in
+    arrangement order): lists of (layout, ids, rev, total of the layout, scaffolds in arrangement order)."""
+    for c0 in range(0, len(orderedChromosomes), len(lanes)):
+        jobs = []
+        for lane, k in zip(lanes, range(c0, min(c0 + len(lanes), len(orderedChromosomes)))):
+            group = orderedChromosomes[k]
+            if chromList is not None:
+                by_name = {s.name: s for s in group}
+                order = [by_name[s.name] for s in _layoutScaffolds(chromList[k])]
+            else:
+                order = sorted(group, key=lambda s: len(s.binList), reverse=True)
+            layout = lane.chrom = ChromosomeLayout(lane, order, binList)
+            total = layout.whole_total()
+            ids, rev = layout.describe(group)
+            jobs.append((layout, ids, rev, total, group))
+        yield jobs
+
+
 def placementSupport(matrix: GenomeMatrix, orderedChromosomes, binList, chromList=None):
     """How well the map supports a finished ordering: every scaffold of every chromosome is taken out of its
     chromosome's arrangement and put back at every gap in both orientations (include/hicmi.h,
@@ -1230,19 +1250,7 @@ def placementSupport(matrix: GenomeMatrix, orderedChromosomes, binList, chromLis
     multi = not direct and SCORE_HOOK is None and hasattr(ctx, "workers") and hasattr(ctx, "p2_support_multi")
     lanes = matrix.lanes(len(orderedChromosomes)) if multi and len(orderedChromosomes) > 1 else [matrix]
     out = []
-    for c0 in range(0, len(orderedChromosomes), len(lanes)):
-        jobs = []
-        for lane, k in zip(lanes, range(c0, min(c0 + len(lanes), len(orderedChromosomes)))):
-            group = orderedChromosomes[k]
-            if chromList is not None:
-                by_name = {s.name: s for s in group}
-                order = [by_name[s.name] for s in _layoutScaffolds(chromList[k])]
-            else:
-                order = sorted(group, key=lambda s: len(s.binList), reverse=True)
-            layout = lane.chrom = ChromosomeLayout(lane, order, binList)
-            total = layout.whole_total()
-            ids, rev = layout.describe(group)
-            jobs.append((layout, ids, rev, total, group))
+    for jobs in _layout_jobs(lanes, orderedChromosomes, binList, chromList):
         if direct:
             tables = [_support_direct(layout, ids, rev, total) for layout, ids, rev, total, _g in jobs]
         elif multi:
@@ -1300,6 +1308,236 @@ def writePlacementSupportToFile(results, outFile, fullDir=None):
     print("Placement support written for scaffolds " + str(sum(len(r["rows"]) for r in results)))
 
 
+# ---- break support of a finished ordering ---------------------------------------------
+BREAK_MOVES = ("as_is", "flip_right", "flip_left", "flip_both", "swap", "swap_flip_right", "swap_flip_left",
+               "swap_flip_both")       # candidate k = 4 w + 2 x + y: pieces swapped, left piece reversed, right piece reversed
+
+
+def _break_row(row0, B, L, p, k):
+    """Bin order of candidate k of the cut after the first p of the L positions from B of ``row0``."""
+    P, Q = row0[B:B + p], row0[B + p:B + L]
+    if k & 2:
+        P = P[::-1]
+    if k & 1:
+        Q = Q[::-1]
+    return np.concatenate([row0[:B], Q, P, row0[B + L:]] if k & 4 else [row0[:B], P, Q, row0[B + L:]])
+
+
+def break_counts(L, minPiece=1):
+    """(L - 1, 8) mask of the candidates that compete for a scaffold's best break: both pieces have ``minPiece`` bins,
+    and the bin order differs from the arrangement's, from the in-place whole flip's and from every earlier candidate's
+    of the same cut (include/hicmi.h, hicmi_p2_breaks)."""
+    m = np.zeros((max(L - 1, 0), 8), dtype=bool)
+    for p in range(1, L):
+        q = L - p
+        if p < minPiece or q < minPiece:
+            continue
+        for k in range(1, 7):
+            if (k & 2 and p == 1) or (k & 1 and q == 1):
+                continue
+            if (k == 5 and p == 1) or (k == 6 and q == 1) or (k == 4 and p == 1 and q == 1):
+                continue
+            m[p - 1, k] = True
+    return m
+
+
+def break_summary(block, L, minPiece=1):
+    """What hicmi_p2_breaks returns as a scaffold's ``best`` from its (L - 1) x 8 block of scores: [8 (p - 1) + k of the
+    first maximum over break_counts, or -1; how many competing candidates lie within NEAR_TOP of it]."""
+    ok = (break_counts(L, minPiece) & np.isfinite(block)).reshape(-1)
+    if not ok.any():
+        return -1, 0
+    v = np.where(ok, np.asarray(block, dtype=np.float64).reshape(-1), -np.inf)
+    top = float(v.max())
+    return int(np.argmax(v)), int(np.count_nonzero(v >= top - abs(top) * NEAR_TOP))
+
+
+def _break_offsets(lengths):
+    """First table row of every scaffold's (L - 1) x 8 block, and the number of rows."""
+    off, at = [], 0
+    for ln in lengths:
+        off.append(at)
+        at += max(ln - 1, 0)
+    return off, at
+
+
+def _breaks_direct(layout, ids, rev, total, minPiece):
+    """A/B path (HICMI_P2_BREAKS_DIRECT=1): the same table from hicmi_p2_score on every candidate's materialised bin
+    order, at most SUPPORT_DIRECT_BYTES of rows at a time."""
+    lengths = [layout.length[int(i)] for i in ids]
+    off, n_rows = _break_offsets(lengths)
+    table = np.zeros((n_rows, 8))
+    best = np.tile(np.array([-1, 0], np.int32), (len(ids), 1))
+    if layout.n < 2 or not total > 0:
+        return table, best
+    row0 = layout.node_row(ids, rev)
+    starts = np.concatenate([[0], np.cumsum(lengths)])
+    cands = [(int(starts[j]), L, p, k) for j, L in enumerate(lengths) for p in range(1, L) for k in range(8)]
+    flat = table.reshape(-1)
+    per = max(1, SUPPORT_DIRECT_BYTES // (4 * layout.n))
+    for c0 in range(0, len(cands), per):
+        rows = np.stack([_break_row(row0, *c) for c in cands[c0:c0 + per]]).astype(np.int32)
+        flat[c0:c0 + len(rows)] = layout.ctx.p2_score(rows, total)
+    for j, L in enumerate(lengths):
+        best[j] = break_summary(table[off[j]:off[j] + L - 1], L, minPiece)
+    return table, best
+
+
+def _breaks_one(layout, ids, rev, total, table, best, group, minPiece):
+    """One chromosome's result from its table: score0, the best break of every scaffold and the verdicts.  The table
+    ranks; a scaffold whose best break has rivals within NEAR_TOP is decided on their literal scores
+    (hicmi_p2_score_exact), first strict maximum.  The reported floats are literal scores too - the arrangement and every
+    best break of the chromosome in one call - so that they do not depend on how the table was computed."""
+    S = len(ids)
+    lengths = [layout.length[int(i)] for i in ids]
+    off, _n = _break_offsets(lengths)
+    starts = np.concatenate([[0], np.cumsum(lengths)]).astype(int)
+    live = layout.n >= 2 and total > 0
+    row0 = layout.node_row(ids, rev)
+    picks, nears = [], []
+    for j in range(S):
+        pick, n_near = (int(best[j][0]), int(best[j][1])) if live else (-1, 0)
+        nears.append(n_near)
+        if pick >= 0 and n_near > 1:
+            L = lengths[j]
+            flat = table[off[j]:off[j] + L - 1].reshape(-1)
+            top = float(flat[pick])
+            near = np.flatnonzero(break_counts(L, minPiece).reshape(-1) & np.isfinite(flat) & (flat >= top - abs(top) * NEAR_TOP))
+            lit = _literal_rows(layout, [_break_row(row0, int(starts[j]), L, int(c) // 8 + 1, int(c) % 8) for c in near], total)
+            top_lit = -math.inf
+            for c, v in zip(near, lit):                   # first strict maximum in enumeration order
+                if v > top_lit:
+                    pick, top_lit = int(c), float(v)
+        picks.append(pick)
+    moves = [j for j in range(S) if picks[j] >= 0]
+    lit = _literal_rows(layout, [row0] + [_break_row(row0, int(starts[j]), lengths[j], picks[j] // 8 + 1, picks[j] % 8)
+                                          for j in moves], total) if live else [0.0]
+    score0 = float(lit[0])
+    delta_of = dict(zip(moves, (float(v) - score0 for v in lit[1:])))
+    rows = []
+    for j in range(S):
+        delta, L = delta_of.get(j), lengths[j]
+        if delta is None:
+            cut = after = move = gain = None
+            verdict = "NA"
+        else:
+            p = picks[j] // 8 + 1
+            cut = L - p if rev[j] else p                  # the scaffold's own bins before the cut, '+' direction
+            after = sorted(group[j].binList)[cut - 1]
+            move = BREAK_MOVES[picks[j] % 8]
+            gain = delta / score0
+            verdict = "breakable" if delta > 0 else "intact"
+        rows.append({"bins": L, "best_cut": cut, "cut_after_bin": after, "best_move": move, "best_delta": delta,
+                     "gain": gain, "verdict": verdict, "near": nears[j]})
+    return {"score0": score0, "total": total, "table": table, "offsets": off, "rows": rows, "minPiece": minPiece}
+
+
+def breakSupport(matrix: GenomeMatrix, orderedChromosomes, binList, chromList=None, minPiece=1):
+    """Where the map would rather have a scaffold cut: every scaffold of every chromosome is cut between every two of
+    its bins and the two pieces are swapped and / or reversed in place (include/hicmi.h, hicmi_p2_breaks).
+    Returns one dict per chromosome: 'score0' (literal objective of the arrangement), 'total', 'table' (the scaffolds'
+    (L - 1) x 8 blocks of scores concatenated in arrangement order: row = cut p as laid down, column = candidate
+    BREAK_MOVES[k]), 'offsets' (first table row of each scaffold), 'names', 'orientations', 'minPiece' and 'rows' (per
+    scaffold in arrangement order: bins, best_cut, cut_after_bin, best_move, best_delta, gain, verdict, and near: how many
+    competing candidates lay within NEAR_TOP of the top closed-form score).
+
+    Total, layout and lanes are placementSupport's.  On the device all chromosomes go through one hicmi_p2_breaks_multi
+    call, one context each; HICMI_P2_BREAKS_DIRECT=1 scores materialised candidates with hicmi_p2_score instead.
+    ``minPiece``: only cuts that leave both pieces at least that many bins compete for the best break."""
+    ctx = matrix.ctx
+    minPiece = max(1, int(minPiece))
+    matrix.bin_index(binList)
+    direct = os.environ.get("HICMI_P2_BREAKS_DIRECT", "") not in ("", "0")
+    multi = not direct and SCORE_HOOK is None and hasattr(ctx, "workers") and hasattr(ctx, "p2_breaks_multi")
+    lanes = matrix.lanes(len(orderedChromosomes)) if multi and len(orderedChromosomes) > 1 else [matrix]
+    out = []
+    for jobs in _layout_jobs(lanes, orderedChromosomes, binList, chromList):
+        lens = [[layout.length[int(i)] for i in ids] for layout, ids, _r, _t, _g in jobs]
+        if direct:
+            tables = [_breaks_direct(layout, ids, rev, total, minPiece) for layout, ids, rev, total, _g in jobs]
+        elif multi:
+            tables = ctx.p2_breaks_multi([(layout.ctx, ids, rev, ln, total) for (layout, ids, rev, total, _g), ln in
+                                          zip(jobs, lens)], minPiece)
+        else:
+            tables = [layout.ctx.p2_breaks(ids, rev, ln, total, minPiece) for (layout, ids, rev, total, _g), ln in
+                      zip(jobs, lens)]
+        for (layout, ids, rev, total, group), (table, best) in zip(jobs, tables):
+            res = _breaks_one(layout, ids, rev, total, np.asarray(table), best, group, minPiece)
+            res["names"] = [s.name for s in group]
+            res["orientations"] = [s.orientation for s in group]
+            out.append(res)
+    return out
+
+
+def breakSupportText(results):
+    """The report: per chromosome ``### Chromosome grouping i ### score0``, then one tab-separated line per scaffold in
+    arrangement order: scaffold, orientation, bins, best_cut, cut_after_bin, best_move, best_delta, gain, verdict.
+    Floats are written with repr; a scaffold without a competing candidate (one or two bins, minPiece): NA."""
+    text = []
+    for k, res in enumerate(results):
+        text.append("### Chromosome grouping " + str(k + 1) + " ### " + repr(res["score0"]) + "\n")
+        for name, orient, row in zip(res["names"], res["orientations"], res["rows"]):
+            text.append("\t".join([name, orient, str(row["bins"])] + [_support_text(row[key]) for key in
+                                                                      ("best_cut", "cut_after_bin", "best_move", "best_delta",
+                                                                       "gain")] + [row["verdict"]]) + "\n")
+    return "".join(text)
+
+
+def writeBreakSupportToFile(results, outFile, fullDir=None):
+    """breakSupportText to ``outFile``; ``fullDir``: also each chromosome's table as ``Chr_i.breaks.tsv``, one line per
+    (scaffold, cut) in enumeration order: scaffold, the scaffold's own bins before the cut, the 8 scores."""
+    with open(outFile, "w") as fh:
+        fh.write(breakSupportText(results))
+    if fullDir:
+        os.makedirs(fullDir, exist_ok=True)
+        for k, res in enumerate(results):
+            table = np.asarray(res["table"])
+            with open(os.path.join(fullDir, "Chr_%d.breaks.tsv" % (k + 1)), "w") as fh:
+                fh.write("\t".join(("scaffold", "cut") + BREAK_MOVES) + "\n")
+                for name, orient, row, at in zip(res["names"], res["orientations"], res["rows"], res["offsets"]):
+                    L = row["bins"]
+                    for p in range(1, L):
+                        fh.write("\t".join([name, str(L - p if orient == "-" else p)]
+                                           + [repr(float(v)) for v in table[at + p - 1]]) + "\n")
+    print("Break support written for scaffolds " + str(sum(len(r["rows"]) for r in results)))
+
+
+def writeBrokenGroupFile(results, chromosomeGroupFile, outFile):
+    """``chromosomeGroupFile`` copied line by line to ``outFile``, except that the lines of every ``breakable`` scaffold
+    name it ``NAME.brk1`` for its bins up to the best cut and ``NAME.brk2`` for the rest.  One pass; the input file is
+    only read."""
+    last = [{name: row["cut_after_bin"] for name, row in zip(res["names"], res["rows"]) if row["verdict"] == "breakable"}
+            for res in results]
+    if os.path.abspath(outFile) == os.path.abspath(chromosomeGroupFile):
+        raise ValueError("the broken group file must not be the chromosomeGroupFile itself")
+    chrom = -1
+    with open(chromosomeGroupFile) as src, open(outFile, "w") as dst:
+        for line in src:
+            if line.startswith("#"):
+                chrom += 1
+            elif 0 <= chrom < len(last) and last[chrom]:
+                cols = line.split("\t", 2)
+                name = cols[1].rstrip("\r\n") if len(cols) == 2 else cols[1]
+                if len(cols) >= 2 and name in last[chrom]:
+                    piece = name + (".brk1" if int(cols[0]) <= last[chrom][name] else ".brk2")
+                    line = "\t".join([cols[0], piece + cols[1][len(name):]] + cols[2:])
+            dst.write(line)
+    print("Broken group file written with scaffolds split " + str(sum(len(d) for d in last)))
+
+
+def breakSupportToFiles(matrix, orderedChromosomes, binList, chromosomeGroupFile, breakSupportFile=None,
+                        brokenChromosomeGroupFile=None, fullDir=None, minPiece=1, chromList=None):
+    """breakSupport of a resident map and the files wanted of it; returns the results."""
+    if chromList is None:
+        chromList = _read_groups_quietly(chromosomeGroupFile)
+    results = breakSupport(matrix, orderedChromosomes, binList, chromList, minPiece=minPiece)
+    if breakSupportFile:
+        writeBreakSupportToFile(results, breakSupportFile, fullDir)
+    if brokenChromosomeGroupFile:
+        writeBrokenGroupFile(results, chromosomeGroupFile, brokenChromosomeGroupFile)
+    return results
+
+
 def getChromosomeOutlineCoords(orderedChromosomes):
     """OG:662-674."""
     coords, index = [], 0
@@ -1318,10 +1556,13 @@ def _read_groups_quietly(chromosomeGroupFile):
 
 def runPipeline(hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroupFile, chromosomeOrderFile,
                 savePlotsDirectory, chromosomePlotSuffix, fullGenomePlot, fullGenomePlotTitle, plotOrderFile,
-                nScaffolds, scanScaffolds, resolution, device=0, resident=None, placementSupportFile=None):
-    """OG:679-712, same positional arguments (``device``, ``resident`` and ``placementSupportFile`` are optional extras).
+                nScaffolds, scanScaffolds, resolution, device=0, resident=None, placementSupportFile=None,
+                breakSupportFile=None, brokenChromosomeGroupFile=None):
+    """OG:679-712, same positional arguments (``device``, ``resident`` and the ``...File`` keywords are optional extras).
 
     ``placementSupportFile``: also write the placement-support report of the final ordering there (placementSupport).
+    ``breakSupportFile`` / ``brokenChromosomeGroupFile``: also write the break-support report and the group file with
+    the breakable scaffolds split (breakSupport).
 
     ``resident=(DeviceMatrix, bins of its rows)`` from Part 1's ``runPipeline(..., keep_resident=True)``: the contact
     matrix already in HBM is used instead of parsing the HiC-Pro text again.  The reference re-loads the matrix
@@ -1343,6 +1584,9 @@ def runPipeline(hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroup
         if placementSupportFile:
             writePlacementSupportToFile(placementSupport(adjMat, orderedChromosomes, binList,
                                                          _read_groups_quietly(chromosomeGroupFile)), placementSupportFile)
+        if breakSupportFile or brokenChromosomeGroupFile:
+            breakSupportToFiles(adjMat, orderedChromosomes, binList, chromosomeGroupFile, breakSupportFile,
+                                brokenChromosomeGroupFile)
         if plotModule.plots_enabled(fullGenomePlot):                      # OG:700-707
             where = adjMat.bin_index(binList)
             rows = [where[b] for group in orderedChromosomes for s in group for b in s.binList]

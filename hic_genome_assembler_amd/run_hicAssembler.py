@@ -64,7 +64,9 @@ _BY_KEY = {k: (kind, prefix) for k, _d, kind, prefix in _SPEC}
 # keys a config may leave out: absent from the returned dictionary unless the file sets them
 _OPTIONAL = {"placementSupportFile": "saveFilesDirectory",     # -part2 also writes the placement-support report there
              "groupSupportFile": "saveFilesDirectory",         # -part1 also writes the group-support report there
-             "rescuedChromosomeGroupFile": "saveFilesDirectory"}   # ... and the group file with the rescued scaffolds
+             "rescuedChromosomeGroupFile": "saveFilesDirectory",   # ... and the group file with the rescued scaffolds
+             "breakSupportFile": "saveFilesDirectory",         # -part2 also writes the break-support report there
+             "brokenChromosomeGroupFile": "saveFilesDirectory"}    # ... and the group file with the breakable scaffolds split
 
 
 def _convert(values, key, text):
@@ -194,7 +196,7 @@ def main(argv=None):
                           v["chromosomeOrderFile"], v["savePlotsDirectory"], v["chromosomePlotSuffix"],
                           v["fullGenomePlot"], v["fullGenomePlotTitle"], v["plotOrderFile"],
                           v["nScaffolds"], v["scanScaffolds"], v["resolution"], device=args.device, resident=resident,
-                          **({"placementSupportFile": v["placementSupportFile"]} if "placementSupportFile" in v else {}))
+                          **{k: v[k] for k in ("placementSupportFile", "breakSupportFile", "brokenChromosomeGroupFile") if k in v})
     if args.part3:
         from . import orientSmallScaffolds as part3
         part3.runPipeline(v["chromosomeOrderFile"], v["hicProScaffSizeFile"], v["restrictionSiteFile"], v["validPairFile"],

@@ -27,7 +27,8 @@ setting of its highest final_score (ties: the earlier setting in grid order).  f
 of its selection (what hicmi_p2_total returns for it), so that settings compare on one footing; it is not the printed
 bestCost, whose total is rounded in arrangement order (OG:343 vs OG:506).  DIR defaults to saveFilesDirectory/sweep_part2.
 ``-support`` also writes ``DIR/best/placementSupport.txt``, the placement-support report (orderGenome.placementSupport) of
-the best orderings; its score0 column is their final_score.
+the best orderings; its score0 column is their final_score - and ``DIR/best/breakSupport.txt``, their break-support
+report (orderGenome.breakSupport).
 """
 from __future__ import annotations
 
@@ -307,6 +308,8 @@ def runSweep(hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroupFil
             if support:
                 _lines(p2.writePlacementSupportToFile, p2.placementSupport(matrix, best_orders, binList, chromList),
                        os.path.join(outDir, "best", "placementSupport.txt"))
+                _lines(p2.writeBreakSupportToFile, p2.breakSupport(matrix, best_orders, binList, chromList),
+                       os.path.join(outDir, "best", "breakSupport.txt"))
             if plots and plotModule.plots_enabled(fullGenomePlot):
                 _plots(matrix, binList, best_orders, os.path.join(outDir, "best"), fullGenomePlot, fullGenomePlotTitle,
                        resolution, chromosomePlotSuffix)
@@ -328,7 +331,7 @@ def _parse_args(argv):
     p.add_argument("-device", type=int, default=0, help="GPU index (default 0)")
     p.add_argument("-out", type=str, default=None, help="output directory (default: saveFilesDirectory/sweep_part2)")
     p.add_argument("-plots", action="store_true", help="draw the best orderings' chromosome and genome figures")
-    p.add_argument("-support", action="store_true", help="write the placement-support report of the best orderings")
+    p.add_argument("-support", action="store_true", help="write the placement-support and break-support reports of the best orderings")
     return p.parse_args(argv)
 
 

@@ -347,6 +347,33 @@ int hicmi_p2_support(hicmi_ctx *ctx, const int32_t *ids, const uint8_t *rev, int
 int hicmi_p2_support_multi(int64_t n_jobs, hicmi_ctx *const *ctxs, const int32_t *const *ids, const uint8_t *const *rev,
                            const int64_t *S, const double *totals, double *const *scores_out, int32_t *const *best_out);
 
+/* Break support of a finished ordering: every scaffold cut at every bin boundary.  Chromosome, arrangement A = (ids,
+ * rev) of S scaffolds and the ONE total are as for hicmi_p2_support.  Scaffold j occupies L positions of A, read as
+ * laid down (a '-' scaffold reads descending); cut p = 1 ... L-1 makes the left piece P, the first p positions, and
+ * the right piece Q, the rest.  Candidate k = 4 w + 2 x + y of (j, p): pieces swapped (w), P reversed (x), Q reversed
+ * (y), every other position of A unchanged; k = 0 is A and k = 7 the whole scaffold flipped in place.
+ * scores_out: for the scaffolds in arrangement order, scaffold j's (L_j - 1) x 8 block [8 (p - 1) + k] = objective of
+ * that candidate under `total`, closed form, fp64; the blocks are concatenated (a one-bin scaffold has none), sum of
+ * 8 (L_j - 1) doubles in all, and the caller computes the offsets.
+ * A candidate competes if both pieces have at least min_piece (>= 1) bins and its bin order differs from A's, from the
+ * in-place whole flip's and from every earlier candidate's of the same cut: x = 1 never with |P| = 1, y = 1 never with
+ * |Q| = 1; of the rest k = 0 and 7 are out, k = 5 when |P| = 1, k = 6 when |Q| = 1, k = 4 when both pieces have one bin.
+ * best_out[2 j] = 8 (p - 1) + k of the first maximum, in enumeration order (p ascending, then k), of the closed-form
+ * scores over j's competing candidates, or -1 when none competes (L = 1, L = 2, min_piece); best_out[2 j + 1] = how
+ * many of them lie within 1e-9 (relative) of that maximum.  1: decided.  More: the caller re-scores them literally
+ * (hicmi_p2_score_exact) and the first strict maximum of those values wins.
+ * A chromosome of fewer than 2 bins, or with total <= 0, gets 0.0 everywhere and no candidate.
+ * More than 40960 bins in one chromosome, or more than 2^31 - 1 workgroups in one call (a scaffold of L bins takes
+ * about L^2 / 4): HICMI_EUNSUPPORTED.
+ * hicmi_p2_breaks_multi: n_jobs chromosomes (one context each, all on one device) in one pair of launches - the grid
+ * runs over (chromosome, scaffold of at least 2 bins) records - and one download.  Replaces the contexts' current
+ * arrangement by A.  Must not run concurrently with other calls on the contexts. */
+int hicmi_p2_breaks(hicmi_ctx *ctx, const int32_t *ids, const uint8_t *rev, int64_t S, double total, int64_t min_piece,
+                    double *scores_out, int32_t *best_out);
+int hicmi_p2_breaks_multi(int64_t n_jobs, hicmi_ctx *const *ctxs, const int32_t *const *ids, const uint8_t *const *rev,
+                          const int64_t *S, const double *totals, int64_t min_piece, double *const *scores_out,
+                          int32_t *const *best_out);
+
 /* ---- Part 3 input scan (host code, no GPU) -----------------------------------------------------
  * readValidPairFile (orientSmallScaffolds.py:159-177): of a HiC-Pro allValidPairs file
  * (read, scaffold1, pos1, strand1, scaffold2, pos2, ...) keep the lines whose (scaffold1, scaffold2) is one of the
