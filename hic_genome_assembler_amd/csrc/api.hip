@@ -2342,15 +2342,18 @@ int queue_insertions(hicmi_ctx* lead, const std::vector<InsJob*>& jobs)
     if (getenv("HICMI_PART2_PROFILE")) {                   // how many lock steps needed a literal tie-break at all
         int64_t hist[5] = {0, 0, 0, 0, 0}, all_direct = 0;       // [0] = taken directly (one candidate near the top)
         for (int64_t t = 0; t < steps_max; t++) {
-            int mx = -1;
+            int mx = -1, ran = 0;
             for (int j = 0; j < nj; j++) {
                 if (t >= jobs[(size_t)j]->n_new - jobs[(size_t)j]->t) continue;
+                const InsState* hs = reinterpret_cast<const InsState*>(blob.data() + blob_off[(size_t)j]);
+                if (hs->fail >= 0 && t >= hs->fail) continue;         // declined: this and the later logs were never written
                 const InsLog* hl = reinterpret_cast<const InsLog*>(blob.data() + blob_off[(size_t)j] + sizeof(InsState));
                 const int ns = hl[t].n_short;
                 hist[ns < 0 ? 0 : (ns > 3 ? 4 : ns + 1)]++;
                 mx = std::max(mx, ns);
+                ran++;
             }
-            if (mx < 0) all_direct++;
+            if (ran && mx < 0) all_direct++;
         }
         fprintf(stderr, "[hicmi] insertion short lists: direct %lld, literal with 0:%lld 1:%lld 2:%lld 3+:%lld candidates; "
                         "lock steps without any literal pass: %lld of %lld\n",

@@ -325,7 +325,10 @@ void launch_insb_diag_cand(const InsStep* steps, int n_chrom, int max_n_used, hi
 void launch_insb_cost(const InsStep* steps, int n_chrom, int max_n_used, hipStream_t s)
 {
     ensure_dynamic_lds(reinterpret_cast<const void*>(k_insb_cost), g_lds_insb_cost, 65536);
-    hipLaunchKernelGGL(k_insb_cost, dim3(INS_MAXC, n_chrom), dim3(256), serial_lds_bytes(max_n_used), s, steps);
+    // `staged` is decided per chromosome: one beyond SERIAL_LDS_MAX streams from L2, but its neighbours in the same
+    // launch still stage up to SERIAL_LDS_MAX doubles, so the largest chromosome must not shrink the allocation
+    const int max_staged = max_n_used < SERIAL_LDS_MAX ? max_n_used : SERIAL_LDS_MAX;
+    hipLaunchKernelGGL(k_insb_cost, dim3(INS_MAXC, n_chrom), dim3(256), serial_lds_bytes(max_staged), s, steps);
 }
 
 // One workgroup (4 waves) per candidate.  Wave w takes rows a = w, w+4, ... of the candidate's
