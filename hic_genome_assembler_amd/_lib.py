@@ -34,11 +34,16 @@ SIGNATURES = {
     "hicmi_set_contacts_device": (ctypes.c_int, [_vp, _vp, c_i64, c_i64]),
     "hicmi_contacts_device": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "hicmi_load_hicpro_matrix": (ctypes.c_int, [ctypes.c_char_p, _vp, c_i64, _vp, ctypes.c_int, ctypes.POINTER(c_i64)]),
+    "hicmi_write_hicpro_matrix": (ctypes.c_int, [ctypes.c_char_p, _vp, c_i64, _vp, ctypes.c_int, ctypes.POINTER(c_i64)]),
+    "hicmi_format_double": (ctypes.c_int, [c_dbl, ctypes.c_char_p, c_i64]),
     "hicmi_row_sums": (ctypes.c_int, [_vp, _vp, _vp]),
     "hicmi_set_row_shard": (ctypes.c_int, [_vp, c_i64, c_i64]),
     "hicmi_set_row_sums": (ctypes.c_int, [_vp, _vp, _vp]),
     "hicmi_compact": (ctypes.c_int, [_vp, _vp, c_i64]),
     "hicmi_group_sums": (ctypes.c_int, [_vp, _vp, _vp, c_i64, c_i64, _vp, _vp]),
+    "hicmi_get_contact_rows": (ctypes.c_int, [_vp, c_i64, c_i64, _vp]),
+    "hicmi_ice_mask_rows": (ctypes.c_int, [_vp, _vp, c_i64]),
+    "hicmi_ice_balance": (ctypes.c_int, [_vp, _vp, c_i64, c_dbl, _vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_dbl)]),
     "hicmi_upgma": (ctypes.c_int, [_vp, _vp, _vp]),
     "hicmi_rank_matrix": (ctypes.c_int, [_vp, _vp]),
     "hicmi_presort_state": (ctypes.c_int, [_vp, _vp, _vp]),
@@ -164,6 +169,25 @@ def load_hicpro_matrix(path, bin_ids, threads: int = 0):
     edges = c_i64()
     _check(load().hicmi_load_hicpro_matrix(os.fsencode(path), _ptr(ids), n, _ptr(out), int(threads), ctypes.byref(edges)))
     return out, edges.value
+
+
+def write_hicpro_matrix(path, mat, bin_ids, threads: int = 0) -> int:
+    """HiC-Pro triplet file of a dense symmetric fp64 matrix, written by libhicmi's multi-threaded host formatter
+    (hicmi_write_hicpro_matrix); returns the number of lines."""
+    mat = np.ascontiguousarray(mat, dtype=np.float64)
+    ids = np.ascontiguousarray(bin_ids, dtype=np.int64)
+    if mat.ndim != 2 or mat.shape[0] != mat.shape[1] or mat.shape[0] != len(ids):
+        raise ValueError("mat must be n x n with one bin ID per row")
+    entries = c_i64()
+    _check(load().hicmi_write_hicpro_matrix(os.fsencode(path), _ptr(mat), len(ids), _ptr(ids), int(threads), ctypes.byref(entries)))
+    return entries.value
+
+
+def format_double(v) -> str:
+    """repr(float(v)) as libhicmi's writer formats it (hicmi_format_double)."""
+    buf = ctypes.create_string_buffer(64)
+    _check(load().hicmi_format_double(float(v), buf, 64))
+    return buf.value.decode("ascii")
 
 
 def scan_valid_pairs(path, names, pairs, threads: int = 0):
@@ -305,6 +329,32 @@ class Context:
         _check(self._lib.hicmi_group_sums(self._h, _ptr(g), _ptr(s), int(n_groups), int(n_scaffolds), _ptr(bins),
                                           _ptr(scaffolds)))
         return bins, scaffolds
+
+    # ---- Part 0: ICE balancing
+    def ice_mask_rows(self, mask):
+        """Zero the rows and columns ``mask`` flags in the context's own matrix (hicmi_ice_mask_rows)."""
+        m = np.ascontiguousarray(mask, dtype=np.uint8)
+        if m.shape != (self.n,):
+            raise ValueError("mask must have n entries")
+        _check(self._lib.hicmi_ice_mask_rows(self._h, _ptr(m), self.n))
+
+    def ice_balance(self, mask=None, max_iter=100, eps=0.1):
+        """ICE-balance the context's own matrix in place (hicmi_ice_balance): returns (biases with nan for the masked
+        bins, iterations run, last sum |bias_prev - bias|)."""
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        if m is not None and m.shape != (self.n,):
+            raise ValueError("mask must have n entries")
+        bias = np.empty(self.n, np.float64)
+        iters, delta = c_i64(0), c_dbl(0.0)
+        _check(self._lib.hicmi_ice_balance(self._h, _ptr(m), int(max_iter), float(eps), _ptr(bias), ctypes.byref(iters),
+                                           ctypes.byref(delta)))
+        return bias, int(iters.value), delta.value
+
+    def contacts_host(self):
+        """The context's contact matrix copied to the host (hicmi_get_contact_rows): n x n fp64."""
+        out = np.empty((self.n, self.n), np.float64)
+        _check(self._lib.hicmi_get_contact_rows(self._h, 0, self.n, _ptr(out)))
+        return out
 
     # ---- Part 1
     def upgma(self, want_linkage: bool = True):

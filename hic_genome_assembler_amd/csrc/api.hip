@@ -137,6 +137,9 @@ struct hicmi_ctx {
     // group support (k_group_support.hip): the member lists of a call, and its partials + the two tables
     int32_t* d_gs_lists = nullptr; int64_t gs_lists_cap = 0;
     double* d_gs_sums = nullptr; int64_t gs_sums_cap = 0;
+    // ICE balancing (k_ice.hip): [y][u][bias][bias_prev][s][d][ones] of n each, [mean0, c], (delta, c) per iteration; the mask
+    double* d_ice = nullptr; int64_t ice_cap = 0;
+    uint8_t* d_ice_mask = nullptr; int64_t ice_mask_cap = 0;
     // HMM boundary finder (k_hmm.hip): resident observation matrices, one per slot (T x ld, columns [0, D) in use);
     // the selected slot's view is mirrored in d_hx / hmm_T / hmm_ld / hmm_D for the single-problem entry points.  The
     // work areas are sized for the largest slot built
@@ -378,6 +381,7 @@ int hicmi_destroy(hicmi_ctx* c)
     free_dev(c->d_arr_packed2); free_dev(c->d_pos2sel2); free_dev(c->d_ins_T); free_dev(c->d_ins_partial); free_dev(c->d_brk_recs);
     free_dev(c->d_ins_blob); free_dev(c->d_ins_steps); free_dev(c->d_sup_recs);
     free_dev(c->d_gs_lists); free_dev(c->d_gs_sums);
+    free_dev(c->d_ice); free_dev(c->d_ice_mask);
     free_dev(c->d_plot_order); free_dev(c->d_plot_work); free_dev(c->d_plot_img);
     for (auto& sl : c->hslot) free_dev(sl.d_x);
     free_dev(c->d_hmulti); free_dev(c->d_horder); free_dev(c->d_hwork); free_dev(c->d_hlab); free_dev(c->d_hbt);
@@ -599,6 +603,137 @@ int hicmi_group_sums(hicmi_ctx* c, const int32_t* grp, const int32_t* scaf, int6
     HIPCHK(hipGetLastError());
     if (bin_sums_out) { rc = download(c, bin_sums_out, c->d_gs_sums + o_bin, sizeof(double) * (size_t)(n * G)); if (rc) return rc; }
     return download(c, scaffold_sums_out, c->d_gs_sums + o_sc, sizeof(double) * (size_t)(S * G));
+}
+
+// ---- ICE balancing: HiC-Pro's `ice` step on the resident raw map -------------------------------------
+namespace {
+// the matrix has changed under everything derived from it
+int ice_matrix_changed(hicmi_ctx* c)
+{
+    c->have_sums = false; c->have_rank = false; c->cached_start = -1; c->n2 = 0;
+    if (c->presort_n && c->stream2) HIPCHK(hipStreamSynchronize(c->stream2));
+    c->presort_n = 0;
+    return HICMI_OK;
+}
+
+int ice_check(hicmi_ctx* c, const char* what)
+{
+    if (!c) return fail(HICMI_EINVAL, "NULL context");
+    if (!c->dC) return fail(HICMI_EINVAL, "no contact matrix set");
+    if (c->n > 65536) return fail(HICMI_EUNSUPPORTED, "n = %lld > 65536 bins", (long long)c->n);
+    if (!c->own_c)
+        return fail(HICMI_ESTATE, "%s rewrites the contact matrix: a matrix adopted with hicmi_set_contacts_device is the "
+                                  "caller's and is not touched", what);
+    return HICMI_OK;
+}
+
+int ice_upload_mask(hicmi_ctx* c, const uint8_t* mask)
+{
+    int rc = ensure(c->d_ice_mask, c->ice_mask_cap, c->n);
+    if (!rc) rc = upload(c, c->d_ice_mask, mask, (size_t)c->n);
+    return rc;
+}
+}  // namespace
+
+int hicmi_ice_mask_rows(hicmi_ctx* c, const uint8_t* mask, int64_t n)
+{
+    int rc = ice_check(c, "hicmi_ice_mask_rows");
+    if (rc) return rc;
+    if (!mask || n != c->n) return fail(HICMI_EINVAL, "mask must have n = %lld entries", (long long)c->n);
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = ice_matrix_changed(c))) return rc;
+    if ((rc = ice_upload_mask(c, mask))) return rc;
+    launch_ice_mask(c->dC, c->ldc, (int)c->n, c->d_ice_mask, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(sync_stream(c));
+    return HICMI_OK;
+}
+
+int hicmi_ice_balance(hicmi_ctx* c, const uint8_t* mask, int64_t max_iter, double eps, double* bias_out, int64_t* iters_out,
+                      double* delta_out)
+{
+    int rc = ice_check(c, "hicmi_ice_balance");
+    if (rc) return rc;
+    if (max_iter < 1 || max_iter > (1 << 20)) return fail(HICMI_EINVAL, "max_iter = %lld outside 1 .. 2^20", (long long)max_iter);
+    if (!(eps >= 0.0)) return fail(HICMI_EINVAL, "eps must be >= 0");
+    const char* env = getenv("HICMI_ICE_INPLACE");
+    const bool inplace = env && !strcmp(env, "1");
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = ice_matrix_changed(c))) return rc;
+    const int n = (int)c->n;
+    const int64_t np = ((int64_t)n + 1) & ~(int64_t)1;       // every vector starts 16-byte aligned
+    if ((rc = ensure(c->d_ice, c->ice_cap, 7 * np + 2 + 2 * max_iter))) return rc;
+    double *y = c->d_ice, *u = y + np, *bias = u + np, *prev = bias + np, *s = prev + np, *d = s + np, *ones = d + np,
+           *st = ones + np, *rec = st + 2;
+    if (mask) {
+        if ((rc = ice_upload_mask(c, mask))) return rc;
+        launch_ice_mask(c->dC, c->ldc, n, c->d_ice_mask, c->stream);
+    }
+    launch_ice_fill(u, (int)(4 * np), 1.0, c->stream);       // u, bias, bias_prev (and s)
+    launch_ice_fill(ones, (int)np, 1.0, c->stream);
+    // the raw map's row sums and mean0
+    launch_ice_rowdot(c->dC, c->ldc, n, ones, y, c->stream);
+    launch_ice_vec_b(n, y, nullptr, bias, prev, s, st, rec, 0, 1, c->stream);
+    HIPCHK(hipGetLastError());
+    int64_t iters = 0;
+    double delta = NAN;
+    for (int64_t it = 0; it < max_iter; it++) {
+        if (inplace) {
+            launch_ice_vec_a(n, y, bias, nullptr, d, c->stream);
+            launch_ice_scale(c->dC, c->ldc, n, d, st, 0, c->stream);
+            launch_ice_rowdot(c->dC, c->ldc, n, ones, y, c->stream);
+            launch_ice_vec_b(n, y, nullptr, bias, prev, s, st, rec, (int)it, 0, c->stream);
+            launch_ice_scale(c->dC, c->ldc, n, d, st, 1, c->stream);
+            launch_ice_rowdot(c->dC, c->ldc, n, ones, y, c->stream);      // the next iteration's row sums
+        } else {
+            launch_ice_vec_a(n, s, bias, u, d, c->stream);
+            launch_ice_rowdot(c->dC, c->ldc, n, u, y, c->stream);
+            launch_ice_vec_b(n, y, u, bias, prev, s, st, rec, (int)it, 0, c->stream);
+        }
+        HIPCHK(hipGetLastError());
+        double r[2];
+        if ((rc = download(c, r, rec + 2 * it, sizeof(r)))) return rc;      // the one small record of this iteration
+        iters = it + 1;
+        if (it > 0) {
+            delta = r[0];
+            if (delta < eps) break;
+        }
+    }
+    if (!inplace) {
+        launch_ice_apply(c->dC, c->ldc, n, u, c->stream);
+        HIPCHK(hipGetLastError());
+    }
+    if (bias_out) {
+        if ((rc = download(c, bias_out, bias, sizeof(double) * (size_t)n))) return rc;
+        if (mask)
+            for (int i = 0; i < n; i++)
+                if (mask[i]) bias_out[i] = NAN;
+    } else HIPCHK(sync_stream(c));
+    if (iters_out) *iters_out = iters;
+    if (delta_out) *delta_out = delta;
+    return HICMI_OK;
+}
+
+int hicmi_get_contact_rows(hicmi_ctx* c, int64_t row0, int64_t nrows, double* out)
+{
+    if (!c || !out) return fail(HICMI_EINVAL, "NULL argument");
+    if (!c->dC) return fail(HICMI_EINVAL, "no contact matrix set");
+    if (row0 < 0 || nrows < 0 || row0 + nrows > c->n) return fail(HICMI_EINVAL, "rows out of range");
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t n = c->n;
+    const int64_t block = std::max<int64_t>(1, ((int64_t)64 << 20) / (8 * n));      // rows per staged copy
+    for (int64_t r = 0; r < nrows; r += block) {
+        const int64_t cnt = std::min(block, nrows - r);
+        const size_t bytes = sizeof(double) * (size_t)(cnt * n);
+        int rc = ensure_pin_down(c, bytes);
+        if (rc) return rc;
+        HIPCHK(hipMemcpy2DAsync(c->pin_down, sizeof(double) * (size_t)n, c->dC + (row0 + r) * c->ldc, sizeof(double) * (size_t)c->ldc,
+                                sizeof(double) * (size_t)n, (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(sync_stream(c));
+        memcpy(out + r * n, c->pin_down, bytes);
+    }
+    if (nrows == 0) HIPCHK(sync_stream(c));
+    return HICMI_OK;
 }
 
 int hicmi_selftest_division(hicmi_ctx* c, uint64_t seed, int64_t samples, uint64_t* mismatches_out)

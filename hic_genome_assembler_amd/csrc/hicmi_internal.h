@@ -404,6 +404,17 @@ void launch_group_sums(const double* C, int64_t ld, int n, int G, int S, const i
                        int n_chunks, const int32_t* group_chunk0, const int32_t* scaf, const int32_t* sbins,
                        const int32_t* soff, double* partial, double* binsum, double* scafsum, bool plain, hipStream_t s);
 
+// k_ice.hip: ICE balancing of a raw map (hicmi_ice_balance).  st: [mean0, last c]; rec: (delta, c) per
+// iteration; u == nullptr in the vector steps: the in-place path.
+void launch_ice_fill(double* v, int n, double value, hipStream_t s);
+void launch_ice_rowdot(const double* C, int64_t ld, int n, const double* u, double* y, hipStream_t s);
+void launch_ice_vec_b(int n, const double* y, double* u, double* bias, double* prev, double* sums, double* st,
+                      double* rec, int it, int first, hipStream_t s);
+void launch_ice_vec_a(int n, const double* sums, double* bias, double* u, double* d, hipStream_t s);
+void launch_ice_apply(double* X, int64_t ld, int n, const double* u, hipStream_t s);
+void launch_ice_scale(double* X, int64_t ld, int n, const double* d, const double* st, int by_c, hipStream_t s);
+void launch_ice_mask(double* X, int64_t ld, int n, const uint8_t* mask, hipStream_t s);
+
 // k_plot.hip
 void launch_plot_select(const double* C, int64_t ldc, const double* np_sum, const double* seq_sum, int kind,
                         const int32_t* order, int n_sel, int n_targets, struct SelectState* d_state, unsigned int* d_hist,

@@ -16,6 +16,8 @@
 
 #include <algorithm>
 #include <atomic>
+#include <charconv>
+#include <cmath>
 #include <chrono>
 #include <cstdio>
 #include <clocale>
@@ -360,5 +362,135 @@ extern "C" int hicmi_scan_fetch(void* handle, int32_t* pair_idx, int64_t* pos1, 
     if (!res->hits.empty() && (!pair_idx || !pos1 || !pos2)) return hicmi::set_error(HICMI_EINVAL, "NULL output");
     for (size_t i = 0; i < res->hits.size(); i++) { pair_idx[i] = res->hits[i].pair; pos1[i] = res->hits[i].p1; pos2[i] = res->hits[i].p2; }
     delete res;
+    return HICMI_OK;
+}
+
+// ---- writer of HiC-Pro's *_iced.matrix (-part0) -------------------------------------------------------------------------
+namespace {
+// Python's repr(float): the shortest digits that read back to the same double (std::to_chars), laid out by CPython's
+// rule - fixed notation while the decimal point falls in (-4, 16], else d.ddde+XX with at least two exponent digits
+char* put_repr(char* p, double v)
+{
+    if (std::isnan(v)) { memcpy(p, "nan", 3); return p + 3; }
+    if (std::isinf(v)) { if (v < 0) *p++ = '-'; memcpy(p, "inf", 3); return p + 3; }
+    char buf[48];
+    const auto r = std::to_chars(buf, buf + sizeof(buf), v, std::chars_format::scientific);
+    const char* s = buf;
+    if (*s == '-') *p++ = *s++;
+    const char* e = s;
+    while (e < r.ptr && *e != 'e') e++;
+    char dig[24];
+    int nd = 0;
+    dig[nd++] = s[0];
+    if (s + 1 < e && s[1] == '.')
+        for (const char* q = s + 2; q < e; q++) dig[nd++] = *q;
+    int ex = 0;
+    {
+        const char* q = e + 1;
+        const bool neg = q < r.ptr && *q == '-';
+        if (q < r.ptr && (*q == '-' || *q == '+')) q++;
+        for (; q < r.ptr; q++) ex = ex * 10 + (*q - '0');
+        if (neg) ex = -ex;
+    }
+    const int decpt = ex + 1;
+    if (-4 < decpt && decpt <= 16) {
+        if (decpt <= 0) {
+            *p++ = '0'; *p++ = '.';
+            for (int k = 0; k < -decpt; k++) *p++ = '0';
+            memcpy(p, dig, (size_t)nd); p += nd;
+        } else if (decpt >= nd) {
+            memcpy(p, dig, (size_t)nd); p += nd;
+            for (int k = nd; k < decpt; k++) *p++ = '0';
+            *p++ = '.'; *p++ = '0';
+        } else {
+            memcpy(p, dig, (size_t)decpt); p += decpt;
+            *p++ = '.';
+            memcpy(p, dig + decpt, (size_t)(nd - decpt)); p += nd - decpt;
+        }
+    } else {
+        *p++ = dig[0];
+        if (nd > 1) { *p++ = '.'; memcpy(p, dig + 1, (size_t)(nd - 1)); p += nd - 1; }
+        *p++ = 'e';
+        *p++ = ex < 0 ? '-' : '+';
+        const int a = ex < 0 ? -ex : ex;
+        if (a >= 100) *p++ = (char)('0' + a / 100);
+        *p++ = (char)('0' + a / 10 % 10);
+        *p++ = (char)('0' + a % 10);
+    }
+    return p;
+}
+}  // namespace
+
+extern "C" int hicmi_format_double(double v, char* out, int64_t cap)
+{
+    char buf[64];
+    const int64_t len = put_repr(buf, v) - buf;
+    if (!out || cap < len + 1) return hicmi::set_error(HICMI_EINVAL, "output buffer too small");
+    memcpy(out, buf, (size_t)len);
+    out[len] = 0;
+    return HICMI_OK;
+}
+
+extern "C" int hicmi_write_hicpro_matrix(const char* path, const double* mat, int64_t n, const int64_t* bin_ids, int threads,
+                                         int64_t* entries_out)
+{
+    if (!path || !mat || !bin_ids || n < 0) return hicmi::set_error(HICMI_EINVAL, "bad arguments");
+    std::vector<std::string> ids((size_t)n);
+    for (int64_t i = 0; i < n; i++) ids[(size_t)i] = std::to_string((long long)bin_ids[i]);
+    FILE* fh = fopen(path, "wb");
+    if (!fh) return hicmi::set_error(HICMI_EINVAL, (std::string("cannot open ") + path + " for writing").c_str());
+    int T = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
+    T = std::max(1, std::min(T, 64));
+    constexpr int64_t kRows = 16;                           // rows per work item
+    const int64_t n_items = (n + kRows - 1) / kRows, per_round = (int64_t)T * 4;
+    std::vector<std::string> text((size_t)per_round);
+    std::vector<int64_t> count((size_t)per_round);
+    int64_t entries = 0;
+    bool io_error = false;
+    for (int64_t base = 0; base < n_items && !io_error; base += per_round) {
+        const int64_t here = std::min(per_round, n_items - base);
+        std::atomic<int64_t> next{0};
+        auto work = [&]() {
+            for (;;) {
+                const int64_t k = next.fetch_add(1);
+                if (k >= here) return;
+                std::string& t = text[(size_t)k];
+                t.clear();
+                int64_t cnt = 0;
+                char line[128];
+                const int64_t r0 = (base + k) * kRows, r1 = std::min(n, r0 + kRows);
+                for (int64_t i = r0; i < r1; i++) {
+                    const double* row = mat + i * n;
+                    const std::string& a = ids[(size_t)i];
+                    for (int64_t j = i; j < n; j++) {
+                        if (row[j] == 0.0) continue;
+                        char* p = line;
+                        memcpy(p, a.data(), a.size()); p += a.size();
+                        *p++ = '\t';
+                        const std::string& b = ids[(size_t)j];
+                        memcpy(p, b.data(), b.size()); p += b.size();
+                        *p++ = '\t';
+                        p = put_repr(p, row[j]);
+                        *p++ = '\n';
+                        t.append(line, (size_t)(p - line));
+                        cnt++;
+                    }
+                }
+                count[(size_t)k] = cnt;
+            }
+        };
+        std::vector<std::thread> pool;
+        for (int t = 1; t < T && t < here; t++) pool.emplace_back(work);
+        work();
+        for (auto& th : pool) th.join();
+        for (int64_t k = 0; k < here; k++) {
+            const std::string& t = text[(size_t)k];
+            if (!t.empty() && fwrite(t.data(), 1, t.size(), fh) != t.size()) io_error = true;
+            entries += count[(size_t)k];
+        }
+    }
+    if (fclose(fh) != 0) io_error = true;
+    if (io_error) return hicmi::set_error(HICMI_EINVAL, (std::string("write error on ") + path).c_str());
+    if (entries_out) *entries_out = entries;
     return HICMI_OK;
 }

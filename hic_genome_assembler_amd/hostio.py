@@ -71,6 +71,45 @@ def initiateLoci(bedFile, biasFile, binID_dict=False):
     return bins
 
 
+def read_bed_bins(bedFile):
+    """Every line of a HiC-Pro ``.bed`` file as a Bin, in file order (bias 1.0): what ``-part0`` starts from, before a
+    biases file exists (initiateLoci reads the two files line-aligned and drops the bins whose bias is nan)."""
+    bins = []
+    with open(bedFile) as bed:
+        for bed_line in bed:
+            cols = bed_line.strip("\r").strip("\n").split("\t")
+            bins.append(Bin(int(cols[3]), cols[0], int(cols[1]), int(cols[2]), 1., 0.))
+    return bins
+
+
+def write_biases(biasFile, bias):
+    """HiC-Pro's ``*_iced.matrix.biases`` as initiateLoci reads it: one line per ``.bed`` line, ``repr`` of the bias or
+    ``nan`` for a bin ICE took out."""
+    with open(biasFile, "w") as fh:
+        fh.write("".join("nan\n" if v != v else repr(v) + "\n" for v in np.asarray(bias, dtype=np.float64).tolist()))
+
+
+def write_iced_matrix(matrixFile, mat, bin_ids, engine: str = "native"):
+    """HiC-Pro's ``*_iced.matrix`` from a dense symmetric array: the upper triangle with the diagonal, row then column
+    ascending, non-zero values only, as ``id1<TAB>id2<TAB>value``.  Values are written with ``repr`` (shortest text that
+    reads back to the same double) and not with HiC-Pro's ``%f``, so read_contact_matrix gives back ``mat`` bit for bit.
+    ``engine="native"`` (default) is libhicmi's multi-threaded formatter (csrc/loader.hip) - a 16,000-bin map has a hundred
+    million lines; ``engine="python"`` writes the same bytes with ``repr`` itself and is kept for cross-checking."""
+    if engine == "native":
+        from . import _lib
+        _lib.write_hicpro_matrix(matrixFile, mat, bin_ids)
+        return
+    ids = [str(int(v)) for v in bin_ids]
+    n = len(ids)
+    with open(matrixFile, "w") as fh:
+        for i in range(n):
+            row = mat[i, i:]
+            cols = np.flatnonzero(row)
+            if len(cols):
+                head = ids[i] + "\t"
+                fh.write("".join([head + ids[i + j] + "\t" + repr(v) + "\n" for j, v in zip(cols.tolist(), row[cols].tolist())]))
+
+
 def _cache_paths(matrixFile, cache):
     """Where the binary copy of a parsed matrix lives: next to the text file (cache=True / "1") or in
     the directory given."""

@@ -1,4 +1,4 @@
-"""Command-line driver: ``run_hicAssembler.py [-part1] [-part2] [-part3] [-part4] -config FILE`` - same flags,
+"""Command-line driver: ``run_hicAssembler.py [-part0] [-part1] [-part2] [-part3] [-part4] -config FILE`` - same flags,
 same ``key = value`` config format and same file layout as the reference driver
 (/root/reference/HIC_ASSEMBLER/run_hicAssembler.py, RUN below), with Parts 1 and 2 executed on
 MI355X.  Parts 3 and 4 (read-pair orientation of small scaffolds, FASTA writing) are host-side text
@@ -13,6 +13,8 @@ Config rules kept from the reference parser (RUN:9-245):
  * booleans accept True/true/False/false; malformed numbers keep the default with a warning;
  * every one of the 33 keys must end up non-empty, also those of parts that do not run
    (RUN:221-245); hyperGeom and hmm may not both be True.
+``-part0`` is this build's own: HiC-Pro's ``ice`` step on the device (iceNormalize.py), from the raw map named by the optional
+key ``hicProRawMatrixFile`` to the two files ``hicProMatrixFile`` / ``hicProBiasFile`` that every other part reads.
 One tolerance is added and reported: a non-comment line without `` = `` (both config files shipped
 with the reference contain one and crash its parser with IndexError) is skipped with a warning.
 """
@@ -67,6 +69,11 @@ _OPTIONAL = {"placementSupportFile": "saveFilesDirectory",     # -part2 also wri
              "rescuedChromosomeGroupFile": "saveFilesDirectory",   # ... and the group file with the rescued scaffolds
              "breakSupportFile": "saveFilesDirectory",         # -part2 also writes the break-support report there
              "brokenChromosomeGroupFile": "saveFilesDirectory"}    # ... and the group file with the breakable scaffolds split
+# -part0's keys, optional in the same way: the raw HiC-Pro map (a full path, like the other hicPro* files) and ICE's
+# settings (defaults: ICE_DEFAULTS); a value that does not parse leaves the key out, with a warning
+_OPTIONAL_PART0 = {"hicProRawMatrixFile": str, "iceFilterLowPerc": float, "iceMaxIter": int, "iceEps": float,
+                   "iceMinScaffoldSize": int}
+ICE_DEFAULTS = {"iceFilterLowPerc": 0.02, "iceMaxIter": 100, "iceEps": 0.1, "iceMinScaffoldSize": None}
 
 
 def _convert(values, key, text):
@@ -132,7 +139,37 @@ def readConfigFileToVariables(configFile):
                 _convert(values, key, text)
             elif key in _OPTIONAL and text:
                 values[key] = values[_OPTIONAL[key]] + '/' + text
+            elif key in _OPTIONAL_PART0 and text:
+                try:
+                    values[key] = _OPTIONAL_PART0[key](text)
+                except ValueError:
+                    print("WARNING... {0} must be {1}... ignoring {0}".format(
+                        key, "an integer value" if _OPTIONAL_PART0[key] is int else "a floating point value"))
     return values
+
+
+def part0Settings(v):
+    """-part0's arguments from the config dictionary; exits with a message when they cannot be used."""
+    if "hicProRawMatrixFile" not in v:
+        sys.exit("ERROR... -part0 needs the raw HiC-Pro matrix: set \"hicProRawMatrixFile = <full path>\" in the config "
+                 "file (the triplet file HiC-Pro writes before its ice step). Exiting...")
+    raw = v["hicProRawMatrixFile"]
+    for key in ("hicProMatrixFile", "hicProBiasFile"):
+        same = os.path.realpath(raw) == os.path.realpath(v[key])
+        if not same and os.path.exists(raw) and os.path.exists(v[key]):
+            same = os.path.samefile(raw, v[key])
+        if same:
+            sys.exit("ERROR... hicProRawMatrixFile and {0} are the same file ({1}): -part0 writes {0} and would overwrite "
+                     "its own input. Exiting...".format(key, raw))
+    s = dict(ICE_DEFAULTS)
+    s.update({k: v[k] for k in ICE_DEFAULTS if k in v})
+    if not 0. <= s["iceFilterLowPerc"] < 1.:
+        sys.exit("ERROR... iceFilterLowPerc must be a value in [0.0, 1.0). Exiting...")
+    if s["iceMaxIter"] < 1:
+        sys.exit("ERROR... iceMaxIter must be at least 1. Exiting...")
+    if not s["iceEps"] >= 0.:
+        sys.exit("ERROR... iceEps must not be negative. Exiting...")
+    return raw, s
 
 
 def ensureAllVariablesAreSet(varDict):
@@ -163,6 +200,8 @@ def ensureAllVariablesAreSet(varDict):
 
 def _parse_args(argv):
     parser = argparse.ArgumentParser(description="Runs the parts of the HiC assembly pipeline (Parts 1 and 2 on MI355X).")
+    parser.add_argument("-part0", help="Run part0: ICE-balance the raw HiC-Pro map (hicProRawMatrixFile) on the GPU and write "
+                                       "hicProMatrixFile and hicProBiasFile", action='store_true')
     for k in (1, 2, 3, 4):
         parser.add_argument("-part%d" % k, help="Run part%d of the pipeline" % k, action='store_true')
     parser.add_argument("-config", help="Full file path to the config file. All arguments must have a value",
@@ -178,6 +217,16 @@ def main(argv=None):
     if ensureAllVariablesAreSet(v):
         sys.exit()
     resident = None
+    balanced = None
+    if args.part0:
+        raw, ice = part0Settings(v)
+        from . import iceNormalize as part0
+        # -part0 -part1 in one run: the balanced matrix, compacted to the bins ICE kept, stays in HBM for Part 1
+        # (HICMI_ICE_REPARSE=1: Part 1 parses the file just written instead)
+        keep0 = bool(args.part1) and not os.environ.get("HICMI_ICE_REPARSE")
+        balanced = part0.runPipeline(v["hicProBedFile"], raw, v["hicProScaffSizeFile"], v["hicProMatrixFile"],
+                                     v["hicProBiasFile"], ice["iceFilterLowPerc"], ice["iceMaxIter"], ice["iceEps"],
+                                     ice["iceMinScaffoldSize"], device=args.device, keep_resident=keep0)
     if args.part1:
         from . import scaffoldToChromosomes as part1
         # -part1 -part2 in one run: the contact matrix stays in HBM for Part 2 (the reference parses the text matrix a
@@ -188,7 +237,7 @@ def main(argv=None):
                                      v["binGroupFile"], v["assessmentFile"], v["chromosomeGroupFile"],
                                      v["hyperGeom"], v["hmm"], v["minSize"], v["modularity"], v["louvainRounds"],
                                      v["psig"], v["convergenceRounds"], v["lookAhead"], v["resolution"], device=args.device,
-                                     keep_resident=keep,
+                                     keep_resident=keep, contacts_ctx=balanced,
                                      **{k: v[k] for k in ("groupSupportFile", "rescuedChromosomeGroupFile") if k in v})
     if args.part2:
         from . import orderGenome as part2

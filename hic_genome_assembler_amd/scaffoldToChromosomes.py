@@ -1037,13 +1037,16 @@ def runPipeline(hicProBedFile, hicProBiasFile, hicProMatrixFile, hicProScaffSize
                 binGroupFile, assessmentFile, chromosomeGroupFile,
                 hyperGeom, hmm, minSize, modularity, louvainRounds,
                 psig, convergenceRounds, lookAhead, resolution, device=0, shard=None, keep_resident=False,
-                groupSupportFile=None, rescuedChromosomeGroupFile=None):
+                groupSupportFile=None, rescuedChromosomeGroupFile=None, contacts_ctx=None):
     """S2C:1104-1174, same positional arguments (``device``, ``shard``, ``keep_resident`` and the two file names are
     optional extras; ``groupSupportFile`` / ``rescuedChromosomeGroupFile``: also write the group-support report and the
     group file with the rescued scaffolds (groupSupport) from the resident map;
     ``shard=(rank, world)``: this process is one of ``world`` that work on the same map, see runResident;
     ``keep_resident=True``: the context with the contact matrix in HBM is not closed but returned as
-    ``(DeviceMatrix, bins of its rows)`` so that Part 2 of the same run need not parse the text matrix again)."""
+    ``(DeviceMatrix, bins of its rows)`` so that Part 2 of the same run need not parse the text matrix again;
+    ``contacts_ctx``: a context that already holds the matrix of exactly the bins the two files give - ``-part0`` of the
+    same run (iceNormalize.runPipeline(..., keep_resident=True)) - used in place of the text parse; it is closed like
+    a context made here)."""
     print("########################################")
     print("### Working on Part1 of the pipeline ###")
     t_all = time.time()
@@ -1052,7 +1055,14 @@ def runPipeline(hicProBedFile, hicProBiasFile, hicProMatrixFile, hicProScaffSize
         raise NotImplementedError("only the hyperGeom = True strategy is implemented on MI355X by default; hmm = True "
                                   "(hmmlearn's EM, restated with a seeded initialisation) needs HICMI_HMM=1")
     binList = initiateLoci(hicProBedFile, hicProBiasFile)
-    adjMat = buildAdjacencyMatrix(hicProMatrixFile, binList, device=device)
+    if contacts_ctx is not None:
+        if contacts_ctx.n != len(binList):
+            contacts_ctx.close()
+            raise ValueError("the resident matrix has %d rows, the bed and biases files give %d bins" % (contacts_ctx.n, len(binList)))
+        print("Rows in adjacency matrix " + str(len(binList)))
+        adjMat = DeviceMatrix(contacts_ctx)
+    else:
+        adjMat = buildAdjacencyMatrix(hicProMatrixFile, binList, device=device)
     try:
         cutIndices = runResident(adjMat, binList, hicProScaffSizeFile, dendrogramOrderFile, binGroupFile,
                                  assessmentFile, chromosomeGroupFile, minSize, modularity, psig,

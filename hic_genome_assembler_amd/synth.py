@@ -177,9 +177,50 @@ def sparsify(contacts: np.ndarray, zero_fraction: float, decimals: int) -> np.nd
     return np.ascontiguousarray(c)
 
 
+def make_raw_counts(layout: Layout, seed: int = 1, depth: float = 200.0, sigma: float = 0.5, inter: float = 0.02,
+                    dead_bins=(), short_scaffolds: int = 0, short_size_bp: int = 5000):
+    """A raw (unbalanced) count map, what HiC-Pro writes before its ``ice`` step, and the layout that goes with it.
+
+    The planted map of :func:`dense_contacts` without its noise - ``1 / (1 + |p_i - p_j|)`` inside a chromosome,
+    ``inter`` between chromosomes - times ``depth`` and the per-bin factors ``g_i g_j`` (log-normal, ``sigma``: the
+    visibility biases ICE is there to remove), Poisson-sampled on the upper triangle and mirrored: symmetric integer
+    counts as fp64.  (``inter`` is well above :func:`dense_contacts`' 4e-4: between blocks that share no reads the ICE
+    iteration swings for ever - each block's row sums go from above the mean to below it and back - and the fewer reads
+    they share, the slower that swing dies out.)  ``dead_bins``: bins (indices in ``.bed`` order) without a single
+    read.  ``short_scaffolds``: that many scaffolds - those with the fewest bins, the lowest index first - get the size
+    ``short_size_bp`` in the returned layout (and their bins' coordinates are clipped to it): the scaffolds an
+    ``iceMinScaffoldSize`` above that drops.  The input layout is not changed."""
+    import dataclasses
+    n = layout.n_bins
+    rng = np.random.default_rng(seed + 104729)
+    g = np.exp(rng.normal(0.0, sigma, size=n))
+    p = layout.pos_of_bin.astype(np.float64)
+    same = layout.chrom_of_bin[:, None] == layout.chrom_of_bin[None, :]
+    lam = np.where(same, 1.0 / (1.0 + np.abs(p[:, None] - p[None, :])), inter) * depth
+    lam *= g[:, None]
+    lam *= g[None, :]
+    c = np.triu(rng.poisson(lam).astype(np.float64))
+    c = c + np.triu(c, 1).T
+    for b in dead_bins:
+        c[int(b), :] = 0.0
+        c[:, int(b)] = 0.0
+    if short_scaffolds:
+        bins_of = np.bincount(layout.scaffold_of_bin, minlength=len(layout.scaffold_names))
+        pick = np.argsort(bins_of, kind="stable")[:int(short_scaffolds)]
+        sizes = layout.scaffold_sizes_bp.copy()
+        sizes[pick] = int(short_size_bp)
+        in_pick = np.isin(layout.scaffold_of_bin, pick)
+        layout = dataclasses.replace(layout, scaffold_sizes_bp=sizes,
+                                     start=np.where(in_pick, np.minimum(layout.start, short_size_bp), layout.start),
+                                     stop=np.where(in_pick, np.minimum(layout.stop, short_size_bp), layout.stop))
+    return np.ascontiguousarray(c), layout
+
+
 def write_hicpro(out_dir: str, layout: Layout, contacts, prefix: str = "synth",
-                 nan_bias_bins=()) -> dict:
+                 nan_bias_bins=(), raw_counts=None) -> dict:
     """Write ``.bed``, ``.biases``, ``.matrix`` (upper-triangle triplets) and the scaffold size file.
+    ``raw_counts`` (a :func:`make_raw_counts` map): also write HiC-Pro's raw ``.matrix`` (integer triplets) beside them;
+    its path is returned under ``hicProRawMatrixFile``.
     ``contacts=None``: a one-line placeholder ``.matrix`` (for runs that read the matrix from its binary cache,
     hostio.read_contact_matrix_cached - a 16,000-bin text file has 128 M lines).
 
@@ -215,14 +256,21 @@ def write_hicpro(out_dir: str, layout: Layout, contacts, prefix: str = "synth",
     with open(paths["hicProScaffSizeFile"], "w") as fh:
         for name, size in zip(layout.scaffold_names, layout.scaffold_sizes_bp):
             fh.write("%s\t%d\n" % (name, size))
+    if raw_counts is not None:
+        paths["hicProRawMatrixFile"] = os.path.join(out_dir, prefix + ".matrix")
+        with open(paths["hicProRawMatrixFile"], "w") as fh:
+            for i in range(n):
+                row = raw_counts[i]
+                fh.write("".join("%d\t%d\t%d\n" % (ids[i], ids[i + j], row[i + j]) for j in np.flatnonzero(row[i:])))
     return paths
 
 
 def write_config(path: str, hicpro_paths: dict, save_dir: str, plot_dir: str, resolution: int,
                  min_size: int = 5, modularity: float = 0.0, psig: float = 0.05,
-                 n_scaffolds: int = 6, scan_scaffolds: int = 5) -> str:
+                 n_scaffolds: int = 6, scan_scaffolds: int = 5, extra=None) -> str:
     """Write a config in the reference's ``key = value`` format with every key set
-    (run_hicAssembler.py:221-245 refuses empty values even for parts that do not run)."""
+    (run_hicAssembler.py:221-245 refuses empty values even for parts that do not run).  ``extra``: further
+    ``key: value`` lines (the optional keys, e.g. ``-part0``'s)."""
     os.makedirs(save_dir, exist_ok=True)
     os.makedirs(plot_dir, exist_ok=True)
     lines = [
@@ -262,6 +310,7 @@ def write_config(path: str, hicpro_paths: dict, save_dir: str, plot_dir: str, re
         "originalFastaFile = /dev/null",
         "assembledFastaFile = assembled.fasta",
     ]
+    lines += ["%s = %s" % (k, val) for k, val in (extra or {}).items()]
     with open(path, "w") as fh:
         fh.write("\n".join(lines) + "\n")
     return path

@@ -72,6 +72,16 @@ int hicmi_contacts_device(hicmi_ctx *ctx, void **d_contacts_out, int64_t *n_out,
 int hicmi_load_hicpro_matrix(const char *path, const int64_t *bin_ids, int64_t n, double *out, int threads,
                              int64_t *edges_out);
 
+/* Host-side writer (no GPU involved) of HiC-Pro's *_iced.matrix, the file hicmi_load_hicpro_matrix reads (replaces the
+ * `%f` output of HiC-Pro's ice script; -part0): the upper triangle with the diagonal of the dense n x n matrix `mat`, row
+ * then column ascending, non-zero values only, "id1<TAB>id2<TAB>value" with bin_ids[i] the ID of row i.  Values are
+ * written as Python's repr(float) writes them - the shortest digits that read back to the same double - so the loader
+ * gives back `mat` bit for bit.  threads <= 0: all hardware threads.  entries_out (may be NULL): lines written.
+ * hicmi_format_double: that text of one value (NUL-terminated; cap >= 32), for tests. */
+int hicmi_write_hicpro_matrix(const char *path, const double *mat, int64_t n, const int64_t *bin_ids, int threads,
+                              int64_t *entries_out);
+int hicmi_format_double(double v, char *out, int64_t cap);
+
 /* Row sums, both flavours the reference uses:
  *   np_sum[i]  = row.sum() as NumPy reduces it (pairwise, 8192-element chunks)   S2C:112, S2C:147
  *   seq_sum[i] = builtin sum() left to right                                     S2C:134
@@ -505,6 +515,33 @@ int hicmi_louvain_modularity(hicmi_ctx *ctx, const int32_t *parts, int64_t round
  * Device scratch: (grouped rows / 64 + n_groups) x n partials and the two tables; n_groups <= 65536. */
 int hicmi_group_sums(hicmi_ctx *ctx, const int32_t *grp, const int32_t *scaf, int64_t n_groups, int64_t n_scaffolds,
                      double *bin_sums_out, double *scaffold_sums_out);
+
+/* ---- Part 0: ICE balancing of a raw map ----------------------------------------
+ * Replaces HiC-Pro's `ice` step (ice --filter_low_counts_perc 0.02 --filter_high_counts_perc 0 --max_iter 100 --eps 0.1
+ * --remove-all-zeros-loci --output-bias 1; iced.normalization.ICE_normalization and iced.filter), which the reference
+ * expects to have run before its loaders (S2C:35-98 read its two output files).  Both calls rewrite the context's OWN
+ * contact matrix (uploaded or compacted; leading dimension honoured): a matrix adopted with hicmi_set_contacts_device is
+ * the caller's and is refused with HICMI_ESTATE, untouched.  Row sums, rank matrix and Part 2 selection of the context
+ * are invalidated.
+ *
+ * hicmi_ice_mask_rows replaces iced.filter's zeroing of the filtered loci: rows and columns i with mask[i] != 0 of the
+ * resident matrix become 0 (n = the matrix size).  The row weights the mask rules need come from hicmi_row_sums. */
+int hicmi_ice_mask_rows(hicmi_ctx *ctx, const uint8_t *mask, int64_t n);
+/* hicmi_ice_balance replaces iced.normalization.ICE_normalization (HiC-Pro's `ice` proper): with X = C (masked rows and
+ * columns zeroed first; mask may be NULL), bias = 1, mean0 = sum X / n^2, for it = 0 .. max_iter - 1:
+ *   s_i = sum_j X_ij;  d_i = s_i / mean(s over s != 0), 1 where s_i == 0;  bias_i *= d_i;  X_ij /= d_i d_j;
+ *   c = (sum X / n^2) / mean0;  bias *= sqrt(c);  X /= c;  stop if it > 0 and sum_i |bias_prev_i - bias_i| < eps.
+ * The resident matrix becomes X (exactly symmetric, masked rows and columns exactly 0).  bias_out (n, may be NULL): the
+ * biases, NaN for masked bins; *iters_out: iterations run (max_iter when it did not converge: not an error);
+ * *delta_out: the last sum |bias_prev - bias| (NaN when fewer than two iterations ran).
+ * By default X is never formed during the loop: with u = 1 / bias, s_i = u_i sum_j C_ij u_j is one read-only pass over
+ * the raw map per iteration, every sum in a fixed order (two calls give the same bits), and X_ij = C_ij (u_i u_j) once at
+ * the end.  HICMI_ICE_INPLACE=1 in the environment rescales the matrix in place every iteration instead (the A/B). */
+int hicmi_ice_balance(hicmi_ctx *ctx, const uint8_t *mask, int64_t max_iter, double eps, double *bias_out,
+                      int64_t *iters_out, double *delta_out);
+/* Copy rows [row0, row0+nrows) of the context's contact matrix to the host, n doubles per row (the balanced map for the
+ * writer of HiC-Pro's *_iced.matrix file; tests). */
+int hicmi_get_contact_rows(hicmi_ctx *ctx, int64_t row0, int64_t nrows, double *out);
 
 /* ---- timing ----------------------------------------------------------------------------------
  * Accumulated device time (HIP events on the context stream) per kernel family since the last
