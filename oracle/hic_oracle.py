@@ -293,8 +293,12 @@ def pre_process_all_matrix_breakpoints(R, min_size=5, min_frac=.05, trace=None):
     return cuts
 
 
-def filter_noisy_breakpoints(R, original_inds, psig=.05, trace=None):
-    """S2C:553-727."""
+def filter_noisy_breakpoints(R, original_inds, psig=.05, trace=None, stats=None):
+    """S2C:553-727.  ``stats``: a dict that receives the counts of outer passes (``passes``), rounds (``rounds``) and
+    exits through the MAX_ROUNDS guard (``max_rounds_exits``, one warning line each in the reference, S2C:592-595);
+    ``trace`` entries carry the segments of their scan as (lo, hi, flagged rows)."""
+    if stats is not None:
+        stats.update(passes=0, rounds=0, max_rounds_exits=0)
     if len(original_inds) == 0:
         return []
     n = R.shape[0]
@@ -306,8 +310,12 @@ def filter_noisy_breakpoints(R, original_inds, psig=.05, trace=None):
         start = 0
         filtered = {}
         round_count = 0
+        if stats is not None:
+            stats["passes"] += 1
         while True:
             if round_count >= MAX_ROUNDS:
+                if stats is not None:
+                    stats["max_rounds_exits"] += 1
                 break
             M = n - start
             noise_found = 0
@@ -322,7 +330,7 @@ def filter_noisy_breakpoints(R, original_inds, psig=.05, trace=None):
                 pvals = np.zeros(n, dtype=np.int64)
                 pvals[rows] = np.where(pv < psig, 1, 0)            # NaN -> 0 here (S2C:633-636)
                 if trace is not None:
-                    trace.append(dict(start=start, c=c, M=M, x=x.copy(), sig=pvals[rows].copy()))
+                    trace.append(dict(start=start, c=c, M=M, x=x.copy(), sig=pvals[rows].copy(), altered=list(altered), seg=[]))
                 sigs = []
                 fc_prev = start
                 right_most = None
@@ -335,6 +343,8 @@ def filter_noisy_breakpoints(R, original_inds, psig=.05, trace=None):
                     if len(ps) == 0:
                         break
                     xx = int(ps.sum())
+                    if trace is not None:
+                        trace[-1]["seg"].append((int(fc_prev - len(ps)), int(ai), xx))
                     noise_p = float(hyper_geom(xx, M, local, len(ps)))
                     if noise_p < psig:
                         right_most = ai
@@ -350,6 +360,8 @@ def filter_noisy_breakpoints(R, original_inds, psig=.05, trace=None):
                     filtered[c] = ''
                     select_from = i
             round_count += 1
+            if stats is not None:
+                stats["rounds"] += 1
             if noise_found == 0:
                 break
             altered = altered[select_from:]
