@@ -40,6 +40,7 @@ SIGNATURES = {
     "hicmi_set_row_shard": (ctypes.c_int, [_vp, c_i64, c_i64]),
     "hicmi_set_row_sums": (ctypes.c_int, [_vp, _vp, _vp]),
     "hicmi_compact": (ctypes.c_int, [_vp, _vp, c_i64]),
+    "hicmi_rebin": (ctypes.c_int, [_vp, _vp, c_i64]),
     "hicmi_group_sums": (ctypes.c_int, [_vp, _vp, _vp, c_i64, c_i64, _vp, _vp]),
     "hicmi_get_contact_rows": (ctypes.c_int, [_vp, c_i64, c_i64, _vp]),
     "hicmi_ice_mask_rows": (ctypes.c_int, [_vp, _vp, c_i64]),
@@ -293,6 +294,13 @@ class Context:
         self.n = n
         self._keepalive = keepalive
 
+    def contacts_device(self):
+        """(device address, n, leading dimension) of the context's contact matrix (hicmi_contacts_device), for a
+        further context on the same GPU to adopt with set_contacts_device(..., keepalive=this context)."""
+        ptr, n, ld = _vp(), c_i64(), c_i64()
+        _check(self._lib.hicmi_contacts_device(self._h, ctypes.byref(ptr), ctypes.byref(n), ctypes.byref(ld)))
+        return ptr.value, n.value, ld.value
+
     def row_sums(self):
         np_sum = np.empty(self.n, np.float64)
         seq = np.empty(self.n, np.float64)
@@ -316,6 +324,15 @@ class Context:
         keep = np.ascontiguousarray(keep, dtype=np.int32)
         _check(self._lib.hicmi_compact(self._h, _ptr(keep), len(keep)))
         self.n = len(keep)
+
+    def rebin(self, group_start):
+        """Sum the context's raw map to coarser bins (hicmi_rebin): coarse bin I is the fine bins
+        [group_start[I], group_start[I + 1]); the m x m result replaces the context's matrix."""
+        g = np.ascontiguousarray(group_start, dtype=np.int32)
+        if g.ndim != 1 or len(g) < 2:
+            raise ValueError("group_start must have m + 1 >= 2 entries")
+        _check(self._lib.hicmi_rebin(self._h, _ptr(g), len(g) - 1))
+        self.n = len(g) - 1
 
     def group_sums(self, grp, scaf, n_groups, n_scaffolds, want_bins=True):
         """Group support sums (hicmi_group_sums): (bin sums n x n_groups or None, scaffold sums

@@ -543,6 +543,56 @@ int hicmi_compact(hicmi_ctx* c, const int32_t* keep, int64_t n_keep)
     return compute_sums(c);
 }
 
+// A coarser map from the resident raw one: HiC-Pro's build_matrix re-run at k times the bin size.  Like
+// hicmi_compact, the result replaces the context's matrix state and an adopted source is only read.
+int hicmi_rebin(hicmi_ctx* c, const int32_t* group_start, int64_t m)
+{
+    if (!c || !group_start) return fail(HICMI_EINVAL, "bad arguments");
+    if (!c->dC) return fail(HICMI_EINVAL, "no contact matrix set");
+    const int64_t n = c->n;
+    if (m < 1 || m > n) return fail(HICMI_EINVAL, "m = %lld outside 1 .. n = %lld", (long long)m, (long long)n);
+    if (group_start[0] != 0 || group_start[m] != n)
+        return fail(HICMI_EINVAL, "group_start must run from 0 to n = %lld", (long long)n);
+    for (int64_t i = 0; i < m; i++)
+        if (group_start[i + 1] <= group_start[i]) return fail(HICMI_EINVAL, "group_start must be strictly ascending");
+    for (int64_t i = 0; i < m; i++)
+        if (group_start[i + 1] - group_start[i] > REBIN_MAX_WIDTH)
+            return fail(HICMI_EUNSUPPORTED, "coarse bin %lld has %d fine bins: at most %d", (long long)i,
+                        group_start[i + 1] - group_start[i], REBIN_MAX_WIDTH);
+    const char* env = getenv("HICMI_REBIN_PLAIN");
+    const bool plain = env && !strcmp(env, "1");
+    // one image of both lists: group_start, then chunk_first
+    const int64_t n_chunks = (n + REBIN_CHUNK - 1) / REBIN_CHUNK;
+    std::vector<int32_t> img((size_t)(m + 1 + n_chunks + 1));
+    memcpy(img.data(), group_start, sizeof(int32_t) * (size_t)(m + 1));
+    {
+        int64_t J = 0;
+        for (int64_t ch = 0; ch <= n_chunks; ch++) {
+            while (J < m && group_start[J + 1] <= ch * REBIN_CHUNK) J++;
+            img[(size_t)(m + 1 + ch)] = (int32_t)J;
+        }
+    }
+    HIPCHK(hipSetDevice(c->device));
+    int32_t* d_lists = nullptr; double* d_new = nullptr;
+    struct Guard { int32_t*& a; double*& b; ~Guard() { free_dev(a); free_dev(b); } } guard{d_lists, d_new};   // error paths
+    HIPCHK(hipMalloc((void**)&d_lists, sizeof(int32_t) * img.size()));
+    HIPCHK(hipMalloc((void**)&d_new, sizeof(double) * (size_t)m * (size_t)m));
+    {
+        int rc_up = upload(c, d_lists, img.data(), sizeof(int32_t) * img.size());
+        if (rc_up) return rc_up;
+    }
+    launch_rebin(c->dC, c->ldc, (int)n, d_lists, d_lists + m + 1, (int)m, d_new, plain, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(sync_stream(c));
+    free_dev(d_lists); d_lists = nullptr;
+    double* kept = d_new; d_new = nullptr;                     // ownership moves to the context below
+    drop_matrix_state(c);
+    c->dC = kept; c->own_c = true; c->n = m; c->ldc = m;
+    int rc = alloc_sums(c);
+    if (rc) return rc;
+    return compute_sums(c);
+}
+
 // Group support: extends the scaffold vote of assessChromosomeClustering (S2C:1001-1077) with the
 // contacts themselves.  The host sorts the grouped rows by group and cuts them into chunks of GS_CHUNK; the kernels of
 // k_group_support.hip read every grouped row once.

@@ -415,6 +415,13 @@ void launch_ice_apply(double* X, int64_t ld, int n, const double* u, hipStream_t
 void launch_ice_scale(double* X, int64_t ld, int n, const double* d, const double* st, int by_c, hipStream_t s);
 void launch_ice_mask(double* X, int64_t ld, int n, const uint8_t* mask, hipStream_t s);
 
+// k_rebin.hip: a raw map summed to a coarser resolution (hicmi_rebin).  group_start: m + 1 entries;
+// chunk_first[c], c = 0 .. ceil(n / REBIN_CHUNK): the coarse columns with group_start[J + 1] <= c * REBIN_CHUNK.  R: m x m.
+static constexpr int REBIN_MAX_WIDTH = 64;    // fine bins per coarse bin
+static constexpr int REBIN_CHUNK = 1024;      // fine columns a workgroup of k_rebin holds column sums of at a time
+void launch_rebin(const double* C, int64_t ld, int n, const int32_t* group_start, const int32_t* chunk_first, int m,
+                  double* R, bool plain, hipStream_t s);
+
 // k_plot.hip
 void launch_plot_select(const double* C, int64_t ldc, const double* np_sum, const double* seq_sum, int kind,
                         const int32_t* order, int n_sel, int n_targets, struct SelectState* d_state, unsigned int* d_hist,

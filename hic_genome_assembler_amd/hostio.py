@@ -82,6 +82,39 @@ def read_bed_bins(bedFile):
     return bins
 
 
+def write_bed(bedFile, binList):
+    """A HiC-Pro ``.bed`` file as read_bed_bins and initiateLoci read it: ``name<TAB>start<TAB>stop<TAB>ID`` per bin."""
+    with open(bedFile, "w") as fh:
+        fh.write("".join("%s\t%d\t%d\t%d\n" % (b.chrom, b.start, b.stop, b.ID) for b in binList))
+
+
+def rebin_bins(binList, k):
+    """The bins of the k times coarser map: every scaffold - a maximal run of consecutive ``.bed`` lines with
+    one name - is cut into groups of ``k`` lines from its first line, the last group of a scaffold keeping what is left.
+    Returns (coarse bin list, group_start): coarse bin I covers the fine lines [group_start[I], group_start[I + 1]), runs
+    from its first line's start to its last line's stop and has the ID I + 1.  A scaffold whose lines are not contiguous
+    is refused with ValueError: its bins could not be merged from the scaffold's own start."""
+    k = int(k)
+    if k < 1:
+        raise ValueError("the rebinning factor must be at least 1")
+    coarse, group_start, closed = [], [0], set()
+    n, i = len(binList), 0
+    while i < n:
+        name = binList[i].chrom
+        if name in closed:
+            raise ValueError("the lines of scaffold %s are not contiguous in the bed file (line %d)" % (name, i + 1))
+        closed.add(name)
+        j = i
+        while j < n and binList[j].chrom == name:
+            j += 1
+        for g in range(i, j, k):
+            e = min(g + k, j)
+            coarse.append(Bin(len(coarse) + 1, name, binList[g].start, binList[e - 1].stop, 1., 0.))
+            group_start.append(e)
+        i = j
+    return coarse, np.asarray(group_start, dtype=np.int32)
+
+
 def write_biases(biasFile, bias):
     """HiC-Pro's ``*_iced.matrix.biases`` as initiateLoci reads it: one line per ``.bed`` line, ``repr`` of the bias or
     ``nan`` for a bin ICE took out."""

@@ -105,6 +105,26 @@ int hicmi_set_row_sums(hicmi_ctx *ctx, const double *np_sum, const double *seq_s
  * device matrix is left untouched). */
 int hicmi_compact(hicmi_ctx *ctx, const int32_t *keep, int64_t n_keep);
 
+/* A coarser raw map from the resident one.  Replaces a re-run of HiC-Pro's build_matrix at k
+ * times the bin size (the reference starts from HiC-Pro's files, S2C:35-98, and its README asks for "a resolution size
+ * of 100-500Kb"): HiC-Pro cuts every scaffold into bins from its own start, so the bins of the coarser map are runs of
+ * consecutive fine bins of one scaffold and its raw counts are sums of the fine ones.
+ * group_start: m + 1 strictly ascending entries from 0 to n; coarse bin I is the fine bins [group_start[I],
+ * group_start[I + 1]), at most 64 of them.  On the context's contact matrix C as it stands (uploaded, compacted, or
+ * adopted with ld >= n):
+ *   R[I][J] = sum of C[i][j] over i in I, j in J                      (I != J)
+ *   R[I][I] = sum of C[i][j] over i <= j, both in I: the dense map holds a read pair between two different bins twice, a
+ *             pair inside one bin once, and two fine bins that fall into one coarse bin turn their pairs into such pairs.
+ * So the sum over the upper triangle with the diagonal - the read pairs - is the same for R and C.  Like hicmi_compact:
+ * the m x m result is owned by the context (ld = m) and replaces its matrix state, both row sums are recomputed on it,
+ * and an adopted source is left untouched.  R is exactly symmetric and two calls give the same bits: every sum has a
+ * fixed order (the columns of J left to right, each column's rows of I top to bottom) and R[J][I] is a copy of R[I][J];
+ * for integer counts below 2^53 every order is exact.  HICMI_REBIN_PLAIN=1 in the environment takes the
+ * one-thread-per-cell kernel instead (the A/B), with the same bits.
+ * HICMI_EINVAL: no matrix set, m < 1, m > n, group_start not from 0 to n or not strictly ascending; HICMI_EUNSUPPORTED: a
+ * coarse bin of more than 64 fine bins.  After either the context is unchanged. */
+int hicmi_rebin(hicmi_ctx *ctx, const int32_t *group_start, int64_t m);
+
 /* ---- Part 1: clustering ---------------------------------------------------------------------
  * convertMatrix(distance) + squareform + scipy average + dendrogram leaf order
  * (S2C:138-155, S2C:187-208).  Z_out: (n-1) x 4 doubles in SciPy's linkage convention (may be
