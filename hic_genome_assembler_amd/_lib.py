@@ -680,73 +680,60 @@ class Context:
         self._n_window_cand = o.shape[0] * r.shape[0]
         return a, b, bst.value, int(rounds.value), total.value
 
+    def _table_call(self, fn, ids, rev, table, args):
+        """One chromosome's table call: hicmi_p2_support / hicmi_p2_breaks(handle, ids, rev, S, *args, table, best)."""
+        a = np.ascontiguousarray(ids, dtype=np.int32)
+        b = np.ascontiguousarray(rev, dtype=np.uint8)
+        best = np.empty((len(a), 2), np.int32)
+        _check(fn(self._h, _ptr(a), _ptr(b), len(a), *args, _ptr(table), _ptr(best)))
+        self._arr_sig, self._arr_len = a.tobytes() + b.tobytes(), len(a)
+        return table, best
+
+    @staticmethod
+    def _table_multi(fn_name, jobs, totals, shape_of, args=()):
+        """The marshalling of hicmi_p2_support_multi / hicmi_p2_breaks_multi: jobs [(context, ids, rev, ...)], one table of
+        ``shape_of(job, S)`` per job, ``args`` between the totals and the outputs; returns [(table, best)]."""
+        n = len(jobs)
+        if n == 0:
+            return []
+        a_l = [np.ascontiguousarray(j[1], dtype=np.int32) for j in jobs]
+        b_l = [np.ascontiguousarray(j[2], dtype=np.uint8) for j in jobs]
+        t_l = [np.empty(shape_of(j, len(a)), np.float64) for j, a in zip(jobs, a_l)]
+        o_l = [np.empty((len(a), 2), np.int32) for a in a_l]
+        handles = (ctypes.c_void_p * n)(*[j[0]._h for j in jobs])
+        pa, pb, pt, po = ((ctypes.c_void_p * n)(*[x.ctypes.data for x in arrs]) for arrs in (a_l, b_l, t_l, o_l))
+        sizes = (c_i64 * n)(*[len(a) for a in a_l])
+        _check(getattr(jobs[0][0]._lib, fn_name)(n, handles, pa, pb, sizes, (c_dbl * n)(*map(float, totals)), *args, pt, po))
+        for j, a, b in zip(jobs, a_l, b_l):
+            j[0]._arr_sig, j[0]._arr_len = a.tobytes() + b.tobytes(), len(a)
+        return list(zip(t_l, o_l))
+
     def p2_support(self, ids, rev, total: float):
         """Placement support of one chromosome (hicmi_p2_support): (S x S x 2 table of closed-form scores,
         S x 2 int32 of [first maximum 2 g + r among the candidates that differ from the arrangement or -1,
         how many of them lie within 1e-9 of it])."""
-        a = np.ascontiguousarray(ids, dtype=np.int32)
-        b = np.ascontiguousarray(rev, dtype=np.uint8)
-        S = len(a)
-        table, best = np.empty((S, S, 2), np.float64), np.empty((S, 2), np.int32)
-        _check(self._lib.hicmi_p2_support(self._h, _ptr(a), _ptr(b), S, float(total), _ptr(table), _ptr(best)))
-        self._arr_sig = a.tobytes() + b.tobytes()
-        self._arr_len = S
-        return table, best
+        return self._table_call(self._lib.hicmi_p2_support, ids, rev, np.empty((len(ids), len(ids), 2), np.float64), (float(total),))
 
     @staticmethod
     def p2_support_multi(jobs):
         """p2_support for several chromosomes in one pair of launches (hicmi_p2_support_multi).
         jobs: [(context, ids, rev, total)], one distinct context per chromosome; returns [(table, best)]."""
-        n = len(jobs)
-        if n == 0:
-            return []
-        lib = jobs[0][0]._lib
-        a_l = [np.ascontiguousarray(j[1], dtype=np.int32) for j in jobs]
-        b_l = [np.ascontiguousarray(j[2], dtype=np.uint8) for j in jobs]
-        t_l = [np.empty((len(a), len(a), 2), np.float64) for a in a_l]
-        o_l = [np.empty((len(a), 2), np.int32) for a in a_l]
-        handles = (ctypes.c_void_p * n)(*[j[0]._h for j in jobs])
-        pa, pb, pt, po = ((ctypes.c_void_p * n)(*[x.ctypes.data for x in arrs]) for arrs in (a_l, b_l, t_l, o_l))
-        sizes = (c_i64 * n)(*[len(a) for a in a_l])
-        totals = (c_dbl * n)(*[float(j[3]) for j in jobs])
-        _check(lib.hicmi_p2_support_multi(n, handles, pa, pb, sizes, totals, pt, po))
-        for (ctx, _i, _r, _t), a, b in zip(jobs, a_l, b_l):
-            ctx._arr_sig = a.tobytes() + b.tobytes()
-            ctx._arr_len = len(a)
-        return list(zip(t_l, o_l))
+        return Context._table_multi("hicmi_p2_support_multi", jobs, [j[3] for j in jobs], lambda j, S: (S, S, 2))
 
     def p2_breaks(self, ids, rev, lengths, total: float, min_piece: int = 1):
         """Break support of one chromosome (hicmi_p2_breaks): see p2_breaks_multi."""
-        return Context.p2_breaks_multi([(self, ids, rev, lengths, total)], min_piece, single=True)[0]
+        table = np.empty((sum(max(int(ln) - 1, 0) for ln in lengths), 8), np.float64)
+        return self._table_call(self._lib.hicmi_p2_breaks, ids, rev, table, (float(total), int(min_piece)))
 
     @staticmethod
-    def p2_breaks_multi(jobs, min_piece: int = 1, single=False):
+    def p2_breaks_multi(jobs, min_piece: int = 1):
         """Break support of several chromosomes in one pair of launches (hicmi_p2_breaks_multi).
         jobs: [(context, ids, rev, lengths, total)], one distinct context per chromosome, ``lengths`` the bins of each
         scaffold of the arrangement; returns [(table, best)]: the scaffolds' (L - 1) x 8 blocks of closed-form scores
         concatenated in arrangement order as one (sum of L - 1) x 8 array, and S x 2 int32 of [8 (p - 1) + k of the first
         maximum among the competing candidates or -1, how many of them lie within 1e-9 of it]."""
-        n = len(jobs)
-        if n == 0:
-            return []
-        lib = jobs[0][0]._lib
-        a_l = [np.ascontiguousarray(j[1], dtype=np.int32) for j in jobs]
-        b_l = [np.ascontiguousarray(j[2], dtype=np.uint8) for j in jobs]
-        t_l = [np.empty((sum(max(int(ln) - 1, 0) for ln in j[3]), 8), np.float64) for j in jobs]
-        o_l = [np.empty((len(a), 2), np.int32) for a in a_l]
-        if single:
-            _check(lib.hicmi_p2_breaks(jobs[0][0]._h, _ptr(a_l[0]), _ptr(b_l[0]), len(a_l[0]), float(jobs[0][4]), int(min_piece),
-                                       t_l[0].ctypes.data, _ptr(o_l[0])))
-        else:
-            handles = (ctypes.c_void_p * n)(*[j[0]._h for j in jobs])
-            pa, pb, pt, po = ((ctypes.c_void_p * n)(*[x.ctypes.data for x in arrs]) for arrs in (a_l, b_l, t_l, o_l))
-            sizes = (c_i64 * n)(*[len(a) for a in a_l])
-            totals = (c_dbl * n)(*[float(j[4]) for j in jobs])
-            _check(lib.hicmi_p2_breaks_multi(n, handles, pa, pb, sizes, totals, int(min_piece), pt, po))
-        for j, a, b in zip(jobs, a_l, b_l):
-            j[0]._arr_sig = a.tobytes() + b.tobytes()
-            j[0]._arr_len = len(a)
-        return list(zip(t_l, o_l))
+        return Context._table_multi("hicmi_p2_breaks_multi", jobs, [j[4] for j in jobs],
+                                    lambda j, S: (sum(max(int(ln) - 1, 0) for ln in j[3]), 8), (int(min_piece),))
 
     def p2_scan_pass(self, ids, rev, k, total, best, cur_fast):
         """One round of scanOrdering; returns (ids, rev, best, cur_fast, improved)."""

@@ -289,6 +289,13 @@ int ensure(T*& p, int64_t& cap, int64_t need)
 
 void free_dev(void* p) { if (p) (void)hipFree(p); }
 
+// a candidate's bin order is staged in LDS as int32, 160 KiB at the most
+int check_candidate_bins(int64_t n_bins)
+{
+    if (n_bins * (int64_t)sizeof(int32_t) > 160 * 1024) return fail(HICMI_EUNSUPPORTED, "candidate longer than 40960 bins");
+    return HICMI_OK;
+}
+
 void drop_matrix_state(hicmi_ctx* c)
 {
     if (c->own_c) free_dev(c->dC);
@@ -316,6 +323,14 @@ int compute_sums(hicmi_ctx* c)
     }
     HIPCHK(hipGetLastError());
     c->have_sums = true;
+    return HICMI_OK;
+}
+
+// job j of a multi-chromosome call: a context of its own, on the first job's device
+int check_job_context(hicmi_ctx* const* ctxs, int64_t j)
+{
+    if (!ctxs[j] || !ctxs[0] || ctxs[j]->device != ctxs[0]->device) return fail(HICMI_EINVAL, "contexts must share one device");
+    for (int64_t q = 0; q < j; q++) if (ctxs[q] == ctxs[j]) return fail(HICMI_EINVAL, "one context per chromosome");
     return HICMI_OK;
 }
 }  // namespace
@@ -1665,7 +1680,7 @@ int hicmi_p2_score(hicmi_ctx* c, const int32_t* perms, int64_t n_cand, int64_t n
     if (c->n2 < 1) return fail(HICMI_EINVAL, "hicmi_p2_select has not run");
     if (n_used > c->n2) return fail(HICMI_EINVAL, "n_used exceeds the selection");
     if (n_cand == 0) return HICMI_OK;
-    if (n_used * (int64_t)sizeof(int32_t) > 160 * 1024) return fail(HICMI_EUNSUPPORTED, "candidate longer than 40960 bins");
+    if (int rc = check_candidate_bins(n_used)) return rc;
     for (int64_t i = 0; i < n_cand * n_used; i++)
         if (perms[i] < 0 || perms[i] >= c->n2) return fail(HICMI_EINVAL, "candidate index out of range");
     HIPCHK(hipSetDevice(c->device));
@@ -1691,7 +1706,7 @@ int hicmi_p2_score_exact(hicmi_ctx* c, const int32_t* perms, int64_t n_cand, int
     if (c->n2 < 1) return fail(HICMI_EINVAL, "hicmi_p2_select has not run");
     if (n_used > c->n2) return fail(HICMI_EINVAL, "n_used exceeds the selection");
     if (n_cand == 0) return HICMI_OK;
-    if (n_used * (int64_t)sizeof(int32_t) > 160 * 1024) return fail(HICMI_EUNSUPPORTED, "candidate longer than 40960 bins");
+    if (int rc = check_candidate_bins(n_used)) return rc;
     for (int64_t i = 0; i < n_cand * n_used; i++)
         if (perms[i] < 0 || perms[i] >= c->n2) return fail(HICMI_EINVAL, "candidate index out of range");
     HIPCHK(hipSetDevice(c->device));
@@ -1839,7 +1854,7 @@ int hicmi_p2_score_insertions(hicmi_ctx* c, int32_t new_id, double total, double
     if (c->n_arr < 1 || S < 1) return fail(HICMI_EINVAL, "hicmi_p2_set_arrangement has not run");
     for (int64_t j = 0; j < S; j++) if (c->h_arr_id[(size_t)j] == new_id) return fail(HICMI_EINVAL, "scaffold is already in the arrangement");
     const int new_len = c->h_scaf_len[(size_t)new_id];
-    if ((c->n_arr + new_len) * (int64_t)sizeof(int32_t) > 160 * 1024) return fail(HICMI_EUNSUPPORTED, "candidate longer than 40960 bins");
+    if (int rc = check_candidate_bins(c->n_arr + new_len)) return rc;
     HIPCHK(hipSetDevice(c->device));
     // incremental form: BASE (64 partial sums) - STRADDLE(g) (prefix sums of S increments) + CROSS(g, r)
     const int NB = kBaseSlabs;
@@ -2449,7 +2464,8 @@ int queue_insertions(hicmi_ctx* lead, const std::vector<InsJob*>& jobs)
         const int64_t n_steps = job.n_new - job.t;
         int64_t n_max = c->n_arr;
         for (int64_t t = 0; t < n_steps; t++) n_max += c->h_scaf_len[(size_t)job.new_ids[job.t + t]];
-        if (n_max * (int64_t)sizeof(int32_t) > 160 * 1024) return fail(HICMI_EUNSUPPORTED, "candidate longer than 40960 bins");
+        rc = check_candidate_bins(n_max);
+        if (rc) return rc;
         const int64_t S_max = job.S + n_steps;
         rc = ensure(c->d_arr_packed2, c->arr2_cap, 3 * std::max<int64_t>(S_max, c->n_scaf) + 2);
         if (rc) return rc;
@@ -2646,8 +2662,7 @@ int hicmi_p2_insert_all_multi(int64_t n_jobs, hicmi_ctx* const* ctxs, int32_t* c
     for (int64_t j = 0; j < n_jobs; j++) {
         InsJob& job = jobs[(size_t)j];
         job.c = ctxs[j]; job.ids = ids[j]; job.rev = rev[j]; job.S = S0[j]; job.new_ids = new_ids[j]; job.n_new = n_new[j];
-        if (!job.c || job.c->device != ctxs[0]->device) return fail(HICMI_EINVAL, "contexts must share one device");
-        for (int64_t q = 0; q < j; q++) if (ctxs[q] == ctxs[j]) return fail(HICMI_EINVAL, "one context per chromosome");
+        if (int rc = check_job_context(ctxs, j)) return rc;
     }
     int rc = run_insert_jobs(jobs);
     if (rc) return rc;
@@ -2655,57 +2670,112 @@ int hicmi_p2_insert_all_multi(int64_t n_jobs, hicmi_ctx* const* ctxs, int32_t* c
     return HICMI_OK;
 }
 
-// Placement support (k_part2_support.hip): every scaffold of every job's arrangement taken out and scored at every gap
-// in both orientations, one record per (job, scaffold), one pair of launches and one download for all jobs.
-int hicmi_p2_support_multi(int64_t n_jobs, hicmi_ctx* const* ctxs, const int32_t* const* ids, const uint8_t* const* rev,
-                           const int64_t* S, const double* totals, double* const* scores_out, int32_t* const* best_out)
+// Placement support and break support are "table jobs": per job (chromosome) a table of closed-form scores, and per
+// scaffold of its arrangement the pick among the competing candidates (pick_first_max_256, hicmi_internal.h) as an int32
+// pair.  run_table_jobs is the driver of both - one record upload, one launch and one download for all jobs - and a
+// TableOps holds what differs between them.
+extern "C++" {
+namespace {
+template <typename Rec>
+struct TableOps {
+    int64_t max_S;                                         // scaffolds per chromosome; 0: no limit
+    Rec* hicmi_ctx::*recs; int64_t hicmi_ctx::*recs_cap;   // the lead context's record buffer
+    // job j, its arrangement set: the length of its table, the doubles it needs in d_ins_partial, its records
+    std::function<void(int64_t j, int64_t& n_table, int64_t& scratch, int64_t& n_rec)> size;
+    // job j's records appended and its work added to algo; d_scores, d_best: its table and its pairs on the device
+    std::function<int(int64_t j, double* d_scores, int32_t* d_best, std::vector<Rec>& recs, double& algo)> append;
+    std::function<void(const Rec* d_recs, int n_rec)> launch;
+};
+
+template <typename Rec>
+int run_table_jobs(int64_t n_jobs, hicmi_ctx* const* ctxs, const int32_t* const* ids, const uint8_t* const* rev,
+                   const int64_t* S, const double* totals, double* const* scores_out, int32_t* const* best_out,
+                   const TableOps<Rec>& ops)
 {
-    if (n_jobs < 1 || !ctxs || !ids || !rev || !S || !totals || !scores_out || !best_out) return fail(HICMI_EINVAL, "bad arguments");
     hicmi_ctx* lead = ctxs[0];
-    const int NB = SUP_BASE_SLABS;
     std::vector<size_t> out_off((size_t)n_jobs, 0);
+    std::vector<int64_t> n_table((size_t)n_jobs, 0);
     std::vector<uint8_t> run((size_t)n_jobs, 0);
     size_t blob_bytes = 0;
     int64_t n_rec = 0;
-    int max_S = 1, max_n = 1;
     for (int64_t j = 0; j < n_jobs; j++) {
+        int rc = check_job_context(ctxs, j);
+        if (rc) return rc;
         hicmi_ctx* c = ctxs[j];
-        if (!c || !lead || c->device != lead->device) return fail(HICMI_EINVAL, "contexts must share one device");
-        for (int64_t q = 0; q < j; q++) if (ctxs[q] == c) return fail(HICMI_EINVAL, "one context per chromosome");
         if (!ids[j] || !rev[j] || !scores_out[j] || !best_out[j] || S[j] < 1) return fail(HICMI_EINVAL, "bad arguments");
-        if (S[j] > SUP_MAX_S) return fail(HICMI_EUNSUPPORTED, "more than %d scaffolds in one chromosome", SUP_MAX_S);
-        int rc = hicmi_p2_set_arrangement(c, ids[j], rev[j], S[j]);
+        if (ops.max_S && S[j] > ops.max_S) return fail(HICMI_EUNSUPPORTED, "more than %d scaffolds in one chromosome", (int)ops.max_S);
+        rc = hicmi_p2_set_arrangement(c, ids[j], rev[j], S[j]);
         if (rc) return rc;
         if (c != lead) HIPCHK(sync_stream(c));             // the launches run on lead's stream
-        if (c->n_arr * (int64_t)sizeof(int32_t) > 160 * 1024) return fail(HICMI_EUNSUPPORTED, "candidate longer than 40960 bins");
-        // fewer than 2 bins, or no contacts: every score is 0.0 and there is no candidate
-        for (int64_t i = 0; i < 2 * S[j] * S[j]; i++) scores_out[j][i] = 0.0;
+        rc = check_candidate_bins(c->n_arr);
+        if (rc) return rc;
+        int64_t scratch = 0, n_rec_j = 0;
+        ops.size(j, n_table[(size_t)j], scratch, n_rec_j);
+        // fewer than 2 bins, no contacts or no record: every score is 0.0 and there is no candidate
+        for (int64_t i = 0; i < n_table[(size_t)j]; i++) scores_out[j][i] = 0.0;
         for (int64_t i = 0; i < S[j]; i++) { best_out[j][2 * i] = -1; best_out[j][2 * i + 1] = 0; }
-        if (c->n_arr < 2 || !(totals[j] > 0.0)) continue;
+        if (c->n_arr < 2 || !(totals[j] > 0.0) || n_rec_j == 0) continue;
         run[(size_t)j] = 1;
-        rc = ensure(c->d_ins_partial, c->ins_partial_cap, S[j] * (NB + c->n_arr + 2 * S[j]));
+        rc = ensure(c->d_ins_partial, c->ins_partial_cap, scratch);
         if (rc) return rc;
         out_off[(size_t)j] = blob_bytes;
-        blob_bytes += ((size_t)(2 * S[j] * S[j]) * sizeof(double) + (size_t)(2 * S[j]) * sizeof(int32_t) + 15) & ~(size_t)15;
-        n_rec += S[j];
-        max_S = std::max(max_S, (int)S[j]);
-        max_n = std::max(max_n, (int)c->n_arr);
+        blob_bytes += ((size_t)n_table[(size_t)j] * sizeof(double) + (size_t)(2 * S[j]) * sizeof(int32_t) + 15) & ~(size_t)15;
+        n_rec += n_rec_j;
     }
     if (n_rec == 0) return HICMI_OK;
     HIPCHK(hipSetDevice(lead->device));
     int rc = ensure(lead->d_ins_blob, lead->ins_blob_cap, (int64_t)blob_bytes);
     if (rc) return rc;
-    rc = ensure(lead->d_sup_recs, lead->sup_recs_cap, n_rec);
+    rc = ensure(lead->*ops.recs, lead->*ops.recs_cap, n_rec);
     if (rc) return rc;
-    std::vector<SupRec> recs;
+    std::vector<Rec> recs;
     recs.reserve((size_t)n_rec);
     double algo = 0.0;
     for (int64_t j = 0; j < n_jobs; j++) {
         if (!run[(size_t)j]) continue;
+        double* d_scores = reinterpret_cast<double*>(lead->d_ins_blob + out_off[(size_t)j]);
+        rc = ops.append(j, d_scores, reinterpret_cast<int32_t*>(d_scores + n_table[(size_t)j]), recs, algo);
+        if (rc) return rc;
+    }
+    rc = upload(lead, lead->*ops.recs, recs.data(), sizeof(Rec) * recs.size());
+    if (rc) return rc;
+    {
+        Timed timed(lead, F_P2_INSERT, algo);
+        ops.launch(lead->*ops.recs, (int)n_rec);
+    }
+    HIPCHK(hipGetLastError());
+    std::vector<unsigned char> blob(blob_bytes);
+    rc = download(lead, blob.data(), lead->d_ins_blob, blob_bytes);
+    if (rc) return rc;
+    for (int64_t j = 0; j < n_jobs; j++) {
+        if (!run[(size_t)j]) continue;
+        const size_t nd = (size_t)n_table[(size_t)j];
+        memcpy(scores_out[j], blob.data() + out_off[(size_t)j], nd * sizeof(double));
+        memcpy(best_out[j], blob.data() + out_off[(size_t)j] + nd * sizeof(double), (size_t)(2 * S[j]) * sizeof(int32_t));
+    }
+    return HICMI_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+// Placement support (k_part2_support.hip): every scaffold of every job's arrangement taken out and scored at every gap
+// in both orientations, one record per (job, scaffold).
+int hicmi_p2_support_multi(int64_t n_jobs, hicmi_ctx* const* ctxs, const int32_t* const* ids, const uint8_t* const* rev,
+                           const int64_t* S, const double* totals, double* const* scores_out, int32_t* const* best_out)
+{
+    if (n_jobs < 1 || !ctxs || !ids || !rev || !S || !totals || !scores_out || !best_out) return fail(HICMI_EINVAL, "bad arguments");
+    const int NB = SUP_BASE_SLABS;
+    int max_S = 1, max_n = 1;
+    TableOps<SupRec> ops;
+    ops.max_S = SUP_MAX_S; ops.recs = &hicmi_ctx::d_sup_recs; ops.recs_cap = &hicmi_ctx::sup_recs_cap;
+    ops.size = [&](int64_t j, int64_t& n_table, int64_t& scratch, int64_t& n_rec) {
+        n_table = 2 * S[j] * S[j]; scratch = S[j] * (NB + ctxs[j]->n_arr + 2 * S[j]); n_rec = S[j];
+    };
+    ops.append = [&](int64_t j, double* d_scores, int32_t* d_best, std::vector<SupRec>& recs, double& algo) {
         hicmi_ctx* c = ctxs[j];
         const int64_t Sj = S[j], n = c->n_arr;
-        double* d_scores = reinterpret_cast<double*>(lead->d_ins_blob + out_off[(size_t)j]);
-        int32_t* d_best = reinterpret_cast<int32_t*>(d_scores + 2 * Sj * Sj);
+        max_S = std::max(max_S, (int)Sj);
+        max_n = std::max(max_n, (int)n);
         for (int64_t k = 0; k < Sj; k++) {
             SupRec d;
             memset(&d, 0, sizeof(d));
@@ -2721,24 +2791,10 @@ int hicmi_p2_support_multi(int64_t n_jobs, hicmi_ctx* const* ctxs, const int32_t
             const double nn = (double)(n - d.L);
             algo += 8.0 * (0.5 * nn * nn + nn * nn + 2.0 * (double)Sj * (double)d.L * nn);
         }
-    }
-    rc = upload(lead, lead->d_sup_recs, recs.data(), sizeof(SupRec) * recs.size());
-    if (rc) return rc;
-    {
-        Timed timed(lead, F_P2_INSERT, algo);
-        launch_sup(lead->d_sup_recs, (int)n_rec, max_S, max_n, kNearTop, lead->stream);
-    }
-    HIPCHK(hipGetLastError());
-    std::vector<unsigned char> blob(blob_bytes);
-    rc = download(lead, blob.data(), lead->d_ins_blob, blob_bytes);
-    if (rc) return rc;
-    for (int64_t j = 0; j < n_jobs; j++) {
-        if (!run[(size_t)j]) continue;
-        const size_t nd = (size_t)(2 * S[j] * S[j]);
-        memcpy(scores_out[j], blob.data() + out_off[(size_t)j], nd * sizeof(double));
-        memcpy(best_out[j], blob.data() + out_off[(size_t)j] + nd * sizeof(double), (size_t)(2 * S[j]) * sizeof(int32_t));
-    }
-    return HICMI_OK;
+        return (int)HICMI_OK;
+    };
+    ops.launch = [&](const SupRec* d_recs, int n_rec) { launch_sup(d_recs, n_rec, max_S, max_n, kNearTop, ctxs[0]->stream); };
+    return run_table_jobs(n_jobs, ctxs, ids, rev, S, totals, scores_out, best_out, ops);
 }
 
 int hicmi_p2_support(hicmi_ctx* c, const int32_t* ids, const uint8_t* rev, int64_t S, double total, double* scores_out,
@@ -2748,66 +2804,30 @@ int hicmi_p2_support(hicmi_ctx* c, const int32_t* ids, const uint8_t* rev, int64
 }
 
 // Break support (k_part2_breaks.hip): every scaffold of every job's arrangement cut at every bin boundary, the two
-// pieces swapped and / or reversed in place; one record per (job, scaffold of at least 2 bins), one pair of launches
-// and one download for all jobs.
+// pieces swapped and / or reversed in place; one record per (job, scaffold of at least 2 bins).
 int hicmi_p2_breaks_multi(int64_t n_jobs, hicmi_ctx* const* ctxs, const int32_t* const* ids, const uint8_t* const* rev,
                           const int64_t* S, const double* totals, int64_t min_piece, double* const* scores_out,
                           int32_t* const* best_out)
 {
     if (n_jobs < 1 || !ctxs || !ids || !rev || !S || !totals || !scores_out || !best_out || min_piece < 1)
         return fail(HICMI_EINVAL, "bad arguments");
-    hicmi_ctx* lead = ctxs[0];
     const int NB = BRK_BASE_SLABS;
-    std::vector<size_t> out_off((size_t)n_jobs, 0);
-    std::vector<int64_t> n_scores((size_t)n_jobs, 0);
-    std::vector<uint8_t> run((size_t)n_jobs, 0);
-    size_t blob_bytes = 0;
-    int64_t n_rec = 0;
-    for (int64_t j = 0; j < n_jobs; j++) {
-        hicmi_ctx* c = ctxs[j];
-        if (!c || !lead || c->device != lead->device) return fail(HICMI_EINVAL, "contexts must share one device");
-        for (int64_t q = 0; q < j; q++) if (ctxs[q] == c) return fail(HICMI_EINVAL, "one context per chromosome");
-        if (!ids[j] || !rev[j] || !scores_out[j] || !best_out[j] || S[j] < 1) return fail(HICMI_EINVAL, "bad arguments");
-        int rc = hicmi_p2_set_arrangement(c, ids[j], rev[j], S[j]);
-        if (rc) return rc;
-        if (c != lead) HIPCHK(sync_stream(c));             // the launches run on lead's stream
-        if (c->n_arr * (int64_t)sizeof(int32_t) > 160 * 1024) return fail(HICMI_EUNSUPPORTED, "candidate longer than 40960 bins");
-        int64_t cand = 0, scratch = NB, multi = 0;
-        for (int64_t k = 0; k < S[j]; k++) {
-            const int64_t L = c->h_scaf_len[(size_t)ids[j][k]];
-            if (L < 2) continue;
-            cand += 8 * (L - 1); scratch += L * L + 3 * (L - 1); multi++;
-        }
-        n_scores[(size_t)j] = cand;
-        // fewer than 2 bins, or no contacts: every score is 0.0 and there is no candidate
-        for (int64_t i = 0; i < cand; i++) scores_out[j][i] = 0.0;
-        for (int64_t i = 0; i < S[j]; i++) { best_out[j][2 * i] = -1; best_out[j][2 * i + 1] = 0; }
-        if (c->n_arr < 2 || !(totals[j] > 0.0) || multi == 0) continue;
-        run[(size_t)j] = 1;
-        rc = ensure(c->d_ins_partial, c->ins_partial_cap, scratch);
-        if (rc) return rc;
-        out_off[(size_t)j] = blob_bytes;
-        blob_bytes += ((size_t)cand * sizeof(double) + (size_t)(2 * S[j]) * sizeof(int32_t) + 15) & ~(size_t)15;
-        n_rec += multi;
-    }
-    if (n_rec == 0) return HICMI_OK;
-    HIPCHK(hipSetDevice(lead->device));
-    int rc = ensure(lead->d_ins_blob, lead->ins_blob_cap, (int64_t)blob_bytes);
-    if (rc) return rc;
-    rc = ensure(lead->d_brk_recs, lead->brk_recs_cap, n_rec);
-    if (rc) return rc;
-    std::vector<BrkRec> recs;
-    recs.reserve((size_t)n_rec);
-    double algo = 0.0;
     int64_t n_wg = 0;
-    for (int64_t j = 0; j < n_jobs; j++) {
-        if (!run[(size_t)j]) continue;
+    TableOps<BrkRec> ops;
+    ops.max_S = 0; ops.recs = &hicmi_ctx::d_brk_recs; ops.recs_cap = &hicmi_ctx::brk_recs_cap;
+    ops.size = [&](int64_t j, int64_t& n_table, int64_t& scratch, int64_t& n_rec) {
+        scratch = NB;
+        for (int64_t k = 0; k < S[j]; k++) {
+            const int64_t L = ctxs[j]->h_scaf_len[(size_t)ids[j][k]];
+            if (L < 2) continue;
+            n_table += 8 * (L - 1); scratch += L * L + 3 * (L - 1); n_rec++;
+        }
+    };
+    ops.append = [&](int64_t j, double* d_scores, int32_t* d_best, std::vector<BrkRec>& recs, double& algo) {
         hicmi_ctx* c = ctxs[j];
         const int64_t Sj = S[j], n = c->n_arr;
-        double* d_scores = reinterpret_cast<double*>(lead->d_ins_blob + out_off[(size_t)j]);
-        int32_t* d_best = reinterpret_cast<int32_t*>(d_scores + n_scores[(size_t)j]);
         // one-bin scaffolds have no record: their (-1, 0) is written here, beside the records' pairs
-        rc = upload(lead, d_best, best_out[j], sizeof(int32_t) * (size_t)(2 * Sj));
+        int rc = upload(ctxs[0], d_best, best_out[j], sizeof(int32_t) * (size_t)(2 * Sj));
         if (rc) return rc;
         double* scratch = c->d_ins_partial + NB;
         int64_t row = 0;
@@ -2833,25 +2853,11 @@ int hicmi_p2_breaks_multi(int64_t n_jobs, hicmi_ctx* const* ctxs, const int32_t*
             algo += 8.0 * ((double)L * (double)L * (double)(n - L) + (double)L * (double)L * (double)L / 6.0);
         }
         algo += 4.0 * (double)n * (double)n;
-    }
-    if (n_wg > 0x7fffffff) return fail(HICMI_EUNSUPPORTED, "more than 2^31 - 1 workgroups in one call");
-    rc = upload(lead, lead->d_brk_recs, recs.data(), sizeof(BrkRec) * recs.size());
-    if (rc) return rc;
-    {
-        Timed timed(lead, F_P2_INSERT, algo);
-        launch_brk(lead->d_brk_recs, (int)n_rec, n_wg, kNearTop, lead->stream);
-    }
-    HIPCHK(hipGetLastError());
-    std::vector<unsigned char> blob(blob_bytes);
-    rc = download(lead, blob.data(), lead->d_ins_blob, blob_bytes);
-    if (rc) return rc;
-    for (int64_t j = 0; j < n_jobs; j++) {
-        if (!run[(size_t)j]) continue;
-        const size_t nd = (size_t)n_scores[(size_t)j];
-        memcpy(scores_out[j], blob.data() + out_off[(size_t)j], nd * sizeof(double));
-        memcpy(best_out[j], blob.data() + out_off[(size_t)j] + nd * sizeof(double), (size_t)(2 * S[j]) * sizeof(int32_t));
-    }
-    return HICMI_OK;
+        if (n_wg > 0x7fffffff) return fail(HICMI_EUNSUPPORTED, "more than 2^31 - 1 workgroups in one call");
+        return (int)HICMI_OK;
+    };
+    ops.launch = [&](const BrkRec* d_recs, int n_rec) { launch_brk(d_recs, n_rec, n_wg, kNearTop, ctxs[0]->stream); };
+    return run_table_jobs(n_jobs, ctxs, ids, rev, S, totals, scores_out, best_out, ops);
 }
 
 int hicmi_p2_breaks(hicmi_ctx* c, const int32_t* ids, const uint8_t* rev, int64_t S, double total, int64_t min_piece,
@@ -2993,9 +2999,7 @@ int hicmi_p2_start_all(int64_t n_jobs, hicmi_ctx* const* ctxs, const int32_t* se
     {
         int64_t so = 0, fo = 0, io = 0;
         for (size_t j = 0; j < nj; j++) {
-            hicmi_ctx* c = ctxs[j];
-            if (!c || c->device != ctxs[0]->device) return fail(HICMI_EINVAL, "contexts must share one device");
-            for (size_t q = 0; q < j; q++) if (ctxs[q] == c) return fail(HICMI_EINVAL, "one context per chromosome");
+            if (int rc = check_job_context(ctxs, (int64_t)j)) return rc;
             if (n_sel[j] < 1 || n_scaf[j] < 1 || k[j] < 1 || k[j] > 8 || k[j] > n_scaf[j]) return fail(HICMI_EINVAL, "bad job %lld", (long long)j);
             if (!orders[k[j]] || !orients[k[j]] || n_orders[k[j]] < 1 || n_orients[k[j]] < 1)
                 return fail(HICMI_EINVAL, "no order / orientation tables for k = %lld", (long long)k[j]);

@@ -298,7 +298,7 @@ void launch_p2_window_near(const double* M2, int64_t ld2, const int32_t* pos2sel
                            double cur_fast, double floor, double near_top, double* part, int32_t* count, NearEntry* near, int cap,
                            hipStream_t s);
 
-// ---- block sums and the closed-form BASE term, shared by k_part2_search.hip and k_part2_support.hip
+// ---- block sums and the closed-form BASE term, shared by k_part2_search.hip, k_part2_support.hip and k_part2_breaks.hip
 __device__ __forceinline__ double wave_sum_s(double v)
 {
 #pragma unroll
@@ -330,6 +330,51 @@ __device__ __forceinline__ void base_partial_body(const double* __restrict__ M2,
     }
     double sum = block_sum_256(acc, s_w);
     if (threadIdx.x == 0) out[0] = sum;
+}
+
+// ---- the pick of a table record, shared by k_part2_support.hip and k_part2_breaks.hip ("The pick").
+// A 256-lane workgroup has just written scores[0 .. n_cand), thread tid the entries tid, tid + 256, ...; every thread
+// reads back only what it wrote.  Among the candidates i with counts(i) and a finite score: best[0] = the first maximum
+// (the lowest index among equals), best[1] = how many lie within near_top of it, relative; (-1, 0) when nothing competes.
+// The host restates this rule as support_summary / break_summary (orderGenome.py).  10 barriers.
+template <typename Counts>
+__device__ __forceinline__ void pick_first_max_256(int tid, int n_cand, const double* scores, int32_t* best,
+                                                   double near_top, Counts counts)
+{
+    __shared__ double s_val[256];
+    __shared__ int s_idx[256], s_cnt;
+    double mx = -__builtin_inf();
+    int at = 0x7fffffff;
+    for (int i = tid; i < n_cand; i += 256) {
+        const double v = scores[i];
+        if (counts(i) && isfinite(v) && v > mx) { mx = v; at = i; }   // ascending i: the first of equals
+    }
+    s_val[tid] = mx; s_idx[tid] = at;
+    if (tid == 0) s_cnt = 0;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (tid < w) {
+            const double o = s_val[tid + w];
+            const int oi = s_idx[tid + w];
+            if (o > s_val[tid] || (o == s_val[tid] && oi < s_idx[tid])) { s_val[tid] = o; s_idx[tid] = oi; }
+        }
+        __syncthreads();
+    }
+    const double top = s_val[0];
+    const int first = s_idx[0];
+    if (first == 0x7fffffff) {                           // nothing competes, or nothing finite
+        if (tid == 0) { best[0] = -1; best[1] = 0; }
+        return;
+    }
+    const double thr = top - fabs(top) * near_top;
+    int near = 0;
+    for (int i = tid; i < n_cand; i += 256) {
+        const double v = scores[i];
+        near += counts(i) && isfinite(v) && v >= thr;
+    }
+    if (near) atomicAdd(&s_cnt, near);
+    __syncthreads();
+    if (tid == 0) { best[0] = first; best[1] = s_cnt; }
 }
 
 // Lock-step insertion (k_part2_insert.hip): orderRemainderScaffolds for several chromosomes at once, every
@@ -371,7 +416,7 @@ struct SupRec {
     const int32_t* arr_pos;                   // prefix positions of A's S scaffolds, S + 1 entries
     double* partial;                          // [SUP_BASE_SLABS BASE slabs][n - L row values][2 S CROSS terms]
     double* scores;                           // out: score(j, g, r) at [2 g + r]
-    int32_t* best;                            // out: first closed-form maximum among the counted candidates (-1: none), how many within near_top
+    int32_t* best;                            // out: the pick (pick_first_max_256) over sup_counts
     double total;
     int32_t n, S, j, start, L, cur_rev;       // start, L: j's range of the selection; cur_rev: its orientation in A
 };
@@ -387,7 +432,7 @@ struct BrkRec {
     double* pq;                               // scratch: [L - 1 cuts][3 P x Q sums]
     double* base;                             // the chromosome's BRK_BASE_SLABS BASE slabs (one area for all its records)
     double* scores;                           // out: score(p, k) at [8 (p - 1) + k]
-    int32_t* best;                            // out: first closed-form maximum among the competing candidates (-1: none), how many within near_top
+    int32_t* best;                            // out: the pick (pick_first_max_256) over brk_counts
     double total;
     int64_t wg0;                              // first workgroup of this record in k_brk_tables
     int32_t n, B, L, min_piece;               // B: first position of j in A

@@ -16,7 +16,7 @@
 //                 slabs of A (base_partial_body); then L * ceil(L / 4) workgroups, one WAVE per entry of X; then one
 //                 workgroup per cut for its three P x Q sums.
 //   k_brk_scores  one workgroup per record: BASE = the slabs left to right, the 8 (L - 1) scores (BASE + delta) /
-//                 total, the first maximum over the competing candidates and how many of them lie within near_top.
+//                 total, and the record's pick (pick_first_max_256, hicmi_internal.h) over the candidates of brk_counts.
 // No candidate bin order is built.  Matrix reads per record: L (n - L) for X's rows (each re-read from cache for the
 // L positions: L^2 (n - L) multiply-adds) and L^3 / 6 for the P x Q sums; the finishing kernel does 8 L^2 look-ups.
 //
@@ -111,20 +111,16 @@ __global__ __launch_bounds__(256) void k_brk_tables(const BrkRec* __restrict__ r
 
 __global__ __launch_bounds__(256) void k_brk_scores(const BrkRec* __restrict__ recs, double near_top)
 {
-    __shared__ double s_part[BRK_BASE_SLABS], s_base, s_val[256];
-    __shared__ int s_idx[256], s_cnt;
+    __shared__ double s_part[BRK_BASE_SLABS], s_base;
     const BrkRec& d = recs[blockIdx.x];
     const int tid = threadIdx.x, L = d.L, mp = d.min_piece;
     for (int i = tid; i < BRK_BASE_SLABS; i += 256) s_part[i] = d.base[i];
-    if (tid == 0) s_cnt = 0;
     __syncthreads();
     if (tid == 0) s_base = serial_sum_lds(s_part, 0, BRK_BASE_SLABS, 0.0);
     __syncthreads();
     const double base = s_base, total = d.total;
     const double* __restrict__ X = d.X;
     const int n_cand = 8 * (L - 1);
-    double mx = -__builtin_inf();
-    int at = 0x7fffffff;
     for (int c = tid; c < n_cand; c += 256) {
         const int p = (c >> 3) + 1, k = c & 7;
         double delta = 0.0;
@@ -139,35 +135,9 @@ __global__ __launch_bounds__(256) void k_brk_scores(const BrkRec* __restrict__ r
             else if (k == 1 || k == 6) delta += pq[1];
             else if (k == 2 || k == 5) delta += pq[2];
         }
-        const double v = (base + delta) / total;
-        d.scores[c] = v;
-        if (brk_counts(p, L, k, mp) && isfinite(v) && v > mx) { mx = v; at = c; }   // ascending c: the first of equals
+        d.scores[c] = (base + delta) / total;
     }
-    s_val[tid] = mx; s_idx[tid] = at;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (tid < w) {
-            const double o = s_val[tid + w];
-            const int oi = s_idx[tid + w];
-            if (o > s_val[tid] || (o == s_val[tid] && oi < s_idx[tid])) { s_val[tid] = o; s_idx[tid] = oi; }
-        }
-        __syncthreads();
-    }
-    const double top = s_val[0];
-    const int first = s_idx[0];
-    if (first == 0x7fffffff) {                           // nothing competes (L = 2, min_piece), or nothing finite
-        if (tid == 0) { d.best[0] = -1; d.best[1] = 0; }
-        return;
-    }
-    const double thr = top - fabs(top) * near_top;
-    int near = 0;
-    for (int c = tid; c < n_cand; c += 256) {            // the scores this thread has just written
-        const double v = d.scores[c];
-        near += brk_counts((c >> 3) + 1, L, c & 7, mp) && isfinite(v) && v >= thr;
-    }
-    if (near) atomicAdd(&s_cnt, near);
-    __syncthreads();
-    if (tid == 0) { d.best[0] = first; d.best[1] = s_cnt; }
+    pick_first_max_256(tid, n_cand, d.scores, d.best, near_top, [=](int c) { return brk_counts((c >> 3) + 1, L, c & 7, mp); });
 }
 
 void launch_brk(const BrkRec* recs, int n_rec, int64_t n_wg, double near_top, hipStream_t s)

@@ -10,9 +10,8 @@
 //                 then one WAVE per position u of "A without j": its row's share s(u) of the STRADDLE increment of its
 //                 own scaffold; then one workgroup per (gap, orientation): CROSS, 4 waves over the bins of j.
 //   k_sup_scores  one workgroup per record: BASE = the slabs left to right, STRADDLE = prefix over the scaffolds in
-//                 position order, the 2 S scores divided by the chromosome's total, and the record's first closed-form
-//                 maximum over the candidates whose bin order differs from A's, with how many of them lie within
-//                 near_top of it (1: decided; more: the host re-scores that short list literally).
+//                 position order, the 2 S scores divided by the chromosome's total, and the record's pick
+//                 (pick_first_max_256, hicmi_internal.h) over the candidates of sup_counts.
 // "A without j" is never written anywhere in global memory: position q of it is position q (q < P_j) or q + L_j of A,
 // and its gap g starts at arr_pos[g] (g <= j) or arr_pos[g + 1] - L_j.  No candidate bin order is built either.
 // Matrix reads per record: n^2/2 (BASE) + n^2 (rows) + 2 S L_j n (CROSS); summed over j that is (3/2 + 2) S n^2 per
@@ -116,13 +115,11 @@ __global__ __launch_bounds__(256) void k_sup_scores(const SupRec* __restrict__ r
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_s[];
     double* buf = reinterpret_cast<double*>(smem_s);     // the STRADDLE prefix, S + 1 entries
-    __shared__ double s_part[SUP_BASE_SLABS], s_base, s_val[256];
-    __shared__ int s_idx[256], s_cnt;
+    __shared__ double s_part[SUP_BASE_SLABS], s_base;
     const SupRec& d = recs[blockIdx.x];
     const int tid = threadIdx.x, S = d.S, j = d.j, L = d.L, n_arr = d.n - d.L;
     const double* __restrict__ partial = d.partial;
     for (int i = tid; i < n_base_blocks; i += 256) s_part[i] = partial[i];
-    if (tid == 0) s_cnt = 0;
     // STRADDLE(g + 1) - STRADDLE(g): the rows of the scaffold after gap g, added in position order
     for (int g = tid; g < S - 1; g += 256) {
         const int P0 = sup_gap_pos(d.arr_pos, g, j, L), P1 = sup_gap_pos(d.arr_pos, g + 1, j, L);
@@ -139,39 +136,9 @@ __global__ __launch_bounds__(256) void k_sup_scores(const SupRec* __restrict__ r
     __syncthreads();
     const double base = s_base, total = d.total;
     const double* __restrict__ cross = partial + n_base_blocks + n_arr;
-    const int n_cand = 2 * S;
-    double mx = -__builtin_inf();
-    int at = 0x7fffffff;
-    for (int i = tid; i < n_cand; i += 256) {
-        const double v = (base - buf[i >> 1] + cross[i]) / total;
-        d.scores[i] = v;
-        if (sup_counts(i, j, L, d.cur_rev, S) && isfinite(v) && v > mx) { mx = v; at = i; }   // ascending i: the first of equals
-    }
-    s_val[tid] = mx; s_idx[tid] = at;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (tid < w) {
-            const double o = s_val[tid + w];
-            const int oi = s_idx[tid + w];
-            if (o > s_val[tid] || (o == s_val[tid] && oi < s_idx[tid])) { s_val[tid] = o; s_idx[tid] = oi; }
-        }
-        __syncthreads();
-    }
-    const double top = s_val[0];
-    const int first = s_idx[0];
-    if (first == 0x7fffffff) {                           // S = 1, or nothing finite
-        if (tid == 0) { d.best[0] = -1; d.best[1] = 0; }
-        return;
-    }
-    const double thr = top - fabs(top) * near_top;
-    int near = 0;
-    for (int i = tid; i < n_cand; i += 256) {
-        const double v = (base - buf[i >> 1] + cross[i]) / total;
-        near += sup_counts(i, j, L, d.cur_rev, S) && isfinite(v) && v >= thr;
-    }
-    if (near) atomicAdd(&s_cnt, near);
-    __syncthreads();
-    if (tid == 0) { d.best[0] = first; d.best[1] = s_cnt; }
+    const int n_cand = 2 * S, cur_rev = d.cur_rev;
+    for (int i = tid; i < n_cand; i += 256) d.scores[i] = (base - buf[i >> 1] + cross[i]) / total;
+    pick_first_max_256(tid, n_cand, d.scores, d.best, near_top, [=](int i) { return sup_counts(i, j, L, cur_rev, S); });
 }
 
 static std::atomic<int> g_lds_sup_fast{0}, g_lds_sup_scores{0};

@@ -1148,20 +1148,23 @@ def support_summary(table, lengths, rev):
     return out
 
 
+def _score_rows(layout, total, flat, row_of):
+    """flat[c] = hicmi_p2_score of candidate c's materialised bin order ``row_of(c)``, at most SUPPORT_DIRECT_BYTES of
+    rows at a time: the table of the two DIRECT paths."""
+    per = max(1, SUPPORT_DIRECT_BYTES // (4 * layout.n))
+    for c0 in range(0, len(flat), per):
+        rows = np.stack([row_of(c) for c in range(c0, min(c0 + per, len(flat)))]).astype(np.int32)
+        flat[c0:c0 + len(rows)] = layout.ctx.p2_score(rows, total)
+
+
 def _support_direct(layout, ids, rev, total):
     """A/B path (HICMI_P2_SUPPORT_DIRECT=1): the same table from hicmi_p2_score on every candidate's materialised bin
     order, at most SUPPORT_DIRECT_BYTES of rows at a time."""
-    S, n = len(ids), layout.n
+    S = len(ids)
     table = np.zeros((S, S, 2))
-    lengths = [layout.length[int(i)] for i in ids]
-    if n >= 2 and total > 0:
-        flat = table.reshape(-1)
-        per = max(1, SUPPORT_DIRECT_BYTES // (4 * n))
-        for c0 in range(0, 2 * S * S, per):
-            cand = range(c0, min(c0 + per, 2 * S * S))
-            rows = np.stack([_support_row(layout, ids, rev, c // (2 * S), (c // 2) % S, c % 2) for c in cand])
-            flat[c0:c0 + len(rows)] = layout.ctx.p2_score(rows, total)
-        return table, support_summary(table, lengths, rev)
+    if layout.n >= 2 and total > 0:
+        _score_rows(layout, total, table.reshape(-1), lambda c: _support_row(layout, ids, rev, c // (2 * S), (c // 2) % S, c % 2))
+        return table, support_summary(table, [layout.length[int(i)] for i in ids], rev)
     return table, np.tile(np.array([-1, 0], np.int32), (S, 1))
 
 
@@ -1172,28 +1175,33 @@ def _literal_rows(layout, rows, total):
     return np.concatenate(out) if out else np.zeros(0)
 
 
+def _decide_near(flat, counts, pick, row_of, layout, total):
+    """A pick with rivals within NEAR_TOP (a near count above 1) decided: ``flat`` are the scaffold's closed-form scores
+    and ``counts`` the candidates that compete; the table only ranks, so the rivals' bin orders ``row_of(c)`` are scored
+    literally (hicmi_p2_score_exact) and the first strict maximum in enumeration order is the pick."""
+    top = float(flat[pick])
+    near = np.flatnonzero(counts & np.isfinite(flat) & (flat >= top - abs(top) * NEAR_TOP))
+    top_lit = -math.inf
+    for c, v in zip(near, _literal_rows(layout, [row_of(int(c)) for c in near], total)):
+        if v > top_lit:
+            pick, top_lit = int(c), float(v)
+    return pick
+
+
 def _support_one(layout, ids, rev, total, table, best):
-    """One chromosome's result from its table: score0, flip / best columns and verdicts.  The table ranks; a scaffold
-    whose best move has rivals within NEAR_TOP is decided on their literal scores (hicmi_p2_score_exact), first strict
-    maximum.  The reported deltas are literal scores too - of the arrangement, each in-place flip and each best move, one
+    """One chromosome's result from its table: score0, flip / best columns and verdicts (the picks: _decide_near).
+    The reported deltas are literal scores too - of the arrangement, each in-place flip and each best move, one
     call - so that they do not depend on how the table was computed."""
     S = len(ids)
     lengths = [layout.length[int(i)] for i in ids]
     live = layout.n >= 2 and total > 0
     counts = support_counts(lengths, rev).reshape(S, 2 * S)
     flat = table.reshape(S, 2 * S)
-    picks = []
+    picks = [int(best[j][0]) if live else -1 for j in range(S)]
     for j in range(S):
-        pick, n_near = (int(best[j][0]), int(best[j][1])) if live else (-1, 0)
-        if pick >= 0 and n_near > 1:
-            top = float(flat[j][pick])
-            near = np.flatnonzero(counts[j] & np.isfinite(flat[j]) & (flat[j] >= top - abs(top) * NEAR_TOP))
-            lit = _literal_rows(layout, [_support_row(layout, ids, rev, j, int(c) // 2, int(c) % 2) for c in near], total)
-            top_lit = -math.inf
-            for c, v in zip(near, lit):                   # first strict maximum in enumeration order
-                if v > top_lit:
-                    pick, top_lit = int(c), float(v)
-        picks.append(pick)
+        if picks[j] >= 0 and int(best[j][1]) > 1:
+            picks[j] = _decide_near(flat[j], counts[j], picks[j], lambda c: _support_row(layout, ids, rev, j, c // 2, c % 2),
+                                    layout, total)
     flips = [j for j in range(S) if live and lengths[j] > 1 and S > 1]
     moves = [j for j in range(S) if picks[j] >= 0]
     lit = _literal_rows(layout, [layout.node_row(ids, rev)]
@@ -1233,6 +1241,35 @@ def _layout_jobs(lanes, orderedChromosomes, binList, chromList):
         yield jobs
 
 
+def _table_report(matrix, orderedChromosomes, binList, chromList, kind, direct_fn, job_of, extra, one):
+    """The driver of placementSupport (``kind`` "support") and breakSupport ("breaks"): every chromosome's (table, best)
+    from HICMI_P2_<KIND>_DIRECT=1's ``direct_fn(layout, ids, rev, total)``, else from one ctx.p2_<kind>_multi call per
+    round of lanes, else (a context without lanes, or SCORE_HOOK) from ctx.p2_<kind> one by one - ``job_of(layout, ids,
+    rev, total)``: a job's arguments after the context, ``extra``: the call's arguments after the jobs - and from those
+    ``one(layout, ids, rev, total, table, best, group)``: the chromosome's result, here given its names and orientations."""
+    ctx = matrix.ctx
+    matrix.bin_index(binList)
+    direct = os.environ.get("HICMI_P2_%s_DIRECT" % kind.upper(), "") not in ("", "0")
+    multi = not direct and SCORE_HOOK is None and hasattr(ctx, "workers") and hasattr(ctx, "p2_%s_multi" % kind)
+    lanes = matrix.lanes(len(orderedChromosomes)) if multi and len(orderedChromosomes) > 1 else [matrix]
+    out = []
+    for jobs in _layout_jobs(lanes, orderedChromosomes, binList, chromList):
+        if direct:
+            tables = [direct_fn(layout, ids, rev, total) for layout, ids, rev, total, _g in jobs]
+        elif multi:
+            tables = getattr(ctx, "p2_%s_multi" % kind)([(layout.ctx,) + job_of(layout, ids, rev, total)
+                                                         for layout, ids, rev, total, _g in jobs], *extra)
+        else:
+            tables = [getattr(layout.ctx, "p2_" + kind)(*(job_of(layout, ids, rev, total) + extra))
+                      for layout, ids, rev, total, _g in jobs]
+        for (layout, ids, rev, total, group), (table, best) in zip(jobs, tables):
+            res = one(layout, ids, rev, total, np.asarray(table), best, group)
+            res["names"] = [s.name for s in group]
+            res["orientations"] = [s.orientation for s in group]
+            out.append(res)
+    return out
+
+
 def placementSupport(matrix: GenomeMatrix, orderedChromosomes, binList, chromList=None):
     """How well the map supports a finished ordering: every scaffold of every chromosome is taken out of its
     chromosome's arrangement and put back at every gap in both orientations (include/hicmi.h,
@@ -1244,25 +1281,9 @@ def placementSupport(matrix: GenomeMatrix, orderedChromosomes, binList, chromLis
     layout being orderChromosome's: ``chromList[i]`` (the group file's rows) fixes it; without it the scaffolds are
     taken largest first in arrangement order.  On the device all chromosomes go through one hicmi_p2_support_multi
     call, one context each; HICMI_P2_SUPPORT_DIRECT=1 scores materialised candidates with hicmi_p2_score instead."""
-    ctx = matrix.ctx
-    matrix.bin_index(binList)
-    direct = os.environ.get("HICMI_P2_SUPPORT_DIRECT", "") not in ("", "0")
-    multi = not direct and SCORE_HOOK is None and hasattr(ctx, "workers") and hasattr(ctx, "p2_support_multi")
-    lanes = matrix.lanes(len(orderedChromosomes)) if multi and len(orderedChromosomes) > 1 else [matrix]
-    out = []
-    for jobs in _layout_jobs(lanes, orderedChromosomes, binList, chromList):
-        if direct:
-            tables = [_support_direct(layout, ids, rev, total) for layout, ids, rev, total, _g in jobs]
-        elif multi:
-            tables = ctx.p2_support_multi([(layout.ctx, ids, rev, total) for layout, ids, rev, total, _g in jobs])
-        else:
-            tables = [layout.ctx.p2_support(ids, rev, total) for layout, ids, rev, total, _g in jobs]
-        for (layout, ids, rev, total, group), (table, best) in zip(jobs, tables):
-            res = _support_one(layout, ids, rev, total, np.asarray(table), best)
-            res["names"] = [s.name for s in group]
-            res["orientations"] = [s.orientation for s in group]
-            out.append(res)
-    return out
+    return _table_report(matrix, orderedChromosomes, binList, chromList, "support", _support_direct,
+                         lambda layout, ids, rev, total: (ids, rev, total), (),
+                         lambda layout, ids, rev, total, table, best, group: _support_one(layout, ids, rev, total, table, best))
 
 
 def _layoutScaffolds(nodeList):
@@ -1373,20 +1394,15 @@ def _breaks_direct(layout, ids, rev, total, minPiece):
     row0 = layout.node_row(ids, rev)
     starts = np.concatenate([[0], np.cumsum(lengths)])
     cands = [(int(starts[j]), L, p, k) for j, L in enumerate(lengths) for p in range(1, L) for k in range(8)]
-    flat = table.reshape(-1)
-    per = max(1, SUPPORT_DIRECT_BYTES // (4 * layout.n))
-    for c0 in range(0, len(cands), per):
-        rows = np.stack([_break_row(row0, *c) for c in cands[c0:c0 + per]]).astype(np.int32)
-        flat[c0:c0 + len(rows)] = layout.ctx.p2_score(rows, total)
+    _score_rows(layout, total, table.reshape(-1), lambda c: _break_row(row0, *cands[c]))
     for j, L in enumerate(lengths):
         best[j] = break_summary(table[off[j]:off[j] + L - 1], L, minPiece)
     return table, best
 
 
 def _breaks_one(layout, ids, rev, total, table, best, group, minPiece):
-    """One chromosome's result from its table: score0, the best break of every scaffold and the verdicts.  The table
-    ranks; a scaffold whose best break has rivals within NEAR_TOP is decided on their literal scores
-    (hicmi_p2_score_exact), first strict maximum.  The reported floats are literal scores too - the arrangement and every
+    """One chromosome's result from its table: score0, the best break of every scaffold and the verdicts (the picks:
+    _decide_near).  The reported floats are literal scores too - the arrangement and every
     best break of the chromosome in one call - so that they do not depend on how the table was computed."""
     S = len(ids)
     lengths = [layout.length[int(i)] for i in ids]
@@ -1394,21 +1410,12 @@ def _breaks_one(layout, ids, rev, total, table, best, group, minPiece):
     starts = np.concatenate([[0], np.cumsum(lengths)]).astype(int)
     live = layout.n >= 2 and total > 0
     row0 = layout.node_row(ids, rev)
-    picks, nears = [], []
-    for j in range(S):
-        pick, n_near = (int(best[j][0]), int(best[j][1])) if live else (-1, 0)
-        nears.append(n_near)
-        if pick >= 0 and n_near > 1:
-            L = lengths[j]
-            flat = table[off[j]:off[j] + L - 1].reshape(-1)
-            top = float(flat[pick])
-            near = np.flatnonzero(break_counts(L, minPiece).reshape(-1) & np.isfinite(flat) & (flat >= top - abs(top) * NEAR_TOP))
-            lit = _literal_rows(layout, [_break_row(row0, int(starts[j]), L, int(c) // 8 + 1, int(c) % 8) for c in near], total)
-            top_lit = -math.inf
-            for c, v in zip(near, lit):                   # first strict maximum in enumeration order
-                if v > top_lit:
-                    pick, top_lit = int(c), float(v)
-        picks.append(pick)
+    nears = [int(best[j][1]) if live else 0 for j in range(S)]
+    picks = [int(best[j][0]) if live else -1 for j in range(S)]
+    for j, L in enumerate(lengths):
+        if picks[j] >= 0 and nears[j] > 1:
+            picks[j] = _decide_near(table[off[j]:off[j] + L - 1].reshape(-1), break_counts(L, minPiece).reshape(-1), picks[j],
+                                    lambda c: _break_row(row0, int(starts[j]), L, c // 8 + 1, c % 8), layout, total)
     moves = [j for j in range(S) if picks[j] >= 0]
     lit = _literal_rows(layout, [row0] + [_break_row(row0, int(starts[j]), lengths[j], picks[j] // 8 + 1, picks[j] % 8)
                                           for j in moves], total) if live else [0.0]
@@ -1444,29 +1451,11 @@ def breakSupport(matrix: GenomeMatrix, orderedChromosomes, binList, chromList=No
     Total, layout and lanes are placementSupport's.  On the device all chromosomes go through one hicmi_p2_breaks_multi
     call, one context each; HICMI_P2_BREAKS_DIRECT=1 scores materialised candidates with hicmi_p2_score instead.
     ``minPiece``: only cuts that leave both pieces at least that many bins compete for the best break."""
-    ctx = matrix.ctx
     minPiece = max(1, int(minPiece))
-    matrix.bin_index(binList)
-    direct = os.environ.get("HICMI_P2_BREAKS_DIRECT", "") not in ("", "0")
-    multi = not direct and SCORE_HOOK is None and hasattr(ctx, "workers") and hasattr(ctx, "p2_breaks_multi")
-    lanes = matrix.lanes(len(orderedChromosomes)) if multi and len(orderedChromosomes) > 1 else [matrix]
-    out = []
-    for jobs in _layout_jobs(lanes, orderedChromosomes, binList, chromList):
-        lens = [[layout.length[int(i)] for i in ids] for layout, ids, _r, _t, _g in jobs]
-        if direct:
-            tables = [_breaks_direct(layout, ids, rev, total, minPiece) for layout, ids, rev, total, _g in jobs]
-        elif multi:
-            tables = ctx.p2_breaks_multi([(layout.ctx, ids, rev, ln, total) for (layout, ids, rev, total, _g), ln in
-                                          zip(jobs, lens)], minPiece)
-        else:
-            tables = [layout.ctx.p2_breaks(ids, rev, ln, total, minPiece) for (layout, ids, rev, total, _g), ln in
-                      zip(jobs, lens)]
-        for (layout, ids, rev, total, group), (table, best) in zip(jobs, tables):
-            res = _breaks_one(layout, ids, rev, total, np.asarray(table), best, group, minPiece)
-            res["names"] = [s.name for s in group]
-            res["orientations"] = [s.orientation for s in group]
-            out.append(res)
-    return out
+    return _table_report(matrix, orderedChromosomes, binList, chromList, "breaks",
+                         lambda layout, ids, rev, total: _breaks_direct(layout, ids, rev, total, minPiece),
+                         lambda layout, ids, rev, total: (ids, rev, [layout.length[int(i)] for i in ids], total), (minPiece,),
+                         lambda *a: _breaks_one(*a, minPiece))
 
 
 def breakSupportText(results):

@@ -26,8 +26,8 @@ import sys
 import time
 
 from . import orderGenome as p2
-from .hostio import initiateLoci, paused_gc
 from .run_hicAssembler import ensureAllVariablesAreSet, readConfigFileToVariables
+from .supportPart2 import reportOnOrderFile
 
 
 def runBreaks(hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroupFile, chromosomeOrderFile, outFile,
@@ -35,17 +35,11 @@ def runBreaks(hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroupFi
     """The report for ``chromosomeOrderFile`` written to ``outFile`` (and the broken group file to ``brokenFile``);
     returns breakSupport's results."""
     t0 = time.time()
-    binDict = p2.readGroupingsToValidBins(chromosomeGroupFile)
-    binList = initiateLoci(hicProBedFile, hicProBiasFile, binID_dict=binDict)
-    matrix = p2.buildAdjacencyMatrix(hicProMatrixFile, binList, device=device)
-    try:
-        with paused_gc():
-            chromList = p2.readChromsFromFile(chromosomeGroupFile)
-            ordered = p2.scaffoldsFromOrderFile(chromList, chromosomeOrderFile)
-            results = p2.breakSupportToFiles(matrix, ordered, binList, chromosomeGroupFile, outFile, brokenFile,
-                                             fullDir=fullDir, minPiece=minPiece, chromList=chromList)
-    finally:
-        matrix.ctx.close()
+    results = reportOnOrderFile(
+        hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroupFile, chromosomeOrderFile, device,
+        lambda matrix, ordered, binList, chromList: p2.breakSupportToFiles(
+            matrix, ordered, binList, chromosomeGroupFile, outFile, brokenFile, fullDir=fullDir, minPiece=minPiece,
+            chromList=chromList))
     print("Total run-time of the break support = " + str(time.time() - t0))
     return results
 

@@ -27,10 +27,10 @@ from .hostio import initiateLoci, paused_gc
 from .run_hicAssembler import ensureAllVariablesAreSet, readConfigFileToVariables
 
 
-def runSupport(hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroupFile, chromosomeOrderFile, outFile,
-               fullDir=None, device=0):
-    """The report for ``chromosomeOrderFile`` written to ``outFile``; returns placementSupport's results."""
-    t0 = time.time()
+def reportOnOrderFile(hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroupFile, chromosomeOrderFile, device,
+                      report):
+    """What runSupport and supportBreaks.runBreaks share: the map of the grouped bins loaded once, the group file and the
+    order file read, and ``report(matrix, ordered chromosomes, binList, chromList)`` returned."""
     binDict = p2.readGroupingsToValidBins(chromosomeGroupFile)
     binList = initiateLoci(hicProBedFile, hicProBiasFile, binID_dict=binDict)
     matrix = p2.buildAdjacencyMatrix(hicProMatrixFile, binList, device=device)
@@ -38,10 +38,22 @@ def runSupport(hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroupF
         with paused_gc():
             chromList = p2.readChromsFromFile(chromosomeGroupFile)
             ordered = p2.scaffoldsFromOrderFile(chromList, chromosomeOrderFile)
-            results = p2.placementSupport(matrix, ordered, binList, chromList)
-            p2.writePlacementSupportToFile(results, outFile, fullDir)
+            return report(matrix, ordered, binList, chromList)
     finally:
         matrix.ctx.close()
+
+
+def runSupport(hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroupFile, chromosomeOrderFile, outFile,
+               fullDir=None, device=0):
+    """The report for ``chromosomeOrderFile`` written to ``outFile``; returns placementSupport's results."""
+    t0 = time.time()
+
+    def report(matrix, ordered, binList, chromList):
+        results = p2.placementSupport(matrix, ordered, binList, chromList)
+        p2.writePlacementSupportToFile(results, outFile, fullDir)
+        return results
+    results = reportOnOrderFile(hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroupFile, chromosomeOrderFile,
+                                device, report)
     print("Total run-time of the placement support = " + str(time.time() - t0))
     return results
 

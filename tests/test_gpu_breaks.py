@@ -267,6 +267,41 @@ def test_min_piece_keeps_the_table_and_narrows_the_best(edges):
     assert [r["verdict"] != "NA" for r in three[4]["rows"]].count(True) == 3        # 7, 6 and 65 bins
 
 
+@pytest.mark.parametrize("kind", ["decay", "ones"])
+def test_best_is_the_summary_of_the_devices_own_table(kind):
+    """The device's pick against its host restatement on the SAME doubles: ``best`` of hicmi_p2_breaks_multi equals
+    break_summary of the blocks that call returned - integer equality, no tolerance, both sides evaluate
+    top - |top| * NEAR_TOP on the same numbers.  8 (L - 1) candidates around the pick's 256-lane stride (L = 32, 33, 34),
+    two strides (L = 65) and its exits (L = 2: nothing competes; L = 3), minPiece 1 and 3, one call each.  On the map of
+    ones many scores are exactly equal: the first of equals wins and near counts above 1 must occur."""
+    from hic_genome_assembler_amd import _lib, orderGenome as p2
+    groups, arrs, pos = [], [], 0
+    for prefix, lens in (("a", [2, 33, 65]), ("b", [34, 3, 32])):
+        g, pos = _chromosome(prefix, pos, lens)
+        groups.append(g)
+        arrs.append([(name, "-" if i == 1 else "+") for i, (name, _idx) in enumerate(g)])
+    host = _decay_map(pos, 43) if kind == "decay" else np.ones((pos, pos))
+    binList, chromList, ordered = _explicit(host, groups, arrs)
+    near = 0
+    with _lib.Context(0) as ctx:
+        ctx.set_contacts(host)
+        matrix = p2.GenomeMatrix(ctx)
+        matrix.bin_index(binList)
+        (jobs,) = p2._layout_jobs(matrix.lanes(len(ordered)), ordered, binList, chromList)
+        lens = [[layout.length[int(i)] for i in ids] for layout, ids, _r, _t, _g in jobs]
+        for min_piece in (1, 3):
+            out = _lib.Context.p2_breaks_multi([(layout.ctx, ids, rev, ln, total) for (layout, ids, rev, total, _g), ln
+                                                in zip(jobs, lens)], min_piece)
+            for ln, (table, best) in zip(lens, out):
+                off, n_rows = p2._break_offsets(ln)
+                assert table.shape == (n_rows, 8) and np.isfinite(table).all()
+                want = np.array([p2.break_summary(table[o:o + L - 1], L, min_piece) for o, L in zip(off, ln)], np.int32)
+                assert np.array_equal(best, want), (min_piece, ln)
+                near = max(near, int(best[:, 1].max()))
+    print(kind, "map: largest near count", near)
+    assert near > 1 or kind == "decay"
+
+
 def _sample(j, L):
     return list(range(1, L)) if L <= 64 else sorted(set([1, 2, 3, L - 3, L - 2, L - 1] + list(range(37, L, 37))))
 

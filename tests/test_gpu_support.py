@@ -156,10 +156,8 @@ def _decay_map(n, seed):
     return np.ascontiguousarray(np.triu(c) + np.triu(c, 1).T)
 
 
-def _run_explicit(host, groups, arrangements, pick=None):
-    """placementSupport on chromosomes given as [(scaffold, row indices)] lists and [(scaffold, orientation)]
-    arrangements, and the oracle on the same."""
-    from hic_genome_assembler_amd import _lib, orderGenome as p2
+def _explicit(host, groups, arrangements):
+    from hic_genome_assembler_amd import orderGenome as p2
     from hic_genome_assembler_amd.hostio import Bin
     binList = [Bin(1000 + i, "c", i, i + 1, 1.0, 0.0) for i in range(len(host))]
     chromList = [sorted([binList[i].ID, name] for name, idx in g for i in idx) for g in groups]
@@ -172,6 +170,14 @@ def _run_explicit(host, groups, arrangements, pick=None):
                 s.flipOrientation()
             scaffs.append(s)
         ordered.append(scaffs)
+    return binList, chromList, ordered
+
+
+def _run_explicit(host, groups, arrangements, pick=None):
+    """placementSupport on chromosomes given as [(scaffold, row indices)] lists and [(scaffold, orientation)]
+    arrangements, and the oracle on the same."""
+    from hic_genome_assembler_amd import _lib, orderGenome as p2
+    binList, chromList, ordered = _explicit(host, groups, arrangements)
     with _lib.Context(0) as ctx:
         ctx.set_contacts(host)
         results = p2.placementSupport(p2.GenomeMatrix(ctx), ordered, binList, chromList)
@@ -208,6 +214,38 @@ def test_small_edges_in_one_call():
     assert results[3]["score0"] == 0.0 and results[3]["rows"][0]["best_gap"] is None
     from hic_genome_assembler_amd import orderGenome as p2
     assert p2.placementSupportText(results).count("\tNA\tNA\tNA\t") == 2
+
+
+@pytest.mark.parametrize("kind", ["decay", "ones"])
+def test_best_is_the_summary_of_the_devices_own_table(kind):
+    """The device's pick against its host restatement on the SAME doubles: ``best`` of hicmi_p2_support_multi equals
+    support_summary of the table that call returned - integer equality, no tolerance, both sides evaluate
+    top - |top| * NEAR_TOP on the same numbers.  2 S candidates around the pick's 256-lane stride (S = 127, 128, 129) and
+    its exits (S = 1: nothing competes; S = 2), scaffolds of 1 to 3 bins, one call.  On the map of ones many scores are
+    exactly equal: the first of equals wins and near counts above 1 must occur."""
+    from hic_genome_assembler_amd import _lib, orderGenome as p2
+    rng = np.random.default_rng(3)
+    groups, arrs, pos = [], [], 0
+    for S in (1, 2, 127, 128, 129):
+        g, pos = _chromosome("s%d_" % S, pos, [int(v) for v in rng.integers(1, 4, S)])
+        groups.append(g)
+        arrs.append([(g[i][0], "-" if rng.random() < 0.5 else "+") for i in rng.permutation(S)])
+    host = _decay_map(pos, 41) if kind == "decay" else np.ones((pos, pos))
+    binList, chromList, ordered = _explicit(host, groups, arrs)
+    with _lib.Context(0) as ctx:
+        ctx.set_contacts(host)
+        matrix = p2.GenomeMatrix(ctx)
+        matrix.bin_index(binList)
+        (jobs,) = p2._layout_jobs(matrix.lanes(len(ordered)), ordered, binList, chromList)
+        out = _lib.Context.p2_support_multi([(layout.ctx, ids, rev, total) for layout, ids, rev, total, _g in jobs])
+    near = 0
+    for (layout, ids, rev, _t, _g), (table, best) in zip(jobs, out):
+        lengths = [layout.length[int(i)] for i in ids]
+        assert table.shape == (len(ids), len(ids), 2) and (len(ids) == 1 or np.isfinite(table).all())
+        assert np.array_equal(best, p2.support_summary(table, lengths, rev)), len(ids)
+        near = max(near, int(best[:, 1].max()))
+    print(kind, "map: largest near count", near)
+    assert near > 1 or kind == "decay"
 
 
 def test_a_chromosome_above_8192_bins_beside_a_small_one():
