@@ -94,6 +94,8 @@ SIGNATURES = {
     "hicmi_p2_support_multi": (ctypes.c_int, [c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hicmi_p2_breaks": (ctypes.c_int, [_vp, _vp, _vp, c_i64, c_dbl, c_i64, _vp, _vp]),
     "hicmi_p2_breaks_multi": (ctypes.c_int, [c_i64, _vp, _vp, _vp, _vp, _vp, c_i64, _vp, _vp]),
+    "hicmi_p2_inversions": (ctypes.c_int, [_vp, _vp, _vp, c_i64, c_dbl, c_i64, _vp, _vp]),
+    "hicmi_p2_inversions_multi": (ctypes.c_int, [c_i64, _vp, _vp, _vp, _vp, _vp, c_i64, _vp, _vp]),
     "hicmi_p2_scan_pass": (ctypes.c_int, [_vp, _vp, _vp, c_i64, c_i64, c_dbl, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl),
                                           ctypes.POINTER(ctypes.c_int32)]),
     "hicmi_p2_scan_all": (ctypes.c_int, [_vp, _vp, _vp, c_i64, c_i64, c_dbl, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl),
@@ -734,6 +736,21 @@ class Context:
         maximum among the competing candidates or -1, how many of them lie within 1e-9 of it]."""
         return Context._table_multi("hicmi_p2_breaks_multi", jobs, [j[4] for j in jobs],
                                     lambda j, S: (sum(max(int(ln) - 1, 0) for ln in j[3]), 8), (int(min_piece),))
+
+    def p2_inversions(self, ids, rev, total: float, max_span: int = 0):
+        """Inversion support of one chromosome (hicmi_p2_inversions): see p2_inversions_multi."""
+        return self._table_call(self._lib.hicmi_p2_inversions, ids, rev, np.empty((len(ids), len(ids)), np.float64),
+                                (float(total), int(max_span)))
+
+    @staticmethod
+    def p2_inversions_multi(jobs, max_span: int = 0):
+        """Inversion support of several chromosomes in one pair of launches (hicmi_p2_inversions_multi).
+        jobs: [(context, ids, rev, total)], one distinct context per chromosome; returns [(table, best)]: the S x S
+        closed-form scores of "scaffolds i ... j reversed and flipped" (row i, column j; 0.0 for j < i and beyond
+        ``max_span`` scaffolds) and S x 2 int32 of [j of the first maximum among the competing candidates with left end i
+        or -1, how many of them lie within 1e-9 of it]."""
+        return Context._table_multi("hicmi_p2_inversions_multi", jobs, [j[3] for j in jobs], lambda j, S: (S, S),
+                                    (int(max_span),))
 
     def p2_scan_pass(self, ids, rev, k, total, best, cur_fast):
         """One round of scanOrdering; returns (ids, rev, best, cur_fast, improved)."""

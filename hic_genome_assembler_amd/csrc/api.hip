@@ -134,6 +134,7 @@ struct hicmi_ctx {
     InsStep* d_ins_steps = nullptr; int64_t ins_steps_cap = 0;       // [step][job] records of a lock-step queue
     SupRec* d_sup_recs = nullptr; int64_t sup_recs_cap = 0;          // hicmi_p2_support_multi: (chromosome, left-out scaffold) records
     BrkRec* d_brk_recs = nullptr; int64_t brk_recs_cap = 0;          // hicmi_p2_breaks_multi: (chromosome, scaffold of 2+ bins) records
+    InvRec* d_inv_recs = nullptr; int64_t inv_recs_cap = 0;          // hicmi_p2_inversions_multi: (chromosome, left end) records
     // group support (k_group_support.hip): the member lists of a call, and its partials + the two tables
     int32_t* d_gs_lists = nullptr; int64_t gs_lists_cap = 0;
     double* d_gs_sums = nullptr; int64_t gs_sums_cap = 0;
@@ -393,7 +394,7 @@ int hicmi_destroy(hicmi_ctx* c)
     free_dev(c->d_scaf_start); free_dev(c->d_scaf_len); free_dev(c->d_arr_packed);
     free_dev(c->d_pos2sel); free_dev(c->d_orders); free_dev(c->d_orients);
     free_dev(c->d_G); free_dev(c->d_delta); free_dev(c->d_wb); free_dev(c->d_wnear);
-    free_dev(c->d_arr_packed2); free_dev(c->d_pos2sel2); free_dev(c->d_ins_T); free_dev(c->d_ins_partial); free_dev(c->d_brk_recs);
+    free_dev(c->d_arr_packed2); free_dev(c->d_pos2sel2); free_dev(c->d_ins_T); free_dev(c->d_ins_partial); free_dev(c->d_brk_recs); free_dev(c->d_inv_recs);
     free_dev(c->d_ins_blob); free_dev(c->d_ins_steps); free_dev(c->d_sup_recs);
     free_dev(c->d_gs_lists); free_dev(c->d_gs_sums);
     free_dev(c->d_ice); free_dev(c->d_ice_mask);
@@ -2864,6 +2865,67 @@ int hicmi_p2_breaks(hicmi_ctx* c, const int32_t* ids, const uint8_t* rev, int64_
                     double* scores_out, int32_t* best_out)
 {
     return hicmi_p2_breaks_multi(1, &c, &ids, &rev, &S, &total, min_piece, &scores_out, &best_out);
+}
+
+// Inversion support (k_part2_invert.hip): the scaffolds i ... j of every job's arrangement reversed and flipped, for
+// every i <= j; one record per (job, left end i).
+int hicmi_p2_inversions_multi(int64_t n_jobs, hicmi_ctx* const* ctxs, const int32_t* const* ids, const uint8_t* const* rev,
+                              const int64_t* S, const double* totals, int64_t max_span, double* const* scores_out,
+                              int32_t* const* best_out)
+{
+    if (n_jobs < 1 || !ctxs || !ids || !rev || !S || !totals || !scores_out || !best_out || max_span < 0)
+        return fail(HICMI_EINVAL, "bad arguments");
+    const int NB = INV_BASE_SLABS;
+    // the bound on a call's work; HICMI_P2_INVERT_MAX_WORK lowers or raises it (tests refuse a small job with it)
+    const char* env = getenv("HICMI_P2_INVERT_MAX_WORK");
+    const double max_work = env && *env ? atof(env) : INV_MAX_WORK;
+    const int64_t span = std::min<int64_t>(max_span, INV_MAX_S);
+    int64_t n_wg = 0;
+    double work = 0.0;
+    TableOps<InvRec> ops;
+    ops.max_S = INV_MAX_S; ops.recs = &hicmi_ctx::d_inv_recs; ops.recs_cap = &hicmi_ctx::inv_recs_cap;
+    ops.size = [&](int64_t j, int64_t& n_table, int64_t& scratch, int64_t& n_rec) {
+        n_table = S[j] * S[j]; scratch = NB; n_rec = S[j];
+    };
+    ops.append = [&](int64_t j, double* d_scores, int32_t* d_best, std::vector<InvRec>& recs, double& algo) {
+        hicmi_ctx* c = ctxs[j];
+        const int64_t Sj = S[j], n = c->n_arr;
+        const double work0 = work;
+        for (int64_t i = 0; i < Sj; i++) {
+            InvRec d;
+            memset(&d, 0, sizeof(d));
+            d.M2 = c->dM2; d.H = c->d_H; d.ld2 = c->ld2;
+            d.pos = c->d_pos2sel; d.arr_pos = c->d_arr_packed + Sj;
+            d.base = c->d_ins_partial;
+            d.scores = d_scores + Sj * i; d.best = d_best + 2 * i;
+            d.total = totals[j];
+            d.wg0 = n_wg;
+            d.n = (int32_t)n; d.S = (int32_t)Sj; d.i = (int32_t)i;
+            d.n_j = (int32_t)(span > 0 ? std::min<int64_t>(Sj - i, span) : Sj - i);
+            d.max_span = (int32_t)span;
+            d.n_base = i == 0 ? NB : 0;
+            n_wg += d.n_base + d.n_j;
+            recs.push_back(d);
+            for (int64_t k = i; k < i + d.n_j; k++) {
+                const double len = (double)(c->h_arr_pos[(size_t)k + 1] - c->h_arr_pos[(size_t)i]);
+                work += len * ((double)n - len);
+            }
+        }
+        algo += 8.0 * (0.5 * (double)n * (double)n + (work - work0));
+        if (work > max_work)
+            return fail(HICMI_EUNSUPPORTED, "inversion table of %.3g matrix reads (limit %.3g): set max_span to bound the segments",
+                        work, max_work);
+        if (n_wg > 0x7fffffff) return fail(HICMI_EUNSUPPORTED, "more than 2^31 - 1 workgroups in one call: set max_span");
+        return (int)HICMI_OK;
+    };
+    ops.launch = [&](const InvRec* d_recs, int n_rec) { launch_inv(d_recs, n_rec, n_wg, kNearTop, ctxs[0]->stream); };
+    return run_table_jobs(n_jobs, ctxs, ids, rev, S, totals, scores_out, best_out, ops);
+}
+
+int hicmi_p2_inversions(hicmi_ctx* c, const int32_t* ids, const uint8_t* rev, int64_t S, double total, int64_t max_span,
+                        double* scores_out, int32_t* best_out)
+{
+    return hicmi_p2_inversions_multi(1, &c, &ids, &rev, &S, &total, max_span, &scores_out, &best_out);
 }
 
 int hicmi_p2_scan_pass(hicmi_ctx* c, int32_t* ids, uint8_t* rev, int64_t S, int64_t k, double total, double* best_io,

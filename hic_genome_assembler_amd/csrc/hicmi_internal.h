@@ -440,6 +440,25 @@ struct BrkRec {
 };
 void launch_brk(const BrkRec* recs, int n_rec, int64_t n_wg, double near_top, hipStream_t s);
 
+// k_part2_invert.hip: inversion support (hicmi_p2_inversions_multi).  One record per (chromosome, left end i): the
+// scaffolds i ... j of the arrangement reversed and flipped, for every right end j = i ... i + n_j - 1.
+static constexpr int INV_BASE_SLABS = 64;     // partial sums of a chromosome's BASE term
+static constexpr int INV_MAX_S = 4096;        // scaffolds per chromosome (the table has S^2 entries)
+static constexpr double INV_MAX_WORK = 1e13;  // matrix elements read by one call: sum of len * (n - len) over its candidates
+struct InvRec {
+    const double* M2; const double* H; int64_t ld2;
+    const int32_t* pos;                       // A as bin order, n entries
+    const int32_t* arr_pos;                   // prefix positions of A's S scaffolds, S + 1 entries
+    double* base;                             // the chromosome's INV_BASE_SLABS BASE slabs (one area for all its records)
+    double* scores;                           // out: row i of the S x S table, score(i, j) at [j]
+    int32_t* best;                            // out: the pick (pick_first_max_256) over inv_counts
+    double total;
+    int64_t wg0;                              // first workgroup of this record in k_inv_tables
+    int32_t n, S, i, n_j;                     // n_j: right ends computed, j = i ... i + n_j - 1 (max_span cuts it short)
+    int32_t max_span, n_base;                 // n_base: INV_BASE_SLABS for a chromosome's first record (it forms the slabs), else 0
+};
+void launch_inv(const InvRec* recs, int n_rec, int64_t n_wg, double near_top, hipStream_t s);
+
 // k_group_support.hip: group support (hicmi_group_sums).  rows: the grouped rows sorted by group, ascending inside a
 // group; chunks[c]: rows[row0 .. row0 + cnt) with cnt <= GS_CHUNK, all of one group; group_chunk0[g] .. [g + 1]: the
 // chunks of group g; sbins / soff: the bins sorted by scaffold.  partial: n_chunks x n, binsum: n x G, scafsum: S x G.

@@ -1241,15 +1241,16 @@ def _layout_jobs(lanes, orderedChromosomes, binList, chromList):
         yield jobs
 
 
-def _table_report(matrix, orderedChromosomes, binList, chromList, kind, direct_fn, job_of, extra, one):
-    """The driver of placementSupport (``kind`` "support") and breakSupport ("breaks"): every chromosome's (table, best)
+def _table_report(matrix, orderedChromosomes, binList, chromList, kind, direct_fn, job_of, extra, one, switch=None):
+    """The driver of placementSupport (``kind`` "support"), breakSupport ("breaks") and inversionSupport ("inversions",
+    whose switch is spelt HICMI_P2_INVERT_DIRECT: ``switch``): every chromosome's (table, best)
     from HICMI_P2_<KIND>_DIRECT=1's ``direct_fn(layout, ids, rev, total)``, else from one ctx.p2_<kind>_multi call per
     round of lanes, else (a context without lanes, or SCORE_HOOK) from ctx.p2_<kind> one by one - ``job_of(layout, ids,
     rev, total)``: a job's arguments after the context, ``extra``: the call's arguments after the jobs - and from those
     ``one(layout, ids, rev, total, table, best, group)``: the chromosome's result, here given its names and orientations."""
     ctx = matrix.ctx
     matrix.bin_index(binList)
-    direct = os.environ.get("HICMI_P2_%s_DIRECT" % kind.upper(), "") not in ("", "0")
+    direct = os.environ.get(switch or "HICMI_P2_%s_DIRECT" % kind.upper(), "") not in ("", "0")
     multi = not direct and SCORE_HOOK is None and hasattr(ctx, "workers") and hasattr(ctx, "p2_%s_multi" % kind)
     lanes = matrix.lanes(len(orderedChromosomes)) if multi and len(orderedChromosomes) > 1 else [matrix]
     out = []
@@ -1527,6 +1528,289 @@ def breakSupportToFiles(matrix, orderedChromosomes, binList, chromosomeGroupFile
     return results
 
 
+# ---- inversion support of a finished ordering ------------------------------------------
+def inversion_counts(S, maxSpan=0):
+    """(S, S) mask of the candidates that compete for a left end's best inversion: row i, column j = scaffolds i ... j
+    reversed and flipped, with j > i (j = i is placement support's in-place flip), not (0, S - 1) (the chromosome read
+    backwards: the same objective) and, with ``maxSpan`` > 0, at most maxSpan scaffolds (include/hicmi.h,
+    hicmi_p2_inversions)."""
+    i, j = np.indices((S, S))
+    m = j > i
+    if S > 1:
+        m[0, S - 1] = False
+    if maxSpan > 0:
+        m &= j - i + 1 <= maxSpan
+    return m
+
+
+def inversion_work(lengths, maxSpan=0):
+    """Matrix elements that one chromosome's table reads: the sum of len * (n - len) over the computed candidates
+    (i <= j, at most ``maxSpan`` scaffolds when > 0), len the bins of the segment - the figure hicmi_p2_inversions_multi
+    holds against its bound of 1e13 per call."""
+    pos = np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))])
+    n, S, work = int(pos[-1]), len(lengths), 0
+    for i in range(S):
+        seg = pos[i + 1:(i + maxSpan if maxSpan > 0 else S) + 1] - pos[i]
+        work += int(np.sum(seg * (n - seg)))
+    return work
+
+
+def inversion_summary(table, maxSpan=0):
+    """What hicmi_p2_inversions returns as ``best`` from an S x S table of scores: per left end [j of the first maximum
+    over inversion_counts, or -1; how many competing candidates lie within NEAR_TOP of it]."""
+    flat = np.asarray(table, dtype=np.float64)
+    S = len(flat)
+    counts = inversion_counts(S, maxSpan)
+    out = np.zeros((S, 2), np.int32)
+    for i in range(S):
+        ok = counts[i] & np.isfinite(flat[i])
+        if not ok.any():
+            out[i] = (-1, 0)
+            continue
+        v = np.where(ok, flat[i], -np.inf)
+        top = float(v.max())
+        out[i] = (int(np.argmax(v)), int(np.count_nonzero(v >= top - abs(top) * NEAR_TOP)))
+    return out
+
+
+def _inversion_row(layout, ids, rev, i, j):
+    """Bin order (selection indices) of "the arrangement with its scaffolds i ... j in reverse order, each flipped"."""
+    oi = [int(v) for v in ids]
+    orr = [int(v) for v in rev]
+    oi[i:j + 1] = oi[i:j + 1][::-1]
+    orr[i:j + 1] = [1 - r for r in orr[i:j + 1][::-1]]
+    return layout.node_row(oi, orr)
+
+
+def _inversions_direct(layout, ids, rev, total, maxSpan):
+    """A/B path (HICMI_P2_INVERT_DIRECT=1): the same table from hicmi_p2_score on every computed candidate's materialised
+    bin order, at most SUPPORT_DIRECT_BYTES of rows at a time."""
+    S = len(ids)
+    table = np.zeros((S, S))
+    if layout.n < 2 or not total > 0:
+        return table, np.tile(np.array([-1, 0], np.int32), (S, 1))
+    cands = [(i, j) for i in range(S) for j in range(i, S) if maxSpan <= 0 or j - i + 1 <= maxSpan]
+    flat = np.zeros(len(cands))
+    _score_rows(layout, total, flat, lambda c: _inversion_row(layout, ids, rev, *cands[c]))
+    for (i, j), v in zip(cands, flat):
+        table[i, j] = v
+    return table, inversion_summary(table, maxSpan)
+
+
+def _inversions_one(layout, ids, rev, total, table, best, group, maxSpan):
+    """One chromosome's result from its table: score0, the best inversion of every left end and the verdicts (the picks:
+    _decide_near).  The reported floats are literal scores - the arrangement and every best inversion of the chromosome
+    in one call - so that they do not depend on how the table was computed."""
+    S = len(ids)
+    lengths = [layout.length[int(i)] for i in ids]
+    live = layout.n >= 2 and total > 0
+    counts = inversion_counts(S, maxSpan)
+    nears = [int(best[i][1]) if live else 0 for i in range(S)]
+    picks = [int(best[i][0]) if live else -1 for i in range(S)]
+    for i in range(S):
+        if picks[i] >= 0 and nears[i] > 1:
+            picks[i] = _decide_near(table[i], counts[i], picks[i], lambda c: _inversion_row(layout, ids, rev, i, c), layout,
+                                    total)
+    moves = [i for i in range(S) if picks[i] >= 0]
+    lit = _literal_rows(layout, [layout.node_row(ids, rev)] + [_inversion_row(layout, ids, rev, i, picks[i]) for i in moves],
+                        total) if live else [0.0]
+    score0 = float(lit[0])
+    delta_of = dict(zip(moves, (float(v) - score0 for v in lit[1:])))
+    rows = []
+    for i in range(S):
+        delta = delta_of.get(i)
+        if delta is None:
+            end = end_name = span = span_bins = gain = None
+            verdict = "NA"
+        else:
+            end = picks[i]
+            end_name, span, span_bins = group[end].name, end - i + 1, sum(lengths[i:end + 1])
+            gain = delta / score0
+            verdict = "invertible" if delta > 0 else "supported"
+        rows.append({"bins": lengths[i], "best_j": end, "best_end": end_name, "span": span, "span_bins": span_bins,
+                     "best_delta": delta, "gain": gain, "verdict": verdict, "near": nears[i]})
+    return {"score0": score0, "total": total, "table": table, "rows": rows, "maxSpan": maxSpan}
+
+
+def inversionSupport(matrix: GenomeMatrix, orderedChromosomes, binList, chromList=None, maxSpan=0):
+    """Which runs of consecutive scaffolds the map would rather read backwards: for every pair i <= j of every
+    chromosome, the scaffolds i ... j in reverse order, each flipped (include/hicmi.h,
+    hicmi_p2_inversions).  Returns one dict per chromosome: 'score0' (literal objective of the arrangement), 'total',
+    'table' (S x S scores: row = first scaffold of the segment, column = last; 0.0 below the diagonal and beyond
+    ``maxSpan`` scaffolds), 'names', 'orientations', 'maxSpan' and 'rows' (per scaffold in arrangement order, as the left
+    end of a segment: bins, best_j, best_end, span, span_bins, best_delta, gain, verdict, and near: how many competing
+    candidates lay within NEAR_TOP of the top closed-form score).
+
+    Total, layout and lanes are placementSupport's.  On the device all chromosomes go through one
+    hicmi_p2_inversions_multi call, one context each; HICMI_P2_INVERT_DIRECT=1 scores materialised candidates with
+    hicmi_p2_score instead.  ``maxSpan`` > 0: only segments of at most that many scaffolds are computed and compete."""
+    maxSpan = max(0, int(maxSpan))
+    return _table_report(matrix, orderedChromosomes, binList, chromList, "inversions",
+                         lambda layout, ids, rev, total: _inversions_direct(layout, ids, rev, total, maxSpan),
+                         lambda layout, ids, rev, total: (ids, rev, total), (maxSpan,),
+                         lambda *a: _inversions_one(*a, maxSpan), switch="HICMI_P2_INVERT_DIRECT")
+
+
+def inversionSupportText(results):
+    """The report: per chromosome ``### Chromosome grouping i ### score0``, then one tab-separated line per scaffold in
+    arrangement order, as the left end of a segment: scaffold, orientation, bins, best_end, span, span_bins, best_delta,
+    gain, verdict.  Floats are written with repr; a left end without a competing candidate: NA."""
+    text = []
+    for k, res in enumerate(results):
+        text.append("### Chromosome grouping " + str(k + 1) + " ### " + repr(res["score0"]) + "\n")
+        for name, orient, row in zip(res["names"], res["orientations"], res["rows"]):
+            text.append("\t".join([name, orient, str(row["bins"])] + [_support_text(row[key]) for key in
+                                                                      ("best_end", "span", "span_bins", "best_delta", "gain")]
+                                  + [row["verdict"]]) + "\n")
+    return "".join(text)
+
+
+def writeInversionSupportToFile(results, outFile, fullDir=None):
+    """inversionSupportText to ``outFile``; ``fullDir``: also each chromosome's S x S table as ``Chr_i.inversions.tsv``
+    (row = first scaffold of the segment, columns = last scaffold)."""
+    with open(outFile, "w") as fh:
+        fh.write(inversionSupportText(results))
+    if fullDir:
+        os.makedirs(fullDir, exist_ok=True)
+        for k, res in enumerate(results):
+            with open(os.path.join(fullDir, "Chr_%d.inversions.tsv" % (k + 1)), "w") as fh:
+                fh.write("\t".join(["scaffold"] + list(res["names"])) + "\n")
+                for name, line in zip(res["names"], np.asarray(res["table"])):
+                    fh.write("\t".join([name] + [repr(float(v)) for v in line]) + "\n")
+    print("Inversion support written for scaffolds " + str(sum(len(r["rows"]) for r in results)))
+
+
+# ---- refinement: the best relocation or inversion applied, round by round (DESIGN.md 9j) ---------------
+REFINE_MOVES = ("relocate", "invert")
+
+
+def choose_move(rel_rows, inv_rows, score0, minGain=0.0):
+    """The move of one round for one chromosome, or None when it has converged.  ``rel_rows[j]``: (gap, reversed,
+    literal delta) of scaffold j's decided best relocation or None; ``inv_rows[i]``: (j, literal delta) of left end i's
+    decided best inversion or None.  The first strict maximum of the deltas wins, relocations j = 0 ... S-1 before
+    inversions i = 0 ... S-2; it is applied only if its delta is > 0 and > minGain * |score0|.  Returns
+    ("relocate", j, gap, reversed, delta) or ("invert", i, j, delta)."""
+    best, top = None, -math.inf
+    for j, row in enumerate(rel_rows or ()):
+        if row is not None and row[2] > top:
+            best, top = ("relocate", j, int(row[0]), int(row[1]), float(row[2])), float(row[2])
+    for i, row in enumerate(inv_rows or ()):
+        if row is not None and row[1] > top:
+            best, top = ("invert", i, int(row[0]), float(row[1])), float(row[1])
+    if best is None or not top > 0 or not top > minGain * abs(score0):
+        return None
+    return best
+
+
+def apply_move(ids, rev, move):
+    """(ids, rev) as lists after ``move`` (choose_move): a relocation takes scaffold j out and puts it back at gap g of
+    the arrangement without it in the given orientation; an inversion reverses the scaffolds i ... j and flips each."""
+    ids, rev = [int(v) for v in ids], [int(v) for v in rev]
+    if move[0] == "relocate":
+        _kind, j, gap, r, _delta = move
+        sid = ids.pop(j)
+        rev.pop(j)
+        ids.insert(gap, sid)
+        rev.insert(gap, int(r))
+    elif move[0] == "invert":
+        _kind, i, j, _delta = move
+        ids[i:j + 1] = ids[i:j + 1][::-1]
+        rev[i:j + 1] = [1 - r for r in rev[i:j + 1][::-1]]
+    else:
+        raise ValueError("unknown move " + repr(move[0]))
+    return ids, rev
+
+
+def _moved_group(group, move):
+    """A chromosome's Scaffold list after ``move``: copies, flipped where the move flips them."""
+    order, flip = apply_move(range(len(group)), [0] * len(group), move)
+    if move[0] == "relocate":                                 # apply_move sets the orientation; a flip is a change of it
+        flip = [int(k == move[1] and (group[k].orientation == "-") != bool(move[3])) for k in order]
+    out = []
+    for k, f in zip(order, flip):
+        s = group[k].copy()
+        if f:
+            s.flipOrientation()
+        out.append(s)
+    return out
+
+
+def refineOrdering(matrix: GenomeMatrix, orderedChromosomes, binList, chromList, moves=REFINE_MOVES, maxSpan=0, minGain=0.0,
+                   maxRounds=100):
+    """Hill climbing from a finished ordering.  One round, for every chromosome that has not converged:
+    the placement table (placementSupport) and the inversion table (inversionSupport), one multi call each for all of
+    them; each scaffold's decided best relocation and each left end's decided best inversion with their literal
+    deltas; the move of the round (choose_move) applied, or the chromosome has converged.  One move per chromosome per
+    round, because the tables are stale after a move; every accepted move strictly raises a literal score, so the loop
+    ends, and ``maxRounds`` caps it.  ``moves``: the families tried.  Returns (the refined ordering, the log: one dict
+    per applied move - round, chromosome, kind, scaffold, to, from / to as text, before, after -, the summary: one
+    dict per chromosome - before, after, moves, rounds, converged)."""
+    moves = tuple(moves)
+    if not moves or any(m not in REFINE_MOVES for m in moves):
+        raise ValueError("moves must be taken from " + ",".join(REFINE_MOVES))
+    current = [list(group) for group in orderedChromosomes]
+    summary = [{"before": None, "after": None, "moves": 0, "rounds": 0, "converged": False} for _g in current]
+    log = []
+    for rnd in range(1, int(maxRounds) + 1):
+        todo = [k for k, s in enumerate(summary) if not s["converged"]]
+        if not todo:
+            break
+        sub = [current[k] for k in todo]
+        sub_list = None if chromList is None else [chromList[k] for k in todo]
+        rel = placementSupport(matrix, sub, binList, sub_list) if "relocate" in moves else None
+        inv = inversionSupport(matrix, sub, binList, sub_list, maxSpan=maxSpan) if "invert" in moves else None
+        for at, k in enumerate(todo):
+            res = rel[at] if rel is not None else inv[at]
+            score0 = res["score0"]
+            rel_rows = inv_rows = None
+            if rel is not None:
+                rel_rows = [None if r["best_delta"] is None else (r["best_gap"], r["best_orientation"] == "-", r["best_delta"])
+                            for r in rel[at]["rows"]]
+            if inv is not None:
+                inv_rows = [None if r["best_delta"] is None else (r["best_j"], r["best_delta"]) for r in inv[at]["rows"]]
+            stat = summary[k]
+            if stat["before"] is None:
+                stat["before"] = score0
+            stat["after"], stat["rounds"] = score0, rnd
+            move = choose_move(rel_rows, inv_rows, score0, minGain)
+            if move is None:
+                stat["converged"] = True
+                continue
+            group = current[k]
+            if move[0] == "relocate":
+                what, src, dst = group[move[1]].name, "%d%s" % (move[1], group[move[1]].orientation), \
+                    "%d%s" % (move[2], "-" if move[3] else "+")
+            else:
+                what, src, dst = group[move[1]].name + ".." + group[move[2]].name, "%d..%d" % (move[1], move[2]), "reversed"
+            current[k] = _moved_group(group, move)
+            stat["moves"] += 1
+            stat["after"] = score0 + move[-1]
+            log.append({"round": rnd, "chromosome": k + 1, "kind": move[0], "scaffold": what, "from": src, "to": dst,
+                        "before": score0, "after": score0 + move[-1], "move": move})
+    return current, log, summary
+
+
+def writeRefinement(refined, log, summary, outDir, chromosomeOrderFile, plotOrderFile):
+    """The refined ordering through the existing writers as ``outDir``/basename of the two files, ``refine.log`` (one
+    line per applied move: round, chromosome, kind, scaffold(s), from -> to, score before, score after) and
+    ``refine_summary.tsv`` (per chromosome: score before and after, moves, rounds, converged)."""
+    os.makedirs(outDir, exist_ok=True)
+    order_out = os.path.join(outDir, os.path.basename(chromosomeOrderFile))
+    writeScaffoldOrderingsToFile(refined, order_out)
+    writeBinIDsOrderingToFile([s for group in refined for s in group], os.path.join(outDir, os.path.basename(plotOrderFile)))
+    with open(os.path.join(outDir, "refine.log"), "w") as fh:
+        for e in log:
+            fh.write("\t".join([str(e["round"]), str(e["chromosome"]), e["kind"], e["scaffold"], e["from"] + " -> " + e["to"],
+                                repr(e["before"]), repr(e["after"])]) + "\n")
+    with open(os.path.join(outDir, "refine_summary.tsv"), "w") as fh:
+        fh.write("chromosome\tscore_before\tscore_after\tmoves\trounds\tconverged\n")
+        for k, s in enumerate(summary):
+            fh.write("\t".join([str(k + 1), repr(s["before"]), repr(s["after"]), str(s["moves"]), str(s["rounds"]),
+                                "yes" if s["converged"] else "no"]) + "\n")
+    print("Refinement moves applied " + str(len(log)))
+    return order_out
+
+
 def getChromosomeOutlineCoords(orderedChromosomes):
     """OG:662-674."""
     coords, index = [], 0
@@ -1546,12 +1830,15 @@ def _read_groups_quietly(chromosomeGroupFile):
 def runPipeline(hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroupFile, chromosomeOrderFile,
                 savePlotsDirectory, chromosomePlotSuffix, fullGenomePlot, fullGenomePlotTitle, plotOrderFile,
                 nScaffolds, scanScaffolds, resolution, device=0, resident=None, placementSupportFile=None,
-                breakSupportFile=None, brokenChromosomeGroupFile=None):
+                breakSupportFile=None, brokenChromosomeGroupFile=None, inversionSupportFile=None,
+                refinedChromosomeOrderFile=None):
     """OG:679-712, same positional arguments (``device``, ``resident`` and the ``...File`` keywords are optional extras).
 
     ``placementSupportFile``: also write the placement-support report of the final ordering there (placementSupport).
     ``breakSupportFile`` / ``brokenChromosomeGroupFile``: also write the break-support report and the group file with
     the breakable scaffolds split (breakSupport).
+    ``inversionSupportFile``: also write the inversion-support report there (inversionSupport).
+    ``refinedChromosomeOrderFile``: also write the ordering after refineOrdering's hill climb there, as an order file.
 
     ``resident=(DeviceMatrix, bins of its rows)`` from Part 1's ``runPipeline(..., keep_resident=True)``: the contact
     matrix already in HBM is used instead of parsing the HiC-Pro text again.  The reference re-loads the matrix
@@ -1576,6 +1863,13 @@ def runPipeline(hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroup
         if breakSupportFile or brokenChromosomeGroupFile:
             breakSupportToFiles(adjMat, orderedChromosomes, binList, chromosomeGroupFile, breakSupportFile,
                                 brokenChromosomeGroupFile)
+        if inversionSupportFile:
+            writeInversionSupportToFile(inversionSupport(adjMat, orderedChromosomes, binList,
+                                                         _read_groups_quietly(chromosomeGroupFile)), inversionSupportFile)
+        if refinedChromosomeOrderFile:
+            refined, _log, _summary = refineOrdering(adjMat, orderedChromosomes, binList,
+                                                     _read_groups_quietly(chromosomeGroupFile))
+            writeScaffoldOrderingsToFile(refined, refinedChromosomeOrderFile)
         if plotModule.plots_enabled(fullGenomePlot):                      # OG:700-707
             where = adjMat.bin_index(binList)
             rows = [where[b] for group in orderedChromosomes for s in group for b in s.binList]

@@ -404,6 +404,36 @@ int hicmi_p2_breaks_multi(int64_t n_jobs, hicmi_ctx *const *ctxs, const int32_t 
                           const int64_t *S, const double *totals, int64_t min_piece, double *const *scores_out,
                           int32_t *const *best_out);
 
+/* Inversion support of a finished ordering: every run of consecutive scaffolds read backwards.  Chromosome, arrangement
+ * A = (ids, rev) of S scaffolds, arr_pos[k] = first position of scaffold k in A and the ONE total are as for
+ * hicmi_p2_support.  Candidate (i, j), 0 <= i <= j < S, is A with its positions [a, b) = [arr_pos[i], arr_pos[j + 1])
+ * read backwards: scaffolds i ... j in reverse order, each flipped, every other position unchanged.  Pairs inside the
+ * segment and pairs outside it keep their distance, so with c = a + b - 1 and h(d) = H[n - 1] - H[d - 1]
+ *     total * (score(i, j) - score0) = sum_{t in [a, b)} [ sum_{o < a}  M[t][o] (h(c - t - o) - h(t - o))
+ *                                                         + sum_{o >= b} M[t][o] (h(o + t - c) - h(o - t)) ],
+ * t and o positions of A and M read through A's bin order.
+ * scores_out[i * S + j] = objective of candidate (i, j) under `total`, closed form, fp64: S x S doubles.  j < i holds
+ * 0.0; j = i is scaffold i flipped in place (hicmi_p2_support's scores_out[(i * S + i) * 2 + 1 - rev[i]]); j > i is the
+ * segment reversal.  max_span > 0: segments of more than max_span scaffolds are not computed and hold 0.0.
+ * A candidate competes if j > i, it is not (0, S - 1) - the chromosome read backwards, the same objective - and, when
+ * max_span > 0, j - i + 1 <= max_span.  best_out[2 i] = j of the first maximum, j ascending, of the closed-form scores
+ * over the competing candidates with left end i, or -1 when none competes (the last scaffold; S = 2);
+ * best_out[2 i + 1] = how many of them lie within 1e-9 (relative) of that maximum.  1: decided.  More: the caller
+ * re-scores them literally (hicmi_p2_score_exact) and the first strict maximum of those values wins.
+ * A chromosome of fewer than 2 bins, or with total <= 0, gets 0.0 everywhere and no candidate.
+ * The call reads sum of len * (n - len) matrix elements over its computed candidates, len = b - a; the host adds that
+ * up first and a call above 1e13 returns HICMI_EUNSUPPORTED naming max_span, as does one of more than 4096 scaffolds or
+ * 40960 bins in a chromosome or 2^31 - 1 workgroups (one per computed candidate).  Scratch: 64 doubles per chromosome.
+ * hicmi_p2_inversions_multi: n_jobs chromosomes (one context each, all on one device) in one pair of launches - the
+ * grid runs over (chromosome, left end) records - and one download.  The sums are added in a fixed order: two calls
+ * give the same bits.  Replaces the contexts' current arrangement by A.  Must not run concurrently with other calls
+ * on the contexts. */
+int hicmi_p2_inversions(hicmi_ctx *ctx, const int32_t *ids, const uint8_t *rev, int64_t S, double total, int64_t max_span,
+                        double *scores_out, int32_t *best_out);
+int hicmi_p2_inversions_multi(int64_t n_jobs, hicmi_ctx *const *ctxs, const int32_t *const *ids, const uint8_t *const *rev,
+                              const int64_t *S, const double *totals, int64_t max_span, double *const *scores_out,
+                              int32_t *const *best_out);
+
 /* ---- Part 3 input scan (host code, no GPU) -----------------------------------------------------
  * readValidPairFile (orientSmallScaffolds.py:159-177): of a HiC-Pro allValidPairs file
  * (read, scaffold1, pos1, strand1, scaffold2, pos2, ...) keep the lines whose (scaffold1, scaffold2) is one of the
