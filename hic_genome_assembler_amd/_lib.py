@@ -42,6 +42,7 @@ SIGNATURES = {
     "hicmi_compact": (ctypes.c_int, [_vp, _vp, c_i64]),
     "hicmi_rebin": (ctypes.c_int, [_vp, _vp, c_i64]),
     "hicmi_group_sums": (ctypes.c_int, [_vp, _vp, _vp, c_i64, c_i64, _vp, _vp]),
+    "hicmi_junction_sums": (ctypes.c_int, [_vp, _vp, c_i64, _vp, c_i64, _vp]),
     "hicmi_get_contact_rows": (ctypes.c_int, [_vp, c_i64, c_i64, _vp]),
     "hicmi_ice_mask_rows": (ctypes.c_int, [_vp, _vp, c_i64]),
     "hicmi_ice_balance": (ctypes.c_int, [_vp, _vp, c_i64, c_dbl, _vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_dbl)]),
@@ -348,6 +349,17 @@ class Context:
         _check(self._lib.hicmi_group_sums(self._h, _ptr(g), _ptr(s), int(n_groups), int(n_scaffolds), _ptr(bins),
                                           _ptr(scaffolds)))
         return bins, scaffolds
+
+    def junction_sums(self, bins, rec):
+        """Junction sums (hicmi_junction_sums): for every row (startA, stepA, lenA, startB, stepB, lenB)
+        of ``rec``, the sum of M[A_a][B_b] / (a + b + 1) over its two sides, views of ``bins`` (matrix indices)."""
+        b = np.ascontiguousarray(bins, dtype=np.int32)
+        r = np.ascontiguousarray(rec, dtype=np.int64)
+        if b.ndim != 1 or r.ndim != 2 or r.shape[1] != 6:
+            raise ValueError("bins must be a vector and rec n_rec x 6")
+        sums = np.empty(len(r), np.float64)
+        _check(self._lib.hicmi_junction_sums(self._h, _ptr(b), len(b), _ptr(r), len(r), _ptr(sums)))
+        return sums
 
     # ---- Part 0: ICE balancing (DESIGN.md 9h)
     def ice_mask_rows(self, mask):

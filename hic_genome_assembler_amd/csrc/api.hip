@@ -138,6 +138,9 @@ struct hicmi_ctx {
     // group support (k_group_support.hip): the member lists of a call, and its partials + the two tables
     int32_t* d_gs_lists = nullptr; int64_t gs_lists_cap = 0;
     double* d_gs_sums = nullptr; int64_t gs_sums_cap = 0;
+    // junction support (k_junctions.hip): [records][bin order] of a call, and its [weights][partials][sums]
+    unsigned char* d_jn_lists = nullptr; int64_t jn_lists_cap = 0;
+    double* d_jn_sums = nullptr; int64_t jn_sums_cap = 0;
     // ICE balancing (k_ice.hip): [y][u][bias][bias_prev][s][d][ones] of n each, [mean0, c], (delta, c) per iteration; the mask
     double* d_ice = nullptr; int64_t ice_cap = 0;
     uint8_t* d_ice_mask = nullptr; int64_t ice_mask_cap = 0;
@@ -397,6 +400,7 @@ int hicmi_destroy(hicmi_ctx* c)
     free_dev(c->d_arr_packed2); free_dev(c->d_pos2sel2); free_dev(c->d_ins_T); free_dev(c->d_ins_partial); free_dev(c->d_brk_recs); free_dev(c->d_inv_recs);
     free_dev(c->d_ins_blob); free_dev(c->d_ins_steps); free_dev(c->d_sup_recs);
     free_dev(c->d_gs_lists); free_dev(c->d_gs_sums);
+    free_dev(c->d_jn_lists); free_dev(c->d_jn_sums);
     free_dev(c->d_ice); free_dev(c->d_ice_mask);
     free_dev(c->d_plot_order); free_dev(c->d_plot_work); free_dev(c->d_plot_img);
     for (auto& sl : c->hslot) free_dev(sl.d_x);
@@ -669,6 +673,64 @@ int hicmi_group_sums(hicmi_ctx* c, const int32_t* grp, const int32_t* scaf, int6
     HIPCHK(hipGetLastError());
     if (bin_sums_out) { rc = download(c, bin_sums_out, c->d_gs_sums + o_bin, sizeof(double) * (size_t)(n * G)); if (rc) return rc; }
     return download(c, scaffold_sums_out, c->d_gs_sums + o_sc, sizeof(double) * (size_t)(S * G));
+}
+
+// Junction support: extends the chromosome loop of orderGenome (OG:608-612), which orders every group on
+// its own and never looks from one group at another.  The host checks every record and cuts the rows of A into slabs;
+// the kernels of k_junctions.hip read the sides as views of `bins`.
+int hicmi_junction_sums(hicmi_ctx* c, const int32_t* bins, int64_t n_listed, const int64_t* rec, int64_t n_rec,
+                        double* sums_out)
+{
+    if (!c) return fail(HICMI_EINVAL, "NULL context");
+    if (!c->dC) return fail(HICMI_EINVAL, "no contact matrix set");
+    if (n_rec < 0 || n_listed < 0) return fail(HICMI_EINVAL, "negative count");
+    if (n_rec == 0) return HICMI_OK;
+    if (!bins || !rec || !sums_out) return fail(HICMI_EINVAL, "NULL argument");
+    if (n_listed < 1 || n_listed > INT_MAX) return fail(HICMI_EINVAL, "n_listed = %lld outside 1 .. 2^31 - 1", (long long)n_listed);
+    if (n_rec > INT_MAX) return fail(HICMI_EUNSUPPORTED, "n_rec = %lld above 2^31 - 1", (long long)n_rec);
+    const int64_t n = c->n;
+    for (int64_t i = 0; i < n_listed; i++)
+        if (bins[i] < 0 || bins[i] >= n)
+            return fail(HICMI_EINVAL, "bins[%lld] = %d outside 0 .. %lld", (long long)i, bins[i], (long long)(n - 1));
+    std::vector<JnRec> recs((size_t)n_rec);
+    int64_t n_wg = 0, max_d = 0;
+    for (int64_t r = 0; r < n_rec; r++) {
+        const int64_t* q = rec + 6 * r;
+        for (int side = 0; side < 2; side++) {
+            const int64_t start = q[3 * side], step = q[3 * side + 1], len = q[3 * side + 2];
+            if (len < 1) return fail(HICMI_EINVAL, "record %lld: a side of %lld bins", (long long)r, (long long)len);
+            if (step != 1 && step != -1) return fail(HICMI_EINVAL, "record %lld: step %lld is not +1 or -1", (long long)r, (long long)step);
+            if (len > n_listed || start < 0 || start >= n_listed || start + (len - 1) * step < 0 || start + (len - 1) * step >= n_listed)
+                return fail(HICMI_EINVAL, "record %lld: a side runs outside the %lld listed bins", (long long)r, (long long)n_listed);
+        }
+        JnRec& d = recs[(size_t)r];
+        d.wg0 = n_wg;
+        d.startA = (int32_t)q[0]; d.stepA = (int32_t)q[1]; d.lenA = (int32_t)q[2];
+        d.startB = (int32_t)q[3]; d.stepB = (int32_t)q[4]; d.lenB = (int32_t)q[5];
+        d.n_slabs = (d.lenA + JN_SLAB_ROWS - 1) / JN_SLAB_ROWS; d.pad = 0;
+        n_wg += d.n_slabs;
+        max_d = std::max<int64_t>(max_d, q[2] + q[5] - 1);
+    }
+    const char* env = getenv("HICMI_JUNCTIONS_PLAIN");
+    const bool plain = env && !strcmp(env, "1");
+    if (!plain && n_wg > INT_MAX) return fail(HICMI_EUNSUPPORTED, "%lld workgroups: at most 2^31 - 1", (long long)n_wg);
+    std::vector<double> w((size_t)max_d + 1);
+    w[0] = 0.0;
+    for (int64_t d = 1; d <= max_d; d++) w[(size_t)d] = 1.0 / (double)d;       // IEEE division: NumPy's 1.0 / d
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t rec_bytes = (int64_t)sizeof(JnRec) * n_rec, list_bytes = rec_bytes + (int64_t)sizeof(int32_t) * n_listed;
+    const int64_t o_part = max_d + 1, o_sums = o_part + (plain ? 0 : n_wg), n_dbl = o_sums + n_rec;
+    int rc = ensure(c->d_jn_lists, c->jn_lists_cap, list_bytes);
+    if (!rc) rc = ensure(c->d_jn_sums, c->jn_sums_cap, n_dbl);
+    if (!rc) rc = upload(c, c->d_jn_lists, recs.data(), (size_t)rec_bytes);
+    if (!rc) rc = upload(c, c->d_jn_lists + rec_bytes, bins, sizeof(int32_t) * (size_t)n_listed);
+    if (!rc) rc = upload(c, c->d_jn_sums, w.data(), sizeof(double) * w.size());
+    if (rc) return rc;
+    launch_junction_sums(c->dC, c->ldc, reinterpret_cast<const int32_t*>(c->d_jn_lists + rec_bytes),
+                         reinterpret_cast<const JnRec*>(c->d_jn_lists), (int)n_rec, n_wg, c->d_jn_sums,
+                         c->d_jn_sums + o_part, c->d_jn_sums + o_sums, plain, c->stream);
+    HIPCHK(hipGetLastError());
+    return download(c, sums_out, c->d_jn_sums + o_sums, sizeof(double) * (size_t)n_rec);
 }
 
 // ---- ICE balancing: HiC-Pro's `ice` step on the resident raw map -------------------------------------

@@ -468,6 +468,19 @@ void launch_group_sums(const double* C, int64_t ld, int n, int G, int S, const i
                        int n_chunks, const int32_t* group_chunk0, const int32_t* scaf, const int32_t* sbins,
                        const int32_t* soff, double* partial, double* binsum, double* scafsum, bool plain, hipStream_t s);
 
+// k_junctions.hip: junction support (hicmi_junction_sums).  bins: the bin order of every chromosome, one
+// after the other (matrix indices); a record's two sides are views of it; w[d] = 1.0 / d for d = 1 .. the largest
+// lenA + lenB - 1 of the call (w[0] unused); partial: one double per workgroup; sums: one per record.
+static constexpr int JN_SLAB_ROWS = 64;       // rows of A per workgroup: part of the summation order
+struct JnRec {
+    int64_t wg0;                              // first workgroup of this record in k_junctions_partial
+    int32_t startA, stepA, lenA;              // side entry k = bins[start + k * step], step = +1 or -1
+    int32_t startB, stepB, lenB;
+    int32_t n_slabs, pad;                     // ceil(lenA / JN_SLAB_ROWS)
+};
+void launch_junction_sums(const double* C, int64_t ld, const int32_t* bins, const JnRec* recs, int n_rec, int64_t n_wg,
+                          const double* w, double* partial, double* sums, bool plain, hipStream_t s);
+
 // k_ice.hip: ICE balancing of a raw map (hicmi_ice_balance).  st: [mean0, last c]; rec: (delta, c) per
 // iteration; u == nullptr in the vector steps: the in-place path.
 void launch_ice_fill(double* v, int n, double value, hipStream_t s);

@@ -1811,6 +1811,385 @@ def writeRefinement(refined, log, summary, outDir, chromosomeOrderFile, plotOrde
     return order_out
 
 
+# ---- junction support of a finished ordering --------------------------------------------
+JUNCTION_WINDOW = 16       # bins of a side (0: the whole block)
+JUNCTION_MIN_REL = 0.25    # J / ref at or above which a junction holds
+
+
+def junction_records(lengths, boundaries, window=JUNCTION_WINDOW):
+    """The records of a junction-support call (include/hicmi.h, hicmi_junction_sums) for chromosomes of ``lengths[c]``
+    bins laid one after the other, chromosome c at offset sum(lengths[:c]).  ``boundaries[c]``: the positions inside
+    chromosome c at which a scaffold other than its first begins, strictly ascending in 1 .. lengths[c] - 1.  A side is
+    cut to its first ``window`` bins (0: the whole block) and never leaves its chromosome.  Returns a dict: 'rec' (int64,
+    n_rec x 6: startA, stepA, lenA, startB, stepB, lenB), first the internal junctions - 'internal': (chromosome,
+    boundary index) each, A the bins to the left read leftwards, B those to the right read rightwards - then the end
+    pairs - 'pairs': (e, f) with e < f on different chromosomes, end 2 c the head of chromosome c (read from its first bin
+    inwards) and 2 c + 1 its tail (from its last bin inwards) - and 'G', 'lengths', 'window'."""
+    window = int(window)
+    if window < 0:
+        raise ValueError("window must be 0 (the whole block) or a positive number of bins")
+    lengths = [int(v) for v in lengths]
+    if any(v < 1 for v in lengths):
+        raise ValueError("every chromosome needs at least one bin")
+    cut = (lambda v: min(v, window)) if window else (lambda v: v)
+    rec, internal, off = [], [], 0
+    offsets = []
+    for c, (n, bounds) in enumerate(zip(lengths, boundaries)):
+        offsets.append(off)
+        last = 0
+        for k, p in enumerate(bounds):
+            p = int(p)
+            if not last < p < n:
+                raise ValueError("chromosome %d: scaffold boundaries must ascend strictly inside 1 .. %d" % (c + 1, n - 1))
+            rec.append((off + p - 1, -1, cut(p), off + p, 1, cut(n - p)))
+            internal.append((c, k))
+            last = p
+        off += n
+    G = len(lengths)
+    side = []
+    for c in range(G):
+        side.append((offsets[c], 1, cut(lengths[c])))                       # head
+        side.append((offsets[c] + lengths[c] - 1, -1, cut(lengths[c])))     # tail
+    pairs = [(e, f) for e in range(2 * G) for f in range(e + 1, 2 * G) if e // 2 != f // 2]
+    rec.extend(side[e] + side[f] for e, f in pairs)
+    return {"rec": np.array(rec, dtype=np.int64).reshape(len(rec), 6), "internal": internal, "pairs": pairs, "G": G,
+            "lengths": lengths, "window": window}
+
+
+def junction_norm(lenA, lenB):
+    """sum over d = 1 .. lenA + lenB - 1 of cnt(d) * (1.0 / d), d ascending: cnt(d) pairs (a, b) have a + b + 1 = d."""
+    lenA, lenB = int(lenA), int(lenB)
+    d = np.arange(1, lenA + lenB, dtype=np.float64)
+    cnt = np.minimum(np.minimum(d, lenA + lenB - d), float(min(lenA, lenB)))
+    return float(np.cumsum(cnt * (1.0 / d))[-1])              # cumsum adds left to right: the loop's bits
+
+
+def junction_summary(sums, records, minRel=JUNCTION_MIN_REL):
+    """Every decision of the junction report from the downloaded ``sums`` of junction_records' ``records`` (DESIGN.md
+    9k).  J = sum / junction_norm; 'ref': numpy.median of J over the internal junctions, None without one or when it is
+    0.  'internal': per internal junction chromosome, boundary, bins_left, bins_right, J, rel, verdict (held: rel >=
+    minRel, else weak).  'table': the 2G x 2G J of the ends, exactly symmetric, NaN inside one chromosome.  'ends': per
+    end best (the first maximum of its row), J, rel, mutual (each is the other's best), second (the best end of a
+    chromosome other than best's; None when G = 2), second_J, verdict (joinable: mutual and rel >= minRel, else free).
+    rel and the verdicts are None without ref, an end's every field when G = 1.  'joinable': (e, f, J) with e < f;
+    'weak': (chromosome, boundary)."""
+    rec, G = records["rec"], records["G"]
+    norms = {}
+
+    def J_of(r):
+        key = (int(rec[r][2]), int(rec[r][5]))
+        if key not in norms:
+            norms[key] = junction_norm(*key)
+        return float(sums[r]) / norms[key]
+    n_int = len(records["internal"])
+    J_int = [J_of(r) for r in range(n_int)]
+    ref = float(np.median(J_int)) if n_int else None
+    if ref is not None and not ref > 0:
+        ref = None
+    internal, weak = [], []
+    for r, (c, k) in enumerate(records["internal"]):
+        rel = J_int[r] / ref if ref is not None else None
+        verdict = None if rel is None else ("held" if rel >= minRel else "weak")
+        if verdict == "weak":
+            weak.append((c, k))
+        internal.append({"chromosome": c, "boundary": k, "bins_left": int(rec[r][2]), "bins_right": int(rec[r][5]),
+                         "J": J_int[r], "rel": rel, "verdict": verdict})
+    table = np.full((2 * G, 2 * G), np.nan)
+    for r, (e, f) in enumerate(records["pairs"], start=n_int):
+        table[e, f] = table[f, e] = J_of(r)
+
+    def first_max(e, skip):
+        at, top = None, -math.inf
+        for f in range(2 * G):
+            if f // 2 not in skip and table[e, f] > top:
+                at, top = f, float(table[e, f])
+        return at
+    best = [first_max(e, (e // 2,)) for e in range(2 * G)] if G > 1 else [None] * (2 * G)
+    window = records["window"]
+    ends, joinable = [], []
+    for e in range(2 * G):
+        f, bins = best[e], min(records["lengths"][e // 2], window) if window else records["lengths"][e // 2]
+        if f is None:
+            ends.append({"bins": bins, "best": None, "J": None, "rel": None, "mutual": None, "second": None,
+                         "second_J": None, "verdict": None})
+            continue
+        J = float(table[e, f])
+        rel = J / ref if ref is not None else None
+        mutual = best[f] == e
+        second = first_max(e, (e // 2, f // 2)) if G > 2 else None
+        verdict = None if rel is None else ("joinable" if mutual and rel >= minRel else "free")
+        if verdict == "joinable" and e < f:
+            joinable.append((e, f, J))
+        ends.append({"bins": bins, "best": f, "J": J, "rel": rel, "mutual": mutual, "second": second,
+                     "second_J": None if second is None else float(table[e, second]), "verdict": verdict})
+    return {"ref": ref, "window": window, "minRel": float(minRel), "internal": internal, "table": table,
+            "ends": ends, "joinable": joinable, "weak": weak}
+
+
+def _flipped(item):
+    return (item[0], "-" if item[1] == "+" else "+")
+
+
+def join_chromosomes(ordered, joins):
+    """``ordered``: per chromosome its (scaffold, '+'/'-') pairs in order; ``joins``: (e, f, J) joins of chromosome ends
+    (end 2 c: the head of chromosome c, 2 c + 1: its tail), every end in at most one of them, so the chromosomes form
+    paths and cycles.  A cycle drops its smallest-J join, the first listed on a tie.  A joined chromosome is read in the
+    direction that keeps its lowest-numbered member as written; a member entered through its tail is reversed: scaffold
+    order reversed, every orientation flipped.  It stands at the position of its lowest-numbered member and all other
+    chromosomes keep their order.  Returns (the new chromosomes, per new chromosome its members as (old chromosome,
+    reversed), the joins applied, the joins dropped)."""
+    G = len(ordered)
+    joins = [(int(e), int(f), float(J)) for e, f, J in joins]
+    partner = {}
+    for at, (e, f, _J) in enumerate(joins):
+        if e // 2 == f // 2 or e in partner or f in partner or not (0 <= e < 2 * G and 0 <= f < 2 * G):
+            raise ValueError("joins must pair each end at most once, across chromosomes")
+        partner[e], partner[f] = (f, at), (e, at)
+    dropped, seen = set(), set()
+    for c in range(G):                                        # cycles: walk from c's tail until an open end or c again
+        if c in seen:
+            continue
+        cur, used, path = 2 * c + 1, [], [c]
+        while cur in partner:
+            nxt, at = partner[cur]
+            used.append(at)
+            if nxt // 2 == c:                                 # back at the start: a cycle
+                worst = min(used, key=lambda a: (joins[a][2], a))
+                dropped.add(worst)
+                break
+            path.append(nxt // 2)
+            cur = nxt ^ 1
+        seen.update(path)
+    live = {e: f for e, (f, at) in partner.items() if at not in dropped}
+    out, members, placed = [], [], set()
+    for c in range(G):
+        if c in placed:
+            continue
+        cur, end = c, 2 * c                                   # c is the lowest-numbered member of its path: leftwards
+                                                              # from its head to the start of the path
+        while end in live:
+            end = live[end] ^ 1
+            cur = end // 2
+        chrom, mem = [], []
+        while True:                                           # `end`: the end the member is entered through
+            rev = bool(end & 1)
+            group = ordered[cur]
+            chrom.extend([_flipped(s) for s in group[::-1]] if rev else list(group))
+            mem.append((cur, rev))
+            if end ^ 1 not in live:
+                break
+            end = live[end ^ 1]
+            cur = end // 2
+        placed.update(k for k, _rev in mem)
+        out.append(chrom)
+        members.append(mem)
+    applied = [j for at, j in enumerate(joins) if at not in dropped]
+    return out, members, applied, [joins[at] for at in sorted(dropped)]
+
+
+def cut_chromosomes(ordered, weak):
+    """``ordered`` as for join_chromosomes with every chromosome split at its ``weak`` junctions, (chromosome, boundary k:
+    between its scaffolds k and k + 1); the pieces stand where the chromosome stood.  Returns (the new chromosomes, per
+    new chromosome (old chromosome, first scaffold, one past its last))."""
+    cuts = {}
+    for c, k in weak:
+        if not (0 <= c < len(ordered) and 0 <= k < len(ordered[c]) - 1):
+            raise ValueError("no junction %d in chromosome %d" % (k, c + 1))
+        cuts.setdefault(int(c), set()).add(int(k) + 1)
+    out, members = [], []
+    for c, group in enumerate(ordered):
+        edges = [0] + sorted(cuts.get(c, ())) + [len(group)]
+        for a, b in zip(edges[:-1], edges[1:]):
+            out.append(list(group[a:b]))
+            members.append((c, a, b))
+    return out, members
+
+
+def junctionSupport(matrix: GenomeMatrix, orderedChromosomes, binList, chromList=None, window=JUNCTION_WINDOW,
+                    minRel=JUNCTION_MIN_REL):
+    """Which chromosome ends belong together and which scaffold junctions do not hold (include/hicmi.h,
+    hicmi_junction_sums): the mean contact, weighted 1 / distance, across every scaffold boundary of every ordered
+    chromosome and between every two ends of different chromosomes, on the genome context's matrix as it stands, in ONE
+    native call.  Returns junction_summary's dict with 'chromosomes' added: per chromosome its names, orientations and
+    scaffold bin counts.  ``chromList`` is accepted for the signature the reports share; the bins come from the ordered
+    scaffolds themselves."""
+    where = matrix.bin_index(binList)
+    bins, lengths, boundaries = [], [], []
+    for group in orderedChromosomes:
+        at, bounds = 0, []
+        for s in group:
+            if at:
+                bounds.append(at)
+            at += len(s.binList)
+            bins.extend(where[b] for b in s.binList)
+        lengths.append(at)
+        boundaries.append(bounds)
+    records = junction_records(lengths, boundaries, window)
+    sums = matrix.ctx.junction_sums(np.asarray(bins, dtype=np.int32), records["rec"]) if len(records["rec"]) \
+        else np.zeros(0)
+    res = junction_summary(sums, records, minRel)
+    res["sums"], res["rec"] = np.asarray(sums), records["rec"]
+    res["chromosomes"] = [{"names": [s.name for s in group], "orientations": [s.orientation for s in group],
+                           "bins": [len(s.binList) for s in group]} for group in orderedChromosomes]
+    return res
+
+
+_END_NAME = ("head", "tail")
+
+
+def junctionSupportText(results):
+    """The report: ``### reference ref window W minRel r``; per chromosome ``### Chromosome grouping i ###`` and one
+    tab-separated line per internal junction: left scaffold, right scaffold, bins_left, bins_right, J, rel, verdict; then
+    ``### Chromosome ends ###`` and one line per end: chromosome, head/tail, the terminal scaffold, bins,
+    best_chromosome, best_end, J, rel, mutual, second_chromosome, second_J, verdict.  Floats are written with repr,
+    what does not exist as NA."""
+    text = ["### reference %s window %d minRel %s\n" % (_support_text(results["ref"]), results["window"],
+                                                        repr(results["minRel"]))]
+    rows = iter(results["internal"])
+    for k, chrom in enumerate(results["chromosomes"]):
+        text.append("### Chromosome grouping " + str(k + 1) + " ###\n")
+        for left, right in zip(chrom["names"][:-1], chrom["names"][1:]):
+            row = next(rows)
+            text.append("\t".join([left, right, str(row["bins_left"]), str(row["bins_right"]), repr(row["J"]),
+                                   _support_text(row["rel"]), row["verdict"] or "NA"]) + "\n")
+    text.append("### Chromosome ends ###\n")
+    for e, row in enumerate(results["ends"]):
+        chrom = results["chromosomes"][e // 2]
+        f, g = row["best"], row["second"]
+        text.append("\t".join([str(e // 2 + 1), _END_NAME[e & 1], chrom["names"][-1 if e & 1 else 0], str(row["bins"]),
+                               "NA" if f is None else str(f // 2 + 1), "NA" if f is None else _END_NAME[f & 1],
+                               _support_text(row["J"]), _support_text(row["rel"]),
+                               "NA" if row["mutual"] is None else ("yes" if row["mutual"] else "no"),
+                               "NA" if g is None else str(g // 2 + 1), _support_text(row["second_J"]),
+                               row["verdict"] or "NA"]) + "\n")
+    return "".join(text)
+
+
+def writeJunctionSupportToFile(results, outFile, fullDir=None):
+    """junctionSupportText to ``outFile``; ``fullDir``: also the 2G x 2G table of J between the ends as
+    ``junctions.ends.tsv`` (rows and columns 1.head, 1.tail, 2.head, ...; NA inside one chromosome)."""
+    with open(outFile, "w") as fh:
+        fh.write(junctionSupportText(results))
+    if fullDir:
+        os.makedirs(fullDir, exist_ok=True)
+        labels = ["%d.%s" % (e // 2 + 1, _END_NAME[e & 1]) for e in range(len(results["ends"]))]
+        with open(os.path.join(fullDir, "junctions.ends.tsv"), "w") as fh:
+            fh.write("\t".join(["end"] + labels) + "\n")
+            for label, line in zip(labels, results["table"]):
+                fh.write("\t".join([label] + ["NA" if v != v else repr(float(v)) for v in line]) + "\n")
+    print("Junction support written for junctions " + str(len(results["internal"])) + " and chromosome ends "
+          + str(len(results["ends"])))
+
+
+def _group_file_lines(chromosomeGroupFile):
+    """Per group of ``chromosomeGroupFile`` its lines verbatim without the header (the first line is group 1's header:
+    readChromsFromFile), each ending in a newline."""
+    with open(chromosomeGroupFile) as fh:
+        lines = fh.read().splitlines(keepends=True)
+    groups = []
+    for k, line in enumerate(lines):
+        if k == 0 or line[0] == "#":
+            groups.append([])
+        else:
+            groups[-1].append(line if line.endswith("\n") else line + "\n")
+    return groups
+
+
+def _write_regrouped(new_groups, new_lines, outDir, chromosomeGroupFile, chromosomeOrderFile, plotOrderFile):
+    """The three files of a regrouped ordering as ``outDir``/basename of the input files: the group file with one
+    ``### Chromosome group i ###`` header per new chromosome over ``new_lines[i]``, the order file and the plot-order file
+    through the existing writers.  The input files are only read."""
+    os.makedirs(outDir, exist_ok=True)
+    names = [os.path.join(outDir, os.path.basename(f)) for f in (chromosomeGroupFile, chromosomeOrderFile, plotOrderFile)]
+    if len(set(names)) != 3:
+        raise ValueError("the group, order and plot-order files need three different names")
+    for new, old in zip(names, (chromosomeGroupFile, chromosomeOrderFile, plotOrderFile)):
+        if os.path.abspath(new) == os.path.abspath(old):
+            raise ValueError("the regrouped files must not replace the input files: " + old)
+    with open(names[0], "w") as fh:
+        for k, lines in enumerate(new_lines):
+            fh.write("### Chromosome group " + str(k + 1) + " ###\n" + "".join(lines))
+    writeScaffoldOrderingsToFile(new_groups, names[1])
+    writeBinIDsOrderingToFile([s for group in new_groups for s in group], names[2])
+    return names
+
+
+def _plain(orderedChromosomes):
+    return [[(s.name, s.orientation) for s in group] for group in orderedChromosomes]
+
+
+def writeJoinedFiles(results, orderedChromosomes, outDir, chromosomeGroupFile, chromosomeOrderFile, plotOrderFile):
+    """The ordering with every ``joinable`` pair of chromosome ends joined (join_chromosomes), as a group file, an order
+    file and a plot-order file in ``outDir`` under the input files' names, and ``joins.log``: one line per join -
+    ``joined`` or ``dropped`` (the smallest join of a cycle), chromosome, end, chromosome, end, J, rel.  A joined group
+    holds its members' lines of the group file verbatim, lowest-numbered member first.  Returns the new chromosomes."""
+    _plainly, members, applied, dropped = join_chromosomes(_plain(orderedChromosomes), results["joinable"])
+    old_lines = _group_file_lines(chromosomeGroupFile)
+    new_groups, new_lines = [], []
+    for mem in members:
+        group = []
+        for c, rev in mem:
+            if rev:
+                for s in orderedChromosomes[c][::-1]:
+                    s = s.copy()
+                    s.flipOrientation()
+                    group.append(s)
+            else:
+                group.extend(orderedChromosomes[c])
+        new_groups.append(group)
+        new_lines.append([line for c in sorted(c for c, _r in mem) for line in old_lines[c]])
+    _write_regrouped(new_groups, new_lines, outDir, chromosomeGroupFile, chromosomeOrderFile, plotOrderFile)
+    ref = results["ref"]
+    with open(os.path.join(outDir, "joins.log"), "w") as fh:
+        for what, joins in (("joined", applied), ("dropped", dropped)):
+            for e, f, J in joins:
+                fh.write("\t".join([what, str(e // 2 + 1), _END_NAME[e & 1], str(f // 2 + 1), _END_NAME[f & 1], repr(J),
+                                    _support_text(None if ref is None else J / ref)]) + "\n")
+    print("Chromosome ends joined " + str(len(applied)))
+    return new_groups
+
+
+def writeCutFiles(results, orderedChromosomes, outDir, chromosomeGroupFile, chromosomeOrderFile, plotOrderFile):
+    """The ordering with every chromosome split at its ``weak`` junctions (cut_chromosomes), as the same three files in
+    ``outDir``, and ``cuts.log``: one line per cut - chromosome, left scaffold, right scaffold, J, rel.  A piece holds the
+    group file's lines of its scaffolds verbatim, in the file's order.  Returns the new chromosomes."""
+    _plainly, members = cut_chromosomes(_plain(orderedChromosomes), results["weak"])
+    old_lines = _group_file_lines(chromosomeGroupFile)
+    new_groups, new_lines = [], []
+    for c, a, b in members:
+        group = orderedChromosomes[c][a:b]
+        mine = {s.name for s in group}
+        new_groups.append(group)
+        new_lines.append([line for line in old_lines[c] if line.rstrip("\r\n").split("\t", 2)[1] in mine])
+    _write_regrouped(new_groups, new_lines, outDir, chromosomeGroupFile, chromosomeOrderFile, plotOrderFile)
+    weak = set(results["weak"])
+    with open(os.path.join(outDir, "cuts.log"), "w") as fh:
+        for row in results["internal"]:
+            if (row["chromosome"], row["boundary"]) in weak:
+                names = results["chromosomes"][row["chromosome"]]["names"]
+                fh.write("\t".join([str(row["chromosome"] + 1), names[row["boundary"]], names[row["boundary"] + 1],
+                                    repr(row["J"]), _support_text(row["rel"])]) + "\n")
+    print("Chromosomes cut at weak junctions " + str(len(weak)))
+    return new_groups
+
+
+def junctionSupportToFiles(matrix, orderedChromosomes, binList, chromosomeGroupFile, chromosomeOrderFile, plotOrderFile,
+                           junctionSupportFile=None, joinedDir=None, cutDir=None, fullDir=None, window=JUNCTION_WINDOW,
+                           minRel=JUNCTION_MIN_REL):
+    """junctionSupport of a resident map and the files wanted of it; returns the results.  Joins and cuts are never
+    applied in one file: ``joinedDir`` and ``cutDir`` must differ."""
+    if joinedDir and cutDir and os.path.abspath(joinedDir) == os.path.abspath(cutDir):
+        raise ValueError("the joined files and the cut files need directories of their own")
+    results = junctionSupport(matrix, orderedChromosomes, binList, window=window, minRel=minRel)
+    if junctionSupportFile:
+        writeJunctionSupportToFile(results, junctionSupportFile, fullDir)
+    if joinedDir:
+        writeJoinedFiles(results, orderedChromosomes, joinedDir, chromosomeGroupFile, chromosomeOrderFile, plotOrderFile)
+    if cutDir:
+        writeCutFiles(results, orderedChromosomes, cutDir, chromosomeGroupFile, chromosomeOrderFile, plotOrderFile)
+    return results
+
+
 def getChromosomeOutlineCoords(orderedChromosomes):
     """OG:662-674."""
     coords, index = [], 0
@@ -1831,7 +2210,7 @@ def runPipeline(hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroup
                 savePlotsDirectory, chromosomePlotSuffix, fullGenomePlot, fullGenomePlotTitle, plotOrderFile,
                 nScaffolds, scanScaffolds, resolution, device=0, resident=None, placementSupportFile=None,
                 breakSupportFile=None, brokenChromosomeGroupFile=None, inversionSupportFile=None,
-                refinedChromosomeOrderFile=None):
+                refinedChromosomeOrderFile=None, junctionSupportFile=None, joinedFilesDirectory=None):
     """OG:679-712, same positional arguments (``device``, ``resident`` and the ``...File`` keywords are optional extras).
 
     ``placementSupportFile``: also write the placement-support report of the final ordering there (placementSupport).
@@ -1839,6 +2218,8 @@ def runPipeline(hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroup
     the breakable scaffolds split (breakSupport).
     ``inversionSupportFile``: also write the inversion-support report there (inversionSupport).
     ``refinedChromosomeOrderFile``: also write the ordering after refineOrdering's hill climb there, as an order file.
+    ``junctionSupportFile`` / ``joinedFilesDirectory``: also write the junction-support report there, and the group,
+    order and plot-order files with the joinable chromosome ends joined into that directory (junctionSupport).
 
     ``resident=(DeviceMatrix, bins of its rows)`` from Part 1's ``runPipeline(..., keep_resident=True)``: the contact
     matrix already in HBM is used instead of parsing the HiC-Pro text again.  The reference re-loads the matrix
@@ -1870,6 +2251,9 @@ def runPipeline(hicProBedFile, hicProBiasFile, hicProMatrixFile, chromosomeGroup
             refined, _log, _summary = refineOrdering(adjMat, orderedChromosomes, binList,
                                                      _read_groups_quietly(chromosomeGroupFile))
             writeScaffoldOrderingsToFile(refined, refinedChromosomeOrderFile)
+        if junctionSupportFile or joinedFilesDirectory:
+            junctionSupportToFiles(adjMat, orderedChromosomes, binList, chromosomeGroupFile, chromosomeOrderFile,
+                                   plotOrderFile, junctionSupportFile, joinedFilesDirectory)
         if plotModule.plots_enabled(fullGenomePlot):                      # OG:700-707
             where = adjMat.bin_index(binList)
             rows = [where[b] for group in orderedChromosomes for s in group for b in s.binList]

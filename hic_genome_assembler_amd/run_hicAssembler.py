@@ -70,7 +70,9 @@ _OPTIONAL = {"placementSupportFile": "saveFilesDirectory",     # -part2 also wri
              "breakSupportFile": "saveFilesDirectory",         # -part2 also writes the break-support report there
              "brokenChromosomeGroupFile": "saveFilesDirectory",    # ... and the group file with the breakable scaffolds split
              "inversionSupportFile": "saveFilesDirectory",     # -part2 also writes the inversion-support report there
-             "refinedChromosomeOrderFile": "saveFilesDirectory"}   # ... and the order file after the refinement's hill climb
+             "refinedChromosomeOrderFile": "saveFilesDirectory",   # ... and the order file after the refinement's hill climb
+             "junctionSupportFile": "saveFilesDirectory",      # -part2 also writes the junction-support report there
+             "joinedFilesDirectory": "saveFilesDirectory"}     # ... and the three files with the joinable ends joined
 # -part0's keys, optional in the same way: the raw HiC-Pro map (a full path, like the other hicPro* files) and ICE's
 # settings (defaults: ICE_DEFAULTS); a value that does not parse leaves the key out, with a warning
 _OPTIONAL_PART0 = {"hicProRawMatrixFile": str, "iceFilterLowPerc": float, "iceMaxIter": int, "iceEps": float,
@@ -248,7 +250,8 @@ def main(argv=None):
                           v["fullGenomePlot"], v["fullGenomePlotTitle"], v["plotOrderFile"],
                           v["nScaffolds"], v["scanScaffolds"], v["resolution"], device=args.device, resident=resident,
                           **{k: v[k] for k in ("placementSupportFile", "breakSupportFile", "brokenChromosomeGroupFile",
-                                                   "inversionSupportFile", "refinedChromosomeOrderFile") if k in v})
+                                                   "inversionSupportFile", "refinedChromosomeOrderFile", "junctionSupportFile",
+                                                   "joinedFilesDirectory") if k in v})
     if args.part3:
         from . import orientSmallScaffolds as part3
         part3.runPipeline(v["chromosomeOrderFile"], v["hicProScaffSizeFile"], v["restrictionSiteFile"], v["validPairFile"],

@@ -566,6 +566,28 @@ int hicmi_louvain_modularity(hicmi_ctx *ctx, const int32_t *parts, int64_t round
 int hicmi_group_sums(hicmi_ctx *ctx, const int32_t *grp, const int32_t *scaf, int64_t n_groups, int64_t n_scaffolds,
                      double *bin_sums_out, double *scaffold_sums_out);
 
+/* ---- Part 2: junction support ---------------------------------------------------
+ * orderGenome.py's chromosome loop (OG:608-612) orders every chromosome group on its own; nothing there looks from one
+ * group at another, or asks whether the two sides of a scaffold boundary belong together.  This entry point extends that
+ * call site: on the context's contact matrix M as it stands (uploaded fp64, fp32 widened, adopted with ld > n, or
+ * compacted; n bins), bins[0 .. n_listed) is the bin order of every ordered chromosome, one after the other, as matrix
+ * indices in [0, n) - uploaded once per call - and rec holds six values per record: startA, stepA, lenA, startB, stepB,
+ * lenB.  A side is read outwards from a junction: its entry k is bins[start + k * step], step = +1 or -1, entry 0
+ * touching the junction.
+ *   sums_out[r] = sum over a < lenA, b < lenB of M[A_a][B_b] * (1.0 / (a + b + 1))
+ * The weights come from a table of 1.0 / d the library builds on the host (IEEE division) and uploads; the kernels do not
+ * divide, and each product is rounded before it is added.  The order of every sum is fixed by (lenA, lenB) alone, so two
+ * calls give the same bits: A's rows in slabs of 64, a slab's rows x lenB elements dealt row-major to 256 lanes, the lane
+ * sums added as a fixed tree, the slab sums left to right (k_junctions_partial, k_junctions_reduce: no atomics, no
+ * dynamic LDS, nothing staged per record).  HICMI_JUNCTIONS_PLAIN=1 in the environment takes one thread per record with
+ * a serial double loop instead - the definition taken literally, the A/B path; it differs in rounding only.
+ * HICMI_EINVAL when no matrix is set, a length is below 1, a step is not +1 or -1, a side runs outside bins, or a bin is
+ * outside [0, n); HICMI_EUNSUPPORTED above 2^31 - 1 workgroups (the sum over the records of ceil(lenA / 64)).  Either is
+ * returned before anything is launched, with the context unchanged.  n_rec = 0: nothing to do.
+ * Device scratch: the records, bins, the weights and one double per workgroup and per record. */
+int hicmi_junction_sums(hicmi_ctx *ctx, const int32_t *bins, int64_t n_listed, const int64_t *rec, int64_t n_rec,
+                        double *sums_out);
+
 /* ---- Part 0: ICE balancing of a raw map ----------------------------------------
  * Replaces HiC-Pro's `ice` step (ice --filter_low_counts_perc 0.02 --filter_high_counts_perc 0 --max_iter 100 --eps 0.1
  * --remove-all-zeros-loci --output-bias 1; iced.normalization.ICE_normalization and iced.filter), which the reference
