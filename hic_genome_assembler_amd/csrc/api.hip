@@ -216,12 +216,20 @@ int resolve_timing(hicmi_ctx* c)
     if (c->regions.empty()) return HICMI_OK;
     HIPCHK(sync_stream(c));
     if (c->stream2) HIPCHK(hipStreamSynchronize(c->stream2));
+    // a region whose elapsed time cannot be read is an error, not a smaller sum (the events go back to the pool either way)
+    int dropped = 0, dropped_fam = 0;
+    hipError_t dropped_err = hipSuccess;
     for (auto& r : c->regions) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) c->ms[r.fam] += ms;
+        const hipError_t e = hipEventElapsedTime(&ms, r.a, r.b);
+        if (e == hipSuccess) c->ms[r.fam] += ms;
+        else if (dropped++ == 0) { dropped_fam = r.fam; dropped_err = e; }
         c->pool.push_back(r.a); c->pool.push_back(r.b);
     }
     c->regions.clear();
+    if (dropped)
+        return fail(HICMI_EHIP, "hipEventElapsedTime failed for %d timed region(s), the first of family %s: %s", dropped,
+                    kFamilyNames[dropped_fam], hipGetErrorString(dropped_err));
     return HICMI_OK;
 }
 
@@ -1104,7 +1112,7 @@ int hicmi_upgma(hicmi_ctx* c, double* Z_out, int32_t* leaves_out)
         int rc_dl = download(c, &nn, nnchain_state_ptr(c->d_size), sizeof(nn));
         if (rc_dl) return rc_dl;
         c->bytes[F_NNCHAIN] += 8.0 * ((double)nn.prof[5] + 3.0 * (0.5 * (double)(n - 1) * (double)(n + 2)));
-        c->nn_scans += (double)nn.prof[6]; c->nn_scan_cols += (double)nn.prof[5]; c->nn_cache_hits += (double)nn.prof[7];
+        c->nn_scans += (double)nn.prof[6]; c->nn_scan_cols += (double)nn.prof[5]; c->nn_cache_hits += (double)(long long)nn.prof[7];
         c->nn_merges += (double)(n - 1);
         if (nn.state[5] != 2 || attempt > 1) break;
         // A peer workgroup of the column-sliced chain did not answer within its spin budget (a GPU shared with other
@@ -1526,8 +1534,9 @@ static int run_scan_multi(hicmi_ctx* c, std::vector<ScanState>& h, const ScanMul
     }
     int64_t scans = 0; double bytes = 0;
     for (const ScanState& r : h) { scans += r.scans; bytes += (double)r.bytes; }
-    c->launches[F_CUT_COUNT] += scans - batches;                  // the family is reported per set and scan
-    c->launches[F_HYPER_FLAGS] += scans;                          // (the decisions ride in the same launches)
+    // the family is reported per set and scan; the flags are decided inside k_cut_rows, by the lanes that hold the counts: no
+    // launch of the hyper_flags family, which is k_hyper_flags after a scan driven from the host (finish_scan)
+    c->launches[F_CUT_COUNT] += scans - batches;
     c->bytes[F_CUT_COUNT] += bytes;
     return HICMI_OK;
 }
@@ -2037,17 +2046,23 @@ int window_batch_enqueue(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k)
     rc = upload(c, c->d_wb, wb.data(), sizeof(WindowBatchEntry) * (size_t)count);
     if (rc) return rc;
     {
-        // the G and delta kernels are launched as a pair; their algorithmic bytes are booked separately
-        c->launches[F_P2_WINDOW_DELTA]++; c->bytes[F_P2_WINDOW_DELTA] += d_bytes;
+        // the G and delta kernels are launched as a pair; each family is a timed region of its own
         if (!direct) { c->launches[F_P2_WINDOW_FLOPS]++; c->bytes[F_P2_WINDOW_FLOPS] += g_flops; }   // (flops of the GEMM form: bench.py's `mfma`)
         Timed t(c, F_P2_WINDOW_G, g_bytes);
         if (direct)
-            launch_p2_window_batch(c->dM2, c->ld2, c->d_pos2sel, (int)c->n_arr, (int)k, c->d_wb, (int)count, max_m, c->d_orders,
-                                   c->d_orients, (int)c->n_orders, (int)c->n_orients, c->d_H, c->d_G, c->d_delta, c->stream);
+            launch_p2_window_batch_G(c->dM2, c->ld2, c->d_pos2sel, (int)c->n_arr, c->d_wb, (int)count, max_m, c->d_H, c->d_G, c->stream);
         else
             launch_p2_window_tables(c->dM2, c->ld2, c->d_pos2sel, (int)c->n_arr, (int)k, c->d_wb, wb.data(), (int)count, max_m,
-                                    c->d_orders, c->d_orients, (int)c->n_orders, (int)c->n_orients, c->d_H, c->d_G, c->d_delta,
-                                    c->stream);
+                                    c->d_H, c->d_G, c->stream);
+    }
+    {
+        Timed t(c, F_P2_WINDOW_DELTA, d_bytes);
+        if (direct)
+            launch_p2_window_batch_delta(c->dM2, c->ld2, c->d_pos2sel, (int)c->n_arr, (int)k, c->d_wb, (int)count, max_m, c->d_orders,
+                                         c->d_orients, (int)c->n_orders, (int)c->n_orients, c->d_H, c->d_G, c->d_delta, c->stream);
+        else
+            launch_p2_window_candidates((int)k, (int)count, c->d_orders, c->d_orients, (int)c->n_orders, (int)c->n_orients, c->d_G,
+                                        c->d_delta, c->stream);
     }
     HIPCHK(hipGetLastError());
     rc = ensure_pin_down(c, sizeof(double) * (size_t)(n_cand * count));

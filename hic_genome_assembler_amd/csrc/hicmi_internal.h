@@ -275,17 +275,23 @@ struct WindowBatchEntry {      // one window of a batch (device array)
     int64_t g_off;             // offset of its m x m table in the batch's G buffer
     int32_t c0, pad;           // candidate of the current configuration (identity order, current signs): short lists
 };
-void launch_p2_window_batch(const double* M2, int64_t ld2, const int32_t* pos2sel, int n, int k,
-                            const WindowBatchEntry* wb, int n_win, int max_m, const int8_t* orders, const uint8_t* orients,
-                            int n_ord, int n_ori, const double* H, double* G_all, double* delta_all, hipStream_t s);
+// (two calls, so that each family - p2_window_G, p2_window_delta - is a timed region of its own)
+void launch_p2_window_batch_G(const double* M2, int64_t ld2, const int32_t* pos2sel, int n, const WindowBatchEntry* wb, int n_win,
+                              int max_m, const double* H, double* G_all, hipStream_t s);
+void launch_p2_window_batch_delta(const double* M2, int64_t ld2, const int32_t* pos2sel, int n, int k,
+                                  const WindowBatchEntry* wb, int n_win, int max_m, const int8_t* orders, const uint8_t* orients,
+                                  int n_ord, int n_ori, const double* H, const double* G_all, double* delta_all, hipStream_t s);
 
 
 // k_part2_window.hip: the same scores from placement tables (one pass over the matrix per table, a few look-ups
 // per candidate); tables = n_win * window_table_doubles(k) doubles of scratch
 int64_t window_table_doubles(int k);
 void launch_p2_window_tables(const double* M2, int64_t ld2, const int32_t* pos2sel, int n, int k,
-                             const WindowBatchEntry* wb, const WindowBatchEntry* h_wb, int n_win, int max_m, const int8_t* orders, const uint8_t* orients,
-                             int n_ord, int n_ori, const double* H, double* tables, double* delta_all, hipStream_t s);
+                             const WindowBatchEntry* wb, const WindowBatchEntry* h_wb, int n_win, int max_m, const double* H,
+                             double* tables, hipStream_t s);
+// ... and the candidates' look-ups in them (the p2_window_delta family)
+void launch_p2_window_candidates(int k, int n_win, const int8_t* orders, const uint8_t* orients, int n_ord, int n_ori,
+                                 const double* tables, double* delta_all, hipStream_t s);
 // The same tables, then only the near-top candidates of every window (the short list of decide_from_delta) without the
 // deltas: pass 1 takes each window's largest finite fast score, pass 2 appends the candidates with fast >= thr to
 // near[w * cap ...] through the counter count[w] (count[w] > cap: the list overflowed and is incomplete).  whole: k == S

@@ -208,7 +208,14 @@ struct NNWorkspace {
                                 // [8] profile on [9] first step of the epoch that ran last [10] test: exchange that is declared late
                                 // [11] test: step whose record replica 1 falsifies
     unsigned long long* prof;   // [0..4] phase totals (100 MHz ticks), [5] columns visited by row scans, [6] row scans,
-                                // [7] chain steps answered by the neighbour cache
+                                // [7] chain steps answered by the neighbour cache.  Every chain step of SciPy's loop is
+                                // counted once: [6] + [7] = its steps.  A scan counts in [6]; a push from the cache and the
+                                // walk's "cache names the previous element" (the confirming step) count in [7]; a scan that
+                                // itself confirms the pair writes that entry and takes the walk's count back, which may fall
+                                // into the next epoch - so [7] is a sum modulo 2^64 that is non-negative once the chain is done
+                                // (api.hip reads it as a signed number).  A fused scan whose entry a cache rebuild
+                                // (k_nn_rowmin) replaces before the walk saw it is scanned again: both scans are in [6], [7]
+                                // is one less, the sum stands.
     void* mail;                 // k_nn_epoch_mwc: 2 parities x NN_MAXWG workgroups x 2 slots of 16 bytes
     uint32_t* alive;            // nwords
     uint16_t* size;             // n
@@ -555,7 +562,7 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_epoch_nc(double* __restrict__
     // lane-0 private chain state
     int len = w.state[1], top = w.state[2], second = w.state[3], first_ptr = w.state[4], ring_lo = len;
     unsigned long long t_book = 0, t_scan = 0, t_pick = 0, t_merge = 0, t_upd = 0, t0 = 0, t1 = 0;
-    unsigned long long c_cols = 0, c_scans = 0, c_hits = 0;
+    unsigned long long c_cols = 0, c_scans = 0; long long c_hits = 0;     // (see NNWorkspace::prof)
     if (tid == 0) { s_stop = 0; w.state[9] = step; }
     __syncthreads();
     int D = 0;                                              // dirty entries (uniform across lanes)
@@ -577,7 +584,7 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_epoch_nc(double* __restrict__
                     const int x = top, prev = (len > 1) ? second : -1;
                     const uint32_t idx = nnidx[x];
                     if (idx == NN_NOIDX) act = 1;
-                    else if ((int)idx == prev) act = 2;
+                    else if ((int)idx == prev) { act = 2; c_hits++; }      // the confirming step (a scan that named prev took it back)
                     else if (prev >= 0 && ((tieb[x >> 5] >> (x & 31)) & 1u)) act = 1;      // an exact tie: the value decides
                     else if (++guard > 4 * n + 8) { stop_code = NN_STOP_GUARD; act = 3; }
                     else {
@@ -646,6 +653,7 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_epoch_nc(double* __restrict__
                         } else {
                             // reciprocal by the tie rule although the cache names another column: let the walk see it
                             nnidx[x] = (uint16_t)prev;
+                            c_hits--;                                // (this scan WAS the confirming step: the walk counts it again)
                         }
                     }
                 }
@@ -781,7 +789,7 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_epoch_nc(double* __restrict__
     if (tid == 0) {
         w.state[0] = step; w.state[1] = len; w.state[2] = top; w.state[3] = second; w.state[4] = first_ptr;
         w.state[5] = stop_code; w.state[6] = D;
-        w.prof[5] += c_cols; w.prof[6] += c_scans; w.prof[7] += c_hits;
+        w.prof[5] += c_cols; w.prof[6] += c_scans; w.prof[7] += (unsigned long long)c_hits;
         if (PROFILE) { w.prof[0] += t_book; w.prof[1] += t_scan; w.prof[2] += t_pick; w.prof[3] += t_merge; w.prof[4] += t_upd; }
     }
 }
@@ -980,7 +988,7 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_epoch_mwc(double* __restrict_
     int lowmark = len;                                       // lane 0: chain entries below this are still the earlier epochs'
     const int step0 = step;
     const int inject_late = w.state[10], inject_wrong = w.state[11];      // test hooks (0 = off)
-    __shared__ unsigned long long s_cnt[3];                  // lane 0: columns visited by scans, scans, cache hits
+    __shared__ unsigned long long s_cnt[3];                  // lane 0: columns visited by scans, scans, cache hits (mod 2^64: NNWorkspace::prof)
     if (tid == 0) { s_cnt[0] = 0; s_cnt[1] = 0; s_cnt[2] = 0; }
     if (tid == 0 && wg == 0) w.state[9] = step0;
     int guard = 0, stop_code = 0;                            // lane 0
@@ -1000,7 +1008,7 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_epoch_mwc(double* __restrict_
                     const int x = top, prev = (len > 1) ? second : -1;
                     const uint32_t idx = nnidx[x];
                     if (idx == NN_NOIDX) act = 1;
-                    else if ((int)idx == prev) act = 2;
+                    else if ((int)idx == prev) { act = 2; s_cnt[2]++; }      // the confirming step (a scan that named prev took it back)
                     else if (prev >= 0 && ((tieb[x >> 5] >> (x & 31)) & 1u)) act = 1;
                     else if (++guard > 4 * n + 8) { stop_code = NN_STOP_GUARD; act = 3; }
                     else {
@@ -1112,7 +1120,7 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_epoch_mwc(double* __restrict_
                             chain[len] = y; ring[len & 255] = y;
                             if (len - 255 > ring_lo) ring_lo = len - 255;
                             second = top; top = y; len++;
-                        } else nnidx[x] = (uint16_t)prev;               // reciprocal by the tie rule: let the walk see it
+                        } else { nnidx[x] = (uint16_t)prev; s_cnt[2]--; }   // reciprocal by the tie rule: let the walk see it
                     }
                 }
             }
@@ -1179,7 +1187,7 @@ __global__ __launch_bounds__(NN_THREADS) void k_nn_epoch_mwc(double* __restrict_
                         chain[len] = y; ring[len & 255] = y;
                         if (len - 255 > ring_lo) ring_lo = len - 255;
                         second = top; top = y; len++;
-                    } else nnidx[a] = (uint16_t)aprev;
+                    } else { nnidx[a] = (uint16_t)aprev; s_cnt[2]--; }
                 }
             }
         };
@@ -1642,7 +1650,7 @@ __global__ __launch_bounds__(64) void k_nn_epoch_w1(double* __restrict__ W, int6
     const unsigned int xseq0 = xseq;
     int guard = 0, stop_code = 0, why = 0;                   // why: which check stopped the chain (diagnostics, state[13])
     unsigned long long hash = 0x243F6A8885A308D3ull;         // of this replica's merge records
-    unsigned long long c_cols = 0, c_scans = 0, c_hits = 0;
+    unsigned long long c_cols = 0, c_scans = 0; long long c_hits = 0;     // (see NNWorkspace::prof)
     unsigned long long tp[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t0 = 0;   // PROF: walk, scan, exchange+after, merge book, issue, arrive, compute, reduce, drain, -
     const bool prof = PROF && wg == 0;
     unsigned long long npolls = 0;                           // PROF: polls of the slowest-answering peer, summed over the exchanges (per lane)
@@ -1760,7 +1768,7 @@ __global__ __launch_bounds__(64) void k_nn_epoch_w1(double* __restrict__ W, int6
                 const int prev = (len > 1) ? second : -1;
                 const uint32_t e = umeta(top);
                 if (!entry_valid(e)) act = 1;
-                else if ((int)(e & W1_NOIDX) == prev) act = 2;
+                else if ((int)(e & W1_NOIDX) == prev) { act = 2; c_hits++; }      // the confirming step (a scan that named prev took it back)
                 else if (prev >= 0 && ((e >> 15) & 1u)) act = 1;             // an exact tie: the value decides
                 else if (++guard > 4 * n + 8) { stop_code = NN_STOP_GUARD; act = 3; why = 2; }
                 else { push((int)(e & W1_NOIDX)); c_hits++; pushed_cached = 1; }
@@ -1816,7 +1824,7 @@ __global__ __launch_bounds__(64) void k_nn_epoch_w1(double* __restrict__ W, int6
                 if (y != prev) {
                     if (++guard > 4 * n + 8) { stop_code = NN_STOP_GUARD; why = 4; }
                     push(y);
-                }
+                } else c_hits--;                             // (this scan WAS the confirming step: the walk counts it again)
             }
             W1_STAMP(2);
         }
@@ -1997,7 +2005,7 @@ __global__ __launch_bounds__(64) void k_nn_epoch_w1(double* __restrict__ W, int6
                 if (y != aprev) {
                     if (++guard > 4 * n + 8) { stop_code = NN_STOP_GUARD; why = 6; }
                     push(y);
-                }
+                } else c_hits--;
             }
         }
         W1_STAMP(2);
@@ -2025,7 +2033,7 @@ __global__ __launch_bounds__(64) void k_nn_epoch_w1(double* __restrict__ W, int6
         w.state[0] = step; w.state[1] = len; w.state[2] = top; w.state[3] = second; w.state[4] = first_ptr;
         w.state[5] = stop_code; w.state[6] = 0; if (why) w.state[13] = why;
         w.state[14] = (int)xseq;
-        w.prof[5] += c_cols; w.prof[6] += c_scans; w.prof[7] += c_hits;
+        w.prof[5] += c_cols; w.prof[6] += c_scans; w.prof[7] += (unsigned long long)c_hits;
         if (PROF) {
             w.prof[0] += tp[0]; w.prof[1] += tp[1]; w.prof[2] += tp[2]; w.prof[3] += tp[3];
             unsigned long long* p2 = reinterpret_cast<unsigned long long*>(reinterpret_cast<unsigned char*>(w.state) + 1280);

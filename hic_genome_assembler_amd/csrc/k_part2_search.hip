@@ -465,9 +465,8 @@ __global__ __launch_bounds__(WD_WAVES * 64) void k_p2_window_delta(const double*
 }
 
 // one launch pair for n_win windows described by the device array wb; max_m = largest window (bins)
-void launch_p2_window_batch(const double* M2, int64_t ld2, const int32_t* pos2sel, int n, int k,
-                            const WindowBatchEntry* wb, int n_win, int max_m, const int8_t* orders, const uint8_t* orients,
-                            int n_ord, int n_ori, const double* H, double* G_all, double* delta_all, hipStream_t s)
+void launch_p2_window_batch_G(const double* M2, int64_t ld2, const int32_t* pos2sel, int n, const WindowBatchEntry* wb, int n_win,
+                              int max_m, const double* H, double* G_all, hipStream_t s)
 {
     if (n_win <= 0 || max_m <= 0) return;
     const size_t h_lds = (((size_t)n * sizeof(double)) + 15) & ~(size_t)15;
@@ -477,6 +476,13 @@ void launch_p2_window_batch(const double* M2, int64_t ld2, const int32_t* pos2se
     } else {
         hipLaunchKernelGGL(k_p2_window_G<false>, dim3(max_m, n_win), dim3(256), 0, s, M2, ld2, pos2sel, n, wb, H, G_all);
     }
+}
+
+void launch_p2_window_batch_delta(const double* M2, int64_t ld2, const int32_t* pos2sel, int n, int k,
+                                  const WindowBatchEntry* wb, int n_win, int max_m, const int8_t* orders, const uint8_t* orients,
+                                  int n_ord, int n_ori, const double* H, const double* G_all, double* delta_all, hipStream_t s)
+{
+    if (n_win <= 0 || max_m <= 0) return;
     const int n_cand = n_ord * n_ori;
     const size_t wt_bytes = (size_t)max_m * sizeof(double);
     const size_t seq4 = ((((size_t)max_m * 2 * 4 * sizeof(int32_t)) + 15) & ~(size_t)15) + wt_bytes;

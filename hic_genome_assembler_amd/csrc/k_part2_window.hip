@@ -580,11 +580,17 @@ static void build_window_tables(const double* M2, int64_t ld2, const int32_t* po
 
 // tables: n_win * window_table_doubles(k) doubles of scratch; delta_all: n_win x (n_ord * n_ori)
 void launch_p2_window_tables(const double* M2, int64_t ld2, const int32_t* pos2sel, int n, int k,
-                             const WindowBatchEntry* wb, const WindowBatchEntry* h_wb, int n_win, int max_m, const int8_t* orders, const uint8_t* orients,
-                             int n_ord, int n_ori, const double* H, double* tables, double* delta_all, hipStream_t s)
+                             const WindowBatchEntry* wb, const WindowBatchEntry* h_wb, int n_win, int max_m, const double* H,
+                             double* tables, hipStream_t s)
 {
     if (n_win <= 0 || k < 1) return;
     build_window_tables(M2, ld2, pos2sel, n, k, wb, h_wb, n_win, max_m, H, tables, s);
+}
+
+void launch_p2_window_candidates(int k, int n_win, const int8_t* orders, const uint8_t* orients, int n_ord, int n_ori,
+                                 const double* tables, double* delta_all, hipStream_t s)
+{
+    if (n_win <= 0 || k < 1) return;
     const int n_cand = n_ord * n_ori;
     hipLaunchKernelGGL(k_win_candidates, dim3((n_cand + 255) / 256, n_win), dim3(256), 0, s, k, orders, orients, n_ori, n_cand,
                        tables, stride_of(k), delta_all);

@@ -220,7 +220,12 @@ int hicmi_get_raw_merges(hicmi_ctx *ctx, double *Zraw_out);
 /* Counters of the nn-chain kernels (scipy average, S2C:197) since the last hicmi_timing_reset, 6 doubles:
  * [0] merges, [1] row scans, [2] columns those scans visited (the "sum over scans of the live columns" of the
  * algorithmic-bytes definition), [3] chain steps answered by the neighbour cache instead of a scan,
- * [4] re-runs on one workgroup after a late peer of the column-sliced kernel, [5] reserved. */
+ * [4] re-runs on one workgroup after a late peer of the column-sliced kernel, [5] reserved.
+ * A chain step is one pass of SciPy's inner loop (the row of the chain's top element is scanned; the pass that confirms
+ * a reciprocal pair included), and every one is counted once: [1] + [3] = SciPy's steps, for every kernel with the
+ * cache; the cache-less kernel (HICMI_NNCHAIN_PLAIN=1) has [1] = SciPy's steps, [2] = the columns they visit, [3] = 0.
+ * The scan fused with a merge is the next step's scan.  How the steps split between [1] and [3] depends on the epoch
+ * length and the kernel, not on the number of replicas. */
 int hicmi_nnchain_stats(hicmi_ctx *ctx, double *out6);
 
 /* ---- Part 2: ordering objective --------------------------------------------------------------
@@ -620,8 +625,12 @@ int hicmi_get_contact_rows(hicmi_ctx *ctx, int64_t row0, int64_t nrows, double *
  * reset, for bench.py's roofline object.  names_out: caller buffer receiving ';'-separated names;
  * ms_out / launches_out / bytes_out: one entry per name (algorithmic bytes as defined in DESIGN.md).
  * hicmi_timing_enable: 0 = off, 1 = every family, 2 = only the Part 1 families that are launched a few times
- * per map (row sums, distance build, nn-chain, row sort, rank inversion) - launches and bytes are counted in
- * every mode. */
+ * per map: row_sums, build_w, nnchain, sort_rows, rank_invert, and the three of the pre-sort path - presort_rows,
+ * rank_relabel, rank_rows_tied.  (presort_rows and the rank_invert behind it are recorded on the pre-sort's second
+ * stream, beside the nn-chain: their ms overlap the chain's.)  Launches and bytes are counted in every mode; ms is
+ * 0 for a family the mode does not time.  p2_window_G_flops is a pure counter: its "bytes" are the flops of the
+ * window tables' GEMM, its ms is always 0.  An event pair whose elapsed time cannot be read is an error
+ * (HICMI_EHIP) of the call that collects it - reset, enable or get - never a smaller sum. */
 int hicmi_timing_reset(hicmi_ctx *ctx);
 int hicmi_timing_enable(hicmi_ctx *ctx, int on);
 int hicmi_timing_get(hicmi_ctx *ctx, char *names_out, int64_t names_cap, double *ms_out,
