@@ -85,6 +85,12 @@ SIGNATURES = {
     "hicmi_scan_valid_pairs": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, _vp, c_i64, ctypes.c_int,
                                               ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(_vp)]),
     "hicmi_scan_fetch": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "hicmi_parse_valid_pairs": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, ctypes.c_int, c_i64, c_i64,
+                                               _vp, _vp, _vp, _vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), _vp]),
+    "hicmi_map_begin": (ctypes.c_int, [_vp, _vp, c_i64, c_i64]),
+    "hicmi_map_add_pairs": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, c_i64]),
+    "hicmi_map_finish": (ctypes.c_int, [_vp, ctypes.POINTER(c_i64)]),
+    "hicmi_build_maps": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, c_i64, _vp, _vp, ctypes.c_int, _vp]),
     "hicmi_plot_percentiles": (ctypes.c_int, [_vp, ctypes.c_int, _vp, c_i64, _vp, c_i64, _vp]),
     "hicmi_plot_downsample": (ctypes.c_int, [_vp, ctypes.c_int, _vp, c_i64, c_i64, _vp]),
     "hicmi_p2_insert_all_multi": (ctypes.c_int, [c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -197,21 +203,70 @@ def format_double(v) -> str:
 def scan_valid_pairs(path, names, pairs, threads: int = 0):
     """Lines of a HiC-Pro allValidPairs file that name one of the ordered scaffold pairs ``pairs`` (indices
     into ``names``): returns (pair index, pos1, pos2) arrays in file order and the number of lines read."""
-    enc = [n.encode("utf-8") for n in names]
-    blob = b"".join(enc)
-    off = np.zeros(len(enc) + 1, np.int64)
-    if enc:
-        off[1:] = np.cumsum([len(e) for e in enc])
+    blob, off = _name_blob(names)
     pa = np.ascontiguousarray([p[0] for p in pairs], dtype=np.int32)
     pb = np.ascontiguousarray([p[1] for p in pairs], dtype=np.int32)
     n_hits, n_lines, handle = c_i64(), c_i64(), _vp()
-    _check(load().hicmi_scan_valid_pairs(os.fsencode(path), blob, _ptr(off), len(enc), _ptr(pa), _ptr(pb), len(pa), int(threads),
+    _check(load().hicmi_scan_valid_pairs(os.fsencode(path), blob, _ptr(off), len(off) - 1, _ptr(pa), _ptr(pb), len(pa), int(threads),
                                          ctypes.byref(n_hits), ctypes.byref(n_lines), ctypes.byref(handle)))
     idx = np.empty(n_hits.value, np.int32)
     p1 = np.empty(n_hits.value, np.int64)
     p2 = np.empty(n_hits.value, np.int64)
     _check(load().hicmi_scan_fetch(handle, _ptr(idx), _ptr(p1), _ptr(p2)))
     return idx, p1, p2, n_lines.value
+
+
+def _name_blob(names):
+    """(concatenated UTF-8 names, int64 offsets) as the valid-pair readers take them."""
+    enc = [n.encode("utf-8") for n in names]
+    off = np.zeros(len(enc) + 1, np.int64)
+    if enc:
+        off[1:] = np.cumsum([len(e) for e in enc])
+    return b"".join(enc), off
+
+
+def parse_valid_pairs(path, names, sizes, first_byte: int = 0, max_pairs=None, threads: int = 0):
+    """Up to ``max_pairs`` read pairs of a HiC-Pro allValidPairs file from ``first_byte`` on (hicmi_parse_valid_pairs,
+    DESIGN.md 9l): (scaffold a, position a, scaffold b, position b) in file order - indices into ``names``, 1-based
+    positions - then next_byte (the file size when the file is done) and (lines, used, unknown_scaffold, out_of_range).
+    ``max_pairs=None``: as many as the rest of the file can hold."""
+    blob, off = _name_blob(names)
+    size = np.ascontiguousarray(sizes, dtype=np.int64)
+    if size.shape != (len(names),):
+        raise ValueError("one size per scaffold name")
+    if max_pairs is None:
+        try:
+            max_pairs = max(1, (os.path.getsize(path) - int(first_byte)) // 12 + 1)     # a six-column line has 12 bytes or more
+        except OSError:
+            max_pairs = 1                                                               # the library reports the file
+    max_pairs = int(max_pairs)
+    sa, sb = np.empty(max(max_pairs, 0), np.int32), np.empty(max(max_pairs, 0), np.int32)
+    pa, pb = np.empty(max(max_pairs, 0), np.int64), np.empty(max(max_pairs, 0), np.int64)
+    n, nxt, stats = c_i64(), c_i64(), np.zeros(4, np.int64)
+    _check(load().hicmi_parse_valid_pairs(os.fsencode(path), blob, _ptr(off), len(names), _ptr(size), int(threads), int(first_byte),
+                                          max_pairs, _ptr(sa), _ptr(pa), _ptr(sb), _ptr(pb), ctypes.byref(n), ctypes.byref(nxt),
+                                          _ptr(stats)))
+    k = n.value
+    return sa[:k], pa[:k], sb[:k], pb[:k], nxt.value, tuple(int(v) for v in stats)
+
+
+def build_maps(path, names, sizes, resolutions, ctxs, threads: int = 0):
+    """One pass over a HiC-Pro allValidPairs file for the raw maps at every resolution of ``resolutions``, ``ctxs[k]``
+    receiving the map at ``resolutions[k]`` (hicmi_build_maps); the contexts are distinct and on one GPU.
+    Returns (lines, used, unknown_scaffold, out_of_range, chunks)."""
+    blob, off = _name_blob(names)
+    size = np.ascontiguousarray(sizes, dtype=np.int64)
+    res = np.ascontiguousarray(resolutions, dtype=np.int64)
+    if size.shape != (len(names),) or res.ndim != 1 or len(res) != len(ctxs) or not len(ctxs):
+        raise ValueError("one size per scaffold name and one context per resolution")
+    handles = (_vp * len(ctxs))(*[c._h for c in ctxs])
+    stats = np.zeros(5, np.int64)
+    _check(load().hicmi_build_maps(os.fsencode(path), blob, _ptr(off), len(names), _ptr(size), len(res), _ptr(res), handles,
+                                   int(threads), _ptr(stats)))
+    for c in ctxs:
+        c.n = c.contacts_device()[1]
+        c._keepalive = None
+    return tuple(int(v) for v in stats)
 
 
 def hypergeom_sf(x, M, n, N) -> float:
@@ -336,6 +391,30 @@ class Context:
             raise ValueError("group_start must have m + 1 >= 2 entries")
         _check(self._lib.hicmi_rebin(self._h, _ptr(g), len(g) - 1))
         self.n = len(g) - 1
+
+    def map_begin(self, sizes, resolution):
+        """Open the count of a raw map from read pairs (hicmi_map_begin): scaffold s has
+        ceil(sizes[s] / resolution) bins.  The context's matrix stays as it is until map_finish."""
+        size = np.ascontiguousarray(sizes, dtype=np.int64)
+        if size.ndim != 1:
+            raise ValueError("sizes must be a vector")
+        _check(self._lib.hicmi_map_begin(self._h, _ptr(size), len(size), int(resolution)))
+
+    def map_add_pairs(self, scaf_a, pos_a, scaf_b, pos_b):
+        """Count the pairs (scaffold index, 1-based position) x 2 into the open map (hicmi_map_add_pairs)."""
+        sa, sb = np.ascontiguousarray(scaf_a, dtype=np.int32), np.ascontiguousarray(scaf_b, dtype=np.int32)
+        pa, pb = np.ascontiguousarray(pos_a, dtype=np.int64), np.ascontiguousarray(pos_b, dtype=np.int64)
+        if not (sa.ndim == 1 and sa.shape == sb.shape == pa.shape == pb.shape):
+            raise ValueError("the four arrays must be vectors of one length")
+        _check(self._lib.hicmi_map_add_pairs(self._h, _ptr(sa), _ptr(pa), _ptr(sb), _ptr(pb), len(sa)))
+
+    def map_finish(self) -> int:
+        """Close the count (hicmi_map_finish): the symmetric map replaces the context's matrix; returns the pairs added."""
+        pairs = c_i64()
+        _check(self._lib.hicmi_map_finish(self._h, ctypes.byref(pairs)))
+        self.n = self.contacts_device()[1]
+        self._keepalive = None
+        return pairs.value
 
     def group_sums(self, grp, scaf, n_groups, n_scaffolds, want_bins=True):
         """Group support sums (hicmi_group_sums): (bin sums n x n_groups or None, scaffold sums

@@ -165,6 +165,12 @@ struct hicmi_ctx {
     double* d_lvvec = nullptr; int64_t lvvec_cap = 0;
     int32_t* d_lvrows = nullptr; int64_t lvrows_cap = 0;
     unsigned char* d_lvwork = nullptr; int64_t lvwork_cap = 0;   // per-call inputs, outputs and scratch
+    // a map being counted from read pairs (k_buildmap.hip), between hicmi_map_begin and hicmi_map_finish: the m x m
+    // 64-bit counts (map_cells != nullptr: a build is open), first_bin on the device, and the staging of a chunk of pairs
+    void* map_cells = nullptr; int64_t map_m = 0, map_res = 0, map_pairs = 0;
+    int32_t* d_map_first = nullptr;
+    std::vector<int32_t> map_first; std::vector<int64_t> map_size;
+    unsigned char* d_map_chunk = nullptr; int64_t map_chunk_cap = 0;
     // plot support
     int32_t* d_plot_order = nullptr; int64_t plot_order_cap = 0;
     unsigned char* d_plot_work = nullptr; int64_t plot_work_cap = 0;
@@ -411,6 +417,7 @@ int hicmi_destroy(hicmi_ctx* c)
     free_dev(c->d_jn_lists); free_dev(c->d_jn_sums);
     free_dev(c->d_ice); free_dev(c->d_ice_mask);
     free_dev(c->d_plot_order); free_dev(c->d_plot_work); free_dev(c->d_plot_img);
+    free_dev(c->map_cells); free_dev(c->d_map_first); free_dev(c->d_map_chunk);
     for (auto& sl : c->hslot) free_dev(sl.d_x);
     free_dev(c->d_hmulti); free_dev(c->d_horder); free_dev(c->d_hwork); free_dev(c->d_hlab); free_dev(c->d_hbt);
     free_dev(c->d_hpart); free_dev(c->d_hsmall); free_dev(c->d_hhist); free_dev(c->d_hst);
@@ -619,6 +626,236 @@ int hicmi_rebin(hicmi_ctx* c, const int32_t* group_start, int64_t m)
     int rc = alloc_sums(c);
     if (rc) return rc;
     return compute_sums(c);
+}
+
+// ---- a raw map counted from read pairs: HiC-Pro's build_matrix at any bin size --------------------------
+// Between hicmi_map_begin and hicmi_map_finish the counts live in scratch of their own (map_cells); the context's matrix
+// state is replaced only by a finish that succeeded.
+static void map_abandon(hicmi_ctx* c)
+{
+    free_dev(c->map_cells); c->map_cells = nullptr;
+    free_dev(c->d_map_first); c->d_map_first = nullptr;
+    c->map_m = 0; c->map_res = 0; c->map_pairs = 0;
+    c->map_first.clear(); c->map_size.clear();
+}
+
+// HICMI_BUILDMAP_PLAIN: "1" one atomic add per pair, "0" the combining kernel, anything else the default - the plain
+// kernel: on the 16,000-bin bench map the combining kernel did not beat it
+constexpr bool kBuildmapPlainByDefault = true;
+static bool buildmap_plain()
+{
+    const char* env = getenv("HICMI_BUILDMAP_PLAIN");
+    if (env && !strcmp(env, "1")) return true;
+    if (env && !strcmp(env, "0")) return false;
+    return kBuildmapPlainByDefault;
+}
+
+int hicmi_map_begin(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, int64_t resolution)
+{
+    if (!c || !scaf_size || n_scaf < 1 || n_scaf > INT_MAX / 2) return fail(HICMI_EINVAL, "bad arguments");
+    if (resolution < 1) return fail(HICMI_EINVAL, "resolution %lld is below 1", (long long)resolution);
+    std::vector<int32_t> first((size_t)n_scaf);
+    int64_t m = 0;
+    for (int64_t s = 0; s < n_scaf; s++) {
+        if (scaf_size[s] < 0) return fail(HICMI_EINVAL, "scaffold %lld has the negative size %lld", (long long)s, (long long)scaf_size[s]);
+        first[(size_t)s] = (int32_t)m;
+        m += scaf_size[s] / resolution + (scaf_size[s] % resolution != 0);
+        if (m > 65536)
+            return fail(HICMI_EUNSUPPORTED, "resolution %lld needs more than 65536 bins: rank matrix is uint16 in this version",
+                        (long long)resolution);
+    }
+    if (m < 1) return fail(HICMI_EINVAL, "the scaffolds have no bins");
+    HIPCHK(hipSetDevice(c->device));
+    map_abandon(c);                                           // a begin without a finish is given up
+    hipError_t e = hipMalloc(&c->map_cells, sizeof(uint64_t) * (size_t)m * (size_t)m);
+    if (e != hipSuccess) {
+        c->map_cells = nullptr;
+        return fail(HICMI_ENOMEM, "hipMalloc(%lld bytes): %s", (long long)(8 * m * m), hipGetErrorString(e));
+    }
+    int rc = HICMI_OK;
+    e = hipMalloc((void**)&c->d_map_first, sizeof(int32_t) * (size_t)n_scaf);
+    if (e != hipSuccess) { c->d_map_first = nullptr; rc = fail(HICMI_ENOMEM, "hipMalloc: %s", hipGetErrorString(e)); }
+    if (!rc) rc = upload(c, c->d_map_first, first.data(), sizeof(int32_t) * (size_t)n_scaf);
+    if (!rc && (e = hipMemsetAsync(c->map_cells, 0, sizeof(uint64_t) * (size_t)m * (size_t)m, c->stream)) != hipSuccess)
+        rc = fail(HICMI_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e));
+    if (!rc && (e = sync_stream(c)) != hipSuccess) rc = fail(HICMI_EHIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
+    if (rc) { map_abandon(c); return rc; }
+    c->map_m = m; c->map_res = resolution; c->map_pairs = 0;
+    c->map_first = std::move(first);
+    c->map_size.assign(scaf_size, scaf_size + n_scaf);
+    return HICMI_OK;
+}
+
+// the four arrays of a chunk, one after the other in one device buffer (8-byte fields first)
+struct MapChunk { int64_t *pos_a, *pos_b; int32_t *scaf_a, *scaf_b; };
+static MapChunk map_chunk_at(unsigned char* base, int64_t n)
+{
+    MapChunk k;
+    k.pos_a = reinterpret_cast<int64_t*>(base);
+    k.pos_b = k.pos_a + n;
+    k.scaf_a = reinterpret_cast<int32_t*>(k.pos_b + n);
+    k.scaf_b = k.scaf_a + n;
+    return k;
+}
+
+int hicmi_map_add_pairs(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b,
+                        int64_t n)
+{
+    if (!c || n < 0 || (n > 0 && (!scaf_a || !pos_a || !scaf_b || !pos_b))) return fail(HICMI_EINVAL, "bad arguments");
+    if (!c->map_cells) return fail(HICMI_EINVAL, "hicmi_map_add_pairs without hicmi_map_begin");
+    const int64_t n_scaf = (int64_t)c->map_size.size();
+    for (int64_t p = 0; p < n; p++) {
+        if (scaf_a[p] < 0 || scaf_a[p] >= n_scaf || scaf_b[p] < 0 || scaf_b[p] >= n_scaf)
+            return fail(HICMI_EINVAL, "pair %lld names a scaffold outside 0 .. %lld", (long long)p, (long long)(n_scaf - 1));
+        if (pos_a[p] < 1 || pos_a[p] > c->map_size[(size_t)scaf_a[p]] || pos_b[p] < 1 || pos_b[p] > c->map_size[(size_t)scaf_b[p]])
+            return fail(HICMI_EINVAL, "pair %lld has a position outside 1 .. the size of its scaffold", (long long)p);
+    }
+    if (n == 0) return HICMI_OK;
+    HIPCHK(hipSetDevice(c->device));
+    // a HIP error from here on gives the build up: what was counted so far cannot be told
+    int rc = ensure(c->d_map_chunk, c->map_chunk_cap, 24 * n);
+    const MapChunk k = map_chunk_at(c->d_map_chunk, n);
+    if (!rc) rc = upload(c, k.pos_a, pos_a, sizeof(int64_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.pos_b, pos_b, sizeof(int64_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.scaf_a, scaf_a, sizeof(int32_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.scaf_b, scaf_b, sizeof(int32_t) * (size_t)n);
+    if (!rc) {
+        launch_buildmap_add(k.scaf_a, k.pos_a, k.scaf_b, k.pos_b, n, c->d_map_first, (int)n_scaf, c->map_res, (int)c->map_m,
+                            c->map_cells, buildmap_plain(), c->stream);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = sync_stream(c);
+        if (e != hipSuccess) rc = fail(HICMI_EHIP, "counting a chunk of pairs: %s", hipGetErrorString(e));
+    }
+    if (rc) { map_abandon(c); return rc; }
+    c->map_pairs += n;
+    return HICMI_OK;
+}
+
+// the counts become the context's matrix; `on` is the stream the conversion runs on (the driver uses one for all maps)
+static int map_install(hicmi_ctx* c, hipStream_t on, int64_t* pairs_out)
+{
+    launch_buildmap_finish(c->map_cells, (int)c->map_m, on);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(on);
+    if (e != hipSuccess) { map_abandon(c); return fail(HICMI_EHIP, "converting the counts: %s", hipGetErrorString(e)); }
+    double* kept = reinterpret_cast<double*>(c->map_cells);
+    c->map_cells = nullptr;                                   // ownership moves to the context below
+    const int64_t m = c->map_m, pairs = c->map_pairs;
+    map_abandon(c);
+    drop_matrix_state(c);
+    c->dC = kept; c->own_c = true; c->n = m; c->ldc = m;
+    int rc = alloc_sums(c);
+    if (rc) return rc;
+    rc = compute_sums(c);
+    if (rc) return rc;
+    if (pairs_out) *pairs_out = pairs;
+    return HICMI_OK;
+}
+
+int hicmi_map_finish(hicmi_ctx* c, int64_t* pairs_out)
+{
+    if (!c) return fail(HICMI_EINVAL, "NULL context");
+    if (!c->map_cells) return fail(HICMI_EINVAL, "hicmi_map_finish without hicmi_map_begin");
+    HIPCHK(hipSetDevice(c->device));
+    return map_install(c, c->stream, pairs_out);
+}
+
+int hicmi_build_maps(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
+                     int64_t n_res, const int64_t* resolution, hicmi_ctx* const* ctxs, int threads, int64_t* stats5)
+{
+    if (!path || !names_blob || !name_off || !scaf_size || !resolution || !ctxs || !stats5 || n_names < 1 || n_res < 1)
+        return fail(HICMI_EINVAL, "bad arguments");
+    for (int k = 0; k < 5; k++) stats5[k] = 0;
+    for (int64_t k = 0; k < n_res; k++) {
+        if (!ctxs[k] || ctxs[k]->device != ctxs[0]->device) return fail(HICMI_EINVAL, "contexts must share one device");
+        for (int64_t q = 0; q < k; q++) if (ctxs[q] == ctxs[k]) return fail(HICMI_EINVAL, "one context per resolution");
+    }
+    int64_t chunk_pairs = (int64_t)1 << 22;
+    if (const char* env = getenv("HICMI_BUILDMAP_CHUNK_PAIRS")) {
+        const long long v = atoll(env);
+        if (v < 1 || v > ((long long)1 << 28)) return fail(HICMI_EINVAL, "HICMI_BUILDMAP_CHUNK_PAIRS = %s outside 1 .. 2^28", env);
+        chunk_pairs = v;
+    }
+    hicmi_ctx* c0 = ctxs[0];
+    HIPCHK(hipSetDevice(c0->device));
+    // everything the call owns: two pinned chunks for the parser, two device chunks for the kernels
+    struct Owned {
+        unsigned char* pin[2] = {nullptr, nullptr}; unsigned char* dev[2] = {nullptr, nullptr};
+        hicmi_ctx* const* ctxs; int64_t n_res; bool keep = false;
+        ~Owned()
+        {
+            for (int b = 0; b < 2; b++) { if (pin[b]) (void)hipHostFree(pin[b]); free_dev(dev[b]); }
+            if (!keep) for (int64_t k = 0; k < n_res; k++) map_abandon(ctxs[k]);
+        }
+    } own;
+    own.ctxs = ctxs; own.n_res = n_res;
+    // begin on every context first: a resolution that cannot be built is refused before the file is read
+    for (int64_t k = 0; k < n_res; k++) {
+        int rc = hicmi_map_begin(ctxs[k], scaf_size, n_names, resolution[k]);
+        if (rc) return rc;
+    }
+    int64_t file_bytes = -1;
+    {
+        // no chunk holds more pairs than the file has room for (a line of six columns is at least 12 bytes)
+        FILE* fh = fopen(path, "rb");
+        if (!fh) return fail(HICMI_EINVAL, "cannot open %s", path);
+        if (fseeko(fh, 0, SEEK_END) == 0) file_bytes = (int64_t)ftello(fh);
+        fclose(fh);
+        if (file_bytes < 0) return fail(HICMI_EINVAL, "cannot tell the size of %s", path);
+        chunk_pairs = std::max<int64_t>(1, std::min(chunk_pairs, file_bytes / 12 + 1));
+    }
+    const size_t chunk_bytes = (size_t)chunk_pairs * 24;
+    for (int b = 0; b < 2; b++) {
+        HIPCHK(hipHostMalloc((void**)&own.pin[b], chunk_bytes, hipHostMallocDefault));
+        hipError_t e = hipMalloc((void**)&own.dev[b], chunk_bytes);
+        if (e != hipSuccess) { own.dev[b] = nullptr; return fail(HICMI_ENOMEM, "hipMalloc(%zu bytes): %s", chunk_bytes, hipGetErrorString(e)); }
+    }
+    const bool plain = buildmap_plain();
+    int64_t next = 0, n_here = 0, st[4];
+    // chunk t + 1 is parsed into the other pinned buffer while chunk t is uploaded and counted on c0's stream
+    auto parse = [&](int b) {
+        const MapChunk h = map_chunk_at(own.pin[b], chunk_pairs);
+        int rc = hicmi_parse_valid_pairs(path, names_blob, name_off, n_names, scaf_size, threads, next, chunk_pairs, h.scaf_a, h.pos_a,
+                                         h.scaf_b, h.pos_b, &n_here, &next, st);
+        if (!rc) { stats5[0] += st[0]; stats5[1] += st[1]; stats5[2] += st[2]; stats5[3] += st[3]; }
+        return rc;
+    };
+    int cur = 0;
+    int rc = parse(cur);
+    if (rc) return rc;
+    for (;;) {
+        const int64_t n = n_here;
+        if (n > 0) {
+            const MapChunk h = map_chunk_at(own.pin[cur], chunk_pairs), d = map_chunk_at(own.dev[cur], chunk_pairs);
+            HIPCHK(hipMemcpyAsync(d.pos_a, h.pos_a, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, c0->stream));
+            HIPCHK(hipMemcpyAsync(d.pos_b, h.pos_b, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, c0->stream));
+            HIPCHK(hipMemcpyAsync(d.scaf_a, h.scaf_a, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c0->stream));
+            HIPCHK(hipMemcpyAsync(d.scaf_b, h.scaf_b, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c0->stream));
+            for (int64_t k = 0; k < n_res; k++) {
+                hicmi_ctx* c = ctxs[k];
+                launch_buildmap_add(d.scaf_a, d.pos_a, d.scaf_b, d.pos_b, n, c->d_map_first, (int)n_names, c->map_res, (int)c->map_m,
+                                    c->map_cells, plain, c0->stream);
+                c->map_pairs += n;
+            }
+            HIPCHK(hipGetLastError());
+            stats5[4]++;
+        }
+        const bool last = next >= file_bytes;                      // the parser has taken the whole file
+        if (!last) rc = parse(cur ^ 1);
+        hipError_t e = hipStreamSynchronize(c0->stream);           // chunk t is counted: its two buffers are free again
+        if (rc) return rc;
+        if (e != hipSuccess) return fail(HICMI_EHIP, "counting a chunk of pairs: %s", hipGetErrorString(e));
+        if (last) break;
+        cur ^= 1;
+    }
+    // every chunk is counted on every map: from here on the contexts change
+    own.keep = true;
+    for (int64_t k = 0; k < n_res; k++) {
+        HIPCHK(hipSetDevice(ctxs[k]->device));
+        rc = map_install(ctxs[k], c0->stream, nullptr);
+        if (rc) { for (int64_t q = k + 1; q < n_res; q++) map_abandon(ctxs[q]); return rc; }
+    }
+    return HICMI_OK;
 }
 
 // Group support: extends the scaffold vote of assessChromosomeClustering (S2C:1001-1077) with the

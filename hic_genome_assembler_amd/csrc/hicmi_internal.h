@@ -505,6 +505,15 @@ static constexpr int REBIN_CHUNK = 1024;      // fine columns a workgroup of k_r
 void launch_rebin(const double* C, int64_t ld, int n, const int32_t* group_start, const int32_t* chunk_first, int m,
                   double* R, bool plain, hipStream_t s);
 
+// k_buildmap.hip: a raw map counted from read pairs (hicmi_map_*, hicmi_build_maps).  The four pair arrays
+// and first_bin (n_scaf entries) are device memory; counts: m x m unsigned 64-bit cells, of which the upper triangle is
+// counted; launch_buildmap_finish turns them in place into the symmetric matrix of doubles.
+static constexpr int BUILDMAP_SLICE = 2048;   // pairs a workgroup of k_buildmap_combine brings together
+static constexpr int BUILDMAP_SLOTS = 4096;   // slots of its hash table in LDS (12 bytes each)
+void launch_buildmap_add(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
+                         const int32_t* first_bin, int n_scaf, int64_t r, int m, void* counts, bool plain, hipStream_t s);
+void launch_buildmap_finish(void* cells, int m, hipStream_t s);
+
 // k_plot.hip
 void launch_plot_select(const double* C, int64_t ldc, const double* np_sum, const double* seq_sum, int kind,
                         const int32_t* order, int n_sel, int n_targets, struct SelectState* d_state, unsigned int* d_hist,

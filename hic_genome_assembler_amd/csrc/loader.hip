@@ -252,6 +252,55 @@ inline bool parse_pos(const char* p, const char* end, int64_t& out)
     const char* q = parse_i64(p, end, out, ok);
     return ok && q == end;
 }
+
+using NameMap = std::unordered_map<std::string_view, int32_t>;
+
+// names_blob / name_off[n_names + 1] -> index of every name (a name given twice keeps its first index)
+NameMap make_name_map(const char* names_blob, const int64_t* name_off, int64_t n_names)
+{
+    NameMap name_id;
+    name_id.reserve((size_t)n_names * 2);
+    for (int64_t i = 0; i < n_names; i++)
+        name_id.emplace(std::string_view(names_blob + name_off[i], (size_t)(name_off[i + 1] - name_off[i])), (int32_t)i);
+    return name_id;
+}
+
+// the starts of the columns 0 .. 6 of the line [p, le): returns how many there are (7 = "seven or more"); column k ends
+// at col[k + 1] - 1, the last one at le
+inline int split_cols(const char* p, const char* le, const char* col[7])
+{
+    int nc = 0;
+    col[nc++] = p;
+    for (const char* q = p; nc < 7;) {
+        const char* tab = (const char*)memchr(q, '\t', (size_t)(le - q));
+        if (!tab) break;
+        col[nc++] = tab + 1;
+        q = tab + 1;
+    }
+    return nc;
+}
+
+// a read-only mapping of a whole file; size 0 maps nothing
+struct MappedFile {
+    const char* data = nullptr; size_t size = 0;
+    ~MappedFile() { if (data) munmap((void*)data, size); }
+    // HICMI_OK, or the code recorded with hicmi::set_error
+    int open_path(const char* path)
+    {
+        int fd = open(path, O_RDONLY);
+        if (fd < 0) return hicmi::set_error(HICMI_EINVAL, (std::string("cannot open ") + path).c_str());
+        struct stat st;
+        if (fstat(fd, &st) != 0) { close(fd); return hicmi::set_error(HICMI_EINVAL, "fstat failed"); }
+        size = (size_t)st.st_size;
+        if (size == 0) { close(fd); return HICMI_OK; }
+        void* m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+        close(fd);
+        if (m == MAP_FAILED) { size = 0; return hicmi::set_error(HICMI_ENOMEM, "mmap failed"); }
+        data = (const char*)m;
+        madvise((void*)data, size, MADV_SEQUENTIAL);
+        return HICMI_OK;
+    }
+};
 }  // namespace
 
 extern "C" int hicmi_scan_valid_pairs(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names,
@@ -263,10 +312,7 @@ extern "C" int hicmi_scan_valid_pairs(const char* path, const char* names_blob, 
         (n_pairs > 0 && (!pair_a || !pair_b)))
         return err(HICMI_EINVAL, "bad arguments");
     *n_hits_out = 0; *n_lines_out = 0; *handle_out = nullptr;
-    std::unordered_map<std::string_view, int32_t> name_id;
-    name_id.reserve((size_t)n_names * 2);
-    for (int64_t i = 0; i < n_names; i++)
-        name_id.emplace(std::string_view(names_blob + name_off[i], (size_t)(name_off[i + 1] - name_off[i])), (int32_t)i);
+    const NameMap name_id = make_name_map(names_blob, name_off, n_names);
     std::unordered_map<uint64_t, int32_t> pair_id;
     pair_id.reserve((size_t)n_pairs * 2);
     for (int64_t i = 0; i < n_pairs; i++) {
@@ -307,14 +353,7 @@ extern "C" int hicmi_scan_valid_pairs(const char* path, const char* names_blob, 
             while (le > p && le[-1] == '\r') le--;
             // columns 0..5
             const char* col[7];
-            int nc = 0;
-            col[nc++] = p;
-            for (const char* q = p; nc < 7;) {
-                const char* tab = (const char*)memchr(q, '\t', (size_t)(le - q));
-                if (!tab) break;
-                col[nc++] = tab + 1;
-                q = tab + 1;
-            }
+            const int nc = split_cols(p, le, col);
             // the reference indexes cols[1] and cols[4] on every line (orientSmallScaffolds.py:168) and cols[2], cols[5]
             // only for a registered pair (:170): a 5-column line that names no such pair is accepted there, so it is here
             if (nc < 5) { bad[(size_t)t] = (int64_t)(p - data); return; }   // cols[4] missing: IndexError in the reference
@@ -362,6 +401,131 @@ extern "C" int hicmi_scan_fetch(void* handle, int32_t* pair_idx, int64_t* pos1, 
     if (!res->hits.empty() && (!pair_idx || !pos1 || !pos2)) return hicmi::set_error(HICMI_EINVAL, "NULL output");
     for (size_t i = 0; i < res->hits.size(); i++) { pair_idx[i] = res->hits[i].pair; pos1[i] = res->hits[i].p1; pos2[i] = res->hits[i].p2; }
     delete res;
+    return HICMI_OK;
+}
+
+// ---- chunked valid-pair parser (buildMap) -------------------------------------------------------------------
+// The scan above keeps the few lines of registered pairs; this one keeps every line whose two ends lie on known
+// scaffolds, `max_pairs` at a time, for the device to count.  A window of bytes sized for the pairs still wanted is cut at
+// line starts into one part per thread; the parts are taken in file order, and the part in which the quota is reached is
+// parsed again by one thread that stops right after the line of the last pair wanted.  So the pairs, the statistics and
+// next_byte of a call depend on the file and on max_pairs alone, never on the number of threads.
+namespace {
+struct PairRec { int32_t sa, sb; int64_t pa, pb; };
+struct PairPart { std::vector<PairRec> recs; int64_t lines = 0, unknown = 0, out_of_range = 0, bad = -1; };
+
+// Parses the whole lines of [begin, end) until `quota` pairs are kept; returns where it stopped (a line start, or end).
+// A malformed line sets part.bad to its offset and stops there.
+const char* parse_pair_lines(const char* data, const char* begin, const char* end, int64_t quota, const NameMap& name_id,
+                             const int64_t* scaf_size, PairPart& part)
+{
+    const char* p = begin;
+    std::string_view last_name[2];                     // the file is sorted by scaffold: the previous line's names first
+    int32_t last_id[2] = {-1, -1};
+    auto lookup = [&](int k, const char* s, const char* e) -> int32_t {
+        const std::string_view name(s, (size_t)(e - s));
+        if (last_name[k].data() && name == last_name[k]) return last_id[k];
+        const auto it = name_id.find(name);
+        last_name[k] = name;
+        return last_id[k] = it == name_id.end() ? -1 : it->second;
+    };
+    while (p < end && (int64_t)part.recs.size() < quota) {
+        const char* eol = (const char*)memchr(p, '\n', (size_t)(end - p));
+        if (!eol) eol = end;
+        const char* le = eol;
+        while (le > p && le[-1] == '\r') le--;
+        const char* col[7];
+        const int nc = split_cols(p, le, col);
+        int64_t p1 = 0, p2 = 0;
+        if (nc < 6 || !parse_pos(col[2], col[3] - 1, p1) || !parse_pos(col[5], nc >= 7 ? col[6] - 1 : le, p2)) {
+            part.bad = (int64_t)(p - data);
+            return p;
+        }
+        part.lines++;
+        const int32_t a = lookup(0, col[1], col[2] - 1), b = lookup(1, col[4], col[5] - 1);
+        if (a < 0 || b < 0) part.unknown++;
+        else if (p1 < 1 || p1 > scaf_size[a] || p2 < 1 || p2 > scaf_size[b]) part.out_of_range++;
+        else part.recs.push_back({a, b, p1, p2});
+        p = eol < end ? eol + 1 : end;
+    }
+    return p;
+}
+}  // namespace
+
+extern "C" int hicmi_parse_valid_pairs(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names,
+                                       const int64_t* scaf_size, int threads, int64_t first_byte, int64_t max_pairs,
+                                       int32_t* scaf_a, int64_t* pos_a, int32_t* scaf_b, int64_t* pos_b, int64_t* n_out,
+                                       int64_t* next_byte_out, int64_t* stats4)
+{
+    auto err = [](int code, const std::string& msg) { return hicmi::set_error(code, msg.c_str()); };
+    if (!path || !names_blob || !name_off || !n_out || !next_byte_out || !stats4 || n_names < 0 || (n_names > 0 && !scaf_size) ||
+        first_byte < 0 || max_pairs < 1 || !scaf_a || !pos_a || !scaf_b || !pos_b)
+        return err(HICMI_EINVAL, "bad arguments");
+    *n_out = 0; *next_byte_out = first_byte;
+    for (int k = 0; k < 4; k++) stats4[k] = 0;
+    const NameMap name_id = make_name_map(names_blob, name_off, n_names);
+    MappedFile file;
+    if (int rc = file.open_path(path)) return rc;
+    const size_t size = file.size;
+    const char* data = file.data;
+    if ((uint64_t)first_byte > size) return err(HICMI_EINVAL, "first_byte " + std::to_string(first_byte) + " is beyond the end of the file");
+    int T_max = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
+    T_max = std::max(1, std::min(T_max, 64));
+    int64_t kept = 0, lines = 0, unknown = 0, out_of_range = 0;
+    auto emit = [&](const PairPart& part) {
+        for (const PairRec& r : part.recs) { scaf_a[kept] = r.sa; pos_a[kept] = r.pa; scaf_b[kept] = r.sb; pos_b[kept] = r.pb; kept++; }
+        lines += part.lines; unknown += part.unknown; out_of_range += part.out_of_range;
+    };
+    auto malformed = [&](int64_t off) { return err(HICMI_EINVAL, "malformed valid-pair line at byte " + std::to_string(off)); };
+    size_t pos = (size_t)first_byte;
+    while (pos < size && kept < max_pairs) {
+        // a window for the pairs still wanted (a full 12-column line is about 60 bytes), closed at a line end
+        const int64_t want = max_pairs - kept;
+        size_t w_end = size;
+        if ((uint64_t)want < (size - pos) / 64) {
+            w_end = std::min(size, pos + std::max<size_t>((size_t)want * 64, (size_t)1 << 12));
+            const char* nl = w_end < size ? (const char*)memchr(data + w_end, '\n', size - w_end) : nullptr;
+            w_end = nl ? (size_t)(nl - data) + 1 : size;
+        }
+        const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)T_max, (w_end - pos) / 4096));
+        std::vector<size_t> cut((size_t)T + 1, w_end);
+        cut[0] = pos;
+        for (int t = 1; t < T; t++) {
+            size_t p = pos + (w_end - pos) / (size_t)T * (size_t)t;
+            while (p < w_end && data[p] != '\n') p++;
+            cut[(size_t)t] = p < w_end ? p + 1 : w_end;
+        }
+        std::vector<PairPart> part((size_t)T);
+        auto work = [&](int t) {
+            part[(size_t)t].recs.reserve((cut[(size_t)t + 1] - cut[(size_t)t]) / 40 + 16);
+            parse_pair_lines(data, data + cut[(size_t)t], data + cut[(size_t)t + 1], INT64_MAX, name_id, scaf_size, part[(size_t)t]);
+        };
+        {
+            std::vector<std::thread> pool;
+            for (int t = 1; t < T; t++) pool.emplace_back(work, t);
+            work(0);
+            for (auto& th : pool) th.join();
+        }
+        for (int t = 0; t < T && kept < max_pairs; t++) {
+            const PairPart& mine = part[(size_t)t];
+            if (kept + (int64_t)mine.recs.size() < max_pairs) {
+                if (mine.bad >= 0) return malformed(mine.bad);
+                emit(mine);
+                pos = cut[(size_t)t + 1];
+            } else {
+                // the quota is reached inside this part: once more, stopping right after the line of the last pair wanted
+                PairPart again;
+                again.recs.reserve((size_t)(max_pairs - kept));
+                const char* stop = parse_pair_lines(data, data + cut[(size_t)t], data + cut[(size_t)t + 1], max_pairs - kept, name_id,
+                                                    scaf_size, again);
+                if (again.bad >= 0) return malformed(again.bad);
+                emit(again);
+                pos = (size_t)(stop - data);
+            }
+        }
+    }
+    *n_out = kept; *next_byte_out = (int64_t)pos;
+    stats4[0] = lines; stats4[1] = kept; stats4[2] = unknown; stats4[3] = out_of_range;
     return HICMI_OK;
 }
 

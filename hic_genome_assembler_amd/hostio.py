@@ -115,6 +115,44 @@ def rebin_bins(binList, k):
     return coarse, np.asarray(group_start, dtype=np.int32)
 
 
+def read_scaffold_sizes(scaffSizeFile):
+    """(names, sizes in bp) of ``hicProScaffSizeFile`` (``name<TAB>size`` lines) in file order; a name given twice is
+    refused with ValueError."""
+    names, sizes, seen = [], [], set()
+    with open(scaffSizeFile) as fh:
+        for line in fh:
+            cols = line.strip("\r").strip("\n").split("\t")
+            if len(cols) >= 2:
+                if cols[0] in seen:
+                    raise ValueError("scaffold %s is listed twice in %s" % (cols[0], scaffSizeFile))
+                seen.add(cols[0])
+                names.append(cols[0])
+                sizes.append(int(cols[1]))
+    return names, np.asarray(sizes, dtype=np.int64)
+
+
+def count_bins(sizes, r):
+    """Bins of the grid of bins_from_sizes, without building it."""
+    return sum(-(-int(size) // int(r)) for size in sizes)
+
+
+def bins_from_sizes(scaffSizeFile, r):
+    """The bin grid HiC-Pro's ``build_matrix`` makes at bin size ``r``: the scaffolds in the order of
+    ``scaffSizeFile`` - a path, or the (names, sizes) it holds - a scaffold of length L cut from its own start into
+    ceil(L / r) bins [k r, min((k + 1) r, L)), IDs from 1 in that order.  So the grid at k r is rebin_bins of the grid at
+    r."""
+    r = int(r)
+    if r < 1:
+        raise ValueError("the resolution must be at least 1")
+    names, sizes = read_scaffold_sizes(scaffSizeFile) if isinstance(scaffSizeFile, (str, os.PathLike)) else scaffSizeFile
+    bins = []
+    for name, size in zip(names, sizes):
+        size = int(size)
+        for start in range(0, size, r):
+            bins.append(Bin(len(bins) + 1, name, start, min(start + r, size), 1., 0.))
+    return bins
+
+
 def write_biases(biasFile, bias):
     """HiC-Pro's ``*_iced.matrix.biases`` as initiateLoci reads it: one line per ``.bed`` line, ``repr`` of the bias or
     ``nan`` for a bin ICE took out."""

@@ -52,10 +52,10 @@ def parse_factors(text):
     return factors
 
 
-def output_paths(outDir, resolution):
-    """The files of one coarse resolution, keyed by the config keys they are written under (plus the directory)."""
+def output_paths(outDir, resolution, prefix="rebin"):
+    """The files of one resolution, keyed by the config keys they are written under (plus the directory)."""
     d = os.path.join(os.path.abspath(outDir), "res%d" % resolution)
-    stem = os.path.join(d, "rebin_%d" % resolution)
+    stem = os.path.join(d, "%s_%d" % (prefix, resolution))
     return {"dir": d, "resolution": str(resolution), "hicProBedFile": stem + "_abs.bed", "hicProRawMatrixFile": stem + ".matrix",
             "hicProMatrixFile": stem + "_iced.matrix", "hicProBiasFile": stem + "_iced.matrix.biases",
             "saveFilesDirectory": os.path.join(d, "out"), "savePlotsDirectory": os.path.join(d, "plots")}
@@ -84,8 +84,49 @@ def scaffold_counts(coarseBins):
     return len(per), sum(1 for c in per.values() if c == 1)
 
 
-def runPipeline(configFile, factors, outDir=None, balance=True, device=0):
+def write_resolution(ctx, binList, paths, configFile, v, ice, balance, line):
+    """The file set of one resolution from the context that owns its raw map (shared with buildMap): the bed file, the
+    raw ``.matrix``, unless ``balance`` is off the ``_iced.matrix`` and its ``.biases`` (iceNormalize.balanceResident with
+    the config's ``ice*`` settings; the context's matrix becomes the balanced map) and ``config.txt``.  ``line``: the start
+    of the line printed for it.  Returns (the five ICE columns of the summary, read pairs)."""
     from . import iceNormalize
+    for d in (paths["dir"], paths["saveFilesDirectory"], paths["savePlotsDirectory"]):
+        os.makedirs(d, exist_ok=True)
+    ids = [b.ID for b in binList]
+    res = int(paths["resolution"])
+    counts = ctx.contacts_host()
+    pairs = float(np.triu(counts).sum())
+    write_bed(paths["hicProBedFile"], binList)
+    write_iced_matrix(paths["hicProRawMatrixFile"], counts, ids)
+    del counts
+    line += ", read pairs %r" % pairs
+    ice_cols = ["NA"] * 5
+    if balance:
+        short = None
+        if ice["iceMinScaffoldSize"] is not None:
+            short = iceNormalize.short_scaffold_bins(binList, v["hicProScaffSizeFile"], ice["iceMinScaffoldSize"])
+        mask, (n_a, n_b, n_c), bias, iters, delta = iceNormalize.balanceResident(
+            ctx, short, ice["iceFilterLowPerc"], ice["iceMaxIter"], ice["iceEps"])
+        write_biases(paths["hicProBiasFile"], bias)
+        write_iced_matrix(paths["hicProMatrixFile"], ctx.contacts_host(), ids)
+        line += ", masked %d (scaffold size %d, no counts %d, low counts %d), iterations %d, final delta %r" % (
+            int(mask.sum()), n_a, n_b, n_c, iters, delta)
+        ice_cols = [str(n_a), str(n_b), str(n_c), str(iters), repr(delta)]
+        if iters >= ice["iceMaxIter"] and not delta < ice["iceEps"]:
+            print("WARNING... ICE did not converge in iceMaxIter = %d iterations at resolution %d (delta %r >= "
+                  "iceEps %r); the map of the last iteration is written" % (ice["iceMaxIter"], res, delta, ice["iceEps"]))
+    text = rewrite_config(configFile, {key: paths[key] for key in REWRITTEN_KEYS})
+    # a key the input config leaves out (buildMap needs no hicProRawMatrixFile) is added at the end
+    missing = [key for key in REWRITTEN_KEYS if key not in v or v[key] == ""]
+    if missing:
+        text += ("" if text.endswith("\n") or not text else "\n") + "".join("%s = %s\n" % (key, paths[key]) for key in missing)
+    with open(os.path.join(paths["dir"], "config.txt"), "w", newline="") as fh:
+        fh.write(text)
+    print(line)
+    return ice_cols, pairs
+
+
+def runPipeline(configFile, factors, outDir=None, balance=True, device=0):
     from . import run_hicAssembler as driver
     v = driver.readConfigFileToVariables(configFile)
     raw, ice = driver.part0Settings(v)
@@ -108,38 +149,13 @@ def runPipeline(configFile, factors, outDir=None, balance=True, device=0):
             for k, coarse, group_start in plans:
                 res = k * v["resolution"]
                 paths = output_paths(outDir, res)
-                for d in (paths["dir"], paths["saveFilesDirectory"], paths["savePlotsDirectory"]):
-                    os.makedirs(d, exist_ok=True)
-                ids = [b.ID for b in coarse]
                 n_scaf, n_one = scaffold_counts(coarse)
                 with _lib.Context(device) as ctx:
                     ctx.set_contacts_device(ptr, n, ld, keepalive=fine)
                     ctx.rebin(group_start)
-                    counts = ctx.contacts_host()
-                    pairs = float(np.triu(counts).sum())
-                    write_bed(paths["hicProBedFile"], coarse)
-                    write_iced_matrix(paths["hicProRawMatrixFile"], counts, ids)
-                    del counts
-                    line = "REBIN: factor %d, resolution %d, bins %d (scaffolds %d, of one bin %d), read pairs %r" % (
-                        k, res, len(coarse), n_scaf, n_one, pairs)
-                    ice_cols = ["NA"] * 5
-                    if balance:
-                        short = None
-                        if ice["iceMinScaffoldSize"] is not None:
-                            short = iceNormalize.short_scaffold_bins(coarse, v["hicProScaffSizeFile"], ice["iceMinScaffoldSize"])
-                        mask, (n_a, n_b, n_c), bias, iters, delta = iceNormalize.balanceResident(
-                            ctx, short, ice["iceFilterLowPerc"], ice["iceMaxIter"], ice["iceEps"])
-                        write_biases(paths["hicProBiasFile"], bias)
-                        write_iced_matrix(paths["hicProMatrixFile"], ctx.contacts_host(), ids)
-                        line += ", masked %d (scaffold size %d, no counts %d, low counts %d), iterations %d, final delta %r" % (
-                            int(mask.sum()), n_a, n_b, n_c, iters, delta)
-                        ice_cols = [str(n_a), str(n_b), str(n_c), str(iters), repr(delta)]
-                        if iters >= ice["iceMaxIter"] and not delta < ice["iceEps"]:
-                            print("WARNING... ICE did not converge in iceMaxIter = %d iterations at resolution %d (delta %r >= "
-                                  "iceEps %r); the map of the last iteration is written" % (ice["iceMaxIter"], res, delta, ice["iceEps"]))
-                with open(os.path.join(paths["dir"], "config.txt"), "w", newline="") as fh:
-                    fh.write(rewrite_config(configFile, {key: paths[key] for key in REWRITTEN_KEYS}))
-                print(line)
+                    line = "REBIN: factor %d, resolution %d, bins %d (scaffolds %d, of one bin %d)" % (
+                        k, res, len(coarse), n_scaf, n_one)
+                    ice_cols, pairs = write_resolution(ctx, coarse, paths, configFile, v, ice, balance, line)
                 rows.append([str(k), str(res), str(len(coarse)), str(n_scaf), str(n_one)] + ice_cols + [repr(pairs)])
     with open(os.path.join(os.path.abspath(outDir), "rebin_summary.tsv"), "w") as fh:
         fh.write("#" + "\t".join(SUMMARY_COLUMNS) + "\n")

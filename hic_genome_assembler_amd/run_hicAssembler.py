@@ -165,6 +165,11 @@ def part0Settings(v):
         if same:
             sys.exit("ERROR... hicProRawMatrixFile and {0} are the same file ({1}): -part0 writes {0} and would overwrite "
                      "its own input. Exiting...".format(key, raw))
+    return raw, iceSettings(v)
+
+
+def iceSettings(v):
+    """ICE's settings from the config dictionary (defaults: ICE_DEFAULTS); exits with a message when one is out of range."""
     s = dict(ICE_DEFAULTS)
     s.update({k: v[k] for k in ICE_DEFAULTS if k in v})
     if not 0. <= s["iceFilterLowPerc"] < 1.:
@@ -173,7 +178,7 @@ def part0Settings(v):
         sys.exit("ERROR... iceMaxIter must be at least 1. Exiting...")
     if not s["iceEps"] >= 0.:
         sys.exit("ERROR... iceEps must not be negative. Exiting...")
-    return raw, s
+    return s
 
 
 def ensureAllVariablesAreSet(varDict):

@@ -265,6 +265,53 @@ def write_hicpro(out_dir: str, layout: Layout, contacts, prefix: str = "synth",
     return paths
 
 
+def natural_key(name: str):
+    """Sort key of ``sort -V``, as HiC-Pro orders scaffold names: digit runs compare as numbers."""
+    import re
+    return [(0, int(part), "") if part.isdigit() else (1, 0, part) for part in re.split(r"(\d+)", name) if part]
+
+
+def draw_valid_pairs(layout: Layout, raw_counts, seed: int = 1, sort: bool = True):
+    """The read pairs behind a raw count map: for every cell (i, j), i <= j, of ``raw_counts`` that many pairs with one
+    end in bin i and one in bin j, the 1-based positions drawn uniformly inside the two bins and either mate first.
+    Returns (scaffold a, position a, scaffold b, position b) - scaffold indices into ``layout.scaffold_names`` - ordered as
+    HiC-Pro's merged allValidPairs file is (``sort``: by scaffold 1 in version order, position 1, scaffold 2, position 2)
+    or shuffled."""
+    rng = np.random.default_rng(seed + 15485863)
+    iu, ju = np.nonzero(np.triu(raw_counts))
+    rep = np.asarray(raw_counts)[iu, ju].astype(np.int64)
+    i, j = np.repeat(iu, rep), np.repeat(ju, rep)
+    width = (layout.stop - layout.start).astype(np.int64)
+    pi = layout.start[i] + 1 + np.floor(rng.random(len(i)) * width[i]).astype(np.int64)
+    pj = layout.start[j] + 1 + np.floor(rng.random(len(j)) * width[j]).astype(np.int64)
+    si, sj = layout.scaffold_of_bin[i].astype(np.int32), layout.scaffold_of_bin[j].astype(np.int32)
+    swap = rng.random(len(i)) < 0.5
+    sa, sb = np.where(swap, sj, si), np.where(swap, si, sj)
+    pa, pb = np.where(swap, pj, pi), np.where(swap, pi, pj)
+    if sort:
+        rank = np.empty(len(layout.scaffold_names), np.int64)
+        rank[sorted(range(len(rank)), key=lambda s: natural_key(layout.scaffold_names[s]))] = np.arange(len(rank))
+        order = np.lexsort((pb, rank[sb], pa, rank[sa]))
+    else:
+        order = rng.permutation(len(sa))
+    return sa[order], pa[order], sb[order], pb[order]
+
+
+def write_valid_pairs(path: str, layout: Layout, raw_counts, seed: int = 1, sort: bool = True) -> int:
+    """A HiC-Pro allValidPairs file (``read scaf1 pos1 strand1 scaf2 pos2 strand2 ...``, twelve columns) holding the pairs
+    of :func:`draw_valid_pairs`: the inverse of buildMap - counting the file at ``layout.resolution`` on the grid of the
+    layout's size file gives ``raw_counts`` back.  Returns the number of lines."""
+    sa, pa, sb, pb = draw_valid_pairs(layout, raw_counts, seed=seed, sort=sort)
+    names = layout.scaffold_names
+    with open(path, "w") as fh:
+        for k0 in range(0, len(sa), 1 << 16):
+            k1 = min(len(sa), k0 + (1 << 16))
+            fh.write("".join("read%d\t%s\t%d\t+\t%s\t%d\t-\t300\tf1\tf2\t42\t42\n" % (k0 + q, names[a], x, names[b], y)
+                             for q, (a, x, b, y) in enumerate(zip(sa[k0:k1].tolist(), pa[k0:k1].tolist(), sb[k0:k1].tolist(),
+                                                                  pb[k0:k1].tolist()))))
+    return len(sa)
+
+
 def write_config(path: str, hicpro_paths: dict, save_dir: str, plot_dir: str, resolution: int,
                  min_size: int = 5, modularity: float = 0.0, psig: float = 0.05,
                  n_scaffolds: int = 6, scan_scaffolds: int = 5, extra=None) -> str:

@@ -452,6 +452,53 @@ int hicmi_scan_valid_pairs(const char *path, const char *names_blob, const int64
                            int64_t *n_hits_out, int64_t *n_lines_out, void **handle_out);
 int hicmi_scan_fetch(void *handle, int32_t *pair_idx, int64_t *pos1, int64_t *pos2);
 
+/* ---- raw contact maps from the valid pairs: HiC-Pro's build_matrix at any bin size -----------------
+ * Scaffold s of the size file (names_blob / name_off / scaf_size, in the file's order) has ceil(size / resolution)
+ * bins from its own start; end (s, pos), pos 1-based, falls in bin first_bin[s] + (pos - 1) / resolution.  A pair with
+ * both ends in one bin adds 1 to C[i][i], any other pair 1 to C[i][j] and 1 to C[j][i]: the dense convention of
+ * hicmi_load_hicpro_matrix and hicmi_rebin, so the upper triangle with the diagonal sums to the pairs used.
+ *
+ * hicmi_parse_valid_pairs (host code, no GPU): the chunked form of hicmi_scan_valid_pairs that keeps every line.  It
+ * parses whole lines from first_byte (a line start; 0 at first) until max_pairs pairs are kept or the file ends, with
+ * `threads` host threads (0 = all); next_byte_out is where the next call starts and equals the file size when the file is
+ * done.  A call that reaches max_pairs stops right after the line of its last pair, so the kept pairs - in file order -
+ * the statistics and next_byte_out depend on the file and max_pairs alone, not on `threads`.  The four output arrays
+ * hold max_pairs entries.  stats4: lines read, pairs kept, lines naming a scaffold that is not in the name list
+ * (skipped), lines with a position below 1 or above the scaffold's size (skipped).  CRLF line ends, a last line without
+ * a newline, an empty file and lines of more than six columns are accepted.  HICMI_EINVAL with "malformed valid-pair
+ * line at byte <offset>": fewer than six columns (an empty line too) or a position that is not an integer.
+ *
+ * hicmi_map_begin / hicmi_map_add_pairs / hicmi_map_finish: one map, counted on the device from host arrays of pairs
+ * (scaffold indices and 1-based positions).  begin allocates m x m zeroed unsigned 64-bit counts as scratch - the
+ * context's matrix state is untouched until finish - and gives up a build that was open.  add_pairs checks every index
+ * and position on the host first (HICMI_EINVAL, nothing uploaded, the open build unchanged), uploads the arrays and
+ * counts the cell (min(i, j), max(i, j)) of every pair with one 64-bit integer atomic add per pair;
+ * HICMI_BUILDMAP_PLAIN=0 in the environment takes the combining kernel instead (the A/B: a workgroup brings the equal
+ * cells of its slice of pairs together in a hash table in LDS and issues one atomic add per distinct cell, carrying its
+ * multiplicity; =1 names the default).  Integer adds: both forms, any split into calls and any arrival order give the
+ * same bits.  finish converts the counts to doubles (exact below 2^53), mirrors the strict
+ * upper triangle into the lower one and installs the result like hicmi_rebin: owned by the context, ld = m, both row
+ * sums recomputed; pairs_out (may be NULL): the pairs added.  HICMI_EINVAL: add_pairs or finish without begin, a
+ * resolution below 1, a negative size, no bins; HICMI_EUNSUPPORTED: more than 65,536 bins.  After any error the
+ * context's matrix state is as before, and hicmi_destroy releases an open build.
+ *
+ * hicmi_build_maps: one pass over the pair file for n_res maps, ctxs[k] at resolution[k], all contexts distinct and on
+ * one device.  Chunks of pairs (2^22 by default, HICMI_BUILDMAP_CHUNK_PAIRS=<n> in the environment) come from
+ * hicmi_parse_valid_pairs into pinned memory, each is uploaded once and counted into every map, and the next chunk is
+ * parsed meanwhile.  stats5: the four of stats4 over the whole file, then the number of chunks.  Every resolution is
+ * checked before the file is read; on any error no context's matrix state has changed. */
+int hicmi_parse_valid_pairs(const char *path, const char *names_blob, const int64_t *name_off, int64_t n_names,
+                            const int64_t *scaf_size, int threads, int64_t first_byte, int64_t max_pairs,
+                            int32_t *scaf_a, int64_t *pos_a, int32_t *scaf_b, int64_t *pos_b,
+                            int64_t *n_out, int64_t *next_byte_out, int64_t *stats4);
+int hicmi_map_begin(hicmi_ctx *ctx, const int64_t *scaf_size, int64_t n_scaf, int64_t resolution);
+int hicmi_map_add_pairs(hicmi_ctx *ctx, const int32_t *scaf_a, const int64_t *pos_a,
+                        const int32_t *scaf_b, const int64_t *pos_b, int64_t n);
+int hicmi_map_finish(hicmi_ctx *ctx, int64_t *pairs_out);
+int hicmi_build_maps(const char *path, const char *names_blob, const int64_t *name_off, int64_t n_names,
+                     const int64_t *scaf_size, int64_t n_res, const int64_t *resolution, hicmi_ctx *const *ctxs,
+                     int threads, int64_t *stats5);
+
 /* ---- plot support -----------------------------------------------------------------------------
  * plotContactMap (plotContactMaps.py:15-91) colours every cell of an N x N matrix between two
  * numpy.percentile limits.  The matrix stays on the device: kind 0 = raw contacts (Part 2 plots,
