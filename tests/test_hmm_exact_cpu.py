@@ -1,6 +1,8 @@
 """The exact HMM references (hmm_exact_reference.py) without a GPU: the longdouble recursions against the sum over all
 2^T paths, the fp64 restatement (hmm_reference.py) against the longdouble recursions on the inputs of the device step
-tests, and the conditions those device tests rely on (test_gpu_hmm_steps.py), asserted on the same arrays."""
+tests, and the conditions those device tests rely on (test_gpu_hmm_steps.py), asserted on the same arrays.  Then the
+same for k-means, the seeding and the observation build (test_gpu_kmeans_steps.py): the longdouble references against
+exact arithmetic, the restatement against both, and the conditions on the inputs."""
 import itertools
 
 import mpmath
@@ -234,3 +236,235 @@ def test_restatement_is_close_to_the_longdouble_recursions():
     print("worst", worst)
     for k, e in worst.items():
         assert e <= 4 * RESTATEMENT_OBSERVED[k], (k, e)
+
+
+# ---- k-means, seeding and the observation build --------------------------------------------------------------------
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+def _same_bits(a, b):
+    return np.array_equal(_bits(a), _bits(b))
+
+
+def test_dist2_and_lloyd_in_longdouble_equal_exact_arithmetic():
+    """lloyd_ld against lloyd_exact (Python ints and Fractions) on the whole exact family, and dist2_ld against the sum
+    of squares in Fractions on rounded data."""
+    for name, (X, cen, max_iter, tol) in ex.exact_inputs().items():
+        e, l = ex.exact_expected(name), ex.lloyd_ld(X, cen, max_iter, tol)
+        assert (l.n_iter, l.rule) == (e.n_iter, e.rule), name
+        assert np.array_equal(l.labels, e.labels), name
+        assert np.array_equal(l.centers.astype(np.float64), e.centers) and float(l.inertia) == e.inertia, name
+        assert [float(s.shift) for s in l.steps] == e.shifts, name
+    rng = np.random.default_rng(23)
+    X, cen = rng.normal(size=(6, 5)), rng.normal(size=(2, 5))
+    d = ex.dist2_ld(X, cen)
+    from fractions import Fraction as F
+    for k in range(2):
+        for t in range(6):
+            want = sum((F(float(x)) - F(float(m))) ** 2 for x, m in zip(X[t], cen[k]))
+            hi = float(d[k, t])
+            got = F(hi) + F(float(d[k, t] - LD(hi)))          # a longdouble as the exact sum of two doubles
+            assert abs(got - want) <= 16 * F(ex.EPS_LD) * want
+    a = ex.assign_ld(X, cen)
+    assert np.array_equal(a.labels, d[1] < d[0]) and np.array_equal(a.margin, np.abs(d[1] - d[0]))
+
+
+def test_exact_cases_are_what_they_are_for():
+    # the tie rows are exactly equidistant, stay in cluster 0, and nothing moves
+    for T in (21, 22, 23, 24):
+        for D in (2, 65, 257):
+            X, cen, ties = ex.tie_case(T, D)
+            d = ex.dist2_ld(X, cen)
+            assert np.all(d[0, ties] == 13) and np.all(d[1, ties] == 13)
+            others = np.setdiff1d(np.arange(T), ties)
+            assert np.all(d[0, others] != d[1, others])
+            assert {t % 4 for t in ties} == {0, 1, 2, 3} and T - 1 in ties
+            assert D == 2 or (X[:, 1:D - 1] == 0).all() and X[:, D - 1].any()
+            e = ex.lloyd_exact(X, cen, 300, -1.)
+            assert (e.n_iter, e.rule) == (2, "strict") and not e.labels[ties].any() and _same_bits(e.centers, cen)
+            assert e.labels.sum() == T - 16 and e.shifts == [0., 0.]
+            e = ex.lloyd_exact(X, cen, 300, 0.)
+            assert (e.n_iter, e.rule) == (1, "tol") and not e.labels[ties].any()
+    # all rows identical: labels 0, cluster 1 empty and unmoved, inertia 0, strict at the second iteration
+    X, cen = ex.identical_case(1025, 3)
+    e = ex.lloyd_exact(X, cen, 300, -1.)
+    assert (e.n_iter, e.rule, e.inertia) == (2, "strict", 0.) and not e.labels.any() and _same_bits(e.centers, cen)
+    assert e.ties == 2 * 1025
+    # a cluster that starts empty: its center comes back as it went in, the shift is the other center's alone
+    X, _far = ex.exact_blobs(32, 5, 0)
+    cen = np.vstack([X[0], np.full(5, 1000.1)])
+    e = ex.lloyd_exact(X, cen, 300, 0.)
+    assert not e.labels.any() and _same_bits(e.centers[1], cen[1]) and (e.n_iter, e.rule) == (2, "strict")
+    assert _same_bits(e.centers[0], X.sum(axis=0) / 64) and e.shifts[0] == float(((X.sum(axis=0) / 64 - X[0]) ** 2).sum())
+    X = ex.exact_scaled(12, 2, 1)
+    e = ex.lloyd_exact(X, X[[4, 4]], 1, 0.)
+    assert _same_bits(e.centers[1], X[4]) and not e.history[0].count(1) and e.ties >= 12
+    assert ex.lloyd_exact(X, X[[4, 4]], 300, 0.).n_iter > 2            # ... and the run goes on from there
+
+
+def test_stop_sequence_is_exact_and_changes_labels_every_iteration():
+    S = ex.stop_case()[:, :3]
+    cen = S[list(ex.STOP_ROWS)]
+    full = ex.lloyd_exact(S, cen, 300, 0.)
+    assert (full.n_iter, full.rule, full.ties) == (6, "strict", 0)
+    assert all(a > b for a, b in zip(full.shifts, full.shifts[1:])) and full.shifts[-1] == 0
+    assert all(full.history[k] != full.history[k + 1] for k in range(4)) and full.history[4] == full.history[5]
+    for k in (1, 2, 3):                                      # tol equal to a shift stops there, the next double below not
+        e = ex.lloyd_exact(S, cen, 300, full.shifts[k])
+        assert (e.n_iter, e.rule) == (k + 1, "tol")
+        e = ex.lloyd_exact(S, cen, 300, np.nextafter(full.shifts[k], 0.))
+        assert e.n_iter == k + 2 and e.rule == ("tol" if full.shifts[k + 1] > 0 else "strict")
+    for m in (1, 2, 3):                                      # the labels returned are not those the centers were made of
+        e = ex.lloyd_exact(S, cen, m, 0.)
+        assert (e.n_iter, e.rule) == (m, "max_iter")
+        assert list(e.labels) == full.history[m] and list(e.labels) != full.history[m - 1]
+
+
+def test_chunk_shapes_hit_every_edge_of_the_column_pass():
+    shapes = {s: (ex.col_chunks(*s),) + ex.col_shape(*s) for s in ex.CHUNK_SHAPES}
+    assert shapes[(5, 3)] == (5, 1, 5)                       # T smaller than the chunk count: one row per chunk
+    R, rows_per, Rr = shapes[(1025, 3)]
+    assert R == 1024 and 1025 - (Rr - 1) * rows_per == 1     # the 1024 cap; a last chunk of exactly one row
+    assert shapes[(16385, 3)][0] == 1024 and shapes[(16385, 3)][1] == 17
+    R, rows_per, Rr = shapes[(700, 4097)]
+    assert (4097 + 255) // 256 == 17 and Rr < R              # 17 column blocks; chunks that hold no rows
+    assert {D for _T, D in ex.CHUNK_SHAPES} >= {255, 256, 257}
+    assert all(T * D <= 3_000_000 for T, D in ex.CHUNK_SHAPES)
+    for T, D in ex.CHUNK_SHAPES:
+        X, cen, labels, want = ex.chunk_case(T, D)
+        rows_per, Rr = ex.col_shape(T, D)
+        for ch in range(Rr):                                 # the other cluster at both ends of every chunk
+            t0, t1 = ch * rows_per, min(T, (ch + 1) * rows_per)
+            assert labels[t0] == labels[t1 - 1] and (t1 - t0 < 3 or labels[t0] != labels[t0 + 1])
+        a = ex.assign_ld(X, cen)
+        assert np.array_equal(a.labels, labels) and float(a.margin.min()) >= 4 * 64 * 64
+        assert np.abs(X).max() == 64 and labels.any() and not labels.all()
+
+
+def test_kmeans_inputs_meet_the_conditions_of_the_device_tests():
+    """On every rounded case and every iteration of its longdouble trajectory at most 1 % of the rows have a margin
+    within the distance bound (none has, and by a factor of 1e3: the trajectory is the device's own); every shift is
+    further from the chosen tol than its bound; the three stop rules all occur."""
+    rules = set()
+    for name, c in ex.km_cases().items():
+        r = ex.km_reference(name)
+        X = ex.view(c)
+        for s in r.full.steps + [r.full.final]:
+            a = s.assign if hasattr(s, "assign") else s
+            assert np.all(a.margin > 1e3 * ex.label_bound(c.D, a)), name
+        for run, (max_iter, tol, n_iter, rule) in r.runs.items():
+            rules.add(rule)
+            got = ex.lloyd_ld(X, X[c.rows], max_iter, tol)
+            assert (got.n_iter, got.rule) == (n_iter, rule), (name, run)
+            for i, s in enumerate(got.steps):
+                _m, scale, _n = ex.cluster_means_ld(X, s.assign.labels, s.centers)
+                assert abs(float(s.shift) - tol) > 1e3 * ex.shift_bound(c, s, scale), (name, run, i)
+    assert rules == {"strict", "tol", "max_iter"}
+    assert sum("tol" in ex.km_reference(n).runs for n in ex.km_cases()) >= 6
+    c = ex.km_cases()["overlap-1024x65"]
+    assert ex.km_reference(c.name).full.n_iter >= 20          # the overlapping Gaussians do take many iterations
+    X = ex.km_cases()["sparse-600x257"].X
+    assert np.mean(X == 0) > .2 and len(np.unique(X)) < X.size // 3      # exact zeros, many equal cells
+    assert ex.km_cases()["overlap-prefix-1025x2"].X.shape[1] == 5 and ex.km_cases()["sparse-prefix-600x64"].X.shape[1] == 257
+
+
+def test_seeding_inputs_have_margins():
+    """For every draw of the seeding grid the distance of a rand_vals entry to the nearest cumulative sum it could cross
+    and the gap between the two candidates' potentials exceed 1e3 times the bound; the restatement picks the same rows."""
+    for name in ex.SEED_CASES:
+        c = ex.km_cases()[name]
+        X = ex.view(c)
+        for g in ex.SEED_GRID:
+            r = ex.kmeanspp_rows_ld(X, np.random.default_rng(list(g)))
+            bound = ex.seed_bound(c.T, c.D, r.pot)
+            assert r.cdf_margin > 1e3 * bound and r.gap > 1e3 * bound, (name, g)
+            assert ref.kmeans_plusplus_rows(X, np.random.default_rng(list(g))) == r.rows, (name, g)
+    X = ex.clamp_case()
+    assert ex.clamp_overshoot(X[:, 0] ** 2) >= 2             # searchsorted does return T here
+    r = ex.kmeanspp_rows_ld(X, ex.FixedDraws(0, ex.CLAMP_DRAWS))
+    assert r.cand[0] == len(X) - 1 and min(r.cdf_margin, r.gap) > 1e3 * ex.seed_bound(len(X), 1, r.pot)
+    assert ref.kmeans_plusplus_rows(X, ex.FixedDraws(0, ex.CLAMP_DRAWS)) == r.rows
+
+
+def test_restatement_kmeans_against_the_references():
+    """hmm_reference.kmeans_lloyd bit for bit on the exact family; on rounded data its labels, iterations and stop at
+    every run of the device tests, its centers to T eps64 scale, its inertia to (T + ceil(D / 64) + 9) eps64; dist2 to
+    the distance bound."""
+    for name, (X, cen, max_iter, tol) in ex.exact_inputs().items():
+        e = ex.exact_expected(name)
+        c_r, l_r, in_r, it_r = ref.kmeans_lloyd(X, cen, max_iter, tol)
+        assert _same_bits(c_r, e.centers) and np.array_equal(l_r, e.labels) and it_r == e.n_iter, name
+        assert _bits([in_r])[0] == _bits([e.inertia])[0], name
+    for T, D in ex.CHUNK_SHAPES:
+        X, cen, labels, want = ex.chunk_case(T, D)
+        c_r, l_r, _in, it_r = ref.kmeans_lloyd(X.astype(np.float64), cen, 1, 0.)
+        assert _same_bits(c_r, want) and np.array_equal(l_r, labels) and it_r == 1, (T, D)
+    worst = 0.
+    for name, c in ex.km_cases().items():
+        r = ex.km_reference(name)
+        X = ex.view(c)
+        for run, (max_iter, tol, n_iter, rule) in r.runs.items():
+            c_r, l_r, in_r, it_r = ref.kmeans_lloyd(X, X[c.rows], max_iter, tol)
+            want = ex.lloyd_ld(X, X[c.rows], max_iter, tol)
+            assert it_r == n_iter and np.array_equal(l_r, want.labels), (name, run)
+            made_of = want.labels if rule == "strict" else want.steps[-1].assign.labels
+            mean, scale, _n = ex.cluster_means_ld(X, made_of, want.steps[-1].centers)
+            err = float((np.abs(c_r - mean) / (ex.EPS64 * scale)).max())
+            worst = max(worst, err)
+            assert err <= c.T, (name, run, err)
+            at = ex.assign_ld(X, c_r)
+            assert abs(in_r - at.mind.sum()) <= (c.T + -(-c.D // 64) + 9) * ex.EPS64 * float(at.mind.sum()), (name, run)
+        d = ref.dist2(X, c.rows)
+        want = ex.dist2_ld(X, X[c.rows])
+        assert np.all(np.abs(d - want) <= (c.D + 3) * ex.EPS64 * want), name    # numpy: a pairwise sum of D terms at most
+    print("restatement centers: worst error %.3g eps64 scale" % worst)
+
+
+def test_log_similarity_in_longdouble():
+    """log_similarity_ld against mpmath on the cells of a small window, exact zeros kept, and the fp64 restatement
+    within 2 ulp of its correctly rounded values."""
+    C, order = ex.sparse_map(ex.OBS_N)
+    assert np.mean(C == 0) > .25 and not np.array_equal(order, np.arange(ex.OBS_N))
+    A = ref.log_similarity(C, order)
+    n_zero = 0
+    for c, p in ex.OBS_WINDOWS:
+        want, s = ex.log_similarity_ld(C, order, c, p)
+        assert want.shape == (ex.OBS_N - c, p - c)
+        assert np.all(want[s == 0] == 0) and np.all(want[s != 0] > 0)
+        n_zero += int((s == 0).sum())
+        got = A[c:, c:p]
+        assert np.all(got[s == 0] == 0)
+        assert np.abs(_bits(got) - _bits(want.astype(np.float64))).max() <= 2, (c, p)
+    assert n_zero > 1000
+    want, s = ex.log_similarity_ld(C, order, 290, 295)
+    with mpmath.workdps(40):
+        for i in range(10):
+            for j in range(5):
+                if s[i, j] != 0:
+                    exact = mpmath.log10(mpmath.mpf(float(s[i, j] + 1.0)))
+                    assert abs(want[i, j] - ex.to_ld(exact)) <= 4 * ex.EPS_LD * want[i, j]
+    assert {p - c for c, p in ex.OBS_WINDOWS} >= {1, 255, 256, 257}
+    assert {c for c, _p in ex.OBS_WINDOWS} >= {0, ex.OBS_N - 1}
+
+
+def test_best_of_ten_restarts_has_one_winner():
+    """The inputs of the device's initialisation test: the restarts end in different optima, the winner is not the first
+    restart, its inertia is below every different one by 1e3 times what an fp64 inertia can be wrong by, every seeding
+    margin and every shift's distance from tol are 1e3 bounds or more; the restatement picks the same winner."""
+    for name, seed, fit in ex.INIT_CASES:
+        c, r = ex.km_cases()[name], ex.init_reference(name, seed, fit)
+        X = ex.view(c)
+        best = r.inertia[r.winner]
+        others = [v for v in r.inertia if abs(v - best) > 1e-9 * best]
+        assert r.winner > 0 and len(others) >= 3, name
+        assert min(others) - best > 1e3 * (c.T + -(-c.D // 64) + 9) * ex.EPS64 * best, name
+        for seeds, run in r.runs:
+            bound = ex.seed_bound(c.T, c.D, seeds.pot)
+            assert seeds.cdf_margin > 1e3 * bound and seeds.gap > 1e3 * bound, name
+            for s in run.steps:
+                _m, scale, _n = ex.cluster_means_ld(X, s.assign.labels, s.centers)
+                assert abs(float(s.shift) - r.tol) > 1e3 * ex.shift_bound(c, s, scale), name
+                assert np.all(s.assign.margin > 1e3 * ex.label_bound(c.D, s.assign)), name
+        means, _covars, _iters = ref.init_params(X, seed, fit)
+        assert np.all(np.abs(means - r.means) <= c.T * ex.EPS64 * r.scale), name
