@@ -91,6 +91,10 @@ SIGNATURES = {
     "hicmi_map_add_pairs": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, c_i64]),
     "hicmi_map_finish": (ctypes.c_int, [_vp, ctypes.POINTER(c_i64)]),
     "hicmi_build_maps": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, c_i64, _vp, _vp, ctypes.c_int, _vp]),
+    "hicmi_map_begin_lifted": (ctypes.c_int, [_vp, _vp, c_i64, _vp, _vp, _vp, _vp, c_i64, c_i64]),
+    "hicmi_pair_stats": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, c_i64, _vp, c_i64, _vp, _vp, _vp, _vp, c_i64, _vp, _vp, _vp, _vp]),
+    "hicmi_lift_maps": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, _vp, _vp, _vp, _vp, c_i64, c_i64, _vp, _vp,
+                                       ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     "hicmi_plot_percentiles": (ctypes.c_int, [_vp, ctypes.c_int, _vp, c_i64, _vp, c_i64, _vp]),
     "hicmi_plot_downsample": (ctypes.c_int, [_vp, ctypes.c_int, _vp, c_i64, c_i64, _vp]),
     "hicmi_p2_insert_all_multi": (ctypes.c_int, [c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -269,6 +273,56 @@ def build_maps(path, names, sizes, resolutions, ctxs, threads: int = 0):
     return tuple(int(v) for v in stats)
 
 
+def _lift_tables(sizes, lift_seq, lift_off, lift_rev, seq_sizes):
+    """The lift tables of DESIGN.md 9m as the library takes them: (scaffold sizes, lift_seq int32, lift_off int64,
+    lift_rev uint8, sequence sizes), one entry per scaffold and one size per sequence."""
+    size = np.ascontiguousarray(sizes, dtype=np.int64)
+    seq = np.ascontiguousarray(lift_seq, dtype=np.int32)
+    off = np.ascontiguousarray(lift_off, dtype=np.int64)
+    rev = np.ascontiguousarray(lift_rev, dtype=np.uint8)
+    seq_size = np.ascontiguousarray(seq_sizes, dtype=np.int64)
+    if size.ndim != 1 or not (seq.shape == off.shape == rev.shape == size.shape) or seq_size.ndim != 1:
+        raise ValueError("one lift_seq, lift_off and lift_rev per scaffold size, and a vector of sequence sizes")
+    return size, seq, off, rev, seq_size
+
+
+def new_pair_stats(n_seq):
+    """Zeroed (decay[256], seq_cis[n_seq], seq_trans[n_seq], unlifted[1]) for Context.pair_stats and lift_maps to add to."""
+    return (np.zeros(256, np.uint64), np.zeros(int(n_seq), np.uint64), np.zeros(int(n_seq), np.uint64), np.zeros(1, np.uint64))
+
+
+def _pair_stats_into(into, n_seq):
+    if into is None:
+        return new_pair_stats(n_seq)
+    decay, cis, trans, unlifted = into
+    for a, shape in ((decay, (256,)), (cis, (n_seq,)), (trans, (n_seq,)), (unlifted, (1,))):
+        if a.dtype != np.uint64 or a.shape != shape or not a.flags.c_contiguous or not a.flags.writeable:
+            raise ValueError("into must be what new_pair_stats(n_seq) returns")
+    return into
+
+
+def lift_maps(path, names, sizes, lift_seq, lift_off, lift_rev, seq_sizes, resolutions, ctxs, threads: int = 0, into=None):
+    """build_maps in the coordinates of an assembly (hicmi_lift_maps): one pass over the pair file for the
+    lifted maps at every resolution - ``ctxs[k]`` receives the one at ``resolutions[k]`` - and the statistics of the
+    pairs, added to ``into`` (new_pair_stats; None: fresh ones).  Returns ((lines, used, unknown_scaffold, out_of_range,
+    chunks), (decay, seq_cis, seq_trans, unlifted))."""
+    blob, off = _name_blob(names)
+    size, seq, loff, rev, seq_size = _lift_tables(sizes, lift_seq, lift_off, lift_rev, seq_sizes)
+    res = np.ascontiguousarray(resolutions, dtype=np.int64)
+    if size.shape != (len(names),) or res.ndim != 1 or len(res) != len(ctxs) or not len(ctxs):
+        raise ValueError("one size per scaffold name and one context per resolution")
+    out = _pair_stats_into(into, len(seq_size))
+    handles = (_vp * len(ctxs))(*[c._h for c in ctxs])
+    stats = np.zeros(5, np.int64)
+    _check(load().hicmi_lift_maps(os.fsencode(path), blob, _ptr(off), len(names), _ptr(size), _ptr(seq), _ptr(loff), _ptr(rev),
+                                  _ptr(seq_size), len(seq_size), len(res), _ptr(res), handles, int(threads), _ptr(stats),
+                                  _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3])))
+    for c in ctxs:
+        c.n = c.contacts_device()[1]
+        c._keepalive = None
+    return tuple(int(v) for v in stats), out
+
+
 def hypergeom_sf(x, M, n, N) -> float:
     """hyper_geom(x, M, n, N) of scaffoldToChromosomes.py:352-368, evaluated by libhicmi's host code."""
     return float(load().hicmi_hypergeom_sf(int(x), int(M), int(n), int(N)))
@@ -399,6 +453,28 @@ class Context:
         if size.ndim != 1:
             raise ValueError("sizes must be a vector")
         _check(self._lib.hicmi_map_begin(self._h, _ptr(size), len(size), int(resolution)))
+
+    def map_begin_lifted(self, sizes, lift_seq, lift_off, lift_rev, seq_sizes, resolution):
+        """Open the count of a map of the assembled genome (hicmi_map_begin_lifted): scaffold s lies in
+        sequence lift_seq[s] (-1: dropped) at offset lift_off[s], reversed where lift_rev[s]; sequence q has
+        ceil(seq_sizes[q] / resolution) bins.  map_add_pairs still takes scaffold indices and positions."""
+        size, seq, off, rev, seq_size = _lift_tables(sizes, lift_seq, lift_off, lift_rev, seq_sizes)
+        _check(self._lib.hicmi_map_begin_lifted(self._h, _ptr(size), len(size), _ptr(seq), _ptr(off), _ptr(rev), _ptr(seq_size),
+                                                len(seq_size), int(resolution)))
+
+    def pair_stats(self, scaf_a, pos_a, scaf_b, pos_b, sizes, lift_seq, lift_off, lift_rev, seq_sizes, into=None):
+        """The statistics of the pairs under the lift (hicmi_pair_stats), added to ``into``
+        (new_pair_stats; None: fresh ones): (decay[256], seq_cis, seq_trans, unlifted[1]) as uint64."""
+        sa, sb = np.ascontiguousarray(scaf_a, dtype=np.int32), np.ascontiguousarray(scaf_b, dtype=np.int32)
+        pa, pb = np.ascontiguousarray(pos_a, dtype=np.int64), np.ascontiguousarray(pos_b, dtype=np.int64)
+        if not (sa.ndim == 1 and sa.shape == sb.shape == pa.shape == pb.shape):
+            raise ValueError("the four arrays must be vectors of one length")
+        size, seq, off, rev, seq_size = _lift_tables(sizes, lift_seq, lift_off, lift_rev, seq_sizes)
+        out = _pair_stats_into(into, len(seq_size))
+        _check(self._lib.hicmi_pair_stats(self._h, _ptr(sa), _ptr(pa), _ptr(sb), _ptr(pb), len(sa), _ptr(size), len(size), _ptr(seq),
+                                          _ptr(off), _ptr(rev), _ptr(seq_size), len(seq_size), _ptr(out[0]), _ptr(out[1]),
+                                          _ptr(out[2]), _ptr(out[3])))
+        return out
 
     def map_add_pairs(self, scaf_a, pos_a, scaf_b, pos_b):
         """Count the pairs (scaffold index, 1-based position) x 2 into the open map (hicmi_map_add_pairs)."""

@@ -171,6 +171,12 @@ struct hicmi_ctx {
     int32_t* d_map_first = nullptr;
     std::vector<int32_t> map_first; std::vector<int64_t> map_size;
     unsigned char* d_map_chunk = nullptr; int64_t map_chunk_cap = 0;
+    // a lifted build (hicmi_map_begin_lifted) keeps its lift tables on the device as well (map_lift.seq !=
+    // nullptr): map_first then describes the assembled sequences, map_size still the scaffolds; map_lift_seq is the host's
+    // copy of the sequence of every scaffold.  d_stat_*: the tables and counters of a hicmi_pair_stats call
+    unsigned char* d_map_lift = nullptr; LiftTables map_lift; std::vector<int32_t> map_lift_seq;
+    unsigned char* d_stat_lift = nullptr; int64_t stat_lift_cap = 0;
+    unsigned long long* d_stat_out = nullptr; int64_t stat_out_cap = 0;
     // plot support
     int32_t* d_plot_order = nullptr; int64_t plot_order_cap = 0;
     unsigned char* d_plot_work = nullptr; int64_t plot_work_cap = 0;
@@ -418,6 +424,7 @@ int hicmi_destroy(hicmi_ctx* c)
     free_dev(c->d_ice); free_dev(c->d_ice_mask);
     free_dev(c->d_plot_order); free_dev(c->d_plot_work); free_dev(c->d_plot_img);
     free_dev(c->map_cells); free_dev(c->d_map_first); free_dev(c->d_map_chunk);
+    free_dev(c->d_map_lift); free_dev(c->d_stat_lift); free_dev(c->d_stat_out);
     for (auto& sl : c->hslot) free_dev(sl.d_x);
     free_dev(c->d_hmulti); free_dev(c->d_horder); free_dev(c->d_hwork); free_dev(c->d_hlab); free_dev(c->d_hbt);
     free_dev(c->d_hpart); free_dev(c->d_hsmall); free_dev(c->d_hhist); free_dev(c->d_hst);
@@ -635,8 +642,10 @@ static void map_abandon(hicmi_ctx* c)
 {
     free_dev(c->map_cells); c->map_cells = nullptr;
     free_dev(c->d_map_first); c->d_map_first = nullptr;
+    free_dev(c->d_map_lift); c->d_map_lift = nullptr;
+    c->map_lift = LiftTables();
     c->map_m = 0; c->map_res = 0; c->map_pairs = 0;
-    c->map_first.clear(); c->map_size.clear();
+    c->map_first.clear(); c->map_size.clear(); c->map_lift_seq.clear();
 }
 
 // HICMI_BUILDMAP_PLAIN: "1" one atomic add per pair, "0" the combining kernel, anything else the default - the plain
@@ -650,21 +659,67 @@ static bool buildmap_plain()
     return kBuildmapPlainByDefault;
 }
 
-int hicmi_map_begin(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, int64_t resolution)
+// HICMI_LIFTMAP_PLAIN: the same choice for a lifted build, read per call
+constexpr bool kLiftmapPlainByDefault = true;
+static bool liftmap_plain()
+{
+    const char* env = getenv("HICMI_LIFTMAP_PLAIN");
+    if (env && !strcmp(env, "1")) return true;
+    if (env && !strcmp(env, "0")) return false;
+    return kLiftmapPlainByDefault;
+}
+
+// the lift of a build as the caller hands it over: host arrays, one entry per scaffold, and the sequences' sizes
+struct LiftHost { const int32_t* seq; const int64_t* off; const uint8_t* rev; const int64_t* seq_size; int64_t n_seq; };
+
+static int lift_check(const int64_t* scaf_size, int64_t n_scaf, const LiftHost& lift)
+{
+    if (!lift.seq || !lift.off || !lift.rev || !lift.seq_size || lift.n_seq < 1 || lift.n_seq > INT_MAX / 4)
+        return fail(HICMI_EINVAL, "bad arguments");
+    char msg[256];
+    if (lift_check_tables(scaf_size, n_scaf, lift.seq, lift.off, lift.rev, lift.seq_size, lift.n_seq, msg, sizeof(msg)))
+        return fail(HICMI_EINVAL, "%s", msg);
+    return HICMI_OK;
+}
+
+// the lift tables as one device image of 21 bytes per scaffold, 8-byte fields first: [off][scaf_size][seq][rev]
+static int lift_upload(hicmi_ctx* c, unsigned char* image, const int64_t* scaf_size, int64_t n_scaf, const LiftHost& lift,
+                       LiftTables* out)
+{
+    int64_t* d_off = reinterpret_cast<int64_t*>(image);
+    int64_t* d_size = d_off + n_scaf;
+    int32_t* d_seq = reinterpret_cast<int32_t*>(d_size + n_scaf);
+    uint8_t* d_rev = reinterpret_cast<uint8_t*>(d_seq + n_scaf);
+    int rc = upload(c, d_off, lift.off, sizeof(int64_t) * (size_t)n_scaf);
+    if (!rc) rc = upload(c, d_size, scaf_size, sizeof(int64_t) * (size_t)n_scaf);
+    if (!rc) rc = upload(c, d_seq, lift.seq, sizeof(int32_t) * (size_t)n_scaf);
+    if (!rc) rc = upload(c, d_rev, lift.rev, (size_t)n_scaf);
+    if (rc) return rc;
+    out->off = d_off; out->scaf_size = d_size; out->seq = d_seq; out->rev = d_rev;
+    out->n_scaf = (int32_t)n_scaf; out->n_seq = (int32_t)lift.n_seq;
+    return HICMI_OK;
+}
+
+// hicmi_map_begin and, with a lift, hicmi_map_begin_lifted: the grid is cut from the scaffolds or from the sequences
+static int map_open(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, int64_t resolution, const LiftHost* lift)
 {
     if (!c || !scaf_size || n_scaf < 1 || n_scaf > INT_MAX / 2) return fail(HICMI_EINVAL, "bad arguments");
     if (resolution < 1) return fail(HICMI_EINVAL, "resolution %lld is below 1", (long long)resolution);
-    std::vector<int32_t> first((size_t)n_scaf);
+    if (lift) { int rc = lift_check(scaf_size, n_scaf, *lift); if (rc) return rc; }
+    const int64_t* grid = lift ? lift->seq_size : scaf_size;
+    const int64_t n_grid = lift ? lift->n_seq : n_scaf;
+    const char* what = lift ? "sequence" : "scaffold";
+    std::vector<int32_t> first((size_t)n_grid);
     int64_t m = 0;
-    for (int64_t s = 0; s < n_scaf; s++) {
-        if (scaf_size[s] < 0) return fail(HICMI_EINVAL, "scaffold %lld has the negative size %lld", (long long)s, (long long)scaf_size[s]);
+    for (int64_t s = 0; s < n_grid; s++) {
+        if (grid[s] < 0) return fail(HICMI_EINVAL, "%s %lld has the negative size %lld", what, (long long)s, (long long)grid[s]);
         first[(size_t)s] = (int32_t)m;
-        m += scaf_size[s] / resolution + (scaf_size[s] % resolution != 0);
+        m += grid[s] / resolution + (grid[s] % resolution != 0);
         if (m > 65536)
             return fail(HICMI_EUNSUPPORTED, "resolution %lld needs more than 65536 bins: rank matrix is uint16 in this version",
                         (long long)resolution);
     }
-    if (m < 1) return fail(HICMI_EINVAL, "the scaffolds have no bins");
+    if (m < 1) return fail(HICMI_EINVAL, "the %ss have no bins", what);
     HIPCHK(hipSetDevice(c->device));
     map_abandon(c);                                           // a begin without a finish is given up
     hipError_t e = hipMalloc(&c->map_cells, sizeof(uint64_t) * (size_t)m * (size_t)m);
@@ -673,9 +728,14 @@ int hicmi_map_begin(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, int6
         return fail(HICMI_ENOMEM, "hipMalloc(%lld bytes): %s", (long long)(8 * m * m), hipGetErrorString(e));
     }
     int rc = HICMI_OK;
-    e = hipMalloc((void**)&c->d_map_first, sizeof(int32_t) * (size_t)n_scaf);
+    e = hipMalloc((void**)&c->d_map_first, sizeof(int32_t) * (size_t)n_grid);
     if (e != hipSuccess) { c->d_map_first = nullptr; rc = fail(HICMI_ENOMEM, "hipMalloc: %s", hipGetErrorString(e)); }
-    if (!rc) rc = upload(c, c->d_map_first, first.data(), sizeof(int32_t) * (size_t)n_scaf);
+    if (!rc) rc = upload(c, c->d_map_first, first.data(), sizeof(int32_t) * (size_t)n_grid);
+    if (!rc && lift) {
+        e = hipMalloc((void**)&c->d_map_lift, 21 * (size_t)n_scaf);
+        if (e != hipSuccess) { c->d_map_lift = nullptr; rc = fail(HICMI_ENOMEM, "hipMalloc: %s", hipGetErrorString(e)); }
+        if (!rc) rc = lift_upload(c, c->d_map_lift, scaf_size, n_scaf, *lift, &c->map_lift);
+    }
     if (!rc && (e = hipMemsetAsync(c->map_cells, 0, sizeof(uint64_t) * (size_t)m * (size_t)m, c->stream)) != hipSuccess)
         rc = fail(HICMI_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e));
     if (!rc && (e = sync_stream(c)) != hipSuccess) rc = fail(HICMI_EHIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
@@ -683,7 +743,20 @@ int hicmi_map_begin(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, int6
     c->map_m = m; c->map_res = resolution; c->map_pairs = 0;
     c->map_first = std::move(first);
     c->map_size.assign(scaf_size, scaf_size + n_scaf);
+    if (lift) c->map_lift_seq.assign(lift->seq, lift->seq + n_scaf);
     return HICMI_OK;
+}
+
+int hicmi_map_begin(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, int64_t resolution)
+{
+    return map_open(c, scaf_size, n_scaf, resolution, nullptr);
+}
+
+int hicmi_map_begin_lifted(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, const int32_t* lift_seq, const int64_t* lift_off,
+                           const uint8_t* lift_rev, const int64_t* seq_size, int64_t n_seq, int64_t resolution)
+{
+    const LiftHost lift{lift_seq, lift_off, lift_rev, seq_size, n_seq};
+    return map_open(c, scaf_size, n_scaf, resolution, &lift);
 }
 
 // the four arrays of a chunk, one after the other in one device buffer (8-byte fields first)
@@ -698,18 +771,45 @@ static MapChunk map_chunk_at(unsigned char* base, int64_t n)
     return k;
 }
 
+// every scaffold index and position of a chunk against the scaffold sizes; with lift_seq, also the pairs that have an end
+// on a dropped scaffold
+static int check_pairs(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
+                       const int64_t* scaf_size, int64_t n_scaf, const int32_t* lift_seq, int64_t* unlifted_out)
+{
+    int64_t unlifted = 0;
+    for (int64_t p = 0; p < n; p++) {
+        if (scaf_a[p] < 0 || scaf_a[p] >= n_scaf || scaf_b[p] < 0 || scaf_b[p] >= n_scaf)
+            return fail(HICMI_EINVAL, "pair %lld names a scaffold outside 0 .. %lld", (long long)p, (long long)(n_scaf - 1));
+        if (pos_a[p] < 1 || pos_a[p] > scaf_size[scaf_a[p]] || pos_b[p] < 1 || pos_b[p] > scaf_size[scaf_b[p]])
+            return fail(HICMI_EINVAL, "pair %lld has a position outside 1 .. the size of its scaffold", (long long)p);
+        if (lift_seq) unlifted += lift_seq[scaf_a[p]] < 0 || lift_seq[scaf_b[p]] < 0;
+    }
+    if (unlifted_out) *unlifted_out = unlifted;
+    return HICMI_OK;
+}
+
+// the counters of k_pair_stats, [decay 256][cis n_seq][trans n_seq][unlifted], added to the caller's arrays
+static void stats_add(const uint64_t* got, int64_t n_seq, uint64_t* decay_out, uint64_t* seq_cis_out, uint64_t* seq_trans_out,
+                      uint64_t* unlifted_out)
+{
+    for (int k = 0; k < LIFT_DECAY_SLOTS; k++) decay_out[k] += got[k];
+    for (int64_t q = 0; q < n_seq; q++) {
+        seq_cis_out[q] += got[LIFT_DECAY_SLOTS + q];
+        seq_trans_out[q] += got[LIFT_DECAY_SLOTS + n_seq + q];
+    }
+    *unlifted_out += got[LIFT_DECAY_SLOTS + 2 * n_seq];
+}
+
 int hicmi_map_add_pairs(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b,
                         int64_t n)
 {
     if (!c || n < 0 || (n > 0 && (!scaf_a || !pos_a || !scaf_b || !pos_b))) return fail(HICMI_EINVAL, "bad arguments");
     if (!c->map_cells) return fail(HICMI_EINVAL, "hicmi_map_add_pairs without hicmi_map_begin");
     const int64_t n_scaf = (int64_t)c->map_size.size();
-    for (int64_t p = 0; p < n; p++) {
-        if (scaf_a[p] < 0 || scaf_a[p] >= n_scaf || scaf_b[p] < 0 || scaf_b[p] >= n_scaf)
-            return fail(HICMI_EINVAL, "pair %lld names a scaffold outside 0 .. %lld", (long long)p, (long long)(n_scaf - 1));
-        if (pos_a[p] < 1 || pos_a[p] > c->map_size[(size_t)scaf_a[p]] || pos_b[p] < 1 || pos_b[p] > c->map_size[(size_t)scaf_b[p]])
-            return fail(HICMI_EINVAL, "pair %lld has a position outside 1 .. the size of its scaffold", (long long)p);
-    }
+    int64_t unlifted = 0;                                     // a lifted build skips the pairs with an end on a dropped scaffold
+    int rc_pairs = check_pairs(scaf_a, pos_a, scaf_b, pos_b, n, c->map_size.data(), n_scaf,
+                               c->map_lift.seq ? c->map_lift_seq.data() : nullptr, &unlifted);
+    if (rc_pairs) return rc_pairs;
     if (n == 0) return HICMI_OK;
     HIPCHK(hipSetDevice(c->device));
     // a HIP error from here on gives the build up: what was counted so far cannot be told
@@ -720,14 +820,52 @@ int hicmi_map_add_pairs(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos_
     if (!rc) rc = upload(c, k.scaf_a, scaf_a, sizeof(int32_t) * (size_t)n);
     if (!rc) rc = upload(c, k.scaf_b, scaf_b, sizeof(int32_t) * (size_t)n);
     if (!rc) {
-        launch_buildmap_add(k.scaf_a, k.pos_a, k.scaf_b, k.pos_b, n, c->d_map_first, (int)n_scaf, c->map_res, (int)c->map_m,
-                            c->map_cells, buildmap_plain(), c->stream);
+        launch_buildmap_add(k.scaf_a, k.pos_a, k.scaf_b, k.pos_b, n, c->d_map_first, (int)c->map_first.size(), c->map_res,
+                            (int)c->map_m, c->map_cells, c->map_lift.seq ? liftmap_plain() : buildmap_plain(), c->map_lift,
+                            c->stream);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = sync_stream(c);
         if (e != hipSuccess) rc = fail(HICMI_EHIP, "counting a chunk of pairs: %s", hipGetErrorString(e));
     }
     if (rc) { map_abandon(c); return rc; }
-    c->map_pairs += n;
+    c->map_pairs += n - unlifted;
+    return HICMI_OK;
+}
+
+// The statistics of a chunk of pairs under a lift, added to the caller's arrays.  No matrix state.
+int hicmi_pair_stats(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
+                     const int64_t* scaf_size, int64_t n_scaf, const int32_t* lift_seq, const int64_t* lift_off,
+                     const uint8_t* lift_rev, const int64_t* seq_size, int64_t n_seq, uint64_t* decay_out, uint64_t* seq_cis_out,
+                     uint64_t* seq_trans_out, uint64_t* unlifted_out)
+{
+    if (!c || n < 0 || (n > 0 && (!scaf_a || !pos_a || !scaf_b || !pos_b)) || !scaf_size || n_scaf < 1 || n_scaf > INT_MAX / 2 ||
+        !decay_out || !seq_cis_out || !seq_trans_out || !unlifted_out)
+        return fail(HICMI_EINVAL, "bad arguments");
+    const LiftHost lift{lift_seq, lift_off, lift_rev, seq_size, n_seq};
+    int rc = lift_check(scaf_size, n_scaf, lift);
+    if (!rc) rc = check_pairs(scaf_a, pos_a, scaf_b, pos_b, n, scaf_size, n_scaf, nullptr, nullptr);
+    if (rc || n == 0) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t n_out = LIFT_DECAY_SLOTS + 2 * n_seq + 1;
+    rc = ensure(c->d_map_chunk, c->map_chunk_cap, 24 * n);
+    if (!rc) rc = ensure(c->d_stat_lift, c->stat_lift_cap, 21 * n_scaf);
+    if (!rc) rc = ensure(c->d_stat_out, c->stat_out_cap, n_out);
+    if (rc) return rc;
+    LiftTables tables;
+    const MapChunk k = map_chunk_at(c->d_map_chunk, n);
+    rc = lift_upload(c, c->d_stat_lift, scaf_size, n_scaf, lift, &tables);
+    if (!rc) rc = upload(c, k.pos_a, pos_a, sizeof(int64_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.pos_b, pos_b, sizeof(int64_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.scaf_a, scaf_a, sizeof(int32_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.scaf_b, scaf_b, sizeof(int32_t) * (size_t)n);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(c->d_stat_out, 0, sizeof(uint64_t) * (size_t)n_out, c->stream));
+    launch_pair_stats(k.scaf_a, k.pos_a, k.scaf_b, k.pos_b, n, tables, c->d_stat_out, c->stream);
+    HIPCHK(hipGetLastError());
+    std::vector<uint64_t> got((size_t)n_out);
+    rc = download(c, got.data(), c->d_stat_out, sizeof(uint64_t) * (size_t)n_out);
+    if (rc) return rc;
+    stats_add(got.data(), n_seq, decay_out, seq_cis_out, seq_trans_out, unlifted_out);
     return HICMI_OK;
 }
 
@@ -760,10 +898,17 @@ int hicmi_map_finish(hicmi_ctx* c, int64_t* pairs_out)
     return map_install(c, c->stream, pairs_out);
 }
 
-int hicmi_build_maps(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
-                     int64_t n_res, const int64_t* resolution, hicmi_ctx* const* ctxs, int threads, int64_t* stats5)
+// The chunk loop of hicmi_build_maps and hicmi_lift_maps.  `lift` (hicmi_lift_maps): every build is a lifted one, the
+// statistics of every chunk are counted beside the maps, and `stat_out` receives them when the whole file is counted.
+struct LiftStatsOut { uint64_t *decay, *seq_cis, *seq_trans, *unlifted; };
+
+static int build_maps_loop(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names,
+                           const int64_t* scaf_size, int64_t n_res, const int64_t* resolution, hicmi_ctx* const* ctxs, int threads,
+                           int64_t* stats5, const LiftHost* lift, const LiftStatsOut* stat_out)
 {
     if (!path || !names_blob || !name_off || !scaf_size || !resolution || !ctxs || !stats5 || n_names < 1 || n_res < 1)
+        return fail(HICMI_EINVAL, "bad arguments");
+    if (lift && (!stat_out->decay || !stat_out->seq_cis || !stat_out->seq_trans || !stat_out->unlifted))
         return fail(HICMI_EINVAL, "bad arguments");
     for (int k = 0; k < 5; k++) stats5[k] = 0;
     for (int64_t k = 0; k < n_res; k++) {
@@ -781,18 +926,26 @@ int hicmi_build_maps(const char* path, const char* names_blob, const int64_t* na
     // everything the call owns: two pinned chunks for the parser, two device chunks for the kernels
     struct Owned {
         unsigned char* pin[2] = {nullptr, nullptr}; unsigned char* dev[2] = {nullptr, nullptr};
+        unsigned long long* d_stats = nullptr;                    // a lifted call: the counters of k_pair_stats
         hicmi_ctx* const* ctxs; int64_t n_res; bool keep = false;
         ~Owned()
         {
             for (int b = 0; b < 2; b++) { if (pin[b]) (void)hipHostFree(pin[b]); free_dev(dev[b]); }
+            free_dev(d_stats);
             if (!keep) for (int64_t k = 0; k < n_res; k++) map_abandon(ctxs[k]);
         }
     } own;
     own.ctxs = ctxs; own.n_res = n_res;
     // begin on every context first: a resolution that cannot be built is refused before the file is read
     for (int64_t k = 0; k < n_res; k++) {
-        int rc = hicmi_map_begin(ctxs[k], scaf_size, n_names, resolution[k]);
+        int rc = map_open(ctxs[k], scaf_size, n_names, resolution[k], lift);
         if (rc) return rc;
+    }
+    const int64_t n_stats = lift ? LIFT_DECAY_SLOTS + 2 * lift->n_seq + 1 : 0;
+    if (lift) {
+        hipError_t e = hipMalloc((void**)&own.d_stats, sizeof(uint64_t) * (size_t)n_stats);
+        if (e != hipSuccess) { own.d_stats = nullptr; return fail(HICMI_ENOMEM, "hipMalloc: %s", hipGetErrorString(e)); }
+        HIPCHK(hipMemsetAsync(own.d_stats, 0, sizeof(uint64_t) * (size_t)n_stats, c0->stream));
     }
     int64_t file_bytes = -1;
     {
@@ -810,7 +963,7 @@ int hicmi_build_maps(const char* path, const char* names_blob, const int64_t* na
         hipError_t e = hipMalloc((void**)&own.dev[b], chunk_bytes);
         if (e != hipSuccess) { own.dev[b] = nullptr; return fail(HICMI_ENOMEM, "hipMalloc(%zu bytes): %s", chunk_bytes, hipGetErrorString(e)); }
     }
-    const bool plain = buildmap_plain();
+    const bool plain = lift ? liftmap_plain() : buildmap_plain();
     int64_t next = 0, n_here = 0, st[4];
     // chunk t + 1 is parsed into the other pinned buffer while chunk t is uploaded and counted on c0's stream
     auto parse = [&](int b) {
@@ -833,10 +986,11 @@ int hicmi_build_maps(const char* path, const char* names_blob, const int64_t* na
             HIPCHK(hipMemcpyAsync(d.scaf_b, h.scaf_b, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c0->stream));
             for (int64_t k = 0; k < n_res; k++) {
                 hicmi_ctx* c = ctxs[k];
-                launch_buildmap_add(d.scaf_a, d.pos_a, d.scaf_b, d.pos_b, n, c->d_map_first, (int)n_names, c->map_res, (int)c->map_m,
-                                    c->map_cells, plain, c0->stream);
+                launch_buildmap_add(d.scaf_a, d.pos_a, d.scaf_b, d.pos_b, n, c->d_map_first, (int)c->map_first.size(), c->map_res,
+                                    (int)c->map_m, c->map_cells, plain, c->map_lift, c0->stream);
                 c->map_pairs += n;
             }
+            if (lift) launch_pair_stats(d.scaf_a, d.pos_a, d.scaf_b, d.pos_b, n, c0->map_lift, own.d_stats, c0->stream);
             HIPCHK(hipGetLastError());
             stats5[4]++;
         }
@@ -848,6 +1002,12 @@ int hicmi_build_maps(const char* path, const char* names_blob, const int64_t* na
         if (last) break;
         cur ^= 1;
     }
+    std::vector<uint64_t> got((size_t)n_stats);
+    if (lift) {
+        // the statistics come down before any context changes; a map has counted the pairs that were lifted
+        HIPCHK(hipMemcpy(got.data(), own.d_stats, sizeof(uint64_t) * (size_t)n_stats, hipMemcpyDeviceToHost));
+        for (int64_t k = 0; k < n_res; k++) ctxs[k]->map_pairs -= (int64_t)got[(size_t)n_stats - 1];
+    }
     // every chunk is counted on every map: from here on the contexts change
     own.keep = true;
     for (int64_t k = 0; k < n_res; k++) {
@@ -855,7 +1015,24 @@ int hicmi_build_maps(const char* path, const char* names_blob, const int64_t* na
         rc = map_install(ctxs[k], c0->stream, nullptr);
         if (rc) { for (int64_t q = k + 1; q < n_res; q++) map_abandon(ctxs[q]); return rc; }
     }
+    if (lift) stats_add(got.data(), lift->n_seq, stat_out->decay, stat_out->seq_cis, stat_out->seq_trans, stat_out->unlifted);
     return HICMI_OK;
+}
+
+int hicmi_build_maps(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
+                     int64_t n_res, const int64_t* resolution, hicmi_ctx* const* ctxs, int threads, int64_t* stats5)
+{
+    return build_maps_loop(path, names_blob, name_off, n_names, scaf_size, n_res, resolution, ctxs, threads, stats5, nullptr, nullptr);
+}
+
+int hicmi_lift_maps(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
+                    const int32_t* lift_seq, const int64_t* lift_off, const uint8_t* lift_rev, const int64_t* seq_size, int64_t n_seq,
+                    int64_t n_res, const int64_t* resolution, hicmi_ctx* const* ctxs, int threads, int64_t* stats5,
+                    uint64_t* decay_out, uint64_t* seq_cis_out, uint64_t* seq_trans_out, uint64_t* unlifted_out)
+{
+    const LiftHost lift{lift_seq, lift_off, lift_rev, seq_size, n_seq};
+    const LiftStatsOut out{decay_out, seq_cis_out, seq_trans_out, unlifted_out};
+    return build_maps_loop(path, names_blob, name_off, n_names, scaf_size, n_res, resolution, ctxs, threads, stats5, &lift, &out);
 }
 
 // Group support: extends the scaffold vote of assessChromosomeClustering (S2C:1001-1077) with the

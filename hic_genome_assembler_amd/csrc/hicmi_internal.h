@@ -6,6 +6,8 @@
 #include <atomic>
 #include <functional>
 
+#include "liftmap.h"
+
 namespace hicmi {
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) only when a launch needs more than any earlier one
@@ -506,12 +508,21 @@ void launch_rebin(const double* C, int64_t ld, int n, const int32_t* group_start
                   double* R, bool plain, hipStream_t s);
 
 // k_buildmap.hip: a raw map counted from read pairs (hicmi_map_*, hicmi_build_maps).  The four pair arrays
-// and first_bin (n_scaf entries) are device memory; counts: m x m unsigned 64-bit cells, of which the upper triangle is
-// counted; launch_buildmap_finish turns them in place into the symmetric matrix of doubles.
+// and first_bin (n_grid entries) are device memory; counts: m x m unsigned 64-bit cells, of which the upper triangle is
+// counted; launch_buildmap_finish turns them in place into the symmetric matrix of doubles.  With lift tables
+// (lift.seq != nullptr, device pointers) every end is lifted to its assembled sequence first and first_bin
+// describes the sequences.  launch_pair_stats adds the statistics of the pairs to out[256 + 2 n_seq + 1]: the decay
+// histogram, cis and trans per sequence, the unlifted pairs.
 static constexpr int BUILDMAP_SLICE = 2048;   // pairs a workgroup of k_buildmap_combine brings together
 static constexpr int BUILDMAP_SLOTS = 4096;   // slots of its hash table in LDS (12 bytes each)
+static constexpr int PAIRSTATS_SLICE = 1024;  // pairs a workgroup of k_pair_stats brings together: up to two keys each
+static constexpr int PAIRSTATS_SLOT_BITS = 12;
+static constexpr int PAIRSTATS_SLOTS = 1 << PAIRSTATS_SLOT_BITS;   // slots of its table in LDS (8 bytes each)
 void launch_buildmap_add(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
-                         const int32_t* first_bin, int n_scaf, int64_t r, int m, void* counts, bool plain, hipStream_t s);
+                         const int32_t* first_bin, int n_grid, int64_t r, int m, void* counts, bool plain, const LiftTables& lift,
+                         hipStream_t s);
+void launch_pair_stats(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
+                       const LiftTables& lift, void* out, hipStream_t s);
 void launch_buildmap_finish(void* cells, int m, hipStream_t s);
 
 // k_plot.hip

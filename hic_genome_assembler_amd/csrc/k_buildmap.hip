@@ -19,6 +19,11 @@
 //                       strict upper triangle is mirrored into the lower one, 64 x 64 tiles through LDS like
 //                       k_rebin_mirror.  A count and its double are both 8 bytes: the cell (r, c), r <= c, is read and
 //                       rewritten by one lane, and the lower triangle is never read.
+// A lifted build (hicmi_map_begin_lifted, hicmi_lift_maps) counts the map of the assembled genome: both
+// counting kernels are templates on LIFTED, and the lifted form sends each end through the per-scaffold lift tables
+// (sequence, offset, reversed; liftmap.h) before the same key arithmetic, with first_bin describing the sequences.
+//   k_pair_stats        the cis / trans split per sequence and the contact-decay histogram of a chunk of pairs under a
+//                       lift, combined in LDS like k_buildmap_combine (up to two 32-bit keys per pair).
 // The host checks every scaffold index and position before a chunk is uploaded; the kernels still drop a pair whose
 // bin would fall outside the map, so a wrong input cannot write out of bounds.
 #include "hicmi_internal.h"
@@ -29,41 +34,46 @@ static_assert((BUILDMAP_SLOTS & (BUILDMAP_SLOTS - 1)) == 0 && BUILDMAP_SLOTS >= 
               "the table is a power of two and at most half full");
 static_assert(BUILDMAP_SLICE % 256 == 0, "lane t takes the pairs t, t + 256, ... of a slice");
 
-constexpr unsigned long long kNoKey = ~0ull;      // lo * m + hi <= 2^32 - 1 for m <= 65536
+static_assert((PAIRSTATS_SLOTS & (PAIRSTATS_SLOTS - 1)) == 0 && PAIRSTATS_SLOTS >= 4 * PAIRSTATS_SLICE,
+              "two keys per pair, and the table is a power of two and at most half full");
+static_assert(PAIRSTATS_SLICE % 256 == 0, "lane t takes the pairs t, t + 256, ... of a slice");
 
-// the key of pair p, or kNoKey for a pair outside the map
+// the key of pair p, or kNoKey for a pair outside the map.  LIFTED: both ends go through the lift tables first, and
+// first_bin / n_grid describe the assembled sequences; that is the only difference (map_cell_key, liftmap.h)
+template <bool LIFTED>
 __device__ __forceinline__ unsigned long long buildmap_key(const int32_t* __restrict__ scaf_a, const int64_t* __restrict__ pos_a,
                                                            const int32_t* __restrict__ scaf_b, const int64_t* __restrict__ pos_b,
-                                                           int64_t p, const int32_t* __restrict__ first_bin, int n_scaf,
-                                                           int64_t r, int m)
+                                                           int64_t p, const int32_t* __restrict__ first_bin, int n_grid,
+                                                           int64_t r, int m, const LiftTables& L)
 {
-    const int32_t sa = scaf_a[p], sb = scaf_b[p];
-    const int64_t pa = pos_a[p] - 1, pb = pos_b[p] - 1;
-    if (sa < 0 || sa >= n_scaf || sb < 0 || sb >= n_scaf || pa < 0 || pb < 0) return kNoKey;
-    int64_t ka, kb;
-    if (((uint64_t)pa | (uint64_t)pb | (uint64_t)r) >> 32) { ka = pa / r; kb = pb / r; }
-    else { ka = (uint32_t)pa / (uint32_t)r; kb = (uint32_t)pb / (uint32_t)r; }      // the usual case: 32-bit division
-    const int64_t i = first_bin[sa] + ka, j = first_bin[sb] + kb;
-    if (i >= m || j >= m) return kNoKey;
-    const int64_t lo = i < j ? i : j, hi = i < j ? j : i;
-    return (unsigned long long)(lo * m + hi);
+    int32_t ga = scaf_a[p], gb = scaf_b[p];
+    int64_t xa = pos_a[p], xb = pos_b[p];
+    if (LIFTED) {
+        int32_t qa, qb;
+        int64_t ya, yb;
+        if (!lift_end(L, ga, xa, &qa, &ya) || !lift_end(L, gb, xb, &qb, &yb)) return kNoKey;
+        ga = qa; gb = qb; xa = ya; xb = yb;
+    }
+    return map_cell_key(ga, xa, gb, xb, first_bin, n_grid, r, m);
 }
 
+template <bool LIFTED>
 __global__ __launch_bounds__(256) void k_buildmap_plain(const int32_t* __restrict__ scaf_a, const int64_t* __restrict__ pos_a,
                                                         const int32_t* __restrict__ scaf_b, const int64_t* __restrict__ pos_b,
-                                                        int64_t n, const int32_t* __restrict__ first_bin, int n_scaf,
-                                                        int64_t r, int m, unsigned long long* __restrict__ counts)
+                                                        int64_t n, const int32_t* __restrict__ first_bin, int n_grid,
+                                                        int64_t r, int m, unsigned long long* __restrict__ counts, LiftTables L)
 {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
-    const unsigned long long key = buildmap_key(scaf_a, pos_a, scaf_b, pos_b, p, first_bin, n_scaf, r, m);
+    const unsigned long long key = buildmap_key<LIFTED>(scaf_a, pos_a, scaf_b, pos_b, p, first_bin, n_grid, r, m, L);
     if (key != kNoKey) atomicAdd(counts + key, 1ull);
 }
 
+template <bool LIFTED>
 __global__ __launch_bounds__(256) void k_buildmap_combine(const int32_t* __restrict__ scaf_a, const int64_t* __restrict__ pos_a,
                                                           const int32_t* __restrict__ scaf_b, const int64_t* __restrict__ pos_b,
-                                                          int64_t n, const int32_t* __restrict__ first_bin, int n_scaf,
-                                                          int64_t r, int m, unsigned long long* __restrict__ counts)
+                                                          int64_t n, const int32_t* __restrict__ first_bin, int n_grid,
+                                                          int64_t r, int m, unsigned long long* __restrict__ counts, LiftTables L)
 {
     __shared__ unsigned long long s_key[BUILDMAP_SLOTS];
     __shared__ unsigned int s_cnt[BUILDMAP_SLOTS];
@@ -75,7 +85,7 @@ __global__ __launch_bounds__(256) void k_buildmap_combine(const int32_t* __restr
     for (int u = 0; u < BUILDMAP_SLICE / 256; u++) {
         const int64_t p = base + u * 256 + t;
         if (p >= n) break;
-        const unsigned long long key = buildmap_key(scaf_a, pos_a, scaf_b, pos_b, p, first_bin, n_scaf, r, m);
+        const unsigned long long key = buildmap_key<LIFTED>(scaf_a, pos_a, scaf_b, pos_b, p, first_bin, n_grid, r, m, L);
         if (key == kNoKey) continue;
         // Fibonacci hashing, then linear probing: at most BUILDMAP_SLICE distinct keys in 2 x BUILDMAP_SLICE slots, so
         // a free or matching slot always comes
@@ -90,6 +100,62 @@ __global__ __launch_bounds__(256) void k_buildmap_combine(const int32_t* __restr
     for (int s = t; s < BUILDMAP_SLOTS; s += 256) {
         const unsigned long long key = s_key[s];
         if (key != kNoKey) atomicAdd(counts + key, (unsigned long long)s_cnt[s]);
+    }
+}
+
+// The statistics of a chunk of pairs under a lift, added to out[256 + 2 n_seq + 1]: the decay histogram,
+// cis per sequence, trans per sequence, the unlifted pairs.  The combining scheme of k_buildmap_combine with up to two
+// keys per pair in one key space - a cis pair its decay slot and 256 + seq, a trans pair 256 + n_seq + seq of either end,
+// an unlifted pair the last counter - and 32-bit keys: a slice of PAIRSTATS_SLICE pairs has at most 2 x PAIRSTATS_SLICE
+// distinct keys in PAIRSTATS_SLOTS >= twice as many slots.  A single chromosome sends most pairs of a slice to one
+// counter: they meet in LDS, and every used slot issues one 64-bit global atomic add.
+constexpr unsigned int kNoStat = ~0u;
+
+__device__ __forceinline__ void pair_stats_count(unsigned int* s_key, unsigned int* s_cnt, unsigned int key)
+{
+    unsigned int h = (key * 0x9E3779B9u) >> (32 - PAIRSTATS_SLOT_BITS);
+    for (;;) {
+        const unsigned int seen = atomicCAS(&s_key[h], kNoStat, key);
+        if (seen == kNoStat || seen == key) { atomicAdd(&s_cnt[h], 1u); return; }
+        h = (h + 1) & (PAIRSTATS_SLOTS - 1);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pair_stats(const int32_t* __restrict__ scaf_a, const int64_t* __restrict__ pos_a,
+                                                    const int32_t* __restrict__ scaf_b, const int64_t* __restrict__ pos_b,
+                                                    int64_t n, LiftTables L, unsigned long long* __restrict__ out)
+{
+    __shared__ unsigned int s_key[PAIRSTATS_SLOTS];
+    __shared__ unsigned int s_cnt[PAIRSTATS_SLOTS];
+    const int t = threadIdx.x;
+    for (int s = t; s < PAIRSTATS_SLOTS; s += 256) { s_key[s] = kNoStat; s_cnt[s] = 0u; }
+    __syncthreads();
+    const unsigned int k_cis = LIFT_DECAY_SLOTS, k_trans = k_cis + (unsigned int)L.n_seq, k_unlifted = k_trans + (unsigned int)L.n_seq;
+    const int64_t base = (int64_t)blockIdx.x * PAIRSTATS_SLICE;
+    for (int u = 0; u < PAIRSTATS_SLICE / 256; u++) {
+        const int64_t p = base + u * 256 + t;
+        if (p >= n) break;
+        int32_t qa, qb;
+        int64_t ya = 0, yb = 0;
+        const bool ok_a = lift_end(L, scaf_a[p], pos_a[p], &qa, &ya), ok_b = lift_end(L, scaf_b[p], pos_b[p], &qb, &yb);
+        if (!ok_a || !ok_b) {
+            // an end on a dropped scaffold; an end outside the tables (the host refuses those) counts nowhere
+            if (qa >= -1 && qb >= -1) pair_stats_count(s_key, s_cnt, k_unlifted);
+            continue;
+        }
+        if (qa == qb) {
+            const uint64_t d = ya < yb ? (uint64_t)(yb - ya) : (uint64_t)(ya - yb);
+            pair_stats_count(s_key, s_cnt, (unsigned int)lift_decay_slot(d));
+            pair_stats_count(s_key, s_cnt, k_cis + (unsigned int)qa);
+        } else {
+            pair_stats_count(s_key, s_cnt, k_trans + (unsigned int)qa);
+            pair_stats_count(s_key, s_cnt, k_trans + (unsigned int)qb);
+        }
+    }
+    __syncthreads();
+    for (int s = t; s < PAIRSTATS_SLOTS; s += 256) {
+        const unsigned int key = s_key[s];
+        if (key != kNoStat) atomicAdd(out + key, (unsigned long long)s_cnt[s]);
     }
 }
 
@@ -118,17 +184,35 @@ __global__ __launch_bounds__(256) void k_buildmap_finish(void* __restrict__ cell
     }
 }
 
+template <bool LIFTED>
+static void launch_add(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
+                       const int32_t* first_bin, int n_grid, int64_t r, int m, unsigned long long* cnt, bool plain,
+                       const LiftTables& L, hipStream_t s)
+{
+    if (plain)
+        hipLaunchKernelGGL(k_buildmap_plain<LIFTED>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, scaf_a, pos_a, scaf_b, pos_b,
+                           n, first_bin, n_grid, r, m, cnt, L);
+    else
+        hipLaunchKernelGGL(k_buildmap_combine<LIFTED>, dim3((unsigned)((n + BUILDMAP_SLICE - 1) / BUILDMAP_SLICE)), dim3(256), 0, s,
+                           scaf_a, pos_a, scaf_b, pos_b, n, first_bin, n_grid, r, m, cnt, L);
+}
+
 void launch_buildmap_add(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
-                         const int32_t* first_bin, int n_scaf, int64_t r, int m, void* counts, bool plain, hipStream_t s)
+                         const int32_t* first_bin, int n_grid, int64_t r, int m, void* counts, bool plain, const LiftTables& lift,
+                         hipStream_t s)
 {
     if (n <= 0) return;
     unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts);
-    if (plain)
-        hipLaunchKernelGGL(k_buildmap_plain, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, scaf_a, pos_a, scaf_b, pos_b, n,
-                           first_bin, n_scaf, r, m, cnt);
-    else
-        hipLaunchKernelGGL(k_buildmap_combine, dim3((unsigned)((n + BUILDMAP_SLICE - 1) / BUILDMAP_SLICE)), dim3(256), 0, s,
-                           scaf_a, pos_a, scaf_b, pos_b, n, first_bin, n_scaf, r, m, cnt);
+    if (lift.seq) launch_add<true>(scaf_a, pos_a, scaf_b, pos_b, n, first_bin, n_grid, r, m, cnt, plain, lift, s);
+    else launch_add<false>(scaf_a, pos_a, scaf_b, pos_b, n, first_bin, n_grid, r, m, cnt, plain, lift, s);
+}
+
+void launch_pair_stats(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
+                       const LiftTables& lift, void* out, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_pair_stats, dim3((unsigned)((n + PAIRSTATS_SLICE - 1) / PAIRSTATS_SLICE)), dim3(256), 0, s, scaf_a, pos_a,
+                       scaf_b, pos_b, n, lift, reinterpret_cast<unsigned long long*>(out));
 }
 
 void launch_buildmap_finish(void* cells, int m, hipStream_t s)

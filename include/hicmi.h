@@ -499,6 +499,50 @@ int hicmi_build_maps(const char *path, const char *names_blob, const int64_t *na
                      const int64_t *scaf_size, int64_t n_res, const int64_t *resolution, hicmi_ctx *const *ctxs,
                      int threads, int64_t *stats5);
 
+/* ---- contact maps of the assembled genome: the pairs counted in chromosome coordinates ------------------
+ * An assembly lays scaffolds end to end into n_seq sequences of the sizes seq_size.  Per scaffold of the size file:
+ * lift_seq (the sequence it lies in, -1: dropped), lift_off (its offset there, >= 0) and lift_rev (non-zero: reversed).
+ * The 1-based position p on a scaffold of length L becomes off + p, or off + L - p + 1 on a reversed scaffold, on its
+ * sequence; bins and counts are those of 9l applied to the sequences: ceil(seq_size / resolution) bins per sequence, cut
+ * from its own start.  A pair with an end on a dropped scaffold is skipped and counted as unlifted.
+ *
+ * hicmi_map_begin_lifted is hicmi_map_begin for such a build: m and first_bin come from seq_size, the tables stay on the
+ * device with the build.  hicmi_map_add_pairs (which still checks indices and positions against the scaffold sizes) and
+ * hicmi_map_finish (whose pairs_out leaves the unlifted pairs out) then work as in 9l.  HICMI_LIFTMAP_PLAIN=1|0 in the
+ * environment names the counting kernel of a lifted build as HICMI_BUILDMAP_PLAIN does for a plain one; it is read at
+ * every call.  HICMI_EINVAL, before anything is allocated, with a message naming the scaffold: lift_seq outside
+ * -1 .. n_seq - 1, a negative offset or size, lift_off + size beyond seq_size[lift_seq], two scaffolds of non-zero size
+ * that overlap in one sequence; HICMI_EUNSUPPORTED: more than 65,536 bins.  After an error the matrix state and an open
+ * build are as the 9l calls leave them.
+ *
+ * hicmi_pair_stats: the statistics of a chunk of pairs (host arrays) under the lift, computed on the context's device
+ * and ADDED to the outputs; it has no matrix state and touches none.  Over the lifted pairs: a pair is cis when both
+ * ends lie in one sequence, else trans; seq_cis_out[s] counts the cis pairs of s, seq_trans_out[s] the trans pairs with
+ * an end in s (a trans pair counts in two sequences); decay_out[256] is the histogram of d = |p'_a - p'_b| over cis
+ * pairs - slot 0 holds d = 0, d >= 1 falls in slot 1 + 4 e + (((d - 2^e) * 4) >> e), e = floor(log2 d) (quarter
+ * octaves; slots above 252 stay 0); *unlifted_out counts the skipped pairs.  All unsigned 64-bit integers: every
+ * chunking and arrival order gives the same bits.
+ *
+ * hicmi_lift_maps is hicmi_build_maps with the lift tables and the statistics outputs: one pass over the file, n_res
+ * lifted maps and the statistics of every chunk, added to the outputs when the whole file is counted.  stats5 as in
+ * hicmi_build_maps.  On an error before every chunk is counted - a resolution or a table refused, the file, a malformed
+ * line, a HIP error while counting - no context's matrix state and no output changes.  The maps are installed one
+ * context after the other only then; should an installation itself fail (the row-sum buffers cannot be allocated, a HIP
+ * error in the conversion), the contexts before it hold their new maps, that one is as the failed step left it, those
+ * after it keep what they held, and the outputs are unchanged.  hicmi_build_maps installs in the same way. */
+int hicmi_map_begin_lifted(hicmi_ctx *ctx, const int64_t *scaf_size, int64_t n_scaf, const int32_t *lift_seq,
+                           const int64_t *lift_off, const uint8_t *lift_rev, const int64_t *seq_size, int64_t n_seq,
+                           int64_t resolution);
+int hicmi_pair_stats(hicmi_ctx *ctx, const int32_t *scaf_a, const int64_t *pos_a, const int32_t *scaf_b,
+                     const int64_t *pos_b, int64_t n, const int64_t *scaf_size, int64_t n_scaf, const int32_t *lift_seq,
+                     const int64_t *lift_off, const uint8_t *lift_rev, const int64_t *seq_size, int64_t n_seq,
+                     uint64_t *decay_out, uint64_t *seq_cis_out, uint64_t *seq_trans_out, uint64_t *unlifted_out);
+int hicmi_lift_maps(const char *path, const char *names_blob, const int64_t *name_off, int64_t n_names,
+                    const int64_t *scaf_size, const int32_t *lift_seq, const int64_t *lift_off, const uint8_t *lift_rev,
+                    const int64_t *seq_size, int64_t n_seq, int64_t n_res, const int64_t *resolution,
+                    hicmi_ctx *const *ctxs, int threads, int64_t *stats5, uint64_t *decay_out, uint64_t *seq_cis_out,
+                    uint64_t *seq_trans_out, uint64_t *unlifted_out);
+
 /* ---- plot support -----------------------------------------------------------------------------
  * plotContactMap (plotContactMaps.py:15-91) colours every cell of an N x N matrix between two
  * numpy.percentile limits.  The matrix stays on the device: kind 0 = raw contacts (Part 2 plots,
