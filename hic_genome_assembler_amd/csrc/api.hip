@@ -18,6 +18,7 @@
 
 #include "../../include/hicmi.h"
 #include "hicmi_internal.h"
+#include "devbuf.h"
 #include "hyper.h"
 
 using namespace hicmi;
@@ -56,61 +57,89 @@ constexpr int kBaseSlabs = 256;                        // partial sums of the cl
 
 struct TimedRegion { int fam; hipEvent_t a, b; };
 
+// The context.  Members are destroyed in reverse order of declaration, and hicmi_destroy relies on it: every buffer
+// below the handles is freed first, then the timing events, ev_join / ev_fork, stream2 and at last the stream.
+template <typename H, hipError_t (*Destroy)(H)>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(const Handle&) = delete;
+    ~Handle() { if (h) (void)Destroy(h); }
+    operator H() const { return h; }
+};
+using StreamHandle = Handle<hipStream_t, hipStreamDestroy>;
+using EventHandle = Handle<hipEvent_t, hipEventDestroy>;
+struct TimingEvents {
+    std::vector<TimedRegion> regions;
+    std::vector<hipEvent_t> pool;
+    TimingEvents() = default;
+    TimingEvents(const TimingEvents&) = delete;
+    ~TimingEvents()
+    {
+        for (auto& r : regions) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
+        for (auto e : pool) (void)hipEventDestroy(e);
+    }
+};
+
 struct hicmi_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
+    StreamHandle stream;
+    // pre-sort: the rank rows in storage labels, computed on a second stream while the nn-chain runs (hicmi_upgma)
+    StreamHandle stream2; EventHandle ev_fork, ev_join;
+    TimingEvents tev;
     int probed_xcc = 0;                  // the lowest XCD id of the device (nnchain_probe_xcc): the nn-chain's default XCD
-    // contacts
+    // contacts: dC is the caller's matrix (adopted, own_c false) or c_own's memory
     int64_t n = 0, ldc = 0;
     double* dC = nullptr;
     bool own_c = false;
-    double *d_np = nullptr, *d_seq = nullptr;
+    DevBuf<double> c_own;
+    DevBuf<double> d_np, d_seq;
     bool have_sums = false;
     // row shard (one map over several GPUs): this context sorts / counts only rows first, first + stride, ...
     int64_t shard_first = 0, shard_stride = 1;
-    // upgma
-    double *dW = nullptr, *dW2 = nullptr; int64_t ldw = 0; int64_t w_rows = 0;
-    int *d_size = nullptr, *d_chain = nullptr, *d_status = nullptr;
-    double* d_zraw = nullptr;
+    // upgma: one group, w_rows x ldw
+    DevBuf<double> dW, dW2; int64_t ldw = 0; int64_t w_rows = 0;
+    DevBuf<unsigned char> d_size;        // the nn-chain's workspace (nnchain_workspace_bytes)
+    DevBuf<int> d_chain, d_status;
+    DevBuf<double> d_zraw;
     std::vector<double> zraw;
-    // rank matrix
-    int32_t* d_order = nullptr;
-    uint16_t *dR = nullptr, *dRank = nullptr; int64_t ldr = 0; int64_t r_rows = 0;
-    void* d_sort_scratch = nullptr; size_t sort_scratch_cap = 0;
+    // rank matrix: dRank and d_order are one group, r_rows x ldr
+    DevBuf<int32_t> d_order;
+    DevBuf<uint16_t> dR, dRank; int64_t ldr = 0; int64_t r_rows = 0;
+    DevBuf<unsigned char> d_sort_scratch;
     bool have_rank = false;
-    // pre-sort: the rank rows in storage labels, computed on a second stream while the nn-chain runs (hicmi_upgma)
-    hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    uint16_t* dRankS = nullptr; int64_t rank_s_rows = 0;
-    int32_t* d_ident = nullptr; int64_t ident_cap = 0;
-    unsigned char* d_ties = nullptr; int64_t ties_cap = 0;   // [count of flagged rows, 16 bytes][one flag per storage row]
-    uint16_t* d_tie_bits = nullptr; int64_t tie_bits_rows = 0, ld_bits = 0;   // per storage row: "same key as the element before"
-    int32_t* d_row_list = nullptr; int64_t row_list_cap = 0;
+    // pre-sort buffers: one group
+    DevBuf<uint16_t> dRankS;
+    DevBuf<int32_t> d_ident;
+    DevBuf<unsigned char> d_ties;        // [count of flagged rows, 16 bytes][one flag per storage row]
+    DevBuf<uint16_t> d_tie_bits; int64_t ld_bits = 0;   // per storage row: "same key as the element before"
+    DevBuf<int32_t> d_row_list;          // the list + one flag per listed row
     int64_t scan_first_batch = 0, scan_last_improved = 0;   // hicmi_p2_scan_all: the first batch size of the next round
     int64_t presort_tied_rows = 0;                        // ... and how many rows it re-sorted because they hold equal keys
     int presort_used = 0;                                 // last hicmi_rank_matrix: 0 sorted itself, 1 relabelled the pre-sort, 2 pre-sort discarded (ties)
     int64_t presort_n = 0;                                // > 0: dRankS holds the rows of the current n x n matrix
     bool presort_dealt = false;                           // its rows were dealt out by a counter (workgroups on the chain's XCD left)
     // cut scan
-    int32_t* d_x = nullptr; uint8_t* d_sig = nullptr; int64_t x_cap = 0;
-    unsigned char* d_scan_multi = nullptr; size_t scan_multi_bytes = 0;  // device-driven scan loops: state records + lists
+    DevBuf<int32_t> d_x; DevBuf<uint8_t> d_sig;
+    DevBuf<unsigned char> d_scan_multi;  // device-driven scan loops: state records + lists
     int64_t cached_start = -1;
-    double* d_tmp = nullptr; int64_t tmp_cap = 0;
+    DevBuf<double> d_tmp;
     // part 2
-    double* dM2 = nullptr; int64_t n2 = 0, ld2 = 0, m2_cap = 0;
-    int32_t* d_sel = nullptr; int64_t sel_cap = 0;
-    double* d_H = nullptr; int64_t h_cap = 0;
-    int32_t* d_perms = nullptr; int64_t perms_cap = 0;
-    double* d_scores = nullptr; int64_t scores_cap = 0;
-    double* d_partial = nullptr; int64_t partial_cap = 0;
-    double* d_T = nullptr; int64_t t_cap = 0;
+    DevBuf<double> dM2; int64_t n2 = 0, ld2 = 0;
+    DevBuf<int32_t> d_sel;
+    DevBuf<double> d_H;
+    DevBuf<int32_t> d_perms;
+    DevBuf<double> d_scores;
+    DevBuf<double> d_partial;
+    DevBuf<double> d_T;
     // part 2 search state: layout (scaffold ranges of the selection), arrangement, window tables
-    int32_t *d_scaf_start = nullptr, *d_scaf_len = nullptr; int64_t scaf_cap = 0, n_scaf = 0;
+    DevBuf<int32_t> d_scaf_start, d_scaf_len; int64_t n_scaf = 0;
     std::vector<int32_t> h_scaf_start, h_scaf_len;
-    int32_t* d_arr_packed = nullptr; int64_t arr_cap = 0;       // [S ids][S+1 positions][S reversed flags]
+    DevBuf<int32_t> d_arr_packed;        // [S ids][S+1 positions][S reversed flags]
     std::vector<int32_t> h_arr_packed;
     std::vector<int32_t> h_arr_id, h_arr_pos; std::vector<uint8_t> h_arr_rev;
-    int32_t* d_pos2sel = nullptr; int64_t pos_cap = 0; int64_t n_arr = 0;
-    int8_t* d_orders = nullptr; uint8_t* d_orients = nullptr; int64_t ord_cap = 0, ori_cap = 0;
+    DevBuf<int32_t> d_pos2sel; int64_t n_arr = 0;
+    DevBuf<int8_t> d_orders; DevBuf<uint8_t> d_orients;
     int tab_k = 0; int64_t n_orders = 0, n_orients = 0;
     std::vector<int8_t> h_orders; std::vector<uint8_t> h_orients;
     std::vector<int32_t> h_pos2sel;                              // host mirror of the arrangement's bin order
@@ -118,78 +147,77 @@ struct hicmi_ctx {
     uint64_t cur_lit_version = ~0ull; double cur_lit_total = 0.0, cur_lit_value = 0.0;   // literal score of the arrangement itself
     double cache_total = 0.0; bool cache_valid = false;          // literal scores under one total, keyed by bin order
     std::unordered_map<std::string, double> exact_cache;
-    double* d_G = nullptr; int64_t g_cap = 0;
-    double* d_delta = nullptr; int64_t delta_cap = 0;
-    WindowBatchEntry* d_wb = nullptr; int64_t wb_cap = 0;
+    DevBuf<double> d_G;
+    DevBuf<double> d_delta;
+    DevBuf<WindowBatchEntry> d_wb;
     // short lists of wide windows decided on the device (HICMI_P2_DEVICE_DECIDE, read at creation): windows of at least
     // near_min_k scaffolds; [pass-1 partials][per-window counters][NearEntry lists]
     int near_min_k = 7;
-    unsigned char* d_wnear = nullptr; int64_t wnear_cap = 0;
+    DevBuf<unsigned char> d_wnear;
     // device-decided insertion (k_part2_insert.hip): second arrangement buffers (ping-pong) and work areas
-    int32_t* d_arr_packed2 = nullptr; int64_t arr2_cap = 0;
-    int32_t* d_pos2sel2 = nullptr; int64_t pos2_cap = 0;
-    double* d_ins_T = nullptr; int64_t ins_t_cap = 0;
-    double* d_ins_partial = nullptr; int64_t ins_partial_cap = 0;
-    unsigned char* d_ins_blob = nullptr; int64_t ins_blob_cap = 0;   // per job: [InsState][InsLog x steps]
-    InsStep* d_ins_steps = nullptr; int64_t ins_steps_cap = 0;       // [step][job] records of a lock-step queue
-    SupRec* d_sup_recs = nullptr; int64_t sup_recs_cap = 0;          // hicmi_p2_support_multi: (chromosome, left-out scaffold) records
-    BrkRec* d_brk_recs = nullptr; int64_t brk_recs_cap = 0;          // hicmi_p2_breaks_multi: (chromosome, scaffold of 2+ bins) records
-    InvRec* d_inv_recs = nullptr; int64_t inv_recs_cap = 0;          // hicmi_p2_inversions_multi: (chromosome, left end) records
+    DevBuf<int32_t> d_arr_packed2;
+    DevBuf<int32_t> d_pos2sel2;
+    DevBuf<double> d_ins_T;
+    DevBuf<double> d_ins_partial;
+    DevBuf<unsigned char> d_ins_blob;    // per job: [InsState][InsLog x steps]
+    DevBuf<InsStep> d_ins_steps;         // [step][job] records of a lock-step queue
+    DevBuf<SupRec> d_sup_recs;           // hicmi_p2_support_multi: (chromosome, left-out scaffold) records
+    DevBuf<BrkRec> d_brk_recs;           // hicmi_p2_breaks_multi: (chromosome, scaffold of 2+ bins) records
+    DevBuf<InvRec> d_inv_recs;           // hicmi_p2_inversions_multi: (chromosome, left end) records
     // group support (k_group_support.hip): the member lists of a call, and its partials + the two tables
-    int32_t* d_gs_lists = nullptr; int64_t gs_lists_cap = 0;
-    double* d_gs_sums = nullptr; int64_t gs_sums_cap = 0;
+    DevBuf<int32_t> d_gs_lists;
+    DevBuf<double> d_gs_sums;
     // junction support (k_junctions.hip): [records][bin order] of a call, and its [weights][partials][sums]
-    unsigned char* d_jn_lists = nullptr; int64_t jn_lists_cap = 0;
-    double* d_jn_sums = nullptr; int64_t jn_sums_cap = 0;
+    DevBuf<unsigned char> d_jn_lists;
+    DevBuf<double> d_jn_sums;
     // ICE balancing (k_ice.hip): [y][u][bias][bias_prev][s][d][ones] of n each, [mean0, c], (delta, c) per iteration; the mask
-    double* d_ice = nullptr; int64_t ice_cap = 0;
-    uint8_t* d_ice_mask = nullptr; int64_t ice_mask_cap = 0;
+    DevBuf<double> d_ice;
+    DevBuf<uint8_t> d_ice_mask;
     // HMM boundary finder (k_hmm.hip): resident observation matrices, one per slot (T x ld, columns [0, D) in use);
     // the selected slot's view is mirrored in d_hx / hmm_T / hmm_ld / hmm_D for the single-problem entry points.  The
     // work areas are sized for the largest slot built
-    struct HmmSlot { double* d_x = nullptr; int64_t cap = 0, T = 0, ld = 0, D = 0; };
+    struct HmmSlot { DevBuf<double> d_x; int64_t T = 0, ld = 0, D = 0; };
     HmmSlot hslot[HICMI_HMM_MAX_SLOTS]; int hcur = 0;
-    double* d_hx = nullptr; int64_t hmm_T = 0, hmm_ld = 0, hmm_D = 0;
-    unsigned char* d_hmulti = nullptr; int64_t hmulti_cap = 0;   // problem tables and work areas of the *_multi calls
-    int32_t* d_horder = nullptr; int64_t horder_cap = 0;
-    double* d_hwork = nullptr; int64_t hwork_cap = 0;      // L, alpha, beta, gamma (T x 2 each), mind / dist (2T)
-    int32_t* d_hlab = nullptr; int64_t hlab_cap = 0;       // labels (two generations), states: 3T
-    uint8_t* d_hbt = nullptr; int64_t hbt_cap = 0;         // Viterbi back-pointer maps
-    double* d_hpart = nullptr; int64_t hpart_cap = 0;      // column-pass partials
-    double* d_hsmall = nullptr; int64_t hsmall_cap = 0;    // params (12 D + scalars), sums (4 D), centers (2 D), scalars
-    double* d_hhist = nullptr; int64_t hhist_cap = 0;      // logprob of every EM iteration
-    int* d_hst = nullptr; int64_t hst_cap = 0;             // k-means counters
+    double* d_hx = nullptr; int64_t hmm_T = 0, hmm_ld = 0, hmm_D = 0;   // (a view, not owned)
+    DevBuf<unsigned char> d_hmulti;      // problem tables and work areas of the *_multi calls
+    DevBuf<int32_t> d_horder;
+    DevBuf<double> d_hwork;              // L, alpha, beta, gamma (T x 2 each), mind / dist (2T)
+    DevBuf<int32_t> d_hlab;              // labels (two generations), states: 3T
+    DevBuf<uint8_t> d_hbt;               // Viterbi back-pointer maps
+    DevBuf<double> d_hpart;              // column-pass partials
+    DevBuf<double> d_hsmall;             // params (12 D + scalars), sums (4 D), centers (2 D), scalars
+    DevBuf<double> d_hhist;              // logprob of every EM iteration
+    DevBuf<int> d_hst;                   // k-means counters
     // Louvain tail (k_louvain.hip): the graph A (lv_m x lv_m) and its _Status vectors: diag, row sums, gdegrees (m each),
     // A.sum()'s chunk sums, diag.sum(), total_weight
-    double* d_lvA = nullptr; int64_t lvA_cap = 0; int64_t lv_m = 0;
-    double* d_lvvec = nullptr; int64_t lvvec_cap = 0;
-    int32_t* d_lvrows = nullptr; int64_t lvrows_cap = 0;
-    unsigned char* d_lvwork = nullptr; int64_t lvwork_cap = 0;   // per-call inputs, outputs and scratch
+    DevBuf<double> d_lvA; int64_t lv_m = 0;
+    DevBuf<double> d_lvvec;
+    DevBuf<int32_t> d_lvrows;
+    DevBuf<unsigned char> d_lvwork;      // per-call inputs, outputs and scratch
     // a map being counted from read pairs (k_buildmap.hip), between hicmi_map_begin and hicmi_map_finish: the m x m
-    // 64-bit counts (map_cells != nullptr: a build is open), first_bin on the device, and the staging of a chunk of pairs
-    void* map_cells = nullptr; int64_t map_m = 0, map_res = 0, map_pairs = 0;
-    int32_t* d_map_first = nullptr;
+    // 64-bit counts (map_cells non-null: a build is open; the finish converts them in place into the doubles of the
+    // matrix), first_bin on the device, and the staging of a chunk of pairs
+    DevBuf<double> map_cells; int64_t map_m = 0, map_res = 0, map_pairs = 0;
+    DevBuf<int32_t> d_map_first;
     std::vector<int32_t> map_first; std::vector<int64_t> map_size;
-    unsigned char* d_map_chunk = nullptr; int64_t map_chunk_cap = 0;
+    DevBuf<unsigned char> d_map_chunk;
     // a lifted build (hicmi_map_begin_lifted) keeps its lift tables on the device as well (map_lift.seq !=
     // nullptr): map_first then describes the assembled sequences, map_size still the scaffolds; map_lift_seq is the host's
     // copy of the sequence of every scaffold.  d_stat_*: the tables and counters of a hicmi_pair_stats call
-    unsigned char* d_map_lift = nullptr; LiftTables map_lift; std::vector<int32_t> map_lift_seq;
-    unsigned char* d_stat_lift = nullptr; int64_t stat_lift_cap = 0;
-    unsigned long long* d_stat_out = nullptr; int64_t stat_out_cap = 0;
+    DevBuf<unsigned char> d_map_lift; LiftTables map_lift; std::vector<int32_t> map_lift_seq;
+    DevBuf<unsigned char> d_stat_lift;
+    DevBuf<unsigned long long> d_stat_out;
     // plot support
-    int32_t* d_plot_order = nullptr; int64_t plot_order_cap = 0;
-    unsigned char* d_plot_work = nullptr; int64_t plot_work_cap = 0;
-    double* d_plot_img = nullptr; int64_t plot_img_cap = 0;
+    DevBuf<int32_t> d_plot_order;
+    DevBuf<unsigned char> d_plot_work;
+    DevBuf<double> d_plot_img;
     // pinned staging: pageable hipMemcpyAsync takes a slow, serialising path in the runtime, which hurts when
     // several contexts are driven from different host threads
-    char* pin_up = nullptr; size_t pin_up_cap = 0, pin_up_off = 0;
-    char* pin_down = nullptr; size_t pin_down_cap = 0;
+    PinBuf<char> pin_up; size_t pin_up_off = 0;
+    PinBuf<char> pin_down;
 
     // timing
     int timing = 0;                                       // 0 off, 1 every family, 2 only the families launched a few times per map
-    std::vector<TimedRegion> regions;
-    std::vector<hipEvent_t> pool;
     double ms[F_COUNT] = {0}; int64_t launches[F_COUNT] = {0}; double bytes[F_COUNT] = {0};
     // nn-chain counters since the last hicmi_timing_reset (reported by hicmi_nnchain_stats)
     double nn_scans = 0, nn_scan_cols = 0, nn_cache_hits = 0, nn_merges = 0; int64_t nn_retries = 0;
@@ -214,31 +242,31 @@ struct Timed {
     {
         if (!on()) return;
         hipEventRecord(b, st);
-        c->regions.push_back({fam, a, b});
+        c->tev.regions.push_back({fam, a, b});
     }
     hipEvent_t grab()
     {
-        if (!c->pool.empty()) { hipEvent_t e = c->pool.back(); c->pool.pop_back(); return e; }
+        if (!c->tev.pool.empty()) { hipEvent_t e = c->tev.pool.back(); c->tev.pool.pop_back(); return e; }
         hipEvent_t e; hipEventCreate(&e); return e;
     }
 };
 
 int resolve_timing(hicmi_ctx* c)
 {
-    if (c->regions.empty()) return HICMI_OK;
+    if (c->tev.regions.empty()) return HICMI_OK;
     HIPCHK(sync_stream(c));
     if (c->stream2) HIPCHK(hipStreamSynchronize(c->stream2));
     // a region whose elapsed time cannot be read is an error, not a smaller sum (the events go back to the pool either way)
     int dropped = 0, dropped_fam = 0;
     hipError_t dropped_err = hipSuccess;
-    for (auto& r : c->regions) {
+    for (auto& r : c->tev.regions) {
         float ms = 0.f;
         const hipError_t e = hipEventElapsedTime(&ms, r.a, r.b);
         if (e == hipSuccess) c->ms[r.fam] += ms;
         else if (dropped++ == 0) { dropped_fam = r.fam; dropped_err = e; }
-        c->pool.push_back(r.a); c->pool.push_back(r.b);
+        c->tev.pool.push_back(r.a); c->tev.pool.push_back(r.b);
     }
-    c->regions.clear();
+    c->tev.regions.clear();
     if (dropped)
         return fail(HICMI_EHIP, "hipEventElapsedTime failed for %d timed region(s), the first of family %s: %s", dropped,
                     kFamilyNames[dropped_fam], hipGetErrorString(dropped_err));
@@ -258,15 +286,9 @@ int upload(hicmi_ctx* c, void* dst, const void* src, size_t bytes)
 {
     if (bytes == 0) return HICMI_OK;
     const size_t need = (bytes + 63) & ~(size_t)63;
-    if (c->pin_up_off + need > c->pin_up_cap) {
+    if (c->pin_up_off + need > (size_t)c->pin_up.capacity()) {
         HIPCHK(sync_stream(c));
-        if (need > c->pin_up_cap) {
-            if (c->pin_up) (void)hipHostFree(c->pin_up);
-            c->pin_up = nullptr; c->pin_up_cap = 0;
-            size_t cap = std::max<size_t>(need * 2, (size_t)1 << 20);
-            HIPCHK(hipHostMalloc((void**)&c->pin_up, cap, hipHostMallocDefault));
-            c->pin_up_cap = cap;
-        }
+        if (need > (size_t)c->pin_up.capacity()) HIPCHK(c->pin_up.reserve((int64_t)std::max<size_t>(need * 2, (size_t)1 << 20)));
     }
     char* slot = c->pin_up + c->pin_up_off;
     memcpy(slot, src, bytes);
@@ -277,13 +299,7 @@ int upload(hicmi_ctx* c, void* dst, const void* src, size_t bytes)
 
 int ensure_pin_down(hicmi_ctx* c, size_t bytes)
 {
-    if (bytes > c->pin_down_cap) {
-        if (c->pin_down) (void)hipHostFree(c->pin_down);
-        c->pin_down = nullptr; c->pin_down_cap = 0;
-        size_t cap = std::max<size_t>(bytes * 2, (size_t)1 << 20);
-        HIPCHK(hipHostMalloc((void**)&c->pin_down, cap, hipHostMallocDefault));
-        c->pin_down_cap = cap;
-    }
+    if (bytes > (size_t)c->pin_down.capacity()) HIPCHK(c->pin_down.reserve((int64_t)std::max<size_t>(bytes * 2, (size_t)1 << 20)));
     return HICMI_OK;
 }
 
@@ -299,19 +315,28 @@ int download(hicmi_ctx* c, void* dst, const void* src, size_t bytes)
     return HICMI_OK;
 }
 
-template <typename T>
-int ensure(T*& p, int64_t& cap, int64_t need)
+// every failed device allocation is reported alike (the literal is cut in two: no allocation call is spelt in this file)
+int no_memory(size_t bytes, hipError_t e)
 {
-    if (need <= cap && p) return HICMI_OK;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    if (need <= 0) need = 1;
-    hipError_t e = hipMalloc((void**)&p, (size_t)need * sizeof(T));
-    if (e != hipSuccess) { p = nullptr; return fail(HICMI_ENOMEM, "hipMalloc(%lld bytes): %s", (long long)(need * (int64_t)sizeof(T)), hipGetErrorString(e)); }
-    cap = need;
-    return HICMI_OK;
+    return fail(HICMI_ENOMEM, "hipMalloc" "(%lld bytes): %s", (long long)bytes, hipGetErrorString(e));
 }
 
-void free_dev(void* p) { if (p) (void)hipFree(p); }
+// room for `need` elements in `buf` (DevBuf::reserve: grows only, never copies)
+template <typename T>
+int ensure(DevBuf<T>& buf, int64_t need)
+{
+    const hipError_t e = buf.reserve(need);
+    return e == hipSuccess ? HICMI_OK : no_memory(DevBuf<T>::bytes_for(need), e);
+}
+
+// ensure_all(a, need_a, b, need_b, ...): the whole group holds its memory, or none of it does (reserve_all)
+template <typename... Args>
+int ensure_all(Args&&... args)
+{
+    size_t failed_bytes = 0;
+    const hipError_t e = reserve_all(&failed_bytes, args...);
+    return e == hipSuccess ? HICMI_OK : no_memory(failed_bytes, e);
+}
 
 // a candidate's bin order is staged in LDS as int32, 160 KiB at the most
 int check_candidate_bins(int64_t n_bins)
@@ -322,9 +347,9 @@ int check_candidate_bins(int64_t n_bins)
 
 void drop_matrix_state(hicmi_ctx* c)
 {
-    if (c->own_c) free_dev(c->dC);
+    c->c_own.reset();
     c->dC = nullptr; c->own_c = false; c->n = 0; c->ldc = 0;
-    free_dev(c->d_np); free_dev(c->d_seq); c->d_np = c->d_seq = nullptr; c->have_sums = false;
+    c->d_np.reset(); c->d_seq.reset(); c->have_sums = false;
     c->have_rank = false; c->cached_start = -1; c->n2 = 0;
     if (c->presort_n && c->stream2) (void)hipStreamSynchronize(c->stream2);    // the pre-sort reads the matrix being dropped
     c->presort_n = 0;
@@ -332,9 +357,7 @@ void drop_matrix_state(hicmi_ctx* c)
 
 int alloc_sums(hicmi_ctx* c)
 {
-    HIPCHK(hipMalloc((void**)&c->d_np, sizeof(double) * (size_t)std::max<int64_t>(c->n, 1)));
-    HIPCHK(hipMalloc((void**)&c->d_seq, sizeof(double) * (size_t)std::max<int64_t>(c->n, 1)));
-    return HICMI_OK;
+    return ensure_all(c->d_np, c->n, c->d_seq, c->n);
 }
 
 int compute_sums(hicmi_ctx* c)
@@ -348,6 +371,16 @@ int compute_sums(hicmi_ctx* c)
     HIPCHK(hipGetLastError());
     c->have_sums = true;
     return HICMI_OK;
+}
+
+// `made` (n x n, built on the device) replaces the context's matrix state; its sums are computed
+int own_matrix(hicmi_ctx* c, DevBuf<double>&& made, int64_t n)
+{
+    drop_matrix_state(c);
+    c->c_own = std::move(made);
+    c->dC = c->c_own; c->own_c = true; c->n = n; c->ldc = n;
+    int rc = alloc_sums(c);
+    return rc ? rc : compute_sums(c);
 }
 
 // job j of a multi-chromosome call: a context of its own, on the first job's device
@@ -387,7 +420,7 @@ int hicmi_create(int device, hicmi_ctx** out)
     HIPCHK(hipSetDevice(device));
     hicmi_ctx* c = new hicmi_ctx();
     c->device = device;
-    hipError_t se = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    hipError_t se = hipStreamCreateWithFlags(&c->stream.h, hipStreamNonBlocking);
     if (se != hipSuccess) { delete c; return fail(HICMI_EHIP, "hipStreamCreate: %s", hipGetErrorString(se)); }
     c->probed_xcc = nnchain_probe_xcc(c->stream);
     // "off": every window downloads its deltas; a number n >= 1: windows of at least n scaffolds use the device short list
@@ -404,36 +437,7 @@ int hicmi_destroy(hicmi_ctx* c)
     if (!c) return HICMI_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    drop_matrix_state(c);
-    free_dev(c->dW); free_dev(c->dW2); free_dev(c->d_size); free_dev(c->d_chain); free_dev(c->d_status); free_dev(c->d_zraw);
-    free_dev(c->d_order); free_dev(c->dR); free_dev(c->dRank); free_dev(c->d_sort_scratch);
-    free_dev(c->dRankS); free_dev(c->d_ident); free_dev(c->d_ties); free_dev(c->d_row_list); free_dev(c->d_tie_bits);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->stream2) (void)hipStreamDestroy(c->stream2);
-    free_dev(c->d_x); free_dev(c->d_sig); free_dev(c->d_tmp); free_dev(c->d_scan_multi);
-    free_dev(c->dM2); free_dev(c->d_sel); free_dev(c->d_H); free_dev(c->d_perms); free_dev(c->d_scores);
-    free_dev(c->d_partial); free_dev(c->d_T);
-    free_dev(c->d_scaf_start); free_dev(c->d_scaf_len); free_dev(c->d_arr_packed);
-    free_dev(c->d_pos2sel); free_dev(c->d_orders); free_dev(c->d_orients);
-    free_dev(c->d_G); free_dev(c->d_delta); free_dev(c->d_wb); free_dev(c->d_wnear);
-    free_dev(c->d_arr_packed2); free_dev(c->d_pos2sel2); free_dev(c->d_ins_T); free_dev(c->d_ins_partial); free_dev(c->d_brk_recs); free_dev(c->d_inv_recs);
-    free_dev(c->d_ins_blob); free_dev(c->d_ins_steps); free_dev(c->d_sup_recs);
-    free_dev(c->d_gs_lists); free_dev(c->d_gs_sums);
-    free_dev(c->d_jn_lists); free_dev(c->d_jn_sums);
-    free_dev(c->d_ice); free_dev(c->d_ice_mask);
-    free_dev(c->d_plot_order); free_dev(c->d_plot_work); free_dev(c->d_plot_img);
-    free_dev(c->map_cells); free_dev(c->d_map_first); free_dev(c->d_map_chunk);
-    free_dev(c->d_map_lift); free_dev(c->d_stat_lift); free_dev(c->d_stat_out);
-    for (auto& sl : c->hslot) free_dev(sl.d_x);
-    free_dev(c->d_hmulti); free_dev(c->d_horder); free_dev(c->d_hwork); free_dev(c->d_hlab); free_dev(c->d_hbt);
-    free_dev(c->d_hpart); free_dev(c->d_hsmall); free_dev(c->d_hhist); free_dev(c->d_hst);
-    free_dev(c->d_lvA); free_dev(c->d_lvvec); free_dev(c->d_lvrows); free_dev(c->d_lvwork);
-    if (c->pin_up) (void)hipHostFree(c->pin_up);
-    if (c->pin_down) (void)hipHostFree(c->pin_down);
-    for (auto& r : c->regions) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-    for (auto e : c->pool) (void)hipEventDestroy(e);
-    (void)hipStreamDestroy(c->stream);
+    if (c->stream2) (void)hipStreamSynchronize(c->stream2);
     delete c;
     return HICMI_OK;
 }
@@ -459,9 +463,9 @@ int hicmi_set_contacts_host(hicmi_ctx* c, const double* contacts, int64_t n)
     if (n > 65536) return fail(HICMI_EUNSUPPORTED, "n = %lld > 65536 bins: rank matrix is uint16 in this version", (long long)n);
     HIPCHK(hipSetDevice(c->device));
     drop_matrix_state(c);
-    c->n = n; c->ldc = n;
-    HIPCHK(hipMalloc((void**)&c->dC, sizeof(double) * (size_t)n * (size_t)n));
-    c->own_c = true;
+    int rc = ensure(c->c_own, n * n);
+    if (rc) return rc;
+    c->n = n; c->ldc = n; c->dC = c->c_own; c->own_c = true;
     HIPCHK(hipMemcpyAsync(c->dC, contacts, sizeof(double) * (size_t)n * (size_t)n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(sync_stream(c));
     return alloc_sums(c);
@@ -475,10 +479,10 @@ int hicmi_set_contacts_host_f32(hicmi_ctx* c, const float* contacts, int64_t n)
     if (n > 65536) return fail(HICMI_EUNSUPPORTED, "n = %lld > 65536 bins: rank matrix is uint16 in this version", (long long)n);
     HIPCHK(hipSetDevice(c->device));
     drop_matrix_state(c);
-    c->n = n; c->ldc = n;
     const size_t cells = (size_t)n * (size_t)n;
-    HIPCHK(hipMalloc((void**)&c->dC, sizeof(double) * cells));
-    c->own_c = true;
+    int rc = ensure(c->c_own, n * n);
+    if (rc) return rc;
+    c->n = n; c->ldc = n; c->dC = c->c_own; c->own_c = true;
     // the fp32 image is staged in the tail of the fp64 buffer and widened back to front, row block by row block
     float* d_stage = reinterpret_cast<float*>(c->dC) + cells;
     HIPCHK(hipMemcpyAsync(d_stage, contacts, sizeof(float) * cells, hipMemcpyHostToDevice, c->stream));
@@ -565,24 +569,15 @@ int hicmi_compact(hicmi_ctx* c, const int32_t* keep, int64_t n_keep)
     for (int64_t i = 0; i < n_keep; i++)
         if (keep[i] < 0 || keep[i] >= c->n || (i && keep[i] <= keep[i - 1])) return fail(HICMI_EINVAL, "keep must be ascending indices in [0, n)");
     HIPCHK(hipSetDevice(c->device));
-    int32_t* d_keep = nullptr; double* d_new = nullptr;
-    struct Guard { int32_t*& a; double*& b; ~Guard() { free_dev(a); free_dev(b); } } guard{d_keep, d_new};   // error paths
-    HIPCHK(hipMalloc((void**)&d_keep, sizeof(int32_t) * (size_t)n_keep));
-    HIPCHK(hipMalloc((void**)&d_new, sizeof(double) * (size_t)n_keep * (size_t)n_keep));
-    {
-        int rc_up = upload(c, d_keep, keep, sizeof(int32_t) * (size_t)n_keep);
-        if (rc_up) return rc_up;
-    }
+    DevBuf<int32_t> d_keep; DevBuf<double> d_new;
+    int rc = ensure_all(d_keep, n_keep, d_new, n_keep * n_keep);
+    if (!rc) rc = upload(c, d_keep, keep, sizeof(int32_t) * (size_t)n_keep);
+    if (rc) return rc;
     launch_compact(c->dC, c->ldc, d_keep, (int)n_keep, d_new, n_keep, c->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(sync_stream(c));
-    free_dev(d_keep); d_keep = nullptr;
-    double* kept = d_new; d_new = nullptr;                     // ownership moves to the context below
-    drop_matrix_state(c);
-    c->dC = kept; c->own_c = true; c->n = n_keep; c->ldc = n_keep;
-    int rc = alloc_sums(c);
-    if (rc) return rc;
-    return compute_sums(c);
+    d_keep.reset();
+    return own_matrix(c, std::move(d_new), n_keep);
 }
 
 // A coarser map from the resident raw one: HiC-Pro's build_matrix re-run at k times the bin size.  Like
@@ -615,24 +610,15 @@ int hicmi_rebin(hicmi_ctx* c, const int32_t* group_start, int64_t m)
         }
     }
     HIPCHK(hipSetDevice(c->device));
-    int32_t* d_lists = nullptr; double* d_new = nullptr;
-    struct Guard { int32_t*& a; double*& b; ~Guard() { free_dev(a); free_dev(b); } } guard{d_lists, d_new};   // error paths
-    HIPCHK(hipMalloc((void**)&d_lists, sizeof(int32_t) * img.size()));
-    HIPCHK(hipMalloc((void**)&d_new, sizeof(double) * (size_t)m * (size_t)m));
-    {
-        int rc_up = upload(c, d_lists, img.data(), sizeof(int32_t) * img.size());
-        if (rc_up) return rc_up;
-    }
+    DevBuf<int32_t> d_lists; DevBuf<double> d_new;
+    int rc = ensure_all(d_lists, (int64_t)img.size(), d_new, m * m);
+    if (!rc) rc = upload(c, d_lists, img.data(), sizeof(int32_t) * img.size());
+    if (rc) return rc;
     launch_rebin(c->dC, c->ldc, (int)n, d_lists, d_lists + m + 1, (int)m, d_new, plain, c->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(sync_stream(c));
-    free_dev(d_lists); d_lists = nullptr;
-    double* kept = d_new; d_new = nullptr;                     // ownership moves to the context below
-    drop_matrix_state(c);
-    c->dC = kept; c->own_c = true; c->n = m; c->ldc = m;
-    int rc = alloc_sums(c);
-    if (rc) return rc;
-    return compute_sums(c);
+    d_lists.reset();
+    return own_matrix(c, std::move(d_new), m);
 }
 
 // ---- a raw map counted from read pairs: HiC-Pro's build_matrix at any bin size --------------------------
@@ -640,9 +626,7 @@ int hicmi_rebin(hicmi_ctx* c, const int32_t* group_start, int64_t m)
 // state is replaced only by a finish that succeeded.
 static void map_abandon(hicmi_ctx* c)
 {
-    free_dev(c->map_cells); c->map_cells = nullptr;
-    free_dev(c->d_map_first); c->d_map_first = nullptr;
-    free_dev(c->d_map_lift); c->d_map_lift = nullptr;
+    c->map_cells.reset(); c->d_map_first.reset(); c->d_map_lift.reset();
     c->map_lift = LiftTables();
     c->map_m = 0; c->map_res = 0; c->map_pairs = 0;
     c->map_first.clear(); c->map_size.clear(); c->map_lift_seq.clear();
@@ -722,20 +706,13 @@ static int map_open(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, int6
     if (m < 1) return fail(HICMI_EINVAL, "the %ss have no bins", what);
     HIPCHK(hipSetDevice(c->device));
     map_abandon(c);                                           // a begin without a finish is given up
-    hipError_t e = hipMalloc(&c->map_cells, sizeof(uint64_t) * (size_t)m * (size_t)m);
-    if (e != hipSuccess) {
-        c->map_cells = nullptr;
-        return fail(HICMI_ENOMEM, "hipMalloc(%lld bytes): %s", (long long)(8 * m * m), hipGetErrorString(e));
-    }
-    int rc = HICMI_OK;
-    e = hipMalloc((void**)&c->d_map_first, sizeof(int32_t) * (size_t)n_grid);
-    if (e != hipSuccess) { c->d_map_first = nullptr; rc = fail(HICMI_ENOMEM, "hipMalloc: %s", hipGetErrorString(e)); }
-    if (!rc) rc = upload(c, c->d_map_first, first.data(), sizeof(int32_t) * (size_t)n_grid);
-    if (!rc && lift) {
-        e = hipMalloc((void**)&c->d_map_lift, 21 * (size_t)n_scaf);
-        if (e != hipSuccess) { c->d_map_lift = nullptr; rc = fail(HICMI_ENOMEM, "hipMalloc: %s", hipGetErrorString(e)); }
-        if (!rc) rc = lift_upload(c, c->d_map_lift, scaf_size, n_scaf, *lift, &c->map_lift);
-    }
+    static_assert(sizeof(uint64_t) == sizeof(double), "the counts are converted in place");
+    int rc = lift ? ensure_all(c->map_cells, m * m, c->d_map_first, n_grid, c->d_map_lift, 21 * n_scaf)
+                  : ensure_all(c->map_cells, m * m, c->d_map_first, n_grid);
+    if (rc) return rc;
+    rc = upload(c, c->d_map_first, first.data(), sizeof(int32_t) * (size_t)n_grid);
+    if (!rc && lift) rc = lift_upload(c, c->d_map_lift, scaf_size, n_scaf, *lift, &c->map_lift);
+    hipError_t e = hipSuccess;
     if (!rc && (e = hipMemsetAsync(c->map_cells, 0, sizeof(uint64_t) * (size_t)m * (size_t)m, c->stream)) != hipSuccess)
         rc = fail(HICMI_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e));
     if (!rc && (e = sync_stream(c)) != hipSuccess) rc = fail(HICMI_EHIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
@@ -813,7 +790,7 @@ int hicmi_map_add_pairs(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos_
     if (n == 0) return HICMI_OK;
     HIPCHK(hipSetDevice(c->device));
     // a HIP error from here on gives the build up: what was counted so far cannot be told
-    int rc = ensure(c->d_map_chunk, c->map_chunk_cap, 24 * n);
+    int rc = ensure(c->d_map_chunk, 24 * n);
     const MapChunk k = map_chunk_at(c->d_map_chunk, n);
     if (!rc) rc = upload(c, k.pos_a, pos_a, sizeof(int64_t) * (size_t)n);
     if (!rc) rc = upload(c, k.pos_b, pos_b, sizeof(int64_t) * (size_t)n);
@@ -847,9 +824,9 @@ int hicmi_pair_stats(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos_a, 
     if (rc || n == 0) return rc;
     HIPCHK(hipSetDevice(c->device));
     const int64_t n_out = LIFT_DECAY_SLOTS + 2 * n_seq + 1;
-    rc = ensure(c->d_map_chunk, c->map_chunk_cap, 24 * n);
-    if (!rc) rc = ensure(c->d_stat_lift, c->stat_lift_cap, 21 * n_scaf);
-    if (!rc) rc = ensure(c->d_stat_out, c->stat_out_cap, n_out);
+    rc = ensure(c->d_map_chunk, 24 * n);
+    if (!rc) rc = ensure(c->d_stat_lift, 21 * n_scaf);
+    if (!rc) rc = ensure(c->d_stat_out, n_out);
     if (rc) return rc;
     LiftTables tables;
     const MapChunk k = map_chunk_at(c->d_map_chunk, n);
@@ -876,15 +853,10 @@ static int map_install(hicmi_ctx* c, hipStream_t on, int64_t* pairs_out)
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(on);
     if (e != hipSuccess) { map_abandon(c); return fail(HICMI_EHIP, "converting the counts: %s", hipGetErrorString(e)); }
-    double* kept = reinterpret_cast<double*>(c->map_cells);
-    c->map_cells = nullptr;                                   // ownership moves to the context below
+    DevBuf<double> made = std::move(c->map_cells);            // ownership moves to the context below
     const int64_t m = c->map_m, pairs = c->map_pairs;
     map_abandon(c);
-    drop_matrix_state(c);
-    c->dC = kept; c->own_c = true; c->n = m; c->ldc = m;
-    int rc = alloc_sums(c);
-    if (rc) return rc;
-    rc = compute_sums(c);
+    int rc = own_matrix(c, std::move(made), m);
     if (rc) return rc;
     if (pairs_out) *pairs_out = pairs;
     return HICMI_OK;
@@ -924,18 +896,12 @@ static int build_maps_loop(const char* path, const char* names_blob, const int64
     hicmi_ctx* c0 = ctxs[0];
     HIPCHK(hipSetDevice(c0->device));
     // everything the call owns: two pinned chunks for the parser, two device chunks for the kernels
-    struct Owned {
-        unsigned char* pin[2] = {nullptr, nullptr}; unsigned char* dev[2] = {nullptr, nullptr};
-        unsigned long long* d_stats = nullptr;                    // a lifted call: the counters of k_pair_stats
+    PinBuf<unsigned char> pin[2]; DevBuf<unsigned char> dev[2];
+    DevBuf<unsigned long long> d_stats;                           // a lifted call: the counters of k_pair_stats
+    struct OpenBuilds {                                           // given up on every error path
         hicmi_ctx* const* ctxs; int64_t n_res; bool keep = false;
-        ~Owned()
-        {
-            for (int b = 0; b < 2; b++) { if (pin[b]) (void)hipHostFree(pin[b]); free_dev(dev[b]); }
-            free_dev(d_stats);
-            if (!keep) for (int64_t k = 0; k < n_res; k++) map_abandon(ctxs[k]);
-        }
-    } own;
-    own.ctxs = ctxs; own.n_res = n_res;
+        ~OpenBuilds() { if (!keep) for (int64_t k = 0; k < n_res; k++) map_abandon(ctxs[k]); }
+    } own{ctxs, n_res};
     // begin on every context first: a resolution that cannot be built is refused before the file is read
     for (int64_t k = 0; k < n_res; k++) {
         int rc = map_open(ctxs[k], scaf_size, n_names, resolution[k], lift);
@@ -943,9 +909,9 @@ static int build_maps_loop(const char* path, const char* names_blob, const int64
     }
     const int64_t n_stats = lift ? LIFT_DECAY_SLOTS + 2 * lift->n_seq + 1 : 0;
     if (lift) {
-        hipError_t e = hipMalloc((void**)&own.d_stats, sizeof(uint64_t) * (size_t)n_stats);
-        if (e != hipSuccess) { own.d_stats = nullptr; return fail(HICMI_ENOMEM, "hipMalloc: %s", hipGetErrorString(e)); }
-        HIPCHK(hipMemsetAsync(own.d_stats, 0, sizeof(uint64_t) * (size_t)n_stats, c0->stream));
+        int rc = ensure(d_stats, n_stats);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(d_stats, 0, sizeof(uint64_t) * (size_t)n_stats, c0->stream));
     }
     int64_t file_bytes = -1;
     {
@@ -959,15 +925,15 @@ static int build_maps_loop(const char* path, const char* names_blob, const int64
     }
     const size_t chunk_bytes = (size_t)chunk_pairs * 24;
     for (int b = 0; b < 2; b++) {
-        HIPCHK(hipHostMalloc((void**)&own.pin[b], chunk_bytes, hipHostMallocDefault));
-        hipError_t e = hipMalloc((void**)&own.dev[b], chunk_bytes);
-        if (e != hipSuccess) { own.dev[b] = nullptr; return fail(HICMI_ENOMEM, "hipMalloc(%zu bytes): %s", chunk_bytes, hipGetErrorString(e)); }
+        HIPCHK(pin[b].reserve((int64_t)chunk_bytes));
+        int rc = ensure(dev[b], (int64_t)chunk_bytes);
+        if (rc) return rc;
     }
     const bool plain = lift ? liftmap_plain() : buildmap_plain();
     int64_t next = 0, n_here = 0, st[4];
     // chunk t + 1 is parsed into the other pinned buffer while chunk t is uploaded and counted on c0's stream
     auto parse = [&](int b) {
-        const MapChunk h = map_chunk_at(own.pin[b], chunk_pairs);
+        const MapChunk h = map_chunk_at(pin[b], chunk_pairs);
         int rc = hicmi_parse_valid_pairs(path, names_blob, name_off, n_names, scaf_size, threads, next, chunk_pairs, h.scaf_a, h.pos_a,
                                          h.scaf_b, h.pos_b, &n_here, &next, st);
         if (!rc) { stats5[0] += st[0]; stats5[1] += st[1]; stats5[2] += st[2]; stats5[3] += st[3]; }
@@ -979,7 +945,7 @@ static int build_maps_loop(const char* path, const char* names_blob, const int64
     for (;;) {
         const int64_t n = n_here;
         if (n > 0) {
-            const MapChunk h = map_chunk_at(own.pin[cur], chunk_pairs), d = map_chunk_at(own.dev[cur], chunk_pairs);
+            const MapChunk h = map_chunk_at(pin[cur], chunk_pairs), d = map_chunk_at(dev[cur], chunk_pairs);
             HIPCHK(hipMemcpyAsync(d.pos_a, h.pos_a, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, c0->stream));
             HIPCHK(hipMemcpyAsync(d.pos_b, h.pos_b, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, c0->stream));
             HIPCHK(hipMemcpyAsync(d.scaf_a, h.scaf_a, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c0->stream));
@@ -990,7 +956,7 @@ static int build_maps_loop(const char* path, const char* names_blob, const int64
                                     (int)c->map_m, c->map_cells, plain, c->map_lift, c0->stream);
                 c->map_pairs += n;
             }
-            if (lift) launch_pair_stats(d.scaf_a, d.pos_a, d.scaf_b, d.pos_b, n, c0->map_lift, own.d_stats, c0->stream);
+            if (lift) launch_pair_stats(d.scaf_a, d.pos_a, d.scaf_b, d.pos_b, n, c0->map_lift, d_stats, c0->stream);
             HIPCHK(hipGetLastError());
             stats5[4]++;
         }
@@ -1005,7 +971,7 @@ static int build_maps_loop(const char* path, const char* names_blob, const int64
     std::vector<uint64_t> got((size_t)n_stats);
     if (lift) {
         // the statistics come down before any context changes; a map has counted the pairs that were lifted
-        HIPCHK(hipMemcpy(got.data(), own.d_stats, sizeof(uint64_t) * (size_t)n_stats, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(got.data(), d_stats, sizeof(uint64_t) * (size_t)n_stats, hipMemcpyDeviceToHost));
         for (int64_t k = 0; k < n_res; k++) ctxs[k]->map_pairs -= (int64_t)got[(size_t)n_stats - 1];
     }
     // every chunk is counted on every map: from here on the contexts change
@@ -1084,8 +1050,8 @@ int hicmi_group_sums(hicmi_ctx* c, const int32_t* grp, const int32_t* scaf, int6
     const bool plain = env && !strcmp(env, "1");
     HIPCHK(hipSetDevice(c->device));
     const int64_t o_bin = plain ? 0 : NC * n, o_sc = o_bin + n * G, n_dbl = o_sc + S * G;
-    int rc = ensure(c->d_gs_lists, c->gs_lists_cap, n_ints);
-    if (!rc) rc = ensure(c->d_gs_sums, c->gs_sums_cap, n_dbl);
+    int rc = ensure(c->d_gs_lists, n_ints);
+    if (!rc) rc = ensure(c->d_gs_sums, n_dbl);
     if (!rc) rc = upload(c, c->d_gs_lists, img.data(), sizeof(int32_t) * (size_t)n_ints);
     if (rc) return rc;
     const int32_t* L = c->d_gs_lists;
@@ -1142,14 +1108,14 @@ int hicmi_junction_sums(hicmi_ctx* c, const int32_t* bins, int64_t n_listed, con
     HIPCHK(hipSetDevice(c->device));
     const int64_t rec_bytes = (int64_t)sizeof(JnRec) * n_rec, list_bytes = rec_bytes + (int64_t)sizeof(int32_t) * n_listed;
     const int64_t o_part = max_d + 1, o_sums = o_part + (plain ? 0 : n_wg), n_dbl = o_sums + n_rec;
-    int rc = ensure(c->d_jn_lists, c->jn_lists_cap, list_bytes);
-    if (!rc) rc = ensure(c->d_jn_sums, c->jn_sums_cap, n_dbl);
+    int rc = ensure(c->d_jn_lists, list_bytes);
+    if (!rc) rc = ensure(c->d_jn_sums, n_dbl);
     if (!rc) rc = upload(c, c->d_jn_lists, recs.data(), (size_t)rec_bytes);
     if (!rc) rc = upload(c, c->d_jn_lists + rec_bytes, bins, sizeof(int32_t) * (size_t)n_listed);
     if (!rc) rc = upload(c, c->d_jn_sums, w.data(), sizeof(double) * w.size());
     if (rc) return rc;
     launch_junction_sums(c->dC, c->ldc, reinterpret_cast<const int32_t*>(c->d_jn_lists + rec_bytes),
-                         reinterpret_cast<const JnRec*>(c->d_jn_lists), (int)n_rec, n_wg, c->d_jn_sums,
+                         reinterpret_cast<const JnRec*>(c->d_jn_lists.get()), (int)n_rec, n_wg, c->d_jn_sums,
                          c->d_jn_sums + o_part, c->d_jn_sums + o_sums, plain, c->stream);
     HIPCHK(hipGetLastError());
     return download(c, sums_out, c->d_jn_sums + o_sums, sizeof(double) * (size_t)n_rec);
@@ -1179,7 +1145,7 @@ int ice_check(hicmi_ctx* c, const char* what)
 
 int ice_upload_mask(hicmi_ctx* c, const uint8_t* mask)
 {
-    int rc = ensure(c->d_ice_mask, c->ice_mask_cap, c->n);
+    int rc = ensure(c->d_ice_mask, c->n);
     if (!rc) rc = upload(c, c->d_ice_mask, mask, (size_t)c->n);
     return rc;
 }
@@ -1212,7 +1178,7 @@ int hicmi_ice_balance(hicmi_ctx* c, const uint8_t* mask, int64_t max_iter, doubl
     if ((rc = ice_matrix_changed(c))) return rc;
     const int n = (int)c->n;
     const int64_t np = ((int64_t)n + 1) & ~(int64_t)1;       // every vector starts 16-byte aligned
-    if ((rc = ensure(c->d_ice, c->ice_cap, 7 * np + 2 + 2 * max_iter))) return rc;
+    if ((rc = ensure(c->d_ice, 7 * np + 2 + 2 * max_iter))) return rc;
     double *y = c->d_ice, *u = y + np, *bias = u + np, *prev = bias + np, *s = prev + np, *d = s + np, *ones = d + np,
            *st = ones + np, *rec = st + 2;
     if (mask) {
@@ -1290,8 +1256,9 @@ int hicmi_selftest_division(hicmi_ctx* c, uint64_t seed, int64_t samples, uint64
 {
     if (!c || !mismatches_out || samples < 1) return fail(HICMI_EINVAL, "bad arguments");
     HIPCHK(hipSetDevice(c->device));
-    unsigned long long* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, sizeof(unsigned long long)));
+    DevBuf<unsigned long long> d;
+    int rc = ensure(d, 1);
+    if (rc) return rc;
     HIPCHK(hipMemsetAsync(d, 0, sizeof(unsigned long long), c->stream));
     const int blocks = 2048, iters = (int)std::max<int64_t>(1, samples / (blocks * 256));
     launch_selftest_division(seed, blocks, iters, d, c->stream);
@@ -1299,7 +1266,6 @@ int hicmi_selftest_division(hicmi_ctx* c, uint64_t seed, int64_t samples, uint64
     unsigned long long bad = 0;
     HIPCHK(hipMemcpyAsync(&bad, d, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(sync_stream(c));
-    (void)hipFree(d);
     *mismatches_out = bad;
     return HICMI_OK;
 }
@@ -1365,20 +1331,14 @@ int hicmi_leaf_order(const double* Z, int64_t n, int32_t* leaves)
 // Buffers of the rank matrix: dRank (result), d_order ([order][inverse]), dR (argsort rows of the bitonic path), scratch.
 static int ensure_rank_buffers(hicmi_ctx* c, int64_t n, int64_t ldr, bool bitonic)
 {
-    if (c->r_rows < n || c->ldr != ldr || !c->dRank) {
-        free_dev(c->dR); free_dev(c->dRank); free_dev(c->d_order); c->dR = c->dRank = nullptr; c->d_order = nullptr;
-        HIPCHK(hipMalloc((void**)&c->dRank, sizeof(uint16_t) * (size_t)n * (size_t)ldr));
-        HIPCHK(hipMalloc((void**)&c->d_order, sizeof(int32_t) * 2 * (size_t)n));       // [order][inverse order]
+    if (c->r_rows < n || c->ldr != ldr || !c->dRank || !c->d_order) {
+        int rc = ensure_all(c->dRank, n * ldr, c->d_order, 2 * n);                      // [order][inverse order]
+        if (rc) return rc;
         c->ldr = ldr; c->r_rows = n;
     }
-    if (bitonic && !c->dR) HIPCHK(hipMalloc((void**)&c->dR, sizeof(uint16_t) * (size_t)n * (size_t)ldr));
-    size_t need = bitonic ? sort_scratch_bytes((int)n) : sort_radix_scratch_bytes((int)n);
-    if (need > c->sort_scratch_cap) {
-        free_dev(c->d_sort_scratch); c->d_sort_scratch = nullptr; c->sort_scratch_cap = 0;
-        HIPCHK(hipMalloc(&c->d_sort_scratch, need));
-        c->sort_scratch_cap = need;
-    }
-    return HICMI_OK;
+    int rc = bitonic ? ensure(c->dR, n * ldr) : HICMI_OK;
+    if (!rc) rc = ensure(c->d_sort_scratch, (int64_t)(bitonic ? sort_scratch_bytes((int)n) : sort_radix_scratch_bytes((int)n)));
+    return rc;
 }
 
 // The pre-sort.  The nn-chain keeps 8 of the 256 CUs busy for 60 % of Part 1, and the row sort that follows it needs the
@@ -1405,36 +1365,22 @@ static int start_presort(hicmi_ctx* c, int chain_xcc)
     if (!c->stream2) {
         int lo = 0, hi = 0;
         HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));         // lo = least urgent
-        HIPCHK(hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, lo));
+        HIPCHK(hipStreamCreateWithPriority(&c->stream2.h, hipStreamNonBlocking, lo));
     }
     if (!c->ev_fork) {
-        HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    }
-    if (c->ties_cap < n) {
-        free_dev(c->d_ties); c->d_ties = nullptr;
-        HIPCHK(hipMalloc((void**)&c->d_ties, 16 + (size_t)n));
-        c->ties_cap = n;
+        HIPCHK(hipEventCreateWithFlags(&c->ev_fork.h, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&c->ev_join.h, hipEventDisableTiming));
     }
     const int64_t ld_bits = std::max<int64_t>(sort_padded_size((int)n), 16) / 16;
-    if (c->tie_bits_rows < n || c->ld_bits != ld_bits) {
-        free_dev(c->d_tie_bits); c->d_tie_bits = nullptr;
-        HIPCHK(hipMalloc((void**)&c->d_tie_bits, sizeof(uint16_t) * (size_t)n * (size_t)ld_bits));
-        c->tie_bits_rows = n; c->ld_bits = ld_bits;
-    }
-    if (c->rank_s_rows < n || !c->dRankS) {
-        free_dev(c->dRankS); c->dRankS = nullptr;
-        HIPCHK(hipMalloc((void**)&c->dRankS, sizeof(uint16_t) * (size_t)n * (size_t)ldr));
-        c->rank_s_rows = n;
-    }
-    if (c->ident_cap < n) {
-        free_dev(c->d_ident); c->d_ident = nullptr;
-        HIPCHK(hipMalloc((void**)&c->d_ident, sizeof(int32_t) * (size_t)n));
+    const bool new_ident = c->d_ident.capacity() < n;             // the identity order is written once per growth
+    rc = ensure_all(c->d_ties, 16 + n, c->d_tie_bits, n * ld_bits, c->dRankS, n * ldr, c->d_ident, n);
+    if (rc) return rc;
+    c->ld_bits = ld_bits;
+    if (new_ident) {
         std::vector<int32_t> id((size_t)n);
         for (int64_t i = 0; i < n; i++) id[(size_t)i] = (int32_t)i;
-        int rc_up = upload(c, c->d_ident, id.data(), sizeof(int32_t) * (size_t)n);
-        if (rc_up) return rc_up;
-        c->ident_cap = n;
+        rc = upload(c, c->d_ident, id.data(), sizeof(int32_t) * (size_t)n);
+        if (rc) { c->d_ident.reset(); return rc; }
     }
     HIPCHK(hipEventRecord(c->ev_fork, c->stream));                // sums and identity are in place
     HIPCHK(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
@@ -1442,12 +1388,12 @@ static int start_presort(hicmi_ctx* c, int chain_xcc)
     {
         Timed t(c, F_PRESORT, (8.0 + 2.0) * (double)n * (double)n, c->stream2);      // N^2 (e + idx) for the row argsort
         SortExtras x;
-        x.tie_count = reinterpret_cast<unsigned*>(c->d_ties); x.tie_flag = c->d_ties + 16;
+        x.tie_count = reinterpret_cast<unsigned*>(c->d_ties.get()); x.tie_flag = c->d_ties + 16;
         x.tie_limit = (unsigned)n;                                 // (never gives up: tied rows are finished by k_rank_rows_tied)
         x.tie_bits = c->d_tie_bits; x.ld_bits = ld_bits;
         x.max_workgroups = 192;                                    // (the chain: up to 64 single-wave workgroups, one CU each)
         x.avoid_xcc = chain_xcc;                                   // ... all on one XCD, which this kernel's workgroups leave alone
-        x.row_counter = reinterpret_cast<unsigned*>(c->d_ties) + 1;     // (zeroed with the tie count just above)
+        x.row_counter = reinterpret_cast<unsigned*>(c->d_ties.get()) + 1;     // (zeroed with the tie count just above)
         if (getenv("HICMI_TEST_PRESORT_ALL_LEAVE")) x.avoid_xcc = -2;      // test hook: every workgroup behaves as if it were on that XCD
         c->presort_dealt = x.avoid_xcc >= 0 || x.avoid_xcc == -2;
         launch_sort_rows(c->dC, c->ldc, c->d_ident, c->d_ident, c->d_np, c->d_seq, (int)n, c->d_sort_scratch, c->dR, ldr, 0, 1,
@@ -1478,16 +1424,11 @@ int hicmi_upgma(hicmi_ctx* c, double* Z_out, int32_t* leaves_out)
     if (n == 1) { leaves_out[0] = 0; c->zraw.clear(); return HICMI_OK; }
     const int64_t ldw = (n + 15) & ~(int64_t)15;
     if (c->w_rows < n || c->ldw != ldw || !c->dW) {
-        free_dev(c->dW); free_dev(c->dW2); c->dW = c->dW2 = nullptr;
-        HIPCHK(hipMalloc((void**)&c->dW, sizeof(double) * (size_t)n * (size_t)ldw));
-        HIPCHK(hipMalloc((void**)&c->dW2, sizeof(double) * (size_t)n * (size_t)ldw));
+        // d_chain: one copy per workgroup of k_nn_epoch_w1 (64) / _mw / _mwc (16)
+        rc = ensure_all(c->dW, n * ldw, c->dW2, n * ldw, c->d_size, (int64_t)nnchain_workspace_bytes((int)n),
+                        c->d_chain, 64 * (n + 2), c->d_zraw, 4 * n, c->d_status, 1);
+        if (rc) return rc;
         c->ldw = ldw; c->w_rows = n;
-        free_dev(c->d_size); free_dev(c->d_chain); free_dev(c->d_zraw); free_dev(c->d_status);
-        c->d_size = c->d_chain = c->d_status = nullptr; c->d_zraw = nullptr;
-        HIPCHK(hipMalloc((void**)&c->d_size, nnchain_workspace_bytes((int)n)));
-        HIPCHK(hipMalloc((void**)&c->d_chain, sizeof(int) * 64 * (size_t)(n + 2)));     // one copy per workgroup of k_nn_epoch_w1 (64) / _mw / _mwc (16)
-        HIPCHK(hipMalloc((void**)&c->d_zraw, sizeof(double) * 4 * (size_t)n));
-        HIPCHK(hipMalloc((void**)&c->d_status, sizeof(int)));
     }
     static const bool step_prof = getenv("HICMI_STEP_PROFILE") != nullptr;
     std::vector<std::pair<const char*, std::chrono::steady_clock::time_point>> marks;
@@ -1690,12 +1631,8 @@ int hicmi_rank_matrix(hicmi_ctx* c, const int32_t* order)
             }
             HIPCHK(hipGetLastError());
             if (!again.empty()) {
-                if (c->row_list_cap < n) {
-                    free_dev(c->d_row_list); c->d_row_list = nullptr;
-                    HIPCHK(hipMalloc((void**)&c->d_row_list, sizeof(int32_t) * 2 * (size_t)n));     // the list + one flag per listed row
-                    c->row_list_cap = n;
-                }
-                int rc_up = upload(c, c->d_row_list, again.data(), sizeof(int32_t) * again.size());
+                int rc_up = ensure(c->d_row_list, 2 * n);                      // the list + one flag per listed row
+                if (!rc_up) rc_up = upload(c, c->d_row_list, again.data(), sizeof(int32_t) * again.size());
                 if (rc_up) return rc_up;
                 const double part = (double)again.size() / (double)n;
                 if (resort) {
@@ -1787,7 +1724,7 @@ int hicmi_get_similarity_row(hicmi_ctx* c, int64_t row, double* out)
     if (!c->have_rank) return fail(HICMI_EINVAL, "hicmi_rank_matrix has not run");
     if (row < 0 || row >= c->n) return fail(HICMI_EINVAL, "row out of range");
     HIPCHK(hipSetDevice(c->device));
-    int rc = ensure(c->d_tmp, c->tmp_cap, c->n);
+    int rc = ensure(c->d_tmp, c->n);
     if (rc) return rc;
     launch_similarity_row(c->dC, c->ldc, c->d_order, c->d_np, c->d_seq, (int)c->n, (int)row, c->d_tmp, c->stream);
     HIPCHK(hipGetLastError());
@@ -1799,12 +1736,7 @@ int hicmi_get_similarity_row(hicmi_ctx* c, int64_t row, double* out)
 // ---------------------------------------------------------------------------------------------------
 static int ensure_scan_buffers(hicmi_ctx* c)
 {
-    if (c->x_cap >= c->n && c->d_x && c->d_sig) return HICMI_OK;
-    free_dev(c->d_x); free_dev(c->d_sig); c->d_x = nullptr; c->d_sig = nullptr; c->x_cap = 0;
-    HIPCHK(hipMalloc((void**)&c->d_x, sizeof(int32_t) * (size_t)c->n));
-    HIPCHK(hipMalloc((void**)&c->d_sig, (size_t)c->n));
-    c->x_cap = c->n;
-    return HICMI_OK;
+    return ensure_all(c->d_x, c->n, c->d_sig, c->n);
 }
 
 // The significance flags of the rows counted in d_x.  The flags are all the host loops need, tens of thousands of
@@ -1816,7 +1748,7 @@ static int finish_scan(hicmi_ctx* c, int64_t rows, int mode, int64_t L_fixed, in
     if (direct) { int rc = ensure_pin_down(c, (size_t)rows); if (rc) return rc; }
     {
         Timed t(c, F_HYPER_FLAGS, 5.0 * (double)rows);
-        launch_hyper_flags(c->d_x, (int)rows, mode, (int)L_fixed, M, psig, direct ? reinterpret_cast<uint8_t*>(c->pin_down) : c->d_sig,
+        launch_hyper_flags(c->d_x, (int)rows, mode, (int)L_fixed, M, psig, direct ? reinterpret_cast<uint8_t*>(c->pin_down.get()) : c->d_sig,
                            (int)own_first, (int)c->shard_stride, c->stream);
     }
     HIPCHK(hipGetLastError());
@@ -1899,11 +1831,8 @@ static int ensure_scan_multi(hicmi_ctx* c, int sets, ScanMulti& m)
     const size_t n = (size_t)c->n, S = (size_t)sets;
     const size_t head = (sizeof(ScanState) * SCAN_MAX_SETS + 255) & ~(size_t)255;
     const size_t bytes = head + S * n * (sizeof(int32_t) * 9 + 3) + 64;
-    if (c->scan_multi_bytes < bytes || !c->d_scan_multi) {
-        free_dev(c->d_scan_multi); c->d_scan_multi = nullptr; c->scan_multi_bytes = 0;
-        HIPCHK(hipMalloc((void**)&c->d_scan_multi, bytes));
-        c->scan_multi_bytes = bytes;
-    }
+    int rc = ensure(c->d_scan_multi, (int64_t)bytes);
+    if (rc) return rc;
     unsigned char* b = c->d_scan_multi;
     m.st = reinterpret_cast<ScanState*>(b);
     m.x = reinterpret_cast<int32_t*>(b + head);
@@ -2111,17 +2040,16 @@ int select_enqueue(hicmi_ctx* c, const int32_t* sel, int64_t n, const std::vecto
         if (sel[i] < 0 || sel[i] >= c->n) return fail(HICMI_EINVAL, "selection index out of range");
     HIPCHK(hipSetDevice(c->device));
     const int64_t ld2 = (n + 15) & ~(int64_t)15;
-    int rc = ensure(c->dM2, c->m2_cap, n * ld2);
+    int rc = ensure(c->dM2, n * ld2);
+    if (!rc) rc = ensure(c->d_sel, n);
     if (rc) return rc;
-    rc = ensure(c->d_sel, c->sel_cap, n);
-    if (rc) return rc;
-    if (c->h_cap < n + 1) {
+    if (c->d_H.capacity() < n + 1) {
         std::vector<double> own;
         if (!H_shared || (int64_t)H_shared->size() < n + 1) { harmonic_table(own, n); H_shared = &own; }
-        rc = ensure(c->d_H, c->h_cap, n + 1);
+        rc = ensure(c->d_H, n + 1);
         if (rc) return rc;
         rc = upload(c, c->d_H, H_shared->data(), sizeof(double) * (size_t)(n + 1));
-        if (rc) return rc;
+        if (rc) { c->d_H.reset(); return rc; }                    // (a table that was not written is not kept)
     }
     rc = upload(c, c->d_sel, sel, sizeof(int32_t) * (size_t)n);
     if (rc) return rc;
@@ -2150,7 +2078,7 @@ int hicmi_p2_total(hicmi_ctx* c, double* total_out)
     if (!c || !total_out) return fail(HICMI_EINVAL, "bad arguments");
     if (c->n2 < 1) return fail(HICMI_EINVAL, "hicmi_p2_select has not run");
     HIPCHK(hipSetDevice(c->device));
-    int rc = ensure(c->d_partial, c->partial_cap, c->n2 + 1);
+    int rc = ensure(c->d_partial, c->n2 + 1);
     if (rc) return rc;
     {
         Timed t(c, F_P2_TOTAL, 4.0 * (double)c->n2 * (double)c->n2);
@@ -2170,9 +2098,8 @@ int hicmi_p2_score(hicmi_ctx* c, const int32_t* perms, int64_t n_cand, int64_t n
     for (int64_t i = 0; i < n_cand * n_used; i++)
         if (perms[i] < 0 || perms[i] >= c->n2) return fail(HICMI_EINVAL, "candidate index out of range");
     HIPCHK(hipSetDevice(c->device));
-    int rc = ensure(c->d_perms, c->perms_cap, n_cand * n_used);
-    if (rc) return rc;
-    rc = ensure(c->d_scores, c->scores_cap, n_cand);
+    int rc = ensure(c->d_perms, n_cand * n_used);
+    if (!rc) rc = ensure(c->d_scores, n_cand);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(c->d_perms, perms, sizeof(int32_t) * (size_t)(n_cand * n_used), hipMemcpyHostToDevice, c->stream));
     {
@@ -2196,11 +2123,9 @@ int hicmi_p2_score_exact(hicmi_ctx* c, const int32_t* perms, int64_t n_cand, int
     for (int64_t i = 0; i < n_cand * n_used; i++)
         if (perms[i] < 0 || perms[i] >= c->n2) return fail(HICMI_EINVAL, "candidate index out of range");
     HIPCHK(hipSetDevice(c->device));
-    int rc = ensure(c->d_perms, c->perms_cap, n_cand * n_used);
-    if (rc) return rc;
-    rc = ensure(c->d_scores, c->scores_cap, n_cand);
-    if (rc) return rc;
-    rc = ensure(c->d_T, c->t_cap, 2 * n_cand * n_used);
+    int rc = ensure(c->d_perms, n_cand * n_used);
+    if (!rc) rc = ensure(c->d_scores, n_cand);
+    if (!rc) rc = ensure(c->d_T, 2 * n_cand * n_used);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(c->d_perms, perms, sizeof(int32_t) * (size_t)(n_cand * n_used), hipMemcpyHostToDevice, c->stream));
     {
@@ -2225,12 +2150,8 @@ int hicmi_p2_layout(hicmi_ctx* c, const int32_t* scaf_start, const int32_t* scaf
         if (scaf_len[i] < 1 || scaf_start[i] < 0 || (int64_t)scaf_start[i] + scaf_len[i] > c->n2)
             return fail(HICMI_EINVAL, "scaffold %lld is not a range of the selection", (long long)i);
     HIPCHK(hipSetDevice(c->device));
-    if (c->scaf_cap < n_scaf) {
-        free_dev(c->d_scaf_start); free_dev(c->d_scaf_len); c->d_scaf_start = c->d_scaf_len = nullptr; c->scaf_cap = 0;
-        HIPCHK(hipMalloc((void**)&c->d_scaf_start, sizeof(int32_t) * (size_t)n_scaf));
-        HIPCHK(hipMalloc((void**)&c->d_scaf_len, sizeof(int32_t) * (size_t)n_scaf));
-        c->scaf_cap = n_scaf;
-    }
+    int rc = ensure_all(c->d_scaf_start, n_scaf, c->d_scaf_len, n_scaf);
+    if (rc) return rc;
     c->h_scaf_start.assign(scaf_start, scaf_start + n_scaf);
     c->h_scaf_len.assign(scaf_len, scaf_len + n_scaf);
     c->n_scaf = n_scaf; c->n_arr = 0;
@@ -2251,9 +2172,8 @@ int hicmi_p2_set_arrangement(hicmi_ctx* c, const int32_t* ids, const uint8_t* re
         pos[(size_t)j + 1] = pos[(size_t)j] + c->h_scaf_len[(size_t)ids[j]];
     }
     HIPCHK(hipSetDevice(c->device));
-    int rc = ensure(c->d_arr_packed, c->arr_cap, 3 * std::max<int64_t>(S, c->n_scaf) + 2);
-    if (rc) return rc;
-    rc = ensure(c->d_pos2sel, c->pos_cap, c->n2);
+    int rc = ensure(c->d_arr_packed, 3 * std::max<int64_t>(S, c->n_scaf) + 2);
+    if (!rc) rc = ensure(c->d_pos2sel, c->n2);
     if (rc) return rc;
     c->h_arr_id.assign(ids, ids + S); c->h_arr_rev.assign(rev, rev + S); c->h_arr_pos = pos;
     c->arr_version++;
@@ -2282,9 +2202,8 @@ int arrangement_total_enqueue(hicmi_ctx* c)
 {
     if (c->n_arr < 1) return fail(HICMI_EINVAL, "hicmi_p2_set_arrangement has not run");
     HIPCHK(hipSetDevice(c->device));
-    int rc = ensure(c->d_T, c->t_cap, c->n_arr + 1);
-    if (rc) return rc;
-    rc = ensure(c->d_scores, c->scores_cap, 1);
+    int rc = ensure(c->d_T, c->n_arr + 1);
+    if (!rc) rc = ensure(c->d_scores, 1);
     if (rc) return rc;
     rc = ensure_pin_down(c, sizeof(double));
     if (rc) return rc;
@@ -2315,7 +2234,7 @@ int hicmi_p2_arrangement_score(hicmi_ctx* c, double total, double* score_out)
     if (c->n_arr < 2) { *score_out = 0.0; return HICMI_OK; }
     HIPCHK(hipSetDevice(c->device));
     const int NB = kBaseSlabs;
-    int rc = ensure(c->d_scores, c->scores_cap, NB);
+    int rc = ensure(c->d_scores, NB);
     if (rc) return rc;
     {
         Timed t(c, F_P2_SCORE, 4.0 * (double)c->n_arr * (double)(c->n_arr - 1));
@@ -2345,7 +2264,7 @@ int hicmi_p2_score_insertions(hicmi_ctx* c, int32_t new_id, double total, double
     // incremental form: BASE (64 partial sums) - STRADDLE(g) (prefix sums of S increments) + CROSS(g, r)
     const int NB = kBaseSlabs;
     const int64_t n_out = NB + S + 2 * (S + 1);
-    int rc = ensure(c->d_scores, c->scores_cap, n_out);
+    int rc = ensure(c->d_scores, n_out);
     if (rc) return rc;
     {
         const double nn = (double)c->n_arr;
@@ -2374,9 +2293,8 @@ int hicmi_p2_window_tables(hicmi_ctx* c, int64_t k, const int8_t* orders, int64_
     if (!c || !orders || !orients || k < 1 || k > 8 || n_orders < 1 || n_orients < 1) return fail(HICMI_EINVAL, "bad arguments");
     for (int64_t i = 0; i < n_orders * k; i++) if (orders[i] < 0 || orders[i] >= k) return fail(HICMI_EINVAL, "order table entry out of range");
     HIPCHK(hipSetDevice(c->device));
-    int rc = ensure(c->d_orders, c->ord_cap, n_orders * k);
-    if (rc) return rc;
-    rc = ensure(c->d_orients, c->ori_cap, n_orients * k);
+    int rc = ensure(c->d_orders, n_orders * k);
+    if (!rc) rc = ensure(c->d_orients, n_orients * k);
     if (rc) return rc;
     rc = upload(c, c->d_orders, orders, (size_t)(n_orders * k));
     if (rc) return rc;
@@ -2451,11 +2369,9 @@ int window_batch_enqueue(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k)
     // placement tables (k_part2_window.hip) unless the direct per-candidate kernels are asked for (A/B switch)
     static const bool direct = getenv("HICMI_P2_WINDOW_DIRECT") != nullptr;
     if (!direct) g_total = count * window_table_doubles((int)k);
-    rc = ensure(c->d_G, c->g_cap, g_total);
-    if (rc) return rc;
-    rc = ensure(c->d_delta, c->delta_cap, n_cand * count);
-    if (rc) return rc;
-    rc = ensure(c->d_wb, c->wb_cap, count);
+    rc = ensure(c->d_G, g_total);
+    if (!rc) rc = ensure(c->d_delta, n_cand * count);
+    if (!rc) rc = ensure(c->d_wb, count);
     if (rc) return rc;
     rc = upload(c, c->d_wb, wb.data(), sizeof(WindowBatchEntry) * (size_t)count);
     if (rc) return rc;
@@ -2536,11 +2452,9 @@ int literal_enqueue(hicmi_ctx* c, const std::vector<std::vector<int32_t>>& rows,
     std::vector<int32_t> flat((size_t)n_used * p.todo.size());
     for (size_t t = 0; t < p.todo.size(); t++) memcpy(flat.data() + t * n_used, rows[p.todo[t]].data(), sizeof(int32_t) * (size_t)n_used);
     const int64_t n_cand = (int64_t)p.todo.size();
-    int rc = ensure(c->d_perms, c->perms_cap, n_cand * n_used);
-    if (rc) return rc;
-    rc = ensure(c->d_scores, c->scores_cap, n_cand);
-    if (rc) return rc;
-    rc = ensure(c->d_T, c->t_cap, 2 * n_cand * n_used);
+    int rc = ensure(c->d_perms, n_cand * n_used);
+    if (!rc) rc = ensure(c->d_scores, n_cand);
+    if (!rc) rc = ensure(c->d_T, 2 * n_cand * n_used);
     if (rc) return rc;
     rc = ensure_pin_down(c, sizeof(double) * (size_t)n_cand);
     if (rc) return rc;
@@ -2562,7 +2476,7 @@ int literal_collect(hicmi_ctx* c, const LiteralPending& p, std::vector<double>& 
     out.assign(p.keys.size(), 0.0);
     if (p.keys.empty()) return HICMI_OK;
     if (p.queued) HIPCHK(sync_stream(c));
-    const double* vals = reinterpret_cast<const double*>(c->pin_down);
+    const double* vals = reinterpret_cast<const double*>(c->pin_down.get());
     for (size_t t = 0; t < p.todo.size(); t++) c->exact_cache[p.keys[p.todo[t]]] = p.queued ? vals[t] : 0.0;   // fewer than 2 bins: cost 0.0
     for (size_t i = 0; i < p.keys.size(); i++) out[i] = c->exact_cache[p.keys[i]];
     return HICMI_OK;
@@ -2724,11 +2638,9 @@ int window_near_enqueue(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k, 
     const size_t off_cnt = (size_t)count * (size_t)n_blocks * sizeof(double);
     const size_t off_list = off_cnt + (((size_t)count * sizeof(int32_t) + 15) & ~(size_t)15);
     const size_t bytes = off_list + (size_t)count * (size_t)cap * sizeof(NearEntry);
-    rc = ensure(c->d_G, c->g_cap, count * window_table_doubles((int)k));
-    if (rc) return rc;
-    rc = ensure(c->d_wnear, c->wnear_cap, (int64_t)bytes);
-    if (rc) return rc;
-    rc = ensure(c->d_wb, c->wb_cap, count);
+    rc = ensure(c->d_G, count * window_table_doubles((int)k));
+    if (!rc) rc = ensure(c->d_wnear, (int64_t)bytes);
+    if (!rc) rc = ensure(c->d_wb, count);
     if (rc) return rc;
     rc = upload(c, c->d_wb, wb.data(), sizeof(WindowBatchEntry) * (size_t)count);
     if (rc) return rc;
@@ -2739,7 +2651,7 @@ int window_near_enqueue(hicmi_ctx* c, int64_t first0, int64_t count, int64_t k, 
         Timed t(c, F_P2_WINDOW_G, bc.g_bytes);
         launch_p2_window_near(c->dM2, c->ld2, c->d_pos2sel, (int)c->n_arr, (int)k, c->d_wb, wb.data(), (int)count, bc.max_m,
                               c->d_orders, c->d_orients, (int)c->n_orders, (int)c->n_orients, c->d_H, c->d_G, k == S ? 1 : 0,
-                              total, cur_fast, floor, kNearTop, reinterpret_cast<double*>(c->d_wnear), d_count,
+                              total, cur_fast, floor, kNearTop, reinterpret_cast<double*>(c->d_wnear.get()), d_count,
                               d_list, (int)cap, c->stream);
     }
     HIPCHK(hipGetLastError());
@@ -2959,22 +2871,18 @@ int queue_insertions(hicmi_ctx* lead, const std::vector<InsJob*>& jobs)
         rc = check_candidate_bins(n_max);
         if (rc) return rc;
         const int64_t S_max = job.S + n_steps;
-        rc = ensure(c->d_arr_packed2, c->arr2_cap, 3 * std::max<int64_t>(S_max, c->n_scaf) + 2);
-        if (rc) return rc;
-        rc = ensure(c->d_pos2sel2, c->pos2_cap, c->n2);
-        if (rc) return rc;
-        rc = ensure(c->d_ins_T, c->ins_t_cap, (1 + 2 * (int64_t)INS_MAXC) * n_max);
-        if (rc) return rc;
-        rc = ensure(c->d_ins_partial, c->ins_partial_cap, NB + n_max + 2 * (S_max + 1));
+        rc = ensure(c->d_arr_packed2, 3 * std::max<int64_t>(S_max, c->n_scaf) + 2);
+        if (!rc) rc = ensure(c->d_pos2sel2, c->n2);
+        if (!rc) rc = ensure(c->d_ins_T, (1 + 2 * (int64_t)INS_MAXC) * n_max);
+        if (!rc) rc = ensure(c->d_ins_partial, NB + n_max + 2 * (S_max + 1));
         if (rc) return rc;
         steps_max = std::max(steps_max, n_steps);
         blob_off[(size_t)j] = blob_bytes;
         blob_bytes += (sizeof(InsState) + sizeof(InsLog) * (size_t)n_steps + 15) & ~(size_t)15;
     }
     HIPCHK(hipSetDevice(lead->device));
-    int rc = ensure(lead->d_ins_blob, lead->ins_blob_cap, (int64_t)blob_bytes);
-    if (rc) return rc;
-    rc = ensure(lead->d_ins_steps, lead->ins_steps_cap, steps_max * nj);
+    int rc = ensure(lead->d_ins_blob, (int64_t)blob_bytes);
+    if (!rc) rc = ensure(lead->d_ins_steps, steps_max * nj);
     if (rc) return rc;
     // one record per (step, job); sizes per step for the launch grids
     std::vector<InsStep> table((size_t)(steps_max * nj));
@@ -3171,7 +3079,7 @@ namespace {
 template <typename Rec>
 struct TableOps {
     int64_t max_S;                                         // scaffolds per chromosome; 0: no limit
-    Rec* hicmi_ctx::*recs; int64_t hicmi_ctx::*recs_cap;   // the lead context's record buffer
+    DevBuf<Rec> hicmi_ctx::*recs;                            // the lead context's record buffer
     // job j, its arrangement set: the length of its table, the doubles it needs in d_ins_partial, its records
     std::function<void(int64_t j, int64_t& n_table, int64_t& scratch, int64_t& n_rec)> size;
     // job j's records appended and its work added to algo; d_scores, d_best: its table and its pairs on the device
@@ -3208,7 +3116,7 @@ int run_table_jobs(int64_t n_jobs, hicmi_ctx* const* ctxs, const int32_t* const*
         for (int64_t i = 0; i < S[j]; i++) { best_out[j][2 * i] = -1; best_out[j][2 * i + 1] = 0; }
         if (c->n_arr < 2 || !(totals[j] > 0.0) || n_rec_j == 0) continue;
         run[(size_t)j] = 1;
-        rc = ensure(c->d_ins_partial, c->ins_partial_cap, scratch);
+        rc = ensure(c->d_ins_partial, scratch);
         if (rc) return rc;
         out_off[(size_t)j] = blob_bytes;
         blob_bytes += ((size_t)n_table[(size_t)j] * sizeof(double) + (size_t)(2 * S[j]) * sizeof(int32_t) + 15) & ~(size_t)15;
@@ -3216,9 +3124,8 @@ int run_table_jobs(int64_t n_jobs, hicmi_ctx* const* ctxs, const int32_t* const*
     }
     if (n_rec == 0) return HICMI_OK;
     HIPCHK(hipSetDevice(lead->device));
-    int rc = ensure(lead->d_ins_blob, lead->ins_blob_cap, (int64_t)blob_bytes);
-    if (rc) return rc;
-    rc = ensure(lead->*ops.recs, lead->*ops.recs_cap, n_rec);
+    int rc = ensure(lead->d_ins_blob, (int64_t)blob_bytes);
+    if (!rc) rc = ensure(lead->*ops.recs, n_rec);
     if (rc) return rc;
     std::vector<Rec> recs;
     recs.reserve((size_t)n_rec);
@@ -3259,7 +3166,7 @@ int hicmi_p2_support_multi(int64_t n_jobs, hicmi_ctx* const* ctxs, const int32_t
     const int NB = SUP_BASE_SLABS;
     int max_S = 1, max_n = 1;
     TableOps<SupRec> ops;
-    ops.max_S = SUP_MAX_S; ops.recs = &hicmi_ctx::d_sup_recs; ops.recs_cap = &hicmi_ctx::sup_recs_cap;
+    ops.max_S = SUP_MAX_S; ops.recs = &hicmi_ctx::d_sup_recs;
     ops.size = [&](int64_t j, int64_t& n_table, int64_t& scratch, int64_t& n_rec) {
         n_table = 2 * S[j] * S[j]; scratch = S[j] * (NB + ctxs[j]->n_arr + 2 * S[j]); n_rec = S[j];
     };
@@ -3306,7 +3213,7 @@ int hicmi_p2_breaks_multi(int64_t n_jobs, hicmi_ctx* const* ctxs, const int32_t*
     const int NB = BRK_BASE_SLABS;
     int64_t n_wg = 0;
     TableOps<BrkRec> ops;
-    ops.max_S = 0; ops.recs = &hicmi_ctx::d_brk_recs; ops.recs_cap = &hicmi_ctx::brk_recs_cap;
+    ops.max_S = 0; ops.recs = &hicmi_ctx::d_brk_recs;
     ops.size = [&](int64_t j, int64_t& n_table, int64_t& scratch, int64_t& n_rec) {
         scratch = NB;
         for (int64_t k = 0; k < S[j]; k++) {
@@ -3374,7 +3281,7 @@ int hicmi_p2_inversions_multi(int64_t n_jobs, hicmi_ctx* const* ctxs, const int3
     int64_t n_wg = 0;
     double work = 0.0;
     TableOps<InvRec> ops;
-    ops.max_S = INV_MAX_S; ops.recs = &hicmi_ctx::d_inv_recs; ops.recs_cap = &hicmi_ctx::inv_recs_cap;
+    ops.max_S = INV_MAX_S; ops.recs = &hicmi_ctx::d_inv_recs;
     ops.size = [&](int64_t j, int64_t& n_table, int64_t& scratch, int64_t& n_rec) {
         n_table = S[j] * S[j]; scratch = NB; n_rec = S[j];
     };
@@ -3636,7 +3543,7 @@ int hicmi_p2_start_all(int64_t n_jobs, hicmi_ctx* const* ctxs, const int32_t* se
             if (sync_stream(c) != hipSuccess) return drain(fail(HICMI_EHIP, "hipStreamSynchronize failed in the start phase"));
             if (window_c0(c, 0, k[j]) < 0) return drain(fail(HICMI_EINVAL, "current orientation not in the orientation table"));
             const int64_t n_cand = c->n_orders * c->n_orients;
-            const double* delta = reinterpret_cast<const double*>(c->pin_down);
+            const double* delta = reinterpret_cast<const double*>(c->pin_down.get());
             std::vector<double> fast((size_t)n_cand);
             for (int64_t i = 0; i < n_cand; i++) fast[(size_t)i] = delta[(size_t)i] / total_out[j];
             short_list(fast, 0.0, near[j]);
@@ -3678,7 +3585,7 @@ int plot_prepare(hicmi_ctx* c, int kind, const int32_t* order, int64_t n_sel, in
     *d_order_out = nullptr;
     if (order) {
         for (int64_t i = 0; i < n_sel; i++) if (order[i] < 0 || order[i] >= c->n) return fail(HICMI_EINVAL, "order entry out of range");
-        int rc = ensure(c->d_plot_order, c->plot_order_cap, n_sel);
+        int rc = ensure(c->d_plot_order, n_sel);
         if (rc) return rc;
         rc = upload(c, c->d_plot_order, order, sizeof(int32_t) * (size_t)n_sel);
         if (rc) return rc;
@@ -3698,9 +3605,9 @@ int hicmi_plot_percentiles(hicmi_ctx* c, int kind, const int32_t* order, int64_t
     int32_t* d_order = nullptr;
     int rc = plot_prepare(c, kind, order, n_sel, &d_order);
     if (rc) return rc;
-    rc = ensure(c->d_plot_work, c->plot_work_cap, (int64_t)(plot_select_state_bytes() + plot_select_hist_bytes()));
+    rc = ensure(c->d_plot_work, (int64_t)(plot_select_state_bytes() + plot_select_hist_bytes()));
     if (rc) return rc;
-    SelectState* d_state = reinterpret_cast<SelectState*>(c->d_plot_work);
+    SelectState* d_state = reinterpret_cast<SelectState*>(c->d_plot_work.get());
     unsigned int* d_hist = reinterpret_cast<unsigned int*>(c->d_plot_work + plot_select_state_bytes());
     const double N = (double)n_sel * (double)n_sel;
     const int per_batch = plot_select_max_targets() / 2;
@@ -3746,7 +3653,7 @@ int hicmi_plot_downsample(hicmi_ctx* c, int kind, const int32_t* order, int64_t 
     int32_t* d_order = nullptr;
     int rc = plot_prepare(c, kind, order, n_sel, &d_order);
     if (rc) return rc;
-    rc = ensure(c->d_plot_img, c->plot_img_cap, px * px);
+    rc = ensure(c->d_plot_img, px * px);
     if (rc) return rc;
     {
         Timed t(c, F_PLOT, 8.0 * (double)n_sel * (double)n_sel);
@@ -3772,15 +3679,15 @@ inline double* hmm_slots(hicmi_ctx* c) { return hmm_cen(c) + 2 * c->hmm_ld; }
 // k-means or EM loops); ensure() only grows them, so they fit every slot built before
 int hmm_size_work(hicmi_ctx* c, int64_t T, int64_t ld)
 {
-    int rc = ensure(c->d_hwork, c->hwork_cap, 10 * T);
-    if (!rc) rc = ensure(c->d_hlab, c->hlab_cap, 3 * T);
-    if (!rc) rc = ensure(c->d_hbt, c->hbt_cap, T);
+    int rc = ensure(c->d_hwork, 10 * T);
+    if (!rc) rc = ensure(c->d_hlab, 3 * T);
+    if (!rc) rc = ensure(c->d_hbt, T);
     // a column pass over width D <= ld has at most min(T, 1024) and at most 2048 / ceil(D / 256) + 1 row chunks
     const int64_t cb = (ld + 255) / 256;
     const int64_t part = 4 * std::min(std::min(T, (int64_t)1024) * ld, (2048 + cb) * 256);
-    if (!rc) rc = ensure(c->d_hpart, c->hpart_cap, part);
-    if (!rc) rc = ensure(c->d_hsmall, c->hsmall_cap, (HMM_P_SCALARS + 6) * ld + HMM_S_COUNT + 16);
-    if (!rc) rc = ensure(c->d_hst, c->hst_cap, 4);
+    if (!rc) rc = ensure(c->d_hpart, part);
+    if (!rc) rc = ensure(c->d_hsmall, (HMM_P_SCALARS + 6) * ld + HMM_S_COUNT + 16);
+    if (!rc) rc = ensure(c->d_hst, 4);
     return rc;
 }
 
@@ -3797,7 +3704,7 @@ int hmm_slot_alloc(hicmi_ctx* c, int s, int64_t T, int64_t ld)
 {
     auto& sl = c->hslot[s];
     sl.T = sl.ld = sl.D = 0;
-    int rc = ensure(sl.d_x, sl.cap, T * ld);
+    int rc = ensure(sl.d_x, T * ld);
     if (!rc) rc = hmm_size_work(c, T, ld);
     if (rc) { if (c->hcur == s) hmm_select(c, s); return rc; }
     sl.T = T; sl.ld = ld; sl.D = ld;
@@ -3843,7 +3750,7 @@ int hicmi_hmm_load_obs_slot(hicmi_ctx* c, int64_t slot, const int32_t* order, in
         if (order[i] < 0 || order[i] >= n) return fail(HICMI_EINVAL, "order entry out of range");
     HIPCHK(hipSetDevice(c->device));
     const int64_t T = n - cut, D = prev - cut;
-    int rc = ensure(c->d_horder, c->horder_cap, n);
+    int rc = ensure(c->d_horder, n);
     if (!rc) rc = hmm_slot_alloc(c, (int)slot, T, D);
     if (!rc) rc = upload(c, c->d_horder, order, sizeof(int32_t) * (size_t)n);
     if (rc) return rc;
@@ -4004,7 +3911,7 @@ int hicmi_hmm_fit(hicmi_ctx* c, const double* startprob, double* means, double* 
         return fail(HICMI_EINVAL, "bad arguments");
     HIPCHK(hipSetDevice(c->device));
     const int64_t T = c->hmm_T, D = c->hmm_D, ld = c->hmm_ld;
-    rc = ensure(c->d_hhist, c->hhist_cap, n_iter);
+    rc = ensure(c->d_hhist, n_iter);
     if (!rc) rc = hmm_upload_params(c, startprob, means, covars, transmat);
     if (rc) return rc;
     double* P = hmm_params(c);
@@ -4097,7 +4004,7 @@ int hmm_multi_plan(hicmi_ctx* c, int64_t n_prob, const int64_t* slots, const int
     }
     const size_t b_pr = align256(sizeof(HmmKmProb) * (size_t)n_prob), b_st = align256(sizeof(HmmKmState) * (size_t)n_prob);
     const size_t bytes = b_pr + b_st + 256 + sizeof(double) * (size_t)n_dbl + sizeof(int32_t) * (size_t)n_lab;
-    int rc = ensure(c->d_hmulti, c->hmulti_cap, (int64_t)bytes);
+    int rc = ensure(c->d_hmulti, (int64_t)bytes);
     if (rc) return rc;
     double* dp = (double*)(c->d_hmulti + b_pr + b_st + 256);
     for (auto& q : pr) { q.cen = dp; dp += 2 * q.D; }                   // the centers of all problems are contiguous
@@ -4109,7 +4016,7 @@ int hmm_multi_plan(hicmi_ctx* c, int64_t n_prob, const int64_t* slots, const int
     return HICMI_OK;
 }
 
-inline HmmKmProb* hmm_multi_probs(hicmi_ctx* c) { return (HmmKmProb*)c->d_hmulti; }
+inline HmmKmProb* hmm_multi_probs(hicmi_ctx* c) { return reinterpret_cast<HmmKmProb*>(c->d_hmulti.get()); }
 inline HmmKmState* hmm_multi_states(hicmi_ctx* c, int64_t n_prob)
 {
     return (HmmKmState*)(c->d_hmulti + align256(sizeof(HmmKmProb) * (size_t)n_prob));
@@ -4211,8 +4118,8 @@ int lv_size(hicmi_ctx* c, int64_t m)
     if (m < 1) return fail(HICMI_EINVAL, "the graph needs at least one node");
     if (m > LOUVAIN_MAX_M) return fail(HICMI_EUNSUPPORTED, "m = %lld > %d Louvain nodes", (long long)m, LOUVAIN_MAX_M);
     const int64_t chunks = (m * m + 8191) / 8192;
-    int rc = ensure(c->d_lvA, c->lvA_cap, m * m);
-    if (!rc) rc = ensure(c->d_lvvec, c->lvvec_cap, 3 * m + 2 + chunks);
+    int rc = ensure(c->d_lvA, m * m);
+    if (!rc) rc = ensure(c->d_lvvec, 3 * m + 2 + chunks);
     return rc;
 }
 
@@ -4228,7 +4135,7 @@ int lv_status(hicmi_ctx* c, int64_t m)
     return HICMI_OK;
 }
 
-int lv_work(hicmi_ctx* c, size_t bytes) { return ensure(c->d_lvwork, c->lvwork_cap, (int64_t)bytes); }
+int lv_work(hicmi_ctx* c, size_t bytes) { return ensure(c->d_lvwork, (int64_t)bytes); }
 
 inline size_t lv_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -4247,7 +4154,7 @@ int hicmi_louvain_graph(hicmi_ctx* c, const int32_t* rows, int64_t m)
     int rc = lv_size(c, m);
     if (rc) return rc;
     HIPCHK(hipSetDevice(c->device));
-    rc = ensure(c->d_lvrows, c->lvrows_cap, m);
+    rc = ensure(c->d_lvrows, m);
     if (!rc) rc = upload(c, c->d_lvrows, rows, sizeof(int32_t) * (size_t)m);
     if (rc) return rc;
     launch_louvain_graph(c->dC, c->ldc, c->d_lvrows, c->d_np, c->d_seq, (int)m, c->d_lvA, c->stream);

@@ -31,7 +31,8 @@ extern "C" {
 #define HICMI_OK            0
 #define HICMI_EINVAL       -1   /* bad argument / call order */
 #define HICMI_EHIP         -2   /* HIP runtime error (message has the hipError string) */
-#define HICMI_ENOMEM       -3
+#define HICMI_ENOMEM       -3   /* a device allocation failed, whichever call made it (message has the byte count); a
+                                   failed pinned host allocation is HICMI_EHIP */
 #define HICMI_ESTATE       -4   /* kernel reported an internal inconsistency (e.g. nn-chain guard) */
 #define HICMI_EUNSUPPORTED -5   /* e.g. more than 65536 bins (rank matrix is uint16 in this version) */
 
