@@ -95,6 +95,11 @@ SIGNATURES = {
     "hicmi_pair_stats": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, c_i64, _vp, c_i64, _vp, _vp, _vp, _vp, c_i64, _vp, _vp, _vp, _vp]),
     "hicmi_lift_maps": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, _vp, _vp, _vp, _vp, c_i64, c_i64, _vp, _vp,
                                        ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "hicmi_span_begin": (ctypes.c_int, [_vp, _vp, c_i64, _vp, _vp, _vp, _vp, c_i64, c_i64, c_i64, _vp, ctypes.POINTER(c_i64)]),
+    "hicmi_span_add_pairs": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, c_i64]),
+    "hicmi_span_finish": (ctypes.c_int, [_vp, c_i64, _vp, c_i64, _vp, _vp, _vp]),
+    "hicmi_span_file": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, _vp, _vp, _vp, _vp, c_i64, c_i64, c_i64,
+                                       c_i64, _vp, c_i64, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(c_i64)]),
     "hicmi_plot_percentiles": (ctypes.c_int, [_vp, ctypes.c_int, _vp, c_i64, _vp, c_i64, _vp]),
     "hicmi_plot_downsample": (ctypes.c_int, [_vp, ctypes.c_int, _vp, c_i64, c_i64, _vp]),
     "hicmi_p2_insert_all_multi": (ctypes.c_int, [c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -323,6 +328,41 @@ def lift_maps(path, names, sizes, lift_seq, lift_off, lift_rev, seq_sizes, resol
     return tuple(int(v) for v in stats), out
 
 
+def _span_records(recs):
+    """The records (lo, hi, q0, q1) of a span call as a contiguous int64 array of shape (n_rec, 4)."""
+    rec = np.ascontiguousarray(recs, dtype=np.int64).reshape(-1, 4)
+    return rec, np.zeros((len(rec), 4), np.int64)
+
+
+def span_cell_count(sizes, lift_seq, step) -> int:
+    """Cells of a span build: ceil(L / step) for every placed scaffold of size L > 0."""
+    size = np.asarray(sizes, dtype=np.int64)
+    placed = size[(np.asarray(lift_seq) >= 0) & (size > 0)]
+    step = int(step)
+    return int((placed // step + (placed % step != 0)).sum()) if step >= 1 else 0
+
+
+def span_file(path, names, sizes, lift_seq, lift_off, lift_rev, seq_sizes, step, max_span, flank, recs, ctx, threads: int = 0,
+              want_depth: bool = True):
+    """Spanning depth of an assembly over a HiC-Pro allValidPairs file in one pass (hicmi_span_file) on the
+    device of ``ctx``, whose matrix and open map build stay as they are.  ``recs``: records (lo, hi, q0, q1) of slots.
+    Returns ((lines, used, unknown_scaffold, out_of_range, chunks), cell_first int64[S], picks int64[n_rec, 4] = (slot, D,
+    Lsum, Rsum), counters uint64[5] = (marked, one_cell, beyond_max_span, trans, unlifted), depth uint64[n_cells] or None)."""
+    blob, off = _name_blob(names)
+    size, seq, loff, rev, seq_size = _lift_tables(sizes, lift_seq, lift_off, lift_rev, seq_sizes)
+    if size.shape != (len(names),):
+        raise ValueError("one size per scaffold name")
+    rec, picks = _span_records(recs)
+    stats, counters = np.zeros(5, np.int64), np.zeros(5, np.uint64)
+    cell_first, n_cells = np.zeros(len(size), np.int64), c_i64()
+    depth = np.zeros(max(span_cell_count(size, seq, step), 1), np.uint64) if want_depth else None
+    _check(load().hicmi_span_file(os.fsencode(path), blob, _ptr(off), len(names), _ptr(size), _ptr(seq), _ptr(loff), _ptr(rev),
+                                  _ptr(seq_size), len(seq_size), int(step), int(max_span), int(flank), _ptr(rec), len(rec), ctx._h,
+                                  int(threads), _ptr(stats), _ptr(picks), _ptr(counters), _ptr(depth), _ptr(cell_first),
+                                  ctypes.byref(n_cells)))
+    return tuple(int(v) for v in stats), cell_first, picks, counters, None if depth is None else depth[:n_cells.value]
+
+
 def hypergeom_sf(x, M, n, N) -> float:
     """hyper_geom(x, M, n, N) of scaffoldToChromosomes.py:352-368, evaluated by libhicmi's host code."""
     return float(load().hicmi_hypergeom_sf(int(x), int(M), int(n), int(N)))
@@ -491,6 +531,35 @@ class Context:
         self.n = self.contacts_device()[1]
         self._keepalive = None
         return pairs.value
+
+    def span_begin(self, sizes, lift_seq, lift_off, lift_rev, seq_sizes, step, max_span: int = 0):
+        """Open a spanning-depth build (hicmi_span_begin) over the assembly of the lift tables, cut into cells
+        of ``step`` bp; pairs further apart than ``max_span`` (0: no limit) will not count.  Returns cell_first int64[S]: the
+        first cell of every scaffold, -1 for a dropped or empty one.  The matrix and an open map build are untouched."""
+        size, seq, off, rev, seq_size = _lift_tables(sizes, lift_seq, lift_off, lift_rev, seq_sizes)
+        cell_first, n_cells = np.zeros(len(size), np.int64), c_i64()
+        _check(self._lib.hicmi_span_begin(self._h, _ptr(size), len(size), _ptr(seq), _ptr(off), _ptr(rev), _ptr(seq_size),
+                                          len(seq_size), int(step), int(max_span), _ptr(cell_first), ctypes.byref(n_cells)))
+        self._span_cells = n_cells.value
+        return cell_first
+
+    def span_add_pairs(self, scaf_a, pos_a, scaf_b, pos_b):
+        """Mark the pairs (scaffold index, 1-based position) x 2 in the open span build (hicmi_span_add_pairs)."""
+        sa, sb = np.ascontiguousarray(scaf_a, dtype=np.int32), np.ascontiguousarray(scaf_b, dtype=np.int32)
+        pa, pb = np.ascontiguousarray(pos_a, dtype=np.int64), np.ascontiguousarray(pos_b, dtype=np.int64)
+        if not (sa.ndim == 1 and sa.shape == sb.shape == pa.shape == pb.shape):
+            raise ValueError("the four arrays must be vectors of one length")
+        _check(self._lib.hicmi_span_add_pairs(self._h, _ptr(sa), _ptr(pa), _ptr(sb), _ptr(pb), len(sa)))
+
+    def span_finish(self, flank, recs, want_depth: bool = True):
+        """Close the span build (hicmi_span_finish): (picks int64[n_rec, 4] = (slot, D, Lsum, Rsum) of the records
+        (lo, hi, q0, q1), counters uint64[5] = (marked, one_cell, beyond_max_span, trans, unlifted), depth uint64[n_cells] or
+        None).  A refused flank or record leaves the build open."""
+        rec, picks = _span_records(recs)
+        counters = np.zeros(5, np.uint64)
+        depth = np.zeros(max(getattr(self, "_span_cells", 0), 1), np.uint64) if want_depth else None
+        _check(self._lib.hicmi_span_finish(self._h, int(flank), _ptr(rec), len(rec), _ptr(picks), _ptr(counters), _ptr(depth)))
+        return picks, counters, None if depth is None else depth[:self._span_cells]
 
     def group_sums(self, grp, scaf, n_groups, n_scaffolds, want_bins=True):
         """Group support sums (hicmi_group_sums): (bin sums n x n_groups or None, scaffold sums

@@ -207,6 +207,14 @@ struct hicmi_ctx {
     DevBuf<unsigned char> d_map_lift; LiftTables map_lift; std::vector<int32_t> map_lift_seq;
     DevBuf<unsigned char> d_stat_lift;
     DevBuf<unsigned long long> d_stat_out;
+    // spanning depth (k_spans.hip), between hicmi_span_begin and hicmi_span_finish (span_marks non-null: a
+    // build is open): the marks of n_cells cells with the five counters behind them, the lift tables and cell_first on the
+    // device, and the host's copies a chunk of pairs and the records of a finish are checked against
+    DevBuf<unsigned long long> span_marks;
+    DevBuf<unsigned char> d_span_lift; LiftTables span_lift; SpanGrid span_grid;
+    DevBuf<int64_t> d_span_first;
+    std::vector<int64_t> span_size, span_seq_first;
+    int64_t span_pairs = 0;
     // plot support
     DevBuf<int32_t> d_plot_order;
     DevBuf<unsigned char> d_plot_work;
@@ -999,6 +1007,265 @@ int hicmi_lift_maps(const char* path, const char* names_blob, const int64_t* nam
     const LiftHost lift{lift_seq, lift_off, lift_rev, seq_size, n_seq};
     const LiftStatsOut out{decay_out, seq_cis_out, seq_trans_out, unlifted_out};
     return build_maps_loop(path, names_blob, name_off, n_names, scaf_size, n_res, resolution, ctxs, threads, stats5, &lift, &out);
+}
+
+// ---- spanning depth: the read pairs with one end on each side of every cell boundary ---------------------
+// Between hicmi_span_begin and hicmi_span_finish the marks live in buffers of their own: the context's matrix state and
+// an open map build are never touched (the staging of a chunk, d_map_chunk, holds nothing between calls).
+static void span_abandon(hicmi_ctx* c)
+{
+    c->span_marks.reset(); c->d_span_lift.reset(); c->d_span_first.reset();
+    c->span_lift = LiftTables(); c->span_grid = SpanGrid();
+    c->span_size.clear(); c->span_seq_first.clear();
+    c->span_pairs = 0;
+}
+
+// HICMI_SPANS_PLAIN: "1" two atomic adds per marking pair, "0" the combining kernel, anything else the default; read per call
+constexpr bool kSpansPlainByDefault = false;
+static bool spans_plain()
+{
+    const char* env = getenv("HICMI_SPANS_PLAIN");
+    if (env && !strcmp(env, "1")) return true;
+    if (env && !strcmp(env, "0")) return false;
+    return kSpansPlainByDefault;
+}
+
+// the numbering of a build, made on the host before anything is allocated
+struct SpanCells { std::vector<int64_t> cell_first, seq_first; int64_t n_cells = 0; };
+
+static int span_number(const int64_t* scaf_size, int64_t n_scaf, const LiftHost& lift, int64_t step, int64_t max_span, SpanCells* out)
+{
+    if (!scaf_size || n_scaf < 1 || n_scaf > INT_MAX / 2) return fail(HICMI_EINVAL, "bad arguments");
+    if (step < 1) return fail(HICMI_EINVAL, "step %lld is below 1", (long long)step);
+    if (max_span < 0) return fail(HICMI_EINVAL, "max_span %lld is negative", (long long)max_span);
+    int rc = lift_check(scaf_size, n_scaf, lift);
+    if (rc) return rc;
+    out->cell_first.resize((size_t)n_scaf);
+    out->seq_first.resize((size_t)lift.n_seq + 1);
+    out->n_cells = span_number_cells(scaf_size, n_scaf, lift.seq, lift.off, lift.n_seq, step, out->cell_first.data(), out->seq_first.data());
+    if (out->n_cells < 0)
+        return fail(HICMI_EUNSUPPORTED, "step %lld cuts the assembly into more than %lld cells", (long long)step, (long long)SPAN_MAX_CELLS);
+    if (out->n_cells < 1) return fail(HICMI_EINVAL, "no scaffold with a base is placed: there are no cells");
+    return HICMI_OK;
+}
+
+static int span_open(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, const LiftHost& lift, int64_t step, int64_t max_span,
+                     SpanCells&& cells)
+{
+    HIPCHK(hipSetDevice(c->device));
+    span_abandon(c);                                          // a begin without a finish is given up
+    const int64_t m = cells.n_cells;
+    int rc = ensure_all(c->span_marks, m + SPAN_COUNTERS, c->d_span_first, n_scaf, c->d_span_lift, 21 * n_scaf);
+    if (rc) return rc;
+    rc = upload(c, c->d_span_first, cells.cell_first.data(), sizeof(int64_t) * (size_t)n_scaf);
+    if (!rc) rc = lift_upload(c, c->d_span_lift, scaf_size, n_scaf, lift, &c->span_lift);
+    hipError_t e = hipSuccess;
+    if (!rc && (e = hipMemsetAsync(c->span_marks, 0, sizeof(uint64_t) * (size_t)(m + SPAN_COUNTERS), c->stream)) != hipSuccess)
+        rc = fail(HICMI_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e));
+    if (!rc && (e = sync_stream(c)) != hipSuccess) rc = fail(HICMI_EHIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
+    if (rc) { span_abandon(c); return rc; }
+    c->span_grid.cell_first = c->d_span_first; c->span_grid.step = step; c->span_grid.max_span = max_span; c->span_grid.n_cells = m;
+    c->span_size.assign(scaf_size, scaf_size + n_scaf);
+    c->span_seq_first = std::move(cells.seq_first);
+    c->span_pairs = 0;
+    return HICMI_OK;
+}
+
+// the flank and the records of a finish against the open build: nothing on the device is looked at
+static int span_check_records(const hicmi_ctx* c, int64_t flank, const int64_t* recs, int64_t n_rec)
+{
+    if (flank < 1 || flank > SPAN_MAX_FLANK)
+        return fail(HICMI_EINVAL, "flank %lld outside 1 .. %lld", (long long)flank, (long long)SPAN_MAX_FLANK);
+    if (n_rec < 0 || n_rec > INT_MAX / 2 || (n_rec > 0 && !recs)) return fail(HICMI_EINVAL, "bad arguments");
+    const std::vector<int64_t>& first = c->span_seq_first;
+    for (int64_t r = 0; r < n_rec; r++) {
+        const int64_t lo = recs[4 * r], hi = recs[4 * r + 1], q0 = recs[4 * r + 2], q1 = recs[4 * r + 3];
+        // the last sequence that starts at or before q0 is the one that has cells there
+        const size_t q = (size_t)(std::upper_bound(first.begin(), first.end(), q0) - first.begin());
+        if (q0 < 0 || q == 0 || q >= first.size() || first[q - 1] != q0 || first[q] != q1 || lo < q0 || hi < lo || hi >= q1)
+            return fail(HICMI_EINVAL, "record %lld (slots %lld .. %lld of the cells %lld .. %lld) is not a slot range inside one sequence",
+                        (long long)r, (long long)lo, (long long)hi, (long long)q0, (long long)q1);
+    }
+    return HICMI_OK;
+}
+
+// the two scans, the picks and the downloads of an open build, which it closes; an output is written only when all are down
+static int span_close(hicmi_ctx* c, int64_t flank, const int64_t* recs, int64_t n_rec, int64_t* picks_out, uint64_t* counters5_out,
+                      uint64_t* depth_out)
+{
+    const int64_t m = c->span_grid.n_cells;
+    if (c->span_pairs > (((int64_t)1 << 53) - 1) / flank) {
+        span_abandon(c);
+        return fail(HICMI_EUNSUPPORTED, "%lld pairs at a flank of %lld: depth x flank could reach 2^53", (long long)c->span_pairs,
+                    (long long)flank);
+    }
+    struct Close { hicmi_ctx* c; ~Close() { span_abandon(c); } } closing{c};
+    DevBuf<unsigned long long> d_depth, d_sums, d_tiles;
+    DevBuf<int64_t> d_recs;                                   // [records][picks]
+    int rc = ensure_all(d_depth, m, d_sums, m, d_tiles, span_scan_tiles(m), d_recs, 8 * n_rec);
+    if (!rc && n_rec) rc = upload(c, d_recs, recs, sizeof(int64_t) * 4 * (size_t)n_rec);
+    if (rc) return rc;
+    launch_span_scan(c->span_marks, d_depth, m, d_tiles, c->stream);
+    launch_span_scan(d_depth, d_sums, m, d_tiles, c->stream);
+    launch_span_pick(d_depth, d_sums, m, flank, d_recs, n_rec, d_recs + 4 * n_rec, c->stream);
+    HIPCHK(hipGetLastError());
+    std::vector<int64_t> picks((size_t)(4 * n_rec));
+    uint64_t counters[SPAN_COUNTERS];
+    rc = download(c, counters, c->span_marks + m, sizeof(counters));
+    if (!rc && n_rec) rc = download(c, picks.data(), d_recs + 4 * n_rec, sizeof(int64_t) * picks.size());
+    if (!rc && depth_out) {
+        HIPCHK(hipMemcpyAsync(depth_out, d_depth, sizeof(uint64_t) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(sync_stream(c));
+    }
+    if (rc) return rc;
+    if (n_rec) memcpy(picks_out, picks.data(), sizeof(int64_t) * picks.size());
+    memcpy(counters5_out, counters, sizeof(counters));
+    return HICMI_OK;
+}
+
+int hicmi_span_begin(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, const int32_t* lift_seq, const int64_t* lift_off,
+                     const uint8_t* lift_rev, const int64_t* seq_size, int64_t n_seq, int64_t step, int64_t max_span,
+                     int64_t* cell_first_out, int64_t* n_cells_out)
+{
+    if (!c || !cell_first_out || !n_cells_out) return fail(HICMI_EINVAL, "bad arguments");
+    const LiftHost lift{lift_seq, lift_off, lift_rev, seq_size, n_seq};
+    SpanCells cells;
+    int rc = span_number(scaf_size, n_scaf, lift, step, max_span, &cells);
+    if (rc) return rc;
+    const std::vector<int64_t> cell_first = cells.cell_first;
+    const int64_t m = cells.n_cells;
+    rc = span_open(c, scaf_size, n_scaf, lift, step, max_span, std::move(cells));
+    if (rc) return rc;
+    memcpy(cell_first_out, cell_first.data(), sizeof(int64_t) * (size_t)n_scaf);
+    *n_cells_out = m;
+    return HICMI_OK;
+}
+
+int hicmi_span_add_pairs(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b,
+                         int64_t n)
+{
+    if (!c || n < 0 || (n > 0 && (!scaf_a || !pos_a || !scaf_b || !pos_b))) return fail(HICMI_EINVAL, "bad arguments");
+    if (!c->span_marks) return fail(HICMI_EINVAL, "hicmi_span_add_pairs without hicmi_span_begin");
+    int rc_pairs = check_pairs(scaf_a, pos_a, scaf_b, pos_b, n, c->span_size.data(), (int64_t)c->span_size.size(), nullptr, nullptr);
+    if (rc_pairs) return rc_pairs;
+    if (n == 0) return HICMI_OK;
+    HIPCHK(hipSetDevice(c->device));
+    // a HIP error from here on gives the build up: what was marked so far cannot be told
+    int rc = ensure(c->d_map_chunk, 24 * n);
+    const MapChunk k = map_chunk_at(c->d_map_chunk, n);
+    if (!rc) rc = upload(c, k.pos_a, pos_a, sizeof(int64_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.pos_b, pos_b, sizeof(int64_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.scaf_a, scaf_a, sizeof(int32_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.scaf_b, scaf_b, sizeof(int32_t) * (size_t)n);
+    if (!rc) {
+        launch_span_mark(k.scaf_a, k.pos_a, k.scaf_b, k.pos_b, n, c->span_lift, c->span_grid, c->span_marks,
+                         c->span_marks + c->span_grid.n_cells, spans_plain(), c->stream);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = sync_stream(c);
+        if (e != hipSuccess) rc = fail(HICMI_EHIP, "marking a chunk of pairs: %s", hipGetErrorString(e));
+    }
+    if (rc) { span_abandon(c); return rc; }
+    c->span_pairs += n;
+    return HICMI_OK;
+}
+
+int hicmi_span_finish(hicmi_ctx* c, int64_t flank, const int64_t* recs, int64_t n_rec, int64_t* picks_out, uint64_t* counters5_out,
+                      uint64_t* depth_out)
+{
+    if (!c || !counters5_out || (n_rec > 0 && !picks_out)) return fail(HICMI_EINVAL, "bad arguments");
+    if (!c->span_marks) return fail(HICMI_EINVAL, "hicmi_span_finish without hicmi_span_begin");
+    int rc = span_check_records(c, flank, recs, n_rec);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    return span_close(c, flank, recs, n_rec, picks_out, counters5_out, depth_out);
+}
+
+// The same over the pair file in one pass: the chunk loop of build_maps_loop with the marks of one build in place of the maps.
+int hicmi_span_file(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
+                    const int32_t* lift_seq, const int64_t* lift_off, const uint8_t* lift_rev, const int64_t* seq_size, int64_t n_seq,
+                    int64_t step, int64_t max_span, int64_t flank, const int64_t* recs, int64_t n_rec, hicmi_ctx* c, int threads,
+                    int64_t* stats5, int64_t* picks_out, uint64_t* counters5_out, uint64_t* depth_out, int64_t* cell_first_out,
+                    int64_t* n_cells_out)
+{
+    if (!path || !names_blob || !name_off || !scaf_size || !c || !stats5 || !counters5_out || !cell_first_out || !n_cells_out ||
+        n_names < 1 || (n_rec > 0 && !picks_out))
+        return fail(HICMI_EINVAL, "bad arguments");
+    const LiftHost lift{lift_seq, lift_off, lift_rev, seq_size, n_seq};
+    SpanCells cells;
+    int rc = span_number(scaf_size, n_names, lift, step, max_span, &cells);
+    if (rc) return rc;
+    int64_t chunk_pairs = (int64_t)1 << 22;
+    if (const char* env = getenv("HICMI_BUILDMAP_CHUNK_PAIRS")) {
+        const long long v = atoll(env);
+        if (v < 1 || v > ((long long)1 << 28)) return fail(HICMI_EINVAL, "HICMI_BUILDMAP_CHUNK_PAIRS = %s outside 1 .. 2^28", env);
+        chunk_pairs = v;
+    }
+    const std::vector<int64_t> cell_first = cells.cell_first;
+    const int64_t m = cells.n_cells;
+    rc = span_open(c, scaf_size, n_names, lift, step, max_span, std::move(cells));
+    if (rc) return rc;
+    struct OpenSpan { hicmi_ctx* c; bool keep = false; ~OpenSpan() { if (!keep) span_abandon(c); } } own{c};   // given up on every error path
+    // the flank and the records are refused before the file is read
+    rc = span_check_records(c, flank, recs, n_rec);
+    if (rc) return rc;
+    PinBuf<unsigned char> pin[2]; DevBuf<unsigned char> dev[2];
+    int64_t file_bytes = -1;
+    {
+        FILE* fh = fopen(path, "rb");
+        if (!fh) return fail(HICMI_EINVAL, "cannot open %s", path);
+        if (fseeko(fh, 0, SEEK_END) == 0) file_bytes = (int64_t)ftello(fh);
+        fclose(fh);
+        if (file_bytes < 0) return fail(HICMI_EINVAL, "cannot tell the size of %s", path);
+        chunk_pairs = std::max<int64_t>(1, std::min(chunk_pairs, file_bytes / 12 + 1));
+    }
+    const size_t chunk_bytes = (size_t)chunk_pairs * 24;
+    for (int b = 0; b < 2; b++) {
+        HIPCHK(pin[b].reserve((int64_t)chunk_bytes));
+        rc = ensure(dev[b], (int64_t)chunk_bytes);
+        if (rc) return rc;
+    }
+    const bool plain = spans_plain();
+    int64_t next = 0, n_here = 0, st[4], stats[5] = {0, 0, 0, 0, 0};
+    // chunk t + 1 is parsed into the other pinned buffer while chunk t is uploaded and marked on the context's stream
+    auto parse = [&](int b) {
+        const MapChunk h = map_chunk_at(pin[b], chunk_pairs);
+        int prc = hicmi_parse_valid_pairs(path, names_blob, name_off, n_names, scaf_size, threads, next, chunk_pairs, h.scaf_a, h.pos_a,
+                                          h.scaf_b, h.pos_b, &n_here, &next, st);
+        if (!prc) { stats[0] += st[0]; stats[1] += st[1]; stats[2] += st[2]; stats[3] += st[3]; }
+        return prc;
+    };
+    int cur = 0;
+    rc = parse(cur);
+    if (rc) return rc;
+    for (;;) {
+        const int64_t n = n_here;
+        if (n > 0) {
+            const MapChunk h = map_chunk_at(pin[cur], chunk_pairs), d = map_chunk_at(dev[cur], chunk_pairs);
+            HIPCHK(hipMemcpyAsync(d.pos_a, h.pos_a, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(d.pos_b, h.pos_b, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(d.scaf_a, h.scaf_a, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(d.scaf_b, h.scaf_b, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+            launch_span_mark(d.scaf_a, d.pos_a, d.scaf_b, d.pos_b, n, c->span_lift, c->span_grid, c->span_marks, c->span_marks + m, plain,
+                             c->stream);
+            HIPCHK(hipGetLastError());
+            c->span_pairs += n;
+            stats[4]++;
+        }
+        const bool last = next >= file_bytes;                      // the parser has taken the whole file
+        if (!last) rc = parse(cur ^ 1);
+        hipError_t e = hipStreamSynchronize(c->stream);            // chunk t is marked: its two buffers are free again
+        if (rc) return rc;
+        if (e != hipSuccess) return fail(HICMI_EHIP, "marking a chunk of pairs: %s", hipGetErrorString(e));
+        if (last) break;
+        cur ^= 1;
+    }
+    own.keep = true;                                               // span_close closes the build, whatever it returns
+    rc = span_close(c, flank, recs, n_rec, picks_out, counters5_out, depth_out);
+    if (rc) return rc;
+    for (int k = 0; k < 5; k++) stats5[k] = stats[k];
+    memcpy(cell_first_out, cell_first.data(), sizeof(int64_t) * (size_t)n_names);
+    *n_cells_out = m;
+    return HICMI_OK;
 }
 
 // Group support: extends the scaffold vote of assessChromosomeClustering (S2C:1001-1077) with the

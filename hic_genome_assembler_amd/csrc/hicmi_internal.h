@@ -7,6 +7,7 @@
 #include <functional>
 
 #include "liftmap.h"
+#include "span.h"
 
 namespace hicmi {
 
@@ -524,6 +525,24 @@ void launch_buildmap_add(const int32_t* scaf_a, const int64_t* pos_a, const int3
 void launch_pair_stats(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
                        const LiftTables& lift, void* out, hipStream_t s);
 void launch_buildmap_finish(void* cells, int m, hipStream_t s);
+
+// k_spans.hip: spanning depth from read pairs (hicmi_span_*).  marks: n_cells unsigned 64-bit cells, +1 and
+// -1 (two's complement) per marking pair; counters: the five kinds of pairs (SpanKind).  launch_span_scan: out = inclusive
+// prefix sum of in (n elements, in != out), tile_sums: span_scan_tiles(n) elements of scratch.  launch_span_pick: four
+// integers (slot, D, Lsum, Rsum) per record (lo, hi, q0, q1); everything is device memory.
+static constexpr int SPAN_SLICE = 2048;        // pairs a workgroup of the combining k_span_mark brings together: two marks each
+static constexpr int SPAN_SLOT_BITS = 11;
+static constexpr int SPAN_SLOTS = 1 << SPAN_SLOT_BITS;   // slots of its table in LDS (8 bytes each); a slice can need twice as many
+static constexpr int SPAN_PROBES = 8;          // a mark that finds no room within so many probes is added directly
+static constexpr int SPAN_SCAN_ITEMS = 8;      // elements a thread of the scan takes in a row
+static constexpr int SPAN_SCAN_TILE = 2048;    // elements of one workgroup of k_span_tile_sums and k_span_scan_add
+static constexpr int SPAN_SCAN_WIDTH = 1024;   // tile sums the one workgroup of k_span_scan_tiles takes at a time
+void launch_span_mark(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
+                      const LiftTables& lift, const SpanGrid& grid, void* marks, void* counters, bool plain, hipStream_t s);
+int64_t span_scan_tiles(int64_t n);
+void launch_span_scan(const void* in, void* out, int64_t n, void* tile_sums, hipStream_t s);
+void launch_span_pick(const void* depth, const void* depth_sums, int64_t n_cells, int64_t flank, const int64_t* recs, int64_t n_rec,
+                      int64_t* picks, hipStream_t s);
 
 // k_plot.hip
 void launch_plot_select(const double* C, int64_t ldc, const double* np_sum, const double* seq_sum, int kind,

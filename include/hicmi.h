@@ -544,6 +544,49 @@ int hicmi_lift_maps(const char *path, const char *names_blob, const int64_t *nam
                     hicmi_ctx *const *ctxs, int threads, int64_t *stats5, uint64_t *decay_out, uint64_t *seq_cis_out,
                     uint64_t *seq_trans_out, uint64_t *unlifted_out);
 
+/* ---- spanning depth: the read pairs with one end on each side of every cut and junction --------------
+ * The assembly is given by the lift tables of 9m, checked in the same way.  Every placed scaffold of size L > 0 is cut
+ * into ceil(L / step) cells from its left end as it lies in its sequence: position p falls in local cell (p - 1) / step,
+ * on a reversed scaffold in (L - p) / step.  The cells are numbered in one order, sequences ascending and inside a
+ * sequence by offset; gaps hold none.  cell_first_out[s] is the first cell of scaffold s, -1 for a dropped or empty one.
+ * Slot c stands for the boundary after cell c; the last cell of a sequence is its terminator.  A pair whose ends lift to
+ * one sequence, at most max_span apart when max_span is not 0, with the cells ca < cb adds +1 at slot ca and -1 at slot
+ * cb; D, the inclusive prefix sum of the marks, is the number of counted pairs with cell(a) <= c < cell(b), and 0 at every
+ * terminator.  counters5: pairs that marked, cis pairs within max_span in one cell, cis pairs beyond max_span, trans
+ * pairs, unlifted pairs.  Unsigned 64-bit integers throughout: every chunking and arrival order gives the same bits.
+ *
+ * hicmi_span_begin checks the tables, returns the numbering and allocates zeroed marks; a span build that was open is
+ * given up.  The context's matrix state and an open map build (9l, 9m) are never touched by these calls.
+ * hicmi_span_add_pairs checks every index and position on the host like hicmi_map_add_pairs (HICMI_EINVAL, nothing
+ * uploaded, the build unchanged), uploads the arrays and marks them.  HICMI_SPANS_PLAIN=1 in the environment, read at
+ * every call, takes two global atomic adds per marking pair; =0 and the default take the combining kernel, in which a
+ * workgroup sums the marks of its slice per slot in a table in LDS first.  Both give the same bits.
+ * hicmi_span_finish scans the marks into D and D into S and answers the n_rec records (lo, hi, q0, q1) of 4 integers each:
+ * [q0, q1) must be the cells of one sequence and q0 <= lo <= hi < q1.  With Lsum(c) = D[c-F] + .. + D[c-1] and
+ * Rsum(c) = D[c+1] + .. + D[c+F], F = flank, slot c competes when c - F >= q0, c + F <= q1 - 2 and min(Lsum, Rsum) > 0;
+ * its ratio is (double)(D[c] F) / (double)min(Lsum, Rsum).  picks_out[4 r ..] = slot, D, Lsum, Rsum of the competing slot
+ * of [lo, hi] with the lowest ratio, the lowest slot among equal ratios; slot -1 (and zeros) when none competes.
+ * depth_out (may be NULL) receives D of every cell.  The build is closed.  HICMI_EINVAL, the build left open and
+ * unchanged: no open build, a flank outside 1 .. 4096, a record that is not a slot range inside one sequence.
+ * HICMI_EINVAL at begin: step < 1, max_span < 0, tables refused, no cells; HICMI_EUNSUPPORTED: more than 2^27 cells, or
+ * (at finish, which closes the build) pairs x flank could reach 2^53.
+ *
+ * hicmi_span_file: begin, every pair of the file, finish, in one pass with the chunked parser as in hicmi_build_maps
+ * (HICMI_BUILDMAP_CHUNK_PAIRS, stats5 as there).  Tables, flank and records are refused before the file is read; on any
+ * error no output is written, and no span build stays open. */
+int hicmi_span_begin(hicmi_ctx *ctx, const int64_t *scaf_size, int64_t n_scaf, const int32_t *lift_seq,
+                     const int64_t *lift_off, const uint8_t *lift_rev, const int64_t *seq_size, int64_t n_seq,
+                     int64_t step, int64_t max_span, int64_t *cell_first_out, int64_t *n_cells_out);
+int hicmi_span_add_pairs(hicmi_ctx *ctx, const int32_t *scaf_a, const int64_t *pos_a,
+                         const int32_t *scaf_b, const int64_t *pos_b, int64_t n);
+int hicmi_span_finish(hicmi_ctx *ctx, int64_t flank, const int64_t *recs, int64_t n_rec, int64_t *picks_out,
+                      uint64_t *counters5_out, uint64_t *depth_out);
+int hicmi_span_file(const char *path, const char *names_blob, const int64_t *name_off, int64_t n_names,
+                    const int64_t *scaf_size, const int32_t *lift_seq, const int64_t *lift_off, const uint8_t *lift_rev,
+                    const int64_t *seq_size, int64_t n_seq, int64_t step, int64_t max_span, int64_t flank,
+                    const int64_t *recs, int64_t n_rec, hicmi_ctx *ctx, int threads, int64_t *stats5, int64_t *picks_out,
+                    uint64_t *counters5_out, uint64_t *depth_out, int64_t *cell_first_out, int64_t *n_cells_out);
+
 /* ---- plot support -----------------------------------------------------------------------------
  * plotContactMap (plotContactMaps.py:15-91) colours every cell of an N x N matrix between two
  * numpy.percentile limits.  The matrix stays on the device: kind 0 = raw contacts (Part 2 plots,
