@@ -100,6 +100,11 @@ SIGNATURES = {
     "hicmi_span_finish": (ctypes.c_int, [_vp, c_i64, _vp, c_i64, _vp, _vp, _vp]),
     "hicmi_span_file": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, _vp, _vp, _vp, _vp, c_i64, c_i64, c_i64,
                                        c_i64, _vp, c_i64, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(c_i64)]),
+    "hicmi_split_pairs": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, c_i64, _vp, c_i64, _vp, _vp, c_i64, _vp, _vp, _vp, _vp, _vp]),
+    "hicmi_split_maps": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, _vp, _vp, c_i64, c_i64, _vp, _vp,
+                                        ctypes.c_int, _vp, _vp]),
+    "hicmi_split_valid_pairs": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, _vp, _vp, c_i64,
+                                               ctypes.c_char_p, _vp, ctypes.c_int, _vp]),
     "hicmi_plot_percentiles": (ctypes.c_int, [_vp, ctypes.c_int, _vp, c_i64, _vp, c_i64, _vp]),
     "hicmi_plot_downsample": (ctypes.c_int, [_vp, ctypes.c_int, _vp, c_i64, c_i64, _vp]),
     "hicmi_p2_insert_all_multi": (ctypes.c_int, [c_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -363,6 +368,79 @@ def span_file(path, names, sizes, lift_seq, lift_off, lift_rev, seq_sizes, step,
     return tuple(int(v) for v in stats), cell_first, picks, counters, None if depth is None else depth[:n_cells.value]
 
 
+def _split_tables(sizes, piece_first, piece_start):
+    """The piece tables of DESIGN.md 9o as the library takes them: (scaffold sizes, piece_first int32[S + 1], piece_start
+    int64[n_piece])."""
+    size = np.ascontiguousarray(sizes, dtype=np.int64)
+    first = np.ascontiguousarray(piece_first, dtype=np.int32)
+    start = np.ascontiguousarray(piece_start, dtype=np.int64)
+    if size.ndim != 1 or first.shape != (len(size) + 1,) or start.ndim != 1:
+        raise ValueError("one piece_first per scaffold size and one more, and a vector of piece starts")
+    return size, first, start
+
+
+def new_split_counters(n_piece):
+    """Zeroed counters uint64[4, n_piece] = (within, sibling, other, mark) for Context.split_pairs and split_maps to add to."""
+    return np.zeros((4, int(n_piece)), np.uint64)
+
+
+def _split_counters_into(into, n_piece):
+    if into is None:
+        return new_split_counters(n_piece)
+    if into.dtype != np.uint64 or into.shape != (4, n_piece) or not into.flags.c_contiguous or not into.flags.writeable:
+        raise ValueError("into must be what new_split_counters(n_piece) returns")
+    return into
+
+
+def split_spanning(piece_first, counters):
+    """``spanning`` of every piece from the mark row of the counters: the prefix sum of the marks inside each scaffold
+    (uint64, wrapping), which is the number of pairs of the scaffold with one end at or before the piece's last base and one
+    after it; 0 at the last piece of a scaffold."""
+    first = np.asarray(piece_first, dtype=np.int64)
+    mark = np.asarray(counters, dtype=np.uint64).reshape(4, -1)[3]
+    total = np.cumsum(mark, dtype=np.uint64)
+    before = np.concatenate([np.zeros(1, np.uint64), total])[first[:-1]]
+    return total - np.repeat(before, np.diff(first))
+
+
+def split_maps(path, names, sizes, piece_first, piece_start, resolutions, ctxs, threads: int = 0, into=None):
+    """build_maps on the pieces the scaffolds are cut into (hicmi_split_maps): one pass over the pair file,
+    every chunk moved from the scaffolds to the pieces on the device and counted into the map of every resolution -
+    ``ctxs[k]`` receives the one at ``resolutions[k]``, cut from the pieces - and the counters of the pieces, added to
+    ``into`` (new_split_counters; None: fresh ones).  No resolution: the counters alone, on the device of ``ctxs[0]``,
+    which is left as it is.  Returns ((lines, used, unknown_scaffold, out_of_range, chunks), counters)."""
+    blob, off = _name_blob(names)
+    size, first, start = _split_tables(sizes, piece_first, piece_start)
+    res = np.ascontiguousarray(resolutions, dtype=np.int64).reshape(-1)
+    if size.shape != (len(names),) or not len(ctxs) or len(ctxs) != max(len(res), 1):
+        raise ValueError("one size per scaffold name and one context per resolution (one context when there is no resolution)")
+    out = _split_counters_into(into, len(start))
+    handles = (_vp * len(ctxs))(*[c._h for c in ctxs])
+    stats = np.zeros(5, np.int64)
+    _check(load().hicmi_split_maps(os.fsencode(path), blob, _ptr(off), len(names), _ptr(size), _ptr(first), _ptr(start), len(start),
+                                   len(res), _ptr(res), handles, int(threads), _ptr(stats), _ptr(out)))
+    if len(res):
+        for c in ctxs:
+            c.n = c.contacts_device()[1]
+            c._keepalive = None
+    return tuple(int(v) for v in stats), out
+
+
+def split_valid_pairs(path_in, path_out, names, sizes, piece_first, piece_start, piece_names, threads: int = 0):
+    """``path_in`` written again as ``path_out`` with both ends of every kept line moved to the pieces
+    (hicmi_split_valid_pairs; host code).  Returns (lines, used, unknown_scaffold, out_of_range)."""
+    blob, off = _name_blob(names)
+    piece_blob, piece_off = _name_blob(piece_names)
+    size, first, start = _split_tables(sizes, piece_first, piece_start)
+    if size.shape != (len(names),) or len(piece_names) != len(start):
+        raise ValueError("one size per scaffold name and one name per piece")
+    stats = np.zeros(4, np.int64)
+    _check(load().hicmi_split_valid_pairs(os.fsencode(path_in), os.fsencode(path_out), blob, _ptr(off), len(names), _ptr(size),
+                                          _ptr(first), _ptr(start), len(start), piece_blob, _ptr(piece_off), int(threads),
+                                          _ptr(stats)))
+    return tuple(int(v) for v in stats)
+
+
 def hypergeom_sf(x, M, n, N) -> float:
     """hyper_geom(x, M, n, N) of scaffoldToChromosomes.py:352-368, evaluated by libhicmi's host code."""
     return float(load().hicmi_hypergeom_sf(int(x), int(M), int(n), int(N)))
@@ -560,6 +638,22 @@ class Context:
         depth = np.zeros(max(getattr(self, "_span_cells", 0), 1), np.uint64) if want_depth else None
         _check(self._lib.hicmi_span_finish(self._h, int(flank), _ptr(rec), len(rec), _ptr(picks), _ptr(counters), _ptr(depth)))
         return picks, counters, None if depth is None else depth[:self._span_cells]
+
+    def split_pairs(self, scaf_a, pos_a, scaf_b, pos_b, sizes, piece_first, piece_start, into=None):
+        """The pairs (scaffold index, 1-based position) x 2 moved to the pieces the scaffolds are cut into
+        (hicmi_split_pairs): (piece a, position a, piece b, position b, counters), the counters uint64[4,
+        n_piece] = (within, sibling, other, mark) added to ``into`` (new_split_counters; None: fresh ones).  The matrix, an
+        open map build and an open span build are untouched."""
+        sa, sb = np.ascontiguousarray(scaf_a, dtype=np.int32), np.ascontiguousarray(scaf_b, dtype=np.int32)
+        pa, pb = np.ascontiguousarray(pos_a, dtype=np.int64), np.ascontiguousarray(pos_b, dtype=np.int64)
+        if not (sa.ndim == 1 and sa.shape == sb.shape == pa.shape == pb.shape):
+            raise ValueError("the four arrays must be vectors of one length")
+        size, first, start = _split_tables(sizes, piece_first, piece_start)
+        out = _split_counters_into(into, len(start))
+        ka, kb, xa, xb = np.empty_like(sa), np.empty_like(sb), np.empty_like(pa), np.empty_like(pb)
+        _check(self._lib.hicmi_split_pairs(self._h, _ptr(sa), _ptr(pa), _ptr(sb), _ptr(pb), len(sa), _ptr(size), len(size),
+                                           _ptr(first), _ptr(start), len(start), _ptr(ka), _ptr(xa), _ptr(kb), _ptr(xb), _ptr(out)))
+        return ka, xa, kb, xb, out
 
     def group_sums(self, grp, scaf, n_groups, n_scaffolds, want_bins=True):
         """Group support sums (hicmi_group_sums): (bin sums n x n_groups or None, scaffold sums

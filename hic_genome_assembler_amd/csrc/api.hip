@@ -878,19 +878,125 @@ int hicmi_map_finish(hicmi_ctx* c, int64_t* pairs_out)
     return map_install(c, c->stream, pairs_out);
 }
 
-// The chunk loop of hicmi_build_maps and hicmi_lift_maps.  `lift` (hicmi_lift_maps): every build is a lifted one, the
-// statistics of every chunk are counted beside the maps, and `stat_out` receives them when the whole file is counted.
+// ---- scaffolds cut into pieces: the tables of a split as the caller hands them over --------------------------
+struct SplitHost { const int32_t* piece_first; const int64_t* piece_start; int64_t n_piece; };
+
+// HICMI_SPLIT_PLAIN: "1" the literal kernel (a scan over the pieces, one atomic add per counter and pair), "0" the
+// combining kernel, anything else the default; read per call
+constexpr bool kSplitPlainByDefault = false;
+static bool split_plain()
+{
+    const char* env = getenv("HICMI_SPLIT_PLAIN");
+    if (env && !strcmp(env, "1")) return true;
+    if (env && !strcmp(env, "0")) return false;
+    return kSplitPlainByDefault;
+}
+
+static int split_check(const int64_t* scaf_size, int64_t n_scaf, const SplitHost& split)
+{
+    if (!scaf_size || n_scaf < 1 || n_scaf > INT_MAX / 4 || !split.piece_first || !split.piece_start || split.n_piece < n_scaf ||
+        split.n_piece > INT_MAX / 4)                              // 4 n_piece counters, each a 32-bit key of the kernel's table
+        return fail(HICMI_EINVAL, "bad arguments");
+    char msg[256];
+    if (split_check_tables(scaf_size, n_scaf, split.piece_first, split.piece_start, split.n_piece, msg, sizeof(msg)))
+        return fail(HICMI_EINVAL, "%s", msg);
+    return HICMI_OK;
+}
+
+// the sizes of the pieces of tables that passed split_check: the grid a split map is cut from
+static std::vector<int64_t> split_piece_sizes(const int64_t* scaf_size, int64_t n_scaf, const SplitHost& split)
+{
+    std::vector<int64_t> out((size_t)split.n_piece);
+    for (int64_t s = 0; s < n_scaf; s++)
+        for (int64_t k = split.piece_first[s]; k < split.piece_first[s + 1]; k++)
+            out[(size_t)k] = (k + 1 < split.piece_first[s + 1] ? split.piece_start[k + 1] : scaf_size[s]) - split.piece_start[k];
+    return out;
+}
+
+// the tables as one device image, 8-byte fields first: [piece_start n_piece][piece_first n_scaf + 1]
+static int64_t split_image_bytes(int64_t n_scaf, int64_t n_piece) { return 8 * n_piece + 4 * (n_scaf + 1); }
+static int split_upload(hicmi_ctx* c, unsigned char* image, int64_t n_scaf, const SplitHost& split, SplitTables* out)
+{
+    int64_t* d_start = reinterpret_cast<int64_t*>(image);
+    int32_t* d_first = reinterpret_cast<int32_t*>(d_start + split.n_piece);
+    int rc = upload(c, d_start, split.piece_start, sizeof(int64_t) * (size_t)split.n_piece);
+    if (!rc) rc = upload(c, d_first, split.piece_first, sizeof(int32_t) * (size_t)(n_scaf + 1));
+    if (rc) return rc;
+    out->piece_start = d_start; out->piece_first = d_first;
+    out->n_scaf = (int32_t)n_scaf; out->n_piece = (int32_t)split.n_piece;
+    return HICMI_OK;
+}
+
+// A chunk of pairs on host arrays moved to the pieces, and what it adds to the counters of the pieces.  No matrix state,
+// no open build: the chunk is staged in d_map_chunk, which holds nothing between calls, the rest in buffers of the call.
+int hicmi_split_pairs(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
+                      const int64_t* scaf_size, int64_t n_scaf, const int32_t* piece_first, const int64_t* piece_start, int64_t n_piece,
+                      int32_t* piece_a_out, int64_t* pos_a_out, int32_t* piece_b_out, int64_t* pos_b_out, uint64_t* counters_out)
+{
+    if (!c || n < 0 || n > INT_MAX || !counters_out ||
+        (n > 0 && (!scaf_a || !pos_a || !scaf_b || !pos_b || !piece_a_out || !pos_a_out || !piece_b_out || !pos_b_out)))
+        return fail(HICMI_EINVAL, "bad arguments");
+    const SplitHost split{piece_first, piece_start, n_piece};
+    int rc = split_check(scaf_size, n_scaf, split);
+    if (!rc) rc = check_pairs(scaf_a, pos_a, scaf_b, pos_b, n, scaf_size, n_scaf, nullptr, nullptr);
+    if (rc || n == 0) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    DevBuf<unsigned char> d_tables;
+    DevBuf<unsigned long long> d_counters;
+    const int64_t n_counters = SPLIT_COUNTERS * n_piece;
+    rc = ensure(c->d_map_chunk, 24 * n);
+    if (!rc) rc = ensure_all(d_tables, split_image_bytes(n_scaf, n_piece), d_counters, n_counters);
+    if (rc) return rc;
+    SplitTables tables;
+    const MapChunk k = map_chunk_at(c->d_map_chunk, n);
+    rc = split_upload(c, d_tables, n_scaf, split, &tables);
+    if (!rc) rc = upload(c, k.pos_a, pos_a, sizeof(int64_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.pos_b, pos_b, sizeof(int64_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.scaf_a, scaf_a, sizeof(int32_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.scaf_b, scaf_b, sizeof(int32_t) * (size_t)n);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(d_counters, 0, sizeof(uint64_t) * (size_t)n_counters, c->stream));
+    launch_split_pairs(k.scaf_a, k.pos_a, k.scaf_b, k.pos_b, n, tables, d_counters, split_plain(), c->stream);
+    HIPCHK(hipGetLastError());
+    // everything comes down before an output is written
+    std::vector<unsigned char> moved((size_t)(24 * n));
+    std::vector<uint64_t> got((size_t)n_counters);
+    rc = download(c, moved.data(), c->d_map_chunk, moved.size());
+    if (!rc) rc = download(c, got.data(), d_counters, sizeof(uint64_t) * got.size());
+    if (rc) return rc;
+    const MapChunk h = map_chunk_at(moved.data(), n);
+    memcpy(pos_a_out, h.pos_a, sizeof(int64_t) * (size_t)n);
+    memcpy(pos_b_out, h.pos_b, sizeof(int64_t) * (size_t)n);
+    memcpy(piece_a_out, h.scaf_a, sizeof(int32_t) * (size_t)n);
+    memcpy(piece_b_out, h.scaf_b, sizeof(int32_t) * (size_t)n);
+    for (int64_t q = 0; q < n_counters; q++) counters_out[q] += got[(size_t)q];
+    return HICMI_OK;
+}
+
+// The chunk loop of hicmi_build_maps, hicmi_lift_maps and hicmi_split_maps.  `lift` (hicmi_lift_maps): every build is a
+// lifted one, the statistics of every chunk are counted beside the maps, and `stat_out` receives them when the whole file
+// is counted.  `split` (hicmi_split_maps): every chunk is moved to the pieces before it is counted, the maps are cut
+// from the pieces, and `split_out` receives the counters of the pieces; n_res may then be 0 (the counters alone), and
+// ctxs[0] lends its device and its stream.
 struct LiftStatsOut { uint64_t *decay, *seq_cis, *seq_trans, *unlifted; };
 
 static int build_maps_loop(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names,
                            const int64_t* scaf_size, int64_t n_res, const int64_t* resolution, hicmi_ctx* const* ctxs, int threads,
-                           int64_t* stats5, const LiftHost* lift, const LiftStatsOut* stat_out)
+                           int64_t* stats5, const LiftHost* lift, const LiftStatsOut* stat_out, const SplitHost* split = nullptr,
+                           uint64_t* split_out = nullptr)
 {
-    if (!path || !names_blob || !name_off || !scaf_size || !resolution || !ctxs || !stats5 || n_names < 1 || n_res < 1)
+    if (!path || !names_blob || !name_off || !scaf_size || !ctxs || !stats5 || n_names < 1 || n_res < (split ? 0 : 1) ||
+        (n_res > 0 && !resolution) || (split && (!split_out || !ctxs[0])))
         return fail(HICMI_EINVAL, "bad arguments");
     if (lift && (!stat_out->decay || !stat_out->seq_cis || !stat_out->seq_trans || !stat_out->unlifted))
         return fail(HICMI_EINVAL, "bad arguments");
     for (int k = 0; k < 5; k++) stats5[k] = 0;
+    std::vector<int64_t> piece_size;                              // a split call: the grid of its maps
+    if (split) {
+        int rc = split_check(scaf_size, n_names, *split);
+        if (rc) return rc;
+        piece_size = split_piece_sizes(scaf_size, n_names, *split);
+    }
     for (int64_t k = 0; k < n_res; k++) {
         if (!ctxs[k] || ctxs[k]->device != ctxs[0]->device) return fail(HICMI_EINVAL, "contexts must share one device");
         for (int64_t q = 0; q < k; q++) if (ctxs[q] == ctxs[k]) return fail(HICMI_EINVAL, "one context per resolution");
@@ -906,14 +1012,25 @@ static int build_maps_loop(const char* path, const char* names_blob, const int64
     // everything the call owns: two pinned chunks for the parser, two device chunks for the kernels
     PinBuf<unsigned char> pin[2]; DevBuf<unsigned char> dev[2];
     DevBuf<unsigned long long> d_stats;                           // a lifted call: the counters of k_pair_stats
+    DevBuf<unsigned char> d_split; DevBuf<unsigned long long> d_split_counters;   // a split call: its tables and counters
+    SplitTables split_tables;
     struct OpenBuilds {                                           // given up on every error path
         hicmi_ctx* const* ctxs; int64_t n_res; bool keep = false;
         ~OpenBuilds() { if (!keep) for (int64_t k = 0; k < n_res; k++) map_abandon(ctxs[k]); }
     } own{ctxs, n_res};
     // begin on every context first: a resolution that cannot be built is refused before the file is read
     for (int64_t k = 0; k < n_res; k++) {
-        int rc = map_open(ctxs[k], scaf_size, n_names, resolution[k], lift);
+        int rc = split ? map_open(ctxs[k], piece_size.data(), split->n_piece, resolution[k], nullptr)
+                       : map_open(ctxs[k], scaf_size, n_names, resolution[k], lift);
         if (rc) return rc;
+    }
+    const int64_t n_split = split ? SPLIT_COUNTERS * split->n_piece : 0;
+    if (split) {
+        int rc = ensure_all(d_split, split_image_bytes(n_names, split->n_piece), d_split_counters, n_split);
+        if (!rc) rc = split_upload(c0, d_split, n_names, *split, &split_tables);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(d_split_counters, 0, sizeof(uint64_t) * (size_t)n_split, c0->stream));
+        HIPCHK(sync_stream(c0));                                  // the tables have left the upload arena
     }
     const int64_t n_stats = lift ? LIFT_DECAY_SLOTS + 2 * lift->n_seq + 1 : 0;
     if (lift) {
@@ -938,6 +1055,7 @@ static int build_maps_loop(const char* path, const char* names_blob, const int64
         if (rc) return rc;
     }
     const bool plain = lift ? liftmap_plain() : buildmap_plain();
+    const bool literal_split = split && split_plain();
     int64_t next = 0, n_here = 0, st[4];
     // chunk t + 1 is parsed into the other pinned buffer while chunk t is uploaded and counted on c0's stream
     auto parse = [&](int b) {
@@ -958,6 +1076,7 @@ static int build_maps_loop(const char* path, const char* names_blob, const int64
             HIPCHK(hipMemcpyAsync(d.pos_b, h.pos_b, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, c0->stream));
             HIPCHK(hipMemcpyAsync(d.scaf_a, h.scaf_a, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c0->stream));
             HIPCHK(hipMemcpyAsync(d.scaf_b, h.scaf_b, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c0->stream));
+            if (split) launch_split_pairs(d.scaf_a, d.pos_a, d.scaf_b, d.pos_b, n, split_tables, d_split_counters, literal_split, c0->stream);
             for (int64_t k = 0; k < n_res; k++) {
                 hicmi_ctx* c = ctxs[k];
                 launch_buildmap_add(d.scaf_a, d.pos_a, d.scaf_b, d.pos_b, n, c->d_map_first, (int)c->map_first.size(), c->map_res,
@@ -982,6 +1101,8 @@ static int build_maps_loop(const char* path, const char* names_blob, const int64
         HIPCHK(hipMemcpy(got.data(), d_stats, sizeof(uint64_t) * (size_t)n_stats, hipMemcpyDeviceToHost));
         for (int64_t k = 0; k < n_res; k++) ctxs[k]->map_pairs -= (int64_t)got[(size_t)n_stats - 1];
     }
+    std::vector<uint64_t> got_split((size_t)n_split);
+    if (split) HIPCHK(hipMemcpy(got_split.data(), d_split_counters, sizeof(uint64_t) * (size_t)n_split, hipMemcpyDeviceToHost));
     // every chunk is counted on every map: from here on the contexts change
     own.keep = true;
     for (int64_t k = 0; k < n_res; k++) {
@@ -990,6 +1111,7 @@ static int build_maps_loop(const char* path, const char* names_blob, const int64
         if (rc) { for (int64_t q = k + 1; q < n_res; q++) map_abandon(ctxs[q]); return rc; }
     }
     if (lift) stats_add(got.data(), lift->n_seq, stat_out->decay, stat_out->seq_cis, stat_out->seq_trans, stat_out->unlifted);
+    for (int64_t q = 0; q < n_split; q++) split_out[q] += got_split[(size_t)q];
     return HICMI_OK;
 }
 
@@ -1007,6 +1129,16 @@ int hicmi_lift_maps(const char* path, const char* names_blob, const int64_t* nam
     const LiftHost lift{lift_seq, lift_off, lift_rev, seq_size, n_seq};
     const LiftStatsOut out{decay_out, seq_cis_out, seq_trans_out, unlifted_out};
     return build_maps_loop(path, names_blob, name_off, n_names, scaf_size, n_res, resolution, ctxs, threads, stats5, &lift, &out);
+}
+
+// hicmi_build_maps on the pieces the scaffolds are cut into: the parser reads the scaffolds' coordinates
+int hicmi_split_maps(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
+                     const int32_t* piece_first, const int64_t* piece_start, int64_t n_piece, int64_t n_res, const int64_t* resolution,
+                     hicmi_ctx* const* ctxs, int threads, int64_t* stats5, uint64_t* counters_out)
+{
+    const SplitHost split{piece_first, piece_start, n_piece};
+    return build_maps_loop(path, names_blob, name_off, n_names, scaf_size, n_res, resolution, ctxs, threads, stats5, nullptr, nullptr,
+                           &split, counters_out);
 }
 
 // ---- spanning depth: the read pairs with one end on each side of every cell boundary ---------------------

@@ -8,6 +8,7 @@
 
 #include "liftmap.h"
 #include "span.h"
+#include "split.h"
 
 namespace hicmi {
 
@@ -543,6 +544,16 @@ int64_t span_scan_tiles(int64_t n);
 void launch_span_scan(const void* in, void* out, int64_t n, void* tile_sums, hipStream_t s);
 void launch_span_pick(const void* depth, const void* depth_sums, int64_t n_cells, int64_t flank, const int64_t* recs, int64_t n_rec,
                       int64_t* picks, hipStream_t s);
+
+// k_split.hip: a chunk of pairs moved in place from scaffolds to the pieces they are cut into (hicmi_split_*),
+// each pair adding to counters[4 n_piece] = [within][sibling][other][mark] of its pieces; everything is device memory.
+static constexpr int SPLIT_SLICE = 2048;       // pairs a workgroup of the combining k_split_pairs takes at a time: up to four counters each
+static constexpr int SPLIT_SLOT_BITS = 11;
+static constexpr int SPLIT_SLOTS = 1 << SPLIT_SLOT_BITS;   // slots of its table in LDS (8 bytes each), kept over all its slices
+static constexpr int SPLIT_PROBES = 8;         // a contribution that finds no room within so many probes is added directly
+static constexpr int SPLIT_MAX_BLOCKS = 1024;  // workgroups of the grid-stride loop: four per compute unit of an MI355X
+void launch_split_pairs(int32_t* scaf_a, int64_t* pos_a, int32_t* scaf_b, int64_t* pos_b, int64_t n, const SplitTables& tables,
+                        void* counters, bool plain, hipStream_t s);
 
 // k_plot.hip
 void launch_plot_select(const double* C, int64_t ldc, const double* np_sum, const double* seq_sum, int kind,

@@ -29,7 +29,10 @@
 #include <thread>
 #include <vector>
 
+#include <hip/hip_runtime.h>   // split.h's functions are __host__ __device__ under hipcc
+
 #include "../../include/hicmi.h"
+#include "split.h"
 
 namespace hicmi { int set_error(int code, const char* msg); }   // api.hip: records the message for hicmi_last_error()
 
@@ -525,6 +528,138 @@ extern "C" int hicmi_parse_valid_pairs(const char* path, const char* names_blob,
         }
     }
     *n_out = kept; *next_byte_out = (int64_t)pos;
+    stats4[0] = lines; stats4[1] = kept; stats4[2] = unknown; stats4[3] = out_of_range;
+    return HICMI_OK;
+}
+
+// ---- valid pairs rewritten onto the pieces of cut scaffolds (splitScaffolds) ------------------------------------
+// Every line the chunked parser keeps is written again with its columns 1, 2, 4 and 5 - scaffold and position of both
+// ends - replaced by the piece and the position in the piece (split.h); every other byte of the line stays.  The lines
+// the parser skips are dropped.  A window of the file is cut at line starts into one part per thread, and the parts are
+// written in file order: a line is rewritten on its own, so the bytes written do not depend on the number of threads.
+namespace {
+struct SplitPart { std::string text; int64_t lines = 0, kept = 0, unknown = 0, out_of_range = 0, bad = -1; };
+
+void rewrite_pair_lines(const char* data, const char* begin, const char* end, const NameMap& name_id, const int64_t* scaf_size,
+                        const hicmi::SplitTables& tables, const char* piece_names, const int64_t* piece_name_off, SplitPart& part)
+{
+    const char* p = begin;
+    std::string_view last_name[2];                     // as in parse_pair_lines: the previous line's names first
+    int32_t last_id[2] = {-1, -1};
+    auto lookup = [&](int k, const char* s, const char* e) -> int32_t {
+        const std::string_view name(s, (size_t)(e - s));
+        if (last_name[k].data() && name == last_name[k]) return last_id[k];
+        const auto it = name_id.find(name);
+        last_name[k] = name;
+        return last_id[k] = it == name_id.end() ? -1 : it->second;
+    };
+    auto put_end = [&](int32_t piece, int64_t pos) {
+        part.text.append(piece_names + piece_name_off[piece], (size_t)(piece_name_off[piece + 1] - piece_name_off[piece]));
+        part.text.push_back('\t');
+        char digits[24];
+        const auto r = std::to_chars(digits, digits + sizeof(digits), (long long)pos);
+        part.text.append(digits, (size_t)(r.ptr - digits));
+    };
+    while (p < end) {
+        const char* eol = (const char*)memchr(p, '\n', (size_t)(end - p));
+        if (!eol) eol = end;
+        const char* le = eol;
+        while (le > p && le[-1] == '\r') le--;
+        const char* col[7];
+        const int nc = split_cols(p, le, col);
+        const char* c5_end = nc >= 7 ? col[6] - 1 : le;
+        int64_t p1 = 0, p2 = 0;
+        if (nc < 6 || !parse_pos(col[2], col[3] - 1, p1) || !parse_pos(col[5], c5_end, p2)) {
+            part.bad = (int64_t)(p - data);
+            return;
+        }
+        part.lines++;
+        const char* next = eol < end ? eol + 1 : end;
+        const int32_t a = lookup(0, col[1], col[2] - 1), b = lookup(1, col[4], col[5] - 1);
+        if (a < 0 || b < 0) part.unknown++;
+        else if (p1 < 1 || p1 > scaf_size[a] || p2 < 1 || p2 > scaf_size[b]) part.out_of_range++;
+        else {
+            int64_t x1, x2;
+            const int32_t k1 = hicmi::split_end(tables, a, p1, &x1), k2 = hicmi::split_end(tables, b, p2, &x2);
+            part.text.append(p, (size_t)(col[1] - p));                         // column 0 and its tab
+            put_end(k1, x1);
+            part.text.append(col[3] - 1, (size_t)(col[4] - (col[3] - 1)));     // the tab, column 3 and its tab
+            put_end(k2, x2);
+            part.text.append(c5_end, (size_t)(next - c5_end));                 // the further columns and the line end as they are
+            part.kept++;
+        }
+        p = next;
+    }
+}
+}  // namespace
+
+extern "C" int hicmi_split_valid_pairs(const char* path_in, const char* path_out, const char* names_blob, const int64_t* name_off,
+                                       int64_t n_names, const int64_t* scaf_size, const int32_t* piece_first, const int64_t* piece_start,
+                                       int64_t n_piece, const char* piece_names_blob, const int64_t* piece_name_off, int threads,
+                                       int64_t* stats4)
+{
+    auto err = [](int code, const std::string& msg) { return hicmi::set_error(code, msg.c_str()); };
+    if (!path_in || !path_out || !names_blob || !name_off || !scaf_size || !piece_first || !piece_start || !piece_names_blob ||
+        !piece_name_off || !stats4 || n_names < 1 || n_names > INT32_MAX / 4 || n_piece < n_names || n_piece > INT32_MAX / 4)
+        return err(HICMI_EINVAL, "bad arguments");
+    for (int k = 0; k < 4; k++) stats4[k] = 0;
+    char msg[256];
+    if (hicmi::split_check_tables(scaf_size, n_names, piece_first, piece_start, n_piece, msg, sizeof(msg))) return err(HICMI_EINVAL, msg);
+    hicmi::SplitTables tables;
+    tables.piece_first = piece_first; tables.piece_start = piece_start;
+    tables.n_scaf = (int32_t)n_names; tables.n_piece = (int32_t)n_piece;
+    const NameMap name_id = make_name_map(names_blob, name_off, n_names);
+    MappedFile file;
+    if (int rc = file.open_path(path_in)) return rc;
+    const size_t size = file.size;
+    const char* data = file.data;
+    // written under a temporary name and renamed when it is whole: an error leaves no output file behind
+    const std::string tmp = std::string(path_out) + ".part";
+    FILE* fh = fopen(tmp.c_str(), "wb");
+    if (!fh) return err(HICMI_EINVAL, std::string("cannot open ") + tmp + " for writing");
+    auto give_up = [&](int code, const std::string& what) { fclose(fh); remove(tmp.c_str()); return err(code, what); };
+    int T_max = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
+    T_max = std::max(1, std::min(T_max, 64));
+    constexpr size_t kWindow = (size_t)64 << 20;
+    int64_t lines = 0, kept = 0, unknown = 0, out_of_range = 0;
+    size_t pos = 0;
+    while (pos < size) {
+        size_t w_end = size;
+        if (size - pos > kWindow) {
+            const char* nl = (const char*)memchr(data + pos + kWindow, '\n', size - pos - kWindow);
+            w_end = nl ? (size_t)(nl - data) + 1 : size;
+        }
+        const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)T_max, (w_end - pos) / 4096));
+        std::vector<size_t> cut((size_t)T + 1, w_end);
+        cut[0] = pos;
+        for (int t = 1; t < T; t++) {
+            size_t p = pos + (w_end - pos) / (size_t)T * (size_t)t;
+            while (p < w_end && data[p] != '\n') p++;
+            cut[(size_t)t] = p < w_end ? p + 1 : w_end;
+        }
+        std::vector<SplitPart> part((size_t)T);
+        auto work = [&](int t) {
+            part[(size_t)t].text.reserve(cut[(size_t)t + 1] - cut[(size_t)t] + 64);
+            rewrite_pair_lines(data, data + cut[(size_t)t], data + cut[(size_t)t + 1], name_id, scaf_size, tables, piece_names_blob,
+                               piece_name_off, part[(size_t)t]);
+        };
+        {
+            std::vector<std::thread> pool;
+            for (int t = 1; t < T; t++) pool.emplace_back(work, t);
+            work(0);
+            for (auto& th : pool) th.join();
+        }
+        for (const SplitPart& mine : part) {
+            // the parts are in file order and each stops at its first malformed line: this is the first one of the file
+            if (mine.bad >= 0) return give_up(HICMI_EINVAL, "malformed valid-pair line at byte " + std::to_string(mine.bad));
+            if (!mine.text.empty() && fwrite(mine.text.data(), 1, mine.text.size(), fh) != mine.text.size())
+                return give_up(HICMI_EINVAL, std::string("write error on ") + tmp);
+            lines += mine.lines; kept += mine.kept; unknown += mine.unknown; out_of_range += mine.out_of_range;
+        }
+        pos = w_end;
+    }
+    if (fclose(fh) != 0) { remove(tmp.c_str()); return err(HICMI_EINVAL, std::string("write error on ") + tmp); }
+    if (rename(tmp.c_str(), path_out) != 0) { remove(tmp.c_str()); return err(HICMI_EINVAL, std::string("cannot rename ") + tmp + " to " + path_out); }
     stats4[0] = lines; stats4[1] = kept; stats4[2] = unknown; stats4[3] = out_of_range;
     return HICMI_OK;
 }

@@ -587,6 +587,51 @@ int hicmi_span_file(const char *path, const char *names_blob, const int64_t *nam
                     const int64_t *recs, int64_t n_rec, hicmi_ctx *ctx, int threads, int64_t *stats5, int64_t *picks_out,
                     uint64_t *counters5_out, uint64_t *depth_out, int64_t *cell_first_out, int64_t *n_cells_out);
 
+/* ---- scaffolds cut into pieces: every read end moved from its scaffold to its piece -------------------
+ * Scaffold s of the n_scaf scaffolds has the pieces piece_first[s] .. piece_first[s + 1] - 1 (int32, n_scaf + 1 entries,
+ * ascending from 0 to n_piece), left to right; piece k starts after piece_start[k] bases of its parent (int64, 0 for a
+ * first piece, strictly ascending inside a scaffold and below its size; a scaffold without a base has one piece).  The
+ * end (s, p), 1 <= p <= scaf_size[s], goes to the last piece k of s with piece_start[k] < p, at p - piece_start[k].
+ * The counters are 4 n_piece unsigned 64-bit integers, [within][sibling][other][mark] of n_piece each, and every call
+ * ADDS to them: a pair with both ends in piece k adds 1 to within[k]; a pair in two pieces of one scaffold adds 1 to
+ * sibling of both, 1 to mark of the lower and -1 (mod 2^64) to mark of the higher piece; a pair in pieces of two scaffolds
+ * adds 1 to other of both.  The prefix sum of mark over the pieces of a scaffold is, at piece k, the number of pairs with
+ * one end at or before the last base of k and one after it.  Every chunking and arrival order gives the same bits.
+ * HICMI_EINVAL for tables that are not so (the message names the scaffold), before anything else is looked at.
+ *
+ * hicmi_split_pairs works on host arrays: every index and position is checked on the host like hicmi_map_add_pairs
+ * (HICMI_EINVAL, nothing uploaded, no output written), then the chunk is moved on the device.  It touches no matrix
+ * state, no open map build and no open span build.  HICMI_SPLIT_PLAIN=1 in the environment, read at every call, takes
+ * the definition literally - a scan over the pieces of the scaffold and one global atomic add per counter and pair; =0
+ * and the default take an uncut scaffold as its one piece, bisect a cut one, and sum the contributions of a workgroup
+ * per counter in a table in LDS first.  Both give the same bits.
+ *
+ * hicmi_split_maps is hicmi_build_maps on the pieces: one pass over the file with the chunked parser, which reads the
+ * scaffolds' names and sizes; each chunk is uploaded once, moved once and counted into the map of every resolution, cut
+ * from the pieces (HICMI_BUILDMAP_CHUNK_PAIRS, HICMI_BUILDMAP_PLAIN, stats5 and the all-or-nothing installation as
+ * there).  n_res = 0 computes the counters alone; ctxs[0] must then still be a context, which lends its device and its
+ * stream and is left as it is.  Tables and resolutions are refused before the file is read; on any error no context and
+ * no counter changes.
+ *
+ * hicmi_split_valid_pairs (host code, no GPU) writes path_out: every line of path_in that hicmi_parse_valid_pairs keeps,
+ * with its columns 1, 2 and 4, 5 replaced by the name of the piece (piece_names_blob, piece_name_off as names_blob,
+ * name_off) and the position in the piece, every other byte - further columns, CR LF, a missing last newline - as it
+ * was; the lines the parser skips are dropped.  stats4 as hicmi_parse_valid_pairs fills it.  A malformed line is the
+ * parser's error with its byte offset.  The file is written under another name and renamed when it is whole, so an
+ * error leaves no output; the bytes do not depend on `threads`. */
+int hicmi_split_pairs(hicmi_ctx *ctx, const int32_t *scaf_a, const int64_t *pos_a, const int32_t *scaf_b,
+                      const int64_t *pos_b, int64_t n, const int64_t *scaf_size, int64_t n_scaf,
+                      const int32_t *piece_first, const int64_t *piece_start, int64_t n_piece, int32_t *piece_a_out,
+                      int64_t *pos_a_out, int32_t *piece_b_out, int64_t *pos_b_out, uint64_t *counters_out);
+int hicmi_split_maps(const char *path, const char *names_blob, const int64_t *name_off, int64_t n_names,
+                     const int64_t *scaf_size, const int32_t *piece_first, const int64_t *piece_start, int64_t n_piece,
+                     int64_t n_res, const int64_t *resolution, hicmi_ctx *const *ctxs, int threads, int64_t *stats5,
+                     uint64_t *counters_out);
+int hicmi_split_valid_pairs(const char *path_in, const char *path_out, const char *names_blob, const int64_t *name_off,
+                            int64_t n_names, const int64_t *scaf_size, const int32_t *piece_first,
+                            const int64_t *piece_start, int64_t n_piece, const char *piece_names_blob,
+                            const int64_t *piece_name_off, int threads, int64_t *stats4);
+
 /* ---- plot support -----------------------------------------------------------------------------
  * plotContactMap (plotContactMaps.py:15-91) colours every cell of an N x N matrix between two
  * numpy.percentile limits.  The matrix stays on the device: kind 0 = raw contacts (Part 2 plots,
