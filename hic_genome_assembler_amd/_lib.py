@@ -100,6 +100,11 @@ SIGNATURES = {
     "hicmi_span_finish": (ctypes.c_int, [_vp, c_i64, _vp, c_i64, _vp, _vp, _vp]),
     "hicmi_span_file": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, _vp, _vp, _vp, _vp, c_i64, c_i64, c_i64,
                                        c_i64, _vp, c_i64, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(c_i64)]),
+    "hicmi_ends_begin": (ctypes.c_int, [_vp, _vp, c_i64, _vp, _vp, _vp, _vp, c_i64, c_i64, c_i64, _vp, ctypes.POINTER(c_i64)]),
+    "hicmi_ends_add_pairs": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, c_i64]),
+    "hicmi_ends_finish": (ctypes.c_int, [_vp, _vp, _vp]),
+    "hicmi_ends_file": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, _vp, _vp, _vp, _vp, c_i64, c_i64, c_i64,
+                                       _vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.POINTER(c_i64)]),
     "hicmi_split_pairs": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, c_i64, _vp, c_i64, _vp, _vp, c_i64, _vp, _vp, _vp, _vp, _vp]),
     "hicmi_split_maps": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, _vp, _vp, c_i64, c_i64, _vp, _vp,
                                         ctypes.c_int, _vp, _vp]),
@@ -366,6 +371,40 @@ def span_file(path, names, sizes, lift_seq, lift_off, lift_rev, seq_sizes, step,
                                   int(threads), _ptr(stats), _ptr(picks), _ptr(counters), _ptr(depth), _ptr(cell_first),
                                   ctypes.byref(n_cells)))
     return tuple(int(v) for v in stats), cell_first, picks, counters, None if depth is None else depth[:n_cells.value]
+
+
+ENDS_MAX_TABLE = 1 << 27
+
+
+def ends_placed_count(sizes, lift_seq) -> int:
+    """Placed scaffolds of an ends build: those of a sequence and of size > 0."""
+    size = np.asarray(sizes, dtype=np.int64)
+    return int(((np.asarray(lift_seq) >= 0) & (size > 0)).sum())
+
+
+def _ends_table(n_placed, reach):
+    """A zeroed table uint64[P, reach, 4] for the library to fill; one counter where it will refuse the build."""
+    reach = int(reach)
+    ok = 1 <= reach <= 64 and 1 <= n_placed and n_placed * reach * 4 <= ENDS_MAX_TABLE
+    return np.zeros((n_placed, reach, 4) if ok else (1, 1, 4), np.uint64)
+
+
+def ends_file(path, names, sizes, lift_seq, lift_off, lift_rev, seq_sizes, window, reach, ctx, threads: int = 0):
+    """End support of an assembly over a HiC-Pro allValidPairs file in one pass (hicmi_ends_file) on the
+    device of ``ctx``, whose matrix, open map build and open span build stay as they are.  Returns ((lines, used,
+    unknown_scaffold, out_of_range, chunks), rank int32[S], table uint64[P, reach, 4], counters uint64[6] = (linked, middle,
+    same, too_far, trans, unlifted))."""
+    blob, off = _name_blob(names)
+    size, seq, loff, rev, seq_size = _lift_tables(sizes, lift_seq, lift_off, lift_rev, seq_sizes)
+    if size.shape != (len(names),):
+        raise ValueError("one size per scaffold name")
+    stats, counters = np.zeros(5, np.int64), np.zeros(6, np.uint64)
+    rank, n_placed = np.zeros(len(size), np.int32), c_i64()
+    table = _ends_table(ends_placed_count(size, seq), reach)
+    _check(load().hicmi_ends_file(os.fsencode(path), blob, _ptr(off), len(names), _ptr(size), _ptr(seq), _ptr(loff), _ptr(rev),
+                                  _ptr(seq_size), len(seq_size), int(window), int(reach), ctx._h, int(threads), _ptr(stats),
+                                  _ptr(table), _ptr(counters), _ptr(rank), ctypes.byref(n_placed)))
+    return tuple(int(v) for v in stats), rank, table, counters
 
 
 def _split_tables(sizes, piece_first, piece_start):
@@ -638,6 +677,34 @@ class Context:
         depth = np.zeros(max(getattr(self, "_span_cells", 0), 1), np.uint64) if want_depth else None
         _check(self._lib.hicmi_span_finish(self._h, int(flank), _ptr(rec), len(rec), _ptr(picks), _ptr(counters), _ptr(depth)))
         return picks, counters, None if depth is None else depth[:self._span_cells]
+
+    def ends_begin(self, sizes, lift_seq, lift_off, lift_rev, seq_sizes, window, reach):
+        """Open an end-support build (hicmi_ends_begin) over the assembly of the lift tables: end zones of
+        ``window`` bases, scaffolds up to ``reach`` ranks apart.  Returns rank int32[S]: the rank of every placed scaffold, -1
+        for a dropped or empty one.  The matrix, an open map build and an open span build are untouched."""
+        size, seq, off, rev, seq_size = _lift_tables(sizes, lift_seq, lift_off, lift_rev, seq_sizes)
+        rank, n_placed = np.zeros(len(size), np.int32), c_i64()
+        _check(self._lib.hicmi_ends_begin(self._h, _ptr(size), len(size), _ptr(seq), _ptr(off), _ptr(rev), _ptr(seq_size),
+                                          len(seq_size), int(window), int(reach), _ptr(rank), ctypes.byref(n_placed)))
+        self._ends_shape = (n_placed.value, int(reach), 4)
+        return rank
+
+    def ends_add_pairs(self, scaf_a, pos_a, scaf_b, pos_b):
+        """Count the pairs (scaffold index, 1-based position) x 2 in the open ends build (hicmi_ends_add_pairs)."""
+        sa, sb = np.ascontiguousarray(scaf_a, dtype=np.int32), np.ascontiguousarray(scaf_b, dtype=np.int32)
+        pa, pb = np.ascontiguousarray(pos_a, dtype=np.int64), np.ascontiguousarray(pos_b, dtype=np.int64)
+        if not (sa.ndim == 1 and sa.shape == sb.shape == pa.shape == pb.shape):
+            raise ValueError("the four arrays must be vectors of one length")
+        _check(self._lib.hicmi_ends_add_pairs(self._h, _ptr(sa), _ptr(pa), _ptr(sb), _ptr(pb), len(sa)))
+
+    def ends_finish(self):
+        """Close the ends build (hicmi_ends_finish): (table uint64[P, reach, 4], counters uint64[6] = (linked, middle, same,
+        too_far, trans, unlifted))."""
+        table = np.zeros(getattr(self, "_ends_shape", None) or (1, 1, 4), np.uint64)
+        counters = np.zeros(6, np.uint64)
+        _check(self._lib.hicmi_ends_finish(self._h, _ptr(table), _ptr(counters)))
+        self._ends_shape = None
+        return table, counters
 
     def split_pairs(self, scaf_a, pos_a, scaf_b, pos_b, sizes, piece_first, piece_start, into=None):
         """The pairs (scaffold index, 1-based position) x 2 moved to the pieces the scaffolds are cut into

@@ -215,6 +215,13 @@ struct hicmi_ctx {
     DevBuf<int64_t> d_span_first;
     std::vector<int64_t> span_size, span_seq_first;
     int64_t span_pairs = 0;
+    // end support (k_ends.hip), between hicmi_ends_begin and hicmi_ends_finish (ends_table non-null: a build
+    // is open): the table of ends_cells counters with the six kinds behind them, the lift tables and the ranks on the
+    // device, and the host's copy of the sizes a chunk of pairs is checked against
+    DevBuf<unsigned long long> ends_table; int64_t ends_cells = 0;
+    DevBuf<unsigned char> d_ends_lift; LiftTables ends_lift; EndsGrid ends_grid;
+    DevBuf<int32_t> d_ends_rank;
+    std::vector<int64_t> ends_size;
     // plot support
     DevBuf<int32_t> d_plot_order;
     DevBuf<unsigned char> d_plot_work;
@@ -1141,6 +1148,77 @@ int hicmi_split_maps(const char* path, const char* names_blob, const int64_t* na
                            &split, counters_out);
 }
 
+// HICMI_BUILDMAP_CHUNK_PAIRS, the pairs of one chunk of a pass over a pair file; read per call
+static int chunk_pairs_setting(int64_t* out)
+{
+    *out = (int64_t)1 << 22;
+    if (const char* env = getenv("HICMI_BUILDMAP_CHUNK_PAIRS")) {
+        const long long v = atoll(env);
+        if (v < 1 || v > ((long long)1 << 28)) return fail(HICMI_EINVAL, "HICMI_BUILDMAP_CHUNK_PAIRS = %s outside 1 .. 2^28", env);
+        *out = v;
+    }
+    return HICMI_OK;
+}
+
+// One pass over a pair file for one build of the context c: chunk t + 1 is parsed into the other pinned buffer while chunk
+// t is uploaded and handed to on_chunk(device arrays, n), which launches on the context's stream.  stats[0 .. 3] are the
+// parser's sums and stats[4] the chunks; `doing` names the work in the message of a HIP error.
+extern "C++" {
+template <typename OnChunk>
+static int pair_file_pass(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
+                          hicmi_ctx* c, int threads, int64_t chunk_pairs, int64_t* stats, const char* doing, OnChunk&& on_chunk)
+{
+    PinBuf<unsigned char> pin[2]; DevBuf<unsigned char> dev[2];
+    int64_t file_bytes = -1;
+    {
+        FILE* fh = fopen(path, "rb");
+        if (!fh) return fail(HICMI_EINVAL, "cannot open %s", path);
+        if (fseeko(fh, 0, SEEK_END) == 0) file_bytes = (int64_t)ftello(fh);
+        fclose(fh);
+        if (file_bytes < 0) return fail(HICMI_EINVAL, "cannot tell the size of %s", path);
+        chunk_pairs = std::max<int64_t>(1, std::min(chunk_pairs, file_bytes / 12 + 1));
+    }
+    const size_t chunk_bytes = (size_t)chunk_pairs * 24;
+    for (int b = 0; b < 2; b++) {
+        HIPCHK(pin[b].reserve((int64_t)chunk_bytes));
+        int rc = ensure(dev[b], (int64_t)chunk_bytes);
+        if (rc) return rc;
+    }
+    int64_t next = 0, n_here = 0, st[4];
+    auto parse = [&](int b) {
+        const MapChunk h = map_chunk_at(pin[b], chunk_pairs);
+        int prc = hicmi_parse_valid_pairs(path, names_blob, name_off, n_names, scaf_size, threads, next, chunk_pairs, h.scaf_a, h.pos_a,
+                                          h.scaf_b, h.pos_b, &n_here, &next, st);
+        if (!prc) { stats[0] += st[0]; stats[1] += st[1]; stats[2] += st[2]; stats[3] += st[3]; }
+        return prc;
+    };
+    int cur = 0;
+    int rc = parse(cur);
+    if (rc) return rc;
+    for (;;) {
+        const int64_t n = n_here;
+        if (n > 0) {
+            const MapChunk h = map_chunk_at(pin[cur], chunk_pairs), d = map_chunk_at(dev[cur], chunk_pairs);
+            HIPCHK(hipMemcpyAsync(d.pos_a, h.pos_a, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(d.pos_b, h.pos_b, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(d.scaf_a, h.scaf_a, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(d.scaf_b, h.scaf_b, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+            on_chunk(d, n);
+            HIPCHK(hipGetLastError());
+            stats[4]++;
+        }
+        const bool last = next >= file_bytes;                      // the parser has taken the whole file
+        if (!last) rc = parse(cur ^ 1);
+        hipError_t e = hipStreamSynchronize(c->stream);            // chunk t is done: its two buffers are free again
+        if (rc) return rc;
+        if (e != hipSuccess) return fail(HICMI_EHIP, "%s: %s", doing, hipGetErrorString(e));
+        if (last) break;
+        cur ^= 1;
+    }
+    return HICMI_OK;
+}
+}  // extern "C++"
+
 // ---- spanning depth: the read pairs with one end on each side of every cell boundary ---------------------
 // Between hicmi_span_begin and hicmi_span_finish the marks live in buffers of their own: the context's matrix state and
 // an open map build are never touched (the staging of a chunk, d_map_chunk, holds nothing between calls).
@@ -1326,12 +1404,9 @@ int hicmi_span_file(const char* path, const char* names_blob, const int64_t* nam
     SpanCells cells;
     int rc = span_number(scaf_size, n_names, lift, step, max_span, &cells);
     if (rc) return rc;
-    int64_t chunk_pairs = (int64_t)1 << 22;
-    if (const char* env = getenv("HICMI_BUILDMAP_CHUNK_PAIRS")) {
-        const long long v = atoll(env);
-        if (v < 1 || v > ((long long)1 << 28)) return fail(HICMI_EINVAL, "HICMI_BUILDMAP_CHUNK_PAIRS = %s outside 1 .. 2^28", env);
-        chunk_pairs = v;
-    }
+    int64_t chunk_pairs = 0;
+    rc = chunk_pairs_setting(&chunk_pairs);
+    if (rc) return rc;
     const std::vector<int64_t> cell_first = cells.cell_first;
     const int64_t m = cells.n_cells;
     rc = span_open(c, scaf_size, n_names, lift, step, max_span, std::move(cells));
@@ -1340,63 +1415,190 @@ int hicmi_span_file(const char* path, const char* names_blob, const int64_t* nam
     // the flank and the records are refused before the file is read
     rc = span_check_records(c, flank, recs, n_rec);
     if (rc) return rc;
-    PinBuf<unsigned char> pin[2]; DevBuf<unsigned char> dev[2];
-    int64_t file_bytes = -1;
-    {
-        FILE* fh = fopen(path, "rb");
-        if (!fh) return fail(HICMI_EINVAL, "cannot open %s", path);
-        if (fseeko(fh, 0, SEEK_END) == 0) file_bytes = (int64_t)ftello(fh);
-        fclose(fh);
-        if (file_bytes < 0) return fail(HICMI_EINVAL, "cannot tell the size of %s", path);
-        chunk_pairs = std::max<int64_t>(1, std::min(chunk_pairs, file_bytes / 12 + 1));
-    }
-    const size_t chunk_bytes = (size_t)chunk_pairs * 24;
-    for (int b = 0; b < 2; b++) {
-        HIPCHK(pin[b].reserve((int64_t)chunk_bytes));
-        rc = ensure(dev[b], (int64_t)chunk_bytes);
-        if (rc) return rc;
-    }
     const bool plain = spans_plain();
-    int64_t next = 0, n_here = 0, st[4], stats[5] = {0, 0, 0, 0, 0};
-    // chunk t + 1 is parsed into the other pinned buffer while chunk t is uploaded and marked on the context's stream
-    auto parse = [&](int b) {
-        const MapChunk h = map_chunk_at(pin[b], chunk_pairs);
-        int prc = hicmi_parse_valid_pairs(path, names_blob, name_off, n_names, scaf_size, threads, next, chunk_pairs, h.scaf_a, h.pos_a,
-                                          h.scaf_b, h.pos_b, &n_here, &next, st);
-        if (!prc) { stats[0] += st[0]; stats[1] += st[1]; stats[2] += st[2]; stats[3] += st[3]; }
-        return prc;
-    };
-    int cur = 0;
-    rc = parse(cur);
+    int64_t stats[5] = {0, 0, 0, 0, 0};
+    rc = pair_file_pass(path, names_blob, name_off, n_names, scaf_size, c, threads, chunk_pairs, stats, "marking a chunk of pairs",
+                        [&](const MapChunk& d, int64_t n) {
+                            launch_span_mark(d.scaf_a, d.pos_a, d.scaf_b, d.pos_b, n, c->span_lift, c->span_grid, c->span_marks,
+                                             c->span_marks + m, plain, c->stream);
+                            c->span_pairs += n;
+                        });
     if (rc) return rc;
-    for (;;) {
-        const int64_t n = n_here;
-        if (n > 0) {
-            const MapChunk h = map_chunk_at(pin[cur], chunk_pairs), d = map_chunk_at(dev[cur], chunk_pairs);
-            HIPCHK(hipMemcpyAsync(d.pos_a, h.pos_a, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(d.pos_b, h.pos_b, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(d.scaf_a, h.scaf_a, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(d.scaf_b, h.scaf_b, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-            launch_span_mark(d.scaf_a, d.pos_a, d.scaf_b, d.pos_b, n, c->span_lift, c->span_grid, c->span_marks, c->span_marks + m, plain,
-                             c->stream);
-            HIPCHK(hipGetLastError());
-            c->span_pairs += n;
-            stats[4]++;
-        }
-        const bool last = next >= file_bytes;                      // the parser has taken the whole file
-        if (!last) rc = parse(cur ^ 1);
-        hipError_t e = hipStreamSynchronize(c->stream);            // chunk t is marked: its two buffers are free again
-        if (rc) return rc;
-        if (e != hipSuccess) return fail(HICMI_EHIP, "marking a chunk of pairs: %s", hipGetErrorString(e));
-        if (last) break;
-        cur ^= 1;
-    }
     own.keep = true;                                               // span_close closes the build, whatever it returns
     rc = span_close(c, flank, recs, n_rec, picks_out, counters5_out, depth_out);
     if (rc) return rc;
     for (int k = 0; k < 5; k++) stats5[k] = stats[k];
     memcpy(cell_first_out, cell_first.data(), sizeof(int64_t) * (size_t)n_names);
     *n_cells_out = m;
+    return HICMI_OK;
+}
+
+// ---- end support: the read pairs that link the ends of neighbouring scaffolds -----------------------------
+// Between hicmi_ends_begin and hicmi_ends_finish the table lives in buffers of its own: the context's matrix state, an
+// open map build and an open span build are never touched (the staging of a chunk, d_map_chunk, holds nothing between calls).
+static void ends_abandon(hicmi_ctx* c)
+{
+    c->ends_table.reset(); c->d_ends_lift.reset(); c->d_ends_rank.reset();
+    c->ends_lift = LiftTables(); c->ends_grid = EndsGrid();
+    c->ends_size.clear();
+    c->ends_cells = 0;
+}
+
+// HICMI_ENDS_PLAIN: "1" one atomic add per linked pair, "0" the combining kernel, anything else the default; read per call
+constexpr bool kEndsPlainByDefault = false;
+static bool ends_plain()
+{
+    const char* env = getenv("HICMI_ENDS_PLAIN");
+    if (env && !strcmp(env, "1")) return true;
+    if (env && !strcmp(env, "0")) return false;
+    return kEndsPlainByDefault;
+}
+
+// the ranks of a build, made on the host before anything is allocated
+struct EndsRanks { std::vector<int32_t> rank; int64_t n_placed = 0; };
+
+static int ends_number(const int64_t* scaf_size, int64_t n_scaf, const LiftHost& lift, int64_t window, int64_t reach, EndsRanks* out)
+{
+    if (!scaf_size || n_scaf < 1 || n_scaf > INT_MAX / 2) return fail(HICMI_EINVAL, "bad arguments");
+    if (window < 1) return fail(HICMI_EINVAL, "window %lld is below 1", (long long)window);
+    if (reach < 1 || reach > ENDS_MAX_REACH)
+        return fail(HICMI_EINVAL, "reach %lld outside 1 .. %lld", (long long)reach, (long long)ENDS_MAX_REACH);
+    int rc = lift_check(scaf_size, n_scaf, lift);
+    if (rc) return rc;
+    out->rank.resize((size_t)n_scaf);
+    std::vector<int64_t> seq_first((size_t)lift.n_seq + 1);
+    out->n_placed = ends_number_ranks(scaf_size, n_scaf, lift.seq, lift.off, lift.n_seq, reach, out->rank.data(), seq_first.data());
+    if (out->n_placed < 0)
+        return fail(HICMI_EUNSUPPORTED, "reach %lld over the placed scaffolds needs a table of more than %lld counters", (long long)reach,
+                    (long long)ENDS_MAX_TABLE);
+    if (out->n_placed < 1) return fail(HICMI_EINVAL, "no scaffold with a base is placed: there are no ends");
+    return HICMI_OK;
+}
+
+static int ends_open(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, const LiftHost& lift, int64_t window, int64_t reach,
+                     const EndsRanks& ranks)
+{
+    HIPCHK(hipSetDevice(c->device));
+    ends_abandon(c);                                          // a begin without a finish is given up
+    const int64_t m = ranks.n_placed * reach * 4;
+    int rc = ensure_all(c->ends_table, m + ENDS_COUNTERS, c->d_ends_rank, n_scaf, c->d_ends_lift, 21 * n_scaf);
+    if (rc) return rc;
+    rc = upload(c, c->d_ends_rank, ranks.rank.data(), sizeof(int32_t) * (size_t)n_scaf);
+    if (!rc) rc = lift_upload(c, c->d_ends_lift, scaf_size, n_scaf, lift, &c->ends_lift);
+    hipError_t e = hipSuccess;
+    if (!rc && (e = hipMemsetAsync(c->ends_table, 0, sizeof(uint64_t) * (size_t)(m + ENDS_COUNTERS), c->stream)) != hipSuccess)
+        rc = fail(HICMI_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e));
+    if (!rc && (e = sync_stream(c)) != hipSuccess) rc = fail(HICMI_EHIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
+    if (rc) { ends_abandon(c); return rc; }
+    c->ends_grid.rank = c->d_ends_rank; c->ends_grid.window = window; c->ends_grid.reach = reach; c->ends_grid.n_placed = ranks.n_placed;
+    c->ends_size.assign(scaf_size, scaf_size + n_scaf);
+    c->ends_cells = m;
+    return HICMI_OK;
+}
+
+// the downloads of an open build, which it closes; the counters are written only when the table is down
+static int ends_close(hicmi_ctx* c, uint64_t* table_out, uint64_t* counters6_out)
+{
+    struct Close { hicmi_ctx* c; ~Close() { ends_abandon(c); } } closing{c};
+    const int64_t m = c->ends_cells;
+    uint64_t counters[ENDS_COUNTERS];
+    int rc = download(c, counters, c->ends_table + m, sizeof(counters));
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(table_out, c->ends_table, sizeof(uint64_t) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_stream(c));
+    memcpy(counters6_out, counters, sizeof(counters));
+    return HICMI_OK;
+}
+
+int hicmi_ends_begin(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, const int32_t* lift_seq, const int64_t* lift_off,
+                     const uint8_t* lift_rev, const int64_t* seq_size, int64_t n_seq, int64_t window, int64_t reach,
+                     int32_t* rank_out, int64_t* n_placed_out)
+{
+    if (!c || !rank_out || !n_placed_out) return fail(HICMI_EINVAL, "bad arguments");
+    const LiftHost lift{lift_seq, lift_off, lift_rev, seq_size, n_seq};
+    EndsRanks ranks;
+    int rc = ends_number(scaf_size, n_scaf, lift, window, reach, &ranks);
+    if (rc) return rc;
+    rc = ends_open(c, scaf_size, n_scaf, lift, window, reach, ranks);
+    if (rc) return rc;
+    memcpy(rank_out, ranks.rank.data(), sizeof(int32_t) * (size_t)n_scaf);
+    *n_placed_out = ranks.n_placed;
+    return HICMI_OK;
+}
+
+int hicmi_ends_add_pairs(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b,
+                         int64_t n)
+{
+    if (!c || n < 0 || (n > 0 && (!scaf_a || !pos_a || !scaf_b || !pos_b))) return fail(HICMI_EINVAL, "bad arguments");
+    if (!c->ends_table) return fail(HICMI_EINVAL, "hicmi_ends_add_pairs without hicmi_ends_begin");
+    int rc_pairs = check_pairs(scaf_a, pos_a, scaf_b, pos_b, n, c->ends_size.data(), (int64_t)c->ends_size.size(), nullptr, nullptr);
+    if (rc_pairs) return rc_pairs;
+    if (n == 0) return HICMI_OK;
+    HIPCHK(hipSetDevice(c->device));
+    // a HIP error from here on gives the build up: what was counted so far cannot be told
+    int rc = ensure(c->d_map_chunk, 24 * n);
+    const MapChunk k = map_chunk_at(c->d_map_chunk, n);
+    if (!rc) rc = upload(c, k.pos_a, pos_a, sizeof(int64_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.pos_b, pos_b, sizeof(int64_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.scaf_a, scaf_a, sizeof(int32_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.scaf_b, scaf_b, sizeof(int32_t) * (size_t)n);
+    if (!rc) {
+        launch_ends_count(k.scaf_a, k.pos_a, k.scaf_b, k.pos_b, n, c->ends_lift, c->ends_grid, c->ends_cells, c->ends_table,
+                          c->ends_table + c->ends_cells, ends_plain(), c->stream);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = sync_stream(c);
+        if (e != hipSuccess) rc = fail(HICMI_EHIP, "counting a chunk of pairs: %s", hipGetErrorString(e));
+    }
+    if (rc) { ends_abandon(c); return rc; }
+    return HICMI_OK;
+}
+
+int hicmi_ends_finish(hicmi_ctx* c, uint64_t* table_out, uint64_t* counters6_out)
+{
+    if (!c || !table_out || !counters6_out) return fail(HICMI_EINVAL, "bad arguments");
+    if (!c->ends_table) return fail(HICMI_EINVAL, "hicmi_ends_finish without hicmi_ends_begin");
+    HIPCHK(hipSetDevice(c->device));
+    return ends_close(c, table_out, counters6_out);
+}
+
+// The same over the pair file in one pass: the chunk loop of hicmi_span_file with the table of one build in place of the marks.
+int hicmi_ends_file(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
+                    const int32_t* lift_seq, const int64_t* lift_off, const uint8_t* lift_rev, const int64_t* seq_size, int64_t n_seq,
+                    int64_t window, int64_t reach, hicmi_ctx* c, int threads, int64_t* stats5, uint64_t* table_out,
+                    uint64_t* counters6_out, int32_t* rank_out, int64_t* n_placed_out)
+{
+    if (!path || !names_blob || !name_off || !scaf_size || !c || !stats5 || !table_out || !counters6_out || !rank_out || !n_placed_out ||
+        n_names < 1)
+        return fail(HICMI_EINVAL, "bad arguments");
+    const LiftHost lift{lift_seq, lift_off, lift_rev, seq_size, n_seq};
+    EndsRanks ranks;
+    int rc = ends_number(scaf_size, n_names, lift, window, reach, &ranks);
+    if (rc) return rc;
+    int64_t chunk_pairs = 0;
+    rc = chunk_pairs_setting(&chunk_pairs);
+    if (rc) return rc;
+    rc = ends_open(c, scaf_size, n_names, lift, window, reach, ranks);
+    if (rc) return rc;
+    struct OpenEnds { hicmi_ctx* c; bool keep = false; ~OpenEnds() { if (!keep) ends_abandon(c); } } own{c};   // given up on every error path
+    const bool plain = ends_plain();
+    int64_t stats[5] = {0, 0, 0, 0, 0};
+    rc = pair_file_pass(path, names_blob, name_off, n_names, scaf_size, c, threads, chunk_pairs, stats, "counting a chunk of pairs",
+                        [&](const MapChunk& d, int64_t n) {
+                            launch_ends_count(d.scaf_a, d.pos_a, d.scaf_b, d.pos_b, n, c->ends_lift, c->ends_grid, c->ends_cells,
+                                              c->ends_table, c->ends_table + c->ends_cells, plain, c->stream);
+                        });
+    if (rc) return rc;
+    // the table comes down into memory of the library's first: an error after it leaves every output as it was
+    std::vector<uint64_t> table((size_t)c->ends_cells);
+    uint64_t counters[ENDS_COUNTERS];
+    own.keep = true;                                               // ends_close closes the build, whatever it returns
+    rc = ends_close(c, table.data(), counters);
+    if (rc) return rc;
+    memcpy(table_out, table.data(), sizeof(uint64_t) * table.size());
+    memcpy(counters6_out, counters, sizeof(counters));
+    for (int k = 0; k < 5; k++) stats5[k] = stats[k];
+    memcpy(rank_out, ranks.rank.data(), sizeof(int32_t) * (size_t)n_names);
+    *n_placed_out = ranks.n_placed;
     return HICMI_OK;
 }
 

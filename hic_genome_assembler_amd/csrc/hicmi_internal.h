@@ -8,6 +8,7 @@
 
 #include "liftmap.h"
 #include "span.h"
+#include "ends.h"
 #include "split.h"
 
 namespace hicmi {
@@ -544,6 +545,17 @@ int64_t span_scan_tiles(int64_t n);
 void launch_span_scan(const void* in, void* out, int64_t n, void* tile_sums, hipStream_t s);
 void launch_span_pick(const void* depth, const void* depth_sums, int64_t n_cells, int64_t flank, const int64_t* recs, int64_t n_rec,
                       int64_t* picks, hipStream_t s);
+
+// k_ends.hip: read-pair links between the ends of ordered scaffolds (hicmi_ends_*).  table: n_table =
+// placed x reach x 4 unsigned 64-bit counters, +1 per linked pair; counters: the six kinds of pairs (EndsKind); everything is
+// device memory.
+static constexpr int ENDS_SLICE = 2048;        // pairs a workgroup of the combining k_ends_count brings together: one counter each
+static constexpr int ENDS_SLOT_BITS = 10;
+static constexpr int ENDS_SLOTS = 1 << ENDS_SLOT_BITS;   // slots of its table in LDS (8 bytes each); a slice can need twice as many
+static constexpr int ENDS_PROBES = 8;          // a pair that finds no room within so many probes is added directly
+void launch_ends_count(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
+                       const LiftTables& lift, const EndsGrid& grid, int64_t n_table, void* table, void* counters, bool plain,
+                       hipStream_t s);
 
 // k_split.hip: a chunk of pairs moved in place from scaffolds to the pieces they are cut into (hicmi_split_*),
 // each pair adding to counters[4 n_piece] = [within][sibling][other][mark] of its pieces; everything is device memory.

@@ -1,0 +1,259 @@
+"""End support: the read pairs that link the ends of neighbouring scaffolds of an ordering, on the device (DESIGN.md
+section 9p).
+
+Every orientation the other reports give is read from the binned contact map, which says nothing about a scaffold of one
+bin; supportSpans counts how many pairs bridge a junction, not which ends they join.  This one reads ``validPairFile``
+itself: every scaffold of the order file has a left and a right end zone of ``-window`` bp as it lies in its chromosome (a
+scaffold of up to two windows is cut in halves), and for every two scaffolds at most ``-reach`` places apart the read pairs
+between their zones are counted in the four combinations left-left, left-right, right-left and right-right.  A scaffold
+that lies the right way round is linked to its neighbours through the ends that face them; one that lies the wrong way
+round through the far ones.
+
+    python -m hic_genome_assembler_amd.supportEnds -config my_config.txt [-order FILE] [-window 50000] [-reach 2] [-minPairs 4] \\
+           [-out FILE] [-flipped FILE] [-full DIR] [-threads 0] [-device 0]
+
+Per scaffold ``as_lies`` is the number of links its ends have with the facing ends of its neighbours, ``flipped`` the number
+they would have if the scaffold alone were turned round; the verdict is ``supported``, ``flip``, ``open`` (a tie, or fewer
+than ``-minPairs`` links in all) or ``NA`` (alone in its chromosome).  Per junction the four combinations are listed and the
+verdict names the strict maximum: ``held``, ``flip_left``, ``flip_right``, ``flip_both`` or ``open``.  Every verdict is
+judged on the order file as it lies, not one after the other.  The scaffolds the order file does not name take no part:
+their pairs are counted as ``unlifted``.  There is no restriction-site normalisation; the two zones of a scaffold are
+equally long to within one base.  The defaults of ``-window``, ``-reach`` and ``-minPairs`` are choices, not tuned values.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+
+from . import _lib
+from .assembledMap import DEFAULT_GAP, build_assembly, read_order_file
+from .buildMap import STATS_COLUMNS, check_valid_pair_file
+from .hostio import paused_gc, read_scaffold_sizes
+
+DEFAULT_WINDOW, DEFAULT_REACH, DEFAULT_MIN_PAIRS = 50000, 2, 4
+MAX_REACH = 64
+MAX_TABLE = 1 << 27
+COUNTER_COLUMNS = ("linked", "middle", "same", "too_far", "trans", "unlifted")
+SCAFFOLD_COLUMNS = ("scaffold", "orientation", "size", "left_zone", "right_zone", "as_lies", "flipped", "verdict")
+JUNCTION_COLUMNS = ("chromosome", "left", "right", "facing", "left_flipped", "right_flipped", "both_flipped", "verdict")
+LINK_COLUMNS = ("scaffold", "d", "neighbour", "left_left", "left_right", "right_left", "right_right")
+JUNCTION_VERDICTS = ("held", "flip_left", "flip_right", "flip_both")
+LL, LR, RL, RR = 0, 1, 2, 3                    # zone at the lower rank x zone at the higher rank
+CHUNK_PAIRS = 1 << 22
+
+
+def number_ranks(asm, sizes):
+    """(rank int32[S], seq_first int64[n_seq + 1]) of DESIGN.md 9p from the components of the assembly: the placed scaffolds
+    of size > 0 in sequence order."""
+    rank = np.full(len(sizes), -1, np.int32)
+    seq_first = np.zeros(len(asm.components) + 1, np.int64)
+    n = 0
+    for q, comps in enumerate(asm.components):
+        for s, _off, _orientation in comps:
+            if sizes[s] > 0:
+                rank[s] = n
+                n += 1
+        seq_first[q + 1] = n
+    return rank, seq_first
+
+
+def zone_sizes(L, window):
+    """(left zone, right zone) of a scaffold of L bases as it lies, in bases."""
+    return min(window, L - L // 2), min(window, L // 2)
+
+
+def scaffold_figures(T, i, q0, q1):
+    """(as_lies, flipped) of the scaffold of rank i in the sequence with the ranks [q0, q1), from the table
+    T[rank, d - 1, zone x zone]."""
+    as_lies = flipped = 0
+    for d in range(1, T.shape[1] + 1):
+        if i + d < q1:
+            as_lies += int(T[i, d - 1, RL])
+            flipped += int(T[i, d - 1, LL])
+        if i - d >= q0:
+            as_lies += int(T[i - d, d - 1, RL])
+            flipped += int(T[i - d, d - 1, RR])
+    return as_lies, flipped
+
+
+def scaffold_verdict(as_lies, flipped, alone, minPairs):
+    if alone:
+        return "NA"
+    if as_lies == flipped or as_lies + flipped < minPairs:
+        return "open"
+    return "supported" if as_lies > flipped else "flip"
+
+
+def junction_figures(T, i):
+    """(facing, left_flipped, right_flipped, both_flipped) of the junction between the ranks i and i + 1."""
+    return [int(T[i, 0, k]) for k in (RL, LL, RR, LR)]
+
+
+def junction_verdict(figures, minPairs):
+    best = max(figures)
+    if sum(figures) < minPairs or figures.count(best) != 1:
+        return "open"
+    return JUNCTION_VERDICTS[figures.index(best)]
+
+
+def measure(ctx, pairFile, names, sizes, asm, window, reach, threads):
+    """(stats4, rank, table, counters) through the array calls of a context the caller owns: the file is parsed on the host
+    in chunks (hicmi_parse_valid_pairs) and counted chunk by chunk."""
+    rank = ctx.ends_begin(sizes, asm.lift_seq, asm.lift_off, asm.lift_rev, asm.seq_sizes, window, reach)
+    stats, at, size = [0, 0, 0, 0], 0, os.path.getsize(pairFile)
+    while True:
+        room = max(1, (size - at) // 12 + 1)                                   # a six-column line has 12 bytes or more
+        sa, pa, sb, pb, at, st = _lib.parse_valid_pairs(pairFile, names, sizes, first_byte=at, max_pairs=min(CHUNK_PAIRS, room),
+                                                        threads=threads)
+        stats = [a + b for a, b in zip(stats, st)]
+        ctx.ends_add_pairs(sa, pa, sb, pb)
+        if at >= size:
+            break
+    table, counters = ctx.ends_finish()
+    return tuple(stats), rank, table, counters
+
+
+def flipped_order_text(orderFile, flips):
+    """The order file again, every line verbatim except that the sign of each scaffold of ``flips`` is changed."""
+    out = []
+    with open(orderFile, newline="") as fh:
+        for k, line in enumerate(fh):
+            body = line.rstrip("\r\n")
+            if k and body and body[0] != "#":
+                cols = body.split("\t")
+                if cols[0] in flips:
+                    cols[1] = "+" if cols[1] == "-" else "-"
+                    line = "\t".join(cols) + line[len(body):]
+            out.append(line)
+    return "".join(out)
+
+
+def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT_REACH, minPairs=DEFAULT_MIN_PAIRS, outFile=None,
+                flippedFile=None, fullDir=None, threads=0, device=0, context=None):
+    """``context``: a context of the caller's - one that has ``ends_file`` answers in one call, any other is driven through
+    ends_begin / ends_add_pairs / ends_finish; None: a context of its own on ``device`` and one pass of hicmi_ends_file."""
+    from . import run_hicAssembler as driver
+    v = driver.readConfigFileToVariables(configFile)
+    if outFile is None:
+        outFile = os.path.join(v["saveFilesDirectory"], "endSupport.txt")
+    try:
+        if window < 1:
+            raise ValueError("the window %d is below 1" % window)
+        if not 1 <= reach <= MAX_REACH:
+            raise ValueError("the reach %d is outside 1 .. %d" % (reach, MAX_REACH))
+        if minPairs < 0:
+            raise ValueError("minPairs %d is negative" % minPairs)
+        check_valid_pair_file(v["validPairFile"])
+        names, sizes = read_scaffold_sizes(v["hicProScaffSizeFile"])
+        if not names:
+            raise ValueError("hicProScaffSizeFile %s lists no scaffold" % v["hicProScaffSizeFile"])
+        if orderFile is None:
+            orderFile = v["finalOrderingsFile"] if os.path.isfile(v["finalOrderingsFile"]) else v["chromosomeOrderFile"]
+        if not os.path.isfile(orderFile):
+            raise ValueError("order file %r does not exist" % orderFile)
+        asm = build_assembly(read_order_file(orderFile), names, sizes, DEFAULT_GAP, chromosomes_only=True)
+        n_placed = _lib.ends_placed_count(sizes, asm.lift_seq)
+        if n_placed * reach * 4 > MAX_TABLE:
+            raise ValueError("reach %d over %d placed scaffolds needs a table of %d counters, more than the %d a build can have"
+                             % (reach, n_placed, n_placed * reach * 4, MAX_TABLE))
+        if n_placed < 1:
+            raise ValueError("no scaffold of %s has a base" % orderFile)
+    except (OSError, ValueError) as exc:
+        sys.exit("ERROR... %s. Exiting..." % exc)
+    rank, seq_first = number_ranks(asm, sizes)
+    tables = (asm.lift_seq, asm.lift_off, asm.lift_rev, asm.seq_sizes)
+    with paused_gc():
+        try:
+            if context is None:
+                with _lib.Context(device) as ctx:
+                    stats, got_rank, T, counters = _lib.ends_file(v["validPairFile"], names, sizes, *tables, window, reach, ctx,
+                                                                  threads=threads)
+            elif hasattr(context, "ends_file"):
+                stats, got_rank, T, counters = context.ends_file(v["validPairFile"], names, sizes, *tables, window, reach, threads=threads)
+            else:
+                stats, got_rank, T, counters = measure(context, v["validPairFile"], names, sizes, asm, window, reach, threads)
+        except _lib.HicmiError as exc:
+            sys.exit("ERROR... %s. Exiting..." % exc)
+    if not np.array_equal(got_rank, rank) or T.shape != (n_placed, reach, 4):
+        sys.exit("ERROR... the library ranks the scaffolds differently from this report. Exiting...")
+    stats = tuple(stats[:4])
+    print("ENDS: lines %d, pairs used %d, unknown scaffold %d, out of range %d" % stats
+          + ", " + ", ".join("%s %d" % kv for kv in zip(COUNTER_COLUMNS, counters.tolist())))
+
+    header = ["window=%d" % window, "reach=%d" % reach, "minPairs=%d" % minPairs]
+    header += ["%s=%d" % kv for kv in zip(STATS_COLUMNS, stats)] + ["%s=%d" % kv for kv in zip(COUNTER_COLUMNS, counters.tolist())]
+    out = ["#" + "\t".join(header) + "\n", "#" + "\t".join(SCAFFOLD_COLUMNS) + "\n"]
+    flips, junctions, verdicts = set(), [], {}
+    for q, comps in enumerate(asm.components):
+        q0, q1 = int(seq_first[q]), int(seq_first[q + 1])
+        out.append("### Chromosome grouping %d ###\n" % (q + 1))
+        for s, _off, orientation in comps:
+            L = int(sizes[s])
+            if rank[s] < 0:                                                    # a scaffold without a base has no ends
+                cols = ["0", "0", "0", "0", "NA"]
+            else:
+                as_lies, flipped = scaffold_figures(T, int(rank[s]), q0, q1)
+                verdict = scaffold_verdict(as_lies, flipped, q1 - q0 == 1, minPairs)
+                cols = [str(x) for x in zone_sizes(L, window) + (as_lies, flipped)] + [verdict]
+            verdicts[names[s]] = cols[-1]
+            if cols[-1] == "flip":
+                flips.add(names[s])
+            out.append("\t".join([names[s], orientation, str(L)] + cols) + "\n")
+        filled = [s for s, _off, _o in comps if sizes[s] > 0]
+        for left, right in zip(filled, filled[1:]):
+            figures = junction_figures(T, int(rank[left]))
+            junctions.append("\t".join([str(q + 1), names[left], names[right]] + [str(x) for x in figures]
+                                       + [junction_verdict(figures, minPairs)]) + "\n")
+    out += ["### Junctions ###\n", "#" + "\t".join(JUNCTION_COLUMNS) + "\n"] + junctions
+    flipped_text = None if flippedFile is None else flipped_order_text(orderFile, flips)
+    os.makedirs(os.path.dirname(os.path.abspath(outFile)), exist_ok=True)
+    with open(outFile, "w") as fh:
+        fh.write("".join(out))
+    if flippedFile is not None:
+        with open(flippedFile, "w", newline="") as fh:
+            fh.write(flipped_text)
+    if fullDir is not None:
+        os.makedirs(fullDir, exist_ok=True)
+        with open(os.path.join(fullDir, "ends.links.tsv"), "w") as fh:
+            fh.write("#" + "\t".join(LINK_COLUMNS) + "\n")
+            for comps in asm.components:
+                filled = [s for s, _off, _o in comps if sizes[s] > 0]
+                for k, s in enumerate(filled):
+                    for d in range(1, min(reach, len(filled) - 1 - k) + 1):
+                        fh.write("%s\t%d\t%s\t%d\t%d\t%d\t%d\n" % ((names[s], d, names[filled[k + d]])
+                                                                    + tuple(int(x) for x in T[rank[s], d - 1])))
+    n_open = sum(x == "open" for x in verdicts.values())
+    print("ENDS: %d scaffold(s) to flip, %d open, %d of %d junction(s) not held" % (
+        len(flips), n_open, sum(not j.endswith("\theld\n") for j in junctions), len(junctions)))
+    return stats, T, counters, sorted(flips)
+
+
+def main(argv=None, context=None):
+    parser = argparse.ArgumentParser(description="Counts, on the GPU, the read pairs of validPairFile that link the end zones of "
+                                                 "neighbouring scaffolds of an ordering, and reports which scaffolds lie the wrong "
+                                                 "way round.")
+    parser.add_argument("-config", help="Full file path to the config file", required=True, type=str)
+    parser.add_argument("-order", help="Order file (default: finalOrderingsFile when it exists, else chromosomeOrderFile)",
+                        type=str, default=None)
+    parser.add_argument("-window", help="End zone in bp (default %d)" % DEFAULT_WINDOW, type=int, default=DEFAULT_WINDOW)
+    parser.add_argument("-reach", help="Places two scaffolds may lie apart, 1 .. %d (default %d)" % (MAX_REACH, DEFAULT_REACH), type=int,
+                        default=DEFAULT_REACH)
+    parser.add_argument("-minPairs", help="Links below which a verdict stays open (default %d)" % DEFAULT_MIN_PAIRS, type=int,
+                        default=DEFAULT_MIN_PAIRS)
+    parser.add_argument("-out", help="Report (default: saveFilesDirectory/endSupport.txt)", type=str, default=None)
+    parser.add_argument("-flipped", help="Write the order file again with the sign of every scaffold called flip changed", type=str,
+                        default=None)
+    parser.add_argument("-full", help="Write ends.links.tsv, the four counts of every entry inside a chromosome, into this directory",
+                        type=str, default=None)
+    parser.add_argument("-threads", help="Host threads of the parser (default 0: all)", type=int, default=0)
+    parser.add_argument("-device", help="GPU index (default 0)", type=int, default=0)
+    args = parser.parse_args(argv)
+    return runPipeline(args.config, args.order, args.window, args.reach, args.minPairs, args.out, args.flipped, args.full,
+                       threads=args.threads, device=args.device, context=context)
+
+
+if __name__ == "__main__":
+    main()

@@ -587,6 +587,43 @@ int hicmi_span_file(const char *path, const char *names_blob, const int64_t *nam
                     const int64_t *recs, int64_t n_rec, hicmi_ctx *ctx, int threads, int64_t *stats5, int64_t *picks_out,
                     uint64_t *counters5_out, uint64_t *depth_out, int64_t *cell_first_out, int64_t *n_cells_out);
 
+/* ---- end support: the read pairs that link the ends of neighbouring scaffolds ------------------------
+ * The assembly is given by the lift tables of 9m, checked in the same way.  The placed scaffolds of size > 0 are ranked
+ * 0 .. P - 1 in the order 9n numbers cells: sequences ascending, inside a sequence by offset, then by index; rank_out[s]
+ * is -1 for a dropped or empty scaffold, and gaps play no part.  A read end at position p of a scaffold of length L has
+ * the lying coordinate x = L - p on a reversed scaffold, else p - 1.  With wl = min(window, L - L / 2) and
+ * wr = min(window, L / 2) its zone is LEFT (0) when x < wl, RIGHT (1) when x >= L - wr, else MIDDLE.  A pair is, in this
+ * order: unlifted (an end on a dropped scaffold), trans (two sequences), same (one scaffold), too far (the ranks differ
+ * by d > reach), middle (either zone is MIDDLE), else linked.  table_out holds P x reach x 4 unsigned 64-bit counters: a
+ * linked pair whose lower-rank scaffold has the rank i and the zone za there, and the zone zb at its other end, adds 1 at
+ * ((i * reach + (d - 1)) * 4 + za * 2 + zb).  An entry whose i + d leaves the sequence of i stays 0.  counters6: linked,
+ * middle, same, too far, trans, unlifted pairs.  Every chunking and arrival order gives the same bits.
+ *
+ * hicmi_ends_begin checks the tables, returns the ranks and P and allocates a zeroed table; an ends build that was open
+ * is given up.  The context's matrix state, an open map build (9l, 9m) and an open span build (9n) are never touched by
+ * these calls.  HICMI_EINVAL: window < 1, reach outside 1 .. 64, tables refused, no placed scaffold; HICMI_EUNSUPPORTED:
+ * P x reach x 4 above 2^27; all before anything is allocated.
+ * hicmi_ends_add_pairs checks every index and position on the host like hicmi_map_add_pairs (HICMI_EINVAL, nothing
+ * uploaded, the build unchanged), uploads the arrays and counts them.  HICMI_ENDS_PLAIN=1 in the environment, read at
+ * every call, takes one global atomic add per linked pair; =0 and the default take the combining kernel, in which a
+ * workgroup sums the pairs of its slice per counter in a table in LDS first.  Both give the same bits.
+ * hicmi_ends_finish downloads the table and the counters and closes the build; HICMI_EINVAL without an open build.
+ *
+ * hicmi_ends_file: begin, every pair of the file, finish, in one pass with the chunked parser as in hicmi_span_file
+ * (HICMI_BUILDMAP_CHUNK_PAIRS, stats5 as there).  Tables, window and reach are refused before the file is read; on any
+ * error no output is written, and no ends build stays open. */
+int hicmi_ends_begin(hicmi_ctx *ctx, const int64_t *scaf_size, int64_t n_scaf, const int32_t *lift_seq,
+                     const int64_t *lift_off, const uint8_t *lift_rev, const int64_t *seq_size, int64_t n_seq,
+                     int64_t window, int64_t reach, int32_t *rank_out, int64_t *n_placed_out);
+int hicmi_ends_add_pairs(hicmi_ctx *ctx, const int32_t *scaf_a, const int64_t *pos_a,
+                         const int32_t *scaf_b, const int64_t *pos_b, int64_t n);
+int hicmi_ends_finish(hicmi_ctx *ctx, uint64_t *table_out, uint64_t *counters6_out);
+int hicmi_ends_file(const char *path, const char *names_blob, const int64_t *name_off, int64_t n_names,
+                    const int64_t *scaf_size, const int32_t *lift_seq, const int64_t *lift_off, const uint8_t *lift_rev,
+                    const int64_t *seq_size, int64_t n_seq, int64_t window, int64_t reach, hicmi_ctx *ctx, int threads,
+                    int64_t *stats5, uint64_t *table_out, uint64_t *counters6_out, int32_t *rank_out,
+                    int64_t *n_placed_out);
+
 /* ---- scaffolds cut into pieces: every read end moved from its scaffold to its piece -------------------
  * Scaffold s of the n_scaf scaffolds has the pieces piece_first[s] .. piece_first[s + 1] - 1 (int32, n_scaf + 1 entries,
  * ascending from 0 to n_piece), left to right; piece k starts after piece_start[k] bases of its parent (int64, 0 for a
