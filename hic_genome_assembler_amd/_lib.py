@@ -105,6 +105,11 @@ SIGNATURES = {
     "hicmi_ends_finish": (ctypes.c_int, [_vp, _vp, _vp]),
     "hicmi_ends_file": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, _vp, _vp, _vp, _vp, c_i64, c_i64, c_i64,
                                        _vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.POINTER(c_i64)]),
+    "hicmi_anchor_begin": (ctypes.c_int, [_vp, _vp, c_i64, _vp, _vp, _vp, _vp, c_i64, _vp, c_i64, _vp, ctypes.POINTER(c_i64)]),
+    "hicmi_anchor_add_pairs": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, c_i64]),
+    "hicmi_anchor_finish": (ctypes.c_int, [_vp, _vp, _vp]),
+    "hicmi_anchor_file": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, _vp, _vp, _vp, _vp, c_i64, _vp, c_i64,
+                                         _vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.POINTER(c_i64)]),
     "hicmi_split_pairs": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, c_i64, _vp, c_i64, _vp, _vp, c_i64, _vp, _vp, _vp, _vp, _vp]),
     "hicmi_split_maps": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, _vp, _vp, c_i64, c_i64, _vp, _vp,
                                         ctypes.c_int, _vp, _vp]),
@@ -407,6 +412,64 @@ def ends_file(path, names, sizes, lift_seq, lift_off, lift_rev, seq_sizes, windo
     return tuple(int(v) for v in stats), rank, table, counters
 
 
+ANCHOR_MAX_TABLE = 1 << 27
+
+
+def anchor_blocks(sizes, lift_seq, n_seq, target=None):
+    """(first int64[S], n_table) of an anchor build: the candidates - the dropped scaffolds of size > 0, in
+    rank mode those with ``target`` >= 0 - in index order, each with a block of ``n_seq`` counters or, in rank mode, of four
+    per placed scaffold of size > 0 of its target sequence; -1 for a scaffold that is no candidate.  n_table is -1 for
+    targets the library will refuse."""
+    size, seq = np.asarray(sizes, dtype=np.int64), np.asarray(lift_seq, dtype=np.int64)
+    candidate = (seq < 0) & (size > 0)
+    if target is None:
+        block = np.full(len(size), int(n_seq), np.int64)
+    else:
+        tgt = np.asarray(target, dtype=np.int64)
+        if tgt.shape != size.shape or ((tgt < -1) | (tgt >= int(n_seq))).any() or (~candidate & (tgt >= 0)).any():
+            return np.full(len(size), -1, np.int64), -1
+        placed = np.bincount(seq[(seq >= 0) & (seq < int(n_seq)) & (size > 0)], minlength=int(n_seq))
+        candidate = tgt >= 0
+        block = 4 * placed[np.where(candidate, tgt, 0)]
+    ends = np.cumsum(np.where(candidate, block, 0))
+    first = np.where(candidate, ends - block, -1).astype(np.int64)
+    return first, int(ends[-1]) if len(ends) else 0
+
+
+def _anchor_table(n_table):
+    """A zeroed table for the library to fill; one counter where it will refuse the build."""
+    return np.zeros(n_table if 1 <= n_table <= ANCHOR_MAX_TABLE else 1, np.uint64)
+
+
+def _anchor_target(target, n_scaf):
+    if target is None:
+        return None
+    tgt = np.ascontiguousarray(target, dtype=np.int32)
+    if tgt.shape != (n_scaf,):
+        raise ValueError("one target per scaffold size")
+    return tgt
+
+
+def anchor_file(path, names, sizes, lift_seq, lift_off, lift_rev, seq_sizes, target, window, ctx, threads: int = 0):
+    """Anchoring of the scaffolds an assembly leaves out over a HiC-Pro allValidPairs file in one pass (hicmi_anchor_file,
+    DESIGN.md 9q) on the device of ``ctx``, whose matrix, open map build, open span build and open ends build stay as they
+    are.  ``target`` None: sequence mode, else the target sequence of every scaffold (-1: none).  Returns ((lines, used,
+    unknown_scaffold, out_of_range, chunks), first int64[S], table uint64[n_table], counters uint64[6] = (anchored, middle,
+    elsewhere, skipped, unplaced, placed))."""
+    blob, off = _name_blob(names)
+    size, seq, loff, rev, seq_size = _lift_tables(sizes, lift_seq, lift_off, lift_rev, seq_sizes)
+    if size.shape != (len(names),):
+        raise ValueError("one size per scaffold name")
+    tgt = _anchor_target(target, len(size))
+    stats, counters = np.zeros(5, np.int64), np.zeros(6, np.uint64)
+    first, n_table = np.zeros(len(size), np.int64), c_i64()
+    table = _anchor_table(anchor_blocks(size, seq, len(seq_size), tgt)[1])
+    _check(load().hicmi_anchor_file(os.fsencode(path), blob, _ptr(off), len(names), _ptr(size), _ptr(seq), _ptr(loff), _ptr(rev),
+                                    _ptr(seq_size), len(seq_size), _ptr(tgt), int(window), ctx._h, int(threads), _ptr(stats),
+                                    _ptr(table), _ptr(counters), _ptr(first), ctypes.byref(n_table)))
+    return tuple(int(v) for v in stats), first, table, counters
+
+
 def _split_tables(sizes, piece_first, piece_start):
     """The piece tables of DESIGN.md 9o as the library takes them: (scaffold sizes, piece_first int32[S + 1], piece_start
     int64[n_piece])."""
@@ -704,6 +767,37 @@ class Context:
         counters = np.zeros(6, np.uint64)
         _check(self._lib.hicmi_ends_finish(self._h, _ptr(table), _ptr(counters)))
         self._ends_shape = None
+        return table, counters
+
+    def anchor_begin(self, sizes, lift_seq, lift_off, lift_rev, seq_sizes, target, window):
+        """Open an anchor build (hicmi_anchor_begin) over the assembly of the lift tables.  ``target`` None:
+        sequence mode, every dropped scaffold of size > 0 against every sequence; else rank mode, the scaffolds with a target
+        >= 0 against the end zones of ``window`` bases of the placed scaffolds of that sequence.  Returns first int64[S]: the
+        offset of every candidate's block of counters, -1 for a scaffold that is none.  The matrix, an open map build, an
+        open span build and an open ends build are untouched."""
+        size, seq, off, rev, seq_size = _lift_tables(sizes, lift_seq, lift_off, lift_rev, seq_sizes)
+        tgt = _anchor_target(target, len(size))
+        first, n_table = np.zeros(len(size), np.int64), c_i64()
+        _check(self._lib.hicmi_anchor_begin(self._h, _ptr(size), len(size), _ptr(seq), _ptr(off), _ptr(rev), _ptr(seq_size),
+                                            len(seq_size), _ptr(tgt), int(window), _ptr(first), ctypes.byref(n_table)))
+        self._anchor_cells = n_table.value
+        return first
+
+    def anchor_add_pairs(self, scaf_a, pos_a, scaf_b, pos_b):
+        """Count the pairs (scaffold index, 1-based position) x 2 in the open anchor build (hicmi_anchor_add_pairs)."""
+        sa, sb = np.ascontiguousarray(scaf_a, dtype=np.int32), np.ascontiguousarray(scaf_b, dtype=np.int32)
+        pa, pb = np.ascontiguousarray(pos_a, dtype=np.int64), np.ascontiguousarray(pos_b, dtype=np.int64)
+        if not (sa.ndim == 1 and sa.shape == sb.shape == pa.shape == pb.shape):
+            raise ValueError("the four arrays must be vectors of one length")
+        _check(self._lib.hicmi_anchor_add_pairs(self._h, _ptr(sa), _ptr(pa), _ptr(sb), _ptr(pb), len(sa)))
+
+    def anchor_finish(self):
+        """Close the anchor build (hicmi_anchor_finish): (table uint64[n_table], counters uint64[6] = (anchored, middle,
+        elsewhere, skipped, unplaced, placed))."""
+        table = np.zeros(getattr(self, "_anchor_cells", None) or 1, np.uint64)
+        counters = np.zeros(6, np.uint64)
+        _check(self._lib.hicmi_anchor_finish(self._h, _ptr(table), _ptr(counters)))
+        self._anchor_cells = None
         return table, counters
 
     def split_pairs(self, scaf_a, pos_a, scaf_b, pos_b, sizes, piece_first, piece_start, into=None):

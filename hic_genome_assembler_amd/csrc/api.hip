@@ -222,6 +222,15 @@ struct hicmi_ctx {
     DevBuf<unsigned char> d_ends_lift; LiftTables ends_lift; EndsGrid ends_grid;
     DevBuf<int32_t> d_ends_rank;
     std::vector<int64_t> ends_size;
+    // anchoring (k_anchor.hip), between hicmi_anchor_begin and hicmi_anchor_finish (anchor_table non-null: a
+    // build is open): the table of anchor_cells counters with the six kinds behind them, the lift tables and the blocks
+    // ([first n_scaf][seq_first n_seq + 1]; in rank mode target and rank, n_scaf each) on the device, and the host's copy
+    // of the sizes a chunk of pairs is checked against
+    DevBuf<unsigned long long> anchor_table; int64_t anchor_cells = 0;
+    DevBuf<unsigned char> d_anchor_lift; LiftTables anchor_lift; AnchorGrid anchor_grid;
+    DevBuf<int64_t> d_anchor_first;
+    DevBuf<int32_t> d_anchor_target;
+    std::vector<int64_t> anchor_size;
     // plot support
     DevBuf<int32_t> d_plot_order;
     DevBuf<unsigned char> d_plot_work;
@@ -1599,6 +1608,191 @@ int hicmi_ends_file(const char* path, const char* names_blob, const int64_t* nam
     for (int k = 0; k < 5; k++) stats5[k] = stats[k];
     memcpy(rank_out, ranks.rank.data(), sizeof(int32_t) * (size_t)n_names);
     *n_placed_out = ranks.n_placed;
+    return HICMI_OK;
+}
+
+// ---- anchoring: the read pairs that link the scaffolds an ordering leaves out to the placed ones -----------
+// Between hicmi_anchor_begin and hicmi_anchor_finish the table lives in buffers of its own: the context's matrix state, an
+// open map build, an open span build and an open ends build are never touched (the staging of a chunk, d_map_chunk, holds
+// nothing between calls).
+static void anchor_abandon(hicmi_ctx* c)
+{
+    c->anchor_table.reset(); c->d_anchor_lift.reset(); c->d_anchor_first.reset(); c->d_anchor_target.reset();
+    c->anchor_lift = LiftTables(); c->anchor_grid = AnchorGrid();
+    c->anchor_size.clear();
+    c->anchor_cells = 0;
+}
+
+// HICMI_ANCHOR_PLAIN: "1" one atomic add per anchored pair, "0" the combining kernel, anything else the default; read per call
+constexpr bool kAnchorPlainByDefault = false;
+static bool anchor_plain()
+{
+    const char* env = getenv("HICMI_ANCHOR_PLAIN");
+    if (env && !strcmp(env, "1")) return true;
+    if (env && !strcmp(env, "0")) return false;
+    return kAnchorPlainByDefault;
+}
+
+// the blocks of a build, made on the host before anything is allocated
+struct AnchorBlocks { std::vector<int64_t> first, seq_first; std::vector<int32_t> rank; int64_t n_table = 0; };
+
+static int anchor_number(const int64_t* scaf_size, int64_t n_scaf, const LiftHost& lift, const int32_t* target, int64_t window,
+                         AnchorBlocks* out)
+{
+    if (!scaf_size || n_scaf < 1 || n_scaf > INT_MAX / 2) return fail(HICMI_EINVAL, "bad arguments");
+    if (window < 1) return fail(HICMI_EINVAL, "window %lld is below 1", (long long)window);
+    int rc = lift_check(scaf_size, n_scaf, lift);
+    if (rc) return rc;
+    out->first.resize((size_t)n_scaf);
+    out->seq_first.assign((size_t)lift.n_seq + 1, 0);
+    if (target) {
+        out->rank.resize((size_t)n_scaf);
+        if (ends_number_ranks(scaf_size, n_scaf, lift.seq, lift.off, lift.n_seq, 1, out->rank.data(), out->seq_first.data()) < 0)
+            return fail(HICMI_EUNSUPPORTED, "more than %lld placed scaffolds", (long long)(ENDS_MAX_TABLE / 4));
+        char msg[256];
+        if (anchor_check_targets(scaf_size, n_scaf, lift.seq, lift.n_seq, target, out->seq_first.data(), msg, sizeof(msg)))
+            return fail(HICMI_EINVAL, "%s", msg);
+    }
+    out->n_table = anchor_number_blocks(scaf_size, n_scaf, lift.seq, lift.n_seq, target, out->seq_first.data(), out->first.data());
+    if (out->n_table < 0)
+        return fail(HICMI_EUNSUPPORTED, "the candidates need a table of more than %lld counters", (long long)ANCHOR_MAX_TABLE);
+    if (out->n_table < 1)
+        return fail(HICMI_EINVAL, target ? "no scaffold has a target: there is no candidate"
+                                         : "every scaffold with a base is placed: there is no candidate");
+    return HICMI_OK;
+}
+
+static int anchor_open(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, const LiftHost& lift, const int32_t* target,
+                       int64_t window, const AnchorBlocks& blocks)
+{
+    HIPCHK(hipSetDevice(c->device));
+    anchor_abandon(c);                                        // a begin without a finish is given up
+    const int64_t m = blocks.n_table, n_first = n_scaf + lift.n_seq + 1;
+    int rc = ensure_all(c->anchor_table, m + ANCHOR_COUNTERS, c->d_anchor_first, n_first, c->d_anchor_target, target ? 2 * n_scaf : 1,
+                        c->d_anchor_lift, 21 * n_scaf);
+    if (rc) return rc;
+    rc = upload(c, c->d_anchor_first, blocks.first.data(), sizeof(int64_t) * (size_t)n_scaf);
+    if (!rc) rc = upload(c, c->d_anchor_first + n_scaf, blocks.seq_first.data(), sizeof(int64_t) * (size_t)(lift.n_seq + 1));
+    if (!rc && target) rc = upload(c, c->d_anchor_target, target, sizeof(int32_t) * (size_t)n_scaf);
+    if (!rc && target) rc = upload(c, c->d_anchor_target + n_scaf, blocks.rank.data(), sizeof(int32_t) * (size_t)n_scaf);
+    if (!rc) rc = lift_upload(c, c->d_anchor_lift, scaf_size, n_scaf, lift, &c->anchor_lift);
+    hipError_t e = hipSuccess;
+    if (!rc && (e = hipMemsetAsync(c->anchor_table, 0, sizeof(uint64_t) * (size_t)(m + ANCHOR_COUNTERS), c->stream)) != hipSuccess)
+        rc = fail(HICMI_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e));
+    if (!rc && (e = sync_stream(c)) != hipSuccess) rc = fail(HICMI_EHIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
+    if (rc) { anchor_abandon(c); return rc; }
+    c->anchor_grid.first = c->d_anchor_first; c->anchor_grid.seq_first = c->d_anchor_first + n_scaf;
+    c->anchor_grid.target = target ? (const int32_t*)c->d_anchor_target : nullptr;
+    c->anchor_grid.rank = target ? c->d_anchor_target + n_scaf : nullptr;
+    c->anchor_grid.window = window;
+    c->anchor_size.assign(scaf_size, scaf_size + n_scaf);
+    c->anchor_cells = m;
+    return HICMI_OK;
+}
+
+// the downloads of an open build, which it closes; the counters are written only when the table is down
+static int anchor_close(hicmi_ctx* c, uint64_t* table_out, uint64_t* counters6_out)
+{
+    struct Close { hicmi_ctx* c; ~Close() { anchor_abandon(c); } } closing{c};
+    const int64_t m = c->anchor_cells;
+    uint64_t counters[ANCHOR_COUNTERS];
+    int rc = download(c, counters, c->anchor_table + m, sizeof(counters));
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(table_out, c->anchor_table, sizeof(uint64_t) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_stream(c));
+    memcpy(counters6_out, counters, sizeof(counters));
+    return HICMI_OK;
+}
+
+int hicmi_anchor_begin(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, const int32_t* lift_seq, const int64_t* lift_off,
+                       const uint8_t* lift_rev, const int64_t* seq_size, int64_t n_seq, const int32_t* target, int64_t window,
+                       int64_t* first_out, int64_t* n_table_out)
+{
+    if (!c || !first_out || !n_table_out) return fail(HICMI_EINVAL, "bad arguments");
+    const LiftHost lift{lift_seq, lift_off, lift_rev, seq_size, n_seq};
+    AnchorBlocks blocks;
+    int rc = anchor_number(scaf_size, n_scaf, lift, target, window, &blocks);
+    if (rc) return rc;
+    rc = anchor_open(c, scaf_size, n_scaf, lift, target, window, blocks);
+    if (rc) return rc;
+    memcpy(first_out, blocks.first.data(), sizeof(int64_t) * (size_t)n_scaf);
+    *n_table_out = blocks.n_table;
+    return HICMI_OK;
+}
+
+int hicmi_anchor_add_pairs(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b,
+                           int64_t n)
+{
+    if (!c || n < 0 || (n > 0 && (!scaf_a || !pos_a || !scaf_b || !pos_b))) return fail(HICMI_EINVAL, "bad arguments");
+    if (!c->anchor_table) return fail(HICMI_EINVAL, "hicmi_anchor_add_pairs without hicmi_anchor_begin");
+    int rc_pairs = check_pairs(scaf_a, pos_a, scaf_b, pos_b, n, c->anchor_size.data(), (int64_t)c->anchor_size.size(), nullptr, nullptr);
+    if (rc_pairs) return rc_pairs;
+    if (n == 0) return HICMI_OK;
+    HIPCHK(hipSetDevice(c->device));
+    // a HIP error from here on gives the build up: what was counted so far cannot be told
+    int rc = ensure(c->d_map_chunk, 24 * n);
+    const MapChunk k = map_chunk_at(c->d_map_chunk, n);
+    if (!rc) rc = upload(c, k.pos_a, pos_a, sizeof(int64_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.pos_b, pos_b, sizeof(int64_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.scaf_a, scaf_a, sizeof(int32_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.scaf_b, scaf_b, sizeof(int32_t) * (size_t)n);
+    if (!rc) {
+        launch_anchor_count(k.scaf_a, k.pos_a, k.scaf_b, k.pos_b, n, c->anchor_lift, c->anchor_grid, c->anchor_cells, c->anchor_table,
+                            c->anchor_table + c->anchor_cells, anchor_plain(), c->stream);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = sync_stream(c);
+        if (e != hipSuccess) rc = fail(HICMI_EHIP, "counting a chunk of pairs: %s", hipGetErrorString(e));
+    }
+    if (rc) { anchor_abandon(c); return rc; }
+    return HICMI_OK;
+}
+
+int hicmi_anchor_finish(hicmi_ctx* c, uint64_t* table_out, uint64_t* counters6_out)
+{
+    if (!c || !table_out || !counters6_out) return fail(HICMI_EINVAL, "bad arguments");
+    if (!c->anchor_table) return fail(HICMI_EINVAL, "hicmi_anchor_finish without hicmi_anchor_begin");
+    HIPCHK(hipSetDevice(c->device));
+    return anchor_close(c, table_out, counters6_out);
+}
+
+// The same over the pair file in one pass: the chunk loop of hicmi_span_file and hicmi_ends_file with the table of one build.
+int hicmi_anchor_file(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
+                      const int32_t* lift_seq, const int64_t* lift_off, const uint8_t* lift_rev, const int64_t* seq_size, int64_t n_seq,
+                      const int32_t* target, int64_t window, hicmi_ctx* c, int threads, int64_t* stats5, uint64_t* table_out,
+                      uint64_t* counters6_out, int64_t* first_out, int64_t* n_table_out)
+{
+    if (!path || !names_blob || !name_off || !scaf_size || !c || !stats5 || !table_out || !counters6_out || !first_out || !n_table_out ||
+        n_names < 1)
+        return fail(HICMI_EINVAL, "bad arguments");
+    const LiftHost lift{lift_seq, lift_off, lift_rev, seq_size, n_seq};
+    AnchorBlocks blocks;
+    int rc = anchor_number(scaf_size, n_names, lift, target, window, &blocks);
+    if (rc) return rc;
+    int64_t chunk_pairs = 0;
+    rc = chunk_pairs_setting(&chunk_pairs);
+    if (rc) return rc;
+    rc = anchor_open(c, scaf_size, n_names, lift, target, window, blocks);
+    if (rc) return rc;
+    struct OpenAnchor { hicmi_ctx* c; bool keep = false; ~OpenAnchor() { if (!keep) anchor_abandon(c); } } own{c};   // given up on every error path
+    const bool plain = anchor_plain();
+    int64_t stats[5] = {0, 0, 0, 0, 0};
+    rc = pair_file_pass(path, names_blob, name_off, n_names, scaf_size, c, threads, chunk_pairs, stats, "counting a chunk of pairs",
+                        [&](const MapChunk& d, int64_t n) {
+                            launch_anchor_count(d.scaf_a, d.pos_a, d.scaf_b, d.pos_b, n, c->anchor_lift, c->anchor_grid, c->anchor_cells,
+                                                c->anchor_table, c->anchor_table + c->anchor_cells, plain, c->stream);
+                        });
+    if (rc) return rc;
+    // the table comes down into memory of the library's first: an error after it leaves every output as it was
+    std::vector<uint64_t> table((size_t)c->anchor_cells);
+    uint64_t counters[ANCHOR_COUNTERS];
+    own.keep = true;                                               // anchor_close closes the build, whatever it returns
+    rc = anchor_close(c, table.data(), counters);
+    if (rc) return rc;
+    memcpy(table_out, table.data(), sizeof(uint64_t) * table.size());
+    memcpy(counters6_out, counters, sizeof(counters));
+    for (int k = 0; k < 5; k++) stats5[k] = stats[k];
+    memcpy(first_out, blocks.first.data(), sizeof(int64_t) * (size_t)n_names);
+    *n_table_out = blocks.n_table;
     return HICMI_OK;
 }
 

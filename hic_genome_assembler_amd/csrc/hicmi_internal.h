@@ -9,6 +9,7 @@
 #include "liftmap.h"
 #include "span.h"
 #include "ends.h"
+#include "anchor.h"
 #include "split.h"
 
 namespace hicmi {
@@ -556,6 +557,17 @@ static constexpr int ENDS_PROBES = 8;          // a pair that finds no room with
 void launch_ends_count(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
                        const LiftTables& lift, const EndsGrid& grid, int64_t n_table, void* table, void* counters, bool plain,
                        hipStream_t s);
+
+// k_anchor.hip: read-pair links between the scaffolds an ordering leaves out and the placed ones (hicmi_anchor_*; DESIGN.md
+// 9q).  table: n_table unsigned 64-bit counters, the blocks of the candidates (anchor.h), +1 per anchored pair; counters:
+// the six kinds of pairs (AnchorKind); everything is device memory.
+static constexpr int ANCHOR_SLICE = 2048;      // pairs a workgroup of the combining k_anchor_count brings together: one counter each
+static constexpr int ANCHOR_SLOT_BITS = 10;
+static constexpr int ANCHOR_SLOTS = 1 << ANCHOR_SLOT_BITS;   // slots of its table in LDS (8 bytes each); a slice can need twice as many
+static constexpr int ANCHOR_PROBES = 8;        // a pair that finds no room within so many probes is added directly
+void launch_anchor_count(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
+                         const LiftTables& lift, const AnchorGrid& grid, int64_t n_table, void* table, void* counters, bool plain,
+                         hipStream_t s);
 
 // k_split.hip: a chunk of pairs moved in place from scaffolds to the pieces they are cut into (hicmi_split_*),
 // each pair adding to counters[4 n_piece] = [within][sibling][other][mark] of its pieces; everything is device memory.

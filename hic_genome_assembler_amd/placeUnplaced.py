@@ -1,0 +1,358 @@
+"""Placing the scaffolds an ordering leaves out, from their read-pair links, on the device.
+
+Every other tool improves or questions the scaffolds an order file already names.  The ones it does not name - dropped by
+Part 1, masked by Part 0, too small for a bin - end as loose sequences.  This one reads ``validPairFile`` itself, twice on
+one context.  Pass 1 counts, for every unplaced scaffold, the read pairs it shares with every chromosome, and gives it to
+the chromosome it is linked to most densely (links per placed base), when that one stands out.  Pass 2 counts the pairs of
+each assigned scaffold against the end zones of ``-window`` bp of the scaffolds of its chromosome, separately for its own
+two halves, and scores every gap of the chromosome in both orientations from the zones that face the gap, up to
+``-reach`` scaffolds away.
+
+    python -m hic_genome_assembler_amd.placeUnplaced -config my_config.txt [-order FILE] [-window 50000] [-reach 2] [-minPairs 4] \\
+           [-minRatio 2] [-minSize 0] [-out FILE] [-placed FILE] [-full DIR] [-threads 0] [-device 0]
+
+Verdicts: ``too_small`` (below ``-minSize``), ``no_links``, ``ambiguous`` (fewer than ``-minPairs`` links with the densest
+chromosome, a tie with the second densest, or a density ratio below ``-minRatio``), ``chromosome_only`` (a chromosome, but
+the best gap score is below ``-minPairs`` or shared by two gaps), ``placed``, ``orientation_open`` (placed as ``+``: both
+orientations of the gap score the same) and ``deferred`` (another scaffold with a higher score, or the same score and an
+earlier line in the size file, chose the same gap).  ``-placed`` writes the order file again with one scaffold inserted per
+gap: run the tool again on that file to place the deferred ones.  A gap at the start or the end of a chromosome has
+neighbours on one side only, and its score is not scaled up for it.  There is no restriction-site normalisation.  The
+defaults are choices, not tuned values.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+
+from . import _lib
+from .assembledMap import DEFAULT_GAP, build_assembly, read_order_file
+from .buildMap import STATS_COLUMNS, check_valid_pair_file
+from .hostio import paused_gc, read_scaffold_sizes
+
+DEFAULT_WINDOW, DEFAULT_REACH, DEFAULT_MIN_PAIRS, DEFAULT_MIN_RATIO, DEFAULT_MIN_SIZE = 50000, 2, 4, 2.0, 0
+MAX_REACH = 64
+MAX_TABLE = 1 << 27
+COUNTER_COLUMNS = ("anchored", "middle", "elsewhere", "skipped", "unplaced", "placed")
+UNPLACED_COLUMNS = ("scaffold", "size", "links", "chromosome", "chrom_links", "second", "second_links", "ratio", "left", "right",
+                    "orientation", "score", "runner_up", "verdict")
+CHROMOSOME_COLUMNS = ("chromosome", "scaffolds", "bases", "assigned", "inserted")
+LEFT, RIGHT = 0, 1                               # end zones of a placed scaffold as it lies
+CHUNK_PAIRS = 1 << 22
+
+
+def number_blocks(asm, sizes, target=None):
+    """(first int64[S], n_table) of DESIGN.md 9q from the components of the assembly: the candidates in size-file order,
+    a block of one counter per sequence each, or with ``target`` of four per scaffold with a base of the target."""
+    filled = [sum(1 for s, _off, _o in comps if sizes[s] > 0) for comps in asm.components]
+    first = np.full(len(sizes), -1, np.int64)
+    n = 0
+    for s in range(len(sizes)):
+        if asm.lift_seq[s] < 0 and sizes[s] > 0 and (target is None or target[s] >= 0):
+            first[s] = n
+            n += len(asm.components) if target is None else 4 * filled[target[s]]
+    return first, n
+
+
+def densest(a, B):
+    """(best, second) of the sequences by links per base, a[q] / B[q], compared by cross-multiplication; a tie goes to the
+    lowest q, and second is None with one sequence."""
+    def first_max(skip):
+        top = None
+        for q in range(len(a)):
+            if q != skip and (top is None or a[q] * B[top] > a[top] * B[q]):
+                top = q
+        return top
+    best = first_max(None)
+    return best, first_max(best)
+
+
+def choose_chromosome(a, B, size, minPairs, minRatio, minSize):
+    """(best, second, ratio, verdict) of a candidate with the links a[q]; the verdict is None when it gets ``best`` as its
+    target.  ratio: a float, inf when the second densest sequence has no link, None with one sequence."""
+    best, second = densest(a, B)
+    ratio = None
+    if second is not None:
+        ratio = float("inf") if a[second] == 0 else (a[best] * B[second]) / (a[second] * B[best]) if a[best] else 0.0
+    if size < minSize:
+        return best, second, ratio, "too_small"
+    if sum(a) == 0:
+        return best, second, ratio, "no_links"
+    if a[best] < minPairs:
+        return best, second, ratio, "ambiguous"
+    if second is not None and (a[best] * B[second] == a[second] * B[best] or ratio < minRatio):
+        return best, second, ratio, "ambiguous"
+    return best, second, ratio, None
+
+
+def gap_scores(T, reach):
+    """scores[g][o] of the gaps g = 0 .. S of a chromosome of S scaffolds and the orientations o = 0 (+) and 1 (-), from the
+    candidate's counters T[k, half, zone]."""
+    S = T.shape[0]
+    scores = []
+    for g in range(S + 1):
+        both = []
+        for o in (0, 1):
+            near, far = (0, 1) if o == 0 else (1, 0)               # the half that lies left, the half that lies right
+            x = sum(int(T[g - d, near, RIGHT]) for d in range(1, reach + 1) if g - d >= 0)
+            x += sum(int(T[g + d - 1, far, LEFT]) for d in range(1, reach + 1) if g + d - 1 < S)
+            both.append(x)
+        scores.append(both)
+    return scores
+
+
+def choose_gap(scores, minPairs):
+    """(gap, orientation, score, runner_up, verdict): the first maximum in the order gap 0 +, gap 0 -, gap 1 +, ..., the best
+    score anywhere else, and ``chromosome_only``, ``placed`` or ``orientation_open``."""
+    flat = [(x, g, o) for g, both in enumerate(scores) for o, x in enumerate(both)]
+    m = max(x for x, _g, _o in flat)
+    at = [(g, o) for x, g, o in flat if x == m]
+    g, o = at[0]
+    runner_up = max(x for x, gg, oo in flat if (gg, oo) != (g, o))
+    if m < minPairs or any(gg != g for gg, _o in at):
+        return g, o, m, runner_up, "chromosome_only"
+    return g, o, m, runner_up, "placed" if len(at) == 1 else "orientation_open"
+
+
+def measure(ctx, pairFile, names, sizes, asm, target, window, threads):
+    """(stats4, first, table, counters) through the array calls of a context the caller owns: the file is parsed on the host
+    in chunks (hicmi_parse_valid_pairs) and counted chunk by chunk."""
+    first = ctx.anchor_begin(sizes, asm.lift_seq, asm.lift_off, asm.lift_rev, asm.seq_sizes, target, window)
+    stats, at, size = [0, 0, 0, 0], 0, os.path.getsize(pairFile)
+    while True:
+        room = max(1, (size - at) // 12 + 1)                                   # a six-column line has 12 bytes or more
+        sa, pa, sb, pb, at, st = _lib.parse_valid_pairs(pairFile, names, sizes, first_byte=at, max_pairs=min(CHUNK_PAIRS, room),
+                                                        threads=threads)
+        stats = [a + b for a, b in zip(stats, st)]
+        ctx.anchor_add_pairs(sa, pa, sb, pb)
+        if at >= size:
+            break
+    table, counters = ctx.anchor_finish()
+    return tuple(stats), first, table, counters
+
+
+def placed_order_text(orderFile, insertions):
+    """The order file again, every line verbatim, with a line ``name<TAB>orientation`` per entry of ``insertions``:
+    {scaffold the line goes before: (name, orientation)} and {(scaffold the line goes after, None): (name, orientation)}.
+    The new line takes the line ending of the line it is placed next to."""
+    out = []
+    with open(orderFile, newline="") as fh:
+        for k, line in enumerate(fh):
+            body = line.rstrip("\r\n")
+            ending = line[len(body):]
+            name = body.split("\t")[0] if k and body and body[0] != "#" else None
+            if name is not None and name in insertions:
+                out.append("%s\t%s" % insertions[name] + (ending or "\n"))
+            out.append(line)
+            if name is not None and (name, None) in insertions:
+                if not ending:
+                    out[-1] = body + "\n"
+                out.append("%s\t%s" % insertions[(name, None)] + ending)
+    return "".join(out)
+
+
+def _ratio_text(ratio):
+    return "NA" if ratio is None else "inf" if ratio == float("inf") else "%.6g" % ratio
+
+
+def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT_REACH, minPairs=DEFAULT_MIN_PAIRS,
+                minRatio=DEFAULT_MIN_RATIO, minSize=DEFAULT_MIN_SIZE, outFile=None, placedFile=None, fullDir=None, threads=0, device=0,
+                context=None):
+    """``context``: a context of the caller's - one that has ``anchor_file`` answers each pass in one call, any other is driven
+    through anchor_begin / anchor_add_pairs / anchor_finish; None: a context of its own on ``device`` and two passes of
+    hicmi_anchor_file."""
+    from . import run_hicAssembler as driver
+    v = driver.readConfigFileToVariables(configFile)
+    if outFile is None:
+        outFile = os.path.join(v["saveFilesDirectory"], "unplacedSupport.txt")
+    try:
+        if window < 1:
+            raise ValueError("the window %d is below 1" % window)
+        if not 1 <= reach <= MAX_REACH:
+            raise ValueError("the reach %d is outside 1 .. %d" % (reach, MAX_REACH))
+        if minPairs < 0:
+            raise ValueError("minPairs %d is negative" % minPairs)
+        if minSize < 0:
+            raise ValueError("minSize %d is negative" % minSize)
+        if not minRatio >= 1:
+            raise ValueError("minRatio %g is below 1" % minRatio)
+        check_valid_pair_file(v["validPairFile"])
+        names, sizes = read_scaffold_sizes(v["hicProScaffSizeFile"])
+        if not names:
+            raise ValueError("hicProScaffSizeFile %s lists no scaffold" % v["hicProScaffSizeFile"])
+        if orderFile is None:
+            orderFile = v["finalOrderingsFile"] if os.path.isfile(v["finalOrderingsFile"]) else v["chromosomeOrderFile"]
+        if not os.path.isfile(orderFile):
+            raise ValueError("order file %r does not exist" % orderFile)
+        asm = build_assembly(read_order_file(orderFile), names, sizes, DEFAULT_GAP, chromosomes_only=True)
+        first1, n1 = number_blocks(asm, sizes)
+        if n1 > MAX_TABLE:
+            raise ValueError("%d unplaced scaffolds against %d chromosomes need a table of %d counters, more than the %d a build can "
+                             "have; -minSize applies after this pass and cannot make it smaller: take the smallest scaffolds out of "
+                             "hicProScaffSizeFile" % (int((first1 >= 0).sum()), len(asm.components), n1, MAX_TABLE))
+    except (OSError, ValueError) as exc:
+        sys.exit("ERROR... %s. Exiting..." % exc)
+    n_seq = len(asm.components)
+    candidates = np.flatnonzero(first1 >= 0).tolist()
+    tables = (asm.lift_seq, asm.lift_off, asm.lift_rev, asm.seq_sizes)
+    filled = [[s for s, _off, _o in comps if sizes[s] > 0] for comps in asm.components]
+    B = [sum(int(sizes[s]) for s in members) for members in filled]
+
+    zero = np.zeros(6, np.uint64)
+
+    def count(ctx, target, first, n_table):
+        """One pass: (stats4, table, counters), the library's blocks checked against this report's."""
+        if context is None:
+            got = _lib.anchor_file(v["validPairFile"], names, sizes, *tables, target, window, ctx, threads=threads)
+        elif hasattr(ctx, "anchor_file"):
+            got = ctx.anchor_file(v["validPairFile"], names, sizes, *tables, target, window, threads=threads)
+        else:
+            got = measure(ctx, v["validPairFile"], names, sizes, asm, target, window, threads)
+        stats, got_first, table, counters = got
+        if not np.array_equal(got_first, first) or table.shape != (n_table,):
+            sys.exit("ERROR... the library numbers the unplaced scaffolds differently from this report. Exiting...")
+        return tuple(stats[:4]), table, counters
+
+    def both_passes(ctx):
+        """(stats4, counters of pass 1, counters of pass 2, links {s: a[q]}, chosen {s: choose_chromosome}, T {s: [k, half, zone]})"""
+        stats, table, counters1 = count(ctx, None, first1, n1)
+        links = {s: [int(x) for x in table[first1[s]:first1[s] + n_seq]] for s in candidates}
+        chosen = {s: choose_chromosome(links[s], B, int(sizes[s]), minPairs, minRatio, minSize) for s in candidates}
+        target = np.full(len(sizes), -1, np.int32)
+        for s, (best, _second, _ratio, verdict) in chosen.items():
+            if verdict is None:
+                target[s] = best
+        if not (target >= 0).any():                                # no scaffold got a chromosome: there is no second pass
+            return stats, counters1, zero, links, chosen, {}
+        first2, n2 = number_blocks(asm, sizes, target)
+        if n2 > MAX_TABLE:
+            sys.exit("ERROR... the %d scaffolds that got a chromosome need a table of %d counters, more than the %d a build can have: "
+                     "raise -minSize. Exiting..." % (int((target >= 0).sum()), n2, MAX_TABLE))
+        stats2, table, counters2 = count(ctx, target, first2, n2)
+        if stats2 != stats:
+            sys.exit("ERROR... validPairFile changed between the two passes. Exiting...")
+        T = {s: table[first2[s]:first2[s] + 4 * len(filled[target[s]])].reshape(-1, 2, 2) for s in np.flatnonzero(target >= 0).tolist()}
+        return stats, counters1, counters2, links, chosen, T
+
+    stats, counters1, counters2, links, chosen, T = (0, 0, 0, 0), zero, zero, {}, {}, {}
+    if candidates:
+        with paused_gc():
+            try:
+                if context is None:
+                    with _lib.Context(device) as ctx:
+                        stats, counters1, counters2, links, chosen, T = both_passes(ctx)
+                else:
+                    stats, counters1, counters2, links, chosen, T = both_passes(context)
+            except _lib.HicmiError as exc:
+                sys.exit("ERROR... %s. Exiting..." % exc)
+    else:
+        print("UNPLACED: nothing is unplaced: %s names every scaffold that has a base" % orderFile)
+    print("UNPLACED: lines %d, pairs used %d, unknown scaffold %d, out of range %d" % stats
+          + "; chromosomes: " + ", ".join("%s %d" % kv for kv in zip(COUNTER_COLUMNS, counters1.tolist()))
+          + "; gaps: " + ", ".join("%s %d" % kv for kv in zip(COUNTER_COLUMNS, counters2.tolist())))
+
+    # the gap of every scaffold that got a chromosome, then one winner per gap: the highest score, then the lowest index
+    scores = {s: gap_scores(T[s], reach) for s in T}
+    gaps = {s: choose_gap(scores[s], minPairs) for s in T}
+    verdicts = {s: chosen[s][3] or gaps[s][4] for s in candidates}
+    winners = {}
+    for s in sorted(gaps):
+        g, _o, m, _runner_up, verdict = gaps[s]
+        key = (chosen[s][0], g)
+        if verdict != "chromosome_only" and (key not in winners or m > gaps[winners[key]][2]):
+            winners[key] = s
+    for s, (g, _o, _m, _runner_up, verdict) in gaps.items():
+        if verdict != "chromosome_only" and winners[(chosen[s][0], g)] != s:
+            verdicts[s] = "deferred"
+
+    header = ["window=%d" % window, "reach=%d" % reach, "minPairs=%d" % minPairs, "minRatio=%g" % minRatio, "minSize=%d" % minSize]
+    header += ["%s=%d" % kv for kv in zip(STATS_COLUMNS, stats)]
+    header += ["chromosomes_%s=%d" % kv for kv in zip(COUNTER_COLUMNS, counters1.tolist())]
+    header += ["gaps_%s=%d" % kv for kv in zip(COUNTER_COLUMNS, counters2.tolist())]
+    out = ["#" + "\t".join(header) + "\n", "### Unplaced ###\n", "#" + "\t".join(UNPLACED_COLUMNS) + "\n"]
+    for s in candidates:
+        best, second, ratio, _verdict = chosen[s]
+        a = links[s]
+        cols = [names[s], str(int(sizes[s])), str(sum(a))]
+        cols += [str(best + 1), str(a[best])] if sum(a) else ["NA", "NA"]
+        cols += [str(second + 1), str(a[second])] if sum(a) and second is not None else ["NA", "NA"]
+        cols.append(_ratio_text(ratio if sum(a) else None))
+        if s in gaps:
+            g, o, m, runner_up, verdict = gaps[s]
+            members = filled[best]
+            if verdict == "chromosome_only":
+                cols += ["NA", "NA", "NA"]
+            else:
+                cols += [names[members[g - 1]] if g else "start", names[members[g]] if g < len(members) else "end", "+-"[o]]
+            cols += [str(m), str(runner_up)]
+        else:
+            cols += ["NA"] * 5
+        out.append("\t".join(cols + [verdicts[s]]) + "\n")
+    out += ["### Chromosomes ###\n", "#" + "\t".join(CHROMOSOME_COLUMNS) + "\n"]
+    for q in range(n_seq):
+        out.append("%d\t%d\t%d\t%d\t%d\n" % (q + 1, len(filled[q]), B[q], sum(chosen[s][0] == q for s in T),
+                                             sum(key[0] == q for key in winners)))
+    insertions = {}
+    for (q, g), s in winners.items():
+        members = filled[q]
+        where = names[members[g]] if g < len(members) else (names[members[-1]], None)
+        insertions[where] = (names[s], "+-"[gaps[s][1]])
+    placed_text = None if placedFile is None else placed_order_text(orderFile, insertions)
+    os.makedirs(os.path.dirname(os.path.abspath(outFile)), exist_ok=True)
+    with open(outFile, "w") as fh:
+        fh.write("".join(out))
+    if placedFile is not None:
+        with open(placedFile, "w", newline="") as fh:
+            fh.write(placed_text)
+    if fullDir is not None:
+        os.makedirs(fullDir, exist_ok=True)
+        with open(os.path.join(fullDir, "unplaced.chromosomes.tsv"), "w") as fh:
+            fh.write("#scaffold\t" + "\t".join("Chr_%d" % (q + 1) for q in range(n_seq)) + "\n")
+            for s in candidates:
+                fh.write(names[s] + "\t" + "\t".join(str(x) for x in links[s]) + "\n")
+        with open(os.path.join(fullDir, "unplaced.gaps.tsv"), "w") as fh:
+            fh.write("#scaffold\tchromosome\tgap\tleft\tright\torientation\tscore\n")
+            for s in sorted(scores):
+                members = filled[chosen[s][0]]
+                for g, both in enumerate(scores[s]):
+                    for o, x in enumerate(both):
+                        fh.write("%s\t%d\t%d\t%s\t%s\t%s\t%d\n" % (names[s], chosen[s][0] + 1, g, names[members[g - 1]] if g else "start",
+                                                                   names[members[g]] if g < len(members) else "end", "+-"[o], x))
+    inserted = sorted(winners.values())
+    print("UNPLACED: %d unplaced scaffold(s), %d with a chromosome, %d inserted, %d deferred" % (
+        len(candidates), len(T), len(inserted), sum(x == "deferred" for x in verdicts.values())))
+    return stats, verdicts, {names[s]: (chosen[s][0], gaps[s][0], "+-"[gaps[s][1]]) for s in inserted}
+
+
+def main(argv=None, context=None):
+    parser = argparse.ArgumentParser(description="Counts, on the GPU, the read pairs of validPairFile that link the scaffolds an order "
+                                                 "file leaves out to its chromosomes and to the ends of their scaffolds, and "
+                                                 "reports where each of them belongs.")
+    parser.add_argument("-config", help="Full file path to the config file", required=True, type=str)
+    parser.add_argument("-order", help="Order file (default: finalOrderingsFile when it exists, else chromosomeOrderFile)",
+                        type=str, default=None)
+    parser.add_argument("-window", help="End zone of a placed scaffold in bp (default %d)" % DEFAULT_WINDOW, type=int, default=DEFAULT_WINDOW)
+    parser.add_argument("-reach", help="Scaffolds on either side of a gap that score it, 1 .. %d (default %d)" % (MAX_REACH, DEFAULT_REACH),
+                        type=int, default=DEFAULT_REACH)
+    parser.add_argument("-minPairs", help="Links below which neither a chromosome nor a gap is chosen (default %d)" % DEFAULT_MIN_PAIRS,
+                        type=int, default=DEFAULT_MIN_PAIRS)
+    parser.add_argument("-minRatio", help="Link density of the best chromosome over the second best below which none is chosen "
+                                          "(default %g)" % DEFAULT_MIN_RATIO, type=float, default=DEFAULT_MIN_RATIO)
+    parser.add_argument("-minSize", help="Scaffolds below this size in bp get no chromosome (default %d)" % DEFAULT_MIN_SIZE, type=int,
+                        default=DEFAULT_MIN_SIZE)
+    parser.add_argument("-out", help="Report (default: saveFilesDirectory/unplacedSupport.txt)", type=str, default=None)
+    parser.add_argument("-placed", help="Write the order file again with one placed scaffold inserted per gap", type=str, default=None)
+    parser.add_argument("-full", help="Write unplaced.chromosomes.tsv and unplaced.gaps.tsv into this directory", type=str, default=None)
+    parser.add_argument("-threads", help="Host threads of the parser (default 0: all)", type=int, default=0)
+    parser.add_argument("-device", help="GPU index (default 0)", type=int, default=0)
+    args = parser.parse_args(argv)
+    return runPipeline(args.config, args.order, args.window, args.reach, args.minPairs, args.minRatio, args.minSize, args.out, args.placed,
+                       args.full, threads=args.threads, device=args.device, context=context)
+
+
+if __name__ == "__main__":
+    main()
+

@@ -624,6 +624,49 @@ int hicmi_ends_file(const char *path, const char *names_blob, const int64_t *nam
                     int64_t *stats5, uint64_t *table_out, uint64_t *counters6_out, int32_t *rank_out,
                     int64_t *n_placed_out);
 
+/* ---- anchoring: the read pairs that link the scaffolds an ordering leaves out to the placed ones ------
+ * The assembly is given by the lift tables of 9m, checked in the same way, and the placed scaffolds of size > 0 are
+ * ranked as in 9p; seq_first[q] is the first rank of sequence q and S_q = seq_first[q + 1] - seq_first[q].  A candidate
+ * is a dropped scaffold (lift_seq = -1) of size > 0; the candidates are taken in index order and each owns a block of
+ * counters of one table, first_out[s] being the block's offset and -1 for a scaffold that is no candidate.
+ *   target == NULL (sequence mode): every dropped scaffold of size > 0 is a candidate with a block of n_seq counters; a
+ *     pair with one end on the candidate c and the other in sequence q adds 1 at first[c] + q.
+ *   target != NULL (rank mode; int32 per scaffold): the candidates are the scaffolds with target[s] >= 0, the block of c
+ *     has 4 x S_target[c] counters, and a pair whose placed end lies on the scaffold of rank r of sequence q = target[c]
+ *     adds 1 at first[c] + (r - seq_first[q]) * 4 + zu * 2 + zp: zu is the half of c its own end p falls in, in the +
+ *     coordinates of c (0 when p - 1 < L - L / 2, else 1), zp the zone of the placed end as it lies (9p; 0 left, 1 right).
+ * counters6: anchored, middle (rank mode: the placed end in no zone), elsewhere (rank mode: the placed end in a sequence
+ * other than the target), skipped (rank mode: the dropped end on a scaffold with target < 0), unplaced (neither end
+ * lifts; two ends on one dropped scaffold too), placed (both ends lift); a pair is checked for placed, unplaced, skipped,
+ * elsewhere and middle in this order.  Every chunking and arrival order gives the same bits.
+ *
+ * hicmi_anchor_begin checks the tables, returns the blocks and the size of the table and allocates a zeroed table; an
+ * anchor build that was open is given up.  The context's matrix state, an open map build (9l, 9m), an open span build
+ * (9n) and an open ends build (9p) are never touched by these calls.  HICMI_EINVAL, the message naming the scaffold:
+ * tables refused, window < 1 (in either mode), no candidate, a target outside -1 .. n_seq - 1, a target >= 0 on a placed
+ * or an empty scaffold, a target sequence with S_q = 0; HICMI_EUNSUPPORTED: more than 2^27 counters, or in rank mode more
+ * than 2^25 placed scaffolds; all before anything is allocated.
+ * hicmi_anchor_add_pairs checks every index and position on the host like hicmi_map_add_pairs (HICMI_EINVAL, nothing
+ * uploaded, the build unchanged), uploads the arrays and counts them.  HICMI_ANCHOR_PLAIN=1 in the environment, read at
+ * every call, takes one global atomic add per anchored pair; =0 and the default take the combining kernel, in which a
+ * workgroup sums the pairs of its slice per counter in a table in LDS first.  Both give the same bits.
+ * hicmi_anchor_finish downloads the table and the counters and closes the build; HICMI_EINVAL without an open build.
+ *
+ * hicmi_anchor_file: begin, every pair of the file, finish, in one pass with the chunked parser as in hicmi_span_file
+ * and hicmi_ends_file (HICMI_BUILDMAP_CHUNK_PAIRS, stats5 as there).  Tables, targets and window are refused before the
+ * file is read; on any error no output is written, and no anchor build stays open. */
+int hicmi_anchor_begin(hicmi_ctx *ctx, const int64_t *scaf_size, int64_t n_scaf, const int32_t *lift_seq,
+                       const int64_t *lift_off, const uint8_t *lift_rev, const int64_t *seq_size, int64_t n_seq,
+                       const int32_t *target, int64_t window, int64_t *first_out, int64_t *n_table_out);
+int hicmi_anchor_add_pairs(hicmi_ctx *ctx, const int32_t *scaf_a, const int64_t *pos_a,
+                           const int32_t *scaf_b, const int64_t *pos_b, int64_t n);
+int hicmi_anchor_finish(hicmi_ctx *ctx, uint64_t *table_out, uint64_t *counters6_out);
+int hicmi_anchor_file(const char *path, const char *names_blob, const int64_t *name_off, int64_t n_names,
+                      const int64_t *scaf_size, const int32_t *lift_seq, const int64_t *lift_off, const uint8_t *lift_rev,
+                      const int64_t *seq_size, int64_t n_seq, const int32_t *target, int64_t window, hicmi_ctx *ctx,
+                      int threads, int64_t *stats5, uint64_t *table_out, uint64_t *counters6_out, int64_t *first_out,
+                      int64_t *n_table_out);
+
 /* ---- scaffolds cut into pieces: every read end moved from its scaffold to its piece -------------------
  * Scaffold s of the n_scaf scaffolds has the pieces piece_first[s] .. piece_first[s + 1] - 1 (int32, n_scaf + 1 entries,
  * ascending from 0 to n_piece), left to right; piece k starts after piece_start[k] bases of its parent (int64, 0 for a
