@@ -110,6 +110,15 @@ SIGNATURES = {
     "hicmi_anchor_finish": (ctypes.c_int, [_vp, _vp, _vp]),
     "hicmi_anchor_file": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, _vp, _vp, _vp, _vp, c_i64, _vp, c_i64,
                                          _vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.POINTER(c_i64)]),
+    "hicmi_pairs_begin": (ctypes.c_int, [_vp, _vp, c_i64]),
+    "hicmi_pairs_add": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, c_i64]),
+    "hicmi_pairs_file": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, _vp, ctypes.c_int, _vp]),
+    "hicmi_pairs_info": (ctypes.c_int, [_vp, ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_uint64), _vp]),
+    "hicmi_pairs_fetch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "hicmi_pairs_drop": (ctypes.c_int, [_vp]),
+    "hicmi_ends_resident": (ctypes.c_int, [_vp, _vp, c_i64, _vp, _vp, _vp, _vp, c_i64, c_i64, c_i64, _vp, _vp, _vp, ctypes.POINTER(c_i64)]),
+    "hicmi_anchor_resident": (ctypes.c_int, [_vp, _vp, c_i64, _vp, _vp, _vp, _vp, c_i64, _vp, c_i64, _vp, _vp, _vp,
+                                             ctypes.POINTER(c_i64)]),
     "hicmi_split_pairs": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, c_i64, _vp, c_i64, _vp, _vp, c_i64, _vp, _vp, _vp, _vp, _vp]),
     "hicmi_split_maps": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, _vp, _vp, c_i64, c_i64, _vp, _vp,
                                         ctypes.c_int, _vp, _vp]),
@@ -470,6 +479,20 @@ def anchor_file(path, names, sizes, lift_seq, lift_off, lift_rev, seq_sizes, tar
     return tuple(int(v) for v in stats), first, table, counters
 
 
+def pairs_file(path, names, sizes, ctx, threads: int = 0):
+    """Load a HiC-Pro allValidPairs file into the resident pair store of ``ctx`` in one pass (hicmi_pairs_file, DESIGN.md
+    9r): the pairs on two scaffolds stay on the device, the others are counted per scaffold.  The matrix and every open
+    build of ``ctx`` stay as they are.  Returns (lines, used, unknown_scaffold, out_of_range, chunks)."""
+    blob, off = _name_blob(names)
+    size = np.ascontiguousarray(sizes, dtype=np.int64)
+    if size.shape != (len(names),):
+        raise ValueError("one size per scaffold name")
+    stats = np.zeros(5, np.int64)
+    _check(load().hicmi_pairs_file(os.fsencode(path), blob, _ptr(off), len(names), _ptr(size), ctx._h, int(threads), _ptr(stats)))
+    ctx._pairs_scaffolds = len(size)
+    return tuple(int(v) for v in stats)
+
+
 def _split_tables(sizes, piece_first, piece_start):
     """The piece tables of DESIGN.md 9o as the library takes them: (scaffold sizes, piece_first int32[S + 1], piece_start
     int64[n_piece])."""
@@ -568,6 +591,7 @@ class Context:
         self._n_window_cand = 0
         self._lv_m = 0                          # nodes of the Louvain graph on the device
         self.shard = (0, 1)
+        self._pairs_scaffolds = 0               # scaffolds of the resident pair store (0: this binding opened none)
 
     def close(self):
         for w in getattr(self, "_workers", []):
@@ -799,6 +823,78 @@ class Context:
         _check(self._lib.hicmi_anchor_finish(self._h, _ptr(table), _ptr(counters)))
         self._anchor_cells = None
         return table, counters
+
+    def pairs_begin(self, sizes):
+        """Open an empty resident pair store (hicmi_pairs_begin) for the scaffolds of ``sizes``.  Refused when
+        the context has one already.  The matrix and every open build are untouched."""
+        size = np.ascontiguousarray(sizes, dtype=np.int64)
+        _check(self._lib.hicmi_pairs_begin(self._h, _ptr(size), len(size)))
+        self._pairs_scaffolds = len(size)
+
+    def pairs_add(self, scaf_a, pos_a, scaf_b, pos_b):
+        """Append the pairs (scaffold index, 1-based position) x 2 that lie on two scaffolds to the store and count the
+        others per scaffold (hicmi_pairs_add)."""
+        sa, sb = np.ascontiguousarray(scaf_a, dtype=np.int32), np.ascontiguousarray(scaf_b, dtype=np.int32)
+        pa, pb = np.ascontiguousarray(pos_a, dtype=np.int64), np.ascontiguousarray(pos_b, dtype=np.int64)
+        if not (sa.ndim == 1 and sa.shape == sb.shape == pa.shape == pb.shape):
+            raise ValueError("the four arrays must be vectors of one length")
+        _check(self._lib.hicmi_pairs_add(self._h, _ptr(sa), _ptr(pa), _ptr(sb), _ptr(pb), len(sa)))
+
+    def pairs_info(self):
+        """(pairs kept, intra pairs, intra uint64[S]) of the store (hicmi_pairs_info)."""
+        n_kept, n_intra = c_i64(), ctypes.c_uint64()
+        # intra[] is asked for only from a store this binding opened, whose scaffold count it therefore knows
+        intra = np.zeros(self._pairs_scaffolds, np.uint64) if self._pairs_scaffolds else None
+        _check(self._lib.hicmi_pairs_info(self._h, ctypes.byref(n_kept), ctypes.byref(n_intra), _ptr(intra)))
+        return n_kept.value, n_intra.value, intra
+
+    def pairs_fetch(self):
+        """The store, downloaded (hicmi_pairs_fetch): (scaf_a int32, pos_a int64, scaf_b int32, pos_b int64)."""
+        n = self.pairs_info()[0]
+        sa, sb = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        pa, pb = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        _check(self._lib.hicmi_pairs_fetch(self._h, _ptr(sa), _ptr(pa), _ptr(sb), _ptr(pb)))
+        return sa, pa, sb, pb
+
+    def pairs_drop(self):
+        """Release the store (hicmi_pairs_drop)."""
+        _check(self._lib.hicmi_pairs_drop(self._h))
+        self._pairs_scaffolds = 0
+
+    def pairs_file(self, path, names, sizes, threads: int = 0):
+        """``pairs_file`` of this module on this context."""
+        return pairs_file(path, names, sizes, self, threads=threads)
+
+    def ends_resident(self, sizes, lift_seq, lift_off, lift_rev, seq_sizes, window, reach):
+        """End support of an assembly from the resident pair store (hicmi_ends_resident): what ``ends_file``
+        returns without the parser's sums, (rank int32[S], table uint64[P, reach, 4], counters uint64[6]).  The store is
+        only read; refused while an ends build is open."""
+        size, seq, off, rev, seq_size = _lift_tables(sizes, lift_seq, lift_off, lift_rev, seq_sizes)
+        counters = np.zeros(6, np.uint64)
+        rank, n_placed = np.zeros(len(size), np.int32), c_i64()
+        table = _ends_table(ends_placed_count(size, seq), reach)
+        _check(self._lib.hicmi_ends_resident(self._h, _ptr(size), len(size), _ptr(seq), _ptr(off), _ptr(rev), _ptr(seq_size),
+                                             len(seq_size), int(window), int(reach), _ptr(table), _ptr(counters), _ptr(rank),
+                                             ctypes.byref(n_placed)))
+        if n_placed.value != table.shape[0]:
+            raise RuntimeError("hicmi_ends_resident placed %d scaffolds, this binding %d" % (n_placed.value, table.shape[0]))
+        return rank, table, counters
+
+    def anchor_resident(self, sizes, lift_seq, lift_off, lift_rev, seq_sizes, target, window):
+        """Anchoring from the resident pair store (hicmi_anchor_resident): what ``anchor_file`` returns without
+        the parser's sums, (first int64[S], table uint64[n_table], counters uint64[6]).  The store is only read; refused
+        while an anchor build is open."""
+        size, seq, off, rev, seq_size = _lift_tables(sizes, lift_seq, lift_off, lift_rev, seq_sizes)
+        tgt = _anchor_target(target, len(size))
+        counters = np.zeros(6, np.uint64)
+        first, n_table = np.zeros(len(size), np.int64), c_i64()
+        table = _anchor_table(anchor_blocks(size, seq, len(seq_size), tgt)[1])
+        _check(self._lib.hicmi_anchor_resident(self._h, _ptr(size), len(size), _ptr(seq), _ptr(off), _ptr(rev), _ptr(seq_size),
+                                               len(seq_size), _ptr(tgt), int(window), _ptr(table), _ptr(counters), _ptr(first),
+                                               ctypes.byref(n_table)))
+        if n_table.value != len(table):
+            raise RuntimeError("hicmi_anchor_resident has a table of %d counters, this binding %d" % (n_table.value, len(table)))
+        return first, table, counters
 
     def split_pairs(self, scaf_a, pos_a, scaf_b, pos_b, sizes, piece_first, piece_start, into=None):
         """The pairs (scaffold index, 1-based position) x 2 moved to the pieces the scaffolds are cut into

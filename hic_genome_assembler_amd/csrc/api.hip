@@ -11,6 +11,7 @@
 #include <cstring>
 #include <numeric>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <functional>
 #include <chrono>
@@ -231,6 +232,17 @@ struct hicmi_ctx {
     DevBuf<int64_t> d_anchor_first;
     DevBuf<int32_t> d_anchor_target;
     std::vector<int64_t> anchor_size;
+    // the resident pair store (k_pairs.hip), between hicmi_pairs_begin / hicmi_pairs_file and hicmi_pairs_drop
+    // (d_pairs_intra non-null: the context has a store): the kept pairs in four arrays of one capacity, pairs_len of
+    // them in use, intra[n_scaf] with the device's copy of the length behind it, the offsets of a chunk's workgroups,
+    // pinned memory the length comes back into, and the host's copy of the sizes
+    DevBuf<int32_t> d_pairs_scaf_a, d_pairs_scaf_b;
+    DevBuf<int64_t> d_pairs_pos_a, d_pairs_pos_b;
+    DevBuf<unsigned long long> d_pairs_intra;
+    DevBuf<long long> d_pairs_work;
+    PinBuf<unsigned long long> pin_pairs_len;
+    int64_t pairs_len = 0;
+    std::vector<int64_t> pairs_size;
     // plot support
     DevBuf<int32_t> d_plot_order;
     DevBuf<unsigned char> d_plot_work;
@@ -1170,8 +1182,9 @@ static int chunk_pairs_setting(int64_t* out)
 }
 
 // One pass over a pair file for one build of the context c: chunk t + 1 is parsed into the other pinned buffer while chunk
-// t is uploaded and handed to on_chunk(device arrays, n), which launches on the context's stream.  stats[0 .. 3] are the
-// parser's sums and stats[4] the chunks; `doing` names the work in the message of a HIP error.
+// t is uploaded and handed to on_chunk(device arrays, n), which launches on the context's stream and returns nothing, or
+// an error code that ends the pass.  stats[0 .. 3] are the parser's sums and stats[4] the chunks; `doing` names the work in
+// the message of a HIP error.
 extern "C++" {
 template <typename OnChunk>
 static int pair_file_pass(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
@@ -1212,7 +1225,11 @@ static int pair_file_pass(const char* path, const char* names_blob, const int64_
             HIPCHK(hipMemcpyAsync(d.pos_b, h.pos_b, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
             HIPCHK(hipMemcpyAsync(d.scaf_a, h.scaf_a, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
             HIPCHK(hipMemcpyAsync(d.scaf_b, h.scaf_b, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-            on_chunk(d, n);
+            if constexpr (std::is_void<decltype(on_chunk(d, n))>::value) on_chunk(d, n);
+            else if ((rc = on_chunk(d, n)) != HICMI_OK) {          // an on_chunk that can fail ends the pass
+                (void)hipStreamSynchronize(c->stream);             // the copies out of the pinned buffers are done
+                return rc;
+            }
             HIPCHK(hipGetLastError());
             stats[4]++;
         }
@@ -1795,6 +1812,9 @@ int hicmi_anchor_file(const char* path, const char* names_blob, const int64_t* n
     *n_table_out = blocks.n_table;
     return HICMI_OK;
 }
+
+// ---- the resident pair store: hicmi_pairs_*, hicmi_ends_resident, hicmi_anchor_resident --------------------
+#include "api_pairs.inc"
 
 // Group support: extends the scaffold vote of assessChromosomeClustering (S2C:1001-1077) with the
 // contacts themselves.  The host sorts the grouped rows by group and cuts them into chunks of GS_CHUNK; the kernels of

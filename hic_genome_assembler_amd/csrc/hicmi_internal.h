@@ -10,6 +10,7 @@
 #include "span.h"
 #include "ends.h"
 #include "anchor.h"
+#include "pairs.h"
 #include "split.h"
 
 namespace hicmi {
@@ -568,6 +569,19 @@ static constexpr int ANCHOR_PROBES = 8;        // a pair that finds no room with
 void launch_anchor_count(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
                          const LiftTables& lift, const AnchorGrid& grid, int64_t n_table, void* table, void* counters, bool plain,
                          hipStream_t s);
+
+// k_pairs.hip: the resident pair store (hicmi_pairs_*).  A chunk of n pairs on the device is compacted into
+// the store: the kept pairs (pairs.h) are appended from *length on, which is advanced, and the others add to intra[n_scaf].
+// work: pairs_keep_blocks(n) 64-bit integers of the default form; everything is device memory, and the caller has made room
+// for *length + n pairs.
+static constexpr int PAIRS_SLICE = 2048;       // pairs a workgroup of the stable k_pairs_keep compacts: one offset per workgroup
+static constexpr int PAIRS_SLOT_BITS = 8;
+static constexpr int PAIRS_SLOTS = 1 << PAIRS_SLOT_BITS;   // slots of the intra table in LDS (8 bytes each): scaffolds of a slice
+static constexpr int PAIRS_PROBES = 8;         // an intra pair that finds no room within so many probes is added directly
+struct PairStore { int32_t* scaf_a = nullptr; int64_t* pos_a = nullptr; int32_t* scaf_b = nullptr; int64_t* pos_b = nullptr; int64_t cap = 0; };
+int64_t pairs_keep_blocks(int64_t n);
+void launch_pairs_keep(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
+                       int64_t n_scaf, const PairStore& store, void* length, void* intra, void* work, bool plain, hipStream_t s);
 
 // k_split.hip: a chunk of pairs moved in place from scaffolds to the pieces they are cut into (hicmi_split_*),
 // each pair adding to counters[4 n_piece] = [within][sibling][other][mark] of its pieces; everything is device memory.

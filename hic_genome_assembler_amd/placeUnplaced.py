@@ -117,6 +117,67 @@ def choose_gap(scores, minPairs):
     return g, o, m, runner_up, "placed" if len(at) == 1 else "orientation_open"
 
 
+def chromosome_members(asm, sizes):
+    """(filled, B): per chromosome its scaffolds that have a base, in the order they lie, and the bases they have."""
+    filled = [[s for s, _off, _o in comps if sizes[s] > 0] for comps in asm.components]
+    return filled, [sum(int(sizes[s]) for s in members) for members in filled]
+
+
+def both_passes(count, asm, sizes, first1, n1, minPairs, minRatio, minSize):
+    """The two passes of a run over ``count(target, first, n_table)`` -> (stats4, table, counters), which counts one pass
+    from the file or from a resident store: (stats4, counters of pass 1, counters of pass 2, links {s: a[q]},
+    chosen {s: choose_chromosome}, T {s: [k, half, zone]})."""
+    n_seq = len(asm.components)
+    candidates = np.flatnonzero(first1 >= 0).tolist()
+    filled, B = chromosome_members(asm, sizes)
+    stats, table, counters1 = count(None, first1, n1)
+    links = {s: [int(x) for x in table[first1[s]:first1[s] + n_seq]] for s in candidates}
+    chosen = {s: choose_chromosome(links[s], B, int(sizes[s]), minPairs, minRatio, minSize) for s in candidates}
+    target = np.full(len(sizes), -1, np.int32)
+    for s, (best, _second, _ratio, verdict) in chosen.items():
+        if verdict is None:
+            target[s] = best
+    if not (target >= 0).any():                                # no scaffold got a chromosome: there is no second pass
+        return stats, counters1, np.zeros(6, np.uint64), links, chosen, {}
+    first2, n2 = number_blocks(asm, sizes, target)
+    if n2 > MAX_TABLE:
+        sys.exit("ERROR... the %d scaffolds that got a chromosome need a table of %d counters, more than the %d a build can have: "
+                 "raise -minSize. Exiting..." % (int((target >= 0).sum()), n2, MAX_TABLE))
+    stats2, table, counters2 = count(target, first2, n2)
+    if stats2 != stats:
+        sys.exit("ERROR... validPairFile changed between the two passes. Exiting...")
+    T = {s: table[first2[s]:first2[s] + 4 * len(filled[target[s]])].reshape(-1, 2, 2) for s in np.flatnonzero(target >= 0).tolist()}
+    return stats, counters1, counters2, links, chosen, T
+
+
+def settle_gaps(T, chosen, candidates, reach, minPairs):
+    """(scores, gaps, verdicts, winners): the gap of every scaffold that got a chromosome, then one winner per gap - the
+    highest score, then the lowest index - and ``deferred`` for the others that chose it."""
+    scores = {s: gap_scores(T[s], reach) for s in T}
+    gaps = {s: choose_gap(scores[s], minPairs) for s in T}
+    verdicts = {s: chosen[s][3] or gaps[s][4] for s in candidates}
+    winners = {}
+    for s in sorted(gaps):
+        g, _o, m, _runner_up, verdict = gaps[s]
+        key = (chosen[s][0], g)
+        if verdict != "chromosome_only" and (key not in winners or m > gaps[winners[key]][2]):
+            winners[key] = s
+    for s, (g, _o, _m, _runner_up, verdict) in gaps.items():
+        if verdict != "chromosome_only" and winners[(chosen[s][0], g)] != s:
+            verdicts[s] = "deferred"
+    return scores, gaps, verdicts, winners
+
+
+def winner_insertions(winners, gaps, filled, names):
+    """The winners as ``placed_order_text`` takes them."""
+    insertions = {}
+    for (q, g), s in winners.items():
+        members = filled[q]
+        where = names[members[g]] if g < len(members) else (names[members[-1]], None)
+        insertions[where] = (names[s], "+-"[gaps[s][1]])
+    return insertions
+
+
 def measure(ctx, pairFile, names, sizes, asm, target, window, threads):
     """(stats4, first, table, counters) through the array calls of a context the caller owns: the file is parsed on the host
     in chunks (hicmi_parse_valid_pairs) and counted chunk by chunk."""
@@ -198,8 +259,7 @@ def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT
     n_seq = len(asm.components)
     candidates = np.flatnonzero(first1 >= 0).tolist()
     tables = (asm.lift_seq, asm.lift_off, asm.lift_rev, asm.seq_sizes)
-    filled = [[s for s, _off, _o in comps if sizes[s] > 0] for comps in asm.components]
-    B = [sum(int(sizes[s]) for s in members) for members in filled]
+    filled, B = chromosome_members(asm, sizes)
 
     zero = np.zeros(6, np.uint64)
 
@@ -216,26 +276,9 @@ def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT
             sys.exit("ERROR... the library numbers the unplaced scaffolds differently from this report. Exiting...")
         return tuple(stats[:4]), table, counters
 
-    def both_passes(ctx):
-        """(stats4, counters of pass 1, counters of pass 2, links {s: a[q]}, chosen {s: choose_chromosome}, T {s: [k, half, zone]})"""
-        stats, table, counters1 = count(ctx, None, first1, n1)
-        links = {s: [int(x) for x in table[first1[s]:first1[s] + n_seq]] for s in candidates}
-        chosen = {s: choose_chromosome(links[s], B, int(sizes[s]), minPairs, minRatio, minSize) for s in candidates}
-        target = np.full(len(sizes), -1, np.int32)
-        for s, (best, _second, _ratio, verdict) in chosen.items():
-            if verdict is None:
-                target[s] = best
-        if not (target >= 0).any():                                # no scaffold got a chromosome: there is no second pass
-            return stats, counters1, zero, links, chosen, {}
-        first2, n2 = number_blocks(asm, sizes, target)
-        if n2 > MAX_TABLE:
-            sys.exit("ERROR... the %d scaffolds that got a chromosome need a table of %d counters, more than the %d a build can have: "
-                     "raise -minSize. Exiting..." % (int((target >= 0).sum()), n2, MAX_TABLE))
-        stats2, table, counters2 = count(ctx, target, first2, n2)
-        if stats2 != stats:
-            sys.exit("ERROR... validPairFile changed between the two passes. Exiting...")
-        T = {s: table[first2[s]:first2[s] + 4 * len(filled[target[s]])].reshape(-1, 2, 2) for s in np.flatnonzero(target >= 0).tolist()}
-        return stats, counters1, counters2, links, chosen, T
+    def passes(ctx):
+        return both_passes(lambda target, first, n_table: count(ctx, target, first, n_table), asm, sizes, first1, n1, minPairs,
+                           minRatio, minSize)
 
     stats, counters1, counters2, links, chosen, T = (0, 0, 0, 0), zero, zero, {}, {}, {}
     if candidates:
@@ -243,9 +286,9 @@ def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT
             try:
                 if context is None:
                     with _lib.Context(device) as ctx:
-                        stats, counters1, counters2, links, chosen, T = both_passes(ctx)
+                        stats, counters1, counters2, links, chosen, T = passes(ctx)
                 else:
-                    stats, counters1, counters2, links, chosen, T = both_passes(context)
+                    stats, counters1, counters2, links, chosen, T = passes(context)
             except _lib.HicmiError as exc:
                 sys.exit("ERROR... %s. Exiting..." % exc)
     else:
@@ -254,19 +297,7 @@ def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT
           + "; chromosomes: " + ", ".join("%s %d" % kv for kv in zip(COUNTER_COLUMNS, counters1.tolist()))
           + "; gaps: " + ", ".join("%s %d" % kv for kv in zip(COUNTER_COLUMNS, counters2.tolist())))
 
-    # the gap of every scaffold that got a chromosome, then one winner per gap: the highest score, then the lowest index
-    scores = {s: gap_scores(T[s], reach) for s in T}
-    gaps = {s: choose_gap(scores[s], minPairs) for s in T}
-    verdicts = {s: chosen[s][3] or gaps[s][4] for s in candidates}
-    winners = {}
-    for s in sorted(gaps):
-        g, _o, m, _runner_up, verdict = gaps[s]
-        key = (chosen[s][0], g)
-        if verdict != "chromosome_only" and (key not in winners or m > gaps[winners[key]][2]):
-            winners[key] = s
-    for s, (g, _o, _m, _runner_up, verdict) in gaps.items():
-        if verdict != "chromosome_only" and winners[(chosen[s][0], g)] != s:
-            verdicts[s] = "deferred"
+    scores, gaps, verdicts, winners = settle_gaps(T, chosen, candidates, reach, minPairs)
 
     header = ["window=%d" % window, "reach=%d" % reach, "minPairs=%d" % minPairs, "minRatio=%g" % minRatio, "minSize=%d" % minSize]
     header += ["%s=%d" % kv for kv in zip(STATS_COLUMNS, stats)]
@@ -295,11 +326,7 @@ def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT
     for q in range(n_seq):
         out.append("%d\t%d\t%d\t%d\t%d\n" % (q + 1, len(filled[q]), B[q], sum(chosen[s][0] == q for s in T),
                                              sum(key[0] == q for key in winners)))
-    insertions = {}
-    for (q, g), s in winners.items():
-        members = filled[q]
-        where = names[members[g]] if g < len(members) else (names[members[-1]], None)
-        insertions[where] = (names[s], "+-"[gaps[s][1]])
+    insertions = winner_insertions(winners, gaps, filled, names)
     placed_text = None if placedFile is None else placed_order_text(orderFile, insertions)
     os.makedirs(os.path.dirname(os.path.abspath(outFile)), exist_ok=True)
     with open(outFile, "w") as fh:

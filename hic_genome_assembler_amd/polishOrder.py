@@ -1,0 +1,268 @@
+"""Polishing an order file to a fixed point: flip, place, flip again, on read pairs kept on the device (DESIGN.md section
+9r).
+
+supportEnds and placeUnplaced each make one pass over ``validPairFile`` and hand the iteration to the user: every flip is
+judged on the order file as it lies, one scaffold is inserted per gap, and after an insertion the neighbours' ends face
+something new.  This tool reads the file once into the resident pair store of a context (hicmi_pairs_file) and runs the
+loop on it: every round counts the store again under new lift tables (hicmi_ends_resident, hicmi_anchor_resident) and takes
+the decisions of the two tools unchanged.
+
+    python -m hic_genome_assembler_amd.polishOrder -config my_config.txt [-order FILE] [-moves flip,place] [-window 50000] \\
+           [-reach 2] [-minPairs 4] [-minRatio 2] [-minSize 0] [-maxRounds 1000] [-out DIR] [-threads 0] [-device 0]
+
+Flip rounds run until no scaffold says ``flip``.  A round takes the scaffolds supportEnds calls ``flip``, by
+``flipped - as_lies`` descending, then by rank, and accepts one when no scaffold accepted before it in this round lies within
+``-reach`` ranks of it in its chromosome: accepted flips touch disjoint entries of the table.  ``F``, the links between
+facing ends, must rise strictly; a round after which it does not is undone and flipping ends (status ``stalled``).  Then one
+place round - one run of placeUnplaced, both passes - inserts one scaffold per gap, and the flip rounds start again.  The
+loop ends when a place round inserts nothing (``converged``) or ``-maxRounds`` rounds were applied and a further one had
+something to do (``max_rounds``).  ``stalled`` stays the status of a run whose flipping was cut short, whatever the place
+rounds did afterwards; ``ended`` in the summary says whether the loop then ran until nothing was left (``nothing_left``) or
+into the limit (``round_limit``).  The input order file is never changed.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+import tempfile
+
+import numpy as np
+
+from . import _lib
+from . import placeUnplaced as place
+from . import supportEnds as ends
+from .assembledMap import DEFAULT_GAP, build_assembly, read_order_file
+from .buildMap import STATS_COLUMNS, check_valid_pair_file
+from .hostio import paused_gc, read_scaffold_sizes
+
+DEFAULT_MAX_ROUNDS = 1000
+MOVES = ("flip", "place")
+LOG_COLUMNS = ("round", "kind", "chromosome", "scaffold", "as_lies|left", "flipped|right", "orientation", "score", "runner_up")
+SUMMARY_COLUMNS = ("chromosome", "scaffolds_before", "scaffolds_after", "flips", "insertions", "facing_before", "facing_after")
+
+
+def facing_links(T, seq_first):
+    """Per chromosome the links between facing ends: the sum of T[i, d - 1, RL] over its ranks."""
+    return [int(T[int(seq_first[q]):int(seq_first[q + 1]), :, ends.RL].sum()) for q in range(len(seq_first) - 1)]
+
+
+def accept_flips(calls, rank, lift_seq, reach):
+    """The scaffolds of a flip round: those called ``flip`` by gain descending, then by rank, each accepted when no scaffold
+    accepted before it lies within ``reach`` ranks of it in its chromosome."""
+    wanting = sorted((s for s, call in calls.items() if call[2] == "flip"), key=lambda s: (calls[s][0] - calls[s][1], int(rank[s])))
+    accepted = []
+    for s in wanting:
+        if all(lift_seq[t] != lift_seq[s] or abs(int(rank[t]) - int(rank[s])) > reach for t in accepted):
+            accepted.append(s)
+    return accepted
+
+
+def _read(path):
+    with open(path, newline="") as fh:
+        return fh.read()
+
+
+def _write(path, text):
+    with open(path, "w", newline="") as fh:
+        fh.write(text)
+
+
+def runPipeline(configFile, orderFile=None, moves="flip,place", window=ends.DEFAULT_WINDOW, reach=ends.DEFAULT_REACH,
+                minPairs=ends.DEFAULT_MIN_PAIRS, minRatio=place.DEFAULT_MIN_RATIO, minSize=place.DEFAULT_MIN_SIZE,
+                maxRounds=DEFAULT_MAX_ROUNDS, outDir=None, threads=0, device=0, context=None):
+    """``context``: a context of the caller's that has ``pairs_file``, ``pairs_info``, ``ends_resident`` and
+    ``anchor_resident``; None: a context of its own on ``device``.  Returns (status, rounds, log rows)."""
+    from . import run_hicAssembler as driver
+    v = driver.readConfigFileToVariables(configFile)
+    if outDir is None:
+        outDir = os.path.join(v["saveFilesDirectory"], "polished")
+    try:
+        kinds = [m for m in str(moves).split(",")]
+        if not kinds or any(m not in MOVES for m in kinds):
+            raise ValueError("-moves %r is not a list of %s" % (moves, " and ".join(MOVES)))
+        if maxRounds < 1:
+            raise ValueError("maxRounds %d is below 1" % maxRounds)
+        if window < 1:
+            raise ValueError("the window %d is below 1" % window)
+        if not 1 <= reach <= ends.MAX_REACH:
+            raise ValueError("the reach %d is outside 1 .. %d" % (reach, ends.MAX_REACH))
+        if minPairs < 0:
+            raise ValueError("minPairs %d is negative" % minPairs)
+        if minSize < 0:
+            raise ValueError("minSize %d is negative" % minSize)
+        if not minRatio >= 1:
+            raise ValueError("minRatio %g is below 1" % minRatio)
+        check_valid_pair_file(v["validPairFile"])
+        names, sizes = read_scaffold_sizes(v["hicProScaffSizeFile"])
+        if not names:
+            raise ValueError("hicProScaffSizeFile %s lists no scaffold" % v["hicProScaffSizeFile"])
+        if orderFile is None:
+            orderFile = v["finalOrderingsFile"] if os.path.isfile(v["finalOrderingsFile"]) else v["chromosomeOrderFile"]
+        if not os.path.isfile(orderFile):
+            raise ValueError("order file %r does not exist" % orderFile)
+        outFile = os.path.join(outDir, os.path.basename(orderFile))
+        if os.path.abspath(outFile) == os.path.abspath(orderFile):
+            raise ValueError("the polished order file %s would replace the order file it is made from" % outFile)
+        asm = build_assembly(read_order_file(orderFile), names, sizes, DEFAULT_GAP, chromosomes_only=True)
+        n_placed = _lib.ends_placed_count(sizes, asm.lift_seq)
+        if n_placed < 1:
+            raise ValueError("no scaffold of %s has a base" % orderFile)
+        # a place round can give every scaffold with a base a rank: the table of the last round is refused now
+        n_most = n_placed if "place" not in kinds else int((np.asarray(sizes) > 0).sum())
+        if n_most * reach * 4 > ends.MAX_TABLE:
+            raise ValueError("reach %d over %d placed scaffolds needs a table of %d counters, more than the %d a build can have"
+                             % (reach, n_most, n_most * reach * 4, ends.MAX_TABLE))
+        first1, n1 = place.number_blocks(asm, sizes)
+        if "place" in kinds and n1 > place.MAX_TABLE:
+            raise ValueError("%d unplaced scaffolds against %d chromosomes need a table of %d counters, more than the %d a build can "
+                             "have: take the smallest scaffolds out of hicProScaffSizeFile"
+                             % (int((first1 >= 0).sum()), len(asm.components), n1, place.MAX_TABLE))
+    except (OSError, ValueError) as exc:
+        sys.exit("ERROR... %s. Exiting..." % exc)
+    n_seq = len(asm.components)
+
+    def polish(ctx, work):
+        """The loop on the working copy ``work`` of the order file: (stats4, kept, intra, rounds, status, ended, log, per
+        chromosome rows)."""
+        stats = tuple(ctx.pairs_file(v["validPairFile"], names, sizes, threads=threads)[:4])
+        try:
+            n_kept, n_intra = ctx.pairs_info()[:2]
+
+            def lay():
+                """The working copy as it lies, counted: (assembly, rank, seq_first, table)."""
+                a = build_assembly(read_order_file(work), names, sizes, DEFAULT_GAP, chromosomes_only=True)
+                rank, seq_first = ends.number_ranks(a, sizes)
+                got_rank, T, _counters = ctx.ends_resident(sizes, a.lift_seq, a.lift_off, a.lift_rev, a.seq_sizes, window, reach)
+                if not np.array_equal(got_rank, rank) or T.shape != (int((rank >= 0).sum()), reach, 4):
+                    sys.exit("ERROR... the library ranks the scaffolds differently from this tool. Exiting...")
+                return a, rank, seq_first, T
+
+            def anchor(a):
+                def count(target, first, n_table):
+                    got_first, table, counters = ctx.anchor_resident(sizes, a.lift_seq, a.lift_off, a.lift_rev, a.seq_sizes, target, window)
+                    if not np.array_equal(got_first, first) or table.shape != (n_table,):
+                        sys.exit("ERROR... the library numbers the unplaced scaffolds differently from this tool. Exiting...")
+                    return (), table, counters
+                return count
+
+            a, rank, seq_first, T = lay()
+            before, scaffolds_before = facing_links(T, seq_first), [len(comps) for comps in a.components]
+            flips, insertions_of = [0] * n_seq, [0] * n_seq
+            rounds, status, log = 0, None, []
+            flipping, placing, stalled = "flip" in kinds, "place" in kinds, False
+            while status is None:
+                while flipping:
+                    calls = ends.scaffold_calls(a, sizes, rank, seq_first, T, minPairs)
+                    accepted = accept_flips(calls, rank, a.lift_seq, reach)
+                    if not accepted:
+                        break
+                    if rounds >= maxRounds:
+                        status = "max_rounds"
+                        break
+                    as_it_was = _read(work)
+                    _write(work, ends.flipped_order_text(work, {names[s] for s in accepted}))
+                    turned = lay()
+                    if int(turned[3][:, :, ends.RL].sum()) <= int(T[:, :, ends.RL].sum()):
+                        _write(work, as_it_was)                    # F did not rise: the round is undone, flipping ends for good
+                        flipping, stalled = False, True
+                        break
+                    rounds += 1
+                    for s in accepted:
+                        flips[a.lift_seq[s]] += 1
+                        log.append((rounds, "flip", int(a.lift_seq[s]) + 1, names[s], calls[s][0], calls[s][1], "NA", "NA", "NA"))
+                    a, rank, seq_first, T = turned
+                if status is not None or not placing:
+                    break
+                first, n_table = place.number_blocks(a, sizes)
+                if not (first >= 0).any():
+                    break
+                candidates = np.flatnonzero(first >= 0).tolist()
+                _st, _c1, _c2, _links, chosen, Tg = place.both_passes(anchor(a), a, sizes, first, n_table, minPairs, minRatio, minSize)
+                _scores, gaps, _verdicts, winners = place.settle_gaps(Tg, chosen, candidates, reach, minPairs)
+                if not winners:
+                    break
+                if rounds >= maxRounds:
+                    status = "max_rounds"
+                    break
+                filled, _B = place.chromosome_members(a, sizes)
+                _write(work, place.placed_order_text(work, place.winner_insertions(winners, gaps, filled, names)))
+                rounds += 1
+                for (q, g), s in sorted(winners.items()):
+                    _g, o, m, runner_up, _verdict = gaps[s]
+                    members = filled[q]
+                    insertions_of[q] += 1
+                    log.append((rounds, "place", q + 1, names[s], names[members[g - 1]] if g else "start",
+                                names[members[g]] if g < len(members) else "end", "+-"[o], m, runner_up))
+                a, rank, seq_first, T = lay()
+            # the loop ran until nothing was left to do unless the limit ended it; a stalled run says which through `ended`
+            ended = "round_limit" if status else "nothing_left"
+            status = status or ("stalled" if stalled else "converged")
+            after = facing_links(T, seq_first)
+            rows = [(q + 1, scaffolds_before[q], len(a.components[q]), flips[q], insertions_of[q], before[q], after[q]) for q in range(n_seq)]
+            return stats, n_kept, n_intra, rounds, status, ended, log, rows
+        finally:
+            ctx.pairs_drop()
+
+    with tempfile.TemporaryDirectory() as tmp, paused_gc():
+        work = os.path.join(tmp, os.path.basename(orderFile))
+        _write(work, _read(orderFile))
+        try:
+            if context is None:
+                with _lib.Context(device) as ctx:
+                    stats, n_kept, n_intra, rounds, status, ended, log, rows = polish(ctx, work)
+            else:
+                stats, n_kept, n_intra, rounds, status, ended, log, rows = polish(context, work)
+        except _lib.HicmiError as exc:
+            sys.exit("ERROR... %s. Exiting..." % exc)
+        polished = _read(work)
+
+    header = ["moves=%s" % ",".join(kinds), "window=%d" % window, "reach=%d" % reach, "minPairs=%d" % minPairs, "minRatio=%g" % minRatio,
+              "minSize=%d" % minSize, "maxRounds=%d" % maxRounds]
+    header += ["%s=%d" % kv for kv in zip(STATS_COLUMNS, stats)]
+    header += ["pairs_kept=%d" % n_kept, "pairs_intra=%d" % n_intra, "rounds=%d" % rounds, "status=%s" % status, "ended=%s" % ended]
+    os.makedirs(outDir, exist_ok=True)
+    _write(outFile, polished)
+    with open(os.path.join(outDir, "polish.log"), "w") as fh:
+        fh.write("#" + "\t".join(LOG_COLUMNS) + "\n")
+        fh.write("".join("\t".join(str(x) for x in row) + "\n" for row in log))
+    with open(os.path.join(outDir, "polish_summary.tsv"), "w") as fh:
+        fh.write("#" + "\t".join(header) + "\n#" + "\t".join(SUMMARY_COLUMNS) + "\n")
+        fh.write("".join("\t".join(str(x) for x in row) + "\n" for row in rows))
+    print("POLISH: lines %d, pairs used %d, unknown scaffold %d, out of range %d" % stats
+          + "; pairs kept %d, intra %d" % (n_kept, n_intra))
+    print("POLISH: %s after %d round(s): %d flip(s), %d insertion(s), facing links %d -> %d" % (
+        status, rounds, sum(r[3] for r in rows), sum(r[4] for r in rows), sum(r[5] for r in rows), sum(r[6] for r in rows)))
+    return status, rounds, log
+
+
+def main(argv=None, context=None):
+    parser = argparse.ArgumentParser(description="Reads validPairFile once into a pair store on the GPU and repeats the flips of "
+                                                 "supportEnds and the insertions of placeUnplaced on an order file until "
+                                                 "neither has anything left to do.")
+    parser.add_argument("-config", help="Full file path to the config file", required=True, type=str)
+    parser.add_argument("-order", help="Order file (default: finalOrderingsFile when it exists, else chromosomeOrderFile)",
+                        type=str, default=None)
+    parser.add_argument("-moves", help="Kinds of move, a list of flip and place (default flip,place)", type=str, default="flip,place")
+    parser.add_argument("-window", help="End zone in bp (default %d)" % ends.DEFAULT_WINDOW, type=int, default=ends.DEFAULT_WINDOW)
+    parser.add_argument("-reach", help="Places two scaffolds may lie apart, 1 .. %d (default %d)" % (ends.MAX_REACH, ends.DEFAULT_REACH),
+                        type=int, default=ends.DEFAULT_REACH)
+    parser.add_argument("-minPairs", help="Links below which nothing is decided (default %d)" % ends.DEFAULT_MIN_PAIRS, type=int,
+                        default=ends.DEFAULT_MIN_PAIRS)
+    parser.add_argument("-minRatio", help="Link density of the best chromosome over the second best below which none is chosen "
+                                          "(default %g)" % place.DEFAULT_MIN_RATIO, type=float, default=place.DEFAULT_MIN_RATIO)
+    parser.add_argument("-minSize", help="Scaffolds below this size in bp get no chromosome (default %d)" % place.DEFAULT_MIN_SIZE,
+                        type=int, default=place.DEFAULT_MIN_SIZE)
+    parser.add_argument("-maxRounds", help="Rounds after which the loop stops (default %d)" % DEFAULT_MAX_ROUNDS, type=int,
+                        default=DEFAULT_MAX_ROUNDS)
+    parser.add_argument("-out", help="Directory of the polished order file, polish.log and polish_summary.tsv (default: "
+                                     "saveFilesDirectory/polished)", type=str, default=None)
+    parser.add_argument("-threads", help="Host threads of the parser (default 0: all)", type=int, default=0)
+    parser.add_argument("-device", help="GPU index (default 0)", type=int, default=0)
+    args = parser.parse_args(argv)
+    return runPipeline(args.config, args.order, args.moves, args.window, args.reach, args.minPairs, args.minRatio, args.minSize,
+                       args.maxRounds, args.out, threads=args.threads, device=args.device, context=context)
+
+
+if __name__ == "__main__":
+    main()

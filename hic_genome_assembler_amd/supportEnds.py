@@ -87,6 +87,19 @@ def scaffold_verdict(as_lies, flipped, alone, minPairs):
     return "supported" if as_lies > flipped else "flip"
 
 
+def scaffold_calls(asm, sizes, rank, seq_first, T, minPairs):
+    """{scaffold: (as_lies, flipped, verdict)} of every scaffold of the assembly that has a base: the decision the report
+    writes down and polishOrder acts on."""
+    calls = {}
+    for q, comps in enumerate(asm.components):
+        q0, q1 = int(seq_first[q]), int(seq_first[q + 1])
+        for s, _off, _orientation in comps:
+            if rank[s] >= 0:
+                as_lies, flipped = scaffold_figures(T, int(rank[s]), q0, q1)
+                calls[s] = (as_lies, flipped, scaffold_verdict(as_lies, flipped, q1 - q0 == 1, minPairs))
+    return calls
+
+
 def junction_figures(T, i):
     """(facing, left_flipped, right_flipped, both_flipped) of the junction between the ranks i and i + 1."""
     return [int(T[i, 0, k]) for k in (RL, LL, RR, LR)]
@@ -187,16 +200,15 @@ def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT
     header += ["%s=%d" % kv for kv in zip(STATS_COLUMNS, stats)] + ["%s=%d" % kv for kv in zip(COUNTER_COLUMNS, counters.tolist())]
     out = ["#" + "\t".join(header) + "\n", "#" + "\t".join(SCAFFOLD_COLUMNS) + "\n"]
     flips, junctions, verdicts = set(), [], {}
+    calls = scaffold_calls(asm, sizes, rank, seq_first, T, minPairs)
     for q, comps in enumerate(asm.components):
-        q0, q1 = int(seq_first[q]), int(seq_first[q + 1])
         out.append("### Chromosome grouping %d ###\n" % (q + 1))
         for s, _off, orientation in comps:
             L = int(sizes[s])
             if rank[s] < 0:                                                    # a scaffold without a base has no ends
                 cols = ["0", "0", "0", "0", "NA"]
             else:
-                as_lies, flipped = scaffold_figures(T, int(rank[s]), q0, q1)
-                verdict = scaffold_verdict(as_lies, flipped, q1 - q0 == 1, minPairs)
+                as_lies, flipped, verdict = calls[s]
                 cols = [str(x) for x in zone_sizes(L, window) + (as_lies, flipped)] + [verdict]
             verdicts[names[s]] = cols[-1]
             if cols[-1] == "flip":

@@ -667,6 +667,53 @@ int hicmi_anchor_file(const char *path, const char *names_blob, const int64_t *n
                       int threads, int64_t *stats5, uint64_t *table_out, uint64_t *counters6_out, int64_t *first_out,
                       int64_t *n_table_out);
 
+/* ---- the resident pair store: read pairs kept on the device between calls ----------------------------
+ * A pair is kept when scaf_a != scaf_b.  A pair with both ends on one scaffold s is intra: it is not stored and adds 1
+ * to intra[s] (unsigned 64-bit, one per scaffold).  The store is four device arrays, scaf_a int32, pos_a int64, scaf_b
+ * int32, pos_b int64, and holds the kept pairs in the order they were added: it is the boolean mask of the input.  No
+ * ordering counts an intra pair in a table of 9p or 9q: it is same (9p) or placed (9q) when its scaffold is placed and
+ * unlifted (9p) or unplaced (9q) when it is dropped, so the resident calls count the kept pairs and add the sums of
+ * intra[] over the placed and over the dropped scaffolds to these counters.
+ *
+ * hicmi_pairs_begin opens an empty store of HICMI_PAIRS_FIRST_PAIRS pairs (default 2^22, read per begin, 1 .. 2^31) and
+ * the zeroed intra array, all or nothing.  HICMI_EINVAL: the context already has a store, a negative size.  The
+ * context's matrix state and open map, span, ends and anchor builds are never touched by the hicmi_pairs_* calls.
+ * hicmi_pairs_add checks every index and position on the host like hicmi_map_add_pairs (HICMI_EINVAL, nothing uploaded,
+ * the store as before the call), uploads the arrays and appends the kept pairs.  The capacity at least doubles when it
+ * runs out, by device-to-device copy; an allocation that fails is HICMI_ENOMEM and, like a HIP error, gives the store
+ * up.  HICMI_PAIRS_PLAIN=1 in the environment, read at every call, takes one thread per pair, one atomic bump of the
+ * length per kept pair and one global atomic add per intra pair: the store is then the same multiset in another order.
+ * =0 and the default take the stable compaction (per-wave ballot, per-workgroup counts, a scan over the workgroups),
+ * which sums the intra pairs of a slice per scaffold in LDS first.  Everything computed from either store has the same
+ * bits.
+ * hicmi_pairs_file: begin and every pair of the file in one pass with the chunked parser as in hicmi_ends_file
+ * (HICMI_BUILDMAP_CHUNK_PAIRS, stats5 as there).  On any error no store is left and no output is written.
+ * hicmi_pairs_info: the pairs kept, the intra pairs in all and, unless intra_out is NULL, intra[n_scaf].
+ * hicmi_pairs_fetch downloads the store into arrays of n_kept elements.  hicmi_pairs_drop releases the store; the
+ * context releases it as well.  All three are HICMI_EINVAL without a store.
+ *
+ * hicmi_ends_resident and hicmi_anchor_resident: the numbering, the refusals, the table and the counters of
+ * hicmi_ends_file and hicmi_anchor_file with the store in place of the file, for any lift tables, as often as wanted;
+ * HICMI_ENDS_PLAIN and HICMI_ANCHOR_PLAIN are honoured.  The store is only read.  HICMI_EINVAL: no store, scaf_size or
+ * n_scaf other than the store's, an open ends (anchor) build on the context, which is left as it was.  Outputs are
+ * written only when everything is down. */
+int hicmi_pairs_begin(hicmi_ctx *ctx, const int64_t *scaf_size, int64_t n_scaf);
+int hicmi_pairs_add(hicmi_ctx *ctx, const int32_t *scaf_a, const int64_t *pos_a, const int32_t *scaf_b,
+                    const int64_t *pos_b, int64_t n);
+int hicmi_pairs_file(const char *path, const char *names_blob, const int64_t *name_off, int64_t n_names,
+                     const int64_t *scaf_size, hicmi_ctx *ctx, int threads, int64_t *stats5);
+int hicmi_pairs_info(hicmi_ctx *ctx, int64_t *n_kept_out, uint64_t *n_intra_out, uint64_t *intra_out);
+int hicmi_pairs_fetch(hicmi_ctx *ctx, int32_t *scaf_a, int64_t *pos_a, int32_t *scaf_b, int64_t *pos_b);
+int hicmi_pairs_drop(hicmi_ctx *ctx);
+int hicmi_ends_resident(hicmi_ctx *ctx, const int64_t *scaf_size, int64_t n_scaf, const int32_t *lift_seq,
+                        const int64_t *lift_off, const uint8_t *lift_rev, const int64_t *seq_size, int64_t n_seq,
+                        int64_t window, int64_t reach, uint64_t *table_out, uint64_t *counters6_out,
+                        int32_t *rank_out, int64_t *n_placed_out);
+int hicmi_anchor_resident(hicmi_ctx *ctx, const int64_t *scaf_size, int64_t n_scaf, const int32_t *lift_seq,
+                          const int64_t *lift_off, const uint8_t *lift_rev, const int64_t *seq_size, int64_t n_seq,
+                          const int32_t *target, int64_t window, uint64_t *table_out, uint64_t *counters6_out,
+                          int64_t *first_out, int64_t *n_table_out);
+
 /* ---- scaffolds cut into pieces: every read end moved from its scaffold to its piece -------------------
  * Scaffold s of the n_scaf scaffolds has the pieces piece_first[s] .. piece_first[s + 1] - 1 (int32, n_scaf + 1 entries,
  * ascending from 0 to n_piece), left to right; piece k starts after piece_start[k] bases of its parent (int64, 0 for a
