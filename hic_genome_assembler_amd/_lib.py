@@ -119,6 +119,8 @@ SIGNATURES = {
     "hicmi_ends_resident": (ctypes.c_int, [_vp, _vp, c_i64, _vp, _vp, _vp, _vp, c_i64, c_i64, c_i64, _vp, _vp, _vp, ctypes.POINTER(c_i64)]),
     "hicmi_anchor_resident": (ctypes.c_int, [_vp, _vp, c_i64, _vp, _vp, _vp, _vp, c_i64, _vp, c_i64, _vp, _vp, _vp,
                                              ctypes.POINTER(c_i64)]),
+    "hicmi_seats_resident": (ctypes.c_int, [_vp, _vp, c_i64, _vp, _vp, _vp, _vp, c_i64, c_i64, _vp, _vp, _vp,
+                                            ctypes.POINTER(c_i64)]),
     "hicmi_split_pairs": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, c_i64, _vp, c_i64, _vp, _vp, c_i64, _vp, _vp, _vp, _vp, _vp]),
     "hicmi_split_maps": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, _vp, _vp, c_i64, c_i64, _vp, _vp,
                                         ctypes.c_int, _vp, _vp]),
@@ -422,6 +424,7 @@ def ends_file(path, names, sizes, lift_seq, lift_off, lift_rev, seq_sizes, windo
 
 
 ANCHOR_MAX_TABLE = 1 << 27
+SEATS_MAX_TABLE = 1 << 27
 
 
 def anchor_blocks(sizes, lift_seq, n_seq, target=None):
@@ -448,6 +451,18 @@ def anchor_blocks(sizes, lift_seq, n_seq, target=None):
 def _anchor_table(n_table):
     """A zeroed table for the library to fill; one counter where it will refuse the build."""
     return np.zeros(n_table if 1 <= n_table <= ANCHOR_MAX_TABLE else 1, np.uint64)
+
+
+def seats_blocks(sizes, lift_seq, n_seq):
+    """(first int64[S], n_table) of a seat-support call: the placed scaffolds of size > 0 in index order, each
+    with a block of ``n_seq`` counters and four per placed scaffold of size > 0 of its own sequence; -1 for a dropped or empty
+    scaffold."""
+    size, seq = np.asarray(sizes, dtype=np.int64), np.asarray(lift_seq, dtype=np.int64)
+    placed = (seq >= 0) & (seq < int(n_seq)) & (size > 0)
+    members = np.bincount(seq[placed], minlength=int(n_seq)).astype(np.int64)
+    block = np.where(placed, int(n_seq) + 4 * members[np.where(placed, seq, 0)], 0)
+    ends = np.cumsum(block)
+    return np.where(placed, ends - block, -1).astype(np.int64), int(ends[-1]) if len(ends) else 0
 
 
 def _anchor_target(target, n_scaf):
@@ -894,6 +909,22 @@ class Context:
                                                ctypes.byref(n_table)))
         if n_table.value != len(table):
             raise RuntimeError("hicmi_anchor_resident has a table of %d counters, this binding %d" % (n_table.value, len(table)))
+        return first, table, counters
+
+    def seats_resident(self, sizes, lift_seq, lift_off, lift_rev, seq_sizes, window):
+        """Seat support from the resident pair store (hicmi_seats_resident): for every placed scaffold what
+        ``anchor_resident`` would count in both of its modes if that scaffold alone were dropped.  Returns (first int64[S],
+        table uint64[n_table], counters uint64[5] = (seated, middle, trans, same, unlifted)).  The store is only read."""
+        size, seq, off, rev, seq_size = _lift_tables(sizes, lift_seq, lift_off, lift_rev, seq_sizes)
+        counters = np.zeros(5, np.uint64)
+        first, n_table = np.zeros(len(size), np.int64), c_i64()
+        n_counters = seats_blocks(size, seq, len(seq_size))[1]
+        table = np.zeros(n_counters if 1 <= n_counters <= SEATS_MAX_TABLE else 1, np.uint64)
+        _check(self._lib.hicmi_seats_resident(self._h, _ptr(size), len(size), _ptr(seq), _ptr(off), _ptr(rev), _ptr(seq_size),
+                                              len(seq_size), int(window), _ptr(table), _ptr(counters), _ptr(first),
+                                              ctypes.byref(n_table)))
+        if n_table.value != len(table):
+            raise RuntimeError("hicmi_seats_resident has a table of %d counters, this binding %d" % (n_table.value, len(table)))
         return first, table, counters
 
     def split_pairs(self, scaf_a, pos_a, scaf_b, pos_b, sizes, piece_first, piece_start, into=None):

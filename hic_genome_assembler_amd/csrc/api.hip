@@ -232,6 +232,13 @@ struct hicmi_ctx {
     DevBuf<int64_t> d_anchor_first;
     DevBuf<int32_t> d_anchor_target;
     std::vector<int64_t> anchor_size;
+    // seat support (k_seats.hip), inside one hicmi_seats_resident call: the table of the blocks of all placed
+    // scaffolds with the five kinds behind it, the lift tables, the blocks ([first n_scaf][seq_first n_seq + 1]) and the
+    // ranks on the device; all four are released before the call returns
+    DevBuf<unsigned long long> seats_table;
+    DevBuf<unsigned char> d_seats_lift;
+    DevBuf<int64_t> d_seats_first;
+    DevBuf<int32_t> d_seats_rank;
     // the resident pair store (k_pairs.hip), between hicmi_pairs_begin / hicmi_pairs_file and hicmi_pairs_drop
     // (d_pairs_intra non-null: the context has a store): the kept pairs in four arrays of one capacity, pairs_len of
     // them in use, intra[n_scaf] with the device's copy of the length behind it, the offsets of a chunk's workgroups,

@@ -1,5 +1,5 @@
-// api_pairs.inc - the resident pair store (DESIGN.md 9r), a part of api.hip that is included there after the ends and the
-// anchor calls it builds on.  The store lives in buffers of its own: the context's matrix state and open map, span, ends
+// api_pairs.inc - the resident pair store (DESIGN.md 9r) and seat support on it (DESIGN.md 9s), a part of api.hip that is
+// included there after the ends and the anchor calls it builds on.  The store lives in buffers of its own: the context's matrix state and open map, span, ends
 // and anchor builds are never touched by hicmi_pairs_* (the staging of a chunk, d_map_chunk, holds nothing between calls).
 static void pairs_abandon(hicmi_ctx* c)
 {
@@ -269,5 +269,78 @@ int hicmi_anchor_resident(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf
     memcpy(counters6_out, counters, sizeof(counters));
     memcpy(first_out, blocks.first.data(), sizeof(int64_t) * (size_t)n_scaf);
     *n_table_out = blocks.n_table;
+    return HICMI_OK;
+}
+
+// ---- seat support (DESIGN.md 9s): every placed scaffold against the chromosomes and the gaps of its own, in one pass --------
+static void seats_abandon(hicmi_ctx* c)
+{
+    c->seats_table.reset(); c->d_seats_lift.reset(); c->d_seats_first.reset(); c->d_seats_rank.reset();
+}
+
+// HICMI_SEATS_PLAIN: "1" up to four atomic adds per pair, "0" the combining kernel, anything else the default; read per call
+constexpr bool kSeatsPlainByDefault = false;
+static bool seats_plain()
+{
+    const char* env = getenv("HICMI_SEATS_PLAIN");
+    if (env && !strcmp(env, "1")) return true;
+    if (env && !strcmp(env, "0")) return false;
+    return kSeatsPlainByDefault;
+}
+
+// What hicmi_anchor_resident would count in both of its modes if one placed scaffold alone were taken out of the ordering,
+// for every placed scaffold at once.  The buffers live for this call only and are closed on every path.
+int hicmi_seats_resident(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, const int32_t* lift_seq, const int64_t* lift_off,
+                         const uint8_t* lift_rev, const int64_t* seq_size, int64_t n_seq, int64_t window, uint64_t* table_out,
+                         uint64_t* counters5_out, int64_t* first_out, int64_t* n_table_out)
+{
+    if (!c || !table_out || !counters5_out || !first_out || !n_table_out) return fail(HICMI_EINVAL, "bad arguments");
+    int rc = pairs_resident_check(c, scaf_size, n_scaf, "hicmi_seats_resident");
+    if (rc) return rc;
+    if (window < 1) return fail(HICMI_EINVAL, "window %lld is below 1", (long long)window);
+    const LiftHost lift{lift_seq, lift_off, lift_rev, seq_size, n_seq};
+    rc = lift_check(scaf_size, n_scaf, lift);
+    if (rc) return rc;
+    std::vector<int32_t> rank((size_t)n_scaf);
+    std::vector<int64_t> blocks((size_t)(n_scaf + n_seq + 1));        // [first n_scaf][seq_first n_seq + 1], as on the device
+    int64_t* first = blocks.data();
+    int64_t* seq_first = first + n_scaf;
+    if (ends_number_ranks(scaf_size, n_scaf, lift_seq, lift_off, n_seq, 1, rank.data(), seq_first) < 0)
+        return fail(HICMI_EUNSUPPORTED, "more than %lld placed scaffolds", (long long)(ENDS_MAX_TABLE / 4));
+    const int64_t m = seats_number_blocks(scaf_size, n_scaf, lift_seq, n_seq, seq_first, first);
+    if (m < 0) return fail(HICMI_EUNSUPPORTED, "the placed scaffolds need a table of more than %lld counters", (long long)SEATS_MAX_TABLE);
+    if (m < 1) return fail(HICMI_EINVAL, "no scaffold with a base is placed");
+    HIPCHK(hipSetDevice(c->device));
+    struct OpenSeats { hicmi_ctx* c; ~OpenSeats() { seats_abandon(c); } } own{c};            // closed on every path
+    rc = ensure_all(c->seats_table, m + SEATS_COUNTERS, c->d_seats_first, n_scaf + n_seq + 1, c->d_seats_rank, n_scaf, c->d_seats_lift,
+                    21 * n_scaf);
+    if (rc) return rc;
+    LiftTables d_lift;
+    rc = upload(c, c->d_seats_first, blocks.data(), sizeof(int64_t) * blocks.size());
+    if (!rc) rc = upload(c, c->d_seats_rank, rank.data(), sizeof(int32_t) * (size_t)n_scaf);
+    if (!rc) rc = lift_upload(c, c->d_seats_lift, scaf_size, n_scaf, lift, &d_lift);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(c->seats_table, 0, sizeof(uint64_t) * (size_t)(m + SEATS_COUNTERS), c->stream));
+    HIPCHK(sync_stream(c));                                        // the tables have left the upload arena
+    std::vector<uint64_t> intra((size_t)n_scaf);
+    rc = download(c, intra.data(), c->d_pairs_intra, sizeof(uint64_t) * intra.size());
+    if (rc) return rc;
+    SeatsGrid grid;
+    grid.first = c->d_seats_first; grid.seq_first = c->d_seats_first + n_scaf; grid.rank = c->d_seats_rank; grid.window = window;
+    launch_seats_count(c->d_pairs_scaf_a, c->d_pairs_pos_a, c->d_pairs_scaf_b, c->d_pairs_pos_b, c->pairs_len, d_lift, grid, m,
+                       c->seats_table, c->seats_table + m, seats_plain(), c->stream);
+    HIPCHK(hipGetLastError());
+    // the table comes down into memory of the library's first: an error after it leaves every output as it was
+    std::vector<uint64_t> table((size_t)m);
+    uint64_t counters[SEATS_COUNTERS];
+    rc = download(c, counters, c->seats_table + m, sizeof(counters));
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(table.data(), c->seats_table, sizeof(uint64_t) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_stream(c));
+    seats_add_intra(intra.data(), lift_seq, n_scaf, counters);
+    memcpy(table_out, table.data(), sizeof(uint64_t) * table.size());
+    memcpy(counters5_out, counters, sizeof(counters));
+    memcpy(first_out, first, sizeof(int64_t) * (size_t)n_scaf);
+    *n_table_out = m;
     return HICMI_OK;
 }

@@ -11,6 +11,7 @@
 #include "ends.h"
 #include "anchor.h"
 #include "pairs.h"
+#include "seats.h"
 #include "split.h"
 
 namespace hicmi {
@@ -569,6 +570,17 @@ static constexpr int ANCHOR_PROBES = 8;        // a pair that finds no room with
 void launch_anchor_count(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
                          const LiftTables& lift, const AnchorGrid& grid, int64_t n_table, void* table, void* counters, bool plain,
                          hipStream_t s);
+
+// k_seats.hip: read-pair links of every placed scaffold with the chromosomes and with the end zones of the scaffolds of its
+// own chromosome (hicmi_seats_resident).  table: n_table unsigned 64-bit counters, the blocks of the placed
+// scaffolds (seats.h), up to four adds per pair; counters: the five kinds of pairs (SeatsKind); everything is device memory.
+static constexpr int SEATS_SLICE = 4096;       // pairs a workgroup of the combining k_seats_count brings together: up to four counters each
+static constexpr int SEATS_SLOT_BITS = 12;
+static constexpr int SEATS_SLOTS = 1 << SEATS_SLOT_BITS;     // slots of its table in LDS (8 bytes each, 32 KB); a slice can need four times as many
+static constexpr int SEATS_PROBES = 8;         // an add that finds no room within so many probes goes to global memory directly
+void launch_seats_count(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
+                        const LiftTables& lift, const SeatsGrid& grid, int64_t n_table, void* table, void* counters, bool plain,
+                        hipStream_t s);
 
 // k_pairs.hip: the resident pair store (hicmi_pairs_*).  A chunk of n pairs on the device is compacted into
 // the store: the kept pairs (pairs.h) are appended from *length on, which is advanced, and the others add to intra[n_scaf].

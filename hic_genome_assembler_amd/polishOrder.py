@@ -1,5 +1,5 @@
-"""Polishing an order file to a fixed point: flip, place, flip again, on read pairs kept on the device (DESIGN.md section
-9r).
+"""Polishing an order file to a fixed point: flip, relocate, place, flip again, on read pairs kept on the device (DESIGN.md
+sections 9r and 9s).
 
 supportEnds and placeUnplaced each make one pass over ``validPairFile`` and hand the iteration to the user: every flip is
 judged on the order file as it lies, one scaffold is inserted per gap, and after an insertion the neighbours' ends face
@@ -7,7 +7,7 @@ something new.  This tool reads the file once into the resident pair store of a 
 loop on it: every round counts the store again under new lift tables (hicmi_ends_resident, hicmi_anchor_resident) and takes
 the decisions of the two tools unchanged.
 
-    python -m hic_genome_assembler_amd.polishOrder -config my_config.txt [-order FILE] [-moves flip,place] [-window 50000] \\
+    python -m hic_genome_assembler_amd.polishOrder -config my_config.txt [-order FILE] [-moves flip,place[,relocate]] [-window 50000] \\
            [-reach 2] [-minPairs 4] [-minRatio 2] [-minSize 0] [-maxRounds 1000] [-out DIR] [-threads 0] [-device 0]
 
 Flip rounds run until no scaffold says ``flip``.  A round takes the scaffolds supportEnds calls ``flip``, by
@@ -19,6 +19,11 @@ loop ends when a place round inserts nothing (``converged``) or ``-maxRounds`` r
 something to do (``max_rounds``).  ``stalled`` stays the status of a run whose flipping was cut short, whatever the place
 rounds did afterwards; ``ended`` in the summary says whether the loop then ran until nothing was left (``nothing_left``) or
 into the limit (``round_limit``).  The input order file is never changed.
+
+With ``relocate`` among the moves (it is not by default) one relocate round follows the flip rounds: the ``-moved`` choice of
+supportSeats - per chromosome the placed scaffold whose best seat lies in another gap, by gain - is applied, and the flip
+rounds start again; the place round runs when a relocate round has nothing to apply.  A relocate round after which ``F`` did
+not rise strictly is undone and relocating ends for good (``stalled``).
 """
 from __future__ import annotations
 
@@ -32,14 +37,16 @@ import numpy as np
 from . import _lib
 from . import placeUnplaced as place
 from . import supportEnds as ends
+from . import supportSeats as seats
 from .assembledMap import DEFAULT_GAP, build_assembly, read_order_file
 from .buildMap import STATS_COLUMNS, check_valid_pair_file
 from .hostio import paused_gc, read_scaffold_sizes
 
 DEFAULT_MAX_ROUNDS = 1000
-MOVES = ("flip", "place")
+MOVES = ("flip", "place", "relocate")
 LOG_COLUMNS = ("round", "kind", "chromosome", "scaffold", "as_lies|left", "flipped|right", "orientation", "score", "runner_up")
 SUMMARY_COLUMNS = ("chromosome", "scaffolds_before", "scaffolds_after", "flips", "insertions", "facing_before", "facing_after")
+RELOCATE_COLUMN = "relocations"                  # the eighth column of the summary when relocate is among the moves
 
 
 def facing_links(T, seq_first):
@@ -72,7 +79,8 @@ def runPipeline(configFile, orderFile=None, moves="flip,place", window=ends.DEFA
                 minPairs=ends.DEFAULT_MIN_PAIRS, minRatio=place.DEFAULT_MIN_RATIO, minSize=place.DEFAULT_MIN_SIZE,
                 maxRounds=DEFAULT_MAX_ROUNDS, outDir=None, threads=0, device=0, context=None):
     """``context``: a context of the caller's that has ``pairs_file``, ``pairs_info``, ``ends_resident`` and
-    ``anchor_resident``; None: a context of its own on ``device``.  Returns (status, rounds, log rows)."""
+    ``anchor_resident``, and ``seats_resident`` when relocate is among the moves; None: a context of its own on ``device``.
+    Returns (status, rounds, log rows)."""
     from . import run_hicAssembler as driver
     v = driver.readConfigFileToVariables(configFile)
     if outDir is None:
@@ -118,6 +126,14 @@ def runPipeline(configFile, orderFile=None, moves="flip,place", window=ends.DEFA
             raise ValueError("%d unplaced scaffolds against %d chromosomes need a table of %d counters, more than the %d a build can "
                              "have: take the smallest scaffolds out of hicProScaffSizeFile"
                              % (int((first1 >= 0).sum()), len(asm.components), n1, place.MAX_TABLE))
+        if "relocate" in kinds:
+            # the table of the last round: a place round can at worst give every unplaced scaffold to the largest chromosome
+            counts = sorted(sum(1 for s, _off, _o in comps if sizes[s] > 0) for comps in asm.components)
+            counts[-1] += n_most - n_placed
+            n_seats = seats.table_size(len(asm.components), counts)
+            if n_seats > seats.MAX_TABLE:
+                raise ValueError("relocating %d placed scaffolds in %d chromosomes needs a table of %d counters, more than the %d a "
+                                 "call can have" % (n_most, len(asm.components), n_seats, seats.MAX_TABLE))
     except (OSError, ValueError) as exc:
         sys.exit("ERROR... %s. Exiting..." % exc)
     n_seq = len(asm.components)
@@ -148,9 +164,9 @@ def runPipeline(configFile, orderFile=None, moves="flip,place", window=ends.DEFA
 
             a, rank, seq_first, T = lay()
             before, scaffolds_before = facing_links(T, seq_first), [len(comps) for comps in a.components]
-            flips, insertions_of = [0] * n_seq, [0] * n_seq
+            flips, insertions_of, relocations = [0] * n_seq, [0] * n_seq, [0] * n_seq
             rounds, status, log = 0, None, []
-            flipping, placing, stalled = "flip" in kinds, "place" in kinds, False
+            flipping, placing, relocating, stalled = "flip" in kinds, "place" in kinds, "relocate" in kinds, False
             while status is None:
                 while flipping:
                     calls = ends.scaffold_calls(a, sizes, rank, seq_first, T, minPairs)
@@ -172,7 +188,37 @@ def runPipeline(configFile, orderFile=None, moves="flip,place", window=ends.DEFA
                         flips[a.lift_seq[s]] += 1
                         log.append((rounds, "flip", int(a.lift_seq[s]) + 1, names[s], calls[s][0], calls[s][1], "NA", "NA", "NA"))
                     a, rank, seq_first, T = turned
-                if status is not None or not placing:
+                if status is not None:
+                    break
+                if relocating:
+                    first, n_table = seats.number_blocks(a, sizes)
+                    got_first, table, _counters = ctx.seats_resident(sizes, a.lift_seq, a.lift_off, a.lift_rev, a.seq_sizes, window)
+                    if not np.array_equal(got_first, first) or table.shape != (n_table,):
+                        sys.exit("ERROR... the library numbers the placed scaffolds differently from this tool. Exiting...")
+                    calls = seats.seat_calls(a, sizes, first, table, reach, minPairs, minRatio)
+                    moves = seats.chosen_moves(a, sizes, calls)
+                    if moves:
+                        if rounds >= maxRounds:
+                            status = "max_rounds"
+                            break
+                        as_it_was = _read(work)
+                        _write(work, seats.moved_order_text(work, seats.move_targets(a, sizes, calls, moves, names)))
+                        moved = lay()
+                        if int(moved[3][:, :, ends.RL].sum()) <= int(T[:, :, ends.RL].sum()):
+                            _write(work, as_it_was)                # F did not rise: the round is undone, relocating ends for good
+                            relocating, stalled = False, True
+                        else:
+                            rounds += 1
+                            filled, _B = place.chromosome_members(a, sizes)
+                            for q, s in sorted(moves.items()):
+                                g, o, m, runner_up, _verdict = calls[s]["gap"]
+                                others = [t for t in filled[q] if t != s]
+                                relocations[q] += 1
+                                log.append((rounds, "relocate", q + 1, names[s], names[others[g - 1]] if g else "start",
+                                            names[others[g]] if g < len(others) else "end", "+-"[o], m, runner_up))
+                            a, rank, seq_first, T = moved
+                            continue                               # back to the flip rounds
+                if not placing:
                     break
                 first, n_table = place.number_blocks(a, sizes)
                 if not (first >= 0).any():
@@ -200,6 +246,8 @@ def runPipeline(configFile, orderFile=None, moves="flip,place", window=ends.DEFA
             status = status or ("stalled" if stalled else "converged")
             after = facing_links(T, seq_first)
             rows = [(q + 1, scaffolds_before[q], len(a.components[q]), flips[q], insertions_of[q], before[q], after[q]) for q in range(n_seq)]
+            if "relocate" in kinds:
+                rows = [row + (relocations[q],) for q, row in enumerate(rows)]
             return stats, n_kept, n_intra, rounds, status, ended, log, rows
         finally:
             ctx.pairs_drop()
@@ -227,23 +275,24 @@ def runPipeline(configFile, orderFile=None, moves="flip,place", window=ends.DEFA
         fh.write("#" + "\t".join(LOG_COLUMNS) + "\n")
         fh.write("".join("\t".join(str(x) for x in row) + "\n" for row in log))
     with open(os.path.join(outDir, "polish_summary.tsv"), "w") as fh:
-        fh.write("#" + "\t".join(header) + "\n#" + "\t".join(SUMMARY_COLUMNS) + "\n")
+        fh.write("#" + "\t".join(header) + "\n#" + "\t".join(SUMMARY_COLUMNS + ((RELOCATE_COLUMN,) if "relocate" in kinds else ())) + "\n")
         fh.write("".join("\t".join(str(x) for x in row) + "\n" for row in rows))
     print("POLISH: lines %d, pairs used %d, unknown scaffold %d, out of range %d" % stats
           + "; pairs kept %d, intra %d" % (n_kept, n_intra))
-    print("POLISH: %s after %d round(s): %d flip(s), %d insertion(s), facing links %d -> %d" % (
-        status, rounds, sum(r[3] for r in rows), sum(r[4] for r in rows), sum(r[5] for r in rows), sum(r[6] for r in rows)))
+    print("POLISH: %s after %d round(s): %d flip(s), %d insertion(s)%s, facing links %d -> %d" % (
+        status, rounds, sum(r[3] for r in rows), sum(r[4] for r in rows),
+        ", %d relocation(s)" % sum(r[7] for r in rows) if "relocate" in kinds else "", sum(r[5] for r in rows), sum(r[6] for r in rows)))
     return status, rounds, log
 
 
 def main(argv=None, context=None):
     parser = argparse.ArgumentParser(description="Reads validPairFile once into a pair store on the GPU and repeats the flips of "
-                                                 "supportEnds and the insertions of placeUnplaced on an order file until "
-                                                 "neither has anything left to do.")
+                                                 "supportEnds, the insertions of placeUnplaced and, when asked for, the moves of "
+                                                 "supportSeats on an order file until none has anything left to do.")
     parser.add_argument("-config", help="Full file path to the config file", required=True, type=str)
     parser.add_argument("-order", help="Order file (default: finalOrderingsFile when it exists, else chromosomeOrderFile)",
                         type=str, default=None)
-    parser.add_argument("-moves", help="Kinds of move, a list of flip and place (default flip,place)", type=str, default="flip,place")
+    parser.add_argument("-moves", help="Kinds of move, a list of flip, place and relocate (default flip,place)", type=str, default="flip,place")
     parser.add_argument("-window", help="End zone in bp (default %d)" % ends.DEFAULT_WINDOW, type=int, default=ends.DEFAULT_WINDOW)
     parser.add_argument("-reach", help="Places two scaffolds may lie apart, 1 .. %d (default %d)" % (ends.MAX_REACH, ends.DEFAULT_REACH),
                         type=int, default=ends.DEFAULT_REACH)

@@ -714,6 +714,33 @@ int hicmi_anchor_resident(hicmi_ctx *ctx, const int64_t *scaf_size, int64_t n_sc
                           const int32_t *target, int64_t window, uint64_t *table_out, uint64_t *counters6_out,
                           int64_t *first_out, int64_t *n_table_out);
 
+/* ---- seat support: every placed scaffold taken out and re-placed from the resident pair store --------
+ * The leave-one-out relocation test of SALSA (Ghurye et al. 2017, BMC Genomics 18:527), 3D-DNA (Dudchenko et al. 2017,
+ * Science 356:92) and YaHS (Zhou et al. 2023, Bioinformatics 39:btac808) on the read pairs themselves.  The seat of a
+ * scaffold is its chromosome, gap and orientation.  rank and seq_first are those of hicmi_ends_begin at reach 1.  A
+ * placed scaffold c with a base, in sequence q with S_q such scaffolds, owns a block of n_seq + 4 S_q unsigned 64-bit
+ * counters; the blocks lie in scaffold-index order and first_out[c] is the start of c's block, -1 for a dropped or empty
+ * scaffold.  first[c] + q' counts the kept pairs between c and any other placed scaffold of sequence q'.
+ * first[c] + n_seq + k * 4 + half * 2 + zone counts the pairs between a half of c (0: the first len - len / 2 bases in
+ * c's own + coordinates) and an end zone (0 left, 1 right, as it lies, of `window` bases as in 9p) of the scaffold of
+ * local rank k in c's own sequence; the row k = rank[c] - seq_first[q] exists and stays zero.  With that row deleted the
+ * two parts of c's block are what hicmi_anchor_resident counts in sequence mode and in rank mode with target[c] = q on
+ * the lift tables with c alone dropped.  A pair between two placed scaffolds adds to the blocks of both.
+ * counters5_out: seated (at least one gap counter), middle (one sequence, both far ends in the middle), trans (two
+ * sequences), same (one scaffold), unlifted (an end on a dropped scaffold); the intra pairs the store does not keep are
+ * added as same or unlifted from intra[].  Their sum is the number of pairs.
+ * HICMI_SEATS_PLAIN=1 in the environment, read at every call, takes one thread per pair and up to four global atomic
+ * adds; =0 takes the combining kernel (equal counters of a slice summed in LDS first).  Both give the same bits, as do
+ * every store order and mate order.  HICMI_EINVAL: no store, scaf_size or n_scaf other than the store's, window < 1,
+ * tables that hicmi_map_begin_lifted refuses, no placed scaffold with a base.  HICMI_EUNSUPPORTED: a table of more than
+ * 2^27 counters.  The store is only read; the context's matrix state and open map, span, ends and anchor builds are
+ * never touched.  table_out has room for n_table counters (the caller numbers the blocks the same way first).  Outputs
+ * are written only when everything is down. */
+int hicmi_seats_resident(hicmi_ctx *ctx, const int64_t *scaf_size, int64_t n_scaf, const int32_t *lift_seq,
+                         const int64_t *lift_off, const uint8_t *lift_rev, const int64_t *seq_size, int64_t n_seq,
+                         int64_t window, uint64_t *table_out, uint64_t *counters5_out, int64_t *first_out,
+                         int64_t *n_table_out);
+
 /* ---- scaffolds cut into pieces: every read end moved from its scaffold to its piece -------------------
  * Scaffold s of the n_scaf scaffolds has the pieces piece_first[s] .. piece_first[s + 1] - 1 (int32, n_scaf + 1 entries,
  * ascending from 0 to n_piece), left to right; piece k starts after piece_start[k] bases of its parent (int64, 0 for a
