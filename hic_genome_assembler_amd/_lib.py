@@ -121,6 +121,9 @@ SIGNATURES = {
                                              ctypes.POINTER(c_i64)]),
     "hicmi_seats_resident": (ctypes.c_int, [_vp, _vp, c_i64, _vp, _vp, _vp, _vp, c_i64, c_i64, _vp, _vp, _vp,
                                             ctypes.POINTER(c_i64)]),
+    "hicmi_links_resident": (ctypes.c_int, [_vp, _vp, c_i64, c_i64, ctypes.POINTER(c_i64), _vp]),
+    "hicmi_links_fetch": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "hicmi_links_info": (ctypes.c_int, [_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_double)]),
     "hicmi_split_pairs": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, c_i64, _vp, c_i64, _vp, _vp, c_i64, _vp, _vp, _vp, _vp, _vp]),
     "hicmi_split_maps": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, _vp, _vp, c_i64, c_i64, _vp, _vp,
                                         ctypes.c_int, _vp, _vp]),
@@ -425,6 +428,21 @@ def ends_file(path, names, sizes, lift_seq, lift_off, lift_rev, seq_sizes, windo
 
 ANCHOR_MAX_TABLE = 1 << 27
 SEATS_MAX_TABLE = 1 << 27
+# the end-link graph: scaffolds of a call, slots of its table, and the sizes of the combining kernel's slice
+# and table in LDS (csrc/hicmi_internal.h), which the tests place their edge cases at
+LINKS_MAX_SCAF, LINKS_MIN_SLOTS, LINKS_MAX_SLOTS = 1 << 30, 1024, 1 << 31
+LINKS_SLICE, LINKS_SLOTS = 8192, 2048
+LINKS_COLUMNS = ("left_left", "left_right", "right_left", "right_right", "other")
+
+
+def links_capacity(n_kept, n_scaf):
+    """Slots of the find-or-insert table of a ``links_resident`` call: the smallest power of two that is at least 1,024 and
+    at least twice min(n_kept, 5 n_scaf (n_scaf - 1) / 2)."""
+    most = min(int(n_kept), 5 * int(n_scaf) * (int(n_scaf) - 1) // 2) if n_kept > 0 and n_scaf > 1 else 0
+    cap = LINKS_MIN_SLOTS
+    while cap < 2 * most:
+        cap *= 2
+    return cap
 
 
 def anchor_blocks(sizes, lift_seq, n_seq, target=None):
@@ -926,6 +944,26 @@ class Context:
         if n_table.value != len(table):
             raise RuntimeError("hicmi_seats_resident has a table of %d counters, this binding %d" % (n_table.value, len(table)))
         return first, table, counters
+
+    def links_resident(self, sizes, window):
+        """The end-link graph of all scaffolds from the resident pair store (hicmi_links_resident and hicmi_links_fetch,
+        DESIGN.md 9t): one row per scaffold pair with at least one kept pair, sorted by (lo, hi).  Returns (lo int32[E],
+        hi int32[E], counts uint64[E, 5] in the order LL, LR, RL, RR, OTHER - first letter: the end zone on ``lo`` -
+        counters uint64[2] = (linked, middle)).  No order file takes part; the store is only read."""
+        size = np.ascontiguousarray(sizes, dtype=np.int64)
+        counters, n_rows = np.zeros(2, np.uint64), c_i64()
+        _check(self._lib.hicmi_links_resident(self._h, _ptr(size), len(size), int(window), ctypes.byref(n_rows), _ptr(counters)))
+        lo, hi = np.zeros(n_rows.value, np.int32), np.zeros(n_rows.value, np.int32)
+        counts = np.zeros((n_rows.value, 5), np.uint64)
+        _check(self._lib.hicmi_links_fetch(self._h, _ptr(lo), _ptr(hi), _ptr(counts)))
+        return lo, hi, counts, counters
+
+    def links_info(self):
+        """(records, slots, sort_ms) of the last ``links_resident`` call (hicmi_links_info): the used slots of its table, the
+        slots the table had, and the milliseconds the host took to sort the records."""
+        n_rec, n_slots, ms = c_i64(), c_i64(), ctypes.c_double()
+        _check(self._lib.hicmi_links_info(self._h, ctypes.byref(n_rec), ctypes.byref(n_slots), ctypes.byref(ms)))
+        return n_rec.value, n_slots.value, ms.value
 
     def split_pairs(self, scaf_a, pos_a, scaf_b, pos_b, sizes, piece_first, piece_start, into=None):
         """The pairs (scaffold index, 1-based position) x 2 moved to the pieces the scaffolds are cut into

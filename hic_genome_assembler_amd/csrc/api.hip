@@ -239,6 +239,16 @@ struct hicmi_ctx {
     DevBuf<unsigned char> d_seats_lift;
     DevBuf<int64_t> d_seats_first;
     DevBuf<int32_t> d_seats_rank;
+    // the end-link graph (k_links.hip), between hicmi_links_resident and hicmi_pairs_drop: the find-or-insert
+    // table ([keys cap][counts cap][LINKS_EXTRAS]), the compacted (key, count) records ([keys][counts]) and the scaffold
+    // sizes on the device, and the rows of the last call on the host, sorted by (lo, hi); links_ready: there are rows to fetch
+    DevBuf<unsigned long long> d_links_table, d_links_recs;
+    DevBuf<int64_t> d_links_size;
+    std::vector<int32_t> links_lo, links_hi;
+    std::vector<uint64_t> links_counts;
+    bool links_ready = false;
+    int64_t links_records = 0, links_slots = 0;       // of the last call: used slots, slots of its table
+    double links_sort_ms = 0.0;                       // and the host's sort of the records, in milliseconds
     // the resident pair store (k_pairs.hip), between hicmi_pairs_begin / hicmi_pairs_file and hicmi_pairs_drop
     // (d_pairs_intra non-null: the context has a store): the kept pairs in four arrays of one capacity, pairs_len of
     // them in use, intra[n_scaf] with the device's copy of the length behind it, the offsets of a chunk's workgroups,

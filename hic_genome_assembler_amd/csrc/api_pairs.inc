@@ -1,8 +1,17 @@
-// api_pairs.inc - the resident pair store (DESIGN.md 9r) and seat support on it (DESIGN.md 9s), a part of api.hip that is
+// api_pairs.inc - the resident pair store (DESIGN.md 9r), seat support (9s) and the end-link graph (9t) on it, a part of api.hip that is
 // included there after the ends and the anchor calls it builds on.  The store lives in buffers of its own: the context's matrix state and open map, span, ends
 // and anchor builds are never touched by hicmi_pairs_* (the staging of a chunk, d_map_chunk, holds nothing between calls).
+// the rows of hicmi_links_resident (DESIGN.md 9t) belong to the store they were counted from and go with it
+static void links_abandon(hicmi_ctx* c)
+{
+    c->d_links_table.reset(); c->d_links_recs.reset(); c->d_links_size.reset();
+    c->links_lo.clear(); c->links_hi.clear(); c->links_counts.clear();
+    c->links_ready = false;
+}
+
 static void pairs_abandon(hicmi_ctx* c)
 {
+    links_abandon(c);
     c->d_pairs_scaf_a.reset(); c->d_pairs_pos_a.reset(); c->d_pairs_scaf_b.reset(); c->d_pairs_pos_b.reset();
     c->d_pairs_intra.reset(); c->d_pairs_work.reset();
     c->pairs_size.clear();
@@ -107,6 +116,7 @@ int hicmi_pairs_add(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos_a, c
     int rc_pairs = check_pairs(scaf_a, pos_a, scaf_b, pos_b, n, c->pairs_size.data(), (int64_t)c->pairs_size.size(), nullptr, nullptr);
     if (rc_pairs) return rc_pairs;
     if (n == 0) return HICMI_OK;
+    c->links_ready = false;                                        // rows counted before these pairs are not the store's any more
     HIPCHK(hipSetDevice(c->device));
     // a HIP error from here on gives the store up: what was kept so far cannot be told
     int rc = ensure(c->d_map_chunk, 24 * n);
@@ -342,5 +352,105 @@ int hicmi_seats_resident(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf,
     memcpy(counters5_out, counters, sizeof(counters));
     memcpy(first_out, first, sizeof(int64_t) * (size_t)n_scaf);
     *n_table_out = m;
+    return HICMI_OK;
+}
+
+// ---- the end-link graph of all scaffolds (DESIGN.md 9t): which scaffold ends are linked to which, before any ordering ------
+// HICMI_LINKS_PLAIN: "1" one find-or-insert per pair, "0" the combining kernel, anything else the default; read per call
+constexpr bool kLinksPlainByDefault = false;
+static bool links_plain()
+{
+    const char* env = getenv("HICMI_LINKS_PLAIN");
+    if (env && !strcmp(env, "1")) return true;
+    if (env && !strcmp(env, "0")) return false;
+    return kLinksPlainByDefault;
+}
+
+// One pass over the store into a find-or-insert table sized for every key the call can see, the used slots compacted on
+// the device, sorted by key on the host (a radix sort, links.h: the records are few next to the pairs, DESIGN.md 9t) and merged into
+// one row per scaffold pair.  The rows stay on the context until the store goes; the device buffers stay with them, so a
+// second call on the same store allocates nothing.
+int hicmi_links_resident(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, int64_t window, int64_t* n_rows_out,
+                         uint64_t* counters2_out)
+{
+    if (!c || !n_rows_out || !counters2_out) return fail(HICMI_EINVAL, "bad arguments");
+    if (n_scaf > LINKS_MAX_SCAF) return fail(HICMI_EUNSUPPORTED, "%lld scaffolds, more than the %lld a link key has room for",
+                                             (long long)n_scaf, (long long)LINKS_MAX_SCAF);
+    int rc = pairs_resident_check(c, scaf_size, n_scaf, "hicmi_links_resident");
+    if (rc) return rc;
+    if (window < 1) return fail(HICMI_EINVAL, "window %lld is below 1", (long long)window);
+    LinksTable T;
+    T.cap = links_capacity(c->pairs_len, n_scaf, &T.bits);
+    if (T.cap > LINKS_MAX_SLOTS)
+        return fail(HICMI_EUNSUPPORTED, "the link table needs %lld slots, more than the %lld a call can have", (long long)T.cap,
+                    (long long)LINKS_MAX_SLOTS);
+    const int64_t most = links_most_keys(c->pairs_len, n_scaf);
+    HIPCHK(hipSetDevice(c->device));
+    rc = ensure_all(c->d_links_table, 2 * T.cap + LINKS_EXTRAS, c->d_links_recs, 2 * most, c->d_links_size, n_scaf);
+    if (rc) { links_abandon(c); return rc; }
+    T.keys = c->d_links_table; T.counts = T.keys + T.cap; T.extras = T.counts + T.cap;
+    unsigned long long* rec_key = c->d_links_recs;
+    unsigned long long* rec_cnt = rec_key + most;
+    rc = upload(c, c->d_links_size, scaf_size, sizeof(int64_t) * (size_t)n_scaf);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(T.keys, 0xFF, sizeof(uint64_t) * (size_t)T.cap, c->stream));
+    HIPCHK(hipMemsetAsync(T.counts, 0, sizeof(uint64_t) * (size_t)(T.cap + LINKS_EXTRAS), c->stream));
+    if (c->pairs_len > 0) {
+        launch_links_count(c->d_pairs_scaf_a, c->d_pairs_pos_a, c->d_pairs_scaf_b, c->d_pairs_pos_b, c->pairs_len, c->d_links_size, n_scaf,
+                           window, T, links_plain(), c->stream);
+        HIPCHK(hipGetLastError());
+        launch_links_compact(T, rec_key, rec_cnt, most, c->stream);
+        HIPCHK(hipGetLastError());
+    }
+    uint64_t extras[LINKS_EXTRAS];
+    rc = download(c, extras, T.extras, sizeof(extras));           // synchronises: the sizes have left the upload arena
+    if (rc) return rc;
+    if (extras[LINKS_FLAG])
+        return fail(HICMI_EHIP, "the link table of %lld slots ran full (flag %llu): the store holds pairs the call did not expect",
+                    (long long)T.cap, (unsigned long long)extras[LINKS_FLAG]);
+    const int64_t n_rec = (int64_t)extras[LINKS_RECORDS];
+    if (n_rec < 0 || n_rec > most) return fail(HICMI_EHIP, "%lld link records where %lld fit", (long long)n_rec, (long long)most);
+    // the records come down into memory of the library's first: an error after it leaves every output as it was
+    std::vector<uint64_t> key((size_t)n_rec), count((size_t)n_rec);
+    if (n_rec) {
+        HIPCHK(hipMemcpyAsync(key.data(), rec_key, sizeof(uint64_t) * (size_t)n_rec, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(count.data(), rec_cnt, sizeof(uint64_t) * (size_t)n_rec, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(sync_stream(c));
+    }
+    // the slot order is the race's: sorted by key on the host, timed for hicmi_links_info
+    const auto t0 = std::chrono::steady_clock::now();
+    links_sort_records(key.data(), count.data(), n_rec);
+    const double sort_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    std::vector<int32_t> lo((size_t)n_rec), hi((size_t)n_rec);
+    std::vector<uint64_t> counts5((size_t)n_rec * LINKS_COMBOS);
+    const int64_t n_rows = links_merge_rows(key.data(), count.data(), n_rec, lo.data(), hi.data(), counts5.data());
+    lo.resize((size_t)n_rows); hi.resize((size_t)n_rows); counts5.resize((size_t)n_rows * LINKS_COMBOS);
+    c->links_lo = std::move(lo); c->links_hi = std::move(hi); c->links_counts = std::move(counts5);
+    c->links_ready = true;
+    c->links_records = n_rec; c->links_slots = T.cap; c->links_sort_ms = sort_ms;
+    *n_rows_out = n_rows;
+    counters2_out[LINKS_LINKED] = extras[LINKS_LINKED];
+    counters2_out[LINKS_MIDDLE] = extras[LINKS_MIDDLE];
+    return HICMI_OK;
+}
+
+int hicmi_links_fetch(hicmi_ctx* c, int32_t* lo, int32_t* hi, uint64_t* counts5)
+{
+    if (!c) return fail(HICMI_EINVAL, "bad arguments");
+    if (!c->links_ready) return fail(HICMI_EINVAL, "hicmi_links_fetch before hicmi_links_resident");
+    const size_t n = c->links_lo.size();
+    if (n == 0) return HICMI_OK;
+    if (!lo || !hi || !counts5) return fail(HICMI_EINVAL, "bad arguments");
+    memcpy(lo, c->links_lo.data(), sizeof(int32_t) * n);
+    memcpy(hi, c->links_hi.data(), sizeof(int32_t) * n);
+    memcpy(counts5, c->links_counts.data(), sizeof(uint64_t) * n * LINKS_COMBOS);
+    return HICMI_OK;
+}
+
+int hicmi_links_info(hicmi_ctx* c, int64_t* n_records_out, int64_t* n_slots_out, double* sort_ms_out)
+{
+    if (!c || !n_records_out || !n_slots_out || !sort_ms_out) return fail(HICMI_EINVAL, "bad arguments");
+    if (!c->links_ready) return fail(HICMI_EINVAL, "hicmi_links_info before hicmi_links_resident");
+    *n_records_out = c->links_records; *n_slots_out = c->links_slots; *sort_ms_out = c->links_sort_ms;
     return HICMI_OK;
 }

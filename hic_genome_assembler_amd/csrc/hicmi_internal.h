@@ -12,6 +12,7 @@
 #include "anchor.h"
 #include "pairs.h"
 #include "seats.h"
+#include "links.h"
 #include "split.h"
 
 namespace hicmi {
@@ -581,6 +582,29 @@ static constexpr int SEATS_PROBES = 8;         // an add that finds no room with
 void launch_seats_count(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
                         const LiftTables& lift, const SeatsGrid& grid, int64_t n_table, void* table, void* counters, bool plain,
                         hipStream_t s);
+
+// k_links.hip: the end-link graph of all scaffolds from the resident pair store (hicmi_links_resident).  The
+// find-or-insert table: keys (LINKS_EMPTY: free) and counts of cap = 2^bits slots, and behind them LINKS_EXTRAS unsigned
+// 64-bit integers: the two kinds of pairs (LinksKind), a flag (bit 0: an insert found the table full, bit 1: a record
+// found no room) and the number of records k_links_compact wrote; everything is device memory, zeroed by the caller but for
+// the keys, which start out as LINKS_EMPTY.
+static constexpr int LINKS_SLICE = 8192;       // pairs a workgroup of the combining k_links_count brings together
+static constexpr int LINKS_SLOT_BITS = 11;
+static constexpr int LINKS_SLOTS = 1 << LINKS_SLOT_BITS;     // slots of its table in LDS (12 bytes each, 24 KB)
+static constexpr int LINKS_PROBES = 8;         // an add that finds no room within so many probes goes to the global table directly
+static constexpr int LINKS_COMPACT_SLICE = 4096;   // slots a workgroup of k_links_compact takes: one bump of the record count each
+static constexpr int LINKS_FLAG = LINKS_COUNTERS, LINKS_RECORDS = LINKS_COUNTERS + 1, LINKS_EXTRAS = LINKS_COUNTERS + 2;
+struct LinksTable {
+    unsigned long long* keys = nullptr;
+    unsigned long long* counts = nullptr;
+    unsigned long long* extras = nullptr;
+    int64_t cap = 0;
+    int bits = 0;
+};
+void launch_links_count(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
+                        const int64_t* scaf_size, int64_t n_scaf, int64_t window, const LinksTable& table, bool plain, hipStream_t s);
+// the used slots as rec_cap (key, count) records at the most, in no order
+void launch_links_compact(const LinksTable& table, void* rec_key, void* rec_cnt, int64_t rec_cap, hipStream_t s);
 
 // k_pairs.hip: the resident pair store (hicmi_pairs_*).  A chunk of n pairs on the device is compacted into
 // the store: the kept pairs (pairs.h) are appended from *length on, which is advanced, and the others add to intra[n_scaf].

@@ -741,6 +741,33 @@ int hicmi_seats_resident(hicmi_ctx *ctx, const int64_t *scaf_size, int64_t n_sca
                          int64_t window, uint64_t *table_out, uint64_t *counters5_out, int64_t *first_out,
                          int64_t *n_table_out);
 
+/* ---- the end-link graph of all scaffolds: which scaffold ends are linked to which, before any ordering --
+ * The question every Hi-C scaffolder starts from (LACHESIS, Burton et al. 2013, Nat Biotechnol 31:1119; SALSA; 3D-DNA;
+ * YaHS), answered from the resident pair store without an order file.  A scaffold is read in its own + coordinates: the
+ * zone of a read end is that of 9p without a reversal (left: the first min(window, len - len / 2) bases, right: the last
+ * min(window, len / 2), middle: the rest).  A kept pair lies on the scaffolds lo < hi; its combination is LL, LR, RL or RR
+ * (first letter: the zone on lo) or OTHER when an end is in a middle zone, and its key lo << 33 | hi << 3 | combination
+ * (0 .. 4).  The keys are counted in a find-or-insert table in device memory (open addressing, linear probing, a 64-bit
+ * compare-and-swap against the empty mark ~0, bounded probing) whose capacity is the smallest power of two that is at
+ * least 1,024 and at least 2 min(n_kept, 5 n_scaf (n_scaf - 1) / 2): it is never more than half full and never grows.
+ * hicmi_links_resident counts the store, compacts the used slots, sorts them by key and merges them into one row per
+ * scaffold pair with at least one pair; the rows stay on the context.  n_rows_out: their number.  counters2_out: linked
+ * (one of the four end combinations) and middle (OTHER); their sum is the pairs kept.
+ * hicmi_links_fetch copies the rows, sorted by (lo, hi): lo and hi of n_rows entries, counts5 of n_rows x 5 row-major in
+ * the order LL, LR, RL, RR, OTHER.  hicmi_pairs_drop releases the rows with the store, and hicmi_pairs_add makes them
+ * stale: a fetch then needs a new count.  hicmi_links_info: of the last count the used slots (records), the slots of
+ * its table and the milliseconds the host took to sort the records, for the measurements of 9t.
+ * HICMI_LINKS_PLAIN=1 in the environment, read at every call, takes one thread and one find-or-insert per pair; =0 takes
+ * the combining kernel (equal keys of a slice summed in LDS first).  Both give the same rows, as do every store order and
+ * mate order.  HICMI_EINVAL: no store, scaf_size or n_scaf other than the store's, window < 1, a fetch or an info before a count.
+ * HICMI_EUNSUPPORTED: n_scaf above 2^30, a table of more than 2^31 slots (the message names the number).  A refusal
+ * leaves every output and the rows of an earlier call as they were.  The store is only read; the context's matrix state
+ * and open builds are never touched. */
+int hicmi_links_resident(hicmi_ctx *ctx, const int64_t *scaf_size, int64_t n_scaf, int64_t window, int64_t *n_rows_out,
+                         uint64_t *counters2_out);
+int hicmi_links_fetch(hicmi_ctx *ctx, int32_t *lo, int32_t *hi, uint64_t *counts5);
+int hicmi_links_info(hicmi_ctx *ctx, int64_t *n_records_out, int64_t *n_slots_out, double *sort_ms_out);
+
 /* ---- scaffolds cut into pieces: every read end moved from its scaffold to its piece -------------------
  * Scaffold s of the n_scaf scaffolds has the pieces piece_first[s] .. piece_first[s + 1] - 1 (int32, n_scaf + 1 entries,
  * ascending from 0 to n_piece), left to right; piece k starts after piece_start[k] bases of its parent (int64, 0 for a
