@@ -79,15 +79,16 @@ def assert_untouched(store, snapshot):
 _NEW = "test_gpu_adopted_ld.py::"
 _SORTERS = [_NEW + "test_rank_matrix_per_call_sorters", _NEW + "test_rank_matrix_lds_sorter_in_a_fresh_process",
             _NEW + "test_rank_matrix_after_the_presort"]
+_SHARD = "test_gpu_shard.py::test_adopted_matrix_under_a_shard"         # every first of stride 3, ld = n + 3
 # callee of csrc/api.hip whose arguments begin `c->dC, c->ldc` (or the 2-D copy from c->dC) -> the tests that run it
 # on a matrix with ld > n
 READERS = {
-    "launch_row_sums": [_NEW + "test_row_sums", _NEW + "test_row_sums_of_a_shard"],
+    "launch_row_sums": [_NEW + "test_row_sums", _NEW + "test_row_sums_of_a_shard", _SHARD],
     "launch_compact": [_NEW + "test_compact"],
     "hipMemcpy2DAsync": [_NEW + "test_row_fetch", _NEW + "test_row_fetch_in_three_blocks"],
     "launch_build_w": [_NEW + "test_upgma", _NEW + "test_upgma_with_the_presort_beside_the_chain"],
-    "launch_sort_rows": _SORTERS,
-    "launch_rank_rows_radix": [_NEW + "test_rank_matrix_per_call_sorters"],
+    "launch_sort_rows": _SORTERS + [_SHARD],
+    "launch_rank_rows_radix": [_NEW + "test_rank_matrix_per_call_sorters", _SHARD],
     "launch_similarity_row": [_NEW + "test_rank_matrix_per_call_sorters"],
     "launch_p2_select": [_NEW + "test_p2_literal_scores", _NEW + "test_workers_reports_equal_an_owned_copy"],
     "launch_plot_select": [_NEW + "test_plot_percentiles_and_downsample"],

@@ -7,19 +7,37 @@ import numpy as np
 import hic_oracle as orc
 
 
+class OracleError(RuntimeError):
+    """What _lib.HicmiError is to libhicmi: the refusal of a call, worded as the library words it."""
+
+
+def _einval(text):
+    return OracleError("libhicmi error -1: " + text)
+
+
 class OracleContext:
     def __init__(self, device=0):
         self.n = 0
         self.mat = None
         self.shard = (0, 1)
         self._sums = None
+        self.R = None
 
     # ---- one map over several ranks: like libhicmi, answer only for the owned rows until the sums are installed
     def set_row_shard(self, first, stride):
-        self.shard = (int(first), int(stride))
+        first, stride = int(first), int(stride)
+        if stride < 1 or first < 0 or first >= stride:
+            raise _einval("row shard needs 0 <= first < stride")          # (the shard in force stays)
+        self.shard = (first, stride)
+        self.R = None                                                      # the rank rows are another shard's
 
     def set_row_sums(self, np_sum, seq_sum):
         self._sums = (np.array(np_sum), np.array(seq_sum))
+
+    def _ranked(self):
+        if self.R is None:
+            raise _einval("hicmi_rank_matrix has not run")
+        return self.R
 
     def _owned(self, first_row, count):
         first, stride = self.shard
@@ -38,8 +56,11 @@ class OracleContext:
         self.mat = np.ascontiguousarray(mat, dtype=np.float64)
         self.n = len(self.mat)
         self._sums = None
+        self.R = None
 
     def row_sums(self):
+        if self._sums is not None and self._sums[0] is not None:
+            return self._sums[0].copy(), self._sums[1].copy()              # the installed vectors, as they were handed over
         a, b = orc.np_row_sums(self.mat), orc.seq_row_sums(self.mat)
         if self.shard[1] > 1 and self._sums is None:
             own = self._owned(0, self.n)
@@ -87,13 +108,20 @@ class OracleContext:
         sim = rs[:, None] * (1.0 - (dist - 1.0))
         self.R = orc.rank_order(sim)
 
+    def presort_state(self):
+        return 0, 0                                                        # every rank_matrix sorts every row itself
+
     def rank_rows(self, row0=0, nrows=None, inverse=False):
-        assert not inverse
         nrows = self.n - row0 if nrows is None else nrows
-        return self.R[row0:row0 + nrows].astype(np.uint16)
+        rows = self._ranked()[row0:row0 + nrows].astype(np.uint16)
+        if inverse:                                                        # position of every column in the sorted row
+            inv = np.empty_like(rows)
+            np.put_along_axis(inv, rows.astype(np.int64), np.arange(self.n, dtype=np.uint16)[None, :], axis=1)
+            return inv
+        return rows
 
     def cut_scan(self, start, M, psig, want_x=False):
-        x = orc.first_pass_counts(self.R, start)[start:]
+        x = orc.first_pass_counts(self._ranked(), start)[start:]
         L = np.arange(1, self.n - start)
         p = orc.hyper_geom(x[1:], M, L, L)
         sig = np.concatenate(([0], np.where(p >= psig, 0, 1))).astype(np.uint8)
@@ -103,7 +131,7 @@ class OracleContext:
         return (sig, x.astype(np.int32)) if want_x else sig
 
     def filter_scan(self, start, c, n_rows, M, psig, want_x=False):
-        sub = self.R[start:start + n_rows, :c - start]
+        sub = self._ranked()[start:start + n_rows, :c - start]
         x = np.count_nonzero((sub >= start) & (sub <= c), axis=1)
         p = orc.hyper_geom(x, M, c - start, c - start)
         sig = np.where(p < psig, 1, 0).astype(np.uint8)
