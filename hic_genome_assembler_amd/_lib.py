@@ -263,15 +263,32 @@ def _name_blob(names):
     return b"".join(enc), off
 
 
+def _names_and_sizes(names, sizes, and_ok=True, and_what=""):
+    """(name blob, int64 offsets, int64 sizes) of the scaffolds of a pair file, one size per name.  ``and_ok`` and
+    ``and_what``: a second condition of the caller's and the words that name it in the same refusal."""
+    blob, off = _name_blob(names)
+    size = np.ascontiguousarray(sizes, dtype=np.int64)
+    if size.shape != (len(names),) or not and_ok:
+        raise ValueError("one size per scaffold name" + and_what)
+    return blob, off, size
+
+
+def _pair_arrays(scaf_a, pos_a, scaf_b, pos_b):
+    """A chunk of pairs as the library takes it: (scaf_a int32, pos_a int64, scaf_b int32, pos_b int64), contiguous
+    vectors of one length."""
+    sa, sb = np.ascontiguousarray(scaf_a, dtype=np.int32), np.ascontiguousarray(scaf_b, dtype=np.int32)
+    pa, pb = np.ascontiguousarray(pos_a, dtype=np.int64), np.ascontiguousarray(pos_b, dtype=np.int64)
+    if not (sa.ndim == 1 and sa.shape == sb.shape == pa.shape == pb.shape):
+        raise ValueError("the four arrays must be vectors of one length")
+    return sa, pa, sb, pb
+
+
 def parse_valid_pairs(path, names, sizes, first_byte: int = 0, max_pairs=None, threads: int = 0):
     """Up to ``max_pairs`` read pairs of a HiC-Pro allValidPairs file from ``first_byte`` on (hicmi_parse_valid_pairs,
     DESIGN.md 9l): (scaffold a, position a, scaffold b, position b) in file order - indices into ``names``, 1-based
     positions - then next_byte (the file size when the file is done) and (lines, used, unknown_scaffold, out_of_range).
     ``max_pairs=None``: as many as the rest of the file can hold."""
-    blob, off = _name_blob(names)
-    size = np.ascontiguousarray(sizes, dtype=np.int64)
-    if size.shape != (len(names),):
-        raise ValueError("one size per scaffold name")
+    blob, off, size = _names_and_sizes(names, sizes)
     if max_pairs is None:
         try:
             max_pairs = max(1, (os.path.getsize(path) - int(first_byte)) // 12 + 1)     # a six-column line has 12 bytes or more
@@ -292,11 +309,9 @@ def build_maps(path, names, sizes, resolutions, ctxs, threads: int = 0):
     """One pass over a HiC-Pro allValidPairs file for the raw maps at every resolution of ``resolutions``, ``ctxs[k]``
     receiving the map at ``resolutions[k]`` (hicmi_build_maps); the contexts are distinct and on one GPU.
     Returns (lines, used, unknown_scaffold, out_of_range, chunks)."""
-    blob, off = _name_blob(names)
-    size = np.ascontiguousarray(sizes, dtype=np.int64)
     res = np.ascontiguousarray(resolutions, dtype=np.int64)
-    if size.shape != (len(names),) or res.ndim != 1 or len(res) != len(ctxs) or not len(ctxs):
-        raise ValueError("one size per scaffold name and one context per resolution")
+    blob, off, size = _names_and_sizes(names, sizes, res.ndim == 1 and len(res) == len(ctxs) and len(ctxs) > 0,
+                                       " and one context per resolution")
     handles = (_vp * len(ctxs))(*[c._h for c in ctxs])
     stats = np.zeros(5, np.int64)
     _check(load().hicmi_build_maps(os.fsencode(path), blob, _ptr(off), len(names), _ptr(size), len(res), _ptr(res), handles,
@@ -340,11 +355,10 @@ def lift_maps(path, names, sizes, lift_seq, lift_off, lift_rev, seq_sizes, resol
     lifted maps at every resolution - ``ctxs[k]`` receives the one at ``resolutions[k]`` - and the statistics of the
     pairs, added to ``into`` (new_pair_stats; None: fresh ones).  Returns ((lines, used, unknown_scaffold, out_of_range,
     chunks), (decay, seq_cis, seq_trans, unlifted))."""
-    blob, off = _name_blob(names)
     size, seq, loff, rev, seq_size = _lift_tables(sizes, lift_seq, lift_off, lift_rev, seq_sizes)
     res = np.ascontiguousarray(resolutions, dtype=np.int64)
-    if size.shape != (len(names),) or res.ndim != 1 or len(res) != len(ctxs) or not len(ctxs):
-        raise ValueError("one size per scaffold name and one context per resolution")
+    blob, off, size = _names_and_sizes(names, size, res.ndim == 1 and len(res) == len(ctxs) and len(ctxs) > 0,
+                                       " and one context per resolution")
     out = _pair_stats_into(into, len(seq_size))
     handles = (_vp * len(ctxs))(*[c._h for c in ctxs])
     stats = np.zeros(5, np.int64)
@@ -377,10 +391,8 @@ def span_file(path, names, sizes, lift_seq, lift_off, lift_rev, seq_sizes, step,
     device of ``ctx``, whose matrix and open map build stay as they are.  ``recs``: records (lo, hi, q0, q1) of slots.
     Returns ((lines, used, unknown_scaffold, out_of_range, chunks), cell_first int64[S], picks int64[n_rec, 4] = (slot, D,
     Lsum, Rsum), counters uint64[5] = (marked, one_cell, beyond_max_span, trans, unlifted), depth uint64[n_cells] or None)."""
-    blob, off = _name_blob(names)
     size, seq, loff, rev, seq_size = _lift_tables(sizes, lift_seq, lift_off, lift_rev, seq_sizes)
-    if size.shape != (len(names),):
-        raise ValueError("one size per scaffold name")
+    blob, off, size = _names_and_sizes(names, size)
     rec, picks = _span_records(recs)
     stats, counters = np.zeros(5, np.int64), np.zeros(5, np.uint64)
     cell_first, n_cells = np.zeros(len(size), np.int64), c_i64()
@@ -413,10 +425,8 @@ def ends_file(path, names, sizes, lift_seq, lift_off, lift_rev, seq_sizes, windo
     device of ``ctx``, whose matrix, open map build and open span build stay as they are.  Returns ((lines, used,
     unknown_scaffold, out_of_range, chunks), rank int32[S], table uint64[P, reach, 4], counters uint64[6] = (linked, middle,
     same, too_far, trans, unlifted))."""
-    blob, off = _name_blob(names)
     size, seq, loff, rev, seq_size = _lift_tables(sizes, lift_seq, lift_off, lift_rev, seq_sizes)
-    if size.shape != (len(names),):
-        raise ValueError("one size per scaffold name")
+    blob, off, size = _names_and_sizes(names, size)
     stats, counters = np.zeros(5, np.int64), np.zeros(6, np.uint64)
     rank, n_placed = np.zeros(len(size), np.int32), c_i64()
     table = _ends_table(ends_placed_count(size, seq), reach)
@@ -498,11 +508,9 @@ def anchor_file(path, names, sizes, lift_seq, lift_off, lift_rev, seq_sizes, tar
     are.  ``target`` None: sequence mode, else the target sequence of every scaffold (-1: none).  Returns ((lines, used,
     unknown_scaffold, out_of_range, chunks), first int64[S], table uint64[n_table], counters uint64[6] = (anchored, middle,
     elsewhere, skipped, unplaced, placed))."""
-    blob, off = _name_blob(names)
     size, seq, loff, rev, seq_size = _lift_tables(sizes, lift_seq, lift_off, lift_rev, seq_sizes)
-    if size.shape != (len(names),):
-        raise ValueError("one size per scaffold name")
-    tgt = _anchor_target(target, len(size))
+    blob, off, size = _names_and_sizes(names, size)
+    tgt =_anchor_target(target, len(size))
     stats, counters = np.zeros(5, np.int64), np.zeros(6, np.uint64)
     first, n_table = np.zeros(len(size), np.int64), c_i64()
     table = _anchor_table(anchor_blocks(size, seq, len(seq_size), tgt)[1])
@@ -516,10 +524,7 @@ def pairs_file(path, names, sizes, ctx, threads: int = 0):
     """Load a HiC-Pro allValidPairs file into the resident pair store of ``ctx`` in one pass (hicmi_pairs_file, DESIGN.md
     9r): the pairs on two scaffolds stay on the device, the others are counted per scaffold.  The matrix and every open
     build of ``ctx`` stay as they are.  Returns (lines, used, unknown_scaffold, out_of_range, chunks)."""
-    blob, off = _name_blob(names)
-    size = np.ascontiguousarray(sizes, dtype=np.int64)
-    if size.shape != (len(names),):
-        raise ValueError("one size per scaffold name")
+    blob, off, size = _names_and_sizes(names, sizes)
     stats = np.zeros(5, np.int64)
     _check(load().hicmi_pairs_file(os.fsencode(path), blob, _ptr(off), len(names), _ptr(size), ctx._h, int(threads), _ptr(stats)))
     ctx._pairs_scaffolds = len(size)
@@ -567,12 +572,11 @@ def split_maps(path, names, sizes, piece_first, piece_start, resolutions, ctxs, 
     ``ctxs[k]`` receives the one at ``resolutions[k]``, cut from the pieces - and the counters of the pieces, added to
     ``into`` (new_split_counters; None: fresh ones).  No resolution: the counters alone, on the device of ``ctxs[0]``,
     which is left as it is.  Returns ((lines, used, unknown_scaffold, out_of_range, chunks), counters)."""
-    blob, off = _name_blob(names)
     size, first, start = _split_tables(sizes, piece_first, piece_start)
     res = np.ascontiguousarray(resolutions, dtype=np.int64).reshape(-1)
-    if size.shape != (len(names),) or not len(ctxs) or len(ctxs) != max(len(res), 1):
-        raise ValueError("one size per scaffold name and one context per resolution (one context when there is no resolution)")
-    out = _split_counters_into(into, len(start))
+    blob, off, size = _names_and_sizes(names, size, len(ctxs) > 0 and len(ctxs) == max(len(res), 1),
+                                       " and one context per resolution (one context when there is no resolution)")
+    out =_split_counters_into(into, len(start))
     handles = (_vp * len(ctxs))(*[c._h for c in ctxs])
     stats = np.zeros(5, np.int64)
     _check(load().hicmi_split_maps(os.fsencode(path), blob, _ptr(off), len(names), _ptr(size), _ptr(first), _ptr(start), len(start),
@@ -587,11 +591,9 @@ def split_maps(path, names, sizes, piece_first, piece_start, resolutions, ctxs, 
 def split_valid_pairs(path_in, path_out, names, sizes, piece_first, piece_start, piece_names, threads: int = 0):
     """``path_in`` written again as ``path_out`` with both ends of every kept line moved to the pieces
     (hicmi_split_valid_pairs; host code).  Returns (lines, used, unknown_scaffold, out_of_range)."""
-    blob, off = _name_blob(names)
     piece_blob, piece_off = _name_blob(piece_names)
     size, first, start = _split_tables(sizes, piece_first, piece_start)
-    if size.shape != (len(names),) or len(piece_names) != len(start):
-        raise ValueError("one size per scaffold name and one name per piece")
+    blob, off, size = _names_and_sizes(names, size, len(piece_names) == len(start), " and one name per piece")
     stats = np.zeros(4, np.int64)
     _check(load().hicmi_split_valid_pairs(os.fsencode(path_in), os.fsencode(path_out), blob, _ptr(off), len(names), _ptr(size),
                                           _ptr(first), _ptr(start), len(start), piece_blob, _ptr(piece_off), int(threads),
@@ -742,10 +744,7 @@ class Context:
     def pair_stats(self, scaf_a, pos_a, scaf_b, pos_b, sizes, lift_seq, lift_off, lift_rev, seq_sizes, into=None):
         """The statistics of the pairs under the lift (hicmi_pair_stats), added to ``into``
         (new_pair_stats; None: fresh ones): (decay[256], seq_cis, seq_trans, unlifted[1]) as uint64."""
-        sa, sb = np.ascontiguousarray(scaf_a, dtype=np.int32), np.ascontiguousarray(scaf_b, dtype=np.int32)
-        pa, pb = np.ascontiguousarray(pos_a, dtype=np.int64), np.ascontiguousarray(pos_b, dtype=np.int64)
-        if not (sa.ndim == 1 and sa.shape == sb.shape == pa.shape == pb.shape):
-            raise ValueError("the four arrays must be vectors of one length")
+        sa, pa, sb, pb = _pair_arrays(scaf_a, pos_a, scaf_b, pos_b)
         size, seq, off, rev, seq_size = _lift_tables(sizes, lift_seq, lift_off, lift_rev, seq_sizes)
         out = _pair_stats_into(into, len(seq_size))
         _check(self._lib.hicmi_pair_stats(self._h, _ptr(sa), _ptr(pa), _ptr(sb), _ptr(pb), len(sa), _ptr(size), len(size), _ptr(seq),
@@ -755,10 +754,7 @@ class Context:
 
     def map_add_pairs(self, scaf_a, pos_a, scaf_b, pos_b):
         """Count the pairs (scaffold index, 1-based position) x 2 into the open map (hicmi_map_add_pairs)."""
-        sa, sb = np.ascontiguousarray(scaf_a, dtype=np.int32), np.ascontiguousarray(scaf_b, dtype=np.int32)
-        pa, pb = np.ascontiguousarray(pos_a, dtype=np.int64), np.ascontiguousarray(pos_b, dtype=np.int64)
-        if not (sa.ndim == 1 and sa.shape == sb.shape == pa.shape == pb.shape):
-            raise ValueError("the four arrays must be vectors of one length")
+        sa, pa, sb, pb = _pair_arrays(scaf_a, pos_a, scaf_b, pos_b)
         _check(self._lib.hicmi_map_add_pairs(self._h, _ptr(sa), _ptr(pa), _ptr(sb), _ptr(pb), len(sa)))
 
     def map_finish(self) -> int:
@@ -782,10 +778,7 @@ class Context:
 
     def span_add_pairs(self, scaf_a, pos_a, scaf_b, pos_b):
         """Mark the pairs (scaffold index, 1-based position) x 2 in the open span build (hicmi_span_add_pairs)."""
-        sa, sb = np.ascontiguousarray(scaf_a, dtype=np.int32), np.ascontiguousarray(scaf_b, dtype=np.int32)
-        pa, pb = np.ascontiguousarray(pos_a, dtype=np.int64), np.ascontiguousarray(pos_b, dtype=np.int64)
-        if not (sa.ndim == 1 and sa.shape == sb.shape == pa.shape == pb.shape):
-            raise ValueError("the four arrays must be vectors of one length")
+        sa, pa, sb, pb = _pair_arrays(scaf_a, pos_a, scaf_b, pos_b)
         _check(self._lib.hicmi_span_add_pairs(self._h, _ptr(sa), _ptr(pa), _ptr(sb), _ptr(pb), len(sa)))
 
     def span_finish(self, flank, recs, want_depth: bool = True):
@@ -811,10 +804,7 @@ class Context:
 
     def ends_add_pairs(self, scaf_a, pos_a, scaf_b, pos_b):
         """Count the pairs (scaffold index, 1-based position) x 2 in the open ends build (hicmi_ends_add_pairs)."""
-        sa, sb = np.ascontiguousarray(scaf_a, dtype=np.int32), np.ascontiguousarray(scaf_b, dtype=np.int32)
-        pa, pb = np.ascontiguousarray(pos_a, dtype=np.int64), np.ascontiguousarray(pos_b, dtype=np.int64)
-        if not (sa.ndim == 1 and sa.shape == sb.shape == pa.shape == pb.shape):
-            raise ValueError("the four arrays must be vectors of one length")
+        sa, pa, sb, pb = _pair_arrays(scaf_a, pos_a, scaf_b, pos_b)
         _check(self._lib.hicmi_ends_add_pairs(self._h, _ptr(sa), _ptr(pa), _ptr(sb), _ptr(pb), len(sa)))
 
     def ends_finish(self):
@@ -842,10 +832,7 @@ class Context:
 
     def anchor_add_pairs(self, scaf_a, pos_a, scaf_b, pos_b):
         """Count the pairs (scaffold index, 1-based position) x 2 in the open anchor build (hicmi_anchor_add_pairs)."""
-        sa, sb = np.ascontiguousarray(scaf_a, dtype=np.int32), np.ascontiguousarray(scaf_b, dtype=np.int32)
-        pa, pb = np.ascontiguousarray(pos_a, dtype=np.int64), np.ascontiguousarray(pos_b, dtype=np.int64)
-        if not (sa.ndim == 1 and sa.shape == sb.shape == pa.shape == pb.shape):
-            raise ValueError("the four arrays must be vectors of one length")
+        sa, pa, sb, pb = _pair_arrays(scaf_a, pos_a, scaf_b, pos_b)
         _check(self._lib.hicmi_anchor_add_pairs(self._h, _ptr(sa), _ptr(pa), _ptr(sb), _ptr(pb), len(sa)))
 
     def anchor_finish(self):
@@ -867,10 +854,7 @@ class Context:
     def pairs_add(self, scaf_a, pos_a, scaf_b, pos_b):
         """Append the pairs (scaffold index, 1-based position) x 2 that lie on two scaffolds to the store and count the
         others per scaffold (hicmi_pairs_add)."""
-        sa, sb = np.ascontiguousarray(scaf_a, dtype=np.int32), np.ascontiguousarray(scaf_b, dtype=np.int32)
-        pa, pb = np.ascontiguousarray(pos_a, dtype=np.int64), np.ascontiguousarray(pos_b, dtype=np.int64)
-        if not (sa.ndim == 1 and sa.shape == sb.shape == pa.shape == pb.shape):
-            raise ValueError("the four arrays must be vectors of one length")
+        sa, pa, sb, pb = _pair_arrays(scaf_a, pos_a, scaf_b, pos_b)
         _check(self._lib.hicmi_pairs_add(self._h, _ptr(sa), _ptr(pa), _ptr(sb), _ptr(pb), len(sa)))
 
     def pairs_info(self):
@@ -970,10 +954,7 @@ class Context:
         (hicmi_split_pairs): (piece a, position a, piece b, position b, counters), the counters uint64[4,
         n_piece] = (within, sibling, other, mark) added to ``into`` (new_split_counters; None: fresh ones).  The matrix, an
         open map build and an open span build are untouched."""
-        sa, sb = np.ascontiguousarray(scaf_a, dtype=np.int32), np.ascontiguousarray(scaf_b, dtype=np.int32)
-        pa, pb = np.ascontiguousarray(pos_a, dtype=np.int64), np.ascontiguousarray(pos_b, dtype=np.int64)
-        if not (sa.ndim == 1 and sa.shape == sb.shape == pa.shape == pb.shape):
-            raise ValueError("the four arrays must be vectors of one length")
+        sa, pa, sb, pb = _pair_arrays(scaf_a, pos_a, scaf_b, pos_b)
         size, first, start = _split_tables(sizes, piece_first, piece_start)
         out = _split_counters_into(into, len(start))
         ka, kb, xa, xb = np.empty_like(sa), np.empty_like(sb), np.empty_like(pa), np.empty_like(pb)

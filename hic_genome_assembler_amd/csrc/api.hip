@@ -391,6 +391,56 @@ int ensure_all(Args&&... args)
     return e == hipSuccess ? HICMI_OK : no_memory(failed_bytes, e);
 }
 
+// a switch of the environment as its caller read it: "1" on, "0" off, anything else (unset too) the caller's default
+bool plain_switch(const char* value, bool dflt)
+{
+    if (value && !strcmp(value, "1")) return true;
+    if (value && !strcmp(value, "0")) return false;
+    return dflt;
+}
+
+// an integer setting `name` of the environment as its caller read it, within 1 .. 2^log2_most; unset: `dflt`
+int setting_in_range(const char* name, const char* value, int log2_most, int64_t dflt, int64_t* out)
+{
+    *out = dflt;
+    if (value) {
+        const long long v = atoll(value);
+        if (v < 1 || v > ((long long)1 << log2_most)) return fail(HICMI_EINVAL, "%s = %s outside 1 .. 2^%d", name, value, log2_most);
+        *out = v;
+    }
+    return HICMI_OK;
+}
+
+// the counters of a build that opens, zeroed, and the tables uploaded before them off the upload arena
+int zero_and_wait(hicmi_ctx* c, void* counters, size_t bytes)
+{
+    hipError_t e = hipMemsetAsync(counters, 0, bytes, c->stream);
+    if (e != hipSuccess) return fail(HICMI_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e));
+    if ((e = sync_stream(c)) != hipSuccess) return fail(HICMI_EHIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
+    return HICMI_OK;
+}
+
+// after a launch on the context's stream: the launch's error or the stream's, reported as "<doing>: <the error>"
+int wait_launched(hicmi_ctx* c, const char* doing)
+{
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = sync_stream(c);
+    return e == hipSuccess ? HICMI_OK : fail(HICMI_EHIP, "%s: %s", doing, hipGetErrorString(e));
+}
+
+// a table of m counters with n_kinds more behind it: the kinds come down first, then the table straight into table_out,
+// and kinds_out is written only when the table is down
+int download_table(hicmi_ctx* c, const unsigned long long* table, int64_t m, int n_kinds, uint64_t* table_out, uint64_t* kinds_out)
+{
+    std::vector<uint64_t> kinds((size_t)n_kinds);
+    int rc = download(c, kinds.data(), table + m, sizeof(uint64_t) * kinds.size());
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(table_out, table, sizeof(uint64_t) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_stream(c));
+    memcpy(kinds_out, kinds.data(), sizeof(uint64_t) * kinds.size());
+    return HICMI_OK;
+}
+
 // a candidate's bin order is staged in LDS as int32, 160 KiB at the most
 int check_candidate_bins(int64_t n_bins)
 {
@@ -649,8 +699,7 @@ int hicmi_rebin(hicmi_ctx* c, const int32_t* group_start, int64_t m)
         if (group_start[i + 1] - group_start[i] > REBIN_MAX_WIDTH)
             return fail(HICMI_EUNSUPPORTED, "coarse bin %lld has %d fine bins: at most %d", (long long)i,
                         group_start[i + 1] - group_start[i], REBIN_MAX_WIDTH);
-    const char* env = getenv("HICMI_REBIN_PLAIN");
-    const bool plain = env && !strcmp(env, "1");
+    const bool plain = plain_switch(getenv("HICMI_REBIN_PLAIN"), false);
     // one image of both lists: group_start, then chunk_first
     const int64_t n_chunks = (n + REBIN_CHUNK - 1) / REBIN_CHUNK;
     std::vector<int32_t> img((size_t)(m + 1 + n_chunks + 1));
@@ -690,20 +739,14 @@ static void map_abandon(hicmi_ctx* c)
 constexpr bool kBuildmapPlainByDefault = true;
 static bool buildmap_plain()
 {
-    const char* env = getenv("HICMI_BUILDMAP_PLAIN");
-    if (env && !strcmp(env, "1")) return true;
-    if (env && !strcmp(env, "0")) return false;
-    return kBuildmapPlainByDefault;
+    return plain_switch(getenv("HICMI_BUILDMAP_PLAIN"), kBuildmapPlainByDefault);
 }
 
 // HICMI_LIFTMAP_PLAIN: the same choice for a lifted build, read per call
 constexpr bool kLiftmapPlainByDefault = true;
 static bool liftmap_plain()
 {
-    const char* env = getenv("HICMI_LIFTMAP_PLAIN");
-    if (env && !strcmp(env, "1")) return true;
-    if (env && !strcmp(env, "0")) return false;
-    return kLiftmapPlainByDefault;
+    return plain_switch(getenv("HICMI_LIFTMAP_PLAIN"), kLiftmapPlainByDefault);
 }
 
 // the lift of a build as the caller hands it over: host arrays, one entry per scaffold, and the sequences' sizes
@@ -765,10 +808,7 @@ static int map_open(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, int6
     if (rc) return rc;
     rc = upload(c, c->d_map_first, first.data(), sizeof(int32_t) * (size_t)n_grid);
     if (!rc && lift) rc = lift_upload(c, c->d_map_lift, scaf_size, n_scaf, *lift, &c->map_lift);
-    hipError_t e = hipSuccess;
-    if (!rc && (e = hipMemsetAsync(c->map_cells, 0, sizeof(uint64_t) * (size_t)m * (size_t)m, c->stream)) != hipSuccess)
-        rc = fail(HICMI_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e));
-    if (!rc && (e = sync_stream(c)) != hipSuccess) rc = fail(HICMI_EHIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
+    if (!rc) rc = zero_and_wait(c, c->map_cells, sizeof(uint64_t) * (size_t)m * (size_t)m);
     if (rc) { map_abandon(c); return rc; }
     c->map_m = m; c->map_res = resolution; c->map_pairs = 0;
     c->map_first = std::move(first);
@@ -818,6 +858,20 @@ static int check_pairs(const int32_t* scaf_a, const int64_t* pos_a, const int32_
     return HICMI_OK;
 }
 
+// a chunk of host arrays on its way into the context's staging (d_map_chunk, which holds nothing between calls)
+static int stage_chunk(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
+                       MapChunk* out)
+{
+    int rc = ensure(c->d_map_chunk, 24 * n);
+    if (rc) return rc;
+    const MapChunk k = *out = map_chunk_at(c->d_map_chunk, n);
+    rc = upload(c, k.pos_a, pos_a, sizeof(int64_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.pos_b, pos_b, sizeof(int64_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.scaf_a, scaf_a, sizeof(int32_t) * (size_t)n);
+    if (!rc) rc = upload(c, k.scaf_b, scaf_b, sizeof(int32_t) * (size_t)n);
+    return rc;
+}
+
 // the counters of k_pair_stats, [decay 256][cis n_seq][trans n_seq][unlifted], added to the caller's arrays
 static void stats_add(const uint64_t* got, int64_t n_seq, uint64_t* decay_out, uint64_t* seq_cis_out, uint64_t* seq_trans_out,
                       uint64_t* unlifted_out)
@@ -843,19 +897,13 @@ int hicmi_map_add_pairs(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos_
     if (n == 0) return HICMI_OK;
     HIPCHK(hipSetDevice(c->device));
     // a HIP error from here on gives the build up: what was counted so far cannot be told
-    int rc = ensure(c->d_map_chunk, 24 * n);
-    const MapChunk k = map_chunk_at(c->d_map_chunk, n);
-    if (!rc) rc = upload(c, k.pos_a, pos_a, sizeof(int64_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.pos_b, pos_b, sizeof(int64_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.scaf_a, scaf_a, sizeof(int32_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.scaf_b, scaf_b, sizeof(int32_t) * (size_t)n);
+    MapChunk k;
+    int rc = stage_chunk(c, scaf_a, pos_a, scaf_b, pos_b, n, &k);
     if (!rc) {
         launch_buildmap_add(k.scaf_a, k.pos_a, k.scaf_b, k.pos_b, n, c->d_map_first, (int)c->map_first.size(), c->map_res,
                             (int)c->map_m, c->map_cells, c->map_lift.seq ? liftmap_plain() : buildmap_plain(), c->map_lift,
                             c->stream);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = sync_stream(c);
-        if (e != hipSuccess) rc = fail(HICMI_EHIP, "counting a chunk of pairs: %s", hipGetErrorString(e));
+        rc = wait_launched(c, "counting a chunk of pairs");
     }
     if (rc) { map_abandon(c); return rc; }
     c->map_pairs += n - unlifted;
@@ -877,17 +925,13 @@ int hicmi_pair_stats(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos_a, 
     if (rc || n == 0) return rc;
     HIPCHK(hipSetDevice(c->device));
     const int64_t n_out = LIFT_DECAY_SLOTS + 2 * n_seq + 1;
-    rc = ensure(c->d_map_chunk, 24 * n);
-    if (!rc) rc = ensure(c->d_stat_lift, 21 * n_scaf);
+    rc = ensure(c->d_stat_lift, 21 * n_scaf);
     if (!rc) rc = ensure(c->d_stat_out, n_out);
     if (rc) return rc;
     LiftTables tables;
-    const MapChunk k = map_chunk_at(c->d_map_chunk, n);
+    MapChunk k;
     rc = lift_upload(c, c->d_stat_lift, scaf_size, n_scaf, lift, &tables);
-    if (!rc) rc = upload(c, k.pos_a, pos_a, sizeof(int64_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.pos_b, pos_b, sizeof(int64_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.scaf_a, scaf_a, sizeof(int32_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.scaf_b, scaf_b, sizeof(int32_t) * (size_t)n);
+    if (!rc) rc = stage_chunk(c, scaf_a, pos_a, scaf_b, pos_b, n, &k);
     if (rc) return rc;
     HIPCHK(hipMemsetAsync(c->d_stat_out, 0, sizeof(uint64_t) * (size_t)n_out, c->stream));
     launch_pair_stats(k.scaf_a, k.pos_a, k.scaf_b, k.pos_b, n, tables, c->d_stat_out, c->stream);
@@ -931,10 +975,7 @@ struct SplitHost { const int32_t* piece_first; const int64_t* piece_start; int64
 constexpr bool kSplitPlainByDefault = false;
 static bool split_plain()
 {
-    const char* env = getenv("HICMI_SPLIT_PLAIN");
-    if (env && !strcmp(env, "1")) return true;
-    if (env && !strcmp(env, "0")) return false;
-    return kSplitPlainByDefault;
+    return plain_switch(getenv("HICMI_SPLIT_PLAIN"), kSplitPlainByDefault);
 }
 
 static int split_check(const int64_t* scaf_size, int64_t n_scaf, const SplitHost& split)
@@ -989,16 +1030,12 @@ int hicmi_split_pairs(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos_a,
     DevBuf<unsigned char> d_tables;
     DevBuf<unsigned long long> d_counters;
     const int64_t n_counters = SPLIT_COUNTERS * n_piece;
-    rc = ensure(c->d_map_chunk, 24 * n);
-    if (!rc) rc = ensure_all(d_tables, split_image_bytes(n_scaf, n_piece), d_counters, n_counters);
+    rc = ensure_all(d_tables, split_image_bytes(n_scaf, n_piece), d_counters, n_counters);
     if (rc) return rc;
     SplitTables tables;
-    const MapChunk k = map_chunk_at(c->d_map_chunk, n);
+    MapChunk k;
     rc = split_upload(c, d_tables, n_scaf, split, &tables);
-    if (!rc) rc = upload(c, k.pos_a, pos_a, sizeof(int64_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.pos_b, pos_b, sizeof(int64_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.scaf_a, scaf_a, sizeof(int32_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.scaf_b, scaf_b, sizeof(int32_t) * (size_t)n);
+    if (!rc) rc = stage_chunk(c, scaf_a, pos_a, scaf_b, pos_b, n, &k);
     if (rc) return rc;
     HIPCHK(hipMemsetAsync(d_counters, 0, sizeof(uint64_t) * (size_t)n_counters, c->stream));
     launch_split_pairs(k.scaf_a, k.pos_a, k.scaf_b, k.pos_b, n, tables, d_counters, split_plain(), c->stream);
@@ -1018,198 +1055,26 @@ int hicmi_split_pairs(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos_a,
     return HICMI_OK;
 }
 
-// The chunk loop of hicmi_build_maps, hicmi_lift_maps and hicmi_split_maps.  `lift` (hicmi_lift_maps): every build is a
-// lifted one, the statistics of every chunk are counted beside the maps, and `stat_out` receives them when the whole file
-// is counted.  `split` (hicmi_split_maps): every chunk is moved to the pieces before it is counted, the maps are cut
-// from the pieces, and `split_out` receives the counters of the pieces; n_res may then be 0 (the counters alone), and
-// ctxs[0] lends its device and its stream.
-struct LiftStatsOut { uint64_t *decay, *seq_cis, *seq_trans, *unlifted; };
-
-static int build_maps_loop(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names,
-                           const int64_t* scaf_size, int64_t n_res, const int64_t* resolution, hicmi_ctx* const* ctxs, int threads,
-                           int64_t* stats5, const LiftHost* lift, const LiftStatsOut* stat_out, const SplitHost* split = nullptr,
-                           uint64_t* split_out = nullptr)
-{
-    if (!path || !names_blob || !name_off || !scaf_size || !ctxs || !stats5 || n_names < 1 || n_res < (split ? 0 : 1) ||
-        (n_res > 0 && !resolution) || (split && (!split_out || !ctxs[0])))
-        return fail(HICMI_EINVAL, "bad arguments");
-    if (lift && (!stat_out->decay || !stat_out->seq_cis || !stat_out->seq_trans || !stat_out->unlifted))
-        return fail(HICMI_EINVAL, "bad arguments");
-    for (int k = 0; k < 5; k++) stats5[k] = 0;
-    std::vector<int64_t> piece_size;                              // a split call: the grid of its maps
-    if (split) {
-        int rc = split_check(scaf_size, n_names, *split);
-        if (rc) return rc;
-        piece_size = split_piece_sizes(scaf_size, n_names, *split);
-    }
-    for (int64_t k = 0; k < n_res; k++) {
-        if (!ctxs[k] || ctxs[k]->device != ctxs[0]->device) return fail(HICMI_EINVAL, "contexts must share one device");
-        for (int64_t q = 0; q < k; q++) if (ctxs[q] == ctxs[k]) return fail(HICMI_EINVAL, "one context per resolution");
-    }
-    int64_t chunk_pairs = (int64_t)1 << 22;
-    if (const char* env = getenv("HICMI_BUILDMAP_CHUNK_PAIRS")) {
-        const long long v = atoll(env);
-        if (v < 1 || v > ((long long)1 << 28)) return fail(HICMI_EINVAL, "HICMI_BUILDMAP_CHUNK_PAIRS = %s outside 1 .. 2^28", env);
-        chunk_pairs = v;
-    }
-    hicmi_ctx* c0 = ctxs[0];
-    HIPCHK(hipSetDevice(c0->device));
-    // everything the call owns: two pinned chunks for the parser, two device chunks for the kernels
-    PinBuf<unsigned char> pin[2]; DevBuf<unsigned char> dev[2];
-    DevBuf<unsigned long long> d_stats;                           // a lifted call: the counters of k_pair_stats
-    DevBuf<unsigned char> d_split; DevBuf<unsigned long long> d_split_counters;   // a split call: its tables and counters
-    SplitTables split_tables;
-    struct OpenBuilds {                                           // given up on every error path
-        hicmi_ctx* const* ctxs; int64_t n_res; bool keep = false;
-        ~OpenBuilds() { if (!keep) for (int64_t k = 0; k < n_res; k++) map_abandon(ctxs[k]); }
-    } own{ctxs, n_res};
-    // begin on every context first: a resolution that cannot be built is refused before the file is read
-    for (int64_t k = 0; k < n_res; k++) {
-        int rc = split ? map_open(ctxs[k], piece_size.data(), split->n_piece, resolution[k], nullptr)
-                       : map_open(ctxs[k], scaf_size, n_names, resolution[k], lift);
-        if (rc) return rc;
-    }
-    const int64_t n_split = split ? SPLIT_COUNTERS * split->n_piece : 0;
-    if (split) {
-        int rc = ensure_all(d_split, split_image_bytes(n_names, split->n_piece), d_split_counters, n_split);
-        if (!rc) rc = split_upload(c0, d_split, n_names, *split, &split_tables);
-        if (rc) return rc;
-        HIPCHK(hipMemsetAsync(d_split_counters, 0, sizeof(uint64_t) * (size_t)n_split, c0->stream));
-        HIPCHK(sync_stream(c0));                                  // the tables have left the upload arena
-    }
-    const int64_t n_stats = lift ? LIFT_DECAY_SLOTS + 2 * lift->n_seq + 1 : 0;
-    if (lift) {
-        int rc = ensure(d_stats, n_stats);
-        if (rc) return rc;
-        HIPCHK(hipMemsetAsync(d_stats, 0, sizeof(uint64_t) * (size_t)n_stats, c0->stream));
-    }
-    int64_t file_bytes = -1;
-    {
-        // no chunk holds more pairs than the file has room for (a line of six columns is at least 12 bytes)
-        FILE* fh = fopen(path, "rb");
-        if (!fh) return fail(HICMI_EINVAL, "cannot open %s", path);
-        if (fseeko(fh, 0, SEEK_END) == 0) file_bytes = (int64_t)ftello(fh);
-        fclose(fh);
-        if (file_bytes < 0) return fail(HICMI_EINVAL, "cannot tell the size of %s", path);
-        chunk_pairs = std::max<int64_t>(1, std::min(chunk_pairs, file_bytes / 12 + 1));
-    }
-    const size_t chunk_bytes = (size_t)chunk_pairs * 24;
-    for (int b = 0; b < 2; b++) {
-        HIPCHK(pin[b].reserve((int64_t)chunk_bytes));
-        int rc = ensure(dev[b], (int64_t)chunk_bytes);
-        if (rc) return rc;
-    }
-    const bool plain = lift ? liftmap_plain() : buildmap_plain();
-    const bool literal_split = split && split_plain();
-    int64_t next = 0, n_here = 0, st[4];
-    // chunk t + 1 is parsed into the other pinned buffer while chunk t is uploaded and counted on c0's stream
-    auto parse = [&](int b) {
-        const MapChunk h = map_chunk_at(pin[b], chunk_pairs);
-        int rc = hicmi_parse_valid_pairs(path, names_blob, name_off, n_names, scaf_size, threads, next, chunk_pairs, h.scaf_a, h.pos_a,
-                                         h.scaf_b, h.pos_b, &n_here, &next, st);
-        if (!rc) { stats5[0] += st[0]; stats5[1] += st[1]; stats5[2] += st[2]; stats5[3] += st[3]; }
-        return rc;
-    };
-    int cur = 0;
-    int rc = parse(cur);
-    if (rc) return rc;
-    for (;;) {
-        const int64_t n = n_here;
-        if (n > 0) {
-            const MapChunk h = map_chunk_at(pin[cur], chunk_pairs), d = map_chunk_at(dev[cur], chunk_pairs);
-            HIPCHK(hipMemcpyAsync(d.pos_a, h.pos_a, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, c0->stream));
-            HIPCHK(hipMemcpyAsync(d.pos_b, h.pos_b, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, c0->stream));
-            HIPCHK(hipMemcpyAsync(d.scaf_a, h.scaf_a, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c0->stream));
-            HIPCHK(hipMemcpyAsync(d.scaf_b, h.scaf_b, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c0->stream));
-            if (split) launch_split_pairs(d.scaf_a, d.pos_a, d.scaf_b, d.pos_b, n, split_tables, d_split_counters, literal_split, c0->stream);
-            for (int64_t k = 0; k < n_res; k++) {
-                hicmi_ctx* c = ctxs[k];
-                launch_buildmap_add(d.scaf_a, d.pos_a, d.scaf_b, d.pos_b, n, c->d_map_first, (int)c->map_first.size(), c->map_res,
-                                    (int)c->map_m, c->map_cells, plain, c->map_lift, c0->stream);
-                c->map_pairs += n;
-            }
-            if (lift) launch_pair_stats(d.scaf_a, d.pos_a, d.scaf_b, d.pos_b, n, c0->map_lift, d_stats, c0->stream);
-            HIPCHK(hipGetLastError());
-            stats5[4]++;
-        }
-        const bool last = next >= file_bytes;                      // the parser has taken the whole file
-        if (!last) rc = parse(cur ^ 1);
-        hipError_t e = hipStreamSynchronize(c0->stream);           // chunk t is counted: its two buffers are free again
-        if (rc) return rc;
-        if (e != hipSuccess) return fail(HICMI_EHIP, "counting a chunk of pairs: %s", hipGetErrorString(e));
-        if (last) break;
-        cur ^= 1;
-    }
-    std::vector<uint64_t> got((size_t)n_stats);
-    if (lift) {
-        // the statistics come down before any context changes; a map has counted the pairs that were lifted
-        HIPCHK(hipMemcpy(got.data(), d_stats, sizeof(uint64_t) * (size_t)n_stats, hipMemcpyDeviceToHost));
-        for (int64_t k = 0; k < n_res; k++) ctxs[k]->map_pairs -= (int64_t)got[(size_t)n_stats - 1];
-    }
-    std::vector<uint64_t> got_split((size_t)n_split);
-    if (split) HIPCHK(hipMemcpy(got_split.data(), d_split_counters, sizeof(uint64_t) * (size_t)n_split, hipMemcpyDeviceToHost));
-    // every chunk is counted on every map: from here on the contexts change
-    own.keep = true;
-    for (int64_t k = 0; k < n_res; k++) {
-        HIPCHK(hipSetDevice(ctxs[k]->device));
-        rc = map_install(ctxs[k], c0->stream, nullptr);
-        if (rc) { for (int64_t q = k + 1; q < n_res; q++) map_abandon(ctxs[q]); return rc; }
-    }
-    if (lift) stats_add(got.data(), lift->n_seq, stat_out->decay, stat_out->seq_cis, stat_out->seq_trans, stat_out->unlifted);
-    for (int64_t q = 0; q < n_split; q++) split_out[q] += got_split[(size_t)q];
-    return HICMI_OK;
-}
-
-int hicmi_build_maps(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
-                     int64_t n_res, const int64_t* resolution, hicmi_ctx* const* ctxs, int threads, int64_t* stats5)
-{
-    return build_maps_loop(path, names_blob, name_off, n_names, scaf_size, n_res, resolution, ctxs, threads, stats5, nullptr, nullptr);
-}
-
-int hicmi_lift_maps(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
-                    const int32_t* lift_seq, const int64_t* lift_off, const uint8_t* lift_rev, const int64_t* seq_size, int64_t n_seq,
-                    int64_t n_res, const int64_t* resolution, hicmi_ctx* const* ctxs, int threads, int64_t* stats5,
-                    uint64_t* decay_out, uint64_t* seq_cis_out, uint64_t* seq_trans_out, uint64_t* unlifted_out)
-{
-    const LiftHost lift{lift_seq, lift_off, lift_rev, seq_size, n_seq};
-    const LiftStatsOut out{decay_out, seq_cis_out, seq_trans_out, unlifted_out};
-    return build_maps_loop(path, names_blob, name_off, n_names, scaf_size, n_res, resolution, ctxs, threads, stats5, &lift, &out);
-}
-
-// hicmi_build_maps on the pieces the scaffolds are cut into (DESIGN.md 9o): the parser reads the scaffolds' coordinates
-int hicmi_split_maps(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
-                     const int32_t* piece_first, const int64_t* piece_start, int64_t n_piece, int64_t n_res, const int64_t* resolution,
-                     hicmi_ctx* const* ctxs, int threads, int64_t* stats5, uint64_t* counters_out)
-{
-    const SplitHost split{piece_first, piece_start, n_piece};
-    return build_maps_loop(path, names_blob, name_off, n_names, scaf_size, n_res, resolution, ctxs, threads, stats5, nullptr, nullptr,
-                           &split, counters_out);
-}
-
 // HICMI_BUILDMAP_CHUNK_PAIRS, the pairs of one chunk of a pass over a pair file; read per call
 static int chunk_pairs_setting(int64_t* out)
 {
-    *out = (int64_t)1 << 22;
-    if (const char* env = getenv("HICMI_BUILDMAP_CHUNK_PAIRS")) {
-        const long long v = atoll(env);
-        if (v < 1 || v > ((long long)1 << 28)) return fail(HICMI_EINVAL, "HICMI_BUILDMAP_CHUNK_PAIRS = %s outside 1 .. 2^28", env);
-        *out = v;
-    }
-    return HICMI_OK;
+    return setting_in_range("HICMI_BUILDMAP_CHUNK_PAIRS", getenv("HICMI_BUILDMAP_CHUNK_PAIRS"), 28, (int64_t)1 << 22, out);
 }
 
-// One pass over a pair file for one build of the context c: chunk t + 1 is parsed into the other pinned buffer while chunk
-// t is uploaded and handed to on_chunk(device arrays, n), which launches on the context's stream and returns nothing, or
-// an error code that ends the pass.  stats[0 .. 3] are the parser's sums and stats[4] the chunks; `doing` names the work in
-// the message of a HIP error.
+// The one loop over the chunks of a pair file, on the stream of the context c: chunk t + 1 is parsed into the other pinned
+// buffer while chunk t is uploaded and handed to on_chunk(device arrays, n), which launches on that stream and returns
+// nothing, or an error code that ends the pass.  stats[0 .. 3] receive the parser's sums and stats[4] the chunks, added to
+// what they hold; `doing` names the work in the message of a HIP error.
 extern "C++" {
 template <typename OnChunk>
 static int pair_file_pass(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
                           hicmi_ctx* c, int threads, int64_t chunk_pairs, int64_t* stats, const char* doing, OnChunk&& on_chunk)
 {
+    // everything the pass owns: two pinned chunks for the parser, two device chunks for the kernels
     PinBuf<unsigned char> pin[2]; DevBuf<unsigned char> dev[2];
     int64_t file_bytes = -1;
     {
+        // no chunk holds more pairs than the file has room for (a line of six columns is at least 12 bytes)
         FILE* fh = fopen(path, "rb");
         if (!fh) return fail(HICMI_EINVAL, "cannot open %s", path);
         if (fseeko(fh, 0, SEEK_END) == 0) file_bytes = (int64_t)ftello(fh);
@@ -1262,6 +1127,129 @@ static int pair_file_pass(const char* path, const char* names_blob, const int64_
 }
 }  // extern "C++"
 
+// The chunk loop of hicmi_build_maps, hicmi_lift_maps and hicmi_split_maps is pair_file_pass with the maps of every
+// context counted from each chunk.  `lift` (hicmi_lift_maps): every build is a lifted one, the statistics of every chunk
+// are counted beside the maps, and `stat_out` receives them when the whole file is counted.  `split` (hicmi_split_maps):
+// every chunk is moved to the pieces before it is counted, the maps are cut from the pieces, and `split_out` receives the
+// counters of the pieces; n_res may then be 0 (the counters alone), and ctxs[0] lends its device and its stream.
+struct LiftStatsOut { uint64_t *decay, *seq_cis, *seq_trans, *unlifted; };
+
+static int build_maps_loop(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names,
+                           const int64_t* scaf_size, int64_t n_res, const int64_t* resolution, hicmi_ctx* const* ctxs, int threads,
+                           int64_t* stats5, const LiftHost* lift, const LiftStatsOut* stat_out, const SplitHost* split = nullptr,
+                           uint64_t* split_out = nullptr)
+{
+    if (!path || !names_blob || !name_off || !scaf_size || !ctxs || !stats5 || n_names < 1 || n_res < (split ? 0 : 1) ||
+        (n_res > 0 && !resolution) || (split && (!split_out || !ctxs[0])))
+        return fail(HICMI_EINVAL, "bad arguments");
+    if (lift && (!stat_out->decay || !stat_out->seq_cis || !stat_out->seq_trans || !stat_out->unlifted))
+        return fail(HICMI_EINVAL, "bad arguments");
+    for (int k = 0; k < 5; k++) stats5[k] = 0;
+    std::vector<int64_t> piece_size;                              // a split call: the grid of its maps
+    if (split) {
+        int rc = split_check(scaf_size, n_names, *split);
+        if (rc) return rc;
+        piece_size = split_piece_sizes(scaf_size, n_names, *split);
+    }
+    for (int64_t k = 0; k < n_res; k++) {
+        if (!ctxs[k] || ctxs[k]->device != ctxs[0]->device) return fail(HICMI_EINVAL, "contexts must share one device");
+        for (int64_t q = 0; q < k; q++) if (ctxs[q] == ctxs[k]) return fail(HICMI_EINVAL, "one context per resolution");
+    }
+    int64_t chunk_pairs = 0;
+    int rc = chunk_pairs_setting(&chunk_pairs);
+    if (rc) return rc;
+    hicmi_ctx* c0 = ctxs[0];
+    HIPCHK(hipSetDevice(c0->device));
+    DevBuf<unsigned long long> d_stats;                          // a lifted call: the counters of k_pair_stats
+    DevBuf<unsigned char> d_split; DevBuf<unsigned long long> d_split_counters;   // a split call: its tables and counters
+    SplitTables split_tables;
+    struct OpenBuilds {                                           // given up on every error path
+        hicmi_ctx* const* ctxs; int64_t n_res; bool keep = false;
+        ~OpenBuilds() { if (!keep) for (int64_t k = 0; k < n_res; k++) map_abandon(ctxs[k]); }
+    } own{ctxs, n_res};
+    // begin on every context first: a resolution that cannot be built is refused before the file is read
+    for (int64_t k = 0; k < n_res; k++) {
+        rc = split ? map_open(ctxs[k], piece_size.data(), split->n_piece, resolution[k], nullptr)
+                   : map_open(ctxs[k], scaf_size, n_names, resolution[k], lift);
+        if (rc) return rc;
+    }
+    const int64_t n_split = split ? SPLIT_COUNTERS * split->n_piece : 0;
+    if (split) {
+        rc = ensure_all(d_split, split_image_bytes(n_names, split->n_piece), d_split_counters, n_split);
+        if (!rc) rc = split_upload(c0, d_split, n_names, *split, &split_tables);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(d_split_counters, 0, sizeof(uint64_t) * (size_t)n_split, c0->stream));
+        HIPCHK(sync_stream(c0));                                  // the tables have left the upload arena
+    }
+    const int64_t n_stats = lift ? LIFT_DECAY_SLOTS + 2 * lift->n_seq + 1 : 0;
+    if (lift) {
+        rc = ensure(d_stats, n_stats);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(d_stats, 0, sizeof(uint64_t) * (size_t)n_stats, c0->stream));
+    }
+    const bool plain = lift ? liftmap_plain() : buildmap_plain();
+    const bool literal_split = split && split_plain();
+    // every chunk on c0's stream: moved to the pieces, counted on every map, its statistics counted beside them
+    rc = pair_file_pass(path, names_blob, name_off, n_names, scaf_size, c0, threads, chunk_pairs, stats5, "counting a chunk of pairs",
+                        [&](const MapChunk& d, int64_t n) {
+                            if (split)
+                                launch_split_pairs(d.scaf_a, d.pos_a, d.scaf_b, d.pos_b, n, split_tables, d_split_counters, literal_split,
+                                                   c0->stream);
+                            for (int64_t k = 0; k < n_res; k++) {
+                                hicmi_ctx* c = ctxs[k];
+                                launch_buildmap_add(d.scaf_a, d.pos_a, d.scaf_b, d.pos_b, n, c->d_map_first, (int)c->map_first.size(),
+                                                    c->map_res, (int)c->map_m, c->map_cells, plain, c->map_lift, c0->stream);
+                                c->map_pairs += n;
+                            }
+                            if (lift) launch_pair_stats(d.scaf_a, d.pos_a, d.scaf_b, d.pos_b, n, c0->map_lift, d_stats, c0->stream);
+                        });
+    if (rc) return rc;
+    std::vector<uint64_t> got((size_t)n_stats);
+    if (lift) {
+        // the statistics come down before any context changes; a map has counted the pairs that were lifted
+        HIPCHK(hipMemcpy(got.data(), d_stats, sizeof(uint64_t) * (size_t)n_stats, hipMemcpyDeviceToHost));
+        for (int64_t k = 0; k < n_res; k++) ctxs[k]->map_pairs -= (int64_t)got[(size_t)n_stats - 1];
+    }
+    std::vector<uint64_t> got_split((size_t)n_split);
+    if (split) HIPCHK(hipMemcpy(got_split.data(), d_split_counters, sizeof(uint64_t) * (size_t)n_split, hipMemcpyDeviceToHost));
+    // every chunk is counted on every map: from here on the contexts change
+    own.keep = true;
+    for (int64_t k = 0; k < n_res; k++) {
+        HIPCHK(hipSetDevice(ctxs[k]->device));
+        rc = map_install(ctxs[k], c0->stream, nullptr);
+        if (rc) { for (int64_t q = k + 1; q < n_res; q++) map_abandon(ctxs[q]); return rc; }
+    }
+    if (lift) stats_add(got.data(), lift->n_seq, stat_out->decay, stat_out->seq_cis, stat_out->seq_trans, stat_out->unlifted);
+    for (int64_t q = 0; q < n_split; q++) split_out[q] += got_split[(size_t)q];
+    return HICMI_OK;
+}
+
+int hicmi_build_maps(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
+                     int64_t n_res, const int64_t* resolution, hicmi_ctx* const* ctxs, int threads, int64_t* stats5)
+{
+    return build_maps_loop(path, names_blob, name_off, n_names, scaf_size, n_res, resolution, ctxs, threads, stats5, nullptr, nullptr);
+}
+
+int hicmi_lift_maps(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
+                    const int32_t* lift_seq, const int64_t* lift_off, const uint8_t* lift_rev, const int64_t* seq_size, int64_t n_seq,
+                    int64_t n_res, const int64_t* resolution, hicmi_ctx* const* ctxs, int threads, int64_t* stats5,
+                    uint64_t* decay_out, uint64_t* seq_cis_out, uint64_t* seq_trans_out, uint64_t* unlifted_out)
+{
+    const LiftHost lift{lift_seq, lift_off, lift_rev, seq_size, n_seq};
+    const LiftStatsOut out{decay_out, seq_cis_out, seq_trans_out, unlifted_out};
+    return build_maps_loop(path, names_blob, name_off, n_names, scaf_size, n_res, resolution, ctxs, threads, stats5, &lift, &out);
+}
+
+// hicmi_build_maps on the pieces the scaffolds are cut into (DESIGN.md 9o): the parser reads the scaffolds' coordinates
+int hicmi_split_maps(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
+                     const int32_t* piece_first, const int64_t* piece_start, int64_t n_piece, int64_t n_res, const int64_t* resolution,
+                     hicmi_ctx* const* ctxs, int threads, int64_t* stats5, uint64_t* counters_out)
+{
+    const SplitHost split{piece_first, piece_start, n_piece};
+    return build_maps_loop(path, names_blob, name_off, n_names, scaf_size, n_res, resolution, ctxs, threads, stats5, nullptr, nullptr,
+                           &split, counters_out);
+}
+
 // ---- spanning depth: the read pairs with one end on each side of every cell boundary ---------------------
 // Between hicmi_span_begin and hicmi_span_finish the marks live in buffers of their own: the context's matrix state and
 // an open map build are never touched (the staging of a chunk, d_map_chunk, holds nothing between calls).
@@ -1277,10 +1265,7 @@ static void span_abandon(hicmi_ctx* c)
 constexpr bool kSpansPlainByDefault = false;
 static bool spans_plain()
 {
-    const char* env = getenv("HICMI_SPANS_PLAIN");
-    if (env && !strcmp(env, "1")) return true;
-    if (env && !strcmp(env, "0")) return false;
-    return kSpansPlainByDefault;
+    return plain_switch(getenv("HICMI_SPANS_PLAIN"), kSpansPlainByDefault);
 }
 
 // the numbering of a build, made on the host before anything is allocated
@@ -1312,10 +1297,7 @@ static int span_open(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, con
     if (rc) return rc;
     rc = upload(c, c->d_span_first, cells.cell_first.data(), sizeof(int64_t) * (size_t)n_scaf);
     if (!rc) rc = lift_upload(c, c->d_span_lift, scaf_size, n_scaf, lift, &c->span_lift);
-    hipError_t e = hipSuccess;
-    if (!rc && (e = hipMemsetAsync(c->span_marks, 0, sizeof(uint64_t) * (size_t)(m + SPAN_COUNTERS), c->stream)) != hipSuccess)
-        rc = fail(HICMI_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e));
-    if (!rc && (e = sync_stream(c)) != hipSuccess) rc = fail(HICMI_EHIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
+    if (!rc) rc = zero_and_wait(c, c->span_marks, sizeof(uint64_t) * (size_t)(m + SPAN_COUNTERS));
     if (rc) { span_abandon(c); return rc; }
     c->span_grid.cell_first = c->d_span_first; c->span_grid.step = step; c->span_grid.max_span = max_span; c->span_grid.n_cells = m;
     c->span_size.assign(scaf_size, scaf_size + n_scaf);
@@ -1404,18 +1386,12 @@ int hicmi_span_add_pairs(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos
     if (n == 0) return HICMI_OK;
     HIPCHK(hipSetDevice(c->device));
     // a HIP error from here on gives the build up: what was marked so far cannot be told
-    int rc = ensure(c->d_map_chunk, 24 * n);
-    const MapChunk k = map_chunk_at(c->d_map_chunk, n);
-    if (!rc) rc = upload(c, k.pos_a, pos_a, sizeof(int64_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.pos_b, pos_b, sizeof(int64_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.scaf_a, scaf_a, sizeof(int32_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.scaf_b, scaf_b, sizeof(int32_t) * (size_t)n);
+    MapChunk k;
+    int rc = stage_chunk(c, scaf_a, pos_a, scaf_b, pos_b, n, &k);
     if (!rc) {
         launch_span_mark(k.scaf_a, k.pos_a, k.scaf_b, k.pos_b, n, c->span_lift, c->span_grid, c->span_marks,
                          c->span_marks + c->span_grid.n_cells, spans_plain(), c->stream);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = sync_stream(c);
-        if (e != hipSuccess) rc = fail(HICMI_EHIP, "marking a chunk of pairs: %s", hipGetErrorString(e));
+        rc = wait_launched(c, "marking a chunk of pairs");
     }
     if (rc) { span_abandon(c); return rc; }
     c->span_pairs += n;
@@ -1433,7 +1409,7 @@ int hicmi_span_finish(hicmi_ctx* c, int64_t flank, const int64_t* recs, int64_t 
     return span_close(c, flank, recs, n_rec, picks_out, counters5_out, depth_out);
 }
 
-// The same over the pair file in one pass: the chunk loop of build_maps_loop with the marks of one build in place of the maps.
+// The same over the pair file in one pass: pair_file_pass with the marks of one build.
 int hicmi_span_file(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
                     const int32_t* lift_seq, const int64_t* lift_off, const uint8_t* lift_rev, const int64_t* seq_size, int64_t n_seq,
                     int64_t step, int64_t max_span, int64_t flank, const int64_t* recs, int64_t n_rec, hicmi_ctx* c, int threads,
@@ -1491,10 +1467,7 @@ static void ends_abandon(hicmi_ctx* c)
 constexpr bool kEndsPlainByDefault = false;
 static bool ends_plain()
 {
-    const char* env = getenv("HICMI_ENDS_PLAIN");
-    if (env && !strcmp(env, "1")) return true;
-    if (env && !strcmp(env, "0")) return false;
-    return kEndsPlainByDefault;
+    return plain_switch(getenv("HICMI_ENDS_PLAIN"), kEndsPlainByDefault);
 }
 
 // the ranks of a build, made on the host before anything is allocated
@@ -1528,10 +1501,7 @@ static int ends_open(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, con
     if (rc) return rc;
     rc = upload(c, c->d_ends_rank, ranks.rank.data(), sizeof(int32_t) * (size_t)n_scaf);
     if (!rc) rc = lift_upload(c, c->d_ends_lift, scaf_size, n_scaf, lift, &c->ends_lift);
-    hipError_t e = hipSuccess;
-    if (!rc && (e = hipMemsetAsync(c->ends_table, 0, sizeof(uint64_t) * (size_t)(m + ENDS_COUNTERS), c->stream)) != hipSuccess)
-        rc = fail(HICMI_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e));
-    if (!rc && (e = sync_stream(c)) != hipSuccess) rc = fail(HICMI_EHIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
+    if (!rc) rc = zero_and_wait(c, c->ends_table, sizeof(uint64_t) * (size_t)(m + ENDS_COUNTERS));
     if (rc) { ends_abandon(c); return rc; }
     c->ends_grid.rank = c->d_ends_rank; c->ends_grid.window = window; c->ends_grid.reach = reach; c->ends_grid.n_placed = ranks.n_placed;
     c->ends_size.assign(scaf_size, scaf_size + n_scaf);
@@ -1543,14 +1513,7 @@ static int ends_open(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, con
 static int ends_close(hicmi_ctx* c, uint64_t* table_out, uint64_t* counters6_out)
 {
     struct Close { hicmi_ctx* c; ~Close() { ends_abandon(c); } } closing{c};
-    const int64_t m = c->ends_cells;
-    uint64_t counters[ENDS_COUNTERS];
-    int rc = download(c, counters, c->ends_table + m, sizeof(counters));
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(table_out, c->ends_table, sizeof(uint64_t) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(sync_stream(c));
-    memcpy(counters6_out, counters, sizeof(counters));
-    return HICMI_OK;
+    return download_table(c, c->ends_table, c->ends_cells, ENDS_COUNTERS, table_out, counters6_out);
 }
 
 int hicmi_ends_begin(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, const int32_t* lift_seq, const int64_t* lift_off,
@@ -1579,18 +1542,12 @@ int hicmi_ends_add_pairs(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos
     if (n == 0) return HICMI_OK;
     HIPCHK(hipSetDevice(c->device));
     // a HIP error from here on gives the build up: what was counted so far cannot be told
-    int rc = ensure(c->d_map_chunk, 24 * n);
-    const MapChunk k = map_chunk_at(c->d_map_chunk, n);
-    if (!rc) rc = upload(c, k.pos_a, pos_a, sizeof(int64_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.pos_b, pos_b, sizeof(int64_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.scaf_a, scaf_a, sizeof(int32_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.scaf_b, scaf_b, sizeof(int32_t) * (size_t)n);
+    MapChunk k;
+    int rc = stage_chunk(c, scaf_a, pos_a, scaf_b, pos_b, n, &k);
     if (!rc) {
         launch_ends_count(k.scaf_a, k.pos_a, k.scaf_b, k.pos_b, n, c->ends_lift, c->ends_grid, c->ends_cells, c->ends_table,
                           c->ends_table + c->ends_cells, ends_plain(), c->stream);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = sync_stream(c);
-        if (e != hipSuccess) rc = fail(HICMI_EHIP, "counting a chunk of pairs: %s", hipGetErrorString(e));
+        rc = wait_launched(c, "counting a chunk of pairs");
     }
     if (rc) { ends_abandon(c); return rc; }
     return HICMI_OK;
@@ -1604,7 +1561,7 @@ int hicmi_ends_finish(hicmi_ctx* c, uint64_t* table_out, uint64_t* counters6_out
     return ends_close(c, table_out, counters6_out);
 }
 
-// The same over the pair file in one pass: the chunk loop of hicmi_span_file with the table of one build in place of the marks.
+// The same over the pair file in one pass: pair_file_pass with the table of one build.
 int hicmi_ends_file(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
                     const int32_t* lift_seq, const int64_t* lift_off, const uint8_t* lift_rev, const int64_t* seq_size, int64_t n_seq,
                     int64_t window, int64_t reach, hicmi_ctx* c, int threads, int64_t* stats5, uint64_t* table_out,
@@ -1661,10 +1618,7 @@ static void anchor_abandon(hicmi_ctx* c)
 constexpr bool kAnchorPlainByDefault = false;
 static bool anchor_plain()
 {
-    const char* env = getenv("HICMI_ANCHOR_PLAIN");
-    if (env && !strcmp(env, "1")) return true;
-    if (env && !strcmp(env, "0")) return false;
-    return kAnchorPlainByDefault;
+    return plain_switch(getenv("HICMI_ANCHOR_PLAIN"), kAnchorPlainByDefault);
 }
 
 // the blocks of a build, made on the host before anything is allocated
@@ -1710,10 +1664,7 @@ static int anchor_open(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, c
     if (!rc && target) rc = upload(c, c->d_anchor_target, target, sizeof(int32_t) * (size_t)n_scaf);
     if (!rc && target) rc = upload(c, c->d_anchor_target + n_scaf, blocks.rank.data(), sizeof(int32_t) * (size_t)n_scaf);
     if (!rc) rc = lift_upload(c, c->d_anchor_lift, scaf_size, n_scaf, lift, &c->anchor_lift);
-    hipError_t e = hipSuccess;
-    if (!rc && (e = hipMemsetAsync(c->anchor_table, 0, sizeof(uint64_t) * (size_t)(m + ANCHOR_COUNTERS), c->stream)) != hipSuccess)
-        rc = fail(HICMI_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e));
-    if (!rc && (e = sync_stream(c)) != hipSuccess) rc = fail(HICMI_EHIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
+    if (!rc) rc = zero_and_wait(c, c->anchor_table, sizeof(uint64_t) * (size_t)(m + ANCHOR_COUNTERS));
     if (rc) { anchor_abandon(c); return rc; }
     c->anchor_grid.first = c->d_anchor_first; c->anchor_grid.seq_first = c->d_anchor_first + n_scaf;
     c->anchor_grid.target = target ? (const int32_t*)c->d_anchor_target : nullptr;
@@ -1728,14 +1679,7 @@ static int anchor_open(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, c
 static int anchor_close(hicmi_ctx* c, uint64_t* table_out, uint64_t* counters6_out)
 {
     struct Close { hicmi_ctx* c; ~Close() { anchor_abandon(c); } } closing{c};
-    const int64_t m = c->anchor_cells;
-    uint64_t counters[ANCHOR_COUNTERS];
-    int rc = download(c, counters, c->anchor_table + m, sizeof(counters));
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(table_out, c->anchor_table, sizeof(uint64_t) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(sync_stream(c));
-    memcpy(counters6_out, counters, sizeof(counters));
-    return HICMI_OK;
+    return download_table(c, c->anchor_table, c->anchor_cells, ANCHOR_COUNTERS, table_out, counters6_out);
 }
 
 int hicmi_anchor_begin(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf, const int32_t* lift_seq, const int64_t* lift_off,
@@ -1764,18 +1708,12 @@ int hicmi_anchor_add_pairs(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* p
     if (n == 0) return HICMI_OK;
     HIPCHK(hipSetDevice(c->device));
     // a HIP error from here on gives the build up: what was counted so far cannot be told
-    int rc = ensure(c->d_map_chunk, 24 * n);
-    const MapChunk k = map_chunk_at(c->d_map_chunk, n);
-    if (!rc) rc = upload(c, k.pos_a, pos_a, sizeof(int64_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.pos_b, pos_b, sizeof(int64_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.scaf_a, scaf_a, sizeof(int32_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.scaf_b, scaf_b, sizeof(int32_t) * (size_t)n);
+    MapChunk k;
+    int rc = stage_chunk(c, scaf_a, pos_a, scaf_b, pos_b, n, &k);
     if (!rc) {
         launch_anchor_count(k.scaf_a, k.pos_a, k.scaf_b, k.pos_b, n, c->anchor_lift, c->anchor_grid, c->anchor_cells, c->anchor_table,
                             c->anchor_table + c->anchor_cells, anchor_plain(), c->stream);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = sync_stream(c);
-        if (e != hipSuccess) rc = fail(HICMI_EHIP, "counting a chunk of pairs: %s", hipGetErrorString(e));
+        rc = wait_launched(c, "counting a chunk of pairs");
     }
     if (rc) { anchor_abandon(c); return rc; }
     return HICMI_OK;
@@ -1789,7 +1727,7 @@ int hicmi_anchor_finish(hicmi_ctx* c, uint64_t* table_out, uint64_t* counters6_o
     return anchor_close(c, table_out, counters6_out);
 }
 
-// The same over the pair file in one pass: the chunk loop of hicmi_span_file and hicmi_ends_file with the table of one build.
+// The same over the pair file in one pass: pair_file_pass with the table of one build.
 int hicmi_anchor_file(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
                       const int32_t* lift_seq, const int64_t* lift_off, const uint8_t* lift_rev, const int64_t* seq_size, int64_t n_seq,
                       const int32_t* target, int64_t window, hicmi_ctx* c, int threads, int64_t* stats5, uint64_t* table_out,
@@ -1878,8 +1816,7 @@ int hicmi_group_sums(hicmi_ctx* c, const int32_t* grp, const int32_t* scaf, int6
     memcpy(&img[(size_t)o_gc0], gc0.data(), sizeof(int32_t) * (size_t)(G + 1));
     memcpy(&img[(size_t)o_scaf], scaf, sizeof(int32_t) * (size_t)n);
     memcpy(&img[(size_t)o_soff], soff.data(), sizeof(int32_t) * (size_t)(S + 1));
-    const char* env = getenv("HICMI_GROUP_SUPPORT_PLAIN");
-    const bool plain = env && !strcmp(env, "1");
+    const bool plain = plain_switch(getenv("HICMI_GROUP_SUPPORT_PLAIN"), false);
     HIPCHK(hipSetDevice(c->device));
     const int64_t o_bin = plain ? 0 : NC * n, o_sc = o_bin + n * G, n_dbl = o_sc + S * G;
     int rc = ensure(c->d_gs_lists, n_ints);
@@ -1931,8 +1868,7 @@ int hicmi_junction_sums(hicmi_ctx* c, const int32_t* bins, int64_t n_listed, con
         n_wg += d.n_slabs;
         max_d = std::max<int64_t>(max_d, q[2] + q[5] - 1);
     }
-    const char* env = getenv("HICMI_JUNCTIONS_PLAIN");
-    const bool plain = env && !strcmp(env, "1");
+    const bool plain = plain_switch(getenv("HICMI_JUNCTIONS_PLAIN"), false);
     if (!plain && n_wg > INT_MAX) return fail(HICMI_EUNSUPPORTED, "%lld workgroups: at most 2^31 - 1", (long long)n_wg);
     std::vector<double> w((size_t)max_d + 1);
     w[0] = 0.0;
@@ -2004,8 +1940,7 @@ int hicmi_ice_balance(hicmi_ctx* c, const uint8_t* mask, int64_t max_iter, doubl
     if (rc) return rc;
     if (max_iter < 1 || max_iter > (1 << 20)) return fail(HICMI_EINVAL, "max_iter = %lld outside 1 .. 2^20", (long long)max_iter);
     if (!(eps >= 0.0)) return fail(HICMI_EINVAL, "eps must be >= 0");
-    const char* env = getenv("HICMI_ICE_INPLACE");
-    const bool inplace = env && !strcmp(env, "1");
+    const bool inplace = plain_switch(getenv("HICMI_ICE_INPLACE"), false);
     HIPCHK(hipSetDevice(c->device));
     if ((rc = ice_matrix_changed(c))) return rc;
     const int n = (int)c->n;

@@ -22,22 +22,13 @@ static void pairs_abandon(hicmi_ctx* c)
 constexpr bool kPairsPlainByDefault = false;
 static bool pairs_plain()
 {
-    const char* env = getenv("HICMI_PAIRS_PLAIN");
-    if (env && !strcmp(env, "1")) return true;
-    if (env && !strcmp(env, "0")) return false;
-    return kPairsPlainByDefault;
+    return plain_switch(getenv("HICMI_PAIRS_PLAIN"), kPairsPlainByDefault);
 }
 
 // HICMI_PAIRS_FIRST_PAIRS, the first capacity of a store; read per begin
 static int pairs_first_setting(int64_t* out)
 {
-    *out = PAIRS_FIRST_PAIRS;
-    if (const char* env = getenv("HICMI_PAIRS_FIRST_PAIRS")) {
-        const long long v = atoll(env);
-        if (v < 1 || v > ((long long)1 << 31)) return fail(HICMI_EINVAL, "HICMI_PAIRS_FIRST_PAIRS = %s outside 1 .. 2^31", env);
-        *out = v;
-    }
-    return HICMI_OK;
+    return setting_in_range("HICMI_PAIRS_FIRST_PAIRS", getenv("HICMI_PAIRS_FIRST_PAIRS"), 31, PAIRS_FIRST_PAIRS, out);
 }
 
 static unsigned long long* pairs_length(hicmi_ctx* c) { return c->d_pairs_intra + c->pairs_size.size(); }
@@ -119,12 +110,8 @@ int hicmi_pairs_add(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos_a, c
     c->links_ready = false;                                        // rows counted before these pairs are not the store's any more
     HIPCHK(hipSetDevice(c->device));
     // a HIP error from here on gives the store up: what was kept so far cannot be told
-    int rc = ensure(c->d_map_chunk, 24 * n);
-    const MapChunk k = map_chunk_at(c->d_map_chunk, n);
-    if (!rc) rc = upload(c, k.pos_a, pos_a, sizeof(int64_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.pos_b, pos_b, sizeof(int64_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.scaf_a, scaf_a, sizeof(int32_t) * (size_t)n);
-    if (!rc) rc = upload(c, k.scaf_b, scaf_b, sizeof(int32_t) * (size_t)n);
+    MapChunk k;
+    int rc = stage_chunk(c, scaf_a, pos_a, scaf_b, pos_b, n, &k);
     if (!rc) rc = pairs_keep_chunk(c, k, n, pairs_plain());
     if (!rc) {
         const hipError_t e = sync_stream(c);
@@ -135,7 +122,7 @@ int hicmi_pairs_add(hicmi_ctx* c, const int32_t* scaf_a, const int64_t* pos_a, c
     return HICMI_OK;
 }
 
-// begin and every pair of the file in one pass with the chunk loop of hicmi_ends_file; a store is left only when the whole
+// begin and every pair of the file in one pass with pair_file_pass; a store is left only when the whole
 // file is down
 int hicmi_pairs_file(const char* path, const char* names_blob, const int64_t* name_off, int64_t n_names, const int64_t* scaf_size,
                      hicmi_ctx* c, int threads, int64_t* stats5)
@@ -292,10 +279,7 @@ static void seats_abandon(hicmi_ctx* c)
 constexpr bool kSeatsPlainByDefault = false;
 static bool seats_plain()
 {
-    const char* env = getenv("HICMI_SEATS_PLAIN");
-    if (env && !strcmp(env, "1")) return true;
-    if (env && !strcmp(env, "0")) return false;
-    return kSeatsPlainByDefault;
+    return plain_switch(getenv("HICMI_SEATS_PLAIN"), kSeatsPlainByDefault);
 }
 
 // What hicmi_anchor_resident would count in both of its modes if one placed scaffold alone were taken out of the ordering,
@@ -343,10 +327,8 @@ int hicmi_seats_resident(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf,
     // the table comes down into memory of the library's first: an error after it leaves every output as it was
     std::vector<uint64_t> table((size_t)m);
     uint64_t counters[SEATS_COUNTERS];
-    rc = download(c, counters, c->seats_table + m, sizeof(counters));
+    rc = download_table(c, c->seats_table, m, SEATS_COUNTERS, table.data(), counters);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(table.data(), c->seats_table, sizeof(uint64_t) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(sync_stream(c));
     seats_add_intra(intra.data(), lift_seq, n_scaf, counters);
     memcpy(table_out, table.data(), sizeof(uint64_t) * table.size());
     memcpy(counters5_out, counters, sizeof(counters));
@@ -360,10 +342,7 @@ int hicmi_seats_resident(hicmi_ctx* c, const int64_t* scaf_size, int64_t n_scaf,
 constexpr bool kLinksPlainByDefault = false;
 static bool links_plain()
 {
-    const char* env = getenv("HICMI_LINKS_PLAIN");
-    if (env && !strcmp(env, "1")) return true;
-    if (env && !strcmp(env, "0")) return false;
-    return kLinksPlainByDefault;
+    return plain_switch(getenv("HICMI_LINKS_PLAIN"), kLinksPlainByDefault);
 }
 
 // One pass over the store into a find-or-insert table sized for every key the call can see, the used slots compacted on

@@ -249,3 +249,17 @@ def test_header_and_binding_declare_the_exports():
         assert callable(getattr(_lib.Context, method))
     assert callable(_lib.parse_valid_pairs) and callable(_lib.build_maps)
     assert lib.hicmi_abi_version() == 1
+
+
+def test_the_pair_path_has_one_chunk_loop_one_staging_step_and_one_switch_reader():
+    csrc = os.path.join(ROOT, "hic_genome_assembler_amd", "csrc")
+    both = ""
+    for name in ("api.hip", "api_pairs.inc"):
+        with open(os.path.join(csrc, name)) as fh:
+            both += fh.read()
+    assert both.count('getenv("HICMI_BUILDMAP_CHUNK_PAIRS")') == 1          # the chunk setting is read in one place
+    assert both.count("map_chunk_at(c->d_map_chunk") == 1                    # host arrays are staged in one place
+    assert both.count('!strcmp(env, "1")') <= 1                              # no switch reader spelt out beside plain_switch
+    assert both.count("static int pair_file_pass(") == 1
+    loop = both[both.index("static int build_maps_loop("):both.index("int hicmi_build_maps(")]
+    assert "pair_file_pass(" in loop and "hipMemcpyAsync(" not in loop and "fopen(" not in loop

@@ -276,6 +276,47 @@ def test_build_maps_error_changes_no_context(chunk, tmp_path, monkeypatch):
         assert a.contacts_host().tobytes() == maps[0].tobytes() and b.contacts_host().tobytes() == maps[1].tobytes()
 
 
+@pytest.mark.parametrize("setting", ["0", str(2 ** 28 + 1)])
+def test_a_chunk_setting_out_of_range_is_refused_by_every_file_call(setting, tmp_path, monkeypatch):
+    """HICMI_BUILDMAP_CHUNK_PAIRS is read in one place for all seven passes over a pair file: each of them refuses a value
+    outside 1 .. 2^28 by name, before it opens a build or a store, and the context's matrix stays what it was."""
+    import liftmap_reference as lref
+    import split_reference as sref
+    from hic_genome_assembler_amd import _lib
+    names, sizes = _scaffolds()
+    path = _write(tmp_path, _odd_file()[0])
+    lift = lref.layout([[(3, "+"), (17, "-")], [(38, "+"), (0, "+")]], sizes, 100, drop_unplaced=True)
+    first, start = sref.make_pieces(sizes, {3: [R], 38: [5, 2 * R]})[:2]
+    _set_form(monkeypatch, "default")
+    monkeypatch.setenv("HICMI_BUILDMAP_CHUNK_PAIRS", setting)
+    held = np.arange(16, dtype=np.float64).reshape(4, 4)
+    held = held + held.T
+    with _lib.Context(0) as ctx:
+        ctx.set_contacts(held)
+        calls = {
+            "build_maps": lambda: _lib.build_maps(path, names, sizes, [R], [ctx]),
+            "lift_maps": lambda: _lib.lift_maps(path, names, sizes, *lift, [R], [ctx]),
+            "split_maps": lambda: _lib.split_maps(path, names, sizes, first, start, [R], [ctx]),
+            "span_file": lambda: _lib.span_file(path, names, sizes, *lift, R, 0, 1, [], ctx),
+            "ends_file": lambda: _lib.ends_file(path, names, sizes, *lift, R, 1, ctx),
+            "anchor_file": lambda: _lib.anchor_file(path, names, sizes, *lift, None, R, ctx),
+            "pairs_file": lambda: _lib.pairs_file(path, names, sizes, ctx),
+        }
+        for name, call in calls.items():
+            with pytest.raises(_lib.HicmiError) as exc:
+                call()
+            assert "error %d:" % EINVAL in str(exc.value) and "HICMI_BUILDMAP_CHUNK_PAIRS = %s " % setting in str(exc.value), name
+        assert ctx.n == 4 and ctx.contacts_host().tobytes() == held.tobytes()
+        for closing in (ctx.map_finish, lambda: ctx.span_finish(1, []), ctx.ends_finish, ctx.anchor_finish, ctx.pairs_info):
+            with pytest.raises(_lib.HicmiError):                                 # nothing was left open
+                closing()
+        # the same calls with the setting gone, on the same context
+        monkeypatch.delenv("HICMI_BUILDMAP_CHUNK_PAIRS")
+        assert _lib.pairs_file(path, names, sizes, ctx)[:4] == _odd_file()[1]
+        assert _lib.build_maps(path, names, sizes, [R], [ctx])[:4] == _odd_file()[1]
+        assert ctx.contacts_host().tobytes() == _odd_file()[2][0].tobytes()
+
+
 # ---- round trip and drop-in ------------------------------------------------------------------------------------------------
 def _read(path):
     with open(path, "rb") as fh:

@@ -40,6 +40,40 @@ def test_no_device_fails_loudly(lib):
         lib.Context(0)
 
 
+def test_pair_arrays_and_names_with_sizes_as_the_library_takes_them():
+    from hic_genome_assembler_amd import _lib
+    # lists, a strided view and a wider integer type all become contiguous vectors of the library's types
+    wide = np.arange(12, dtype=np.int64)
+    sa, pa, sb, pb = _lib._pair_arrays([0, 1, 2], wide[::4], np.array([2, 1, 0], np.int16), (7, 8, 9))
+    assert [a.dtype for a in (sa, pa, sb, pb)] == [np.int32, np.int64, np.int32, np.int64]
+    assert all(a.flags.c_contiguous and a.shape == (3,) for a in (sa, pa, sb, pb))
+    assert (sa.tolist(), pa.tolist(), sb.tolist(), pb.tolist()) == ([0, 1, 2], [0, 4, 8], [2, 1, 0], [7, 8, 9])
+    held = np.array([5, 6], np.int32)
+    assert _lib._pair_arrays(held, [1, 2], held, [3, 4])[0] is held          # what already fits is not copied
+    assert all(len(a) == 0 for a in _lib._pair_arrays([], [], [], []))
+    for bad in (([0, 1], [1], [0, 1], [1, 2]), ([0], [1], [0], [1, 2]), ([[0, 1]], [[1, 2]], [[0, 1]], [[1, 2]])):
+        with pytest.raises(ValueError, match="^the four arrays must be vectors of one length$"):
+            _lib._pair_arrays(*bad)
+
+    names = ["scaffold_1", "scäffold_2", ""]
+    blob, off, size = _lib._names_and_sizes(names, [10, 20, 30])
+    assert blob == "".join(names).encode("utf-8") and off.dtype == np.int64 and off.tolist() == [0, 10, 21, 21]
+    assert size.dtype == np.int64 and size.flags.c_contiguous and size.tolist() == [10, 20, 30]
+    kept = np.array([1, 2, 3], np.int64)
+    assert _lib._names_and_sizes(names, kept)[2] is kept
+    assert _lib._names_and_sizes(names, np.arange(6, dtype=np.int32)[::2])[2].flags.c_contiguous
+    for bad in ([10, 20], [10, 20, 30, 40], [[10, 20, 30]], 10):
+        with pytest.raises(ValueError, match="^one size per scaffold name$"):
+            _lib._names_and_sizes(names, bad)
+    with pytest.raises(ValueError, match="^one size per scaffold name$"):
+        _lib._names_and_sizes([], [1])
+    # a caller's second condition is refused in the same sentence, whichever of the two fails
+    for sizes, ok in (([10, 20], True), ([10, 20, 30], False)):
+        with pytest.raises(ValueError, match="^one size per scaffold name and one name per piece$"):
+            _lib._names_and_sizes(names, sizes, ok, " and one name per piece")
+    assert _lib._names_and_sizes(names, [1, 2, 3], True, " and one name per piece")[2].tolist() == [1, 2, 3]
+
+
 def test_host_hypergeom_matches_scipy(lib):
     from scipy.stats import hypergeom
     assert lib.hypergeom_sf(8, 600, 50, 50) == pytest.approx(0.045750386176022624, rel=1e-12)

@@ -180,7 +180,9 @@ def test_the_kernel_form_is_read_at_every_call_and_the_constants_are_named():
         make = fh.read()
     assert " split.h " in make and " k_split.hip " in make
     # one chunk loop: the split pass is an argument of build_maps_loop, and the split calls read no contact matrix
-    assert api.count("static int build_maps_loop(") == 1 and api.count("hicmi_parse_valid_pairs(") == 2
+    assert api.count("static int build_maps_loop(") == 1 and api.count("hicmi_parse_valid_pairs(") == 1
+    with open(os.path.join(CSRC, "api_pairs.inc")) as fh:
+        assert fh.read().count("hicmi_parse_valid_pairs(") == 0
     split_code = api[api.index("struct SplitHost"):api.index("// The chunk loop of hicmi_build_maps")]
     assert "c->dC" not in split_code and "map_cells" not in split_code and "drop_matrix_state" not in split_code
 
