@@ -124,6 +124,7 @@ SIGNATURES = {
     "hicmi_links_resident": (ctypes.c_int, [_vp, _vp, c_i64, c_i64, ctypes.POINTER(c_i64), _vp]),
     "hicmi_links_fetch": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "hicmi_links_info": (ctypes.c_int, [_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_double)]),
+    "hicmi_links_lifted": (ctypes.c_int, [_vp, _vp, c_i64, _vp, _vp, _vp, _vp, c_i64, c_i64, ctypes.POINTER(c_i64), _vp]),
     "hicmi_split_pairs": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, c_i64, _vp, c_i64, _vp, _vp, c_i64, _vp, _vp, _vp, _vp, _vp]),
     "hicmi_split_maps": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _vp, c_i64, _vp, _vp, _vp, c_i64, c_i64, _vp, _vp,
                                         ctypes.c_int, _vp, _vp]),
@@ -942,8 +943,22 @@ class Context:
         _check(self._lib.hicmi_links_fetch(self._h, _ptr(lo), _ptr(hi), _ptr(counts)))
         return lo, hi, counts, counters
 
+    def links_lifted(self, sizes, lift_seq, lift_off, lift_rev, seq_sizes, window):
+        """The end-link graph between the ends of sequences that consist of several scaffolds (hicmi_links_lifted and
+        hicmi_links_fetch): ``links_resident`` with both ends of every pair lifted onto the sequences first.
+        Returns (lo int32[E], hi int32[E], counts uint64[E, 5], counters uint64[4] = (linked, middle, inside, unlifted));
+        ``lo`` and ``hi`` are sequence indices.  The store is only read."""
+        size, seq, off, rev, seq_size = _lift_tables(sizes, lift_seq, lift_off, lift_rev, seq_sizes)
+        counters, n_rows = np.zeros(4, np.uint64), c_i64()
+        _check(self._lib.hicmi_links_lifted(self._h, _ptr(size), len(size), _ptr(seq), _ptr(off), _ptr(rev), _ptr(seq_size),
+                                            len(seq_size), int(window), ctypes.byref(n_rows), _ptr(counters)))
+        lo, hi = np.zeros(n_rows.value, np.int32), np.zeros(n_rows.value, np.int32)
+        counts = np.zeros((n_rows.value, 5), np.uint64)
+        _check(self._lib.hicmi_links_fetch(self._h, _ptr(lo), _ptr(hi), _ptr(counts)))
+        return lo, hi, counts, counters
+
     def links_info(self):
-        """(records, slots, sort_ms) of the last ``links_resident`` call (hicmi_links_info): the used slots of its table, the
+        """(records, slots, sort_ms) of the last ``links_resident`` or ``links_lifted`` call (hicmi_links_info): the used slots of its table, the
         slots the table had, and the milliseconds the host took to sort the records."""
         n_rec, n_slots, ms = c_i64(), c_i64(), ctypes.c_double()
         _check(self._lib.hicmi_links_info(self._h, ctypes.byref(n_rec), ctypes.byref(n_slots), ctypes.byref(ms)))

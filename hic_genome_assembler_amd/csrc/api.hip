@@ -244,6 +244,9 @@ struct hicmi_ctx {
     // sizes on the device, and the rows of the last call on the host, sorted by (lo, hi); links_ready: there are rows to fetch
     DevBuf<unsigned long long> d_links_table, d_links_recs;
     DevBuf<int64_t> d_links_size;
+    // hicmi_links_lifted, for the time of one call: the lift tables as lift_upload lays them out, the sequence sizes
+    DevBuf<unsigned char> d_links_lift;
+    DevBuf<int64_t> d_links_seq_size;
     std::vector<int32_t> links_lo, links_hi;
     std::vector<uint64_t> links_counts;
     bool links_ready = false;
@@ -1770,6 +1773,9 @@ int hicmi_anchor_file(const char* path, const char* names_blob, const int64_t* n
 
 // ---- the resident pair store: hicmi_pairs_*, hicmi_ends_resident, hicmi_anchor_resident --------------------
 #include "api_pairs.inc"
+
+// ---- the end-link graph on lifted ends: hicmi_links_lifted, on the store and the rows of the calls above ----
+#include "api_links.inc"
 
 // Group support: extends the scaffold vote of assessChromosomeClustering (S2C:1001-1077) with the
 // contacts themselves.  The host sorts the grouped rows by group and cuts them into chunks of GS_CHUNK; the kernels of

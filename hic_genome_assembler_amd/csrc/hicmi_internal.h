@@ -603,6 +603,15 @@ struct LinksTable {
 };
 void launch_links_count(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
                         const int64_t* scaf_size, int64_t n_scaf, int64_t window, const LinksTable& table, bool plain, hipStream_t s);
+// The count on lifted ends (hicmi_links_lifted): the same table with LINKS_LIFTED_EXTRAS integers behind the
+// counts.  The first LINKS_EXTRAS are what they are above, so links_add_global and k_links_compact find the flag and the
+// number of records where they look for them; the counters of the kinds INSIDE and UNLIFTED follow.  seq_size: n_seq sizes
+// of the sequences of `lift`, device memory.
+static constexpr int LINKS_LIFTED_EXTRAS = LINKS_EXTRAS + (LINKS_LIFTED_COUNTERS - LINKS_COUNTERS);
+constexpr int links_lifted_extra(int kind) { return kind < LINKS_COUNTERS ? kind : LINKS_EXTRAS + (kind - LINKS_COUNTERS); }
+void launch_links_count_lifted(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
+                               const LiftTables& lift, const int64_t* seq_size, int64_t window, const LinksTable& table, bool plain,
+                               hipStream_t s);
 // the used slots as rec_cap (key, count) records at the most, in no order
 void launch_links_compact(const LinksTable& table, void* rec_key, void* rec_cnt, int64_t rec_cap, hipStream_t s);
 

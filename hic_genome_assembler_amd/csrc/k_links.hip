@@ -14,6 +14,10 @@
 //                          goes to the global table directly.  Then every used slot issues one global find-or-insert and add.
 //                          Both forms count the two kinds of pairs per wave (a ballot per kind), per workgroup in LDS, and
 //                          add two numbers per workgroup to the global counters.
+//   k_links_count_lifted   the same two forms for hicmi_links_lifted: every end is lifted onto its sequence
+//                          first - its scaffold's sequence, offset, reversal and size are gathered from the lift tables, then
+//                          the size of its sequence - and the key is that of the two sequences (links_classify_lifted).  Four
+//                          kinds of pairs, counted the same way: a ballot per kind and wave, four numbers per workgroup.
 //   k_links_compact        the used slots into (key, count) records: a workgroup counts the used ones of LINKS_COMPACT_SLICE
 //                          slots (a ballot per wave), bumps the record count once, and places them behind that (a ballot per
 //                          wave, a cursor in LDS).  The order of the records is the race's; the host sorts them.
@@ -26,6 +30,8 @@ static_assert(LINKS_SLICE % 256 == 0 && LINKS_COMPACT_SLICE % 256 == 0, "lane t 
 static_assert(LINKS_PROBES >= 1 && LINKS_PROBES <= LINKS_SLOTS, "a probe sequence does not lap the table");
 static_assert(LINKS_SLOTS * (sizeof(unsigned long long) + sizeof(unsigned int)) <= 64 * 1024, "key and count of every slot fit the LDS of a workgroup");
 static_assert(LINKS_EXTRAS == LINKS_COUNTERS + 2, "the counters, the flag and the number of records");
+static_assert(LINKS_LIFTED_LINKED == LINKS_LINKED && LINKS_LIFTED_MIDDLE == LINKS_MIDDLE && links_lifted_extra(LINKS_LIFTED_INSIDE) == LINKS_EXTRAS &&
+              links_lifted_extra(LINKS_LIFTED_UNLIFTED) == LINKS_LIFTED_EXTRAS - 1, "the lifted count keeps the flag and the records where they are");
 
 // `add` at `key` in the global table: the slot that holds the key, or the first free one of its probe sequence
 __device__ __forceinline__ void links_add_global(const LinksTable& T, unsigned long long key, unsigned long long add)
@@ -92,6 +98,48 @@ __global__ __launch_bounds__(256) void k_links_count(const int32_t* __restrict__
     if (t < LINKS_COUNTERS && s_kind[t]) atomicAdd(T.extras + t, (unsigned long long)s_kind[t]);
 }
 
+// The count on lifted ends.  The table in LDS, the probing and the spill are those of k_links_count; the lift tables and the
+// sequence sizes are a few bytes per scaffold, read by every pair and so served from the caches.
+template <bool PLAIN>
+__global__ __launch_bounds__(256) void k_links_count_lifted(const int32_t* __restrict__ scaf_a, const int64_t* __restrict__ pos_a,
+                                                            const int32_t* __restrict__ scaf_b, const int64_t* __restrict__ pos_b, int64_t n,
+                                                            LiftTables L, const int64_t* __restrict__ seq_size, int64_t window, LinksTable T)
+{
+    __shared__ unsigned long long s_key[PLAIN ? 1 : LINKS_SLOTS];
+    __shared__ unsigned int s_cnt[PLAIN ? 1 : LINKS_SLOTS];
+    __shared__ unsigned int s_kind[LINKS_LIFTED_COUNTERS];
+    const int t = threadIdx.x;
+    if (!PLAIN)
+        for (int s = t; s < LINKS_SLOTS; s += 256) { s_key[s] = LINKS_EMPTY; s_cnt[s] = 0u; }
+    if (t < LINKS_LIFTED_COUNTERS) s_kind[t] = 0u;
+    __syncthreads();
+    constexpr int kPerLane = PLAIN ? 1 : LINKS_SLICE / 256;
+    const int64_t base = (int64_t)blockIdx.x * (256 * kPerLane);
+    for (int u = 0; u < kPerLane; u++) {
+        const int64_t p = base + u * 256 + t;
+        int kind = LINKS_LIFTED_NOWHERE;
+        uint64_t key = LINKS_EMPTY;
+        if (p < n) kind = links_classify_lifted(L, seq_size, scaf_a[p], pos_a[p], scaf_b[p], pos_b[p], window, &key);
+        if (kind == LINKS_LIFTED_LINKED || kind == LINKS_LIFTED_MIDDLE) {
+            if (PLAIN) links_add_global(T, (unsigned long long)key, 1ull);
+            else links_add_lds(s_key, s_cnt, T, (unsigned long long)key);
+        }
+        // the four counters: one ballot per kind and wave (every lane of the wave is here: no lane left the loop)
+#pragma unroll
+        for (int k = 0; k < LINKS_LIFTED_COUNTERS; k++) {
+            const unsigned long long who = __ballot(kind == k);
+            if ((t & 63) == 0 && who) atomicAdd(&s_kind[k], (unsigned int)__popcll(who));
+        }
+    }
+    __syncthreads();
+    if (!PLAIN)
+        for (int s = t; s < LINKS_SLOTS; s += 256) {
+            const unsigned long long key = s_key[s];
+            if (key != LINKS_EMPTY) links_add_global(T, key, (unsigned long long)s_cnt[s]);
+        }
+    if (t < LINKS_LIFTED_COUNTERS && s_kind[t]) atomicAdd(T.extras + links_lifted_extra(t), (unsigned long long)s_kind[t]);
+}
+
 // the used slots as records; a record that finds no room (the host sized rec_cap for every key a call can see) raises the flag.
 // Two passes over the workgroup's LINKS_COMPACT_SLICE slots: the first counts the used ones, the second places them.
 __global__ __launch_bounds__(256) void k_links_compact(LinksTable T, unsigned long long* __restrict__ rec_key,
@@ -141,6 +189,19 @@ void launch_links_count(const int32_t* scaf_a, const int64_t* pos_a, const int32
     else
         hipLaunchKernelGGL((k_links_count<false>), dim3((unsigned)((n + LINKS_SLICE - 1) / LINKS_SLICE)), dim3(256), 0, s, scaf_a, pos_a,
                            scaf_b, pos_b, n, scaf_size, n_scaf, window, table);
+}
+
+void launch_links_count_lifted(const int32_t* scaf_a, const int64_t* pos_a, const int32_t* scaf_b, const int64_t* pos_b, int64_t n,
+                               const LiftTables& lift, const int64_t* seq_size, int64_t window, const LinksTable& table, bool plain,
+                               hipStream_t s)
+{
+    if (n <= 0) return;
+    if (plain)
+        hipLaunchKernelGGL((k_links_count_lifted<true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, scaf_a, pos_a, scaf_b, pos_b,
+                           n, lift, seq_size, window, table);
+    else
+        hipLaunchKernelGGL((k_links_count_lifted<false>), dim3((unsigned)((n + LINKS_SLICE - 1) / LINKS_SLICE)), dim3(256), 0, s, scaf_a,
+                           pos_a, scaf_b, pos_b, n, lift, seq_size, window, table);
 }
 
 void launch_links_compact(const LinksTable& table, void* rec_key, void* rec_cnt, int64_t rec_cap, hipStream_t s)

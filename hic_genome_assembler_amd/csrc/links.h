@@ -38,6 +38,33 @@ LIFT_HD int links_classify(const int64_t* scaf_size, int64_t n_scaf, int32_t sa,
     return combo == LINKS_OTHER ? LINKS_MIDDLE : LINKS_LINKED;
 }
 
+// what a stored pair is to the counters of a count on lifted ends, checked in the order UNLIFTED, INSIDE,
+// MIDDLE; what is left is LINKED.  The first two values are those of LinksKind.
+enum LinksLiftedKind { LINKS_LIFTED_LINKED = 0, LINKS_LIFTED_MIDDLE = 1, LINKS_LIFTED_INSIDE = 2, LINKS_LIFTED_UNLIFTED = 3,
+                       LINKS_LIFTED_COUNTERS = 4, LINKS_LIFTED_NOWHERE = -1 };
+
+// The kind of the pair (sa, pa, sb, pb) between the ends of sequences that consist of several scaffolds, and for LINKED and
+// MIDDLE its key.  Both ends are lifted (liftmap.h); an end on a dropped scaffold makes the pair UNLIFTED, two ends in one
+// sequence make it INSIDE.  The zone of an end is that of its lifted 1-based position on its sequence read left to right:
+// the bases of a gap belong to a zone and hold no read.  The key is that of the sequences in index order.  NOWHERE: a pair
+// the store never holds (one scaffold, or an end outside the tables or its scaffold).
+LIFT_HD int links_classify_lifted(const LiftTables& L, const int64_t* seq_size, int32_t sa, int64_t pa, int32_t sb, int64_t pb,
+                                  int64_t window, uint64_t* key_out)
+{
+    if (sa == sb) return LINKS_LIFTED_NOWHERE;
+    int32_t qa, qb;
+    int64_t ya = 0, yb = 0;
+    const bool ok_a = lift_end(L, sa, pa, &qa, &ya), ok_b = lift_end(L, sb, pb, &qb, &yb);
+    if (!ok_a || !ok_b) return qa >= -1 && qb >= -1 ? LINKS_LIFTED_UNLIFTED : LINKS_LIFTED_NOWHERE;
+    if (qa == qb) return LINKS_LIFTED_INSIDE;
+    const int za = ends_zone(seq_size[qa], ya, false, window), zb = ends_zone(seq_size[qb], yb, false, window);
+    const bool a_low = qa < qb;
+    const int zlo = a_low ? za : zb, zhi = a_low ? zb : za;
+    const int combo = zlo == ENDS_MID || zhi == ENDS_MID ? LINKS_OTHER : zlo * 2 + zhi;
+    *key_out = links_key(a_low ? qa : qb, a_low ? qb : qa, combo);
+    return combo == LINKS_OTHER ? LINKS_LIFTED_MIDDLE : LINKS_LIFTED_LINKED;
+}
+
 // The slot a key starts its probe sequence at in a table of 2^bits slots (1 <= bits <= 63): the high bits of the product
 // with 2^64 / phi, so that the consecutive keys of one scaffold pair and of neighbouring scaffolds spread over the table.
 LIFT_HD uint64_t links_slot(uint64_t key, int bits) { return (key * 0x9E3779B97F4A7C15ull) >> (64 - bits); }

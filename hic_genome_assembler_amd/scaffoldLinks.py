@@ -10,13 +10,20 @@ partner of every scaffold end with a verdict, the paths the reciprocal best ends
 ``polishOrder`` take - and, with ``-order``, an audit of every junction of an order file against the read pairs.
 
     python -m hic_genome_assembler_amd.scaffoldLinks -config my_config.txt [-window 50000] [-minPairs 4] [-minRatio 2] \\
-           [-minSize 0] [-order FILE] [-out DIR] [-threads 0] [-device 0]
+           [-minSize 0] [-order FILE] [-rounds 1] [-growth 1] [-gap 100] [-out DIR] [-threads 0] [-device 0]
+
+With ``-rounds R`` above 1 the tool iterates as those scaffolders do: the paths of a round are the
+sequences of the next, laid out as ``assembledMap`` lays out a chromosome with ``-gap`` bases between neighbours, and round
+r counts the pairs between the end zones of those sequences - both ends of every stored pair lifted, one more pass over the
+store - at the window of the round before times ``-growth``.  The same verdicts, ``-minPairs``, ``-minRatio`` and
+``-minSize`` then apply to sequences.  The loop ends ``nothing_left`` after a round that keeps no join and ``round_limit``
+after round R; a join is never undone in a later round.  Round 1 writes what it writes without the flag; round r writes
+``round<r>/sequences.tsv``, ``links.tsv``, ``ends.tsv`` and ``paths.order``, and the run ``rounds.tsv`` and ``final.order``.
 
 Verdicts of a scaffold end, checked in this order: ``too_small`` (the scaffold is below ``-minSize``: it neither chooses nor
 is chosen), ``no_links``, ``weak`` (the best partner end has fewer than ``-minPairs`` pairs), ``tied`` (two ends share the
 maximum), ``ambiguous`` (the best is below ``-minRatio`` times the best end of any other scaffold), ``one_sided`` (the chosen
-end chose another) and ``joined`` (reciprocal).  There is no restriction-site normalisation and no second round that joins
-paths into chromosomes.  The defaults are choices, not tuned values.  A ``-window`` wider than the shortest scaffolds makes
+end chose another) and ``joined`` (reciprocal).  There is no restriction-site normalisation.  The defaults are choices, not tuned values.  A ``-window`` wider than the shortest scaffolds makes
 ends skip over them: a scaffold of up to two windows is all end zone, so its neighbours' ends see each other through it.
 """
 from __future__ import annotations
@@ -24,6 +31,7 @@ from __future__ import annotations
 import argparse
 import contextlib
 import io
+import math
 import os
 import sys
 
@@ -46,6 +54,10 @@ PATH_COLUMNS = ("path", "scaffolds", "bases", "fewest_pairs")
 JUNCTION_COLUMNS = ("chromosome", "left_scaffold", "left_end", "right_scaffold", "right_end", "pairs", "left_best", "left_best_pairs",
                     "right_best", "right_best_pairs", "verdict")
 CHOSE = ("one_sided", "joined")
+DEFAULT_ROUNDS, DEFAULT_GROWTH = 1, 1.0
+SEQUENCE_COLUMNS = ("sequence", "scaffolds", "bases", "members")
+ROUND_COLUMNS = ("round", "window", "sequences_in", "rows", "linked", "middle", "inside", "unlifted", "joins", "cycles_cut",
+                 "sequences_out", "paths", "singles")
 
 
 def zone_bases(size, window):
@@ -217,7 +229,138 @@ def junction_rows(asm, names, links, calls):
     return rows
 
 
-def check_arguments(window, minPairs, minRatio, minSize):
+def decide(lo, hi, counts, sizes, minPairs, minRatio, minSize):
+    """(links, calls, all joins, paths, cycles cut, kept joins) of one round from its rows and the sizes of its units."""
+    links = end_links(lo, hi, counts, len(sizes))
+    calls = end_calls(links, sizes, minPairs, minRatio, minSize)
+    all_joins = joins_of(calls)
+    return (links, calls, all_joins) + paths_of(all_joins, sizes)
+
+
+# ---- the later rounds (DESIGN.md 9u): the paths of one round are the sequences of the next -------------------------------------
+def expand_paths(sequences, paths):
+    """The sequences after a round, each [(scaffold, "+" / "-"), ...]: a path of sequences is expanded to scaffolds - a sequence
+    entered as ``-`` has its scaffolds in reverse order and every orientation flipped - and turned so that it starts at its
+    terminal scaffold of lower index; a sequence no path names stays as it is.  They are numbered by their first scaffold."""
+    flip = {"+": "-", "-": "+"}
+    out, used = [], set()
+    for path in paths:
+        members = []
+        for q, o in path:
+            used.add(q)
+            members += sequences[q] if o == "+" else [(s, flip[p]) for s, p in reversed(sequences[q])]
+        if members[-1][0] < members[0][0]:
+            members = [(s, flip[p]) for s, p in reversed(members)]
+        out.append(members)
+    out += [list(members) for q, members in enumerate(sequences) if q not in used]
+    return sorted(out, key=lambda members: members[0][0])
+
+
+def sequence_tables(sequences, sizes, gap):
+    """(lift_seq int32, lift_off int64, lift_rev uint8, seq_sizes int64) of the sequences laid out as assembledMap lays out a
+    chromosome: offsets from 0 and ``gap`` bases between neighbours.  Every scaffold lies in one sequence."""
+    n_scaf = len(sizes)
+    seq, off, rev = np.full(n_scaf, -1, np.int32), np.zeros(n_scaf, np.int64), np.zeros(n_scaf, np.uint8)
+    seq_sizes = np.zeros(len(sequences), np.int64)
+    for q, members in enumerate(sequences):
+        at = 0
+        for k, (s, o) in enumerate(members):
+            at += gap if k else 0
+            seq[s], off[s], rev[s] = q, at, o == "-"
+            at += int(sizes[s])
+        seq_sizes[q] = at
+    assert np.all(seq >= 0)
+    return seq, off, rev, seq_sizes
+
+
+def layout_paths(sequences, sizes):
+    """The sequences of two or more scaffolds as an order file has them: by scaffold bases descending, then by first scaffold."""
+    return sorted((m for m in sequences if len(m) > 1), key=lambda m: (-sum(int(sizes[s]) for s, _o in m), m[0][0]))
+
+
+def next_window(window, growth):
+    """floor(window x growth), kept inside 64 bits: beyond every sequence all windows are one."""
+    return min(int(math.floor(window * growth)), 1 << 62)
+
+
+def later_rounds(ctx, names, sizes, first_paths, window, rounds, growth, gap, minPairs, minRatio, minSize):
+    """Rounds 2 .. ``rounds`` on the resident store of ``ctx``, from the paths of round 1.  Returns (per-round dicts, how the
+    loop ended, the last sequences).  A round dict holds everything its files are written from."""
+    sequences = expand_paths([[(s, "+")] for s in range(len(names))], first_paths)
+    done, joined = [], len(first_paths) > 0
+    for r in range(2, rounds + 1):
+        if not joined:
+            break
+        window = next_window(window, growth)
+        tables = sequence_tables(sequences, sizes, gap)
+        lo, hi, counts, counters = ctx.links_lifted(sizes, *tables, window)
+        links, calls, all_joins, paths, cut, joins = decide(lo, hi, counts, tables[3], minPairs, minRatio, minSize)
+        after = expand_paths(sequences, paths)
+        done.append({"round": r, "window": window, "sequences": sequences, "seq_sizes": tables[3], "lo": lo, "hi": hi, "counts": counts,
+                     "counters": counters, "calls": calls, "all_joins": all_joins, "cut": cut, "after": after})
+        sequences, joined = after, len(joins) > 0
+    ended = "round_limit" if joined else "nothing_left"
+    return done, ended, sequences
+
+
+def table_texts(labels, sizes, window, lo, hi, counts, calls):
+    """The lines of links.tsv and of ends.tsv for units - scaffolds, or the sequences of a later round - of these labels and sizes."""
+    link_text = ["#" + "\t".join(LINK_COLUMNS) + "\n"]
+    for a, b, row in zip(lo.tolist(), hi.tolist(), counts.tolist()):
+        link_text.append("\t".join([labels[a], labels[b], str(sum(row))] + [str(x) for x in row[:4]]) + "\n")
+    end_text = ["#" + "\t".join(END_COLUMNS) + "\n"]
+    for e in range(2 * len(labels)):
+        call = calls[e]
+        cols = [labels[e // 2], END_NAMES[e % 2], str(zone_bases(sizes[e // 2], window)[e % 2]), str(call["links"])]
+        for which in ("best", "second"):
+            cols += ["NA", "NA", "NA"] if call[which] is None else [labels[call[which][0] // 2], END_NAMES[call[which][0] % 2], str(call[which][1])]
+        end_text.append("\t".join(cols + [place._ratio_text(call["ratio"]), call["verdict"]]) + "\n")
+    return link_text, end_text
+
+
+def write_order(path, names, sequences, sizes):
+    with contextlib.redirect_stdout(io.StringIO()):               # the writer reports what it wrote; this tool prints its own lines
+        writeScaffoldOrderingsToFile([[[names[s], o] for s, o in m] for m in layout_paths(sequences, sizes)], path)
+
+
+def write_rounds(outDir, names, sizes, first, done, ended, sequences):
+    """round<r>/ of every later round, rounds.tsv and final.order; one printed line per later round and a closing one."""
+    lines = ["#" + "\t".join(ROUND_COLUMNS) + "\n"]
+    for rnd in [first] + done:
+        r, after = rnd["round"], rnd["after"]
+        n_paths = sum(len(m) > 1 for m in after)
+        lines.append("\t".join(str(x) for x in [r, rnd["window"], len(rnd["sequences"]), len(rnd["lo"])] + [int(x) for x in rnd["counters"]]
+                               + [len(rnd["all_joins"]), rnd["cut"], len(after), n_paths, len(after) - n_paths]) + "\n")
+        if r == 1:
+            continue
+        labels = ["seq_%d" % (q + 1) for q in range(len(rnd["sequences"]))]
+        seq_text = ["#" + "\t".join(SEQUENCE_COLUMNS) + "\n"]
+        for label, members, bases in zip(labels, rnd["sequences"], rnd["seq_sizes"].tolist()):
+            seq_text.append("%s\t%d\t%d\t%s\n" % (label, len(members), bases, ",".join(names[s] + o for s, o in members)))
+        link_text, end_text = table_texts(labels, rnd["seq_sizes"], rnd["window"], rnd["lo"], rnd["hi"], rnd["counts"], rnd["calls"])
+        where = os.path.join(outDir, "round%d" % r)
+        os.makedirs(where, exist_ok=True)
+        for fn, text in (("sequences.tsv", seq_text), ("links.tsv", link_text), ("ends.tsv", end_text)):
+            with open(os.path.join(where, fn), "w") as fh:
+                fh.write("".join(text))
+        write_order(os.path.join(where, "paths.order"), names, after, sizes)
+        print("LINKS round %d: window %d, sequences %d, rows %d, joins %d, sequences out %d"
+              % (r, rnd["window"], len(rnd["sequences"]), len(rnd["lo"]), len(rnd["all_joins"]), len(after)))
+    lines.append("#ended=%s\n" % ended)
+    with open(os.path.join(outDir, "rounds.tsv"), "w") as fh:
+        fh.write("".join(lines))
+    write_order(os.path.join(outDir, "final.order"), names, sequences, sizes)
+    n_paths = sum(len(m) > 1 for m in sequences)
+    print("LINKS: %d rounds, ended %s, paths %d, singles %d" % (1 + len(done), ended, n_paths, len(sequences) - n_paths))
+
+
+def check_arguments(window, minPairs, minRatio, minSize, rounds=1, growth=1.0, gap=DEFAULT_GAP):
+    if rounds < 1:
+        raise ValueError("rounds %d is below 1" % rounds)
+    if not growth >= 1:
+        raise ValueError("growth %g is below 1" % growth)
+    if gap < 0:
+        raise ValueError("gap %d is negative" % gap)
     if window < 1:
         raise ValueError("the window %d is below 1" % window)
     if minPairs < 0:
@@ -229,16 +372,18 @@ def check_arguments(window, minPairs, minRatio, minSize):
 
 
 def runPipeline(configFile, window=DEFAULT_WINDOW, minPairs=DEFAULT_MIN_PAIRS, minRatio=DEFAULT_MIN_RATIO, minSize=DEFAULT_MIN_SIZE,
-                orderFile=None, outDir=None, threads=0, device=0, context=None):
-    """``context``: a context of the caller's that has ``pairs_file``, ``pairs_info``, ``links_resident`` and ``pairs_drop``;
-    None: a context of its own on ``device``.  Either way the file is loaded into the resident pair store once, counted in
-    one call and the store dropped.  Returns (stats4, joins [(end name, end name, pairs)], paths [[(name, orientation)]])."""
+                orderFile=None, outDir=None, threads=0, device=0, context=None, rounds=DEFAULT_ROUNDS, growth=DEFAULT_GROWTH,
+                gap=DEFAULT_GAP):
+    """``context``: a context of the caller's that has ``pairs_file``, ``pairs_info``, ``links_resident`` and ``pairs_drop``
+    (and ``links_lifted`` when ``rounds`` is above 1); None: a context of its own on ``device``.  Either way the file is
+    loaded into the resident pair store once, counted in one call per round and the store dropped.  Returns (stats4, joins
+    [(end name, end name, pairs)], paths [[(name, orientation)]]) of round 1."""
     from . import run_hicAssembler as driver
     v = driver.readConfigFileToVariables(configFile)
     if outDir is None:
         outDir = os.path.join(v["saveFilesDirectory"], "links")
     try:
-        check_arguments(window, minPairs, minRatio, minSize)
+        check_arguments(window, minPairs, minRatio, minSize, rounds, growth, gap)
         check_valid_pair_file(v["validPairFile"])
         names, sizes = read_scaffold_sizes(v["hicProScaffSizeFile"])
         if not names:
@@ -254,11 +399,18 @@ def runPipeline(configFile, window=DEFAULT_WINDOW, minPairs=DEFAULT_MIN_PAIRS, m
         sys.exit("ERROR... %s. Exiting..." % exc)
     n_scaf = len(names)
 
+    made = {"decided": None, "later": None}
+
     def count(ctx):
         stats = tuple(ctx.pairs_file(v["validPairFile"], names, sizes, threads=threads)[:4])
         try:
             n_kept, n_intra = ctx.pairs_info()[:2]
-            return (stats, int(n_kept), int(n_intra)) + tuple(ctx.links_resident(sizes, window))
+            first = tuple(ctx.links_resident(sizes, window))
+            if rounds > 1:                                        # the later rounds need the store; every file is written below
+                made["decided"] = decide(first[0], first[1], first[2], sizes, minPairs, minRatio, minSize)
+                made["later"] = later_rounds(ctx, names, sizes, made["decided"][3], window, rounds, growth, gap, minPairs, minRatio,
+                                             minSize)
+            return (stats, int(n_kept), int(n_intra)) + first
         finally:
             ctx.pairs_drop()
 
@@ -274,11 +426,12 @@ def runPipeline(configFile, window=DEFAULT_WINDOW, minPairs=DEFAULT_MIN_PAIRS, m
     if int(counts.sum()) != n_kept or int(counters.sum()) != n_kept:
         sys.exit("ERROR... the rows hold %d pairs and the counters %d where the store kept %d. Exiting..."
                  % (int(counts.sum()), int(counters.sum()), n_kept))
+    for rnd in made["later"][0] if made["later"] else ():
+        if int(rnd["counters"].sum()) != n_kept or int(rnd["counts"].sum()) != int(rnd["counters"][:2].sum()):
+            sys.exit("ERROR... round %d: the rows hold %d pairs and the counters %d where the store kept %d. Exiting..."
+                     % (rnd["round"], int(rnd["counts"].sum()), int(rnd["counters"].sum()), n_kept))
 
-    links = end_links(lo, hi, counts, n_scaf)
-    calls = end_calls(links, sizes, minPairs, minRatio, minSize)
-    all_joins = joins_of(calls)
-    paths, cut, joins = paths_of(all_joins, sizes)
+    links, calls, all_joins, paths, cut, joins = made["decided"] or decide(lo, hi, counts, sizes, minPairs, minRatio, minSize)
     in_paths = sum(len(p) for p in paths)
     header = ["window=%d" % window, "minPairs=%d" % minPairs, "minRatio=%g" % minRatio, "minSize=%d" % minSize]
     header += ["%s=%d" % kv for kv in zip(STATS_COLUMNS, stats)]
@@ -286,16 +439,7 @@ def runPipeline(configFile, window=DEFAULT_WINDOW, minPairs=DEFAULT_MIN_PAIRS, m
                "rows=%d" % len(lo), "joins=%d" % len(all_joins), "cycles_cut=%d" % cut, "paths=%d" % len(paths),
                "singles=%d" % (n_scaf - in_paths)]
 
-    link_text = ["#" + "\t".join(LINK_COLUMNS) + "\n"]
-    for a, b, row in zip(lo.tolist(), hi.tolist(), counts.tolist()):
-        link_text.append("\t".join([names[a], names[b], str(sum(row))] + [str(x) for x in row[:4]]) + "\n")
-    end_text = ["#" + "\t".join(END_COLUMNS) + "\n"]
-    for e in range(2 * n_scaf):
-        call = calls[e]
-        cols = [names[e // 2], END_NAMES[e % 2], str(zone_bases(sizes[e // 2], window)[e % 2]), str(call["links"])]
-        for which in ("best", "second"):
-            cols += ["NA", "NA", "NA"] if call[which] is None else [names[call[which][0] // 2], END_NAMES[call[which][0] % 2], str(call[which][1])]
-        end_text.append("\t".join(cols + [place._ratio_text(call["ratio"]), call["verdict"]]) + "\n")
+    link_text, end_text = table_texts(names, sizes, window, lo, hi, counts, calls)
     summary = ["#" + "\t".join(header) + "\n", "#" + "\t".join(PATH_COLUMNS) + "\n"]
     for k, path in enumerate(paths, 1):
         summary.append("%d\t%d\t%d\t%d\n" % (k, len(path), sum(int(sizes[t]) for t, _o in path), fewest_pairs(path, joins)))
@@ -311,6 +455,11 @@ def runPipeline(configFile, window=DEFAULT_WINDOW, minPairs=DEFAULT_MIN_PAIRS, m
     with contextlib.redirect_stdout(io.StringIO()):               # the writer reports what it wrote; this tool prints one line
         writeScaffoldOrderingsToFile([[[names[t], o] for t, o in path] for path in paths], os.path.join(outDir, "paths.order"))
     print("LINKS: scaffolds %d, pairs kept %d, rows %d, joins %d, paths %d" % (n_scaf, n_kept, len(lo), len(all_joins), len(paths)))
+    if made["later"]:
+        first = {"round": 1, "window": window, "sequences": [[(s, "+")] for s in range(n_scaf)], "lo": lo,
+                 "counters": [int(counters[0]), int(counters[1]), 0, 0], "all_joins": all_joins, "cut": cut,
+                 "after": expand_paths([[(s, "+")] for s in range(n_scaf)], paths)}
+        write_rounds(outDir, names, sizes, first, *made["later"])
     return (stats, [(_end_text(names, a), _end_text(names, b), x) for a, b, x in all_joins],
             [[(names[t], o) for t, o in path] for path in paths])
 
@@ -329,12 +478,19 @@ def main(argv=None, context=None):
                         type=int, default=DEFAULT_MIN_SIZE)
     parser.add_argument("-order", help="Audit the junctions of this order file against the links (junctions.tsv); it is never changed",
                         type=str, default=None)
+    parser.add_argument("-rounds", help="Rounds at the most: from round 2 on the paths of the round before are the units, their links "
+                                        "counted between lifted ends (default %d: a single round)" % DEFAULT_ROUNDS, type=int,
+                        default=DEFAULT_ROUNDS)
+    parser.add_argument("-growth", help="Factor of at least 1 by which -window grows from a round to the next (default %g)" % DEFAULT_GROWTH,
+                        type=float, default=DEFAULT_GROWTH)
+    parser.add_argument("-gap", help="Bases between neighbouring scaffolds of a sequence of a later round (default %d, as assembledMap)"
+                                     % DEFAULT_GAP, type=int, default=DEFAULT_GAP)
     parser.add_argument("-out", help="Directory of the results (default: saveFilesDirectory/links)", type=str, default=None)
     parser.add_argument("-threads", help="Host threads of the parser (default 0: all)", type=int, default=0)
     parser.add_argument("-device", help="GPU index (default 0)", type=int, default=0)
     args = parser.parse_args(argv)
     return runPipeline(args.config, args.window, args.minPairs, args.minRatio, args.minSize, args.order, args.out, threads=args.threads,
-                       device=args.device, context=context)
+                       device=args.device, context=context, rounds=args.rounds, growth=args.growth, gap=args.gap)
 
 
 if __name__ == "__main__":

@@ -768,6 +768,29 @@ int hicmi_links_resident(hicmi_ctx *ctx, const int64_t *scaf_size, int64_t n_sca
 int hicmi_links_fetch(hicmi_ctx *ctx, int32_t *lo, int32_t *hi, uint64_t *counts5);
 int hicmi_links_info(hicmi_ctx *ctx, int64_t *n_records_out, int64_t *n_slots_out, double *sort_ms_out);
 
+/* ---- the end-link graph on lifted ends: links between the ends of sequences of several scaffolds ---------
+ * What a scaffolder's second and later rounds count: the paths of one round are the units of the next.  The tables are
+ * those of hicmi_map_begin_lifted: scaffold s lies in sequence lift_seq[s] (-1: dropped) at the offset lift_off[s],
+ * reversed when lift_rev[s] is not 0; seq_size[n_seq] are the sizes of the sequences, gaps included.  Both ends of a kept
+ * pair are lifted.  An end on a dropped scaffold makes the pair `unlifted`, two ends in one sequence make it `inside`.
+ * Otherwise the zone of an end is that of 9t on its lifted position in its sequence read left to right (the bases of a
+ * gap belong to a zone and hold no read), the pair lies on the sequences lo < hi, and its combination and key are those
+ * of 9t with sequence indices in place of scaffold indices: `linked` for LL, LR, RL and RR, `middle` for OTHER.
+ * hicmi_links_lifted counts the store in one pass into a table of the capacity of 9t for n_seq sequences, compacts, sorts
+ * and merges as hicmi_links_resident does; the rows replace those of an earlier hicmi_links_resident or
+ * hicmi_links_lifted call on the context (and the other way round) and are read with hicmi_links_fetch, lo and hi being
+ * sequence indices; hicmi_links_info reports on the call.  n_rows_out: their number.  counters4_out: linked, middle,
+ * inside, unlifted; their sum is the pairs kept (the intra pairs of the store are not added).  With every scaffold its
+ * own + sequence in index order the rows and the first two counters are those of hicmi_links_resident.
+ * HICMI_LINKS_PLAIN is read at every call as in 9t; both forms give the same rows.  HICMI_EINVAL: no store, scaf_size or
+ * n_scaf other than the store's, window < 1, a null pointer, tables that hicmi_map_begin_lifted refuses (n_seq < 1
+ * among them).  HICMI_EUNSUPPORTED: n_seq above 2^30, a table of more than 2^31 slots.  n_seq = 1 and every scaffold
+ * dropped are valid calls with zero rows.  A refusal leaves every output and the rows of an earlier call as they were.
+ * The store is only read; the context's matrix state and open builds are never touched. */
+int hicmi_links_lifted(hicmi_ctx *ctx, const int64_t *scaf_size, int64_t n_scaf, const int32_t *lift_seq,
+                       const int64_t *lift_off, const uint8_t *lift_rev, const int64_t *seq_size, int64_t n_seq,
+                       int64_t window, int64_t *n_rows_out, uint64_t *counters4_out);
+
 /* ---- scaffolds cut into pieces: every read end moved from its scaffold to its piece -------------------
  * Scaffold s of the n_scaf scaffolds has the pieces piece_first[s] .. piece_first[s + 1] - 1 (int32, n_scaf + 1 entries,
  * ascending from 0 to n_piece), left to right; piece k starts after piece_start[k] bases of its parent (int64, 0 for a
