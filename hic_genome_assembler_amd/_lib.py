@@ -320,6 +320,7 @@ def build_maps(path, names, sizes, resolutions, ctxs, threads: int = 0):
     for c in ctxs:
         c.n = c.contacts_device()[1]
         c._keepalive = None
+        c._matrix_replaced()
     return tuple(int(v) for v in stats)
 
 
@@ -369,6 +370,7 @@ def lift_maps(path, names, sizes, lift_seq, lift_off, lift_rev, seq_sizes, resol
     for c in ctxs:
         c.n = c.contacts_device()[1]
         c._keepalive = None
+        c._matrix_replaced()
     return tuple(int(v) for v in stats), out
 
 
@@ -586,6 +588,7 @@ def split_maps(path, names, sizes, piece_first, piece_start, resolutions, ctxs, 
         for c in ctxs:
             c.n = c.contacts_device()[1]
             c._keepalive = None
+            c._matrix_replaced()
     return tuple(int(v) for v in stats), out
 
 
@@ -665,6 +668,12 @@ class Context:
     def __exit__(self, *exc):
         self.close()
 
+    def _matrix_replaced(self):
+        """The context is about to hold another matrix: the library forgets everything derived from the old one
+        (include/hicmi.h, "What a new matrix invalidates"), and so does this binding - its note of the arrangement on the
+        device, by which p2_set_arrangement skips an upload, goes with it."""
+        self._arr_sig = None
+
     # ---- contacts
     def set_contacts(self, mat: np.ndarray):
         """Upload a square contact matrix: fp64, or fp32 (widened on the device, half the transfer)."""
@@ -672,16 +681,19 @@ class Context:
             mat = np.ascontiguousarray(mat)
             if mat.ndim != 2 or mat.shape[0] != mat.shape[1]:
                 raise ValueError("contact matrix must be square")
+            self._matrix_replaced()
             _check(self._lib.hicmi_set_contacts_host_f32(self._h, _ptr(mat), mat.shape[0]))
             self.n = mat.shape[0]
             return
         mat = np.ascontiguousarray(mat, dtype=np.float64)
         if mat.ndim != 2 or mat.shape[0] != mat.shape[1]:
             raise ValueError("contact matrix must be square")
+        self._matrix_replaced()
         _check(self._lib.hicmi_set_contacts_host(self._h, _ptr(mat), mat.shape[0]))
         self.n = mat.shape[0]
 
     def set_contacts_device(self, data_ptr: int, n: int, ld: int | None = None, keepalive=None):
+        self._matrix_replaced()
         _check(self._lib.hicmi_set_contacts_device(self._h, _vp(data_ptr), n, n if ld is None else ld))
         self.n = n
         self._keepalive = keepalive
@@ -714,6 +726,7 @@ class Context:
 
     def compact(self, keep):
         keep = np.ascontiguousarray(keep, dtype=np.int32)
+        self._matrix_replaced()
         _check(self._lib.hicmi_compact(self._h, _ptr(keep), len(keep)))
         self.n = len(keep)
 
@@ -723,6 +736,7 @@ class Context:
         g = np.ascontiguousarray(group_start, dtype=np.int32)
         if g.ndim != 1 or len(g) < 2:
             raise ValueError("group_start must have m + 1 >= 2 entries")
+        self._matrix_replaced()
         _check(self._lib.hicmi_rebin(self._h, _ptr(g), len(g) - 1))
         self.n = len(g) - 1
 
@@ -761,6 +775,7 @@ class Context:
     def map_finish(self) -> int:
         """Close the count (hicmi_map_finish): the symmetric map replaces the context's matrix; returns the pairs added."""
         pairs = c_i64()
+        self._matrix_replaced()
         _check(self._lib.hicmi_map_finish(self._h, ctypes.byref(pairs)))
         self.n = self.contacts_device()[1]
         self._keepalive = None
@@ -1007,6 +1022,7 @@ class Context:
         m = np.ascontiguousarray(mask, dtype=np.uint8)
         if m.shape != (self.n,):
             raise ValueError("mask must have n entries")
+        self._matrix_replaced()
         _check(self._lib.hicmi_ice_mask_rows(self._h, _ptr(m), self.n))
 
     def ice_balance(self, mask=None, max_iter=100, eps=0.1):
@@ -1017,6 +1033,7 @@ class Context:
             raise ValueError("mask must have n entries")
         bias = np.empty(self.n, np.float64)
         iters, delta = c_i64(0), c_dbl(0.0)
+        self._matrix_replaced()
         _check(self._lib.hicmi_ice_balance(self._h, _ptr(m), int(max_iter), float(eps), _ptr(bias), ctypes.byref(iters),
                                            ctypes.byref(delta)))
         return bias, int(iters.value), delta.value

@@ -451,14 +451,30 @@ int check_candidate_bins(int64_t n_bins)
     return HICMI_OK;
 }
 
+// Everything derived from the matrix is gone (include/hicmi.h, "What a new matrix invalidates"): the computed sums, the
+// merges, the rank matrix and its pre-sort, the cut scan's cached row, and all of Part 2 from the selection down (layout,
+// arrangement, its literal score, the exact-score cache).  The snapshots (HMM slots, the Louvain graph, the window
+// tables, the pair store, open builds) are copies and stay.
+int forget_matrix_derived(hicmi_ctx* c)
+{
+    hipError_t e = hipSuccess;
+    if (c->presort_n && c->stream2) e = hipStreamSynchronize(c->stream2);     // the pre-sort reads the matrix being replaced
+    c->presort_n = 0;
+    c->have_sums = false; c->have_rank = false; c->cached_start = -1;
+    c->zraw.clear();
+    c->n2 = 0; c->n_scaf = 0; c->n_arr = 0; c->h_arr_id.clear();
+    c->cur_lit_version = ~0ull;
+    c->cache_valid = false; c->exact_cache.clear();
+    HIPCHK(e);
+    return HICMI_OK;
+}
+
 void drop_matrix_state(hicmi_ctx* c)
 {
+    (void)forget_matrix_derived(c);
     c->c_own.reset();
     c->dC = nullptr; c->own_c = false; c->n = 0; c->ldc = 0;
-    c->d_np.reset(); c->d_seq.reset(); c->have_sums = false;
-    c->have_rank = false; c->cached_start = -1; c->n2 = 0;
-    if (c->presort_n && c->stream2) (void)hipStreamSynchronize(c->stream2);    // the pre-sort reads the matrix being dropped
-    c->presort_n = 0;
+    c->d_np.reset(); c->d_seq.reset();
 }
 
 int alloc_sums(hicmi_ctx* c)
@@ -637,7 +653,9 @@ int hicmi_set_row_sums(hicmi_ctx* c, const double* np_sum, const double* seq_sum
     if (rc) return rc;
     HIPCHK(sync_stream(c));
     if (c->presort_n && c->stream2) HIPCHK(hipStreamSynchronize(c->stream2));
-    c->presort_n = 0;                                      // the similarity keys depend on the sums
+    c->presort_n = 0;                                      // the similarity keys depend on the sums,
+    c->have_rank = false; c->cached_start = -1;            // and so do the rank matrix and the scan row counted from it,
+    c->zraw.clear();                                       // and the merges (the distances divide by np_sum)
     c->have_sums = true;
     return HICMI_OK;
 }
@@ -1900,10 +1918,7 @@ namespace {
 // the matrix has changed under everything derived from it
 int ice_matrix_changed(hicmi_ctx* c)
 {
-    c->have_sums = false; c->have_rank = false; c->cached_start = -1; c->n2 = 0;
-    if (c->presort_n && c->stream2) HIPCHK(hipStreamSynchronize(c->stream2));
-    c->presort_n = 0;
-    return HICMI_OK;
+    return forget_matrix_derived(c);
 }
 
 int ice_check(hicmi_ctx* c, const char* what)
@@ -4108,12 +4123,12 @@ int hicmi_p2_scan_pass(hicmi_ctx* c, int32_t* ids, uint8_t* rev, int64_t S, int6
     // against the new arrangement.
     if (!c || !ids || !rev || !best_io || !cur_fast_io || !improved_out || S < 1 || k < 1 || k > S)
         return fail(HICMI_EINVAL, "bad arguments");
-    *improved_out = 0;
     const int64_t n_ori = c->n_orients, n_cand = c->n_orders * c->n_orients;
     int rc = hicmi_p2_set_arrangement(c, ids, rev, S);
     if (rc) return rc;
     rc = check_window_call(c, 0, k);
     if (rc) return rc;
+    *improved_out = 0;                                      // (a refused call has written nothing)
     use_total(c, total);
     const int64_t last = S - k;
     std::vector<double> delta;
@@ -4177,17 +4192,16 @@ int hicmi_p2_scan_all(hicmi_ctx* c, int32_t* ids, uint8_t* rev, int64_t S, int64
     // scanOrdering's outer loop (OG:509-547) as ONE call: a chromosome's ~20 rounds are ~20 returns to the interpreter
     // otherwise, each of which waits for the interpreter lock behind the other chromosomes' threads
     if (!rounds_out) return fail(HICMI_EINVAL, "bad arguments");
-    *rounds_out = 0;
     c->scan_first_batch = 0;
-    for (;;) {
+    for (int64_t rounds = 0;;) {
         int32_t improved = 0;
         int rc = hicmi_p2_scan_pass(c, ids, rev, S, k, total, best_io, cur_fast_io, &improved);
         c->scan_first_batch = (rc == 0 && c->scan_last_improved <= 1) ? 32 : 0;
         if (rc || !improved) { c->scan_first_batch = 0; }
-        if (rc) return rc;
-        ++*rounds_out;
+        if (rc) return rc;                                  // (refused in its first round, the call has written nothing)
+        *rounds_out = ++rounds;
         if (!improved) return HICMI_OK;
-        if (*rounds_out > 100000) return fail(HICMI_ESTATE, "scanOrdering does not converge");
+        if (rounds > 100000) return fail(HICMI_ESTATE, "scanOrdering does not converge");
     }
 }
 

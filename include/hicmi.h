@@ -53,7 +53,37 @@ int hicmi_synchronize(hicmi_ctx *ctx);
 /* ---- contact matrix -------------------------------------------------------------------------
  * Replaces the dense fp64 matrix built by buildAdjacencyMatrix (S2C:70-98, OG:65-93).
  * _host copies n*n doubles to the GPU; _device adopts a caller-owned device allocation (leading
- * dimension ld >= n, in elements) without copying - the caller keeps it alive and unchanged. */
+ * dimension ld >= n, in elements) without copying - the caller keeps it alive and unchanged.
+ *
+ * What a new matrix invalidates.  A context is kept over many maps, and its state falls into three classes
+ * (tests/test_gpu_stale_state.py holds every call below to this rule):
+ *   REPLACERS put another matrix under the context: hicmi_set_contacts_host, _host_f32, _device, hicmi_compact,
+ *     hicmi_rebin, hicmi_map_finish of a plain and of a lifted build (and the file calls that end in it:
+ *     hicmi_build_maps, hicmi_lift_maps, hicmi_split_maps), hicmi_ice_mask_rows, hicmi_ice_balance.
+ *     hicmi_set_row_sums keeps the matrix and replaces the sums.
+ *   INVALIDATED by every replacer of the matrix - the call that rebuilds it in brackets; until then every call that
+ *     answers from it returns HICMI_EINVAL "<that call> has not run" and writes nothing:
+ *       the computed row sums (recomputed on demand; hicmi_compact, hicmi_rebin and hicmi_map_finish recompute them);
+ *       the merges of hicmi_get_raw_merges [hicmi_upgma];
+ *       the rank matrix, its pre-sort and the cached row of hicmi_cut_scan: hicmi_get_rank_rows, hicmi_cut_scan,
+ *         hicmi_filter_scan, hicmi_first_pass_cuts, hicmi_filter_cuts and their _multi forms, and
+ *         hicmi_get_similarity_row, which reads the leaf order that call uploads [hicmi_rank_matrix];
+ *       the Part 2 selection: hicmi_p2_total, _score, _score_exact, _layout [hicmi_p2_select];
+ *       the layout: hicmi_p2_set_arrangement, _decide_insertion, _insert_all, _support, _breaks, _inversions, _scan_pass,
+ *         _scan_all, _scan_arranged and their _multi forms [hicmi_p2_layout];
+ *       the arrangement, its literal score and the cache of exact scores: hicmi_p2_arrangement_total,
+ *         _arrangement_score, _score_insertions, _score_window, _decide_window, _window_shortlist
+ *         [hicmi_p2_set_arrangement].
+ *     hicmi_set_row_sums invalidates what depends on the sums: the merges (the distances divide by np_sum) and the rank
+ *     matrix with its pre-sort and cached scan row (the similarity keys multiply by seq_sum).  Part 2 reads the matrix
+ *     alone and stands.
+ *   SNAPSHOTS are copies and survive every replacer bit for bit: the HMM observation slots, the Louvain graph, the
+ *     window order and orientation tables of hicmi_p2_window_tables, the resident pair store with the rows of the last
+ *     links call, and every build that is open between its _begin and its _finish (map, span, ends, anchor) - it
+ *     finishes to the result it gives undisturbed.
+ *   STATELESS calls read the matrix (and the sums) as they stand at the call and keep nothing: hicmi_row_sums,
+ *     hicmi_get_contact_rows, hicmi_group_sums, hicmi_junction_sums, hicmi_plot_*,
+ *     hicmi_pair_stats, hicmi_split_pairs and the *_resident calls. */
 int hicmi_set_contacts_host(hicmi_ctx *ctx, const double *contacts, int64_t n);
 /* The same from an fp32 host matrix (BASELINE.json configs[4]: 64,000 bins stored as fp32): half the host memory and
  * PCIe traffic; the values are widened to fp64 on the device and every stage computes on exactly those values. */

@@ -22,6 +22,7 @@ class OracleContext:
         self.shard = (0, 1)
         self._sums = None
         self.R = None
+        self.sub = self.scaf_start = self.arr_ids = None
 
     # ---- one map over several ranks: like libhicmi, answer only for the owned rows until the sums are installed
     def set_row_shard(self, first, stride):
@@ -33,6 +34,20 @@ class OracleContext:
 
     def set_row_sums(self, np_sum, seq_sum):
         self._sums = (np.array(np_sum), np.array(seq_sum))
+        self.R = None                                                      # the similarity keys depend on the sums
+
+    # ---- like libhicmi, forget with the matrix everything derived from it, and refuse to answer from what is gone
+    def _selected(self):
+        if self.sub is None:
+            raise _einval("hicmi_p2_select has not run")
+
+    def _laid_out(self):
+        if self.scaf_start is None:
+            raise _einval("hicmi_p2_layout has not run")
+
+    def _arranged(self):
+        if self.arr_ids is None:
+            raise _einval("hicmi_p2_set_arrangement has not run")
 
     def _ranked(self):
         if self.R is None:
@@ -57,6 +72,7 @@ class OracleContext:
         self.n = len(self.mat)
         self._sums = None
         self.R = None
+        self.sub = self.scaf_start = self.arr_ids = None
 
     def row_sums(self):
         if self._sums is not None and self._sums[0] is not None:
@@ -143,13 +159,16 @@ class OracleContext:
     def p2_select(self, sel):
         sel = np.asarray(sel, dtype=np.int64)
         self.sub = np.ascontiguousarray(self.mat[np.ix_(sel, sel)])
+        self.scaf_start = self.arr_ids = None
 
     def p2_total(self):
+        self._selected()
         n = len(self.sub)
         ident = np.arange(n, dtype=np.int32)
         return orc.lib().hio_total_upper(orc._dp(self.sub), n, orc._ip(ident), n)
 
     def p2_score(self, perms, total):
+        self._selected()
         perms = np.ascontiguousarray(perms, dtype=np.int32)
         out = np.zeros(len(perms))
         orc.lib().hio_cost_literal_batch(orc._dp(self.sub), self.sub.shape[1], orc._ip(perms), perms.shape[0],
@@ -160,6 +179,8 @@ class OracleContext:
 
     # ---- device-side enumeration API, answered by expanding every candidate on the host
     def p2_layout(self, scaf_start, scaf_len):
+        self._selected()
+        self.arr_ids = None
         self.scaf_start = [int(v) for v in scaf_start]
         self.scaf_len = [int(v) for v in scaf_len]
 
@@ -168,6 +189,7 @@ class OracleContext:
         return a[::-1] if rev else a
 
     def p2_set_arrangement(self, ids, rev):
+        self._laid_out()
         self.arr_ids = [int(v) for v in ids]
         self.arr_rev = [int(v) for v in rev]
         self._arr_len = len(self.arr_ids)
@@ -180,13 +202,16 @@ class OracleContext:
         return self.p2_score(rows, total)
 
     def p2_arrangement_total(self):
+        self._arranged()
         row = self._row(self.arr_ids, self.arr_rev)
         return orc.lib().hio_total_upper(orc._dp(self.sub), self.sub.shape[1], orc._ip(row), len(row))
 
     def p2_arrangement_score(self, total):
+        self._arranged()
         return float(self._literal(self._row(self.arr_ids, self.arr_rev)[None, :], total)[0])
 
     def p2_score_insertions(self, new_id, total):
+        self._arranged()
         pieces = [self._positions(i, r) for i, r in zip(self.arr_ids, self.arr_rev)]
         rows = []
         for g in range(len(pieces) + 1):
@@ -200,6 +225,7 @@ class OracleContext:
         self._n_window_cand = len(self.orders) * len(self.orients)
 
     def p2_score_window(self, first, k):
+        self._arranged()
         head = self._row(self.arr_ids[:first], self.arr_rev[:first])
         tail = self._row(self.arr_ids[first + k:], self.arr_rev[first + k:])
         win = self.arr_ids[first:first + k]

@@ -2,10 +2,15 @@
 (192 -> 320 bins) and then meets "the capacity suffices but the leading dimension differs" (320 -> 192: ldr and ldw 320
 against 192).  Every array the reused context returns must equal, bit for bit, what a fresh context returns for the same
 map.  Then the context is closed and another is opened and run: tear-down left the device usable.  (Nothing is said about
-free memory: on a shared card that figure moves with other people's work.)"""
+free memory: on a shared card that figure moves with other people's work.)
+
+The same is asked of every stage family of tests/reuse_cases.py: its three cases on one context give the bytes of three
+fresh contexts, family by family and with the families interleaved, so that no family reads what it or another one left in
+a buffer.  Fresh contexts are run twice and compared first: bit equality needs run-to-run reproducibility."""
 import numpy as np
 import pytest
 
+import reuse_cases as rc
 from hic_genome_assembler_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -86,3 +91,91 @@ def test_one_context_over_maps_of_changing_size(maps, monkeypatch):
     # the reused context is closed: a second one opens and runs on the same device
     with _lib.Context(0) as ctx:
         _same(_run(ctx, *maps[1]), fresh[1], "a context opened after the tear-down")
+
+
+# ---- every stage family -------------------------------------------------------------------------------------------------------
+FORMS = [(family, "default") for family in rc.FAMILIES] + [(family, "plain") for family in rc.PLAIN_FORMS]
+_fresh_cache = {}
+
+
+def _set_form(monkeypatch, family, form):
+    rc.default_forms(monkeypatch)
+    if form != "default":
+        for key, value in rc.PLAIN_FORMS[family].items():
+            monkeypatch.setenv(key, value)
+
+
+def _fresh(family, form):
+    """The three cases of a family, each on a context of its own, run twice: the second run must repeat the first.  (The
+    one output that is the race's by design, the order of a plain pair store, is compared in rc.canonical's form.)"""
+    from hic_genome_assembler_amd import _lib
+    if (family, form) not in _fresh_cache:
+        runs = []
+        for _repeat in range(2):
+            runs.append([])
+            for case in rc.cases_of(family):
+                with _lib.Context(0) as ctx:
+                    runs[-1].append(rc.canonical(family, form, rc.FAMILIES[family](ctx, case)))
+        for k, (first, second) in enumerate(zip(*runs)):
+            _same(second, first, "%s, case %d, a second fresh context" % (family, k))
+        _fresh_cache[family, form] = runs[0]
+    return _fresh_cache[family, form]
+
+
+def _differ(a, b):
+    return any(np.asarray(a[key]).shape != np.asarray(b[key]).shape or np.asarray(a[key]).tobytes() != np.asarray(b[key]).tobytes()
+               for key in a if key != "sizes")
+
+
+def _exercises_what_it_says(family, fresh):
+    small, large = (0, 1) if family in rc.MATRIX_FAMILIES else (1, 2)
+    # a later case needs more of every size the family allocates by ...
+    assert (fresh[large]["sizes"] > fresh[small]["sizes"]).all(), (family, fresh[small]["sizes"], fresh[large]["sizes"])
+    if family in rc.PAIR_FAMILIES:                           # ... and the pair families shrink first: case 1 needs less than case 0
+        assert (fresh[1]["sizes"] < fresh[0]["sizes"]).all() and (fresh[2]["sizes"] > fresh[0]["sizes"]).all(), family
+    # ... and the third case is not the first again: something stale would be noticed
+    assert _differ(fresh[0], fresh[2]), family
+    if family == "part1":
+        # the pre-sort ran and was used (dRankS, d_ident, d_ties, d_tie_bits), on the map in whole counts with rows of equal
+        # similarities to sort again (d_row_list); cuts were found
+        for got in fresh:
+            assert got["presort"][0] == 1 and got["tied_presort"][0] == 1 and got["tied_presort"][1] > 0 and len(got["cuts"]) >= 3
+    if family in ("p2_tables", "p2_search"):
+        assert all(got["sizes"][2] >= 10 for got in fresh)           # scaffolds to place, windows of 7 among them
+
+
+@pytest.mark.parametrize("family,form", FORMS, ids=["%s-%s" % f for f in FORMS])
+def test_family_on_a_reused_context(family, form, monkeypatch):
+    from hic_genome_assembler_amd import _lib
+    _set_form(monkeypatch, family, form)
+    fresh = _fresh(family, form)
+    _exercises_what_it_says(family, fresh)
+    with _lib.Context(0) as ctx:
+        for k, case in enumerate(rc.cases_of(family)):
+            got = rc.canonical(family, form, rc.FAMILIES[family](ctx, case))
+            _same(got, fresh[k], "%s, case %d on the reused context" % (family, k))
+
+
+def test_families_interleaved_on_one_context(monkeypatch):
+    """Case 0 of every family, case 1 of every family in reverse order, case 2 in the first order, on one context: the
+    Part 2 families, the plots and the scans share scratch (d_scores, d_T, d_partial, d_tmp, d_ins_partial and the pinned
+    staging), and only interleaving shows a family that reads what another one left there.  The pair families do the same
+    on a second context that holds a pair store all the while: the store is loaded before the round's other families run
+    and read, by pairs_fetch and by every resident stage, after them."""
+    from hic_genome_assembler_amd import _lib
+    rc.default_forms(monkeypatch)
+    fresh = {family: _fresh(family, "default") for family in rc.FAMILIES}
+    matrix, pair = list(rc.MATRIX_FAMILIES), [f for f in rc.PAIR_FAMILIES if f not in ("pairs_store", "resident")]
+    with _lib.Context(0) as ctx:
+        for k, order in enumerate((matrix, matrix[::-1], matrix)):
+            for family in order:
+                _same(rc.FAMILIES[family](ctx, rc.matrix_cases()[k]), fresh[family][k], "%s, case %d, interleaved" % (family, k))
+    with _lib.Context(0) as ctx:
+        for k, order in enumerate((pair, pair[::-1], pair)):
+            case = rc.pair_cases()[k]
+            rc.load_store(ctx, case)
+            for family in order:
+                _same(rc.FAMILIES[family](ctx, case), fresh[family][k], "%s, case %d, interleaved beside a pair store" % (family, k))
+            _same(rc.read_store(ctx, case), fresh["pairs_store"][k], "the pair store of case %d after the other families" % k)
+            _same(rc.read_resident(ctx, case), fresh["resident"][k], "the resident stages of case %d after the other families" % k)
+            ctx.pairs_drop()
