@@ -24,24 +24,18 @@ from __future__ import annotations
 
 import argparse
 import os
-import sys
 
 import numpy as np
 
-from . import _lib
-from .assembledMap import DEFAULT_GAP, build_assembly, read_order_file
-from .buildMap import STATS_COLUMNS, check_valid_pair_file
-from .hostio import paused_gc, read_scaffold_sizes
+from . import _lib, pairtool
+from .pairtool import (DEFAULT_MIN_PAIRS, DEFAULT_MIN_RATIO, DEFAULT_MIN_SIZE, DEFAULT_REACH, DEFAULT_WINDOW, MAX_REACH,  # noqa: F401
+                       MAX_TABLE, placed_order_text)
 
-DEFAULT_WINDOW, DEFAULT_REACH, DEFAULT_MIN_PAIRS, DEFAULT_MIN_RATIO, DEFAULT_MIN_SIZE = 50000, 2, 4, 2.0, 0
-MAX_REACH = 64
-MAX_TABLE = 1 << 27
 COUNTER_COLUMNS = ("anchored", "middle", "elsewhere", "skipped", "unplaced", "placed")
 UNPLACED_COLUMNS = ("scaffold", "size", "links", "chromosome", "chrom_links", "second", "second_links", "ratio", "left", "right",
                     "orientation", "score", "runner_up", "verdict")
 CHROMOSOME_COLUMNS = ("chromosome", "scaffolds", "bases", "assigned", "inserted")
 LEFT, RIGHT = 0, 1                               # end zones of a placed scaffold as it lies
-CHUNK_PAIRS = 1 << 22
 
 
 def number_blocks(asm, sizes, target=None):
@@ -141,11 +135,11 @@ def both_passes(count, asm, sizes, first1, n1, minPairs, minRatio, minSize):
         return stats, counters1, np.zeros(6, np.uint64), links, chosen, {}
     first2, n2 = number_blocks(asm, sizes, target)
     if n2 > MAX_TABLE:
-        sys.exit("ERROR... the %d scaffolds that got a chromosome need a table of %d counters, more than the %d a build can have: "
-                 "raise -minSize. Exiting..." % (int((target >= 0).sum()), n2, MAX_TABLE))
+        pairtool.refuse("the %d scaffolds that got a chromosome need a table of %d counters, more than the %d a build can have: "
+                        "raise -minSize" % (int((target >= 0).sum()), n2, MAX_TABLE))
     stats2, table, counters2 = count(target, first2, n2)
     if stats2 != stats:
-        sys.exit("ERROR... validPairFile changed between the two passes. Exiting...")
+        pairtool.refuse("validPairFile changed between the two passes")
     T = {s: table[first2[s]:first2[s] + 4 * len(filled[target[s]])].reshape(-1, 2, 2) for s in np.flatnonzero(target >= 0).tolist()}
     return stats, counters1, counters2, links, chosen, T
 
@@ -182,37 +176,9 @@ def measure(ctx, pairFile, names, sizes, asm, target, window, threads):
     """(stats4, first, table, counters) through the array calls of a context the caller owns: the file is parsed on the host
     in chunks (hicmi_parse_valid_pairs) and counted chunk by chunk."""
     first = ctx.anchor_begin(sizes, asm.lift_seq, asm.lift_off, asm.lift_rev, asm.seq_sizes, target, window)
-    stats, at, size = [0, 0, 0, 0], 0, os.path.getsize(pairFile)
-    while True:
-        room = max(1, (size - at) // 12 + 1)                                   # a six-column line has 12 bytes or more
-        sa, pa, sb, pb, at, st = _lib.parse_valid_pairs(pairFile, names, sizes, first_byte=at, max_pairs=min(CHUNK_PAIRS, room),
-                                                        threads=threads)
-        stats = [a + b for a, b in zip(stats, st)]
-        ctx.anchor_add_pairs(sa, pa, sb, pb)
-        if at >= size:
-            break
+    stats = pairtool.parse_in_chunks(pairFile, names, sizes, threads, ctx.anchor_add_pairs)
     table, counters = ctx.anchor_finish()
-    return tuple(stats), first, table, counters
-
-
-def placed_order_text(orderFile, insertions):
-    """The order file again, every line verbatim, with a line ``name<TAB>orientation`` per entry of ``insertions``:
-    {scaffold the line goes before: (name, orientation)} and {(scaffold the line goes after, None): (name, orientation)}.
-    The new line takes the line ending of the line it is placed next to."""
-    out = []
-    with open(orderFile, newline="") as fh:
-        for k, line in enumerate(fh):
-            body = line.rstrip("\r\n")
-            ending = line[len(body):]
-            name = body.split("\t")[0] if k and body and body[0] != "#" else None
-            if name is not None and name in insertions:
-                out.append("%s\t%s" % insertions[name] + (ending or "\n"))
-            out.append(line)
-            if name is not None and (name, None) in insertions:
-                if not ending:
-                    out[-1] = body + "\n"
-                out.append("%s\t%s" % insertions[(name, None)] + ending)
-    return "".join(out)
+    return stats, first, table, counters
 
 
 def _ratio_text(ratio):
@@ -229,33 +195,14 @@ def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT
     v = driver.readConfigFileToVariables(configFile)
     if outFile is None:
         outFile = os.path.join(v["saveFilesDirectory"], "unplacedSupport.txt")
-    try:
-        if window < 1:
-            raise ValueError("the window %d is below 1" % window)
-        if not 1 <= reach <= MAX_REACH:
-            raise ValueError("the reach %d is outside 1 .. %d" % (reach, MAX_REACH))
-        if minPairs < 0:
-            raise ValueError("minPairs %d is negative" % minPairs)
-        if minSize < 0:
-            raise ValueError("minSize %d is negative" % minSize)
-        if not minRatio >= 1:
-            raise ValueError("minRatio %g is below 1" % minRatio)
-        check_valid_pair_file(v["validPairFile"])
-        names, sizes = read_scaffold_sizes(v["hicProScaffSizeFile"])
-        if not names:
-            raise ValueError("hicProScaffSizeFile %s lists no scaffold" % v["hicProScaffSizeFile"])
-        if orderFile is None:
-            orderFile = v["finalOrderingsFile"] if os.path.isfile(v["finalOrderingsFile"]) else v["chromosomeOrderFile"]
-        if not os.path.isfile(orderFile):
-            raise ValueError("order file %r does not exist" % orderFile)
-        asm = build_assembly(read_order_file(orderFile), names, sizes, DEFAULT_GAP, chromosomes_only=True)
+    with pairtool.refusing(OSError, ValueError):
+        pairtool.check_thresholds(window, reach, minPairs, minSize, minRatio)
+        names, sizes, orderFile, asm = pairtool.load(v, orderFile)
         first1, n1 = number_blocks(asm, sizes)
         if n1 > MAX_TABLE:
             raise ValueError("%d unplaced scaffolds against %d chromosomes need a table of %d counters, more than the %d a build can "
                              "have; -minSize applies after this pass and cannot make it smaller: take the smallest scaffolds out of "
                              "hicProScaffSizeFile" % (int((first1 >= 0).sum()), len(asm.components), n1, MAX_TABLE))
-    except (OSError, ValueError) as exc:
-        sys.exit("ERROR... %s. Exiting..." % exc)
     n_seq = len(asm.components)
     candidates = np.flatnonzero(first1 >= 0).tolist()
     tables = (asm.lift_seq, asm.lift_off, asm.lift_rev, asm.seq_sizes)
@@ -273,7 +220,7 @@ def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT
             got = measure(ctx, v["validPairFile"], names, sizes, asm, target, window, threads)
         stats, got_first, table, counters = got
         if not np.array_equal(got_first, first) or table.shape != (n_table,):
-            sys.exit("ERROR... the library numbers the unplaced scaffolds differently from this report. Exiting...")
+            pairtool.refuse("the library numbers the unplaced scaffolds differently from this report")
         return tuple(stats[:4]), table, counters
 
     def passes(ctx):
@@ -282,27 +229,17 @@ def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT
 
     stats, counters1, counters2, links, chosen, T = (0, 0, 0, 0), zero, zero, {}, {}, {}
     if candidates:
-        with paused_gc():
-            try:
-                if context is None:
-                    with _lib.Context(device) as ctx:
-                        stats, counters1, counters2, links, chosen, T = passes(ctx)
-                else:
-                    stats, counters1, counters2, links, chosen, T = passes(context)
-            except _lib.HicmiError as exc:
-                sys.exit("ERROR... %s. Exiting..." % exc)
+        stats, counters1, counters2, links, chosen, T = pairtool.on_context(context, device, passes)
     else:
         print("UNPLACED: nothing is unplaced: %s names every scaffold that has a base" % orderFile)
-    print("UNPLACED: lines %d, pairs used %d, unknown scaffold %d, out of range %d" % stats
-          + "; chromosomes: " + ", ".join("%s %d" % kv for kv in zip(COUNTER_COLUMNS, counters1.tolist()))
-          + "; gaps: " + ", ".join("%s %d" % kv for kv in zip(COUNTER_COLUMNS, counters2.tolist())))
+    print(pairtool.lines_line("UNPLACED", stats) + "; chromosomes: " + pairtool.counted(COUNTER_COLUMNS, counters1)
+          + "; gaps: " + pairtool.counted(COUNTER_COLUMNS, counters2))
 
     scores, gaps, verdicts, winners = settle_gaps(T, chosen, candidates, reach, minPairs)
 
     header = ["window=%d" % window, "reach=%d" % reach, "minPairs=%d" % minPairs, "minRatio=%g" % minRatio, "minSize=%d" % minSize]
-    header += ["%s=%d" % kv for kv in zip(STATS_COLUMNS, stats)]
-    header += ["chromosomes_%s=%d" % kv for kv in zip(COUNTER_COLUMNS, counters1.tolist())]
-    header += ["gaps_%s=%d" % kv for kv in zip(COUNTER_COLUMNS, counters2.tolist())]
+    header += pairtool.fields(pairtool.STATS_COLUMNS, stats) + pairtool.fields(COUNTER_COLUMNS, counters1.tolist(), "chromosomes_")
+    header += pairtool.fields(COUNTER_COLUMNS, counters2.tolist(), "gaps_")
     out = ["#" + "\t".join(header) + "\n", "### Unplaced ###\n", "#" + "\t".join(UNPLACED_COLUMNS) + "\n"]
     for s in candidates:
         best, second, ratio, _verdict = chosen[s]
@@ -313,11 +250,7 @@ def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT
         cols.append(_ratio_text(ratio if sum(a) else None))
         if s in gaps:
             g, o, m, runner_up, verdict = gaps[s]
-            members = filled[best]
-            if verdict == "chromosome_only":
-                cols += ["NA", "NA", "NA"]
-            else:
-                cols += [names[members[g - 1]] if g else "start", names[members[g]] if g < len(members) else "end", "+-"[o]]
+            cols += ["NA", "NA", "NA"] if verdict == "chromosome_only" else list(pairtool.gap_neighbours(names, filled[best], g)) + ["+-"[o]]
             cols += [str(m), str(runner_up)]
         else:
             cols += ["NA"] * 5
@@ -328,26 +261,12 @@ def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT
                                              sum(key[0] == q for key in winners)))
     insertions = winner_insertions(winners, gaps, filled, names)
     placed_text = None if placedFile is None else placed_order_text(orderFile, insertions)
-    os.makedirs(os.path.dirname(os.path.abspath(outFile)), exist_ok=True)
-    with open(outFile, "w") as fh:
-        fh.write("".join(out))
+    pairtool.write_text(outFile, "".join(out), mkdir=True)
     if placedFile is not None:
-        with open(placedFile, "w", newline="") as fh:
-            fh.write(placed_text)
+        pairtool.write_text(placedFile, placed_text, newline="")
     if fullDir is not None:
-        os.makedirs(fullDir, exist_ok=True)
-        with open(os.path.join(fullDir, "unplaced.chromosomes.tsv"), "w") as fh:
-            fh.write("#scaffold\t" + "\t".join("Chr_%d" % (q + 1) for q in range(n_seq)) + "\n")
-            for s in candidates:
-                fh.write(names[s] + "\t" + "\t".join(str(x) for x in links[s]) + "\n")
-        with open(os.path.join(fullDir, "unplaced.gaps.tsv"), "w") as fh:
-            fh.write("#scaffold\tchromosome\tgap\tleft\tright\torientation\tscore\n")
-            for s in sorted(scores):
-                members = filled[chosen[s][0]]
-                for g, both in enumerate(scores[s]):
-                    for o, x in enumerate(both):
-                        fh.write("%s\t%d\t%d\t%s\t%s\t%s\t%d\n" % (names[s], chosen[s][0] + 1, g, names[members[g - 1]] if g else "start",
-                                                                   names[members[g]] if g < len(members) else "end", "+-"[o], x))
+        pairtool.write_gap_tables(fullDir, "unplaced", names, n_seq, [(s, links[s]) for s in candidates],
+                                  [(s, chosen[s][0], filled[chosen[s][0]], scores[s]) for s in sorted(scores)])
     inserted = sorted(winners.values())
     print("UNPLACED: %d unplaced scaffold(s), %d with a chromosome, %d inserted, %d deferred" % (
         len(candidates), len(T), len(inserted), sum(x == "deferred" for x in verdicts.values())))
@@ -358,23 +277,20 @@ def main(argv=None, context=None):
     parser = argparse.ArgumentParser(description="Counts, on the GPU, the read pairs of validPairFile that link the scaffolds an order "
                                                  "file leaves out to its chromosomes and to the ends of their scaffolds, and "
                                                  "reports where each of them belongs.")
-    parser.add_argument("-config", help="Full file path to the config file", required=True, type=str)
-    parser.add_argument("-order", help="Order file (default: finalOrderingsFile when it exists, else chromosomeOrderFile)",
-                        type=str, default=None)
-    parser.add_argument("-window", help="End zone of a placed scaffold in bp (default %d)" % DEFAULT_WINDOW, type=int, default=DEFAULT_WINDOW)
-    parser.add_argument("-reach", help="Scaffolds on either side of a gap that score it, 1 .. %d (default %d)" % (MAX_REACH, DEFAULT_REACH),
-                        type=int, default=DEFAULT_REACH)
-    parser.add_argument("-minPairs", help="Links below which neither a chromosome nor a gap is chosen (default %d)" % DEFAULT_MIN_PAIRS,
-                        type=int, default=DEFAULT_MIN_PAIRS)
-    parser.add_argument("-minRatio", help="Link density of the best chromosome over the second best below which none is chosen "
-                                          "(default %g)" % DEFAULT_MIN_RATIO, type=float, default=DEFAULT_MIN_RATIO)
-    parser.add_argument("-minSize", help="Scaffolds below this size in bp get no chromosome (default %d)" % DEFAULT_MIN_SIZE, type=int,
-                        default=DEFAULT_MIN_SIZE)
-    parser.add_argument("-out", help="Report (default: saveFilesDirectory/unplacedSupport.txt)", type=str, default=None)
-    parser.add_argument("-placed", help="Write the order file again with one placed scaffold inserted per gap", type=str, default=None)
-    parser.add_argument("-full", help="Write unplaced.chromosomes.tsv and unplaced.gaps.tsv into this directory", type=str, default=None)
-    parser.add_argument("-threads", help="Host threads of the parser (default 0: all)", type=int, default=0)
-    parser.add_argument("-device", help="GPU index (default 0)", type=int, default=0)
+    with pairtool.common_arguments(parser):
+        parser.add_argument("-window", help="End zone of a placed scaffold in bp (default %d)" % DEFAULT_WINDOW, type=int,
+                            default=DEFAULT_WINDOW)
+        parser.add_argument("-reach", help="Scaffolds on either side of a gap that score it, 1 .. %d (default %d)" % (MAX_REACH, DEFAULT_REACH),
+                            type=int, default=DEFAULT_REACH)
+        parser.add_argument("-minPairs", help="Links below which neither a chromosome nor a gap is chosen (default %d)" % DEFAULT_MIN_PAIRS,
+                            type=int, default=DEFAULT_MIN_PAIRS)
+        parser.add_argument("-minRatio", help="Link density of the best chromosome over the second best below which none is chosen "
+                                              "(default %g)" % DEFAULT_MIN_RATIO, type=float, default=DEFAULT_MIN_RATIO)
+        parser.add_argument("-minSize", help="Scaffolds below this size in bp get no chromosome (default %d)" % DEFAULT_MIN_SIZE, type=int,
+                            default=DEFAULT_MIN_SIZE)
+        parser.add_argument("-out", help="Report (default: saveFilesDirectory/unplacedSupport.txt)", type=str, default=None)
+        parser.add_argument("-placed", help="Write the order file again with one placed scaffold inserted per gap", type=str, default=None)
+        parser.add_argument("-full", help="Write unplaced.chromosomes.tsv and unplaced.gaps.tsv into this directory", type=str, default=None)
     args = parser.parse_args(argv)
     return runPipeline(args.config, args.order, args.window, args.reach, args.minPairs, args.minRatio, args.minSize, args.out, args.placed,
                        args.full, threads=args.threads, device=args.device, context=context)

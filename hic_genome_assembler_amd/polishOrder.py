@@ -29,18 +29,14 @@ from __future__ import annotations
 
 import argparse
 import os
-import sys
 import tempfile
 
 import numpy as np
 
-from . import _lib
+from . import _lib, pairtool
 from . import placeUnplaced as place
 from . import supportEnds as ends
 from . import supportSeats as seats
-from .assembledMap import DEFAULT_GAP, build_assembly, read_order_file
-from .buildMap import STATS_COLUMNS, check_valid_pair_file
-from .hostio import paused_gc, read_scaffold_sizes
 
 DEFAULT_MAX_ROUNDS = 1000
 MOVES = ("flip", "place", "relocate")
@@ -71,8 +67,7 @@ def _read(path):
 
 
 def _write(path, text):
-    with open(path, "w", newline="") as fh:
-        fh.write(text)
+    pairtool.write_text(path, text, newline="")
 
 
 def runPipeline(configFile, orderFile=None, moves="flip,place", window=ends.DEFAULT_WINDOW, reach=ends.DEFAULT_REACH,
@@ -85,34 +80,19 @@ def runPipeline(configFile, orderFile=None, moves="flip,place", window=ends.DEFA
     v = driver.readConfigFileToVariables(configFile)
     if outDir is None:
         outDir = os.path.join(v["saveFilesDirectory"], "polished")
-    try:
+    with pairtool.refusing(OSError, ValueError):
         kinds = [m for m in str(moves).split(",")]
         if not kinds or any(m not in MOVES for m in kinds):
             raise ValueError("-moves %r is not a list of %s" % (moves, " and ".join(MOVES)))
         if maxRounds < 1:
             raise ValueError("maxRounds %d is below 1" % maxRounds)
-        if window < 1:
-            raise ValueError("the window %d is below 1" % window)
-        if not 1 <= reach <= ends.MAX_REACH:
-            raise ValueError("the reach %d is outside 1 .. %d" % (reach, ends.MAX_REACH))
-        if minPairs < 0:
-            raise ValueError("minPairs %d is negative" % minPairs)
-        if minSize < 0:
-            raise ValueError("minSize %d is negative" % minSize)
-        if not minRatio >= 1:
-            raise ValueError("minRatio %g is below 1" % minRatio)
-        check_valid_pair_file(v["validPairFile"])
-        names, sizes = read_scaffold_sizes(v["hicProScaffSizeFile"])
-        if not names:
-            raise ValueError("hicProScaffSizeFile %s lists no scaffold" % v["hicProScaffSizeFile"])
-        if orderFile is None:
-            orderFile = v["finalOrderingsFile"] if os.path.isfile(v["finalOrderingsFile"]) else v["chromosomeOrderFile"]
-        if not os.path.isfile(orderFile):
-            raise ValueError("order file %r does not exist" % orderFile)
+        pairtool.check_thresholds(window, reach, minPairs, minSize, minRatio)
+        names, sizes = pairtool.read_scaffolds(v)
+        orderFile = pairtool.resolve_order(v, orderFile)
         outFile = os.path.join(outDir, os.path.basename(orderFile))
         if os.path.abspath(outFile) == os.path.abspath(orderFile):
             raise ValueError("the polished order file %s would replace the order file it is made from" % outFile)
-        asm = build_assembly(read_order_file(orderFile), names, sizes, DEFAULT_GAP, chromosomes_only=True)
+        asm = pairtool.order_assembly(orderFile, names, sizes)
         n_placed = _lib.ends_placed_count(sizes, asm.lift_seq)
         if n_placed < 1:
             raise ValueError("no scaffold of %s has a base" % orderFile)
@@ -134,8 +114,6 @@ def runPipeline(configFile, orderFile=None, moves="flip,place", window=ends.DEFA
             if n_seats > seats.MAX_TABLE:
                 raise ValueError("relocating %d placed scaffolds in %d chromosomes needs a table of %d counters, more than the %d a "
                                  "call can have" % (n_most, len(asm.components), n_seats, seats.MAX_TABLE))
-    except (OSError, ValueError) as exc:
-        sys.exit("ERROR... %s. Exiting..." % exc)
     n_seq = len(asm.components)
 
     def polish(ctx, work):
@@ -147,18 +125,18 @@ def runPipeline(configFile, orderFile=None, moves="flip,place", window=ends.DEFA
 
             def lay():
                 """The working copy as it lies, counted: (assembly, rank, seq_first, table)."""
-                a = build_assembly(read_order_file(work), names, sizes, DEFAULT_GAP, chromosomes_only=True)
+                a = pairtool.order_assembly(work, names, sizes)
                 rank, seq_first = ends.number_ranks(a, sizes)
                 got_rank, T, _counters = ctx.ends_resident(sizes, a.lift_seq, a.lift_off, a.lift_rev, a.seq_sizes, window, reach)
                 if not np.array_equal(got_rank, rank) or T.shape != (int((rank >= 0).sum()), reach, 4):
-                    sys.exit("ERROR... the library ranks the scaffolds differently from this tool. Exiting...")
+                    pairtool.refuse("the library ranks the scaffolds differently from this tool")
                 return a, rank, seq_first, T
 
             def anchor(a):
                 def count(target, first, n_table):
                     got_first, table, counters = ctx.anchor_resident(sizes, a.lift_seq, a.lift_off, a.lift_rev, a.seq_sizes, target, window)
                     if not np.array_equal(got_first, first) or table.shape != (n_table,):
-                        sys.exit("ERROR... the library numbers the unplaced scaffolds differently from this tool. Exiting...")
+                        pairtool.refuse("the library numbers the unplaced scaffolds differently from this tool")
                     return (), table, counters
                 return count
 
@@ -194,7 +172,7 @@ def runPipeline(configFile, orderFile=None, moves="flip,place", window=ends.DEFA
                     first, n_table = seats.number_blocks(a, sizes)
                     got_first, table, _counters = ctx.seats_resident(sizes, a.lift_seq, a.lift_off, a.lift_rev, a.seq_sizes, window)
                     if not np.array_equal(got_first, first) or table.shape != (n_table,):
-                        sys.exit("ERROR... the library numbers the placed scaffolds differently from this tool. Exiting...")
+                        pairtool.refuse("the library numbers the placed scaffolds differently from this tool")
                     calls = seats.seat_calls(a, sizes, first, table, reach, minPairs, minRatio)
                     moves = seats.chosen_moves(a, sizes, calls)
                     if moves:
@@ -214,8 +192,8 @@ def runPipeline(configFile, orderFile=None, moves="flip,place", window=ends.DEFA
                                 g, o, m, runner_up, _verdict = calls[s]["gap"]
                                 others = [t for t in filled[q] if t != s]
                                 relocations[q] += 1
-                                log.append((rounds, "relocate", q + 1, names[s], names[others[g - 1]] if g else "start",
-                                            names[others[g]] if g < len(others) else "end", "+-"[o], m, runner_up))
+                                log.append((rounds, "relocate", q + 1, names[s]) + pairtool.gap_neighbours(names, others, g)
+                                           + ("+-"[o], m, runner_up))
                             a, rank, seq_first, T = moved
                             continue                               # back to the flip rounds
                 if not placing:
@@ -236,10 +214,8 @@ def runPipeline(configFile, orderFile=None, moves="flip,place", window=ends.DEFA
                 rounds += 1
                 for (q, g), s in sorted(winners.items()):
                     _g, o, m, runner_up, _verdict = gaps[s]
-                    members = filled[q]
                     insertions_of[q] += 1
-                    log.append((rounds, "place", q + 1, names[s], names[members[g - 1]] if g else "start",
-                                names[members[g]] if g < len(members) else "end", "+-"[o], m, runner_up))
+                    log.append((rounds, "place", q + 1, names[s]) + pairtool.gap_neighbours(names, filled[q], g) + ("+-"[o], m, runner_up))
                 a, rank, seq_first, T = lay()
             # the loop ran until nothing was left to do unless the limit ended it; a stalled run says which through `ended`
             ended = "round_limit" if status else "nothing_left"
@@ -252,33 +228,24 @@ def runPipeline(configFile, orderFile=None, moves="flip,place", window=ends.DEFA
         finally:
             ctx.pairs_drop()
 
-    with tempfile.TemporaryDirectory() as tmp, paused_gc():
+    with tempfile.TemporaryDirectory() as tmp:
         work = os.path.join(tmp, os.path.basename(orderFile))
         _write(work, _read(orderFile))
-        try:
-            if context is None:
-                with _lib.Context(device) as ctx:
-                    stats, n_kept, n_intra, rounds, status, ended, log, rows = polish(ctx, work)
-            else:
-                stats, n_kept, n_intra, rounds, status, ended, log, rows = polish(context, work)
-        except _lib.HicmiError as exc:
-            sys.exit("ERROR... %s. Exiting..." % exc)
+        stats, n_kept, n_intra, rounds, status, ended, log, rows = pairtool.on_context(context, device, lambda ctx: polish(ctx, work))
         polished = _read(work)
 
     header = ["moves=%s" % ",".join(kinds), "window=%d" % window, "reach=%d" % reach, "minPairs=%d" % minPairs, "minRatio=%g" % minRatio,
               "minSize=%d" % minSize, "maxRounds=%d" % maxRounds]
-    header += ["%s=%d" % kv for kv in zip(STATS_COLUMNS, stats)]
+    header += pairtool.fields(pairtool.STATS_COLUMNS, stats)
     header += ["pairs_kept=%d" % n_kept, "pairs_intra=%d" % n_intra, "rounds=%d" % rounds, "status=%s" % status, "ended=%s" % ended]
     os.makedirs(outDir, exist_ok=True)
     _write(outFile, polished)
-    with open(os.path.join(outDir, "polish.log"), "w") as fh:
-        fh.write("#" + "\t".join(LOG_COLUMNS) + "\n")
-        fh.write("".join("\t".join(str(x) for x in row) + "\n" for row in log))
-    with open(os.path.join(outDir, "polish_summary.tsv"), "w") as fh:
-        fh.write("#" + "\t".join(header) + "\n#" + "\t".join(SUMMARY_COLUMNS + ((RELOCATE_COLUMN,) if "relocate" in kinds else ())) + "\n")
-        fh.write("".join("\t".join(str(x) for x in row) + "\n" for row in rows))
-    print("POLISH: lines %d, pairs used %d, unknown scaffold %d, out of range %d" % stats
-          + "; pairs kept %d, intra %d" % (n_kept, n_intra))
+    pairtool.write_text(os.path.join(outDir, "polish.log"),
+                        "#" + "\t".join(LOG_COLUMNS) + "\n" + "".join("\t".join(str(x) for x in row) + "\n" for row in log))
+    pairtool.write_text(os.path.join(outDir, "polish_summary.tsv"),
+                        "#" + "\t".join(header) + "\n#" + "\t".join(SUMMARY_COLUMNS + ((RELOCATE_COLUMN,) if "relocate" in kinds else ())) + "\n"
+                        + "".join("\t".join(str(x) for x in row) + "\n" for row in rows))
+    print(pairtool.lines_line("POLISH", stats) + "; pairs kept %d, intra %d" % (n_kept, n_intra))
     print("POLISH: %s after %d round(s): %d flip(s), %d insertion(s)%s, facing links %d -> %d" % (
         status, rounds, sum(r[3] for r in rows), sum(r[4] for r in rows),
         ", %d relocation(s)" % sum(r[7] for r in rows) if "relocate" in kinds else "", sum(r[5] for r in rows), sum(r[6] for r in rows)))
@@ -289,25 +256,22 @@ def main(argv=None, context=None):
     parser = argparse.ArgumentParser(description="Reads validPairFile once into a pair store on the GPU and repeats the flips of "
                                                  "supportEnds, the insertions of placeUnplaced and, when asked for, the moves of "
                                                  "supportSeats on an order file until none has anything left to do.")
-    parser.add_argument("-config", help="Full file path to the config file", required=True, type=str)
-    parser.add_argument("-order", help="Order file (default: finalOrderingsFile when it exists, else chromosomeOrderFile)",
-                        type=str, default=None)
-    parser.add_argument("-moves", help="Kinds of move, a list of flip, place and relocate (default flip,place)", type=str, default="flip,place")
-    parser.add_argument("-window", help="End zone in bp (default %d)" % ends.DEFAULT_WINDOW, type=int, default=ends.DEFAULT_WINDOW)
-    parser.add_argument("-reach", help="Places two scaffolds may lie apart, 1 .. %d (default %d)" % (ends.MAX_REACH, ends.DEFAULT_REACH),
-                        type=int, default=ends.DEFAULT_REACH)
-    parser.add_argument("-minPairs", help="Links below which nothing is decided (default %d)" % ends.DEFAULT_MIN_PAIRS, type=int,
-                        default=ends.DEFAULT_MIN_PAIRS)
-    parser.add_argument("-minRatio", help="Link density of the best chromosome over the second best below which none is chosen "
-                                          "(default %g)" % place.DEFAULT_MIN_RATIO, type=float, default=place.DEFAULT_MIN_RATIO)
-    parser.add_argument("-minSize", help="Scaffolds below this size in bp get no chromosome (default %d)" % place.DEFAULT_MIN_SIZE,
-                        type=int, default=place.DEFAULT_MIN_SIZE)
-    parser.add_argument("-maxRounds", help="Rounds after which the loop stops (default %d)" % DEFAULT_MAX_ROUNDS, type=int,
-                        default=DEFAULT_MAX_ROUNDS)
-    parser.add_argument("-out", help="Directory of the polished order file, polish.log and polish_summary.tsv (default: "
-                                     "saveFilesDirectory/polished)", type=str, default=None)
-    parser.add_argument("-threads", help="Host threads of the parser (default 0: all)", type=int, default=0)
-    parser.add_argument("-device", help="GPU index (default 0)", type=int, default=0)
+    with pairtool.common_arguments(parser):
+        parser.add_argument("-moves", help="Kinds of move, a list of flip, place and relocate (default flip,place)", type=str,
+                            default="flip,place")
+        parser.add_argument("-window", help="End zone in bp (default %d)" % ends.DEFAULT_WINDOW, type=int, default=ends.DEFAULT_WINDOW)
+        parser.add_argument("-reach", help="Places two scaffolds may lie apart, 1 .. %d (default %d)" % (ends.MAX_REACH, ends.DEFAULT_REACH),
+                            type=int, default=ends.DEFAULT_REACH)
+        parser.add_argument("-minPairs", help="Links below which nothing is decided (default %d)" % ends.DEFAULT_MIN_PAIRS, type=int,
+                            default=ends.DEFAULT_MIN_PAIRS)
+        parser.add_argument("-minRatio", help="Link density of the best chromosome over the second best below which none is chosen "
+                                              "(default %g)" % place.DEFAULT_MIN_RATIO, type=float, default=place.DEFAULT_MIN_RATIO)
+        parser.add_argument("-minSize", help="Scaffolds below this size in bp get no chromosome (default %d)" % place.DEFAULT_MIN_SIZE,
+                            type=int, default=place.DEFAULT_MIN_SIZE)
+        parser.add_argument("-maxRounds", help="Rounds after which the loop stops (default %d)" % DEFAULT_MAX_ROUNDS, type=int,
+                            default=DEFAULT_MAX_ROUNDS)
+        parser.add_argument("-out", help="Directory of the polished order file, polish.log and polish_summary.tsv (default: "
+                                         "saveFilesDirectory/polished)", type=str, default=None)
     args = parser.parse_args(argv)
     return runPipeline(args.config, args.order, args.moves, args.window, args.reach, args.minPairs, args.minRatio, args.minSize,
                        args.maxRounds, args.out, threads=args.threads, device=args.device, context=context)

@@ -33,18 +33,15 @@ import contextlib
 import io
 import math
 import os
-import sys
 
 import numpy as np
 
-from . import _lib
+from . import _lib, pairtool
 from . import placeUnplaced as place
-from .assembledMap import DEFAULT_GAP, build_assembly, read_order_file
-from .buildMap import STATS_COLUMNS, check_valid_pair_file
-from .hostio import paused_gc, read_scaffold_sizes
+from .assembledMap import DEFAULT_GAP
 from .orientSmallScaffolds import writeScaffoldOrderingsToFile
+from .pairtool import DEFAULT_MIN_PAIRS, DEFAULT_MIN_RATIO, DEFAULT_MIN_SIZE, DEFAULT_WINDOW
 
-DEFAULT_WINDOW, DEFAULT_MIN_PAIRS, DEFAULT_MIN_RATIO, DEFAULT_MIN_SIZE = 50000, 4, 2.0, 0
 MAX_SCAFFOLDS = _lib.LINKS_MAX_SCAF
 END_NAMES = ("left", "right")
 LINK_COLUMNS = ("scaffold_a", "scaffold_b", "pairs", "left_left", "left_right", "right_left", "right_right")
@@ -341,34 +338,15 @@ def write_rounds(outDir, names, sizes, first, done, ended, sequences):
         where = os.path.join(outDir, "round%d" % r)
         os.makedirs(where, exist_ok=True)
         for fn, text in (("sequences.tsv", seq_text), ("links.tsv", link_text), ("ends.tsv", end_text)):
-            with open(os.path.join(where, fn), "w") as fh:
-                fh.write("".join(text))
+            pairtool.write_text(os.path.join(where, fn), "".join(text))
         write_order(os.path.join(where, "paths.order"), names, after, sizes)
         print("LINKS round %d: window %d, sequences %d, rows %d, joins %d, sequences out %d"
               % (r, rnd["window"], len(rnd["sequences"]), len(rnd["lo"]), len(rnd["all_joins"]), len(after)))
     lines.append("#ended=%s\n" % ended)
-    with open(os.path.join(outDir, "rounds.tsv"), "w") as fh:
-        fh.write("".join(lines))
+    pairtool.write_text(os.path.join(outDir, "rounds.tsv"), "".join(lines))
     write_order(os.path.join(outDir, "final.order"), names, sequences, sizes)
     n_paths = sum(len(m) > 1 for m in sequences)
     print("LINKS: %d rounds, ended %s, paths %d, singles %d" % (1 + len(done), ended, n_paths, len(sequences) - n_paths))
-
-
-def check_arguments(window, minPairs, minRatio, minSize, rounds=1, growth=1.0, gap=DEFAULT_GAP):
-    if rounds < 1:
-        raise ValueError("rounds %d is below 1" % rounds)
-    if not growth >= 1:
-        raise ValueError("growth %g is below 1" % growth)
-    if gap < 0:
-        raise ValueError("gap %d is negative" % gap)
-    if window < 1:
-        raise ValueError("the window %d is below 1" % window)
-    if minPairs < 0:
-        raise ValueError("minPairs %d is negative" % minPairs)
-    if minSize < 0:
-        raise ValueError("minSize %d is negative" % minSize)
-    if not minRatio >= 1:
-        raise ValueError("minRatio %g is below 1" % minRatio)
 
 
 def runPipeline(configFile, window=DEFAULT_WINDOW, minPairs=DEFAULT_MIN_PAIRS, minRatio=DEFAULT_MIN_RATIO, minSize=DEFAULT_MIN_SIZE,
@@ -382,21 +360,20 @@ def runPipeline(configFile, window=DEFAULT_WINDOW, minPairs=DEFAULT_MIN_PAIRS, m
     v = driver.readConfigFileToVariables(configFile)
     if outDir is None:
         outDir = os.path.join(v["saveFilesDirectory"], "links")
-    try:
-        check_arguments(window, minPairs, minRatio, minSize, rounds, growth, gap)
-        check_valid_pair_file(v["validPairFile"])
-        names, sizes = read_scaffold_sizes(v["hicProScaffSizeFile"])
-        if not names:
-            raise ValueError("hicProScaffSizeFile %s lists no scaffold" % v["hicProScaffSizeFile"])
+    with pairtool.refusing(OSError, ValueError):
+        if rounds < 1:
+            raise ValueError("rounds %d is below 1" % rounds)
+        if not growth >= 1:
+            raise ValueError("growth %g is below 1" % growth)
+        if gap < 0:
+            raise ValueError("gap %d is negative" % gap)
+        pairtool.check_thresholds(window=window, minPairs=minPairs, minSize=minSize, minRatio=minRatio)
+        names, sizes = pairtool.read_scaffolds(v)
         if len(names) > MAX_SCAFFOLDS:
             raise ValueError("%d scaffolds, more than the %d a link key has room for" % (len(names), MAX_SCAFFOLDS))
         asm = None
-        if orderFile is not None:
-            if not os.path.isfile(orderFile):
-                raise ValueError("order file %r does not exist" % orderFile)
-            asm = build_assembly(read_order_file(orderFile), names, sizes, DEFAULT_GAP, chromosomes_only=True)
-    except (OSError, ValueError) as exc:
-        sys.exit("ERROR... %s. Exiting..." % exc)
+        if pairtool.resolve_order(v, orderFile, default=False) is not None:
+            asm = pairtool.order_assembly(orderFile, names, sizes)
     n_scaf = len(names)
 
     made = {"decided": None, "later": None}
@@ -414,27 +391,18 @@ def runPipeline(configFile, window=DEFAULT_WINDOW, minPairs=DEFAULT_MIN_PAIRS, m
         finally:
             ctx.pairs_drop()
 
-    with paused_gc():
-        try:
-            if context is None:
-                with _lib.Context(device) as ctx:
-                    stats, n_kept, n_intra, lo, hi, counts, counters = count(ctx)
-            else:
-                stats, n_kept, n_intra, lo, hi, counts, counters = count(context)
-        except _lib.HicmiError as exc:
-            sys.exit("ERROR... %s. Exiting..." % exc)
+    stats, n_kept, n_intra, lo, hi, counts, counters = pairtool.on_context(context, device, count)
     if int(counts.sum()) != n_kept or int(counters.sum()) != n_kept:
-        sys.exit("ERROR... the rows hold %d pairs and the counters %d where the store kept %d. Exiting..."
-                 % (int(counts.sum()), int(counters.sum()), n_kept))
+        pairtool.refuse("the rows hold %d pairs and the counters %d where the store kept %d" % (int(counts.sum()), int(counters.sum()), n_kept))
     for rnd in made["later"][0] if made["later"] else ():
         if int(rnd["counters"].sum()) != n_kept or int(rnd["counts"].sum()) != int(rnd["counters"][:2].sum()):
-            sys.exit("ERROR... round %d: the rows hold %d pairs and the counters %d where the store kept %d. Exiting..."
-                     % (rnd["round"], int(rnd["counts"].sum()), int(rnd["counters"].sum()), n_kept))
+            pairtool.refuse("round %d: the rows hold %d pairs and the counters %d where the store kept %d"
+                            % (rnd["round"], int(rnd["counts"].sum()), int(rnd["counters"].sum()), n_kept))
 
     links, calls, all_joins, paths, cut, joins = made["decided"] or decide(lo, hi, counts, sizes, minPairs, minRatio, minSize)
     in_paths = sum(len(p) for p in paths)
     header = ["window=%d" % window, "minPairs=%d" % minPairs, "minRatio=%g" % minRatio, "minSize=%d" % minSize]
-    header += ["%s=%d" % kv for kv in zip(STATS_COLUMNS, stats)]
+    header += pairtool.fields(pairtool.STATS_COLUMNS, stats)
     header += ["pairs_kept=%d" % n_kept, "pairs_intra=%d" % n_intra, "linked=%d" % int(counters[0]), "middle=%d" % int(counters[1]),
                "rows=%d" % len(lo), "joins=%d" % len(all_joins), "cycles_cut=%d" % cut, "paths=%d" % len(paths),
                "singles=%d" % (n_scaf - in_paths)]
@@ -450,8 +418,7 @@ def runPipeline(configFile, window=DEFAULT_WINDOW, minPairs=DEFAULT_MIN_PAIRS, m
     os.makedirs(outDir, exist_ok=True)
     for fn, text in (("links.tsv", link_text), ("ends.tsv", end_text), ("links_summary.tsv", summary), ("junctions.tsv", junction_text)):
         if text is not None:
-            with open(os.path.join(outDir, fn), "w") as fh:
-                fh.write("".join(text))
+            pairtool.write_text(os.path.join(outDir, fn), "".join(text))
     with contextlib.redirect_stdout(io.StringIO()):               # the writer reports what it wrote; this tool prints one line
         writeScaffoldOrderingsToFile([[[names[t], o] for t, o in path] for path in paths], os.path.join(outDir, "paths.order"))
     print("LINKS: scaffolds %d, pairs kept %d, rows %d, joins %d, paths %d" % (n_scaf, n_kept, len(lo), len(all_joins), len(paths)))
@@ -468,26 +435,24 @@ def main(argv=None, context=None):
     parser = argparse.ArgumentParser(description="Counts, on the GPU, the read pairs of validPairFile between the end zones of "
                                                  "every two scaffolds, without an order file, and writes the link table, the best "
                                                  "partner of every scaffold end and the paths the reciprocal best ends form.")
-    parser.add_argument("-config", help="Full file path to the config file", required=True, type=str)
-    parser.add_argument("-window", help="End zone of a scaffold in bp (default %d)" % DEFAULT_WINDOW, type=int, default=DEFAULT_WINDOW)
-    parser.add_argument("-minPairs", help="Pairs below which an end chooses no partner (default %d)" % DEFAULT_MIN_PAIRS, type=int,
-                        default=DEFAULT_MIN_PAIRS)
-    parser.add_argument("-minRatio", help="Pairs of the best partner end over the best end of any other scaffold below which an end "
-                                          "chooses none (default %g)" % DEFAULT_MIN_RATIO, type=float, default=DEFAULT_MIN_RATIO)
-    parser.add_argument("-minSize", help="Scaffolds below this size neither choose nor are chosen (default %d)" % DEFAULT_MIN_SIZE,
-                        type=int, default=DEFAULT_MIN_SIZE)
-    parser.add_argument("-order", help="Audit the junctions of this order file against the links (junctions.tsv); it is never changed",
-                        type=str, default=None)
-    parser.add_argument("-rounds", help="Rounds at the most: from round 2 on the paths of the round before are the units, their links "
-                                        "counted between lifted ends (default %d: a single round)" % DEFAULT_ROUNDS, type=int,
-                        default=DEFAULT_ROUNDS)
-    parser.add_argument("-growth", help="Factor of at least 1 by which -window grows from a round to the next (default %g)" % DEFAULT_GROWTH,
-                        type=float, default=DEFAULT_GROWTH)
-    parser.add_argument("-gap", help="Bases between neighbouring scaffolds of a sequence of a later round (default %d, as assembledMap)"
-                                     % DEFAULT_GAP, type=int, default=DEFAULT_GAP)
-    parser.add_argument("-out", help="Directory of the results (default: saveFilesDirectory/links)", type=str, default=None)
-    parser.add_argument("-threads", help="Host threads of the parser (default 0: all)", type=int, default=0)
-    parser.add_argument("-device", help="GPU index (default 0)", type=int, default=0)
+    with pairtool.common_arguments(parser, order=False):
+        parser.add_argument("-window", help="End zone of a scaffold in bp (default %d)" % DEFAULT_WINDOW, type=int, default=DEFAULT_WINDOW)
+        parser.add_argument("-minPairs", help="Pairs below which an end chooses no partner (default %d)" % DEFAULT_MIN_PAIRS, type=int,
+                            default=DEFAULT_MIN_PAIRS)
+        parser.add_argument("-minRatio", help="Pairs of the best partner end over the best end of any other scaffold below which an end "
+                                              "chooses none (default %g)" % DEFAULT_MIN_RATIO, type=float, default=DEFAULT_MIN_RATIO)
+        parser.add_argument("-minSize", help="Scaffolds below this size neither choose nor are chosen (default %d)" % DEFAULT_MIN_SIZE,
+                            type=int, default=DEFAULT_MIN_SIZE)
+        parser.add_argument("-order", help="Audit the junctions of this order file against the links (junctions.tsv); it is never changed",
+                            type=str, default=None)
+        parser.add_argument("-rounds", help="Rounds at the most: from round 2 on the paths of the round before are the units, their links "
+                                            "counted between lifted ends (default %d: a single round)" % DEFAULT_ROUNDS, type=int,
+                            default=DEFAULT_ROUNDS)
+        parser.add_argument("-growth", help="Factor of at least 1 by which -window grows from a round to the next (default %g)"
+                                            % DEFAULT_GROWTH, type=float, default=DEFAULT_GROWTH)
+        parser.add_argument("-gap", help="Bases between neighbouring scaffolds of a sequence of a later round (default %d, as assembledMap)"
+                                         % DEFAULT_GAP, type=int, default=DEFAULT_GAP)
+        parser.add_argument("-out", help="Directory of the results (default: saveFilesDirectory/links)", type=str, default=None)
     args = parser.parse_args(argv)
     return runPipeline(args.config, args.window, args.minPairs, args.minRatio, args.minSize, args.order, args.out, threads=args.threads,
                        device=args.device, context=context, rounds=args.rounds, growth=args.growth, gap=args.gap)

@@ -24,25 +24,18 @@ from __future__ import annotations
 
 import argparse
 import os
-import sys
 
 import numpy as np
 
-from . import _lib
-from .assembledMap import DEFAULT_GAP, build_assembly, read_order_file
-from .buildMap import STATS_COLUMNS, check_valid_pair_file
-from .hostio import paused_gc, read_scaffold_sizes
+from . import _lib, pairtool
+from .pairtool import DEFAULT_MIN_PAIRS, DEFAULT_REACH, DEFAULT_WINDOW, MAX_REACH, MAX_TABLE, flipped_order_text  # noqa: F401
 
-DEFAULT_WINDOW, DEFAULT_REACH, DEFAULT_MIN_PAIRS = 50000, 2, 4
-MAX_REACH = 64
-MAX_TABLE = 1 << 27
 COUNTER_COLUMNS = ("linked", "middle", "same", "too_far", "trans", "unlifted")
 SCAFFOLD_COLUMNS = ("scaffold", "orientation", "size", "left_zone", "right_zone", "as_lies", "flipped", "verdict")
 JUNCTION_COLUMNS = ("chromosome", "left", "right", "facing", "left_flipped", "right_flipped", "both_flipped", "verdict")
 LINK_COLUMNS = ("scaffold", "d", "neighbour", "left_left", "left_right", "right_left", "right_right")
 JUNCTION_VERDICTS = ("held", "flip_left", "flip_right", "flip_both")
 LL, LR, RL, RR = 0, 1, 2, 3                    # zone at the lower rank x zone at the higher rank
-CHUNK_PAIRS = 1 << 22
 
 
 def number_ranks(asm, sizes):
@@ -116,32 +109,9 @@ def measure(ctx, pairFile, names, sizes, asm, window, reach, threads):
     """(stats4, rank, table, counters) through the array calls of a context the caller owns: the file is parsed on the host
     in chunks (hicmi_parse_valid_pairs) and counted chunk by chunk."""
     rank = ctx.ends_begin(sizes, asm.lift_seq, asm.lift_off, asm.lift_rev, asm.seq_sizes, window, reach)
-    stats, at, size = [0, 0, 0, 0], 0, os.path.getsize(pairFile)
-    while True:
-        room = max(1, (size - at) // 12 + 1)                                   # a six-column line has 12 bytes or more
-        sa, pa, sb, pb, at, st = _lib.parse_valid_pairs(pairFile, names, sizes, first_byte=at, max_pairs=min(CHUNK_PAIRS, room),
-                                                        threads=threads)
-        stats = [a + b for a, b in zip(stats, st)]
-        ctx.ends_add_pairs(sa, pa, sb, pb)
-        if at >= size:
-            break
+    stats = pairtool.parse_in_chunks(pairFile, names, sizes, threads, ctx.ends_add_pairs)
     table, counters = ctx.ends_finish()
-    return tuple(stats), rank, table, counters
-
-
-def flipped_order_text(orderFile, flips):
-    """The order file again, every line verbatim except that the sign of each scaffold of ``flips`` is changed."""
-    out = []
-    with open(orderFile, newline="") as fh:
-        for k, line in enumerate(fh):
-            body = line.rstrip("\r\n")
-            if k and body and body[0] != "#":
-                cols = body.split("\t")
-                if cols[0] in flips:
-                    cols[1] = "+" if cols[1] == "-" else "-"
-                    line = "\t".join(cols) + line[len(body):]
-            out.append(line)
-    return "".join(out)
+    return stats, rank, table, counters
 
 
 def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT_REACH, minPairs=DEFAULT_MIN_PAIRS, outFile=None,
@@ -152,52 +122,33 @@ def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT
     v = driver.readConfigFileToVariables(configFile)
     if outFile is None:
         outFile = os.path.join(v["saveFilesDirectory"], "endSupport.txt")
-    try:
-        if window < 1:
-            raise ValueError("the window %d is below 1" % window)
-        if not 1 <= reach <= MAX_REACH:
-            raise ValueError("the reach %d is outside 1 .. %d" % (reach, MAX_REACH))
-        if minPairs < 0:
-            raise ValueError("minPairs %d is negative" % minPairs)
-        check_valid_pair_file(v["validPairFile"])
-        names, sizes = read_scaffold_sizes(v["hicProScaffSizeFile"])
-        if not names:
-            raise ValueError("hicProScaffSizeFile %s lists no scaffold" % v["hicProScaffSizeFile"])
-        if orderFile is None:
-            orderFile = v["finalOrderingsFile"] if os.path.isfile(v["finalOrderingsFile"]) else v["chromosomeOrderFile"]
-        if not os.path.isfile(orderFile):
-            raise ValueError("order file %r does not exist" % orderFile)
-        asm = build_assembly(read_order_file(orderFile), names, sizes, DEFAULT_GAP, chromosomes_only=True)
+    with pairtool.refusing(OSError, ValueError):
+        pairtool.check_thresholds(window=window, reach=reach, minPairs=minPairs)
+        names, sizes, orderFile, asm = pairtool.load(v, orderFile)
         n_placed = _lib.ends_placed_count(sizes, asm.lift_seq)
         if n_placed * reach * 4 > MAX_TABLE:
             raise ValueError("reach %d over %d placed scaffolds needs a table of %d counters, more than the %d a build can have"
                              % (reach, n_placed, n_placed * reach * 4, MAX_TABLE))
         if n_placed < 1:
             raise ValueError("no scaffold of %s has a base" % orderFile)
-    except (OSError, ValueError) as exc:
-        sys.exit("ERROR... %s. Exiting..." % exc)
     rank, seq_first = number_ranks(asm, sizes)
     tables = (asm.lift_seq, asm.lift_off, asm.lift_rev, asm.seq_sizes)
-    with paused_gc():
-        try:
-            if context is None:
-                with _lib.Context(device) as ctx:
-                    stats, got_rank, T, counters = _lib.ends_file(v["validPairFile"], names, sizes, *tables, window, reach, ctx,
-                                                                  threads=threads)
-            elif hasattr(context, "ends_file"):
-                stats, got_rank, T, counters = context.ends_file(v["validPairFile"], names, sizes, *tables, window, reach, threads=threads)
-            else:
-                stats, got_rank, T, counters = measure(context, v["validPairFile"], names, sizes, asm, window, reach, threads)
-        except _lib.HicmiError as exc:
-            sys.exit("ERROR... %s. Exiting..." % exc)
+
+    def count(ctx):
+        if context is None:
+            return _lib.ends_file(v["validPairFile"], names, sizes, *tables, window, reach, ctx, threads=threads)
+        if hasattr(ctx, "ends_file"):
+            return ctx.ends_file(v["validPairFile"], names, sizes, *tables, window, reach, threads=threads)
+        return measure(ctx, v["validPairFile"], names, sizes, asm, window, reach, threads)
+
+    stats, got_rank, T, counters = pairtool.on_context(context, device, count)
     if not np.array_equal(got_rank, rank) or T.shape != (n_placed, reach, 4):
-        sys.exit("ERROR... the library ranks the scaffolds differently from this report. Exiting...")
+        pairtool.refuse("the library ranks the scaffolds differently from this report")
     stats = tuple(stats[:4])
-    print("ENDS: lines %d, pairs used %d, unknown scaffold %d, out of range %d" % stats
-          + ", " + ", ".join("%s %d" % kv for kv in zip(COUNTER_COLUMNS, counters.tolist())))
+    print(pairtool.lines_line("ENDS", stats) + ", " + pairtool.counted(COUNTER_COLUMNS, counters))
 
     header = ["window=%d" % window, "reach=%d" % reach, "minPairs=%d" % minPairs]
-    header += ["%s=%d" % kv for kv in zip(STATS_COLUMNS, stats)] + ["%s=%d" % kv for kv in zip(COUNTER_COLUMNS, counters.tolist())]
+    header += pairtool.fields(pairtool.STATS_COLUMNS, stats) + pairtool.fields(COUNTER_COLUMNS, counters.tolist())
     out = ["#" + "\t".join(header) + "\n", "#" + "\t".join(SCAFFOLD_COLUMNS) + "\n"]
     flips, junctions, verdicts = set(), [], {}
     calls = scaffold_calls(asm, sizes, rank, seq_first, T, minPairs)
@@ -221,22 +172,17 @@ def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT
                                        + [junction_verdict(figures, minPairs)]) + "\n")
     out += ["### Junctions ###\n", "#" + "\t".join(JUNCTION_COLUMNS) + "\n"] + junctions
     flipped_text = None if flippedFile is None else flipped_order_text(orderFile, flips)
-    os.makedirs(os.path.dirname(os.path.abspath(outFile)), exist_ok=True)
-    with open(outFile, "w") as fh:
-        fh.write("".join(out))
+    pairtool.write_text(outFile, "".join(out), mkdir=True)
     if flippedFile is not None:
-        with open(flippedFile, "w", newline="") as fh:
-            fh.write(flipped_text)
+        pairtool.write_text(flippedFile, flipped_text, newline="")
     if fullDir is not None:
-        os.makedirs(fullDir, exist_ok=True)
-        with open(os.path.join(fullDir, "ends.links.tsv"), "w") as fh:
-            fh.write("#" + "\t".join(LINK_COLUMNS) + "\n")
-            for comps in asm.components:
-                filled = [s for s, _off, _o in comps if sizes[s] > 0]
-                for k, s in enumerate(filled):
-                    for d in range(1, min(reach, len(filled) - 1 - k) + 1):
-                        fh.write("%s\t%d\t%s\t%d\t%d\t%d\t%d\n" % ((names[s], d, names[filled[k + d]])
-                                                                    + tuple(int(x) for x in T[rank[s], d - 1])))
+        links = ["#" + "\t".join(LINK_COLUMNS) + "\n"]
+        for comps in asm.components:
+            filled = [s for s, _off, _o in comps if sizes[s] > 0]
+            for k, s in enumerate(filled):
+                for d in range(1, min(reach, len(filled) - 1 - k) + 1):
+                    links.append("%s\t%d\t%s\t%d\t%d\t%d\t%d\n" % ((names[s], d, names[filled[k + d]]) + tuple(int(x) for x in T[rank[s], d - 1])))
+        pairtool.write_text(os.path.join(fullDir, "ends.links.tsv"), "".join(links), mkdir=True)
     n_open = sum(x == "open" for x in verdicts.values())
     print("ENDS: %d scaffold(s) to flip, %d open, %d of %d junction(s) not held" % (
         len(flips), n_open, sum(not j.endswith("\theld\n") for j in junctions), len(junctions)))
@@ -247,21 +193,17 @@ def main(argv=None, context=None):
     parser = argparse.ArgumentParser(description="Counts, on the GPU, the read pairs of validPairFile that link the end zones of "
                                                  "neighbouring scaffolds of an ordering, and reports which scaffolds lie the wrong "
                                                  "way round.")
-    parser.add_argument("-config", help="Full file path to the config file", required=True, type=str)
-    parser.add_argument("-order", help="Order file (default: finalOrderingsFile when it exists, else chromosomeOrderFile)",
-                        type=str, default=None)
-    parser.add_argument("-window", help="End zone in bp (default %d)" % DEFAULT_WINDOW, type=int, default=DEFAULT_WINDOW)
-    parser.add_argument("-reach", help="Places two scaffolds may lie apart, 1 .. %d (default %d)" % (MAX_REACH, DEFAULT_REACH), type=int,
-                        default=DEFAULT_REACH)
-    parser.add_argument("-minPairs", help="Links below which a verdict stays open (default %d)" % DEFAULT_MIN_PAIRS, type=int,
-                        default=DEFAULT_MIN_PAIRS)
-    parser.add_argument("-out", help="Report (default: saveFilesDirectory/endSupport.txt)", type=str, default=None)
-    parser.add_argument("-flipped", help="Write the order file again with the sign of every scaffold called flip changed", type=str,
-                        default=None)
-    parser.add_argument("-full", help="Write ends.links.tsv, the four counts of every entry inside a chromosome, into this directory",
-                        type=str, default=None)
-    parser.add_argument("-threads", help="Host threads of the parser (default 0: all)", type=int, default=0)
-    parser.add_argument("-device", help="GPU index (default 0)", type=int, default=0)
+    with pairtool.common_arguments(parser):
+        parser.add_argument("-window", help="End zone in bp (default %d)" % DEFAULT_WINDOW, type=int, default=DEFAULT_WINDOW)
+        parser.add_argument("-reach", help="Places two scaffolds may lie apart, 1 .. %d (default %d)" % (MAX_REACH, DEFAULT_REACH),
+                            type=int, default=DEFAULT_REACH)
+        parser.add_argument("-minPairs", help="Links below which a verdict stays open (default %d)" % DEFAULT_MIN_PAIRS, type=int,
+                            default=DEFAULT_MIN_PAIRS)
+        parser.add_argument("-out", help="Report (default: saveFilesDirectory/endSupport.txt)", type=str, default=None)
+        parser.add_argument("-flipped", help="Write the order file again with the sign of every scaffold called flip changed", type=str,
+                            default=None)
+        parser.add_argument("-full", help="Write ends.links.tsv, the four counts of every entry inside a chromosome, into this directory",
+                            type=str, default=None)
     args = parser.parse_args(argv)
     return runPipeline(args.config, args.order, args.window, args.reach, args.minPairs, args.out, args.flipped, args.full,
                        threads=args.threads, device=args.device, context=context)

@@ -23,19 +23,14 @@ from __future__ import annotations
 
 import argparse
 import os
-import sys
 
 import numpy as np
 
-from . import _lib
+from . import _lib, pairtool
 from . import placeUnplaced as place
-from .assembledMap import DEFAULT_GAP, build_assembly, read_order_file
-from .buildMap import STATS_COLUMNS, check_valid_pair_file
-from .hostio import paused_gc, read_scaffold_sizes
+from .pairtool import (DEFAULT_MIN_PAIRS, DEFAULT_MIN_RATIO, DEFAULT_REACH, DEFAULT_WINDOW, MAX_REACH, MAX_TABLE,  # noqa: F401
+                       moved_order_text)
 
-DEFAULT_WINDOW, DEFAULT_REACH, DEFAULT_MIN_PAIRS, DEFAULT_MIN_RATIO = 50000, 2, 4, 2.0
-MAX_REACH = 64
-MAX_TABLE = 1 << 27
 COUNTER_COLUMNS = ("seated", "middle", "trans", "same", "unlifted")
 SEAT_COLUMNS = ("scaffold", "orientation", "size", "links", "chrom_links", "best_chromosome", "ratio", "home_score", "left", "right",
                 "best_orientation", "score", "runner_up", "gain", "verdict")
@@ -128,60 +123,6 @@ def move_targets(asm, sizes, calls, moves, names):
     return out
 
 
-def moved_order_text(orderFile, moves):
-    """The order file again with the line of every scaffold of ``moves`` - {name: (where, orientation)} - taken out and put
-    back before the line of the scaffold ``where``, or after it when ``where`` is (name, None), its sign set to
-    ``orientation``.  Every other byte of every line is kept; a file without a final newline stays one."""
-    with open(orderFile, newline="") as fh:
-        lines = list(fh)
-
-    def name_of(k):
-        body = lines[k].rstrip("\r\n")
-        return body.split("\t")[0] if k and body and body[0] != "#" else None
-
-    taken = {}
-    for k in range(len(lines)):
-        name = name_of(k)
-        if name in moves:
-            body = lines[k].rstrip("\r\n")
-            cols = body.split("\t")
-            cols[1] = moves[name][1]
-            taken[name] = "\t".join(cols) + lines[k][len(body):]
-    before = {where: name for name, (where, _o) in moves.items() if not isinstance(where, tuple)}
-    after = {where[0]: name for name, (where, _o) in moves.items() if isinstance(where, tuple)}
-    out = []
-    for k, line in enumerate(lines):
-        name = name_of(k)
-        if name in taken:
-            continue
-        if name is not None and name in before:
-            out.append(taken[before[name]])
-        out.append(line)
-        if name is not None and name in after:
-            out.append(taken[after[name]])
-    # the one line without an ending was the last one: inside the file it takes its neighbour's, and the new last line has none
-    final = bool(lines) and lines[-1].endswith(("\n", "\r"))
-    for k, line in enumerate(out):
-        body = line.rstrip("\r\n")
-        if k < len(out) - 1 and body == line:
-            nxt = out[k + 1]
-            out[k] = body + (nxt[len(nxt.rstrip("\r\n")):] or "\n")
-        elif k == len(out) - 1 and not final:
-            out[k] = body
-    return "".join(out)
-
-
-def check_arguments(window, reach, minPairs, minRatio):
-    if window < 1:
-        raise ValueError("the window %d is below 1" % window)
-    if not 1 <= reach <= MAX_REACH:
-        raise ValueError("the reach %d is outside 1 .. %d" % (reach, MAX_REACH))
-    if minPairs < 0:
-        raise ValueError("minPairs %d is negative" % minPairs)
-    if not minRatio >= 1:
-        raise ValueError("minRatio %g is below 1" % minRatio)
-
-
 def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT_REACH, minPairs=DEFAULT_MIN_PAIRS,
                 minRatio=DEFAULT_MIN_RATIO, outFile=None, movedFile=None, fullDir=None, threads=0, device=0, context=None):
     """``context``: a context of the caller's that has ``pairs_file``, ``seats_resident`` and ``pairs_drop``; None: a context
@@ -191,17 +132,9 @@ def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT
     v = driver.readConfigFileToVariables(configFile)
     if outFile is None:
         outFile = os.path.join(v["saveFilesDirectory"], "seatSupport.txt")
-    try:
-        check_arguments(window, reach, minPairs, minRatio)
-        check_valid_pair_file(v["validPairFile"])
-        names, sizes = read_scaffold_sizes(v["hicProScaffSizeFile"])
-        if not names:
-            raise ValueError("hicProScaffSizeFile %s lists no scaffold" % v["hicProScaffSizeFile"])
-        if orderFile is None:
-            orderFile = v["finalOrderingsFile"] if os.path.isfile(v["finalOrderingsFile"]) else v["chromosomeOrderFile"]
-        if not os.path.isfile(orderFile):
-            raise ValueError("order file %r does not exist" % orderFile)
-        asm = build_assembly(read_order_file(orderFile), names, sizes, DEFAULT_GAP, chromosomes_only=True)
+    with pairtool.refusing(OSError, ValueError):
+        pairtool.check_thresholds(window=window, reach=reach, minPairs=minPairs, minRatio=minRatio)
+        names, sizes, orderFile, asm = pairtool.load(v, orderFile)
         n_placed = _lib.ends_placed_count(sizes, asm.lift_seq)
         if n_placed < 1:
             raise ValueError("no scaffold of %s has a base" % orderFile)
@@ -209,8 +142,6 @@ def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT
         if n_table > MAX_TABLE:
             raise ValueError("%d placed scaffolds in %d chromosomes need a table of %d counters, more than the %d a call can have"
                              % (n_placed, len(asm.components), n_table, MAX_TABLE))
-    except (OSError, ValueError) as exc:
-        sys.exit("ERROR... %s. Exiting..." % exc)
     n_seq = len(asm.components)
 
     def count(ctx):
@@ -220,25 +151,16 @@ def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT
         finally:
             ctx.pairs_drop()
 
-    with paused_gc():
-        try:
-            if context is None:
-                with _lib.Context(device) as ctx:
-                    stats, got_first, table, counters = count(ctx)
-            else:
-                stats, got_first, table, counters = count(context)
-        except _lib.HicmiError as exc:
-            sys.exit("ERROR... %s. Exiting..." % exc)
+    stats, got_first, table, counters = pairtool.on_context(context, device, count)
     if not np.array_equal(got_first, first) or table.shape != (n_table,):
-        sys.exit("ERROR... the library numbers the placed scaffolds differently from this report. Exiting...")
-    print("SEATS: lines %d, pairs used %d, unknown scaffold %d, out of range %d" % stats
-          + ", " + ", ".join("%s %d" % kv for kv in zip(COUNTER_COLUMNS, counters.tolist())))
+        pairtool.refuse("the library numbers the placed scaffolds differently from this report")
+    print(pairtool.lines_line("SEATS", stats) + ", " + pairtool.counted(COUNTER_COLUMNS, counters))
 
     calls = seat_calls(asm, sizes, first, table, reach, minPairs, minRatio)
     moves = chosen_moves(asm, sizes, calls)
     filled, _B = place.chromosome_members(asm, sizes)
     header = ["window=%d" % window, "reach=%d" % reach, "minPairs=%d" % minPairs, "minRatio=%g" % minRatio]
-    header += ["%s=%d" % kv for kv in zip(STATS_COLUMNS, stats)] + ["%s=%d" % kv for kv in zip(COUNTER_COLUMNS, counters.tolist())]
+    header += pairtool.fields(pairtool.STATS_COLUMNS, stats) + pairtool.fields(COUNTER_COLUMNS, counters.tolist())
     out = ["#" + "\t".join(header) + "\n", "#" + "\t".join(SEAT_COLUMNS) + "\n"]
     verdicts = {}
     for q, comps in enumerate(asm.components):
@@ -257,36 +179,19 @@ def runPipeline(configFile, orderFile=None, window=DEFAULT_WINDOW, reach=DEFAULT
                 g, o, m, runner_up, gap_verdict = call["gap"]
                 others = [t for t in filled[q] if t != s]
                 cols.append(str(call["home_score"]))
-                if gap_verdict == "chromosome_only":
-                    cols += ["NA", "NA", "NA"]
-                else:
-                    cols += [names[others[g - 1]] if g else "start", names[others[g]] if g < len(others) else "end", "+-"[o]]
+                cols += ["NA", "NA", "NA"] if gap_verdict == "chromosome_only" else list(pairtool.gap_neighbours(names, others, g)) + ["+-"[o]]
                 cols += [str(m), str(runner_up), str(call["gain"])]
             else:
                 cols += ["NA"] * 7
             out.append("\t".join(cols + [call["verdict"]]) + "\n")
     moved_text = None if movedFile is None else moved_order_text(orderFile, move_targets(asm, sizes, calls, moves, names))
-    os.makedirs(os.path.dirname(os.path.abspath(outFile)), exist_ok=True)
-    with open(outFile, "w") as fh:
-        fh.write("".join(out))
+    pairtool.write_text(outFile, "".join(out), mkdir=True)
     if movedFile is not None:
-        with open(movedFile, "w", newline="") as fh:
-            fh.write(moved_text)
+        pairtool.write_text(movedFile, moved_text, newline="")
     if fullDir is not None:
-        os.makedirs(fullDir, exist_ok=True)
-        with open(os.path.join(fullDir, "seats.chromosomes.tsv"), "w") as fh:
-            fh.write("#scaffold\t" + "\t".join("Chr_%d" % (q + 1) for q in range(n_seq)) + "\n")
-            for s in sorted(s for s in calls if "a" in calls[s]):
-                fh.write(names[s] + "\t" + "\t".join(str(x) for x in calls[s]["a"]) + "\n")
-        with open(os.path.join(fullDir, "seats.gaps.tsv"), "w") as fh:
-            fh.write("#scaffold\tchromosome\tgap\tleft\tright\torientation\tscore\n")
-            for s in sorted(s for s in calls if "scores" in calls[s]):
-                q = calls[s]["q"]
-                others = [t for t in filled[q] if t != s]
-                for g, both in enumerate(calls[s]["scores"]):
-                    for o, x in enumerate(both):
-                        fh.write("%s\t%d\t%d\t%s\t%s\t%s\t%d\n" % (names[s], q + 1, g, names[others[g - 1]] if g else "start",
-                                                                   names[others[g]] if g < len(others) else "end", "+-"[o], x))
+        pairtool.write_gap_tables(fullDir, "seats", names, n_seq, [(s, calls[s]["a"]) for s in sorted(calls) if "a" in calls[s]],
+                                  [(s, calls[s]["q"], [t for t in filled[calls[s]["q"]] if t != s], calls[s]["scores"])
+                                   for s in sorted(calls) if "scores" in calls[s]])
     tally = {w: sum(x == w for x in verdicts.values()) for w in ("move", "flip", "elsewhere", "open")}
     print("SEATS: %d scaffold(s) to move, %d to flip, %d elsewhere, %d open; %d move(s) chosen" % (
         tally["move"], tally["flip"], tally["elsewhere"], tally["open"], len(moves)))
@@ -297,21 +202,17 @@ def main(argv=None, context=None):
     parser = argparse.ArgumentParser(description="Counts, on the GPU, for every scaffold of an order file the read pairs of "
                                                  "validPairFile that link it to the chromosomes and to the ends of the scaffolds "
                                                  "of its own, and reports whether it lies where they place it.")
-    parser.add_argument("-config", help="Full file path to the config file", required=True, type=str)
-    parser.add_argument("-order", help="Order file (default: finalOrderingsFile when it exists, else chromosomeOrderFile)",
-                        type=str, default=None)
-    parser.add_argument("-window", help="End zone of a scaffold in bp (default %d)" % DEFAULT_WINDOW, type=int, default=DEFAULT_WINDOW)
-    parser.add_argument("-reach", help="Scaffolds on either side of a gap that score it, 1 .. %d (default %d)" % (MAX_REACH, DEFAULT_REACH),
-                        type=int, default=DEFAULT_REACH)
-    parser.add_argument("-minPairs", help="Links below which neither a chromosome nor a gap is chosen (default %d)" % DEFAULT_MIN_PAIRS,
-                        type=int, default=DEFAULT_MIN_PAIRS)
-    parser.add_argument("-minRatio", help="Link density of the best chromosome over the second best below which none is chosen "
-                                          "(default %g)" % DEFAULT_MIN_RATIO, type=float, default=DEFAULT_MIN_RATIO)
-    parser.add_argument("-out", help="Report (default: saveFilesDirectory/seatSupport.txt)", type=str, default=None)
-    parser.add_argument("-moved", help="Write the order file again with one move per chromosome applied", type=str, default=None)
-    parser.add_argument("-full", help="Write seats.chromosomes.tsv and seats.gaps.tsv into this directory", type=str, default=None)
-    parser.add_argument("-threads", help="Host threads of the parser (default 0: all)", type=int, default=0)
-    parser.add_argument("-device", help="GPU index (default 0)", type=int, default=0)
+    with pairtool.common_arguments(parser):
+        parser.add_argument("-window", help="End zone of a scaffold in bp (default %d)" % DEFAULT_WINDOW, type=int, default=DEFAULT_WINDOW)
+        parser.add_argument("-reach", help="Scaffolds on either side of a gap that score it, 1 .. %d (default %d)" % (MAX_REACH, DEFAULT_REACH),
+                            type=int, default=DEFAULT_REACH)
+        parser.add_argument("-minPairs", help="Links below which neither a chromosome nor a gap is chosen (default %d)" % DEFAULT_MIN_PAIRS,
+                            type=int, default=DEFAULT_MIN_PAIRS)
+        parser.add_argument("-minRatio", help="Link density of the best chromosome over the second best below which none is chosen "
+                                              "(default %g)" % DEFAULT_MIN_RATIO, type=float, default=DEFAULT_MIN_RATIO)
+        parser.add_argument("-out", help="Report (default: saveFilesDirectory/seatSupport.txt)", type=str, default=None)
+        parser.add_argument("-moved", help="Write the order file again with one move per chromosome applied", type=str, default=None)
+        parser.add_argument("-full", help="Write seats.chromosomes.tsv and seats.gaps.tsv into this directory", type=str, default=None)
     args = parser.parse_args(argv)
     return runPipeline(args.config, args.order, args.window, args.reach, args.minPairs, args.minRatio, args.out, args.moved, args.full,
                        threads=args.threads, device=args.device, context=context)

@@ -19,14 +19,11 @@ from __future__ import annotations
 
 import argparse
 import os
-import sys
 
 import numpy as np
 
-from . import _lib
-from .assembledMap import DEFAULT_GAP, build_assembly, read_order_file
-from .buildMap import STATS_COLUMNS, check_valid_pair_file
-from .hostio import paused_gc, read_scaffold_sizes
+from . import _lib, pairtool
+from .assembledMap import DEFAULT_GAP, build_assembly
 
 DEFAULT_STEP, DEFAULT_FLANK, DEFAULT_MIN_RATIO = 10000, 8, 0.2
 MAX_FLANK = 4096
@@ -34,7 +31,6 @@ MAX_CELLS = 1 << 27
 COUNTER_COLUMNS = ("marked", "one_cell", "beyond_max_span", "trans", "unlifted")
 SCAFFOLD_COLUMNS = ("scaffold", "orientation", "size", "cells", "cut_after", "depth", "flank_depth", "ratio", "verdict")
 JUNCTION_COLUMNS = ("chromosome", "left", "right", "depth", "flank_depth", "ratio", "verdict")
-CHUNK_PAIRS = 1 << 22
 
 
 def identity_assembly(names, sizes):
@@ -80,17 +76,9 @@ def measure(ctx, pairFile, names, sizes, asm, step, maxSpan, flank, recs, thread
     """(stats4, cell_first, picks, counters, depth) through the array calls of a context the caller owns: the file is parsed on
     the host in chunks (hicmi_parse_valid_pairs) and marked chunk by chunk."""
     cell_first = ctx.span_begin(sizes, asm.lift_seq, asm.lift_off, asm.lift_rev, asm.seq_sizes, step, maxSpan)
-    stats, at, size = [0, 0, 0, 0], 0, os.path.getsize(pairFile)
-    while True:
-        room = max(1, (size - at) // 12 + 1)                                   # a six-column line has 12 bytes or more
-        sa, pa, sb, pb, at, st = _lib.parse_valid_pairs(pairFile, names, sizes, first_byte=at, max_pairs=min(CHUNK_PAIRS, room),
-                                                        threads=threads)
-        stats = [a + b for a, b in zip(stats, st)]
-        ctx.span_add_pairs(sa, pa, sb, pb)
-        if at >= size:
-            break
+    stats = pairtool.parse_in_chunks(pairFile, names, sizes, threads, ctx.span_add_pairs)
     picks, counters, depth = ctx.span_finish(flank, recs, want_depth=want_depth)
-    return tuple(stats), cell_first, picks, counters, depth
+    return stats, cell_first, picks, counters, depth
 
 
 def pick_columns(pick, flank, minRatio, low, fine):
@@ -110,7 +98,7 @@ def runPipeline(configFile, orderFile=None, scaffoldsOnly=False, gap=DEFAULT_GAP
     v = driver.readConfigFileToVariables(configFile)
     if outFile is None:
         outFile = os.path.join(v["saveFilesDirectory"], "spanSupport.txt")
-    try:
+    with pairtool.refusing(OSError, ValueError):
         if step < 1:
             raise ValueError("the step %d is below 1" % step)
         if not 1 <= flank <= MAX_FLANK:
@@ -119,47 +107,33 @@ def runPipeline(configFile, orderFile=None, scaffoldsOnly=False, gap=DEFAULT_GAP
             raise ValueError("maxSpan %d is negative" % maxSpan)
         if gap < 0:
             raise ValueError("the gap %d is negative" % gap)
-        check_valid_pair_file(v["validPairFile"])
-        names, sizes = read_scaffold_sizes(v["hicProScaffSizeFile"])
-        if not names:
-            raise ValueError("hicProScaffSizeFile %s lists no scaffold" % v["hicProScaffSizeFile"])
+        names, sizes = pairtool.read_scaffolds(v)
         if scaffoldsOnly:
             if orderFile is not None:
                 raise ValueError("-scaffolds takes no order file")
             asm = identity_assembly(names, sizes)
         else:
-            if orderFile is None:
-                orderFile = v["finalOrderingsFile"] if os.path.isfile(v["finalOrderingsFile"]) else v["chromosomeOrderFile"]
-            if not os.path.isfile(orderFile):
-                raise ValueError("order file %r does not exist" % orderFile)
-            asm = build_assembly(read_order_file(orderFile), names, sizes, gap)
+            asm = pairtool.order_assembly(pairtool.resolve_order(v, orderFile), names, sizes, gap, chromosomes_only=False)
         n_cells = _lib.span_cell_count(sizes, asm.lift_seq, step)
         if n_cells > MAX_CELLS:
             raise ValueError("step %d cuts the assembly into %d cells, more than the %d a build can have" % (step, n_cells, MAX_CELLS))
         if n_cells < 1:
             raise ValueError("no scaffold of %s has a base" % v["hicProScaffSizeFile"])
-    except (OSError, ValueError) as exc:
-        sys.exit("ERROR... %s. Exiting..." % exc)
     cell_first, seq_first = number_cells(asm, sizes, step)
     recs, of_scaffold, of_junction = make_records(asm, sizes, step, cell_first, seq_first)
     want_depth = fullDir is not None
-    with paused_gc():
-        try:
-            if context is not None:
-                stats, got_first, picks, counters, depth = measure(context, v["validPairFile"], names, sizes, asm, step, maxSpan, flank,
-                                                                    recs, threads, want_depth)
-            else:
-                with _lib.Context(device) as ctx:
-                    stats, got_first, picks, counters, depth = _lib.span_file(
-                        v["validPairFile"], names, sizes, asm.lift_seq, asm.lift_off, asm.lift_rev, asm.seq_sizes, step, maxSpan, flank,
-                        recs, ctx, threads=threads, want_depth=want_depth)
-        except _lib.HicmiError as exc:
-            sys.exit("ERROR... %s. Exiting..." % exc)
+
+    def count(ctx):
+        if context is not None:
+            return measure(ctx, v["validPairFile"], names, sizes, asm, step, maxSpan, flank, recs, threads, want_depth)
+        return _lib.span_file(v["validPairFile"], names, sizes, asm.lift_seq, asm.lift_off, asm.lift_rev, asm.seq_sizes, step, maxSpan, flank,
+                              recs, ctx, threads=threads, want_depth=want_depth)
+
+    stats, got_first, picks, counters, depth = pairtool.on_context(context, device, count)
     if not np.array_equal(got_first, cell_first):
-        sys.exit("ERROR... the library numbers the cells differently from this report. Exiting...")
+        pairtool.refuse("the library numbers the cells differently from this report")
     stats = tuple(stats[:4])
-    print("SPANS: lines %d, pairs used %d, unknown scaffold %d, out of range %d" % stats
-          + ", " + ", ".join("%s %d" % kv for kv in zip(COUNTER_COLUMNS, counters.tolist())))
+    print(pairtool.lines_line("SPANS", stats) + ", " + pairtool.counted(COUNTER_COLUMNS, counters))
 
     def scaffold_line(s, orientation):
         L, cells = int(sizes[s]), (-(-int(sizes[s]) // step) if cell_first[s] >= 0 else 0)
@@ -172,7 +146,7 @@ def runPipeline(configFile, orderFile=None, scaffoldsOnly=False, gap=DEFAULT_GAP
         return [names[s], orientation, str(L), str(cells), cut] + cols
 
     header = ["step=%d" % step, "maxSpan=%d" % maxSpan, "flank=%d" % flank, "minRatio=%r" % float(minRatio)]
-    header += ["%s=%d" % kv for kv in zip(STATS_COLUMNS, stats)] + ["%s=%d" % kv for kv in zip(COUNTER_COLUMNS, counters.tolist())]
+    header += pairtool.fields(pairtool.STATS_COLUMNS, stats) + pairtool.fields(COUNTER_COLUMNS, counters.tolist())
     out = ["#" + "\t".join(header) + "\n", "#" + "\t".join(SCAFFOLD_COLUMNS) + "\n"]
     suspects, junctions = [], []
     n_listed = len(asm.components) if scaffoldsOnly else asm.n_chromosomes
@@ -201,12 +175,9 @@ def runPipeline(configFile, orderFile=None, scaffoldsOnly=False, gap=DEFAULT_GAP
                 out.append("\t".join(cols) + "\n")
                 if cols[-1] == "suspect":
                     suspects.append((cols[0], cols[4], cols[7]))
-    os.makedirs(os.path.dirname(os.path.abspath(outFile)), exist_ok=True)
-    with open(outFile, "w") as fh:
-        fh.write("".join(out))
+    pairtool.write_text(outFile, "".join(out), mkdir=True)
     if cutsFile is not None:
-        with open(cutsFile, "w") as fh:
-            fh.write("".join("%s\t%s\t%s\n" % row for row in suspects))
+        pairtool.write_text(cutsFile, "".join("%s\t%s\t%s\n" % row for row in suspects))
     if fullDir is not None:
         os.makedirs(fullDir, exist_ok=True)
         with open(os.path.join(fullDir, "spans.depth.tsv"), "w") as fh:
@@ -224,22 +195,18 @@ def runPipeline(configFile, orderFile=None, scaffoldsOnly=False, gap=DEFAULT_GAP
 def main(argv=None, context=None):
     parser = argparse.ArgumentParser(description="Counts, on the GPU, the read pairs of validPairFile that span every cut of every "
                                                  "scaffold and every junction of an ordering, and reports where the depth dips.")
-    parser.add_argument("-config", help="Full file path to the config file", required=True, type=str)
-    parser.add_argument("-order", help="Order file (default: finalOrderingsFile when it exists, else chromosomeOrderFile)",
-                        type=str, default=None)
-    parser.add_argument("-scaffolds", help="Every scaffold on its own: no order file, only cuts are reported", action="store_true")
-    parser.add_argument("-gap", help="Bases between neighbouring scaffolds (default %d, as Part 4 writes)" % DEFAULT_GAP, type=int,
-                        default=DEFAULT_GAP)
-    parser.add_argument("-step", help="Cell size in bp (default %d)" % DEFAULT_STEP, type=int, default=DEFAULT_STEP)
-    parser.add_argument("-maxSpan", help="Longest distance of a pair that counts, in bp (default 0: no limit)", type=int, default=0)
-    parser.add_argument("-flank", help="Cells of each flank (default %d)" % DEFAULT_FLANK, type=int, default=DEFAULT_FLANK)
-    parser.add_argument("-minRatio", help="Ratio below which a cut is suspect and a junction weak (default %r)" % DEFAULT_MIN_RATIO,
-                        type=float, default=DEFAULT_MIN_RATIO)
-    parser.add_argument("-out", help="Report (default: saveFilesDirectory/spanSupport.txt)", type=str, default=None)
-    parser.add_argument("-cuts", help="Write scaffold, cut_after and ratio of every suspect scaffold to this file", type=str, default=None)
-    parser.add_argument("-full", help="Write spans.depth.tsv, the depth of every cell, into this directory", type=str, default=None)
-    parser.add_argument("-threads", help="Host threads of the parser (default 0: all)", type=int, default=0)
-    parser.add_argument("-device", help="GPU index (default 0)", type=int, default=0)
+    with pairtool.common_arguments(parser):
+        parser.add_argument("-scaffolds", help="Every scaffold on its own: no order file, only cuts are reported", action="store_true")
+        parser.add_argument("-gap", help="Bases between neighbouring scaffolds (default %d, as Part 4 writes)" % DEFAULT_GAP, type=int,
+                            default=DEFAULT_GAP)
+        parser.add_argument("-step", help="Cell size in bp (default %d)" % DEFAULT_STEP, type=int, default=DEFAULT_STEP)
+        parser.add_argument("-maxSpan", help="Longest distance of a pair that counts, in bp (default 0: no limit)", type=int, default=0)
+        parser.add_argument("-flank", help="Cells of each flank (default %d)" % DEFAULT_FLANK, type=int, default=DEFAULT_FLANK)
+        parser.add_argument("-minRatio", help="Ratio below which a cut is suspect and a junction weak (default %r)" % DEFAULT_MIN_RATIO,
+                            type=float, default=DEFAULT_MIN_RATIO)
+        parser.add_argument("-out", help="Report (default: saveFilesDirectory/spanSupport.txt)", type=str, default=None)
+        parser.add_argument("-cuts", help="Write scaffold, cut_after and ratio of every suspect scaffold to this file", type=str, default=None)
+        parser.add_argument("-full", help="Write spans.depth.tsv, the depth of every cell, into this directory", type=str, default=None)
     args = parser.parse_args(argv)
     return runPipeline(args.config, args.order, args.scaffolds, args.gap, args.step, args.maxSpan, args.flank, args.minRatio, args.out,
                        args.cuts, args.full, threads=args.threads, device=args.device, context=context)
