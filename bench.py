@@ -3,13 +3,20 @@
 ICE-balanced contact map that is already resident in HBM (BASELINE.json metric: Part1+Part2
 wall-clock and bins/s).
 
-    python bench.py --gpus 1 --steps 3 --warmup 1            # 16,000-bin map (BASELINE configs[2])
+    python bench.py --gpus 1 --steps 3 --warmup 1            # 16,000-bin map (BASELINE configs[2]): the headline figure
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full     # + every other measurement below (minutes, not seconds)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
     python bench.py ... --dump-outputs DIR                   # + the last timed step's outputs as DIR/<name>.npy
 
 The inputs are seeded: the same arguments give the same map, so two builds can be compared output for output.
 
-Rank 0 prints ONE JSON line (contract in the task prompt) with these extra objects:
+A plain run does only what its headline figure needs: it sets the map up, warms up, times the steps, writes the outputs if
+asked to, and prints the line.  Whatever takes a run of its own - another map size, an untimed step with events around every
+launch, the CPU oracle, the CLI from files - is behind --full (extra_legs() below); the --no-* options leave single ones out
+of a --full run.
+
+Rank 0 prints ONE JSON line.  `roofline` (and `kernels_ms_per_step`) is read from the timed steps themselves and always
+there; the other objects of this list need --full:
   roofline       - the kernel family that took the most device time in the timed region: its ALGORITHMIC bytes per
                    launch (for the nn-chain the kernels count the columns their row scans visit) / its
                    average launch duration (HIP events on the library's own stream, hicmi_timing_*), against the
@@ -437,6 +444,18 @@ def timed_run(job, steps, warmup, timing_mode, barrier, reduce_dev):
     return elapsed, timing, stats
 
 
+def extra_legs(args, world):
+    """Which measurements beside the headline figure this run makes: none without --full; with it, each one that its
+    --no-* option, the number of ranks and the workload leave in (what a default run made before --full existed)."""
+    full, one = bool(args.full), world == 1
+    whole = one and not args.part1_only
+    return {"table": full and one and not args.no_table,
+            "32k": full and whole and not args.no_32k and args.bins != 32000,
+            "64k": full and whole and not args.no_64k and args.bins != 64000,
+            "cpu_baseline": full and one and not args.no_cpu_baseline,
+            "e2e": full and one and not args.no_e2e and not args.no_cpu_baseline}
+
+
 def roofline_of(timing, stats, steps, n, workers):
     # Part 2 families are summed over the concurrent worker streams (and the queued insertion is timed as
     # one region per chromosome), so their wall-clock share is about 1/workers of the sum
@@ -462,7 +481,7 @@ def roofline_of(timing, stats, steps, n, workers):
     return out
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=4)
@@ -473,11 +492,14 @@ def main():
     ap.add_argument("--part1-only", action="store_true", help="BASELINE configs[1]: clustering + cuts only")
     ap.add_argument("--f32", action="store_true", help="contacts rounded to fp32 values (BASELINE configs[4] stores fp32)")
     ap.add_argument("--cpu-sample-bins", type=int, default=2000, help="BASELINE configs[0]")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-32k", action="store_true", help="skip the north_star_32k object")
-    ap.add_argument("--no-64k", action="store_true", help="skip the configs4_64k_f32 object")
-    ap.add_argument("--no-table", action="store_true", help="skip the extra untimed step behind roofline_all")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the text-to-files run of the CLI at 2,000 bins")
+    ap.add_argument("--full", action="store_true",
+                    help="also make every measurement beside the headline figure: roofline_all / mfma, north_star_32k, "
+                         "configs4_64k_f32, cpu_baseline, e2e (a plain run makes none of them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle (and without e2e)")
+    ap.add_argument("--no-32k", action="store_true", help="--full without the north_star_32k object")
+    ap.add_argument("--no-64k", action="store_true", help="--full without the configs4_64k_f32 object")
+    ap.add_argument("--no-table", action="store_true", help="--full without the extra untimed step behind roofline_all")
+    ap.add_argument("--no-e2e", action="store_true", help="--full without the text-to-files runs of the CLI")
     ap.add_argument("--weak", action="store_true",
                     help="N > 1: one independent map per rank (weak scaling) instead of ONE map over all ranks")
     ap.add_argument("--one-map", action="store_true", help="(default for N > 1; kept for earlier command lines)")
@@ -489,6 +511,11 @@ def main():
                     help="which kernel families get HIP-event timing inside the timed region")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64)")
+    return ap
+
+
+def main():
+    ap = arg_parser()
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -577,7 +604,8 @@ def main():
                                 "part2_load_imbalance_max_over_mean": (max(loads) / (sum(loads) / len(loads))) if sum(loads) else None,
                                 "part1": "row-sharded (one all-gather of the owned flags per scan)" if shard_p1 else
                                          "replicated on every rank (the chain does not shard: DESIGN.md section 7)"}
-    if world == 1 and not args.no_table:
+    legs = extra_legs(args, world)
+    if legs["table"]:
         # one more step, untimed, with events around EVERY launch: the per-kernel roofline table
         _e, t_all, _s = timed_run(job, 1, 0, 1, dist.barrier, reduce_dev)
         out["roofline_all"] = family_table(t_all, 1, n, max(1, min(p2.WORKERS, 8)))
@@ -602,22 +630,22 @@ def main():
         torch.cuda.empty_cache()
         return obj
 
-    if world == 1 and not args.no_32k and n != 32000 and not args.part1_only:
+    if legs["32k"]:
         # north_star's single-GPU target size, same step, a few repetitions (its own synthetic map)
         out["north_star_32k"] = side_job(32000, False, 3, 1)
-    if world == 1 and not args.no_64k and n != 64000 and not args.part1_only:
+    if legs["64k"]:
         # BASELINE configs[4]'s map on ONE GPU: 64,000 bins, contacts rounded to fp32 values (every row then holds equal
         # similarities: the exposed part of the row sort is k_rank_rows_tied, reported in kernels_ms_per_step)
         out["configs4_64k_f32"] = side_job(64000, True, 2, 1)
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if legs["cpu_baseline"]:
             work = tempfile.mkdtemp(prefix="hicbench_cpu_")
             with contextlib.redirect_stdout(io.StringIO()):
                 out["cpu_baseline"] = cpu_baseline(args.cpu_sample_bins, args.n_scaffolds, args.scan_scaffolds, work)
             shutil.rmtree(work, ignore_errors=True)
         else:
             out["cpu_baseline"] = None
-        if not args.no_e2e and not args.no_cpu_baseline and world == 1:
+        if legs["e2e"]:
             work = tempfile.mkdtemp(prefix="hicbench_e2e_")
             try:
                 with contextlib.redirect_stdout(io.StringIO()):

@@ -16,7 +16,7 @@ cd "$ROOT"
 OUT=gpurun_out
 mkdir -p $OUT
 FAST="--no-cpu-baseline --no-32k --no-64k --no-table --no-e2e"
-python3 bench.py > $OUT/${TAG}_bench16k_default.json
+python3 bench.py --full > $OUT/${TAG}_bench16k_default.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats -o run -- python3 bench.py $FAST > $OUT/${TAG}_stats.log 2>&1
 cp $(find $OUT/${TAG}_stats -name '*kernel_stats.csv' | head -1) $OUT/${TAG}_rocprofv3_kernel_stats_bench16k.csv
 for N in 16000 32000; do

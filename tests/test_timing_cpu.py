@@ -133,3 +133,63 @@ def test_few_launch_set_of_mode_2_is_what_the_header_says():
     comment = header[header.index("hicmi_timing_enable: 0 = off"):header.index("int hicmi_timing_reset")]
     for nm in few[:-1]:
         assert nm in comment, nm
+
+
+# ------------------------------------------------------------------------------ a plain benchmark run and --full
+ALL_LEGS = {"table", "32k", "64k", "cpu_baseline", "e2e"}
+
+
+@pytest.fixture(scope="module")
+def bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("hicmi_bench_module", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)                        # stdlib imports only: torch and the library are loaded in main()
+    return mod
+
+
+def _legs(bench, argv, world=1):
+    legs = bench.extra_legs(bench.arg_parser().parse_args(argv), world)
+    assert set(legs) == ALL_LEGS
+    return {k for k, on in legs.items() if on}
+
+
+@pytest.mark.parametrize("argv", [[], ["--gpus", "1", "--steps", "3", "--warmup", "1"], ["--dump-outputs", "somewhere"],
+                                  ["--part1-only"], ["--bins", "32000"], ["--kernel-times", "all"]])
+def test_a_plain_bench_run_makes_no_measurement_of_its_own(bench, argv):
+    """Without --full nothing beside the warm-up and the timed steps runs, whatever else is asked for."""
+    assert _legs(bench, argv) == set()
+    assert _legs(bench, argv, world=4) == set()
+
+
+def test_full_bench_run_makes_what_a_default_run_made(bench):
+    """--full: every measurement; a --no-* option leaves its own out (and --no-cpu-baseline the CLI runs with it, as
+    before); a map size is not measured twice; Part 2's sizes are not run beside --part1-only; one process only."""
+    assert _legs(bench, ["--full"]) == ALL_LEGS
+    assert _legs(bench, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"]) == ALL_LEGS
+    assert _legs(bench, ["--full", "--no-table"]) == ALL_LEGS - {"table"}
+    assert _legs(bench, ["--full", "--no-32k"]) == ALL_LEGS - {"32k"}
+    assert _legs(bench, ["--full", "--no-64k"]) == ALL_LEGS - {"64k"}
+    assert _legs(bench, ["--full", "--no-e2e"]) == ALL_LEGS - {"e2e"}
+    assert _legs(bench, ["--full", "--no-cpu-baseline"]) == ALL_LEGS - {"cpu_baseline", "e2e"}
+    assert _legs(bench, ["--full", "--bins", "32000"]) == ALL_LEGS - {"32k"}
+    assert _legs(bench, ["--full", "--bins", "64000"]) == ALL_LEGS - {"64k"}
+    assert _legs(bench, ["--full", "--part1-only"]) == ALL_LEGS - {"32k", "64k"}
+    assert _legs(bench, ["--full"], world=2) == set()
+    assert _legs(bench, ["--full", "--no-cpu-baseline", "--no-32k", "--no-64k", "--no-e2e", "--no-table"]) == set()
+
+
+def test_every_extra_measurement_of_bench_is_behind_its_leg():
+    """main() starts each of them in one place, directly under the test of its leg."""
+    src = _read("bench.py")
+    main = src[src.index("def main():"):]
+    for leg, call in (("table", "timed_run(job, 1, 0, 1,"), ("32k", "side_job(32000,"), ("64k", "side_job(64000,"),
+                      ("cpu_baseline", "cpu_baseline(args.cpu_sample_bins,"), ("e2e", "e2e_cli(2000,"),
+                      ("e2e", "e2e_cli_cached(16000,")):
+        assert main.count(call) == 1, call
+        guard = main.rindex("if legs[", 0, main.index(call))
+        assert main[guard:].startswith('if legs["%s"]:' % leg), call
+        between = main[guard:main.index(call)]
+        assert "\n    if " not in between and "\nif " not in between, call      # no other top-level branch in between
+    # timed_run: the headline's, the table's, side_job's own; side_job: its definition and the two sizes
+    assert main.count("timed_run(") == 3 and main.count("side_job(") == 3
